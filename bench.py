@@ -1,15 +1,22 @@
 #!/usr/bin/env python3
 """bench.py -- FECFRAMEs/s of the DVB-S2 FEC decode hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: launched by torch.distributed.run, one rank per GPU; frames shard across ranks with no
    data-path collective -- "scaling": "weak", 4096 frames per GPU per step.)
 
 A step = one pass of the hot path over one batch of synthetic frames already resident in HBM. The headline `value`
 is BASELINE config 2: QPSK 1/2 normal FECFRAMEs (DVB_S2_TABLE_B4, N=64800), LDPC capped at 50 iterations, batch 4096 per
 GPU, reference batch grouping G=32, never-converging int8 LLRs clamp(round(N(0, 8^2))) so that exactly 50 updates run for
-every frame (SURVEY 8(d) primary input). The same invocation also measures the other BASELINE configs and reports them
-under "configs" (each with its own parity gate, timing and roofline object):
+every frame (SURVEY 8(d) primary input).
+
+A plain run does only what the headline needs: set-up, W warm-up steps, exactly K timed steps, the outputs of the last
+step written by --dump-outputs DIR (dump_outputs), and ONE JSON line with `value`, `ms_per_step` and the roofline of the
+timed steps' own HIP events. No parity gate runs in a plain run: the dumped outputs are compared between builds instead,
+and the test suite checks the same decode bit for bit.
+
+--full adds everything else, each part with its own runs: the headline's parity gate, `shader_clock`, `device_copy`, the
+other BASELINE configs under "configs" (each with its own parity gate, timing and roofline object):
   config3  8PSK 3/4 normal: soft demapper + LDPC (S2_TABLE_B7) + BCH(48600,48408,12), 4096 frames, noise-only symbols
   config4  QPSK 1/4 short (S2_TABLE_C1), 25 iterations, 16384 frames
   config5  9/10 normal from LLRs: LDPC (S2_TABLE_B11) + BCH(58320,58192,8), 4096 frames per GPU (32768 over 8 GPUs)
@@ -26,8 +33,9 @@ the roofline on the updates actually executed, the rate against the never-conver
 plus `device_copy` (measured device-to-device copy bandwidth beside the 8 TB/s nominal peak), `host_link` (plain hipMemcpyAsync rates of
 the box's host link: what the host entry could at most be fed with) and `roofline.mapping_ceiling` (the same kernel build on B4's
 hazard-free degree-7 sibling S2X_TABLE_B3, per edge update, projected onto B4: what this mapping does when nothing orders the rows).
-At N > 1 every rank additionally runs `config2_host` at the same time (per-rank and summed rates): the host feed of the sharded job.
-Every parity gate compares the WHOLE batch with the genuine reference run on all host cores (--gate first: first group only).
+At N > 1 every rank additionally runs `config5` and `config2_host` at the same time (per-rank and summed rates): the host feed of the sharded job.
+Every parity gate compares the WHOLE batch with the genuine reference run on all host cores (--gate first: first group only),
+and `cpu_baseline` times the genuine reference on the host cores.
 config 1 (one frame through a CPU path) has no counterpart in the bench: the library has no CPU path by design; its
 workload runs on the HIP path in tests/test_ldpc_gpu.py::test_baseline_config1_one_frame_replicated.
 Prints ONE JSON line (rank 0).
@@ -287,6 +295,26 @@ roofline.clock_ghz = None  # shader clock under VALU load measured in this run (
 def noise_llr(torch, nf, N, dev, seed):
     g = torch.Generator(device=dev); g.manual_seed(seed)
     return torch.clamp(torch.round(torch.randn((nf, N), generator=g, device=dev) * 8.0), -128, 127).to(torch.int8)
+
+
+DUMP_LIMIT = 64_000_000  # bytes of all arrays that --dump-outputs writes together
+
+
+def dump_outputs(np, dirname, bits, ret, seed=2024):
+    """--dump-outputs: what the headline step hands its caller, from the last timed step, as float32 .npy files in `dirname`:
+      bits.npy    packed message bytes (OM_MESSAGE, MSB first), one row per frame: the whole batch, or a fixed seeded sample of
+                  its frames when the whole batch would not fit DUMP_LIMIT
+      frames.npy  the frame index of every row of bits.npy (float64)
+      ret.npy     the per-group return values (updates left, -1 = not converged), every group
+    The inputs are seeded, so the same arguments give the same files on every run and every correct build."""
+    os.makedirs(dirname, exist_ok=True)
+    ret_f = np.ascontiguousarray(ret, dtype=np.float32)
+    nf, nb = bits.shape
+    rows = max(0, (DUMP_LIMIT - ret_f.nbytes - 3 * 1024) // (nb * 4 + 8))  # 1 KiB per .npy header
+    idx = np.arange(nf) if nf <= rows else np.sort(np.random.default_rng(seed).choice(nf, rows, replace=False))
+    np.save(os.path.join(dirname, "bits.npy"), bits[idx].astype(np.float32))
+    np.save(os.path.join(dirname, "frames.npy"), idx.astype(np.float64))
+    np.save(os.path.join(dirname, "ret.npy"), ret_f)
 
 
 def ldpc_gate(T, np, torch, dec, table, llr, G, trials, stream, full=True):
@@ -629,13 +657,22 @@ def main():
     ap.add_argument("--trials", type=int, default=50)
     ap.add_argument("--group", type=int, default=32)
     ap.add_argument("--input", choices=["noise", "awgn"], default="noise")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="headline only (profiling runs)")
-    ap.add_argument("--only", default="", help="comma list of extra configs to run (default: all at N=1, config5 at N>1)")
-    ap.add_argument("--gate", choices=["full", "first", "none"], default="full",
-                    help="parity gates: whole batch vs the genuine reference on all host cores / first group / none (profiling passes)")
-    ap.add_argument("--esn0", type=float, default=2.0, help="Es/N0 in dB of the operating-point run (config2_awgn)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/*.npy (float32 / float64, at most 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the parity gates, the other configs, the secondaries, device copy / shader clock / host link and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) without the CPU baseline")
+    ap.add_argument("--no-configs", action="store_true", help="(--full) headline only (profiling runs)")
+    ap.add_argument("--only", default="", help="(--full) comma list of extra configs to run (default: all at N=1, config5 at N>1)")
+    ap.add_argument("--gate", choices=["full", "first", "none"], default=None,
+                    help="(--full) parity gates: whole batch vs the genuine reference on all host cores / first group / none (profiling passes)")
+    ap.add_argument("--esn0", type=float, default=2.0, help="Es/N0 in dB of the operating-point input (--input awgn, config2_awgn)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full and (args.only or args.gate):
+        ap.error("--only and --gate select parts of a --full run")
+    args.gate = args.gate or ("full" if args.full else "none")
 
     import numpy as np
     import torch
@@ -651,8 +688,10 @@ def main():
     dev = torch.device("cuda", local)
     if capi.lib.dvbs2_device_count() < 1:
         raise RuntimeError("no HIP device: the hot path has no CPU fallback")
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import fec_testlib as T  # the CPU checkers: parity gates and the cpu_baseline leg only
+    T = None
+    if args.full or args.input == "awgn":
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import fec_testlib as T  # the CPU checkers: parity gates, the cpu_baseline leg and the encoder of the AWGN inputs only
     stream = torch.cuda.current_stream().cuda_stream
     G = args.group
 
@@ -700,24 +739,30 @@ def main():
         sy = txd + float(np.sqrt(n0v_ / 2.0)) * torch.randn(txd.shape, generator=g, device=dev)
         return sy, n0v_, msg0_
 
-    trace("device_copy")
-    device_copy = device_copy_bandwidth(torch, dev)  # first: the limiter objects compare the fabric-side rate with it
-    roofline.copy_gbs = device_copy["read_plus_write_gbs"]
-    shader_clock = None
-    try:
-        import ctypes as C
-        ghz, pms = C.c_double(), C.c_double()
-        capi.check(capi.lib.dvbs2_measure_shader_clock(local, C.byref(ghz), C.byref(pms)))
-        shader_clock = {"ghz": ghz.value, "probe_kernel_ms": pms.value,
-                        "what": "s_memtime delta / s_memrealtime delta (100 MHz) of a ~1 ms kernel that keeps every SIMD issuing VALU adds"}
-        roofline.clock_ghz = ghz.value
-    except Exception as e:  # (diagnostic only)
-        shader_clock = {"error": str(e)}
+    device_copy = shader_clock = None
+    if args.full:
+        # (a plain run leaves both out: its limiter falls back to the nominal peak and clock, and says so)
+        trace("device_copy")
+        device_copy = device_copy_bandwidth(torch, dev)  # first: the limiter objects compare the fabric-side rate with it
+        roofline.copy_gbs = device_copy["read_plus_write_gbs"]
+        try:
+            import ctypes as C
+            ghz, pms = C.c_double(), C.c_double()
+            capi.check(capi.lib.dvbs2_measure_shader_clock(local, C.byref(ghz), C.byref(pms)))
+            shader_clock = {"ghz": ghz.value, "probe_kernel_ms": pms.value,
+                            "what": "s_memtime delta / s_memrealtime delta (100 MHz) of a ~1 ms kernel that keeps every SIMD issuing VALU adds"}
+            roofline.clock_ghz = ghz.value
+        except Exception as e:  # (diagnostic only)
+            shader_clock = {"error": str(e)}
     trace("headline input + gate")
     llr = noise_llr(torch, nf, N, dev, 12345 + rank) if args.input == "noise" else awgn_llr(4242 + rank)
     d_bits = torch.empty((nf, out_bytes), dtype=torch.uint8, device=dev)
     d_ret = torch.empty((nf + G - 1) // G, dtype=torch.int32, device=dev)
-    parity = ldpc_gate(T, np, torch, dec, table, llr, G, args.trials, stream, gate_full)[0] if rank == 0 and gate_on else "skipped"
+    parity = "skipped"
+    if not args.full:
+        parity = "not checked in a plain run (--full gates it; compare --dump-outputs between builds)"
+    elif rank == 0 and gate_on:
+        parity = ldpc_gate(T, np, torch, dec, table, llr, G, args.trials, stream, gate_full)[0]
 
     def step():
         dec.work_device(llr.data_ptr(), nf, d_bits.data_ptr(), 0, d_ret.data_ptr(), stream)
@@ -728,6 +773,8 @@ def main():
     dec.profile(True)  # HIP events around the dominant kernel, on its launch stream
     dt = timed(step, args.steps, 0, shard, dev)
     own_s = timed.own_s
+    if args.dump_outputs and rank == 0:
+        dump_outputs(np, args.dump_outputs, d_bits.cpu().numpy(), d_ret.cpu().numpy())
     iters_mean = float(torch.where(d_ret < 0, torch.full_like(d_ret, args.trials), args.trials - d_ret).float().mean().item())
     b_alg = ldpc_bytes(N, out_bytes, info["links_total"], iters_mean)
     rl = roofline(dec, b_alg, nf, None, "config2" if args.input == "noise" else None, args.trials, info["links_total"])
@@ -752,7 +799,8 @@ def main():
                            "spread": (max(per_rank) - min(per_rank)) / max(per_rank),
                            "note": "each rank's own clock over the same K steps (common start after the barrier, its own last "
                                    "completion); `value` uses the slowest rank's time"}
-    out["shader_clock"] = shader_clock
+    if args.full:
+        out["shader_clock"] = shader_clock
     out["fallback_rounds"] = dec.fallback_rounds  # host-driven rounds of the group stop (zero in normal operation)
     dec.close()
     del llr, d_bits
@@ -807,7 +855,7 @@ def main():
                          "step_bytes_per_frame": b_step, "step_frac_of_hbm_peak": b_step * val / world / 1e9 / HBM_PEAK_GBS}
         ch.close()
 
-    if not args.no_configs:
+    if args.full and not args.no_configs:
         if "config3" in want:
             trace("config3")
             fi = get_fec_info(capi.STANDARD_DVBS2, capi.FECFRAME_NORMAL, "C3_4")
@@ -851,7 +899,7 @@ def main():
         out["configs"] = configs
 
     # ---------------------------------------------------------------- SURVEY 8(d) secondaries of config 2 (one GPU)
-    if world == 1 and not args.no_configs and args.input == "noise":
+    if world == 1 and args.full and not args.no_configs and args.input == "noise":
         extras = [c for c in args.only.split(",") if c] or ["config2_awgn", "config3_awgn", "config4_awgn", "config2_host", "config3_host", "demap",
                                                             "device_copy", "host_link", "mapping_ceiling"]
         if "host_link" in extras or "config3_host" in extras:
@@ -1058,7 +1106,7 @@ def main():
                         "what is left between `value` and it are B4's 8 hazard layers (ordered lane chains, DESIGN.md 3-4)"}
         out["configs"] = configs
 
-    if world > 1 and not args.no_configs and args.input == "noise":
+    if world > 1 and args.full and not args.no_configs and args.input == "noise":
         # the expected limiter of the sharded job is host feeding, not the GPUs. Every rank runs the host-buffer entry
         # (H2D + decode + D2H per call, call site lib/ldpc_decoder_bb_impl.cc:406-449) at the same time; per-rank and summed rates
         # beside the resident `value`.
@@ -1077,7 +1125,7 @@ def main():
             "unit": "frames/s", "value": feed["pageable"]["sum_frames_per_s"], "ranks": feed, "fallback_rounds": sum(fbs)}
 
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(table, N, args.trials)
         print(json.dumps(out))
     shard.finalize()

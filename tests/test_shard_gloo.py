@@ -105,7 +105,7 @@ def test_bench_n2_branch_runs_on_one_gpu():
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     env = dict(os.environ, DVBS2_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--gate", "first",
+           "--master-port", str(port), os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--gate", "first",
            "--frames", "1024"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert p.returncode == 0, p.stderr[-3000:]

@@ -2,7 +2,7 @@
 """tools/gen_traffic.py <summary.txt of tools/profile_round.sh> -> profiles/traffic.json
 
 HBM bytes per launch of every BASELINE configuration's dominant kernel from the rocprofv3 PMC passes of ONE bench.py run
-(`python bench.py --steps 3 --warmup 1 --no-cpu-baseline --gate none --only config3,config4,config5,config5_s2x`; FETCH_SIZE and
+(`python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --gate none --only config3,config4,config5,config5_s2x`; FETCH_SIZE and
 WRITE_SIZE in separate passes). Per kernel the counters are sums over all its dispatches in the run, every one a whole batch
 (warm-up + timed steps, no parity-gate launches); divided by the pass's own dispatch count = one launch of the configuration's batch. The file records the digest of
 gr-dvbs2rx_amd/csrc it was profiled at (bench.csrc_sha256); bench.py reports `traffic` only for exactly that tree. Units KiB; FETCH_SIZE doubled (MI355X_MICROARCH.md: gfx950 tallies 128-byte read requests at

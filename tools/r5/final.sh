@@ -5,7 +5,7 @@ timeout 900 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; echo "
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -1 $O/smoke.log
 FUZZ_S=${FUZZ_S:-200} bash tools/r5/fuzz.sh ${TAG}full
 bash tools/profile_round.sh $TAG > /dev/null 2>&1
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "bench rc $?"
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "bench rc $?"
 python - "$O" <<'PY'
 import json, sys
 d=json.loads([l for l in open(sys.argv[1]+'/bench.json') if l.startswith('{')][-1])

@@ -3,7 +3,7 @@
 O=gpurun_out/r6r; mkdir -p $O
 timeout 900 python -m pytest tests/test_ldpc_gpu.py tests/test_shard_gloo.py tests/test_host_blocks.py -q -m gpu -k "host or page_locked or bench_n2 or rccl or copy" > $O/pytest.log 2>&1; echo "pytest rc $?"; tail -3 $O/pytest.log
 for i in 1 2 3; do
-  BENCH_TRACE=1 timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench$i.json 2> $O/bench$i.err; echo "bench $i rc $?"; grep -c "bench\]" $O/bench$i.err; grep -i "fault\|error" $O/bench$i.err | head -3
+  BENCH_TRACE=1 timeout 1200 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench$i.json 2> $O/bench$i.err; echo "bench $i rc $?"; grep -c "bench\]" $O/bench$i.err; grep -i "fault\|error" $O/bench$i.err | head -3
 done
 python - "$O" <<'PY'
 import json, sys

@@ -11,7 +11,7 @@ for a in "S2_TABLE_B4 2.0 50 4096" "S2_TABLE_C1 0.5 25 16384"; do set -- $a
   done
 done > $O/awgn.txt 2>&1; cat $O/awgn.txt
 timeout 600 python -m pytest tests/test_shard_gloo.py tests/test_bch_demap_gpu.py -x -q -m gpu -k "rccl or chain_host" > $O/pytest2.log 2>&1; echo "pytest2 rc $?"; tail -2 $O/pytest2.log
-timeout 900 python bench.py --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline --gate none --only config3_host > $O/bench_host.json 2> $O/bench_host.err
+timeout 900 python bench.py --full --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline --gate none --only config3_host > $O/bench_host.json 2> $O/bench_host.err
 python - "$O" <<'PY'
 import json, sys
 d=json.loads([l for l in open(sys.argv[1]+'/bench_host.json') if l.startswith('{')][-1])
