@@ -264,7 +264,9 @@ class Demapper:
             pass
 
     def work(self, syms, n0):
-        """syms: (n_frames, n_syms) complex64; n0: scalar or (n_frames,) float32 -> (n_frames, n_llr) int8."""
+        """syms: (n_frames, n_syms) complex (converted to complex64); n0: scalar or (n_frames,) float32 -> (n_frames, n_llr) int8."""
+        if np.asarray(syms).dtype.kind != "c":
+            raise TypeError(f"symbols must be complex, not {np.asarray(syms).dtype}")
         syms = np.ascontiguousarray(syms, dtype=np.complex64)
         nf = syms.shape[0]
         assert syms.shape == (nf, self.n_syms)
@@ -425,9 +427,18 @@ class FecChain:
 
     def work(self, syms, n0, want_ret=True):
         """HOST buffers (dvbs2_chain_decode): syms complex64 [n_frames, n_syms] (or float32 [n_frames, 2 n_syms]), n0 scalar or
-        one float per frame. Returns (msg uint8 [n_frames, msg_bytes], ldpc_ret int32 per group, bch_corr int32 per frame)."""
-        syms = np.ascontiguousarray(syms)
+        one float per frame. Returns (msg uint8 [n_frames, msg_bytes], ldpc_ret int32 per group, bch_corr int32 per frame).
+        Other complex / float widths are converted (the C entry reads float32 pairs); any other dtype is refused."""
+        syms = np.asarray(syms)
+        if syms.dtype.kind == "c":
+            syms = np.ascontiguousarray(syms, np.complex64)
+        elif syms.dtype.kind == "f":
+            syms = np.ascontiguousarray(syms, np.float32)
+        else:
+            raise TypeError(f"symbols must be complex or float, not {syms.dtype}")
         n_frames = syms.shape[0]
+        if syms.size * syms.itemsize != n_frames * self.n_syms * 8:
+            raise ValueError(f"symbols: expected {n_frames} frames of {self.n_syms} complex values, got shape {syms.shape}")
         n0 = np.ascontiguousarray(np.atleast_1d(np.asarray(n0, np.float32)))
         msg = np.empty((n_frames, self.msg_bytes), np.uint8)
         ret = np.empty(((n_frames + self.group_size - 1) // self.group_size,), np.int32)

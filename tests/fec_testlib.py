@@ -230,6 +230,23 @@ def pack_bits(llr, nbits):
     return out
 
 
+# ------------------------------------------------------------------ kernel builds
+VARIANTS = {  # every build of the sweep kernel gives the same bits (environment overrides of the per-table policy)
+    "policy": {},
+    "pr-byte-records": {"DVBS2_PR_W1": "0"},                                                       # parity in records with two-dword records also for degree <= 4
+    "pr-plain": {"DVBS2_PR_V2": "0"},                                                             # the two-dword-record kernel with its plain nodes everywhere
+    "pr-packed": {"DVBS2_PR": "1", "DVBS2_PR_W1": "0", "DVBS2_PR_V2": "1"},                          # parity in records on every eligible table (normal frames too), packed nodes in the regular middle layers
+    "classic": {"DVBS2_PR": "0", "DVBS2_DENSE": "0"},                                              # no parity-in-records / dense build
+    "plain": {"DVBS2_PR": "0", "DVBS2_DENSE": "0", "DVBS2_HZ2": "0", "DVBS2_V2": "0", "DVBS2_SOLO": "0"},          # byte messages, scalar nodes, pair workgroups
+    "packed-pair": {"DVBS2_PR": "0", "DVBS2_DENSE": "0", "DVBS2_HZ2": "0", "DVBS2_V2": "1", "DVBS2_SOLO": "0"},    # packed nodes, six-bit messages, pair workgroups
+    "plain-solo": {"DVBS2_PR": "0", "DVBS2_DENSE": "0", "DVBS2_HZ2": "0", "DVBS2_V2": "0", "DVBS2_SOLO": "1"},     # scalar nodes, one frame per workgroup
+    "packed-solo": {"DVBS2_PR": "0", "DVBS2_DENSE": "0", "DVBS2_HZ2": "0", "DVBS2_V2": "1", "DVBS2_SOLO": "1"},
+    "packed-pair-plain-hazard": {"DVBS2_PR": "0", "DVBS2_DENSE": "0", "DVBS2_HZ2": "0", "DVBS2_V2": "1", "DVBS2_SOLO": "0", "DVBS2_V2P": "0"},  # hazard layers through the plain node (what a wave whose record does not fit the packed format runs)
+    "heavy-hazard": {"DVBS2_PR": "0", "DVBS2_DENSE": "0", "DVBS2_HZ2": "1"},                       # twelve ordered entries, two-level walk (degree classes >= 12)
+    "soft-barrier": {"DVBS2_PR": "0", "DVBS2_DENSE": "0", "DVBS2_HZ2": "0", "DVBS2_V2": "1", "DVBS2_SOLO": "0", "DVBS2_SOFT_BARRIER": "1"},  # per-frame software barriers
+}
+
+
 # ------------------------------------------------------------------ input generators
 def llr_noise(n_frames, N, seed, sigma=8.0):
     """Never-converging input of SURVEY 8(d): i.i.d. clamp(round(N(0, sigma^2)))."""
@@ -402,6 +419,228 @@ def map_8psk(bits3):
     b = 1 - 2 * bits3.astype(np.int32)  # bit 0 -> +1, bit 1 -> -1 (positive LLR = bit 0)
     idx = (((b[..., 0] + 1) << 1) ^ 0x4) | ((b[..., 1] + 1) ^ 0x2) | (((b[..., 2] + 1) >> 1) ^ 0x1)
     return M8PSK[idx]
+
+
+# ------------------------------------------------------------------ demapper: float64 reference of the formulas
+# The restatement above (oracle/demap_oracle.c) and the kernels (demap_math.hpp) evaluate the reference's formulas in float32.
+# What follows evaluates the same formulas in float64 -- the mathematics, not a second float32 restatement -- plus a float32
+# emulation in numpy (IEEE single operations, no FMA, the operation order of demap_math.hpp) used to construct exact ties.
+U32 = 2.0 ** -24  # unit roundoff of float32 (round to nearest)
+RS2_F32 = float(np.float32(0.70710678118654752440))  # the reference points are float constants (lib/psk.hh, lib/qpsk.h)
+COS_PI_8, SIN_PI_8 = np.cos(np.pi / 8), np.sin(np.pi / 8)
+SNR_FLOOR = float(np.float32(1e-12))  # noise power floor, lib/qpsk.h:61-62, lib/xfecframe_demapper_cb_impl.cc:141-143
+
+# 8PSK column order by RATE NAME (reference lib/xfecframe_demapper_cb_impl.cc:50-69): 0 = "012", 1 = "210", 2 = "102"
+COLUMN_ORDER_210 = ("C3_5",)
+COLUMN_ORDER_102 = ("C25_36", "C13_18", "C7_15", "C8_15", "C26_45")
+
+
+def column_order(rate_name):
+    return 1 if rate_name in COLUMN_ORDER_210 else 2 if rate_name in COLUMN_ORDER_102 else 0
+
+
+def column_bases(rows, order):
+    """(ra0, ra1, ra2): where bits b0, b1, b2 of symbol s land in the de-interleaved frame (ra_k + s)."""
+    return {0: (0, rows, 2 * rows), 1: (2 * rows, rows, 0), 2: (rows, 0, 2 * rows)}[order]
+
+
+def _n0_f64(n0, nf):
+    # N0 is a float in the block (d_N0); the formulas see that float value
+    return np.broadcast_to(np.asarray(n0, np.float32), (nf,)).astype(np.float64)[:, None]
+
+
+def _rotate_f64(syms):
+    re, im = syms.real.astype(np.float64), syms.imag.astype(np.float64)
+    return re * COS_PI_8 + im * SIN_PI_8, -re * SIN_PI_8 + im * COS_PI_8  # x * exp(-j pi/8)
+
+
+def demap_f64(syms, n0, constellation, order=0):
+    """UNQUANTISED LLRs in float64, (n_frames, n_llr), in the block's output order. constellation: 4 (QPSK) or 8 (8PSK).
+    QPSK  x * 2 sqrt(2) / N0 on re, im of each symbol (reference lib/qpsk.h:208-214).
+    8PSK  c = x exp(-j pi/8); b1 = Re c * D, b2 = Im c * D, b0 = (|Re c| - |Im c|) / sqrt(2) * D, D = 2 sin(pi/8) * 4 / N0
+          (lib/psk.hh:113-150, precision 4 / N0 at lib/xfecframe_demapper_cb_impl.cc:148); bit k of symbol s at ra_k + s
+          (:50-69, 162-176)."""
+    syms = np.asarray(syms, np.complex64)
+    nf, ns = syms.shape
+    n0 = _n0_f64(n0, nf)
+    if constellation == 4:
+        out = np.empty((nf, 2 * ns))
+        S = 2.0 * np.sqrt(2.0) / n0
+        out[:, 0::2], out[:, 1::2] = syms.real * S, syms.imag * S
+        return out
+    D = 2.0 * SIN_PI_8 * 4.0 / n0
+    cr, ci = _rotate_f64(syms)
+    ra = column_bases(ns, order)
+    out = np.empty((nf, 3 * ns))
+    for a, v in zip(ra, ((np.abs(cr) - np.abs(ci)) / np.sqrt(2.0) * D, cr * D, ci * D)):
+        out[:, a:a + ns] = v
+    return out
+
+
+def quantise_f64(v):
+    """clamp(rint(v), -128, 127) with ties to even (rintf / nearbyintf / VOLK's convert)."""
+    return np.clip(np.rint(v), -128, 127).astype(np.int8)
+
+
+def near_tie_mask(syms, n0, constellation, order=0):
+    """Positions where a float32 evaluation of the formulas may quantise differently from quantise_f64(demap_f64(...)).
+
+    The bound is on the INPUT magnitudes A = |re| + |im| of the symbol (u = 2^-24): 8PSK cancels in re rr - im ri and in
+    |cr| - |ci|, so an error relative to the output is not a bound.
+      QPSK  scalar = fl(2 sqrt(2) / N0) = S (1 + d1); v = fl(x scalar): |v - x S| <= (2u + u^2) |x| S.      k = 3
+      8PSK  rr, ri are float roundings of cos, sin (u each); the two products (u each) and the sum / difference (u):
+            |cr32 - cr| <= 3.01 u A, same for ci. dp = fl(fl(2 sin_pi_8) fl(4 / N0)) = D (1 + e), |e| <= 3.01 u.
+            b1, b2 = fl(c dp):               <= 3.01 u A D + 4.01 u |c| D                      <= 7.02 u A D
+            w = fl(|cr32| - |ci32|):         |w - (|cr| - |ci|)| <= 6.02 u A + u A            =  7.02 u A
+            z = fl(fl(1/sqrt 2) w):          <= (7.02 + 2.01) u A / sqrt 2                    <= 6.39 u A
+            b0 = fl(z dp):                   <= 6.39 u A D + 4.01 u (A / sqrt 2) D            <= 9.23 u A D    k = 10
+    plus an absolute term for products that land in the subnormal range (each rounds by <= 2^-150, scaled by D).
+    Quantisation is clamp(rint(v)): it is discontinuous only at the half-integers -127.5 .. 126.5 (at -128.5 and 127.5 rint and
+    clamp agree); the mask takes every half-integer from -128.5 to 127.5, so it also covers the saturation points. Non-finite
+    values are exact (+-inf saturates either way) and never near."""
+    syms = np.asarray(syms, np.complex64)
+    nf, ns = syms.shape
+    v = demap_f64(syms, n0, constellation, order)
+    n0 = _n0_f64(n0, nf)
+    if constellation == 4:
+        S = 2.0 * np.sqrt(2.0) / n0
+        a = np.empty_like(v)
+        a[:, 0::2], a[:, 1::2] = np.abs(syms.real), np.abs(syms.imag)
+        margin = 3 * U32 * a * S + 2.0 ** -149
+    else:
+        D = 2.0 * SIN_PI_8 * 4.0 / n0
+        A = np.abs(syms.real).astype(np.float64) + np.abs(syms.imag)
+        m = 10 * U32 * A * D + 2.0 ** -147 * D + 2.0 ** -149
+        margin = np.concatenate([m, m, m], axis=1)  # the same bound in every column
+    with np.errstate(invalid="ignore"):
+        d = np.where(v < -128.5, -128.5 - v, np.where(v > 127.5, v - 127.5, np.abs(v - (np.floor(v) + 0.5))))
+        return np.isfinite(v) & (d <= margin)
+
+
+def check_demap_vs_f64(got, syms, n0, constellation, order=0, what=""):
+    """Every LLR outside near_tie_mask equals quantise_f64(demap_f64(...)); near-tie ones are within +-1. Returns the near-tie count."""
+    want = quantise_f64(demap_f64(syms, n0, constellation, order))
+    near = near_tie_mask(syms, n0, constellation, order)
+    diff = got.astype(np.int16) - want
+    far_bad = np.nonzero((diff != 0) & ~near)
+    assert far_bad[0].size == 0, f"{what}: {far_bad[0].size} LLRs differ away from a tie, first at {far_bad[0][0]}, {far_bad[1][0]}"
+    assert np.abs(diff[near]).max(initial=0) <= 1, what
+    return int(near.sum())
+
+def demap_f32_pre(syms, n0, constellation):
+    """The float32 values just before rint, emulated in numpy (IEEE single operations, no FMA, demap_math.hpp's order), for a
+    single N0. QPSK: (..., 2 n) interleaved; 8PSK: (b0, b1, b2) per symbol, natural order."""
+    syms = np.asarray(syms, np.complex64)
+    f = np.float32
+    n0 = f(n0)
+    re, im = syms.real.astype(f), syms.imag.astype(f)
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+        if constellation == 4:
+            S = f(2.0 * 1.41421356237309504880 / np.float64(n0))
+            out = np.empty(syms.shape[:-1] + (2 * syms.shape[-1],), f)
+            out[..., 0::2], out[..., 1::2] = re * S, im * S
+            return out
+        rr, ri = f(np.cos(-np.pi / 8)), f(np.sin(-np.pi / 8))
+        dp = f(f(2 * f(0.38268343236508977173)) * f(4.0 / np.float64(n0)))
+        cr = re * rr - im * ri
+        ci = re * ri + im * rr
+        return f(0.70710678118654752440) * (np.abs(cr) - np.abs(ci)) * dp, cr * dp, ci * dp
+
+
+def tie_symbols(n0, constellation, targets=None, reach=512):
+    """Symbols whose float32 product lands EXACTLY on a tie t = k + 0.5 (default: every k in -129 .. 127), for one N0.
+    QPSK: x on one axis. 8PSK: (x, 0) for b1 and, for positive b0, the b0 search; (0, x) for b2 and for negative b0 (b0 has
+    the sign of |cos| - |sin| there). Each candidate x is searched over +-reach float32 steps around t / gain.
+    Returns {t: complex64 symbol} for the ties found."""
+    f = np.float32
+    if targets is None:
+        targets = np.arange(-129, 128) + 0.5
+    n0 = f(n0)
+    D = float(f(f(2 * f(0.38268343236508977173)) * f(4.0 / np.float64(n0))))
+    S = float(f(2.0 * 1.41421356237309504880 / np.float64(n0)))
+    if constellation == 4:
+        combos = [(0, 1, S), (1, 1, S)]  # (axis, output index in the pair, gain)
+    else:
+        c, s = COS_PI_8, SIN_PI_8
+        combos = [(0, 1, c * D), (0, 0, (c - s) / np.sqrt(2) * D), (1, 2, c * D), (1, 0, (s - c) / np.sqrt(2) * D)]
+    steps = np.arange(-reach, reach + 1, dtype=np.int64)
+    found = {}
+    for t in targets:
+        for axis, which, gain in combos:
+            x0 = t / gain
+            if not np.isfinite(x0) or abs(x0) >= 3e38 or x0 == 0:
+                continue
+            mag = (np.abs(np.float32(x0)).view(np.int32).astype(np.int64) + steps)
+            mag = mag[(mag > 0) & (mag < 0x7f800000)].astype(np.int32).view(np.float32)
+            x = np.sign(x0).astype(np.float32) * mag
+            sy = (x + 0j).astype(np.complex64) if axis == 0 else (1j * x).astype(np.complex64)
+            pre = demap_f32_pre(sy, n0, constellation)
+            v = pre[1::2] if (constellation == 4 and axis == 1) else pre[0::2] if constellation == 4 else pre[which]
+            hit = np.nonzero(v == np.float32(t))[0]
+            if hit.size:
+                found[float(t)] = sy[hit[0]]
+                break
+    return found
+
+
+def edge_symbols(n0, constellation):
+    """Symbols at the quantiser's edges for one N0: every exact tie found, far beyond saturation, +-0 in every combination,
+    zero, the smallest subnormal, and (QPSK only: 8PSK turns inf into NaN through |cr| - |ci|) +-inf."""
+    ties = list(tie_symbols(n0, constellation).values())
+    big = [1e3, -1e3, 3e38, -3e38]
+    z = [complex(a, b) for a in (0.0, -0.0) for b in (0.0, -0.0)]
+    tiny = [complex(1e-45, -1e-45), complex(-1e-45, 1e-45)]
+    extra = [complex(b, 0) for b in big] + [complex(0, b) for b in big] + [complex(b, -b) for b in big[:2]] + z + tiny
+    if constellation == 4:
+        extra += [complex(np.inf, -np.inf), complex(-np.inf, np.inf), complex(np.inf, 0.0), complex(0.0, -np.inf)]
+    out = np.array(ties + extra, np.complex64)
+    # complex(a, b) drops the sign of a -0.0 real part in some paths: set the +-0 ones explicitly
+    k0 = len(ties) + 10
+    out.real[k0:k0 + 4] = np.array([0.0, 0.0, -0.0, -0.0], np.float32)
+    out.imag[k0:k0 + 4] = np.array([0.0, -0.0, 0.0, -0.0], np.float32)
+    return out
+
+
+def snr_f64(syms, constellation, ref_llr=None, order=0):
+    """Linear SNR per frame in float64: reference points by hard slice of the symbol (pre-decoder, lib/qpsk.h:171-181,
+    lib/xfecframe_demapper_cb_impl.cc:132-141) or re-mapped from the signs of ref_llr (post-decoder, :268-307, lib/qpsk.h:266-281;
+    LLR 0 counts as positive), then sum |s|^2 / sum |x - s|^2 with the noise floored at (float)1e-12. The points are the float
+    constants of the reference's tables (M8PSK, RS2_F32), exactly as the block holds them."""
+    syms = np.asarray(syms, np.complex64)
+    nf, ns = syms.shape
+    re, im = syms.real.astype(np.float64), syms.imag.astype(np.float64)
+    if constellation == 4:
+        if ref_llr is None:
+            pr, pi = re >= 0, im >= 0
+        else:
+            ref_llr = np.asarray(ref_llr)
+            pr, pi = ref_llr[:, 0::2] >= 0, ref_llr[:, 1::2] >= 0
+        sr, si = np.where(pr, RS2_F32, -RS2_F32), np.where(pi, RS2_F32, -RS2_F32)
+    else:
+        if ref_llr is None:
+            cr, ci = _rotate_f64(syms)
+            b0, b1, b2 = np.where(np.abs(cr) < np.abs(ci), -1, 1), np.where(cr < 0, -1, 1), np.where(ci < 0, -1, 1)
+        else:
+            ra = column_bases(ns, order)
+            b0, b1, b2 = (np.where(np.asarray(ref_llr)[:, a:a + ns] < 0, -1, 1) for a in ra)
+        idx = (((b0 + 1) << 1) ^ 0x4) | ((b1 + 1) ^ 0x2) | (((b2 + 1) >> 1) ^ 0x1)
+        pts = M8PSK.astype(np.complex128)[idx]
+        sr, si = pts.real, pts.imag
+    sp = (sr * sr + si * si).sum(axis=1)
+    npow = ((re - sr) ** 2 + (im - si) ** 2).sum(axis=1)
+    npow = np.where(npow > 0, npow, SNR_FLOOR)
+    return sp / npow
+
+
+def oracle_snr(syms, constellation, ref_llr=None, order=0):
+    """oracle_demap_snr / oracle_demap_snr_refined per frame (float32, sequential accumulation)."""
+    syms = np.ascontiguousarray(syms, np.complex64)
+    nf, ns = syms.shape
+    if ref_llr is None:
+        return np.array([oracle().oracle_demap_snr(ptr(syms[f]), ns, constellation) for f in range(nf)], np.float64)
+    ref_llr = np.ascontiguousarray(ref_llr, np.int8)
+    return np.array([oracle().oracle_demap_snr_refined(ptr(syms[f]), ptr(ref_llr[f]), ns, constellation, order) for f in range(nf)],
+                    np.float64)
 
 
 def oracle_bb_descramble(msg):

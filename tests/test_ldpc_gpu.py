@@ -10,6 +10,7 @@ import pytest
 
 import fec_testlib as T
 from dvbs2rx_amd import ldpc_table_names, LdpcDecoder, capi, get_fec_info
+from fec_testlib import VARIANTS
 
 pytestmark = pytest.mark.gpu
 
@@ -60,22 +61,6 @@ def test_near_threshold_groups(table, amp, sigma, G):
     llr, _ = T.llr_codeword_awgn(table, 64, 99, amp=amp, sigma=sigma)
     ret = compare(table, llr, G, 50)
     assert len(ret) == 64 // G
-
-
-VARIANTS = {  # every build of the sweep kernel gives the same bits (environment overrides of the per-table policy)
-    "policy": {},
-    "pr-byte-records": {"DVBS2_PR_W1": "0"},                                                       # parity in records with two-dword records also for degree <= 4
-    "pr-plain": {"DVBS2_PR_V2": "0"},                                                             # the two-dword-record kernel with its plain nodes everywhere
-    "pr-packed": {"DVBS2_PR": "1", "DVBS2_PR_W1": "0", "DVBS2_PR_V2": "1"},                          # parity in records on every eligible table (normal frames too), packed nodes in the regular middle layers
-    "classic": {"DVBS2_PR": "0", "DVBS2_DENSE": "0"},                                              # no parity-in-records / dense build
-    "plain": {"DVBS2_PR": "0", "DVBS2_DENSE": "0", "DVBS2_HZ2": "0", "DVBS2_V2": "0", "DVBS2_SOLO": "0"},          # byte messages, scalar nodes, pair workgroups
-    "packed-pair": {"DVBS2_PR": "0", "DVBS2_DENSE": "0", "DVBS2_HZ2": "0", "DVBS2_V2": "1", "DVBS2_SOLO": "0"},    # packed nodes, six-bit messages, pair workgroups
-    "plain-solo": {"DVBS2_PR": "0", "DVBS2_DENSE": "0", "DVBS2_HZ2": "0", "DVBS2_V2": "0", "DVBS2_SOLO": "1"},     # scalar nodes, one frame per workgroup
-    "packed-solo": {"DVBS2_PR": "0", "DVBS2_DENSE": "0", "DVBS2_HZ2": "0", "DVBS2_V2": "1", "DVBS2_SOLO": "1"},
-    "packed-pair-plain-hazard": {"DVBS2_PR": "0", "DVBS2_DENSE": "0", "DVBS2_HZ2": "0", "DVBS2_V2": "1", "DVBS2_SOLO": "0", "DVBS2_V2P": "0"},  # hazard layers through the plain node (what a wave whose record does not fit the packed format runs)
-    "heavy-hazard": {"DVBS2_PR": "0", "DVBS2_DENSE": "0", "DVBS2_HZ2": "1"},                       # twelve ordered entries, two-level walk (degree classes >= 12)
-    "soft-barrier": {"DVBS2_PR": "0", "DVBS2_DENSE": "0", "DVBS2_HZ2": "0", "DVBS2_V2": "1", "DVBS2_SOLO": "0", "DVBS2_SOFT_BARRIER": "1"},  # per-frame software barriers
-}
 
 
 @pytest.mark.parametrize("variant", list(VARIANTS))
