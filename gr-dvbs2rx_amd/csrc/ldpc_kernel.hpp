@@ -389,9 +389,12 @@ __device__ __forceinline__ int pm_min_clamped(int p) { return clamp_mag((int)((u
 //     add / subtract then IS the reference's int8 saturation (R1 sat8(L - m), R6 sat8(inp + out)), the message clamp (R7)
 //     is one packed max + min per pair, |inp| is packed max(d, 0 - d). A positive saturation leaves 0xff in the low
 //     byte of a half; nothing below lets it reach a result (see the notes at the uses).
-//   * MAGNITUDES are reduced in scalar form (v_min3 / v_med3 triples need fewer slots than a packed running pair), the
-//     selection "mag == min0 ? min1 : min0" is packed again: T - clamp(mag, B0, B1) with B0 = min0, B1 = B0 + (min1' -
-//     min0'), T = min1' + B0, where x' = max(x - 1, 0) (R2's offset and floor applied once per check, not per edge).
+//   * MAGNITUDES are reduced in packed form too (two_smallest_pk: a tree of sorted pairs per half position, one cross-half step
+//     with swapped operand halves), the selection "mag == min0 ? min1 : min0" is T - clamp(mag, B0, B1) = T - min(mag, B1)
+//     with B0 = min0, B1 = B0 + (min1' - min0'), T = min1' + B0, where x' = max(x - 1, 0) (R2's offset and floor applied once
+//     per check, not per edge), and the sign goes onto T and the clamped magnitude before the subtraction (pair_out).
+//     Census of the degree-7 node in the degree class 8 (tools/node_census.py): 108 -> 94 VALU instructions, 385 -> 345
+//     issue cycles per wave (notes/r07_packed_node.md).
 // Messages of such a layer are two's complement bytes (this layer's records are private to it: layer 0 and hazard
 // layers keep offset binary); logical entry e = 2 j + h of pair j lives in dword j / 2, byte (j & 1) + 2 h, so that both
 // pairs of a dword unpack with one instruction each. LLR bytes in LDS stay offset binary (shared with the other paths).
@@ -455,8 +458,78 @@ __device__ __forceinline__ void msg_pack16(const uint32_t* R /*clamped messages 
             nm[w] = (2 * w + 1 < NP) ? ((R[2 * w] >> 8) | R[2 * w + 1]) : (R[2 * w] >> 8);
     }
 }
+// msg_pack16 with the pad half of an odd degree still in R[NP - 1]. One-byte messages: one v_perm per word instead of shift + or,
+// and the pad byte is selected as zero instead of masked.
+template <bool P6, int NP, int NW, bool ODD>
+__device__ __forceinline__ void msg_pack16_hb(uint32_t* R, uint32_t* nm)
+{
+    if constexpr (P6) {
+        if (ODD) R[NP - 1] &= 0x0000ffffu;
+        msg_pack16<P6, NP, NW>(R, nm);
+    } else {
+#pragma unroll
+        for (int w = 0; w < (NP + 1) / 2; w++) {
+            const bool two = 2 * w + 1 < NP;                        // word w holds pairs 2w and 2w + 1
+            const bool pad_lo = ODD && !two, pad_hi = ODD && two && 2 * w + 1 == NP - 1;
+            const uint32_t sel = 0x01u | (two ? 0x05u : 0x0cu) << 8 | (pad_lo ? 0x0cu : 0x03u) << 16 | ((two && !pad_hi) ? 0x07u : 0x0cu) << 24;
+            nm[w] = __builtin_amdgcn_perm(two ? R[2 * w + 1] : 0u, R[2 * w], sel); // bytes 1, 3 of pair 2w -> 0, 2; of pair 2w + 1 -> 1, 3
+        }
+    }
+}
 // words of one check's message record that hold fields, and whether word k is a 16-bit access, for degree deg
 __host__ __device__ constexpr int p6_fields(int deg, int k) { return deg - 5 * k < 0 ? 0 : (deg - 5 * k > 5 ? 5 : deg - 5 * k); }
+
+// R3 on pairs: the two smallest of the 2 NP halves of a[] (all of them real: the caller lifts a pad above every magnitude). Per half
+// position a tree of sorted pairs (min / max of two registers, then merges of two sorted pairs in four instructions), then ONE
+// cross-half step with swapped operand halves (op_sel): m0 / m1 come out in BOTH halves. 3 NP - 4 + 4 packed instructions, against
+// DEG extractions + the v_min3 / v_med3 network of two_smallest on scalars.
+__device__ __forceinline__ v2s16 swap16(v2s16 x) { return __builtin_shufflevector(x, x, 1, 0); }
+template <int NP>
+__device__ __forceinline__ void two_smallest_pk(const v2s16* a, v2s16& m0, v2s16& m1)
+{
+    static_assert(NP >= 2, "two pairs at least");
+    constexpr int NS = (NP + 1) / 2;
+    v2s16 lo[NS], hi[NS]; // sorted pairs; a lone register has no second element (0x7fff: never below a magnitude)
+#pragma unroll
+    for (int k = 0; k < NS; k++) {
+        if (2 * k + 1 < NP) { lo[k] = __builtin_elementwise_min(a[2 * k], a[2 * k + 1]); hi[k] = __builtin_elementwise_max(a[2 * k], a[2 * k + 1]); }
+        else { lo[k] = a[2 * k]; hi[k] = (v2s16){ 0x7fff, 0x7fff }; }
+    }
+#pragma unroll
+    for (int w = 1; w < NS; w *= 2) {
+#pragma unroll
+        for (int k = 0; k + w < NS; k += 2 * w) {
+            const bool lone = (NP & 1) && k + w == NS - 1; // the lone register (never a receiver) has no second element: merge in three
+            const v2s16 l = __builtin_elementwise_min(lo[k], lo[k + w]), x = __builtin_elementwise_max(lo[k], lo[k + w]);
+            hi[k] = __builtin_elementwise_min(x, lone ? hi[k] : __builtin_elementwise_min(hi[k], hi[k + w]));
+            lo[k] = l;
+        }
+    }
+    const v2s16 s0 = swap16(lo[0]);
+    m0 = __builtin_elementwise_min(lo[0], s0);
+    m1 = __builtin_elementwise_min(__builtin_elementwise_max(lo[0], s0), __builtin_elementwise_min(hi[0], swap16(hi[0])));
+}
+
+// R5 - R7 of one pair (regular entries of the packed nodes). d: inp << 8, a: |inp| << 8 (>= B0 on every real half), B1p: B1 in both
+// halves, Tt: T in both halves ^ tm, tm: all ones when the check's sign product is negative. The sign of an output is S = sg ^ tm with
+// sg the sign mask of inp, and with S all ones or zero per half  (other ^ S) - S  ==  (T ^ S) - (c ^ S)  for other = T - c: the two
+// xors are one v_bitop3 each and the negation costs no packed instruction of its own. clamp(a, B0, B1) is min(a, B1): a >= min0 >= B0.
+// nl: the new LLR bytes of the pair in bits 0-7 and 16-23 (ds_write_b8 / ds_write_b8_d16_hi); R: the stored messages (R7) << 8.
+template <bool TC>
+__device__ __forceinline__ void pair_out(v2s16 d, v2s16 a, v2s16 B1p, uint32_t Tt, uint32_t tm, uint32_t& nl, uint32_t& R)
+{
+    const v2s16 c = __builtin_elementwise_min(a, B1p);
+    const uint32_t sg = as_u32(d >> (v2s16){ 15, 15 });
+    uint32_t cs; // c ^ sg ^ tm as ONE v_bitop3 (the compiler splits a visible xor chain into two xors and re-associates Tt's)
+    asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x96" : "=v"(cs) : "v"(as_u32(c)), "v"(sg), "v"(tm));
+    const v2s16 out = as_v2s(Tt ^ sg) - as_v2s(cs);
+    // R6: LLR = sat8(inp + out); the low byte of a half never reaches the byte that is stored. (The shift is opaque to the compiler:
+    // it folds a visible one into the >> 16 of the second byte and stores that with a plain ds_write_b8 behind a second shift.)
+    const uint32_t sum = as_u32(__builtin_elementwise_add_sat(d, out)) ^ kObPair<TC>;
+    asm("v_lshrrev_b32 %0, 8, %1" : "=v"(nl) : "v"(sum));
+    // R7
+    R = as_u32(__builtin_elementwise_min(__builtin_elementwise_max(out, (v2s16){ -32 * 256, -32 * 256 }), (v2s16){ 31 * 256, 31 * 256 }));
+}
 
 template <int DEG, int DMAX, bool P6, bool TC, class Prefetch>
 __device__ __forceinline__ void check_node_v2(const uint32_t* ent /*record words 4..: S0w[DMAX], then (mask lo, mask hi)[NFIX]*/,
@@ -498,38 +571,29 @@ __device__ __forceinline__ void check_node_v2(const uint32_t* ent /*record words
     // it cost 9 % on table B4 and a factor 4 on the degree-30 class through what it does to register allocation. The loads stay
     // at the top of the layer; notes/history.md 3.4.)
     (void)prefetch_next_record;
-    int mg[DEG];
-#pragma unroll
-    for (int k = 0; k < DEG; k++) mg[k] = (k & 1) ? (int)(as_u32(a[k >> 1]) >> 16) : (int)(as_u32(a[k >> 1]) & 0xffffu);
-    int n0, n1;
-    two_smallest<DEG>(mg, n0, n1);
-    // the low byte (0xff after a saturation) is dropped HERE, once per check: every selected magnitude below is B0/B1-clamped,
+    if (ODD) a[NP - 1] = as_v2s(as_u32(a[NP - 1]) | 0x7fff0000u); // the pad's magnitude: above every real one
+    v2s16 m0, m1;
+    two_smallest_pk<NP>(a, m0, m1);
+    // the low byte (0xff after a saturation) is dropped HERE, once per check: every selected magnitude below is B1-clamped,
     // so a 0x7fff among the inputs can only come out as the clean 0x7f00 level it stands for
-    n0 &= 0x7f00; n1 &= 0x7f00;
+    const int n0 = (int)(as_u32(m0) & 0x7f00u), n1 = (int)(as_u32(m1) & 0x7f00u);
     // R2: mag = max(|inp| - 1, 0), applied to the two minima (monotone); unsigned saturating subtract (full rate)
     const int n0m = (int)__builtin_elementwise_sub_sat((uint32_t)n0, 256u), n1m = (int)__builtin_elementwise_sub_sat((uint32_t)n1, 256u);
-    const int B0 = n0, B1 = n0 + n1m - n0m, T = n1m + n0;
-    const v2s16 B0p = { (short)B0, (short)B0 }, B1p = { (short)B1, (short)B1 }, Tp = { (short)T, (short)T };
+    const int B1 = n0 + n1m - n0m, T = n1m + n0;
     const uint32_t tm = (uint32_t)((int)(sx ^ (sx << 16)) >> 31); // all ones when the number of negative inputs is odd
+    const v2s16 B1p = { (short)B1, (short)B1 };
+    const uint32_t Tt = __builtin_amdgcn_perm((uint32_t)T, (uint32_t)T, 0x01000100u) ^ tm; // T in both halves (one v_perm; the compiler's own broadcast is a multiply)
     if constexpr (!KEEP_AD) { asm volatile("" ::: "memory"); addresses(); }
     uint32_t R[NP];
 #pragma unroll
     for (int j = 0; j < NP; j++) {
-        // R5: |out| = mag == min0 ? min1' : min0'  ==  T - clamp(|inp|, B0, B1); sign = total ^ own
-        const v2s16 c = __builtin_elementwise_min(__builtin_elementwise_max(a[j], B0p), B1p);
-        const v2s16 other = Tp - c;
-        const v2s16 sg = as_v2s(as_u32(d[j]) ^ tm) >> (v2s16){ 15, 15 };
-        const v2s16 out = as_v2s(as_u32(other) ^ as_u32(sg)) - sg;
-        // R6: LLR = sat8(inp + out); the low byte of a half never reaches the byte that is stored
-        const uint32_t nl = (as_u32(__builtin_elementwise_add_sat(d[j], out)) ^ kObPair<TC>) >> 8;
+        uint32_t nl;
+        pair_out<TC>(d[j], a[j], B1p, Tt, tm, nl, R[j]);
         lds_wr(ad[2 * j], (int)nl);
         if (!(ODD && j == NP - 1)) lds_wr_hi(ad[2 * j + 1], nl);
-        // R7
-        R[j] = as_u32(__builtin_elementwise_min(__builtin_elementwise_max(out, (v2s16){ -32 * 256, -32 * 256 }), (v2s16){ 31 * 256, 31 * 256 }));
     }
     __builtin_amdgcn_s_setprio(3);
-    if (ODD) R[NP - 1] &= 0x0000ffffu; // the pad's message stays zero
-    msg_pack16<P6, NP, DMAX / 4>(R, nm);
+    msg_pack16_hb<P6, NP, DMAX / 4, ODD>(R, nm);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
