@@ -11,6 +11,7 @@ namespace dvbs2 {
 // per-CU wave-pattern counters of the one-frame sweep kernels: one device array per device key (ldpc_hip.hip)
 int* cu_slot_table(int device_key, std::string* err);
 constexpr int kCuSlotWords = 16 * 8 * 2 * 16;
+enum class LdpcBuild : uint8_t; // the builds of the sweep kernel (ldpc_kernel.hpp)
 
 class LdpcDecoderHip {
 public:
@@ -84,16 +85,9 @@ private:
     uint32_t* d_wrecs_ = nullptr; // per-(layer, wave) sweep records of the classic kernel
     size_t lds_bytes_ = 0;
     std::string kname_;
-    bool v2_ = false;             // the build with the packed nodes (check_node_v2 / check_node_chain_v2)
-    bool chain_plain_ = false;    // plain sweep kernel with the packed register chain for single-pair hazard layers
-    bool soft_bar_ = false;       // per-frame software barriers (high-degree tables without hazard layers)
+    LdpcBuild build_{};           // the build of the sweep kernel this handle runs (decided in the constructor)
     int fallback_rounds_ = 0;
-    bool pr_w1_ = false;          // parity-in-records kernel with one-dword records (check degree <= 4)
-    bool pr_v2_ = false;          // parity-in-records kernel with packed nodes in the regular middle layers (two-dword records, per-wave sweep records)
-    bool hz2_ = false;            // the build with the heavy-hazard paths (ldpc_kernel.hpp, HZ2)
-    bool solo_ = false;           // one frame per workgroup, complementary wave roles per CU (ldpc_kernel.hpp)
     int* d_cu_slots_ = nullptr;   // per-CU pattern counters of the solo kernels
-    bool dense_ = false;          // 80-VGPR build of the classic kernel selected (two workgroups per CU)
     bool pr_ = false;             // parity-in-records kernel variant selected (ldpc_kernel_pr.hpp)
     unsigned long long* d_tdbg_ = nullptr; // DVBS2_TIMING=1: per-wave cycle-counter breakdown (diagnostics)
     uint8_t* d_state_ = nullptr;  // max_frames * N, internal layout, offset-binary LLRs

@@ -24,6 +24,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <optional>
 #include <vector>
 
 namespace dvbs2 {
@@ -106,34 +107,77 @@ int* cu_slot_table(int device_key, std::string* err)
     return slots;
 }
 
+namespace {
+// Environment overrides of the per-table choices below (the tests run every build on every table), read once per handle. Unset: the rule.
+struct LdpcOverrides {
+    std::optional<int> pr, pr_w1, pr_v2, dense, hz2, solo, soft_barrier, v2, v2p, group_sync, group_spin_max, resolve_rounds;
+    bool timing = false; // DVBS2_TIMING: the cycle-stamped build and its printouts (diagnostics)
+    LdpcOverrides()
+    {
+        auto get = [](const char* name) -> std::optional<int> { if (const char* e = getenv(name)) return atoi(e); return std::nullopt; };
+        pr = get("DVBS2_PR"); pr_w1 = get("DVBS2_PR_W1"); pr_v2 = get("DVBS2_PR_V2"); dense = get("DVBS2_DENSE"); hz2 = get("DVBS2_HZ2");
+        solo = get("DVBS2_SOLO"); soft_barrier = get("DVBS2_SOFT_BARRIER"); v2 = get("DVBS2_V2"); v2p = get("DVBS2_V2P");
+        group_sync = get("DVBS2_GROUP_SYNC"); group_spin_max = get("DVBS2_GROUP_SPIN_MAX"); resolve_rounds = get("DVBS2_RESOLVE_ROUNDS");
+        timing = getenv("DVBS2_TIMING") != nullptr;
+    }
+};
+bool pick(const std::optional<int>& o, bool rule) { return o ? *o != 0 : rule; } // the override where one is set, else the rule
+
+// The nearest pair (a, b) among the hazard entries of layer L (two entries of one group; distance d1 in rows) and the distance d2 of the
+// next-nearest pair. The two-level walk (check_node_hazard) applies when the nearest pair is the layer's block and every other pair is at
+// least twice as far apart -- the rows then go in outer blocks of d2 rows and only the near pair in ordered steps inside them.
+struct NearPair { int a = -1, b = -1, d1 = 360, d2 = 360; bool two_level = false; };
+NearPair nearest_pair(const LdpcSchedule& s, const LdpcLayer& L)
+{
+    NearPair p;
+    for (int a = 0; a < L.n_conflict; a++)
+        for (int b = a + 1; b < L.n_conflict; b++) {
+            const LdpcEntry& ea = s.entries[L.entry_off + a], & eb = s.entries[L.entry_off + b];
+            if (ea.base != eb.base) continue;
+            const int d = std::abs((int)ea.rot - (int)eb.rot), dist = std::min(d, 360 - d);
+            if (dist < p.d1) { p.d2 = p.d1; p.d1 = dist; p.a = a; p.b = b; }
+            else p.d2 = std::min(p.d2, dist);
+        }
+    p.two_level = p.a >= 0 && p.d1 == L.block && p.d2 >= 2 * p.d1 && 360 / p.d1 - 360 / p.d2 >= 3;
+    return p;
+}
+
+// the entry points of one sweep kernel family: the classic kernel per degree class (ldpc_inst_<dmax>.hip), parity in records (ldpc_inst_pr.hip)
+struct SweepOps { hipError_t (*prepare)(LdpcBuild, size_t pair_lds_bytes, size_t solo_lds_bytes); void (*launch)(const LdpcLaunch&); };
+hipError_t pr_prepare(LdpcBuild b, size_t lds_bytes, size_t) { return ldpc_pr_prepare(b, lds_bytes); }
+const SweepOps& sweep_ops(bool pr, int dmax)
+{
+    static const SweepOps kPr = { pr_prepare, ldpc_pr_launch };
+    static const SweepOps kClassic[8] = {
+        { ldpc_variant_prepare<4>, ldpc_variant_launch<4> },   { ldpc_variant_prepare<8>, ldpc_variant_launch<8> },
+        { ldpc_variant_prepare<12>, ldpc_variant_launch<12> }, { ldpc_variant_prepare<16>, ldpc_variant_launch<16> },
+        { ldpc_variant_prepare<20>, ldpc_variant_launch<20> }, { ldpc_variant_prepare<24>, ldpc_variant_launch<24> },
+        { ldpc_variant_prepare<28>, ldpc_variant_launch<28> }, { ldpc_variant_prepare<32>, ldpc_variant_launch<32> },
+    };
+    return pr ? kPr : kClassic[dmax / 4 - 1];
+}
+} // namespace
+
 LdpcDecoderHip::LdpcDecoderHip(const LdpcTableDesc* table, int out_bits_message, int group_size, int max_frames, int device)
     : out_bits_message_(out_bits_message), G_(group_size), max_frames_(max_frames), device_(device)
 {
     if (!compile_ldpc_schedule(table, &sched_)) { err_ = "unknown or inconsistent LDPC table"; return; }
     if (G_ < 1 || max_frames_ < 1 || max_frames_ > 65535) { err_ = "bad group_size/max_frames (max_frames 1..65535: frames are one launch dimension)"; return; }
     if (out_bits_message_ <= 0 || out_bits_message_ > sched_.N || out_bits_message_ % 8) { err_ = "bad message length"; return; }
-#ifdef DVBS2_EXPERIMENTS // timing-only bounds that give WRONG results: compiled into experiment builds only (tools/build_variant.sh <name> -DDVBS2_EXPERIMENTS),
-                         // never into the library that ships -- a stray environment variable cannot corrupt a deployment's output
-    if (getenv("DVBS2_EXP_NOHAZ")) { // every layer runs as a regular layer
-        for (LdpcLayer& L : sched_.layers) { L.block = 360; L.n_conflict = 0; }
-        sched_.conflict_layers = 0;
-    }
-    if (getenv("DVBS2_EXP_NOSYNC")) // no barrier in front of a regular layer
-        for (LdpcLayer& L : sched_.layers) if (L.block >= 360) L.sync_before = 0;
-#endif
+    const LdpcOverrides ov;
     int degmax = 0, degmin = 1000;
     for (const LdpcLayer& L : sched_.layers) { degmax = std::max(degmax, L.cnt + 2); degmin = std::min(degmin, L.cnt + 2); }
     if (degmax > 32) { err_ = "check degree > 32 unsupported"; return; }
+    // ---- which build of the sweep kernel (decided once, here, before the records are laid out for it) ----
     // "parity in records" variant (ldpc_kernel_pr.hpp): check degree <= 7, at most 4 hazard entries per layer, and two
     // pair workgroups must fit the 160 KB of LDS
     // Policy (measured on MI355X, tools/pr_sweep.sh; the two variants give identical bits): every eligible short and
     // medium table gains 12-43 % from the second workgroup per CU. On normal frames the classic kernel is as fast or
     // faster since its hazard layers run as lane chains (B4: 109 k vs 106 k frames/s; thin-layer tables lose up to
-    // 20 % with parity-in-records). DVBS2_PR=0 / 1 overrides.
+    // 20 % with parity-in-records).
     // Round 6: also the two NORMAL tables of check degree <= 4 (1/4 normal, S2X 2/9 normal: one-dword records, four frames per CU): interleaved A/B
     // 154.1 -> 158.9 k and 152.8 -> 157.6 k frames/s (+3.1 %); the other normal tables of degree <= 7 lose with it (2/5 0.958, B4 0.989, 1/3 0.941, S2X 13/45 0.849).
-    pr_ = degmax <= 7 && (sched_.N < 64800 || degmax <= 4);
-    if (const char* e = getenv("DVBS2_PR")) pr_ = degmax <= 7 && atoi(e) != 0;
+    pr_ = degmax <= 7 && pick(ov.pr, sched_.N < 64800 || degmax <= 4);
     for (const LdpcLayer& L : sched_.layers)
         if (L.block < 360 && (L.n_conflict > 4 || (L.n_conflict > 2 ? 4 : 2) > L.cnt)) pr_ = false;
     pr_shared_sv_ = 2 * pr_lds_bytes(sched_.N, sched_.K) > 160 * 1024; // (normal frames forced onto this kernel: one sign-vector area per workgroup)
@@ -143,12 +187,16 @@ LdpcDecoderHip::LdpcDecoderHip(const LdpcTableDesc* table, int out_bits_message,
     dmax_ = pr_ ? 8 : std::max(4, (degmax + 3) / 4 * 4);
     if (degmin < 3 || degmin <= dmax_ - 8) { err_ = "check degree spread unsupported by the kernel variants"; return; }
     words_per_check_ = dmax_ / 4;
-    DeviceGuard dev_guard(device_); // the caller's current device is restored when the constructor returns (device_guard.h)
-    if (!dev_guard.ok) { err_ = "hipSetDevice failed"; return; }
-    const int RS = rec_stride(dmax_);
-    std::vector<uint32_t> hr((size_t)sched_.q * RS, 0);
-    // Which build of the sweep kernel: measured per table (ldpc_policy.inc <- tools/policy_sweep.py + tools/gen_policy.py); a table
-    // that is not listed takes the plain pair kernel. DVBS2_V2 / DVBS2_SOLO override (tests run every build on every table).
+    // Short frames whose layers are mostly hazard layers (latency-bound ordered steps) and whose degree rules out the
+    // parity-in-records kernel: the 80-VGPR build puts a second workgroup on the CU (measured: short 3/5 and 2/3 +34 %;
+    // it costs 6-18 % where regular layers dominate, hence the 70 % threshold; degree classes above 12 do not fit 80 VGPRs).
+    // It has no two-level lane chain (76 -> 349 spilled registers, round 3) and, since round 4, no single-pair lane chain either -- with
+    // its tables addressed as LDS (typed pointers, ldpc_kernel.hpp) the chain code made that build spill ten times as much (72 -> 725)
+    // and short 3/5 / 2/3 lost 30 %; its layers take the block scheme.
+    const bool dense = !pr_ && dmax_ == 12 && 4 * half_lds_bytes(sched_.N) <= 160 * 1024 &&
+                       pick(ov.dense, sched_.N < 64800 && 10 * sched_.conflict_layers >= 7 * sched_.q);
+    // Which of the other builds: measured per table (ldpc_policy.inc <- tools/policy_sweep.py + tools/gen_policy.py); a table
+    // that is not listed takes the plain pair kernel.
     bool pol_packed = false, pol_solo = false;
     {
         struct Pol { const char* table; int packed, solo; };
@@ -159,34 +207,15 @@ LdpcDecoderHip::LdpcDecoderHip(const LdpcTableDesc* table, int out_bits_message,
     }
     // The build with the heavy-hazard paths (HZ2: up to twelve ordered entries per check instead of the one-wave walk, two-level walk
     // where one hazard pair is much closer than the rest): tables listed in ldpc_policy_hz2.inc (measured, tools/hz2_sweep.sh).
-    hz2_ = false;
+    bool pol_hz2 = false;
     {
         static const char* const kHz2[] = {
 #include "ldpc_policy_hz2.inc"
         };
-        for (const char* n : kHz2) if (!strcmp(n, table->name)) hz2_ = true;
+        for (const char* n : kHz2) if (!strcmp(n, table->name)) pol_hz2 = true;
     }
-    if (const char* e = getenv("DVBS2_HZ2")) hz2_ = atoi(e) != 0;
-    {   // (not for tables that run the 80-VGPR build, chosen below by the same rule)
-        bool dense = sched_.N < 64800 && dmax_ == 12 && 10 * sched_.conflict_layers >= 7 * sched_.q && 4 * half_lds_bytes(sched_.N) <= 160 * 1024;
-        if (const char* e = getenv("DVBS2_DENSE")) dense = dmax_ == 12 && atoi(e) != 0 && 4 * half_lds_bytes(sched_.N) <= 160 * 1024;
-        hz2_ = hz2_ && dmax_ >= 12 && !dense;
-    }
-    bool two_level_on = true;
-    if (const char* e = getenv("DVBS2_TWO_LEVEL")) two_level_on = atoi(e) != 0; // experiments / tests
-    int lane_chain_max = kChainMaxBlock; // rounds 2-3 (integer walk): gains up to block 64, flat to 128, slightly negative at 180; round 4 (float walk, packed chain): +0.2...1.6 % at 180
-    if (const char* e = getenv("DVBS2_LANE_CHAIN_MAX")) lane_chain_max = std::min(kChainMaxBlock, atoi(e)); // experiments
-    // the 80-VGPR build (same rule as where dense_ is set below): no two-level lane chain (76 -> 349 spilled registers, round 3) and, since
-    // round 4, no single-pair lane chain either -- with its tables addressed as LDS (typed pointers, ldpc_kernel.hpp) the chain code made that
-    // build spill ten times as much (72 -> 725) and short 3/5 / 2/3 lost 30 %; its layers take the block scheme
-    // (the build -- 80 VGPRs, one frame per workgroup, software frame barriers -- is decided HERE, once, before the records are laid out for it)
-    dense_ = !pr_ && sched_.N < 64800 && dmax_ == 12 && 10 * sched_.conflict_layers >= 7 * sched_.q && 4 * half_lds_bytes(sched_.N) <= 160 * 1024;
-    if (const char* e = getenv("DVBS2_DENSE")) dense_ = !pr_ && dmax_ == 12 && atoi(e) != 0 && 4 * half_lds_bytes(sched_.N) <= 160 * 1024;
-    const bool dense_here = dense_;
-    const bool timing_on = getenv("DVBS2_TIMING") != nullptr;
-    solo_ = !pr_ && !dense_ && !hz2_ && dmax_ <= kSoloMaxDmax && pol_solo;
-    if (const char* e = getenv("DVBS2_SOLO")) solo_ = !pr_ && !dense_ && !hz2_ && dmax_ <= kSoloMaxDmax && atoi(e) != 0;
-    if (timing_on) solo_ = false;
+    const bool hz2 = !dense && dmax_ >= 12 && pick(ov.hz2, pol_hz2);
+    const bool solo = !pr_ && !dense && !hz2 && dmax_ <= kSoloMaxDmax && !ov.timing && pick(ov.solo, pol_solo);
     // frame barriers in software (ldpc_kernel.hpp): by rule where no layer has hazards; with hazard layers only for the tables listed in
     // ldpc_policy_soft.inc (measured on two leases, tools/soft_sweep.py)
     bool pol_soft = sched_.conflict_layers == 0;
@@ -196,12 +225,23 @@ LdpcDecoderHip::LdpcDecoderHip(const LdpcTableDesc* table, int out_bits_message,
         };
         for (const char* n : kSoft) if (!strcmp(n, table->name)) pol_soft = true;
     }
-    soft_bar_ = !pr_ && !dense_ && !solo_ && dmax_ >= 20 && pol_soft;
-    if (const char* e = getenv("DVBS2_SOFT_BARRIER")) soft_bar_ = !pr_ && !dense_ && !solo_ && dmax_ >= 20 && atoi(e) != 0; // (built for the degree classes >= 20)
-    if (hz2_ || timing_on) soft_bar_ = false;
-    // (the packed build is the table's policy or forced; a later check may still send the table to the plain build, which ignores a chain bit it has no code for)
-    bool packed_intent = !pr_ && !dense_ && !hz2_ && pol_packed;
-    if (const char* e = getenv("DVBS2_V2")) packed_intent = !pr_ && !dense_ && !hz2_ && atoi(e) != 0;
+    const bool soft_bar = !pr_ && !dense && !solo && !hz2 && !ov.timing && dmax_ >= 20 && pick(ov.soft_barrier, pol_soft); // (built for the degree classes >= 20)
+    // the packed build is the table's policy or forced; the fit test below may still send the table to the plain build
+    bool packed = !pr_ && !dense && !hz2 && pick(ov.v2, pol_packed);
+    const bool v2p_on = pick(ov.v2p, true); // hazard layers with the packed first / last phase (classes v2p_class); DVBS2_V2P=0: tests
+    // one-dword records (four 6-bit messages + the parity byte, ldpc_kernel_pr.hpp): check degree <= 4
+    const bool pr_w1 = pr_ && degmax <= 4 && pick(ov.pr_w1, true);
+    if (pr_w1) words_per_check_ = 1;
+    // packed nodes (check_node_v2_pr) in the regular middle layers of the two-dword-record kernel: per-wave sweep records as for the classic packed builds
+    // Measured (MI355X, interleaved A/B x 3): short 2/5, 1/2, S2X short 26/45 / medium 1/3 +3.0 ... +3.8 %, short 1/3 +0.7 %; on NORMAL frames forced onto
+    // this kernel (DVBS2_PR=1) B4 +2.1 % and S2X 9/20 +2.5 % on never-converging input -- and B4 9 % SLOWER at its operating point (Es/N0 2.0 dB: 353 -> 323 k frames/s;
+    // this kernel's full syndrome test fetches the parity signs from the records): short / medium frames by rule, normal frames stay with the classic builds.
+    const bool pr_v2 = pr_ && !pr_w1 && pick(ov.pr_v2, sched_.N < 64800);
+
+    DeviceGuard dev_guard(device_); // the caller's current device is restored when the constructor returns (device_guard.h)
+    if (!dev_guard.ok) { err_ = "hipSetDevice failed"; return; }
+    const int RS = rec_stride(dmax_);
+    std::vector<uint32_t> hr((size_t)sched_.q * RS, 0);
     std::vector<std::vector<int>> layer_order(sched_.q); // record order of every layer's entries (ordered entries first, host-oriented pairs)
     std::vector<int> layer_nc(sched_.q, 0);              // ordered entries the kernel handles in the layer's ordered phase (2, 4, 8, 12; kHazardWalk)
     for (int i = 0; i < sched_.q; i++) {
@@ -209,16 +249,17 @@ LdpcDecoderHip::LdpcDecoderHip(const LdpcTableDesc* table, int out_bits_message,
         uint32_t nc_code = 0;
         if (L.block < 360) {
             nc_code = L.n_conflict <= 2 ? 2 : L.n_conflict <= 4 ? 4 : L.n_conflict <= 8 ? 8 : 12;
-            if (L.n_conflict > (hz2_ && dmax_ <= kMaxHazard12Dmax ? kMaxHazardHz2 : kMaxHazard) || (int)nc_code > L.cnt) nc_code = kHazardWalk;
+            if (L.n_conflict > (hz2 && dmax_ <= kMaxHazard12Dmax ? kMaxHazardHz2 : kMaxHazard) || (int)nc_code > L.cnt) nc_code = kHazardWalk;
         }
         // A layer whose only hazard is ONE pair (two entries of one group) with a small block is walked as a lane
         // chain (check_node_hazard): the pair is ordered so that entry 0's bit of row j is entry 1's bit of row
         // j + block, i.e. (rot0 - rot1) mod 360 == block; header bit 12. Needs lane_chain_words(block) of scratch per
-        // frame in the sign-vector area.
+        // frame in the sign-vector area. (Rounds 2-3, integer walk: gains up to block 64, flat to 128, slightly negative at 180; round 4,
+        // float walk and packed chain: +0.2...1.6 % at 180.)
         int order[64];
         for (int k = 0; k < L.cnt + 2; k++) order[k] = k;
         uint32_t chain = 0;
-        if (!dense_here && L.block <= lane_chain_max && nc_code == 2 && L.n_conflict == 2 && (L.cnt + 2 <= kLaneChainMaxDeg || (packed_intent && v2p_class(dmax_) && L.cnt + 2 <= kLaneChainMaxDegV2p)) &&
+        if (!dense && L.block <= kChainMaxBlock && nc_code == 2 && L.n_conflict == 2 && (L.cnt + 2 <= kLaneChainMaxDeg || (packed && v2p_class(dmax_))) &&
             (sched_.N / 360) * kSvWords >= lane_chain_words(L.block)) {
             const LdpcEntry& a = sched_.entries[L.entry_off], & b = sched_.entries[L.entry_off + 1];
             if (a.base == b.base) {
@@ -227,50 +268,32 @@ LdpcDecoderHip::LdpcDecoderHip(const LdpcTableDesc* table, int out_bits_message,
                 else if (360 - D == L.block) { order[0] = 1; order[1] = 0; chain = 1; }
             }
         }
-        // Two-level walk (check_node_hazard): ONE pair of hazard entries is closer than every other pair by a factor of two or more.
-        // It goes first (entries 0, 1); word 2 of the record = the distance of the nearest OTHER pair = rows per outer block.
+        // Two-level walk (check_node_hazard, nearest_pair): the near pair goes first (entries 0, 1); word 2 of the record = the distance
+        // of the nearest OTHER pair = rows per outer block.
         uint32_t block2 = 0;
+        auto near_pair_first = [&](const NearPair& p) {
+            block2 = (uint32_t)p.d2;
+            order[0] = p.a; order[1] = p.b;
+            int n = 2;
+            for (int k = 0; k < L.n_conflict; k++) if (k != p.a && k != p.b) order[n++] = k;
+        };
         // (the degree class 32 without the heavy-hazard paths walks the near pair as a lane chain inside the outer blocks -- the
-        // two-level lane chain of check_node_hazard: the pair additionally has to be oriented like a single-pair chain, bit 12)
-        // (not in the 80-VGPR build -- same rule as where dense_ is set below --: the chain's state does not fit there, 76 -> 349 spilled registers)
-        const bool tlc_build = tlc_class(dmax_) && !hz2_ && !pr_ && !dense_here && !soft_bar_; // (kTlc<DMAX, HZ2> && !SOFT && MINW == 1 in the kernel)
-        if (tlc_build && two_level_on && L.block < 360 && L.block <= lane_chain_max && (nc_code == 4 || nc_code == 8) &&
+        // two-level lane chain of check_node_hazard: the pair additionally has to be oriented like a single-pair chain, bit 12;
+        // not in the 80-VGPR build: the chain's state does not fit there, 76 -> 349 spilled registers)
+        const bool tlc_build = tlc_class(dmax_) && !hz2 && !pr_ && !dense && !soft_bar; // (kTlc<DMAX, HZ2> && !SOFT && MINW == 1 in the kernel)
+        if (tlc_build && L.block < 360 && L.block <= kChainMaxBlock && (nc_code == 4 || nc_code == 8) &&
             (sched_.N / 360) * kSvWords >= lane_chain_words(L.block)) {
-            int best_a = -1, best_b = -1, d1 = 360, d2 = 360;
-            for (int a = 0; a < L.n_conflict; a++)
-                for (int b = a + 1; b < L.n_conflict; b++) {
-                    const LdpcEntry& ea = sched_.entries[L.entry_off + a], & eb = sched_.entries[L.entry_off + b];
-                    if (ea.base != eb.base) continue;
-                    const int d = std::abs((int)ea.rot - (int)eb.rot), dist = std::min(d, 360 - d);
-                    if (dist < d1) { d2 = d1; d1 = dist; best_a = a; best_b = b; }
-                    else d2 = std::min(d2, dist);
-                }
-            if (best_a >= 0 && d1 == L.block && d2 >= 2 * d1 && 360 / d1 - 360 / d2 >= 3) {
-                const int D = ((int)sched_.entries[L.entry_off + best_a].rot - (int)sched_.entries[L.entry_off + best_b].rot + 360) % 360;
-                if (D != L.block) std::swap(best_a, best_b); // entry 0's bit of row r = entry 1's bit of row r + block  <=>  (rot0 - rot1) mod 360 == block
-                block2 = (uint32_t)d2;
+            NearPair p = nearest_pair(sched_, L);
+            if (p.two_level) {
+                const int D = ((int)sched_.entries[L.entry_off + p.a].rot - (int)sched_.entries[L.entry_off + p.b].rot + 360) % 360;
+                if (D != L.block) std::swap(p.a, p.b); // entry 0's bit of row r = entry 1's bit of row r + block  <=>  (rot0 - rot1) mod 360 == block
                 chain = 1;
-                order[0] = best_a; order[1] = best_b;
-                int n = 2;
-                for (int k = 0; k < L.n_conflict; k++) if (k != best_a && k != best_b) order[n++] = k;
+                near_pair_first(p);
             }
         }
-        if (hz2_ && two_level_on && L.block < 360 && nc_code >= 4 && nc_code != (uint32_t)kHazardWalk && (L.cnt + 2 < 29 || nc_code == 8)) {
-            int best_a = -1, best_b = -1, d1 = 360, d2 = 360;
-            for (int a = 0; a < L.n_conflict; a++)
-                for (int b = a + 1; b < L.n_conflict; b++) {
-                    const LdpcEntry& ea = sched_.entries[L.entry_off + a], & eb = sched_.entries[L.entry_off + b];
-                    if (ea.base != eb.base) continue;
-                    const int d = std::abs((int)ea.rot - (int)eb.rot), dist = std::min(d, 360 - d);
-                    if (dist < d1) { d2 = d1; d1 = dist; best_a = a; best_b = b; }
-                    else d2 = std::min(d2, dist);
-                }
-            if (best_a >= 0 && d1 == L.block && d2 >= 2 * d1 && 360 / d1 - 360 / d2 >= 3) {
-                block2 = (uint32_t)d2;
-                order[0] = best_a; order[1] = best_b;
-                int n = 2;
-                for (int k = 0; k < L.n_conflict; k++) if (k != best_a && k != best_b) order[n++] = k;
-            }
+        if (hz2 && L.block < 360 && nc_code >= 4 && nc_code != (uint32_t)kHazardWalk && (L.cnt + 2 < 29 || nc_code == 8)) {
+            const NearPair p = nearest_pair(sched_, L);
+            if (p.two_level) near_pair_first(p);
         }
         layer_order[i].assign(order, order + L.cnt + 2);
         layer_nc[i] = (int)nc_code;
@@ -282,16 +305,6 @@ LdpcDecoderHip::LdpcDecoderHip(const LdpcTableDesc* table, int out_bits_message,
             hr[(size_t)i * RS + 5 + 2 * k] = 360u - e.rot;
         }
     }
-    // one-dword records (four 6-bit messages + the parity byte, ldpc_kernel_pr.hpp): check degree <= 4
-    pr_w1_ = pr_ && degmax <= 4;
-    if (const char* e = getenv("DVBS2_PR_W1")) pr_w1_ = pr_ && degmax <= 4 && atoi(e) != 0;
-    if (pr_w1_) words_per_check_ = 1;
-    // packed nodes (check_node_v2_pr) in the regular middle layers of the two-dword-record kernel: per-wave sweep records as for the classic packed builds
-    // Measured (MI355X, interleaved A/B x 3, gpurun_out/r6u, r6w): short 2/5, 1/2, S2X short 26/45 / medium 1/3 +3.0 ... +3.8 %, short 1/3 +0.7 %; on NORMAL frames forced onto
-    // this kernel (DVBS2_PR=1) B4 +2.1 % and S2X 9/20 +2.5 % on never-converging input -- and B4 9 % SLOWER at its operating point (Es/N0 2.0 dB: 353 -> 323 k frames/s;
-    // this kernel's full syndrome test fetches the parity signs from the records): short / medium frames by rule, normal frames stay with the classic builds.
-    pr_v2_ = pr_ && !pr_w1_ && sched_.N < 64800;
-    if (const char* e = getenv("DVBS2_PR_V2")) pr_v2_ = pr_ && !pr_w1_ && atoi(e) != 0;
     if (pr_) for (int i = 0; i < sched_.q; i++) hr[(size_t)i * RS] &= ~(1u << 12); // that kernel has no lane chain (80 VGPRs)
     if (pr_) {
         const int q = sched_.q;
@@ -303,22 +316,14 @@ LdpcDecoderHip::LdpcDecoderHip(const LdpcTableDesc* table, int out_bits_message,
     HIP_OK(hipMalloc(&d_recs_alloc_, (hr.size() + kRecHeaderWords) * 4)); // header (group-synchronous stop, filled below) + records
     d_recs_ = d_recs_alloc_ + kRecHeaderWords;
     HIP_OK(hipMemcpy(d_recs_, hr.data(), hr.size() * 4, hipMemcpyHostToDevice));
-    // Short frames whose layers are mostly hazard layers (latency-bound ordered steps) and whose degree rules out the
-    // parity-in-records kernel: the 80-VGPR build puts a second workgroup on the CU (measured: short 3/5 and 2/3 +34 %;
-    // it costs 6-18 % where regular layers dominate, hence the 70 % threshold; degree classes above 12 do not fit 80 VGPRs). DVBS2_DENSE=0 / 1 overrides.
-    // (dense_ was decided before the records were laid out)
     // Sweep records per (layer, wave) for the classic kernel (check_node_v2 in ldpc_kernel.hpp). A regular layer i > 0 gets,
     // for each of the six waves of a frame, its data entries reordered "mixed first" (mixed = the wrap point 360 - rot lies
     // inside the wave's rows), window offsets pre-adjusted for the wave, and the lane masks of the mixed entries; a wave
     // with more mixed entries than fix slots, layer 0 and hazard layers keep the classic record (replicated).
-    bool v2 = !pr_ && !dense_ && !hz2_ && pol_packed; // (the 80-VGPR build has no packed nodes)
-    if (const char* e = getenv("DVBS2_V2")) v2 = !pr_ && !dense_ && !hz2_ && atoi(e) != 0;
-    bool v2p_on = true; // hazard layers with the packed first / last phase (classes from DVBS2_V2P_MIN_DMAX up); DVBS2_V2P=0: experiments, tests
-    if (const char* e = getenv("DVBS2_V2P")) v2p_on = atoi(e) != 0;
-    // "Pure" packed builds (ldpc_kernel.hpp, kPure: the hardware-barrier packed build of the degree class 32): the plain nodes exist for layer 0
+    // "Pure" packed builds (ldpc_kernel.hpp, kPure: the packed builds of the degree class 32): the plain nodes exist for layer 0
     // only, so EVERY (layer > 0, wave) record has to fit the packed format -- mixed entries within the fix slots, no one-wave walk layer. A
     // table that does not fit takes the plain build (of the 57 tables this concerns 9/10 normal only, which fits).
-    if (v2 && (!soft_bar_ || DVBS2_V2_PURE_SOFT) && v2_pure_class(dmax_)) {
+    if (packed && v2_pure_class(dmax_)) {
         bool fits = v2p_on;
         for (int i = 1; fits && i < sched_.q; i++) {
             const LdpcLayer& L = sched_.layers[i];
@@ -331,20 +336,14 @@ LdpcDecoderHip::LdpcDecoderHip(const LdpcTableDesc* table, int out_bits_message,
                 if (nm > (L.block < 360 ? std::min(dmax_ / 2, (int)L.cnt) - ncv : std::min(v2_nfix(dmax_), (int)L.cnt))) fits = false;
             }
         }
-        if (!fits) v2 = false;
+        if (!fits) packed = false;
     }
-    v2_ = v2;
     const int RSW = rec_stride_wave(dmax_);
     std::vector<uint32_t> wr((size_t)sched_.q * 6 * RSW, 0);
-    // single-pair hazard layers walked by the packed register chain (check_node_chain_v2): block <= kChainMaxBlock, the pair are
-    // the first two entries (schedule compiler), and on every wave the mixed regular entries fit the fix slots after the pair's
+    // single-pair hazard layers walked by the packed register chain (check_node_chain_v2, built for the degree classes <= 16): block <=
+    // kChainMaxBlock, the pair are the first two entries (schedule compiler), and on every wave the mixed regular entries fit the fix slots after the pair's
     std::vector<char> chain_v2_layer(sched_.q, 0), chain_order(sched_.q, 0);
-    chain_plain_ = false; // plain build + packed chain node (ldpc_kernel.hpp, CHAIN): measured slower, not built (kChainBuilt); experiments only
-    if (const char* e = getenv("DVBS2_CHAIN_PLAIN")) chain_plain_ = !pr_ && !dense_ && !v2 && dmax_ <= 16 && atoi(e) != 0;
-    bool chain_v2 = (v2 || chain_plain_) && dmax_ <= 16; // the packed chain node is only built for the low degree classes
-    if (const char* e = getenv("DVBS2_CHAIN_V2")) chain_v2 = chain_v2 && atoi(e) != 0;
-    for (int i = 1; chain_v2 && i < sched_.q; i++) {
-        if (false) break;
+    for (int i = 1; packed && dmax_ <= 16 && i < sched_.q; i++) {
         const LdpcLayer& L = sched_.layers[i];
         if (L.block >= 360 || L.block > kChainMaxBlock || L.n_conflict != 2 || L.cnt < 2) continue;
         const LdpcEntry& a = sched_.entries[L.entry_off], & b = sched_.entries[L.entry_off + 1];
@@ -359,7 +358,6 @@ LdpcDecoderHip::LdpcDecoderHip(const LdpcTableDesc* table, int out_bits_message,
             if (nm > v2_nfix(dmax_)) fits = false;
         }
         chain_v2_layer[i] = fits;
-        if (const char* e = getenv("DVBS2_CHAIN_ONLY")) if (atoi(e) != i) chain_v2_layer[i] = 0; // debugging: one layer only
     }
     for (int i = 0; i < sched_.q; i++) {
         const LdpcLayer& L = sched_.layers[i];
@@ -371,9 +369,9 @@ LdpcDecoderHip::LdpcDecoderHip(const LdpcTableDesc* table, int out_bits_message,
             // hazard layers of the packed builds whose ordered phase is the generic one (check_node_hazard<..., V2P>, ldpc_kernel.hpp): the NC
             // ordered entries keep their record order in the first fix slots, the mixed regular entries follow; dmax / 2 fix slots in all
             const int ncv = layer_nc[i];
-            const bool v2p = v2 && v2p_on && v2p_class(dmax_) && L.block < 360 && !chain2 && (ncv == 2 || ncv == 4 || ncv == 8) && (int)L.cnt >= ncv;
+            const bool v2p = packed && v2p_on && v2p_class(dmax_) && L.block < 360 && !chain2 && (ncv == 2 || ncv == 4 || ncv == 8) && (int)L.cnt >= ncv;
             // (parity-in-records: the last layer keeps its plain node, like layer 0; check_node_v2_pr exists for the degrees 5 .. 7)
-            if (L.block < 360 ? !(chain2 || v2p) : !(v2 || (pr_v2_ && i != sched_.q - 1 && L.cnt + 2 >= 5))) continue;
+            if (L.block < 360 ? !(chain2 || v2p) : !(packed || (pr_v2 && i != sched_.q - 1 && L.cnt + 2 >= 5))) continue;
             const int lo = 64 * w, hi = std::min(64 * w + 63, 359);
             std::vector<int> mixed, plain;
             auto is_mixed = [&](int k) { const int thr = 360 - (int)sched_.entries[L.entry_off + k].rot; return lo < thr && thr <= hi; };
@@ -410,9 +408,9 @@ LdpcDecoderHip::LdpcDecoderHip(const LdpcTableDesc* table, int out_bits_message,
         }
     }
     // "Pure" packed builds have no plain node for layers > 0: a (layer, wave) record that is NOT in the packed format would do no work there and
-    // the decode would be silently wrong. The `fits` predicate above is a second copy of the record builder's rules (ADVICE r5): check the
+    // the decode would be silently wrong. The `fits` predicate above is a second copy of the record builder's rules: check the
     // records that were actually BUILT, and refuse the table loudly instead of trusting the copy.
-    if (v2 && (!soft_bar_ || DVBS2_V2_PURE_SOFT) && v2_pure_class(dmax_)) {
+    if (packed && v2_pure_class(dmax_)) {
         for (int i = 1; i < sched_.q; i++)
             for (int w = 0; w < 6; w++) {
                 const uint32_t h0 = wr[((size_t)i * 6 + w) * RSW];
@@ -423,16 +421,12 @@ LdpcDecoderHip::LdpcDecoderHip(const LdpcTableDesc* table, int out_bits_message,
                 }
             }
     }
-    if (chain_plain_) { // the per-layer records of the plain build point chain layers to their per-wave records (bit 14)
-        for (int i = 0; i < sched_.q; i++) if (chain_v2_layer[i]) hr[(size_t)i * RS] |= 1u << 14;
-        HIP_OK(hipMemcpy(d_recs_, hr.data(), hr.size() * 4, hipMemcpyHostToDevice));
-    }
-    // word 1 of a record: message format of the NEXT layer for the same wave (the sweep loads messages one layer ahead)
-    for (int i = 0; i + 1 < sched_.q; i++)
-        for (int w = 0; w < 6; w++) {
-            const uint32_t nh = wr[((size_t)(i + 1) * 6 + w) * RSW];
-            wr[((size_t)i * 6 + w) * RSW + 1] = ((nh & 0xffu) + 2u) | (((nh >> 13) & 1u) << 8);
-        }
+    if (pr_) build_ = pr_w1 ? LdpcBuild::pr_w1 : pr_v2 ? LdpcBuild::pr_packed : LdpcBuild::pr;
+    else if (dense) build_ = LdpcBuild::dense;
+    else if (hz2) build_ = LdpcBuild::hz2;
+    else if (soft_bar) build_ = packed ? LdpcBuild::packed_soft : LdpcBuild::soft;
+    else if (solo) build_ = packed ? LdpcBuild::packed_solo : LdpcBuild::solo;
+    else build_ = packed ? LdpcBuild::packed : LdpcBuild::plain;
     HIP_OK(hipMalloc(&d_wrecs_, wr.size() * 4));
     HIP_OK(hipMemcpy(d_wrecs_, wr.data(), wr.size() * 4, hipMemcpyHostToDevice));
     HIP_OK(hipMalloc(&d_state_, (size_t)max_frames_ * sched_.N));
@@ -444,24 +438,22 @@ LdpcDecoderHip::LdpcDecoderHip(const LdpcTableDesc* table, int out_bits_message,
     // group stops at the reference's count inside the first pass and the resolution rounds have nothing left to do (they stay as
     // the fallback; with the rule on, none is enqueued ahead of time). Needs the members of a group resident together: groups of up
     // to 64 frames (at most 32 pair workgroups of 256 CUs). DVBS2_GROUP_SYNC=0 / 1 overrides (tests run both).
-    gsync_on_ = G_ <= 64;
-    if (const char* e = getenv("DVBS2_GROUP_SYNC")) gsync_on_ = atoi(e) != 0 && G_ <= 64;
+    gsync_on_ = G_ <= 64 && pick(ov.group_sync, true);
     if (gsync_on_) {
         HIP_OK(hipMalloc(&d_gsync_, (size_t)(max_frames_ + 64) * 4)); // one status word per frame (group_decide)
         resolve_rounds_ = 0;
         const unsigned long long a = (unsigned long long)d_iters_, b = (unsigned long long)d_gsync_;
-        int spin_max = kGroupSpinMax;
-        if (const char* e = getenv("DVBS2_GROUP_SPIN_MAX")) spin_max = std::max(0, atoi(e)); // tests: 0 = a waiting member gives up at once (fallback path)
+        const int spin_max = ov.group_spin_max ? std::max(0, *ov.group_spin_max) : kGroupSpinMax; // tests: 0 = a waiting member gives up at once (fallback path)
         const uint32_t hd[kRecHeaderWords] = { (uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32), (uint32_t)G_, (uint32_t)spin_max, 0, 0 };
         HIP_OK(hipMemcpy(d_recs_alloc_, hd, sizeof(hd), hipMemcpyHostToDevice));
     }
-    if (const char* e = getenv("DVBS2_RESOLVE_ROUNDS")) resolve_rounds_ = std::max(0, std::min(8, atoi(e))); // tests: 0 forces the host-side leftover path
+    if (ov.resolve_rounds) resolve_rounds_ = std::max(0, std::min(8, *ov.resolve_rounds)); // tests: 0 forces the host-side leftover path
     HIP_OK(hipMalloc(&d_flag_, 4 * kSlots));
     HIP_OK(hipHostMalloc(&h_flag_, 4 * kSlots));
     HIP_OK(hipEventCreate(&ev0_));
     HIP_OK(hipEventCreate(&ev1_));
-    if (getenv("DVBS2_TIMING")) { HIP_OK(hipMalloc(&d_tdbg_, ((size_t)max_frames_ * 48 + 512) * 8)); HIP_OK(hipMemset(d_tdbg_, 0, ((size_t)max_frames_ * 48 + 512) * 8)); }
-    if (solo_) {
+    if (ov.timing) { HIP_OK(hipMalloc(&d_tdbg_, ((size_t)max_frames_ * 48 + 512) * 8)); HIP_OK(hipMemset(d_tdbg_, 0, ((size_t)max_frames_ * 48 + 512) * 8)); }
+    if (is_solo(build_)) {
         // The per-CU pattern counters of the one-frame builds are shared by ALL handles of a device: two workgroups on a CU take
         // complementary wave patterns through them, whichever launch (handle, stream) they belong to. With one array per handle two
         // pipelined handles both chose pattern 0 on every CU: 4,4,2,2 working waves per SIMD instead of 3,3,3,3 and the operating point
@@ -476,17 +468,11 @@ LdpcDecoderHip::LdpcDecoderHip(const LdpcTableDesc* table, int out_bits_message,
         if (!slots) { err_ = e; return; }
         d_cu_slots_ = slots;
     }
-    kname_ = pr_ ? std::string(pr_w1_ ? "ldpc_layered_pr_kernel<w1>" : pr_v2_ ? "ldpc_layered_pr_kernel<packed>" : "ldpc_layered_pr_kernel") : "ldpc_layered_kernel<" + std::to_string(dmax_) + (dense_ ? ", dense>" : std::string(v2_ ? ", packed" : chain_plain_ ? ", chain" : "") + (solo_ ? ", solo>" : hz2_ ? ", hz2>" : soft_bar_ ? ", soft>" : ">"));
+    static const char* const kSuffix[kLdpcBuilds] = { ">", ", packed>", ", solo>", ", packed, solo>", ", hz2>", ", soft>", ", packed, soft>", ", dense>",
+                                                      "", "<w1>", "<packed>" };
+    kname_ = std::string(pr_ ? "ldpc_layered_pr_kernel" : "ldpc_layered_kernel<" + std::to_string(dmax_)) + kSuffix[(int)build_];
     lds_bytes_ = pr_ ? pr_lds_bytes(sched_.N, sched_.K, pr_shared_sv_) : 2 * half_lds_bytes(sched_.N);
-    if (const char* e = getenv("DVBS2_LDS_PAD")) lds_bytes_ += (size_t)atoi(e); // occupancy experiments only
-    if (pr_) HIP_OK(ldpc_pr_prepare(lds_bytes_));
-    else switch (dmax_) {
-        case 4: HIP_OK(ldpc_variant_prepare<4>(2 * half_lds_bytes(sched_.N), half_lds_bytes(sched_.N))); break;
-        case 8: HIP_OK(ldpc_variant_prepare<8>(2 * half_lds_bytes(sched_.N), half_lds_bytes(sched_.N))); break;   case 12: HIP_OK(ldpc_variant_prepare<12>(2 * half_lds_bytes(sched_.N), half_lds_bytes(sched_.N))); break;
-        case 16: HIP_OK(ldpc_variant_prepare<16>(2 * half_lds_bytes(sched_.N), half_lds_bytes(sched_.N))); break; case 20: HIP_OK(ldpc_variant_prepare<20>(2 * half_lds_bytes(sched_.N), half_lds_bytes(sched_.N))); break;
-        case 24: HIP_OK(ldpc_variant_prepare<24>(2 * half_lds_bytes(sched_.N), half_lds_bytes(sched_.N))); break; case 28: HIP_OK(ldpc_variant_prepare<28>(2 * half_lds_bytes(sched_.N), half_lds_bytes(sched_.N))); break;
-        case 32: HIP_OK(ldpc_variant_prepare<32>(2 * half_lds_bytes(sched_.N), half_lds_bytes(sched_.N))); break;
-    }
+    HIP_OK(sweep_ops(pr_, dmax_).prepare(build_, lds_bytes_, half_lds_bytes(sched_.N)));
 }
 
 LdpcDecoderHip::~LdpcDecoderHip()
@@ -509,19 +495,13 @@ void LdpcDecoderHip::launch_sweep(const int8_t* in, bool resume, int stop_on_goo
     la.iters = d_iters_ + fb; la.good = d_good_ + fb; la.target = resume ? d_target_ + fb : nullptr;
     const bool gs = gsync_on_ && !resume && stop_on_good; // group-synchronous stop: bit 2 of the flag word; its words start from zero
     if (gs) (void)hipMemsetAsync(d_gsync_ + frame_base, 0, (size_t)n_frames * 4, stream); // (frame_base is a multiple of the group size: enqueue())
-    la.n_frames = n_frames; la.N = sched_.N; la.K = sched_.K; la.q = sched_.q; la.cap = max_trials; la.stop_on_good = stop_on_good | (soft_bar_ ? 2 : 0) | (gs ? 4 : 0) | (pr_ && pr_shared_sv_ ? 8 : 0);
-    la.tdbg = d_tdbg_; la.lds_bytes = solo_ ? half_lds_bytes(sched_.N) : lds_bytes_; la.stream = stream; la.dense = dense_;
-    la.v2 = pr_ ? pr_w1_ : v2_; la.solo = solo_; la.chain = chain_plain_; la.pr_packed = pr_ && pr_v2_; la.hz2 = hz2_; la.soft = soft_bar_; la.cu_slots = d_cu_slots_;
+    const bool soft_bar = build_ == LdpcBuild::soft || build_ == LdpcBuild::packed_soft;
+    la.n_frames = n_frames; la.N = sched_.N; la.K = sched_.K; la.q = sched_.q; la.cap = max_trials; la.stop_on_good = stop_on_good | (soft_bar ? 2 : 0) | (gs ? 4 : 0) | (pr_ && pr_shared_sv_ ? 8 : 0);
+    la.tdbg = d_tdbg_; la.lds_bytes = is_solo(build_) ? half_lds_bytes(sched_.N) : lds_bytes_; la.stream = stream;
+    la.build = build_; la.cu_slots = d_cu_slots_;
     la.dm = DemapFused{};
     if (dm && !resume) la.dm = *dm;
-    if (pr_) ldpc_pr_launch(la);
-    else switch (dmax_) {
-        case 4: ldpc_variant_launch<4>(la); break;
-        case 8: ldpc_variant_launch<8>(la); break;   case 12: ldpc_variant_launch<12>(la); break;
-        case 16: ldpc_variant_launch<16>(la); break; case 20: ldpc_variant_launch<20>(la); break;
-        case 24: ldpc_variant_launch<24>(la); break; case 28: ldpc_variant_launch<28>(la); break;
-        case 32: ldpc_variant_launch<32>(la); break;
-    }
+    sweep_ops(pr_, dmax_).launch(la);
     if (profiling_ && !resume) { // the first pass is the dominant launch; timing it serialises the stream (bench.py's roofline leg only)
         (void)hipEventRecord(ev1_, stream);
         (void)hipEventSynchronize(ev1_);

@@ -6,52 +6,14 @@
 #include <cstdint>
 #include "demap_math.hpp"
 
-#ifndef DVBS2_FWALK_MAXDEG
-#define DVBS2_FWALK_MAXDEG 12 // measured (round 4, interleaved A/B): 8 -> B2 +8 %, B4 +0.5 %; 12 -> 3/5 normal +1 %, T2 2/3 +4 %, the one-frame class-12 tables +5 %; 16 -> B7 -1 %; 28 -> 8/9 normal -8 %, 5/6 -3 %
-#endif
-#ifndef DVBS2_FWALK
-#define DVBS2_FWALK 1 // float walk with four rows in flight in the plain lane chain of the degree class 8 (check_node_hazard)
-#endif
-
-// Lane-chain layers (check_node_hazard), round 4: the pair's LLR bytes read with the regular entries, and the float walk on absolute LDS
-// addresses. Largest check degree that gets them -- measured (interleaved A/B, whole tables): degree <= 8: B4 +0.7 %, 9/20 ... S2_TABLE_B3 +1.8 %,
-// B1 +1 %, B2 -0.6 %; degree class 12: 3/5 normal 0, 2/3 normal and T2 2/3 -4 % (register allocation of their one-frame builds) -- and the
-// degree-5..8 instantiations INSIDE the class-12 kernel cost its tables 3-7 % as well (S2X 99/180 ... S2X_TABLE_B4 -7 %), so the switch is the
-// kernel's class (CLASS8 = DMAX <= 8), not the check degree
-#ifndef DVBS2_EARLY_PAIR_MAXDEG
-#define DVBS2_EARLY_PAIR_MAXDEG 8
-#endif
-#ifndef DVBS2_WALK_ABS_MAXDEG
-#define DVBS2_WALK_ABS_MAXDEG 8
-#endif
-// The new messages of a layer are stored behind an explicit `s_waitcnt vmcnt(0)`. The compiler waits for the NEXT layer's prefetched
-// messages (loaded at the head of this layer) with vmcnt(0) -- loads and stores share the counter and across this loop's control flow it
-// cannot count them -- and, left alone, places that wait at their first use, i.e. right AFTER the stores it has just issued: every wave of the
-// workgroup then sat through the L2's acknowledgement of its stores at every layer boundary. Waiting first costs nothing (the prefetch
-// is a layer old) and leaves the stores a whole layer to complete; no register is added. Measured (interleaved A/B): 1/4 normal +7 %,
-// B4 +3.6 %, 1/3 normal +8 %, 3/4 normal +3 % (23 tables, none loses); not in the software-barrier builds (S2X 154/180 -4 %).
-#ifndef DVBS2_PF_SMALL_MAX_DMAX
-#define DVBS2_PF_SMALL_MAX_DMAX 8 // up to this degree class the whole record is double-buffered in scalar registers. Measured: class 8 loses 2-3 % without it
-#endif                            // (B4 119.7 -> 117.1 k), class 12 GAINS 1-3 % without it (3/5, 2/3 normal, S2X 11/20, T2 2/3, short 2/3; short 3/5 -0.7 %)
-#ifndef DVBS2_PREFETCH_AFTER_BARRIER_MAX_DMAX
-#define DVBS2_PREFETCH_AFTER_BARRIER_MAX_DMAX 8
-#endif
-#ifndef DVBS2_PRETEST_CHUNK
-#define DVBS2_PRETEST_CHUNK 1 // the one-layer syndrome pre-test four edges per trip (round 6; 0: edge by edge)
-#endif
-#ifndef DVBS2_WAIT_RECORDS
-#define DVBS2_WAIT_RECORDS 1 // first measured on the plain class-8 build: B4 119.6 -> 115.9 k (off); re-measured once B4 ran the packed one-frame build: B4 133.2 -> 134.5 k, 2/5 normal +0.7 %, 3/5 +1 %, the others +-0.5 % (on)
-#endif
-#ifndef DVBS2_WAIT_BEFORE_STORE
-#define DVBS2_WAIT_BEFORE_STORE 1
-#endif
-// s_waitcnt vmcnt(0) (expcnt, lgkmcnt untouched) that memory operations are not moved across
+// s_waitcnt vmcnt(0) (expcnt, lgkmcnt untouched) that memory operations are not moved across, in front of the stores of a layer's new
+// messages. The compiler waits for the NEXT layer's prefetched messages (loaded at the head of this layer) with vmcnt(0) -- loads and
+// stores share the counter and across this loop's control flow it cannot count them -- and, left alone, places that wait at their first
+// use, i.e. right AFTER the stores it has just issued: every wave of the workgroup then sat through the L2's acknowledgement of its stores
+// at every layer boundary. Waiting first costs nothing (the prefetch is a layer old) and leaves the stores a whole layer to complete; no
+// register is added. Measured (interleaved A/B): 1/4 normal +7 %, B4 +3.6 %, 1/3 normal +8 %, 3/4 normal +3 % (23 tables, none loses).
 // (kWaitStore in scope: not in the builds with software frame barriers -- S2X 154/180 lost 4 % with it)
 #define DVBS2_WAIT_VM0() do { if (kWaitStore) { asm volatile("" ::: "memory"); __builtin_amdgcn_s_waitcnt(0x0f70); asm volatile("" ::: "memory"); } } while (0)
-#ifndef DVBS2_TLC_FWALK_MIN_DMAX
-#define DVBS2_TLC_FWALK_MIN_DMAX 24 // the near pair of a two-level lane chain walked in float (six instructions per row, 16-byte operand records) in the
-                                    // packed hazard nodes from this degree class up -- measured (round 5): 5/6 normal +3.1 %, 9/10 normal +0.35 %; 3/4 normal (class 16) -2.0 %
-#endif
 
 namespace dvbs2 {
 
@@ -82,10 +44,9 @@ __host__ __device__ constexpr int rec_stride_wave(int dmax) { return 2 * dmax + 
 constexpr int kRecHeaderWords = 8; // [0,1] iters base, [2,3] base of the per-frame status words (group_decide), [4] group size, [5] polls before a waiting member gives up, rest unused
 // per frame: N LLR bytes, then the sign-vector area (syndrome test; scratch of the ordered hazard phases during a sweep:
 // at least kChainScratchWords dwords, which is what short frames get instead of their small sign-vector area), then 8 flag words
-#ifndef DVBS2_CHAIN_MAX_BLOCK
-#define DVBS2_CHAIN_MAX_BLOCK 180 // round 4: 128 -> 180 (blocks 129..180 are three-step block-scheme layers otherwise): 3/4 normal +1.6 %, 3/5 +1.3 %, B4 / 2/5 normal +0.4 %
-#endif
-constexpr int kChainMaxBlock = DVBS2_CHAIN_MAX_BLOCK;                                             // largest block walked as a register chain
+// largest block walked as a register chain -- round 4: 128 -> 180 (blocks 129..180 are three-step block-scheme layers otherwise): 3/4 normal
+// +1.6 %, 3/5 +1.3 %, B4 / 2/5 normal +0.4 %
+constexpr int kChainMaxBlock = 180;
 constexpr int kChainScratchWords = (kM + kChainMaxBlock) * 5 + 4;               // (360 + block) x (16-byte record + 4-byte log) + 16 bytes: the records are 16-byte aligned and the area starts at N, which is 8 mod 16 for short frames
 __host__ __device__ constexpr int sv_area_words(int N) { return (N / kM) * kSvWords > kChainScratchWords ? (N / kM) * kSvWords : kChainScratchWords; }
 __host__ __device__ constexpr size_t half_lds_bytes(int N) { return ((size_t)N + (size_t)sv_area_words(N) * 4 + 32 + 15) / 16 * 16; }
@@ -204,9 +165,7 @@ __device__ __forceinline__ void lds_wr(int a, int v) { *reinterpret_cast<lds_byt
 // Measured (interleaved A/B, all packed builds with and without): the degree class 8 gains (B4 135.4 -> 137.7 k, S2X 9/20 +0.7 %), every other
 // class loses 0.2-3 % (3/4 normal -2.7 %, 4/5 -3 %, short 3/4 -2.9 %: their scalar paths pay the conversion, and removing 7 % of the packed
 // node's VALU instructions buys almost nothing where the layer is as much bound by its message traffic and barriers) -- so: class 8 only.
-#ifndef DVBS2_TC_MAX_DMAX
-#define DVBS2_TC_MAX_DMAX 8
-#endif
+constexpr int kTcMaxDmax = 8;
 template <bool TC> __device__ __forceinline__ int lds_rdx(int a) { const int v = lds_rd(a); return TC ? (v ^ 0x80) : v; }          // offset-binary value of the LLR byte at a
 template <bool TC> __device__ __forceinline__ void lds_wrx(int a, int v) { lds_wr(a, TC ? (v ^ 0x80) : v); }                        // store an offset-binary value
 template <bool TC> constexpr uint32_t kObPair = TC ? 0u : 0x80008000u; // offset binary -> two's complement << 8 of a pair register
@@ -363,15 +322,11 @@ __device__ __forceinline__ void check_node(uint8_t* __restrict__ lds /*the whole
 // 32 (9/10 normal + 8 %).
 template <int DMAX, bool HZ2> constexpr bool kTlc = (DMAX == 16 || DMAX == 24 || DMAX == 32) && !HZ2;
 // Hazard layers with the packed first / last phase (check_node_hazard<..., V2P>, round 5): compiled into the packed builds of the degree
-// classes from DVBS2_V2P_MIN_DMAX up -- the classes whose hazard layers all took the plain node (no packed chain node there).
-#ifndef DVBS2_V2P_MIN_DMAX
-#define DVBS2_V2P_MIN_DMAX 20
-#endif
-__host__ __device__ constexpr bool v2p_class(int dmax) { return dmax >= DVBS2_V2P_MIN_DMAX; }
-#ifndef DVBS2_V2_PURE_MIN_DMAX
-#define DVBS2_V2_PURE_MIN_DMAX 32 // measured (round 5, interleaved A/B): class 32 (9/10 normal) 80.2 -> 83.9 k; 28 (8/9) 95.9 -> 91.2 k, 24 (5/6) 76.9 -> 74.2 k
-#endif
-__host__ __device__ constexpr bool v2_pure_class(int dmax) { return dmax >= DVBS2_V2_PURE_MIN_DMAX; }
+// classes from 20 up -- the classes whose hazard layers all took the plain node (no packed chain node there).
+__host__ __device__ constexpr bool v2p_class(int dmax) { return dmax >= 20; }
+// "pure" packed builds (kPure in ldpc_layered_kernel) -- measured (round 5, interleaved A/B): class 32 (9/10 normal) 80.2 -> 83.9 k;
+// 28 (8/9) 95.9 -> 91.2 k, 24 (5/6) 76.9 -> 74.2 k
+__host__ __device__ constexpr bool v2_pure_class(int dmax) { return dmax >= 32; }
 __host__ __device__ constexpr bool tlc_class(int dmax) { return dmax == 16 || dmax == 24 || dmax == 32; }
 constexpr int kTlcLowRegMinDmax = 24; // from this degree class on a two-level-chain layer keeps its regular entries in the low-register form
 __device__ __forceinline__ int pm_pack(int magp, int d) { return (int)__builtin_amdgcn_perm((uint32_t)magp, (uint32_t)d, 0x0c0c0400u); } // d.b0 | magp.b0 << 8
@@ -416,68 +371,39 @@ __device__ __forceinline__ int fix_wrap(int ad, uint32_t mlo, uint32_t mhi)
     return ad;
 }
 
-#ifndef DVBS2_V2_NFIX32
-#define DVBS2_V2_NFIX32 10 // fix slots of the degree class 32: with 10 every wave record of S2X 154/180 fits the packed format (8: two of its 150 did not)
-#endif
-__host__ __device__ constexpr int v2_nfix(int dmax) { return dmax == 32 ? DVBS2_V2_NFIX32 : dmax / 4; } // fix slots per record: masks live in record words 4 + dmax + 2 k
+// fix slots per record: masks live in record words 4 + dmax + 2 k. The degree class 32 has ten: with them every wave record of S2X 154/180
+// fits the packed format (with 8 two of its 150 did not).
+__host__ __device__ constexpr int v2_nfix(int dmax) { return dmax == 32 ? 10 : dmax / 4; }
 
-// Message storage of the packed nodes. A stored message is clamp(out, -32, 31) (R7): six bits. P6 = true keeps them as six-bit
-// two's complement fields, five per dword (entry e in word e / 5 at bit 6 (e % 5); a last word with one or two fields is a
-// 16-bit access): 4, 4, 6, 6, 8 ... bytes per check for degree 4, 5, 6, 7, 8 instead of 8. The regular layers of the
-// low-degree tables run at the bandwidth the memory system gives to this access pattern (~4.9 TB/s of message traffic on
-// table B4, whatever the node costs), so the bytes are what counts there; the unpacking costs ~2.5 VALU instructions per
-// edge, which those layers have to spare. P6 = false: one byte per message (pair j in bytes (j & 1) and (j & 1) + 2 of word j / 2).
-template <bool P6>
+// Message storage of the packed nodes: one byte per message (R7 clamps a stored message to six bits, clamp(out, -32, 31)), pair j in
+// bytes (j & 1) and (j & 1) + 2 of word j / 2. (Six-bit fields, five per dword, measured slower on table B4, 4096 frames: 107 k frames/s
+// with byte messages, 93 k with six-bit fields at the same traffic, 85-91 k with the traffic actually reduced by a quarter -- the
+// unpacking costs more than the bytes bring: the regular layers are limited by VALU issue and memory traffic at the same time.)
 __device__ __forceinline__ uint32_t msg_pair16(const uint32_t* mw, int j)
 {
-    if constexpr (P6) {
-        const int e0 = 2 * j, e1 = 2 * j + 1;
-        const int lo = __builtin_amdgcn_sbfe((int)mw[e0 / 5], 6 * (e0 % 5), 6), hi = __builtin_amdgcn_sbfe((int)mw[e1 / 5], 6 * (e1 % 5), 6);
-        return __builtin_amdgcn_perm((uint32_t)hi, (uint32_t)lo, 0x040c000cu); // [hi << 8 | lo << 8]; a field past the degree reads 0
-    } else {
-        const uint32_t w = mw[j >> 1];
-        return (j & 1) ? (w & 0xff00ff00u) : __builtin_amdgcn_perm(w, 0u, 0x060c040cu); // bytes 2, 0 of w to bytes 3, 1
-    }
+    const uint32_t w = mw[j >> 1];
+    return (j & 1) ? (w & 0xff00ff00u) : __builtin_amdgcn_perm(w, 0u, 0x060c040cu); // bytes 2, 0 of w to bytes 3, 1
 }
-template <bool P6, int NP, int NW>
+template <int NP>
 __device__ __forceinline__ void msg_pack16(const uint32_t* R /*clamped messages << 8 in both halves, pad half zero*/, uint32_t* nm)
 {
-    if constexpr (P6) {
 #pragma unroll
-        for (int w = 0; w < NW; w++) nm[w] = 0;
-#pragma unroll
-        for (int e = 0; e < 2 * NP; e++) {
-            if (e / 5 < NW) {
-                const uint32_t f = __builtin_amdgcn_ubfe(R[e >> 1], (e & 1) ? 24 : 8, 6);
-                nm[e / 5] = (e % 5) ? ((f << (6 * (e % 5))) | nm[e / 5]) : f;
-            }
-        }
-    } else {
-#pragma unroll
-        for (int w = 0; w < (NP + 1) / 2; w++)
-            nm[w] = (2 * w + 1 < NP) ? ((R[2 * w] >> 8) | R[2 * w + 1]) : (R[2 * w] >> 8);
-    }
+    for (int w = 0; w < (NP + 1) / 2; w++)
+        nm[w] = (2 * w + 1 < NP) ? ((R[2 * w] >> 8) | R[2 * w + 1]) : (R[2 * w] >> 8);
 }
-// msg_pack16 with the pad half of an odd degree still in R[NP - 1]. One-byte messages: one v_perm per word instead of shift + or,
-// and the pad byte is selected as zero instead of masked.
-template <bool P6, int NP, int NW, bool ODD>
+// msg_pack16 with the pad half of an odd degree still in R[NP - 1]: one v_perm per word instead of shift + or, and the pad byte is
+// selected as zero instead of masked.
+template <int NP, bool ODD>
 __device__ __forceinline__ void msg_pack16_hb(uint32_t* R, uint32_t* nm)
 {
-    if constexpr (P6) {
-        if (ODD) R[NP - 1] &= 0x0000ffffu;
-        msg_pack16<P6, NP, NW>(R, nm);
-    } else {
 #pragma unroll
-        for (int w = 0; w < (NP + 1) / 2; w++) {
-            const bool two = 2 * w + 1 < NP;                        // word w holds pairs 2w and 2w + 1
-            const bool pad_lo = ODD && !two, pad_hi = ODD && two && 2 * w + 1 == NP - 1;
-            const uint32_t sel = 0x01u | (two ? 0x05u : 0x0cu) << 8 | (pad_lo ? 0x0cu : 0x03u) << 16 | ((two && !pad_hi) ? 0x07u : 0x0cu) << 24;
-            nm[w] = __builtin_amdgcn_perm(two ? R[2 * w + 1] : 0u, R[2 * w], sel); // bytes 1, 3 of pair 2w -> 0, 2; of pair 2w + 1 -> 1, 3
-        }
+    for (int w = 0; w < (NP + 1) / 2; w++) {
+        const bool two = 2 * w + 1 < NP;                        // word w holds pairs 2w and 2w + 1
+        const bool pad_lo = ODD && !two, pad_hi = ODD && two && 2 * w + 1 == NP - 1;
+        const uint32_t sel = 0x01u | (two ? 0x05u : 0x0cu) << 8 | (pad_lo ? 0x0cu : 0x03u) << 16 | ((two && !pad_hi) ? 0x07u : 0x0cu) << 24;
+        nm[w] = __builtin_amdgcn_perm(two ? R[2 * w + 1] : 0u, R[2 * w], sel); // bytes 1, 3 of pair 2w -> 0, 2; of pair 2w + 1 -> 1, 3
     }
 }
-// words of one check's message record that hold fields, and whether word k is a 16-bit access, for degree deg
-__host__ __device__ constexpr int p6_fields(int deg, int k) { return deg - 5 * k < 0 ? 0 : (deg - 5 * k > 5 ? 5 : deg - 5 * k); }
 
 // R3 on pairs: the two smallest of the 2 NP halves of a[] (all of them real: the caller lifts a pad above every magnitude). Per half
 // position a tree of sorted pairs (min / max of two registers, then merges of two sorted pairs in four instructions), then ONE
@@ -531,7 +457,7 @@ __device__ __forceinline__ void pair_out(v2s16 d, v2s16 a, v2s16 B1p, uint32_t T
     R = as_u32(__builtin_elementwise_min(__builtin_elementwise_max(out, (v2s16){ -32 * 256, -32 * 256 }), (v2s16){ 31 * 256, 31 * 256 }));
 }
 
-template <int DEG, int DMAX, bool P6, bool TC, class Prefetch>
+template <int DEG, int DMAX, bool TC, class Prefetch>
 __device__ __forceinline__ void check_node_v2(const uint32_t* ent /*record words 4..: S0w[DMAX], then (mask lo, mask hi)[NFIX]*/,
                                               int jjb, const uint32_t* mw, uint32_t* nm, Prefetch prefetch_next_record)
 {
@@ -547,10 +473,6 @@ __device__ __forceinline__ void check_node_v2(const uint32_t* ent /*record words
         for (int k = 0; k < NFIX; k++) ad[k] = fix_wrap(ad[k], ent[DMAX + 2 * k], ent[DMAX + 2 * k + 1]);
     };
     addresses();
-#ifndef DVBS2_V2_KEEP_AD_MAXDEG
-#define DVBS2_V2_KEEP_AD_MAXDEG 32 // experiments: above this degree the addresses are computed again in the output phase instead of held across the node
-#endif
-    constexpr bool KEEP_AD = DEG <= DVBS2_V2_KEEP_AD_MAXDEG;
     int Lb[DEG];
 #pragma unroll
     for (int k = 0; k < DEG; k++) Lb[k] = lds_rd(ad[k]);
@@ -558,7 +480,7 @@ __device__ __forceinline__ void check_node_v2(const uint32_t* ent /*record words
     uint32_t sx = 0;
 #pragma unroll
     for (int j = 0; j < NP; j++) {
-        const uint32_t M = msg_pair16<P6>(mw, j); // messages of pair j: << 8 in both halves
+        const uint32_t M = msg_pair16(mw, j); // messages of pair j: << 8 in both halves
         const uint32_t hi = (ODD && j == NP - 1) ? (TC ? 0x00u : 0x80u) : (uint32_t)Lb[2 * j + 1];
         const uint32_t L = __builtin_amdgcn_perm(hi, (uint32_t)Lb[2 * j], 0x040c000cu) ^ kObPair<TC>; // -> two's complement << 8
         d[j] = __builtin_elementwise_sub_sat(as_v2s(L), as_v2s(M));           // R1 (a half that saturates upwards reads 0x7fff)
@@ -583,7 +505,6 @@ __device__ __forceinline__ void check_node_v2(const uint32_t* ent /*record words
     const uint32_t tm = (uint32_t)((int)(sx ^ (sx << 16)) >> 31); // all ones when the number of negative inputs is odd
     const v2s16 B1p = { (short)B1, (short)B1 };
     const uint32_t Tt = __builtin_amdgcn_perm((uint32_t)T, (uint32_t)T, 0x01000100u) ^ tm; // T in both halves (one v_perm; the compiler's own broadcast is a multiply)
-    if constexpr (!KEEP_AD) { asm volatile("" ::: "memory"); addresses(); }
     uint32_t R[NP];
 #pragma unroll
     for (int j = 0; j < NP; j++) {
@@ -593,7 +514,7 @@ __device__ __forceinline__ void check_node_v2(const uint32_t* ent /*record words
         if (!(ODD && j == NP - 1)) lds_wr_hi(ad[2 * j + 1], nl);
     }
     __builtin_amdgcn_s_setprio(3);
-    msg_pack16_hb<P6, NP, DMAX / 4, ODD>(R, nm);
+    msg_pack16_hb<NP, ODD>(R, nm);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -614,7 +535,7 @@ __device__ __forceinline__ float as_f32(uint32_t x) { return __builtin_bit_cast(
 __device__ __forceinline__ float vmed3_f32(float a, float b, float c) { return __builtin_amdgcn_fmed3f(a, b, c); }
 __device__ __forceinline__ float byte1_f32(uint32_t x) { return (float)((x >> 8) & 0xffu); } // v_cvt_f32_ubyte1
 
-template <int DEG, int DMAX, bool P6, bool TC>
+template <int DEG, int DMAX, bool TC>
 __device__ __forceinline__ void check_node_chain_v2(const uint32_t* ent /*S0w[DMAX], masks[NFIX + 2]*/, int jj, int jjb, bool work, int B,
                                                     const uint32_t* mw, uint32_t* nm, lds_u32_t* tab /*LDS scratch, 16-byte aligned*/,
                                                     volatile lds_i32_t* hb_ctr, int& hb_epoch, const int hb_lane)
@@ -643,7 +564,7 @@ __device__ __forceinline__ void check_node_chain_v2(const uint32_t* ent /*S0w[DM
     };
     auto pair0 = [&](int LbX, int LbY) { // d, |d| of the pair [X | Y] (LLR bytes as they lie in LDS)
         const uint32_t L = __builtin_amdgcn_perm((uint32_t)LbY, (uint32_t)LbX, 0x040c000cu) ^ kObPair<TC>;
-        const uint32_t M = msg_pair16<P6>(mw, 0);
+        const uint32_t M = msg_pair16(mw, 0);
         d[0] = __builtin_elementwise_sub_sat(as_v2s(L), as_v2s(M));
         a[0] = __builtin_elementwise_max(d[0], __builtin_elementwise_sub_sat(as_v2s(0u), d[0]));
     };
@@ -657,7 +578,7 @@ __device__ __forceinline__ void check_node_chain_v2(const uint32_t* ent /*S0w[DM
         else if (middle) LbX = lds_rd(ad[0]); // original value: the only other row that touches this bit comes later (row jj + B)
 #pragma unroll
         for (int j = 1; j < NP; j++) {
-            const uint32_t M = msg_pair16<P6>(mw, j);
+            const uint32_t M = msg_pair16(mw, j);
             const uint32_t hi = (ODD && j == NP - 1) ? (TC ? 0x00u : 0x80u) : (uint32_t)Lb[2 * j + 1];
             const uint32_t L = __builtin_amdgcn_perm(hi, (uint32_t)Lb[2 * j], 0x040c000cu) ^ kObPair<TC>;
             d[j] = __builtin_elementwise_sub_sat(as_v2s(L), as_v2s(M));
@@ -688,7 +609,7 @@ __device__ __forceinline__ void check_node_chain_v2(const uint32_t* ent /*S0w[DM
     // chain operands of the middle rows (a tail row only receives: the walker logs what arrives there and needs nothing from it)
     if (middle) {
         const uint32_t L = __builtin_amdgcn_perm(TC ? 0x00u : 0x80u, (uint32_t)LbX, 0x040c000cu) ^ kObPair<TC>;
-        const uint32_t M0 = msg_pair16<P6>(mw, 0);
+        const uint32_t M0 = msg_pair16(mw, 0);
         const uint32_t M = M0 & 0x0000ffffu;
         const v2s16 dx = __builtin_elementwise_sub_sat(as_v2s(L), as_v2s(M));       // [inp_X | 0]
         const uint32_t fold = sxp ^ (sxp << 16);                                      // bit 31: parity of the signs of the regular entries (the inputs other than X and Y)
@@ -770,7 +691,7 @@ __device__ __forceinline__ void check_node_chain_v2(const uint32_t* ent /*S0w[DM
         }
         __builtin_amdgcn_s_setprio(3);
         if (ODD) R[NP - 1] &= 0x0000ffffu;
-        msg_pack16<P6, NP, DMAX / 4>(R, nm);
+        msg_pack16<NP>(R, nm);
     }
 }
 
@@ -788,12 +709,14 @@ __device__ __forceinline__ void check_node_chain_v2(const uint32_t* ent /*S0w[DM
 // (moving a regular entry into the ordered part does not change the result).
 // LDS scratch of a lane chain with block size B: (360 + B) per-row records (dwords) + as many log bytes
 __host__ __device__ constexpr int lane_chain_words(int block) { return (kM + block) + (kM + block + 3) / 4; }
-#ifndef DVBS2_LANE_CHAIN_MAXDEG_V2P
-#define DVBS2_LANE_CHAIN_MAXDEG_V2P 32 // the lane chain in hazard nodes with the packed first / last phase (their state is smaller): 9/10 normal 83.9 -> 86.3 k (round 5)
-#endif
-constexpr int kLaneChainMaxDegV2p = DVBS2_LANE_CHAIN_MAXDEG_V2P;
 constexpr int kLaneChainMaxDeg = 28;                                  // not instantiated for the big variants nor for the
-                                                                      // 80-VGPR parity-in-records kernel (registers)
+                                                                      // 80-VGPR parity-in-records kernel (registers); hazard nodes with
+                                                                      // the packed first / last phase (their state is smaller) have it at
+                                                                      // every degree: 9/10 normal 83.9 -> 86.3 k (round 5)
+constexpr int kFwalkMaxDeg = 12;     // largest check degree of a single-pair lane chain walked in float (kFloatWalk)
+constexpr int kTlcFwalkMinDmax = 24; // the near pair of a two-level lane chain walked in float (six instructions per row, 16-byte operand records)
+                                     // in the packed hazard nodes from this degree class up -- measured (round 5): 5/6 normal +3.1 %, 9/10 normal
+                                     // +0.35 %; 3/4 normal (class 16) -2.0 %
 constexpr int kMaxHazard = 8;     // ordered entries per check in the common builds, kMaxHazardHz2 in the HZ2 builds (ldpc_layered_kernel)
 constexpr int kMaxHazardHz2 = 12;
 constexpr int kMaxHazard12Dmax = 28; // (the degree class 32 has the two-level walk only: twelve ordered entries on top of 30 edges do not fit its registers)
@@ -802,11 +725,11 @@ template <int DEG, int NC, bool LAYER0, bool PR = false, bool LAST = false, bool
           bool LR = false /*low-register form: a regular entry keeps ONE word pm = |Lb - mb| << 8 | (inp & 0xff) between the phases and its address is computed twice (two-level-chain layers of the classes >= 24)*/,
           bool TLC = false /*two-level walk with the near pair as a LANE CHAIN (round 3), see below*/,
           bool CHAINOK = true /*false: no lane chain in this build (the 80-VGPR build since round 4, see kLaneChainBuilt)*/,
-          bool CLASS8 = false /*the kernel of the degree class <= 8: early pair reads, walk on absolute addresses (DVBS2_EARLY_PAIR_MAXDEG)*/,
+          bool CLASS8 = false /*the kernel of the degree class <= 8: early pair reads, walk on absolute addresses (kEarlyPair)*/,
           bool V2P = false /*round 5: FIRST and LAST phase in the packed form of check_node_v2 (pairs of regular entries in the halves of one
                              register, one-add addresses from this wave's record, two's complement messages in pair-byte order); the ordered
                              phase in between is untouched. `ent` is then the per-wave record: S0w[DMAXV], lane masks of the first NFIXH slots*/,
-          int DMAXV = 0, bool P6 = false, bool TC = false /*LLR bytes in LDS are two's complement (the builds with packed nodes)*/>
+          int DMAXV = 0, bool TC = false /*LLR bytes in LDS are two's complement (the builds with packed nodes)*/>
 __device__ __forceinline__ void check_node_hazard(uint8_t* __restrict__ lds, const uint32_t* ent, int jj, int lb, bool work,
                                                   int block, int block2 /*two-level walk: rows per outer block, 0 = off*/, const uint32_t* mw, uint32_t* nm, int own_in, int* carry,
                                                   lds_u32_t* tab /*lane_chain_words(block) of LDS scratch when the layer is a lane chain*/,
@@ -833,7 +756,11 @@ __device__ __forceinline__ void check_node_hazard(uint8_t* __restrict__ lds, con
     // Lane-chain layers of the low degree classes: the pair's two LLR bytes are read WITH the regular entries (one LDS round trip for all
     // seven instead of three in a row on the wave that walks the chain afterwards). A value read here is used only by the rows for which
     // no earlier row of this layer writes that bit: entry 0 of the rows below 360 - block, entry 1 of the heads.
-    constexpr bool kEarlyPair = CLASS8 && DEG <= DVBS2_EARLY_PAIR_MAXDEG && NC == 2 && !LR && !PR && CHAINOK && DEG <= DVBS2_FWALK_MAXDEG && !V2P;
+    // Measured (round 4, interleaved A/B, whole tables): degree <= 8: B4 +0.7 %, 9/20 ... S2_TABLE_B3 +1.8 %, B1 +1 %, B2 -0.6 %; degree class
+    // 12: 3/5 normal 0, 2/3 normal and T2 2/3 -4 % (register allocation of their one-frame builds) -- and the degree-5..8 instantiations
+    // INSIDE the class-12 kernel cost its tables 3-7 % as well (S2X 99/180 ... S2X_TABLE_B4 -7 %), so the switch is the kernel's class
+    // (CLASS8 = DMAX <= 8), not the check degree.
+    constexpr bool kEarlyPair = CLASS8 && NC == 2 && !LR && !PR && CHAINOK && !V2P;
     int Lh01[2] = { 0x80, 0x80 };
     int p0 = 0, p1 = 0;
     const int jjb = jj + lb, jjb360 = jjb - kM;
@@ -859,7 +786,7 @@ __device__ __forceinline__ void check_node_hazard(uint8_t* __restrict__ lds, con
             for (int k = NC; k < DEG; k++) Lb[k] = lds_rd(ad[k]);
 #pragma unroll
             for (int j = NPH; j < NP; j++) {
-                const uint32_t M = msg_pair16<P6>(mw, j);
+                const uint32_t M = msg_pair16(mw, j);
                 const uint32_t hi = (ODD && j == NP - 1) ? (TC ? 0x00u : 0x80u) : (uint32_t)Lb[2 * j + 1];
                 const uint32_t L = __builtin_amdgcn_perm(hi, (uint32_t)Lb[2 * j], 0x040c000cu) ^ kObPair<TC>;
                 dP[j] = __builtin_elementwise_sub_sat(as_v2s(L), as_v2s(M));
@@ -937,7 +864,7 @@ __device__ __forceinline__ void check_node_hazard(uint8_t* __restrict__ lds, con
     __builtin_amdgcn_s_setprio(3);
     bool lane_chain = false;
     // (the low-register form has room for it at every degree)
-    constexpr bool kLaneChainBuilt = NC == 2 && (LR || DEG <= (V2P ? kLaneChainMaxDegV2p : kLaneChainMaxDeg)) && !PR && CHAINOK;
+    constexpr bool kLaneChainBuilt = NC == 2 && (LR || V2P || DEG <= kLaneChainMaxDeg) && !PR && CHAINOK;
     if constexpr (kLaneChainBuilt) lane_chain = tab != nullptr; // wave-uniform (header bit 12)
     if constexpr (kLaneChainBuilt) if (lane_chain) {
         // LANE CHAIN (one hazard pair, block <= 128, host-ordered so that entry 0's bit of row r is entry 1's bit of
@@ -960,7 +887,7 @@ __device__ __forceinline__ void check_node_hazard(uint8_t* __restrict__ lds, con
         // VGPRs; B4 113.2 k -> 112.4 k, the 80-VGPR and one-frame builds -4 ... -8 %. It stays in the packed chain node.)
         lds_byte_t* ulog = reinterpret_cast<lds_byte_t*>(tab + kM + block); // after the per-row records (360 rows + one block of padding)
         int chained = 0x80;
-        // Round 4, degree class 8 (DVBS2_FWALK): the walk on exact small integers in float with the operands of FOUR rows in flight. The
+        // Round 4, degree class 8: the walk on exact small integers in float with the operands of FOUR rows in flight. The
         // integer step is ~17 dependent VALU instructions and one record read ahead: a lone wave needs ~110 cycles per row either way
         // (issue ~4 cycles per instruction, an LDS read 100-130), 1.4 k cycles for the 8-10 rows of table B4's chains. In float the step is
         // six instructions (fma, two med3 with a negated operand, sub, add, clamp -- the packed chain node's step, check_node_chain_v2)
@@ -968,7 +895,9 @@ __device__ __forceinline__ void check_node_hazard(uint8_t* __restrict__ lds, con
         //   record of row r: { sigma, -sigma m1, P + 1, inp0 + 128 }  (sigma = +-1: partial sign; m1: entry 1's message, offset binary;
         //   P: partial minimum); incoming entry-1 LLR c (offset binary):  x = sigma (c - m1), w = clamp(x, -(P+1), P+1),
         //   out = w - sgn(w) = sgn(x) min(P, max(|x| - 1, 0)),  c' = clamp(inp0 + 128 + out, 0, 255)
-        constexpr bool kFloatWalk = (DVBS2_FWALK != 0) && DEG <= DVBS2_FWALK_MAXDEG && !LR && !PR;
+        // Largest check degree that walks in float -- measured (round 4, interleaved A/B): 8 -> B2 +8 %, B4 +0.5 %; 12 -> 3/5 normal +1 %,
+        // T2 2/3 +4 %, the one-frame class-12 tables +5 %; 16 -> B7 -1 %; 28 -> 8/9 normal -8 %, 5/6 -3 %.
+        constexpr bool kFloatWalk = DEG <= kFwalkMaxDeg && !LR && !PR;
         lds_v4f_t* frec = lds_align16<lds_v4f_t>(tab);                                                   // [360 + block]
         lds_f32_t* flog = reinterpret_cast<lds_f32_t*>(frec) + 4 * (kM + kChainMaxBlock);              // [360 + block]
         auto publish = [&]() {
@@ -984,10 +913,7 @@ __device__ __forceinline__ void check_node_hazard(uint8_t* __restrict__ lds, con
         // (degrees above 20 without the low-register form keep the round-2 order -- heads | barrier | publishing | barrier | walk |
         // barrier | completion | barrier --: reading entry 0 inside the first phase costs the degree class 28 sixteen more spilled
         // registers and table B10 7 %)
-#ifndef DVBS2_TWO_BARRIER_V2P
-#define DVBS2_TWO_BARRIER_V2P 0 // experiments (round 6): the two-barrier order also in the packed hazard nodes of degree > 20
-#endif
-        constexpr bool kTwoBarrier = LR || DEG <= 20 || (V2P && DVBS2_TWO_BARRIER_V2P != 0);
+        constexpr bool kTwoBarrier = LR || DEG <= 20;
         const bool orig0 = work && (kTwoBarrier ? jj + block < kM : jj < block); // entry 0 still holds its value from before the layer (every head is one: block <= 128)
         if (orig0) {
             const int L0 = kEarlyPair ? Lh01[0] : lds_rdx<TC>(ad[0]);
@@ -1020,7 +946,7 @@ __device__ __forceinline__ void check_node_hazard(uint8_t* __restrict__ lds, con
         DVBS2_PH(1); // chain heads + publishing
         lds_barrier();
         DVBS2_PH(3); // barrier
-        if constexpr (kFloatWalk && CLASS8 && DEG <= DVBS2_WALK_ABS_MAXDEG) { if (head) {
+        if constexpr (kFloatWalk && CLASS8) { if (head) {
             // absolute LDS addresses, ONE running address for the records and one for the log (through typed pointers the compiler kept
             // eight offsets and added the array base at every access: four address instructions per step of a lone wave)
             int ra = (int)(uint32_t)(size_t)(frec + jj + block), la = (int)(uint32_t)(size_t)(flog + jj + block);
@@ -1136,7 +1062,7 @@ __device__ __forceinline__ void check_node_hazard(uint8_t* __restrict__ lds, con
     if constexpr (kTlcBuilt) tlc = block2 > 0 && tab != nullptr; // wave-uniform
     if constexpr (kTlcBuilt) if (tlc) {
         lds_byte_t* ulog = reinterpret_cast<lds_byte_t*>(tab + kM + block);
-        constexpr bool kTlcFloat = V2P && DMAXV >= DVBS2_TLC_FWALK_MIN_DMAX;
+        constexpr bool kTlcFloat = V2P && DMAXV >= kTlcFwalkMinDmax;
         lds_v4f_t* trec = lds_align16<lds_v4f_t>(tab);                                      // kTlcFloat: [360 + block] operand records { sigma, -sigma m1, P + 1, inp0 + 128 }
         lds_f32_t* tlog = reinterpret_cast<lds_f32_t*>(trec) + 4 * (kM + kChainMaxBlock); //            [360 + block] the value that arrived at a row
         int chained = 0x80;
@@ -1367,7 +1293,7 @@ __device__ __forceinline__ void check_node_hazard(uint8_t* __restrict__ lds, con
         // same wavefront (LDS operations of a wave execute in program order)
         if ((start >> 6) != ((start + 2 * block - 1) >> 6)) lds_barrier();
     }
-    if (!lane_chain || !(LR || DEG <= 20 || (V2P && DVBS2_TWO_BARRIER_V2P != 0))) lds_barrier(); // (uniform; the last phase of a two-barrier lane chain and the outputs below touch different bits)
+    if (!lane_chain || !(LR || DEG <= 20)) lds_barrier(); // (uniform; the last phase of a two-barrier lane chain and the outputs below touch different bits)
     DVBS2_PH(6); // ordered steps of the block scheme + closing barrier / completion of the chain rows
     if constexpr (V2P) {
         // LAST PHASE, packed: the ordered entries enter the packed domain as pairs [inp << 8] (what they read in their step is final), the
@@ -1410,7 +1336,7 @@ __device__ __forceinline__ void check_node_hazard(uint8_t* __restrict__ lds, con
             }
             __builtin_amdgcn_s_setprio(3);
             if (ODD) R[NP - 1] &= 0x0000ffffu;
-            msg_pack16<P6, NP, DMAXV / 4>(R, nm);
+            msg_pack16<NP>(R, nm);
         }
         DVBS2_PH(7);
         return;
@@ -1479,7 +1405,7 @@ __device__ __forceinline__ void check_node_hazard(uint8_t* __restrict__ lds, con
         DVBS2_DEG_CASE(27) DVBS2_DEG_CASE(28) DVBS2_DEG_CASE(29) DVBS2_DEG_CASE(30) DVBS2_DEG_CASE(31) DVBS2_DEG_CASE(32) \
         default: break; }
 
-#define DVBS2_V2_CASE(D) case D: if constexpr (D >= 3 && D <= DMAX && D > DMAX - 8) { check_node_v2<(D >= 3 ? D : 3), DMAX, P6, TC>(ent, jj + lb, mw, nm, prefetch); } break;
+#define DVBS2_V2_CASE(D) case D: if constexpr (D >= 3 && D <= DMAX && D > DMAX - 8) { check_node_v2<(D >= 3 ? D : 3), DMAX, TC>(ent, jj + lb, mw, nm, prefetch); } break;
 #define DVBS2_V2_SWITCH switch (deg) { \
         DVBS2_V2_CASE(3) DVBS2_V2_CASE(4) DVBS2_V2_CASE(5) DVBS2_V2_CASE(6) DVBS2_V2_CASE(7) DVBS2_V2_CASE(8) \
         DVBS2_V2_CASE(9) DVBS2_V2_CASE(10) DVBS2_V2_CASE(11) DVBS2_V2_CASE(12) DVBS2_V2_CASE(13) DVBS2_V2_CASE(14) \
@@ -1488,7 +1414,7 @@ __device__ __forceinline__ void check_node_hazard(uint8_t* __restrict__ lds, con
         DVBS2_V2_CASE(27) DVBS2_V2_CASE(28) DVBS2_V2_CASE(29) DVBS2_V2_CASE(30) DVBS2_V2_CASE(31) DVBS2_V2_CASE(32) \
         default: break; }
 
-#define DVBS2_CHAIN_CASE(D) case D: if constexpr (D >= 4 && D <= DMAX && D > DMAX - 8) { check_node_chain_v2<(D >= 4 ? D : 4), DMAX, P6, TC>(ent, jj, jj + lb, work, block, mw, nm, htab16, hb_ctr, hb_epoch, hb_lane); } break;
+#define DVBS2_CHAIN_CASE(D) case D: if constexpr (D >= 4 && D <= DMAX && D > DMAX - 8) { check_node_chain_v2<(D >= 4 ? D : 4), DMAX, TC>(ent, jj, jj + lb, work, block, mw, nm, htab16, hb_ctr, hb_epoch, hb_lane); } break;
 #define DVBS2_CHAIN_SWITCH switch (deg) { \
         DVBS2_CHAIN_CASE(4) DVBS2_CHAIN_CASE(5) DVBS2_CHAIN_CASE(6) DVBS2_CHAIN_CASE(7) DVBS2_CHAIN_CASE(8) \
         DVBS2_CHAIN_CASE(9) DVBS2_CHAIN_CASE(10) DVBS2_CHAIN_CASE(11) DVBS2_CHAIN_CASE(12) DVBS2_CHAIN_CASE(13) DVBS2_CHAIN_CASE(14) \
@@ -1502,7 +1428,7 @@ __device__ __forceinline__ void check_node_hazard(uint8_t* __restrict__ lds, con
 // state made the compiler spill the regular entries of EVERY four- and eight-entry layer around it, 9/10 normal's multi-pair
 // layers went from 12-17 k to 25-34 k cycles.)
 #define DVBS2_HAZ_CALL1(D, NCV, LRV, TLCV) { \
-        if (layer0) check_node_hazard<D, NCV, true, false, false, HZ2, LRV, TLCV, (MINW == 1), (DMAX <= 8), false, 0, false, TC>(lds_all, ent, jj, lb, work, block, block2, mw, nm, 0, nullptr, htab, hb_ctr, hb_epoch, hb_lane, hz_ph); else { if constexpr (!kPure) check_node_hazard<D, NCV, false, false, false, HZ2, LRV, TLCV, (MINW == 1), (DMAX <= 8), false, 0, false, TC>(lds_all, ent, jj, lb, work, block, block2, mw, nm, 0, nullptr, htab, hb_ctr, hb_epoch, hb_lane, hz_ph); } }
+        if (layer0) check_node_hazard<D, NCV, true, false, false, HZ2, LRV, TLCV, (MINW == 1), (DMAX <= 8), false, 0, TC>(lds_all, ent, jj, lb, work, block, block2, mw, nm, 0, nullptr, htab, hb_ctr, hb_epoch, hb_lane, hz_ph); else { if constexpr (!kPure) check_node_hazard<D, NCV, false, false, false, HZ2, LRV, TLCV, (MINW == 1), (DMAX <= 8), false, 0, TC>(lds_all, ent, jj, lb, work, block, block2, mw, nm, 0, nullptr, htab, hb_ctr, hb_epoch, hb_lane, hz_ph); } }
 #define DVBS2_HAZ_CALL(D, NCV) { if constexpr (D - 2 >= NCV) { \
         if constexpr (kTlc<DMAX, HZ2> && !SOFT && MINW == 1 && (NCV == 4 || NCV == 8)) { if (block2 > 0 && htab != nullptr) DVBS2_HAZ_CALL1(D, NCV, (DMAX >= kTlcLowRegMinDmax), true) else DVBS2_HAZ_CALL1(D, NCV, false, false) } \
         else DVBS2_HAZ_CALL1(D, NCV, false, false) } }
@@ -1510,7 +1436,7 @@ __device__ __forceinline__ void check_node_hazard(uint8_t* __restrict__ lds, con
         if (nc == 2) DVBS2_HAZ_CALL((D >= 4 ? D : 4), 2) else if (nc == 4) DVBS2_HAZ_CALL((D >= 4 ? D : 4), 4) else { if constexpr (HZ2 && DMAX <= kMaxHazard12Dmax) { if (nc == 8) DVBS2_HAZ_CALL((D >= 4 ? D : 4), 8) else DVBS2_HAZ_CALL((D >= 4 ? D : 4), 12) } else DVBS2_HAZ_CALL((D >= 4 ? D : 4), 8) } } break;
 // The same with the packed first / last phase (check_node_hazard<..., V2P>): regular layers i > 0 of the builds with packed nodes whose
 // wave record the host laid out in the packed format (header bit 14); the ordered phase is the plain one, instantiation for instantiation.
-#define DVBS2_HAZP_CALL1(D, NCV, TLCV) { check_node_hazard<D, NCV, false, false, false, HZ2, false, TLCV, (MINW == 1), (DMAX <= 8), true, DMAX, P6, TC>(lds_all, ent, jj, lb, work, block, block2, mw, nm, 0, nullptr, htab, hb_ctr, hb_epoch, hb_lane, hz_ph); }
+#define DVBS2_HAZP_CALL1(D, NCV, TLCV) { check_node_hazard<D, NCV, false, false, false, HZ2, false, TLCV, (MINW == 1), (DMAX <= 8), true, DMAX, TC>(lds_all, ent, jj, lb, work, block, block2, mw, nm, 0, nullptr, htab, hb_ctr, hb_epoch, hb_lane, hz_ph); }
 #define DVBS2_HAZP_CALL(D, NCV) { if constexpr (D - 2 >= NCV) { \
         if constexpr (kTlc<DMAX, HZ2> && !SOFT && MINW == 1 && (NCV == 4 || NCV == 8)) { if (block2 > 0 && htab != nullptr) DVBS2_HAZP_CALL1(D, NCV, true) else DVBS2_HAZP_CALL1(D, NCV, false) } \
         else DVBS2_HAZP_CALL1(D, NCV, false) } }
@@ -1574,8 +1500,7 @@ __device__ __forceinline__ uint32_t hw_cu_index()
 }
 constexpr int kCuSlots = 16 * 8 * 2 * 16;
 
-template <int DMAX, bool TIMING, int MINW = 1, bool V2 = false, bool SOLO = false, bool CHAIN = false /*V2 = false only: the packed chain node alone*/,
-          bool HZ2 = false, bool SOFT = false /*SOFT: frame barriers in software -- a build of its own: the barrier state in every barrier of
+template <int DMAX, bool TIMING, int MINW = 1, bool V2 = false, bool SOLO = false, bool HZ2 = false, bool SOFT = false /*SOFT: frame barriers in software -- a build of its own: the barrier state in every barrier of
                              every build cost the 80-VGPR build 25-30 % (54 -> 199 spilled VGPRs) and the degree classes 20..32 4-10 %*/
           /*HZ2: heavy hazard layers: twelve ordered entries, two-level walk (check_node_hazard); a build of its own because the
                              extra register state costs the degree classes 28 and 32 ten percent everywhere else (B11, S2X B21)*/>
@@ -1602,14 +1527,12 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
     constexpr int RS = rec_stride(DMAX);
     constexpr int RSW = V2 ? 6 * rec_stride_wave(DMAX) : rec_stride(DMAX); // dwords from one layer's sweep record to the next
     constexpr int MW = DMAX / 4; // message dwords per check (fixed per kernel variant)
-    // "pure" packed builds (DVBS2_V2_PURE_MIN_DMAX; hardware barriers only): the plain nodes are compiled for layer 0 only -- the plain hazard
+    // "pure" packed builds (v2_pure_class): the plain nodes are compiled for layer 0 only -- the plain hazard
     // nodes of the degree class 32 cost the packed ones around them 5 % through register allocation --; the host runs such a build only
     // for tables whose every (layer > 0, wave) record fits the packed format (ldpc_hip.hip)
-#ifndef DVBS2_V2_PURE_SOFT
-#define DVBS2_V2_PURE_SOFT 1 // also the software-barrier packed build of the pure classes (S2X 154/180 131.8 -> 133.9 k with ten fix slots, round 5)
-#endif
-    constexpr bool kPure = V2 && (!SOFT || DVBS2_V2_PURE_SOFT) && v2_pure_class(DMAX);
-    constexpr bool TC = V2 && DMAX <= DVBS2_TC_MAX_DMAX;        // LLR bytes in LDS as two's complement (see lds_rdx)
+    // (also the software-barrier packed build of the pure classes: S2X 154/180 131.8 -> 133.9 k with ten fix slots, round 5)
+    constexpr bool kPure = V2 && v2_pure_class(DMAX);
+    constexpr bool TC = V2 && DMAX <= kTcMaxDmax;        // LLR bytes in LDS as two's complement (see lds_rdx)
     constexpr uint32_t kObState = TC ? 0x80808080u : 0u;        // LDS bytes <-> the offset-binary state in HBM
     int solo_tid = (int)threadIdx.x;
     int solo_slot = -1, solo_pat = 0;
@@ -1739,40 +1662,13 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
     constexpr int kLayerBytes = MW * kMsgStride * 4;
 #define MSG_LD(soff, w, r4) __builtin_amdgcn_raw_buffer_load_b32(mrs, (r4), (soff) + (w) * (kMsgStride * 4), 0)
 #define MSG_ST(v, soff, w, r4) __builtin_amdgcn_raw_buffer_store_b32((v), mrs, (r4), (soff) + (w) * (kMsgStride * 4), 0)
-    // six-bit message fields (msg_pair16): word w of a check of degree dg holds p6_fields(dg, w) fields; one or two fields are a
-    // 16-bit access (row * 2 inside the word's 1536-byte slot), none is no access at all
-#ifndef DVBS2_P6_DW
-#define DVBS2_P6_DW 3 // fields from which a word is a dword access (experiments: 1 = never use 16-bit accesses)
-#endif
-    // measured (table B4, 4096 frames): 107 k frames/s with byte messages, 93 k with six-bit fields at the same traffic (dword accesses
-    // only), 85-91 k with the traffic actually reduced by a quarter: the unpacking costs more than the bytes bring -- the regular layers
-    // are limited by VALU issue and memory traffic at the same time. Kept behind this switch, off.
-#ifndef DVBS2_P6
-#define DVBS2_P6 0
-#endif
-    constexpr bool P6 = DVBS2_P6 != 0;
-    auto msg_load = [&](uint32_t* dst, int soff, int r4, bool packed, int dg) {
+    auto msg_load = [&](uint32_t* dst, int soff, int r4) {
 #pragma unroll
-        for (int w = 0; w < MW; w++) {
-            if (P6 && packed) {
-                const int nf = dg - 5 * w; // uniform
-                if (nf >= DVBS2_P6_DW) dst[w] = MSG_LD(soff, w, r4);
-                else if (nf >= 1) dst[w] = (uint32_t)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(mrs, r4 >> 1, soff + w * (kMsgStride * 4), 1 /* sc0: a sub-dword store does not update a line held in the vector L1 */);
-                else dst[w] = 0u;
-            }
-            else dst[w] = MSG_LD(soff, w, r4);
-        }
+        for (int w = 0; w < MW; w++) dst[w] = MSG_LD(soff, w, r4);
     };
-    auto msg_store = [&](const uint32_t* src, int soff, int r4, bool packed, int dg) {
+    auto msg_store = [&](const uint32_t* src, int soff, int r4) {
 #pragma unroll
-        for (int w = 0; w < MW; w++) {
-            if (P6 && packed) {
-                const int nf = dg - 5 * w;
-                if (nf >= DVBS2_P6_DW) MSG_ST(src[w], soff, w, r4);
-                else if (nf >= 1) __builtin_amdgcn_raw_buffer_store_b16((unsigned short)src[w], mrs, r4 >> 1, soff + w * (kMsgStride * 4), 0);
-            }
-            else MSG_ST(src[w], soff, w, r4);
-        }
+        for (int w = 0; w < MW; w++) MSG_ST(src[w], soff, w, r4);
     };
     // bnl = 0 before the first update (layered_decoder.hh:27-31,149): a frame's first sweep (it == 0, in the first pass or
     // when a frame that stopped at once is resumed) takes offset-binary zero bytes instead of loading them -- no memset
@@ -1797,7 +1693,7 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
             // per build, measured (round 6, interleaved A/B of whole tables against the edge-by-edge loop): 9/10 normal +4.7 %, 5/6 +4.0 %, 8/9 +2.0 %,
             // 4/5 +1.3 %, S2X 25/36 +1.6 %, 1/4 normal +1.0 %, short 3/5 (the 80-VGPR build) +45 %; 3/4 normal -2.5 % and short 2/3 -1.0 % (class 16),
             // S2X 154/180 -1.8 % (class 32 with software barriers), B4 and short 1/4 unchanged
-            constexpr bool kPretestChunk = (DVBS2_PRETEST_CHUNK != 0) && DMAX != 16 && !(DMAX == 32 && SOFT);
+            constexpr bool kPretestChunk = DMAX != 16 && !(DMAX == 32 && SOFT);
             if constexpr (kPretestChunk) {
             // Round 6: FOUR edges per trip -- their eight record words in one scalar load, the four LDS reads in flight together. Edge by
             // edge the loop paid one scalar-cache round trip and one LDS round trip per edge (~300 cycles x 30 edges of a 9/10 normal
@@ -1832,11 +1728,7 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
             if (__ballot(bad_pre) != 0 && lane == 0) flags[2] = 1;
         }
         lds_barrier();
-#ifdef DVBS2_EXP_ALWAYS_FULL // timing experiment (same results): the full test after every update, whatever the pre-test says
-        const bool need_full = need_synd;
-#else
         const bool need_full = need_synd && flags[2] == 0;
-#endif
         if (tid == 0) flags[3] = need_full ? 1 : 0;
         lds_barrier();
         const bool full_any = flags[3] != 0 || (!soft_bar && !SOLO && other_flags[3] != 0); // uniform over the barrier domain
@@ -1923,7 +1815,7 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
         // timing builds: cycles per phase of the hazard nodes, frame 0, lane 0 of waves 0 and 5 (slots 256.. and 272.. after the per-layer sums)
         unsigned long long* const hz_ph = (TIMING && tdbg && f == 0 && (tid == 0 || tid == 320)) ? tdbg + (size_t)n_frames * 48 + 256 + (tid ? 16 : 0) : nullptr;
         uint32_t pre[MW]; // messages of the next layer for check tid, loaded one layer ahead
-        constexpr bool kWaitStore = (DVBS2_WAIT_BEFORE_STORE != 0) && !SOFT;
+        constexpr bool kWaitStore = !SOFT; // (DVBS2_WAIT_VM0)
         if (work) {
 #pragma unroll
             for (int w = 0; w < MW; w++) {
@@ -1937,41 +1829,44 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
         // (Rounds 1-3 carried every 8th word of the large records over from the previous layer; round 4 measured none -- the header words only --
         // 1-9 % faster on 16 of 17 tables of the classes 16-32: each carried word was its own `s_load_dword; s_waitcnt lgkmcnt(0); v_writelane`
         // at every layer head, and the records of a table (5-7 KB) stay in the scalar cache anyway.)
-        constexpr int PF = DMAX <= DVBS2_PF_SMALL_MAX_DMAX ? 1 : 2 * DMAX;
+        // Up to kPfSmallMaxDmax the whole record is double-buffered in scalar registers. Measured: class 8 loses 2-3 % without it
+        // (B4 119.7 -> 117.1 k), class 12 GAINS 1-3 % without it (3/5, 2/3 normal, S2X 11/20, T2 2/3, short 2/3; short 3/5 -0.7 %)
+        constexpr int kPfSmallMaxDmax = 8;
+        constexpr int PF = DMAX <= kPfSmallMaxDmax ? 1 : 2 * DMAX;
         // the sweep reads the records of its own WAVE (check_node_v2): wrecs[(layer * 6 + wave) * RS]
         const uint32_t* wr = V2 ? wrecs + (size_t)wave_u * rec_stride_wave(DMAX) : recs; // builds without packed nodes read the per-layer records
-        uint32_t nhdr = wr[0], ninfo = wr[1]; // word 1: message format of the NEXT layer for this wave (degree | packed << 8)
+        // (word 1 carries nothing: it is loaded with the header only for the first record, which keeps the scalar loads of the kernel as measured)
+        uint32_t nhdr = wr[0], nw1 = wr[1];
         uint32_t nent[2 * DMAX];
 #pragma unroll
         for (int k = 0; k < 2 * DMAX; k += PF) nent[k] = wr[4 + k]; // (PF = 2 DMAX: word 0 only, never used)
         DVBS2_WAIT_VM0(); // (the first layer's messages: once per sweep, so that inside the loop no path has a load pending at a layer boundary)
-#if DVBS2_WAIT_RECORDS
         // the same for the first layer's RECORD: with its scalar loads pending on the path into the loop the compiler waits for them at the
         // first use of the header -- behind the next record's prefetch, which every iteration then waits for as soon as it has issued it
         // (an empty asm statement that "uses" the loaded words: the compiler has to complete the loads in front of it; an explicit s_waitcnt
-        // alone does not hold them -- loads of constant memory are moved across it)
-        asm volatile("" : "+s"(nhdr), "+s"(ninfo), "+s"(nent[0]));
-#endif
+        // alone does not hold them -- loads of constant memory are moved across it). First measured on the plain class-8 build: B4 119.6 ->
+        // 115.9 k without it; re-measured once B4 ran the packed one-frame build: B4 133.2 -> 134.5 k, 2/5 normal +0.7 %, 3/5 +1 %, others +-0.5 %.
+        asm volatile("" : "+s"(nhdr), "+s"(nw1), "+s"(nent[0]));
         for (int i = 0; i < q; i++) {
-            const uint32_t hdr = nhdr, info = ninfo;
-            const bool npacked = (info >> 8) & 1u; const int ndeg = (int)(info & 0xffu);
+            const uint32_t hdr = nhdr;
             uint32_t ent[2 * DMAX];
 #pragma unroll
             for (int k = 0; k < 2 * DMAX; k++) ent[k] = (PF <= 2 * DMAX - 1 && k % PF == 0) ? nent[k] : wr[(size_t)i * RSW + 4 + k];
             const uint32_t* nrec = wr + (size_t)(i + 1 < q ? i + 1 : 0) * RSW;
             auto prefetch = [&](uint32_t after) {
                 const uint32_t* p = nrec; (void)after;
-                nhdr = p[0]; ninfo = p[1];
+                nhdr = p[0];
                 if constexpr (PF <= 2 * DMAX - 1) {
 #pragma unroll
                     for (int k = 0; k < 2 * DMAX; k += PF) nent[k] = p[4 + k];
                 }
             };
             // a packed-node layer (bit 13) may issue these loads from inside the node; the others here
-            // Degree classes up to DVBS2_PREFETCH_AFTER_BARRIER_MAX_DMAX issue them BEHIND the layer's barrier: in front of it the wave waits
-            // for them (lgkmcnt(0) of the barrier and of the first use of the header) as soon as it has issued them. Measured: B4 +0.7 %,
-            // 1/3 normal +1.5 %, S2X 9/20 +1.2 %, 1/4 normal +1.4 %; the classes 12-32 lose up to 5 % (S2X_TABLE_B16) -- class 8 only.
-            constexpr bool kPab = DMAX <= DVBS2_PREFETCH_AFTER_BARRIER_MAX_DMAX;
+            // Degree classes up to kPabMaxDmax issue them BEHIND the layer's barrier: in front of it the wave waits for them (lgkmcnt(0)
+            // of the barrier and of the first use of the header) as soon as it has issued them. Measured: B4 +0.7 %, 1/3 normal +1.5 %,
+            // S2X 9/20 +1.2 %, 1/4 normal +1.4 %; the classes 12-32 lose up to 5 % (S2X_TABLE_B16) -- class 8 only.
+            constexpr int kPabMaxDmax = 8;
+            constexpr bool kPab = DMAX <= kPabMaxDmax;
             if constexpr (!kPab) prefetch(0u);
             const int deg = (int)(hdr & 0xffu) + 2;
             const int nc = (int)((hdr >> 8) & 0xfu);
@@ -1994,10 +1889,10 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
                     uint32_t mw[MW], nm[MW];
 #pragma unroll
                     for (int w = 0; w < MW; w++) mw[w] = zero_msgs ? (v2 ? 0u : 0x80808080u) : pre[w];
-                    if (i + 1 < q && !zero_msgs) msg_load(pre, mso + kLayerBytes, row4, npacked, ndeg);
+                    if (i + 1 < q && !zero_msgs) msg_load(pre, mso + kLayerBytes, row4);
                     if constexpr (V2) { if (v2) { DVBS2_V2_SWITCH } else DVBS2_DEG_SWITCH } else DVBS2_DEG_SWITCH
                     DVBS2_WAIT_VM0();
-                    msg_store(nm, mso, row4, v2, deg);
+                    msg_store(nm, mso, row4);
                 }
                 TSTAMP(tC); tm_body += tC - tB;
                 if (TIMING && tdbg && f == 0 && tid == 0) tdbg[(size_t)n_frames * 48 + i] += tC - tA; // per-layer cycles of frame 0, wave 0 (incl. its barrier)
@@ -2005,33 +1900,24 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
                 if (nc != kHazardWalk) {
                     // sequential-order hazard inside the layer: check_node_hazard (every thread takes every barrier)
                     const int jj = row;
-                    // hv2: packed single-pair chain (check_node_chain_v2): two's complement messages. In a build without the packed regular
-                    // node (CHAIN) the layer's per-wave record is fetched here, from wrecs, when the per-layer record says so (bit 14).
-                    const bool hv2 = (V2 && ((hdr >> 13) & 1u)) || (!V2 && CHAIN && ((hdr >> 14) & 1u));
-                    if constexpr (!V2 && CHAIN) {
-                        if (hv2) {
-                            const uint32_t* cw = wrecs + ((size_t)i * 6 + wave_u) * rec_stride_wave(DMAX) + 4;
-#pragma unroll
-                            for (int k = 0; k < 2 * DMAX; k++) ent[k] = cw[k];
-                        }
-                    }
+                    // hv2: packed single-pair chain (check_node_chain_v2): two's complement messages
+                    const bool hv2 = V2 && ((hdr >> 13) & 1u);
                     uint32_t mw[MW], nm[MW];
 #pragma unroll
                     for (int w = 0; w < MW; w++) mw[w] = (work && !zero_msgs) ? pre[w] : (hv2 ? 0u : 0x80808080u);
-                    if (work && i + 1 < q && !zero_msgs) msg_load(pre, mso + kLayerBytes, row4, npacked, ndeg);
+                    if (work && i + 1 < q && !zero_msgs) msg_load(pre, mso + kLayerBytes, row4);
                     // hvp: the generic hazard node with the packed first / last phase (header bit 14 of this wave's record; every wave of the
                     // layer runs the same ordered phase, whichever form its own record has)
                     const bool hvp = V2 && v2p_class(DMAX) && ((hdr >> 14) & 1u);
-                    if constexpr ((V2 || CHAIN) && DMAX <= 16) { // (the chain node's register state costs the high-degree builds more than it saves: not built there)
-                        if (hv2 && !hvp) {
+                    if constexpr (V2 && DMAX <= 16) { // (the chain node's register state costs the high-degree builds more than it saves: not built there)
+                        if (hv2) {
                             lds_u32_t* htab16 = lds_align16<lds_u32_t>(sv); // 16-byte records
                             DVBS2_CHAIN_SWITCH
-                        } else if constexpr (V2 && v2p_class(DMAX)) { if (hvp) { DVBS2_HAZP_SWITCH } else DVBS2_HAZ_SWITCH }
-                        else DVBS2_HAZ_SWITCH
+                        } else DVBS2_HAZ_SWITCH
                     } else if constexpr (V2 && v2p_class(DMAX)) { if (hvp) { DVBS2_HAZP_SWITCH } else DVBS2_HAZ_SWITCH }
                     else DVBS2_HAZ_SWITCH
                     DVBS2_WAIT_VM0(); // (on every path, so that nothing is pending behind it whatever the branch)
-                    if (work) msg_store(nm, mso, row4, hv2, deg);
+                    if (work) msg_store(nm, mso, row4);
                 } else {
                     // too many hazard entries: the first wave of the half walks the 360 checks alone in ascending
                     // chunks of min(B_i, 64) (LDS operations of one wave execute in order: no barrier between chunks)
@@ -2050,8 +1936,8 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
                         }
                     }
                     lds_barrier();
-                    if (work && i + 1 < q && !zero_msgs) msg_load(pre, mso + kLayerBytes, row4, npacked, ndeg);
-                    DVBS2_WAIT_VM0(); // (rare path; keeps "nothing pending at the end of a layer" true on EVERY path, see DVBS2_WAIT_BEFORE_STORE)
+                    if (work && i + 1 < q && !zero_msgs) msg_load(pre, mso + kLayerBytes, row4);
+                    DVBS2_WAIT_VM0(); // (rare path; keeps "nothing pending at the end of a layer" true on EVERY path, see DVBS2_WAIT_VM0)
                 }
                 TSTAMP(tC); tm_conf += tC - tB;
                 if (TIMING && tdbg && f == 0 && tid == 0) tdbg[(size_t)n_frames * 48 + i] += tC - tA;
@@ -2079,32 +1965,40 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
 
 
 // ---- host-side launch interface of one kernel variant (defined in ldpc_inst_*.hip) ----
+// The build of the sweep kernel a handle runs, decided once per table by the host (ldpc_hip.hip). The classic kernel's builds exist
+// in the degree classes the k*Built rules below give; the parity-in-records builds (ldpc_kernel_pr.hpp) in the class 8 only.
+enum class LdpcBuild : uint8_t {
+    plain,       // pair workgroups, scalar nodes
+    packed,      // pair workgroups with the packed nodes (check_node_v2, check_node_chain_v2)
+    solo,        // one frame per workgroup (kSoloBuilt)
+    packed_solo,
+    hz2,         // the heavy-hazard paths (kHz2Built)
+    soft,        // software frame barriers (kSoftBuilt)
+    packed_soft,
+    dense,       // 80 VGPRs, two workgroups per CU (kDenseBuilt)
+    pr,          // parity in records: two-dword records, plain nodes
+    pr_w1,       //                    one-dword records (check degree <= 4)
+    pr_packed,   //                    two-dword records, packed nodes in the regular middle layers
+};
+constexpr int kLdpcBuilds = (int)LdpcBuild::pr_packed + 1;
+__host__ __device__ constexpr bool is_solo(LdpcBuild b) { return b == LdpcBuild::solo || b == LdpcBuild::packed_solo; }
 struct LdpcLaunch {
     const uint32_t* recs; const uint32_t* wrecs; const int8_t* llr_in; uint8_t* state; uint32_t* msgs; int* iters; int* good; const int* target;
-    int n_frames, N, K, q, cap, stop_on_good; unsigned long long* tdbg;
+    int n_frames, N, K, q, cap, stop_on_good; unsigned long long* tdbg /*non-null: the cycle-stamped build where it exists*/;
     DemapFused dm;
     size_t lds_bytes; hipStream_t stream;
-    bool dense; // the 80-VGPR build of the kernel (two workgroups per CU), see kDenseBuilt
-    bool v2;    // the build with the packed nodes
-    bool solo;  // one frame per workgroup (kSoloBuilt)
-    bool chain; // plain build + packed chain node (kChainBuilt; ignored with v2, which has it anyway)
-    bool hz2;   // plain pair build with the heavy-hazard paths (kHz2Built)
-    bool soft;  // pair build (plain or packed) with software frame barriers (kSoftBuilt)
-    bool pr_packed = false; // parity-in-records kernel (ldpc_kernel_pr.hpp): packed nodes in the regular middle layers (two-dword records; v2 there = one-dword records)
+    LdpcBuild build;
     int* cu_slots;
 };
-template <int DMAX> hipError_t ldpc_variant_prepare(size_t pair_lds_bytes, size_t solo_lds_bytes);
+// prepare: sets the dynamic-LDS limit of every build of the class (one-frame builds take solo_lds_bytes); fails when `build` is not one of them
+template <int DMAX> hipError_t ldpc_variant_prepare(LdpcBuild build, size_t pair_lds_bytes, size_t solo_lds_bytes);
 template <int DMAX> void ldpc_variant_launch(const LdpcLaunch& a);
-#ifndef DVBS2_SOLO_MAX_DMAX
-#define DVBS2_SOLO_MAX_DMAX 16 // (experiments: one-frame workgroups -- 128 VGPRs -- for higher degree classes; round 6 bound, notes/r06_experiments.md)
-#endif
-constexpr int kSoloMaxDmax = DVBS2_SOLO_MAX_DMAX;
+constexpr int kSoloMaxDmax = 16; // one-frame workgroups (128 VGPRs) up to this degree class (round 6 bound, notes/r06_experiments.md)
 template <int DMAX> constexpr bool kSoloBuilt = (DMAX <= kSoloMaxDmax);
-// plain builds with the packed chain node: measured SLOWER than the plain build's own lane chain (B4 107.8 k vs 109.8 k, B5 57.9 k vs
-// 62.2 k frames/s) although its ordered steps cost a third -- the node's register state hurts the rest of the kernel. Not built.
 template <int DMAX> constexpr bool kHz2Built = (DMAX >= 12);
 template <int DMAX> constexpr bool kSoftBuilt = (DMAX >= 20); // pays where layers are long and barriers few (measured: S2X B10, B20, B21, B24)
-template <int DMAX> constexpr bool kChainBuilt = false; // 128 VGPRs: four waves per SIMD must fit while a workgroup starts
+// (Plain builds with the packed chain node measured SLOWER than the plain build's own lane chain -- B4 107.8 k vs 109.8 k, B5 57.9 k vs
+// 62.2 k frames/s -- although its ordered steps cost a third: the node's register state hurts the rest of the kernel. Not built.)
 
 #ifdef DVBS2_LDPC_INSTANTIATE
 // The cycle-stamped variant (DVBS2_TIMING=1, tools/exp_tables.py) is only built for DMAX = 8 -- the headline tables --
@@ -2117,79 +2011,51 @@ template <int DMAX> constexpr bool kTimingBuilt = (DMAX == 8);
 // only the degree class 5..12 survives 80 VGPRs (120 B of scratch); the classes of short 5/6 and 8/9 (DMAX 20, 28) spill so
 // much that they run 8x slower (measured)
 template <int DMAX> constexpr bool kDenseBuilt = (DMAX == 12);
-#ifdef DVBS2_TIMING_HZ2 // experiment builds: cycle stamps in the heavy-hazard build instead of the packed one
-#define DVBS2_TIMING_KERNEL ldpc_layered_kernel<DMAX, true, 1, false, false, false, true>
-#else
-#define DVBS2_TIMING_KERNEL ldpc_layered_kernel<DMAX, true, 1, true, false>
-#endif
-#define DVBS2_KARGS a.recs, a.wrecs, a.llr_in, a.state, a.msgs, a.iters, a.good, a.target, a.n_frames, a.N, a.K, a.q, a.cap, a.stop_on_good
-template <int DMAX> hipError_t ldpc_variant_prepare(size_t pair_lds_bytes, size_t solo_lds_bytes)
+typedef void (*SweepKernel)(const uint32_t*, const uint32_t*, const int8_t*, uint8_t*, uint32_t*, int*, int*, const int*,
+                            int, int, int, int, int, int, unsigned long long*, int*, DemapFused);
+// The builds of the degree class DMAX, in one place: the kernel of `b`, or null where that build is not compiled for this class.
+template <int DMAX> SweepKernel sweep_kernel(LdpcBuild b)
 {
-    auto set = [](const void* k, size_t b) { return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b); };
-    hipError_t e = set((const void*)ldpc_layered_kernel<DMAX, false, 1, false, false>, pair_lds_bytes);
-    if (e == hipSuccess) e = set((const void*)ldpc_layered_kernel<DMAX, false, 1, true, false>, pair_lds_bytes);
-    if constexpr (kSoloBuilt<DMAX>) {
-        if (e == hipSuccess) e = set((const void*)ldpc_layered_kernel<DMAX, false, 1, false, true>, solo_lds_bytes);
-        if (e == hipSuccess) e = set((const void*)ldpc_layered_kernel<DMAX, false, 1, true, true>, solo_lds_bytes);
+    switch (b) {
+    case LdpcBuild::plain: return ldpc_layered_kernel<DMAX, false>;
+    case LdpcBuild::packed: return ldpc_layered_kernel<DMAX, false, 1, true>;
+    case LdpcBuild::solo: if constexpr (kSoloBuilt<DMAX>) return ldpc_layered_kernel<DMAX, false, 1, false, true>; break;
+    case LdpcBuild::packed_solo: if constexpr (kSoloBuilt<DMAX>) return ldpc_layered_kernel<DMAX, false, 1, true, true>; break;
+    case LdpcBuild::hz2: if constexpr (kHz2Built<DMAX>) return ldpc_layered_kernel<DMAX, false, 1, false, false, true>; break;
+    case LdpcBuild::soft: if constexpr (kSoftBuilt<DMAX>) return ldpc_layered_kernel<DMAX, false, 1, false, false, false, true>; break;
+    case LdpcBuild::packed_soft: if constexpr (kSoftBuilt<DMAX>) return ldpc_layered_kernel<DMAX, false, 1, true, false, false, true>; break;
+    case LdpcBuild::dense: if constexpr (kDenseBuilt<DMAX>) return ldpc_layered_kernel<DMAX, false, 6>; break;
+    default: break;
     }
-    if constexpr (kChainBuilt<DMAX>) {
-        if (e == hipSuccess) e = set((const void*)ldpc_layered_kernel<DMAX, false, 1, false, false, true>, pair_lds_bytes);
-        if (e == hipSuccess) e = set((const void*)ldpc_layered_kernel<DMAX, false, 1, false, true, true>, solo_lds_bytes);
-    }
-    if constexpr (kHz2Built<DMAX>) if (e == hipSuccess) e = set((const void*)ldpc_layered_kernel<DMAX, false, 1, false, false, false, true>, pair_lds_bytes);
-    if constexpr (kSoftBuilt<DMAX>) {
-        if (e == hipSuccess) e = set((const void*)ldpc_layered_kernel<DMAX, false, 1, false, false, false, false, true>, pair_lds_bytes);
-        if (e == hipSuccess) e = set((const void*)ldpc_layered_kernel<DMAX, false, 1, true, false, false, false, true>, pair_lds_bytes);
-    }
-    if constexpr (kDenseBuilt<DMAX>) if (e == hipSuccess) e = set((const void*)ldpc_layered_kernel<DMAX, false, 6, false, false>, pair_lds_bytes);
-    if constexpr (kTimingBuilt<DMAX>) if (e == hipSuccess) e = set((const void*)DVBS2_TIMING_KERNEL, pair_lds_bytes);
+    return nullptr;
+}
+// the cycle-stamped build (packed nodes, pair workgroups): launched instead of the handle's build while DVBS2_TIMING is set, where it exists
+template <int DMAX> SweepKernel timing_kernel()
+{
+    if constexpr (kTimingBuilt<DMAX>) return ldpc_layered_kernel<DMAX, true, 1, true>;
+    return nullptr;
+}
+template <int DMAX> hipError_t ldpc_variant_prepare(LdpcBuild build, size_t pair_lds_bytes, size_t solo_lds_bytes)
+{
+    if (!sweep_kernel<DMAX>(build)) return hipErrorInvalidDeviceFunction;
+    auto set = [](SweepKernel k, size_t b) { return hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b); };
+    hipError_t e = hipSuccess;
+    for (int b = 0; b < kLdpcBuilds && e == hipSuccess; b++)
+        if (const SweepKernel k = sweep_kernel<DMAX>((LdpcBuild)b)) e = set(k, is_solo((LdpcBuild)b) ? solo_lds_bytes : pair_lds_bytes);
+    if (const SweepKernel k = timing_kernel<DMAX>(); k && e == hipSuccess) e = set(k, pair_lds_bytes);
     return e;
 }
 template <int DMAX> void ldpc_variant_launch(const LdpcLaunch& a)
 {
-    const dim3 grid((a.n_frames + 1) / 2), block(kThreads);
-    if constexpr (kTimingBuilt<DMAX>) {
-        if (a.tdbg) {
-            hipLaunchKernelGGL((DVBS2_TIMING_KERNEL), grid, block, a.lds_bytes, a.stream, DVBS2_KARGS, a.tdbg, nullptr, a.dm);
-            return;
-        }
-    }
-    if constexpr (kDenseBuilt<DMAX>) {
-        if (a.dense) {
-            hipLaunchKernelGGL((ldpc_layered_kernel<DMAX, false, 6, false, false>), grid, block, a.lds_bytes, a.stream, DVBS2_KARGS, nullptr, nullptr, a.dm);
-            return;
-        }
-    }
-    if constexpr (kHz2Built<DMAX>) {
-        if (a.hz2) {
-            hipLaunchKernelGGL((ldpc_layered_kernel<DMAX, false, 1, false, false, false, true>), grid, block, a.lds_bytes, a.stream, DVBS2_KARGS, nullptr, nullptr, a.dm);
-            return;
-        }
-    }
-    if constexpr (kSoftBuilt<DMAX>) {
-        if (a.soft && !a.solo) {
-            if (a.v2) hipLaunchKernelGGL((ldpc_layered_kernel<DMAX, false, 1, true, false, false, false, true>), grid, block, a.lds_bytes, a.stream, DVBS2_KARGS, nullptr, nullptr, a.dm);
-            else hipLaunchKernelGGL((ldpc_layered_kernel<DMAX, false, 1, false, false, false, false, true>), grid, block, a.lds_bytes, a.stream, DVBS2_KARGS, nullptr, nullptr, a.dm);
-            return;
-        }
-    }
-    if constexpr (kSoloBuilt<DMAX>) {
-        if (a.solo) {
-            const dim3 sgrid(a.n_frames), sblock(kSoloThreads);
-            if (a.v2) hipLaunchKernelGGL((ldpc_layered_kernel<DMAX, false, 1, true, true>), sgrid, sblock, a.lds_bytes, a.stream, DVBS2_KARGS, nullptr, a.cu_slots, a.dm);
-            else if (a.chain) hipLaunchKernelGGL((ldpc_layered_kernel<DMAX, false, 1, false, true, true>), sgrid, sblock, a.lds_bytes, a.stream, DVBS2_KARGS, nullptr, a.cu_slots, a.dm);
-            else hipLaunchKernelGGL((ldpc_layered_kernel<DMAX, false, 1, false, true>), sgrid, sblock, a.lds_bytes, a.stream, DVBS2_KARGS, nullptr, a.cu_slots, a.dm);
-            return;
-        }
-    }
-    if (a.v2) hipLaunchKernelGGL((ldpc_layered_kernel<DMAX, false, 1, true, false>), grid, block, a.lds_bytes, a.stream, DVBS2_KARGS, nullptr, nullptr, a.dm);
-    else if constexpr (kChainBuilt<DMAX>) {
-        if (a.chain) hipLaunchKernelGGL((ldpc_layered_kernel<DMAX, false, 1, false, false, true>), grid, block, a.lds_bytes, a.stream, DVBS2_KARGS, nullptr, nullptr, a.dm);
-        else hipLaunchKernelGGL((ldpc_layered_kernel<DMAX, false, 1, false, false>), grid, block, a.lds_bytes, a.stream, DVBS2_KARGS, nullptr, nullptr, a.dm);
-    }
-    else hipLaunchKernelGGL((ldpc_layered_kernel<DMAX, false, 1, false, false>), grid, block, a.lds_bytes, a.stream, DVBS2_KARGS, nullptr, nullptr, a.dm);
+    const SweepKernel tk = a.tdbg ? timing_kernel<DMAX>() : nullptr;
+    const SweepKernel k = tk ? tk : sweep_kernel<DMAX>(a.build);
+    if (!k) return; // (ldpc_variant_prepare refused such a build)
+    const bool solo = !tk && is_solo(a.build);
+    hipLaunchKernelGGL(k, solo ? dim3(a.n_frames) : dim3((a.n_frames + 1) / 2), solo ? dim3(kSoloThreads) : dim3(kThreads), a.lds_bytes, a.stream,
+                       a.recs, a.wrecs, a.llr_in, a.state, a.msgs, a.iters, a.good, a.target, a.n_frames, a.N, a.K, a.q, a.cap, a.stop_on_good,
+                       tk ? a.tdbg : nullptr, solo ? a.cu_slots : nullptr, a.dm);
 }
-template hipError_t ldpc_variant_prepare<DVBS2_LDPC_INSTANTIATE>(size_t, size_t);
+template hipError_t ldpc_variant_prepare<DVBS2_LDPC_INSTANTIATE>(LdpcBuild, size_t, size_t);
 template void ldpc_variant_launch<DVBS2_LDPC_INSTANTIATE>(const LdpcLaunch&);
 #endif
 

@@ -18,12 +18,7 @@
 // the ~18 VALU instructions of the conversion around the node.
 #pragma once
 #include "ldpc_kernel.hpp"
-#include <cstdio>
-#include <cstdlib>
 
-#ifndef DVBS2_PR_DEFER_STORE
-#define DVBS2_PR_DEFER_STORE 1
-#endif
 // Round 6: the degree-3 / 4 node of the one-dword-record kernel takes the minimum over the OTHER links directly (see check_node_pr6). Interleaved A/B against
 // "two smallest + select" (three repetitions, gpurun_out/r6m): short 1/4 1059.8 -> 1074.1 k (+1.3 %), S2X short 1220 -> 1232 k, medium 1/5 and 11/45 +1.0 / +1.1 %,
 // 1/4 normal and S2X 2/9 normal +0.9 / +1.2 %; the kernel's other tables (two-dword records) 1.000 / 1.001.
@@ -167,7 +162,7 @@ __device__ __forceinline__ void check_node_v2_pr(const uint32_t* ent /*record wo
     uint32_t sx = 0;
 #pragma unroll
     for (int j = 0; j < NP; j++) {
-        uint32_t M = msg_pair16<false>(mw, j);
+        uint32_t M = msg_pair16(mw, j);
         if (ODD && j == NP - 1 && (j & 1)) M &= 0x0000ff00u; // degree 7: byte 3 of word 1 is the parity LLR, not the pad's message
         const uint32_t hi = (ODD && j == NP - 1) ? 0x80u : (uint32_t)Lb[2 * j + 1];
         const uint32_t L = __builtin_amdgcn_perm(hi, (uint32_t)Lb[2 * j], 0x040c000cu) ^ kObPair<false>;
@@ -209,7 +204,7 @@ __device__ __forceinline__ void check_node_v2_pr(const uint32_t* ent /*record wo
     }
     __builtin_amdgcn_s_setprio(3);
     if (ODD) R[NP - 1] &= 0x0000ffffu;
-    msg_pack16<false, NP, 2>(R, nm);
+    msg_pack16<NP>(R, nm);
     nm[1] = (nm[1] & 0x00ffffffu) | ((uint32_t)spare << 24);
 }
 
@@ -370,11 +365,7 @@ __global__ __launch_bounds__(kThreads, 6) void ldpc_layered_pr_kernel(
             if (__ballot(bad_pre) != 0 && lane == 0) flags[2] = 1;
         }
         __syncthreads();
-#ifdef DVBS2_EXP_ALWAYS_FULL // timing experiment (same results): the full test after every update, whatever the pre-test says
-        const bool need_full = need_synd;
-#else
         const bool need_full = need_synd && flags[2] == 0;
-#endif
         if (tid == 0) flags[3] = need_full ? 1 : 0;
         __syncthreads();
         if (flags[3] != 0 || other_flags[3] != 0) { // uniform over the workgroup
@@ -453,11 +444,10 @@ __global__ __launch_bounds__(kThreads, 6) void ldpc_layered_pr_kernel(
 #pragma unroll
         for (int k = 0; k < 2 * DMAX; k++) nent[k] = srec[4 + k];
         // The record a layer produces is STORED at the head of the next layer, behind an explicit s_waitcnt vmcnt(0) (see
-        // DVBS2_WAIT_BEFORE_STORE in ldpc_kernel.hpp: the compiler waits for the prefetched record with vmcnt(0) at the head of a layer,
+        // DVBS2_WAIT_VM0 in ldpc_kernel.hpp: the compiler waits for the prefetched record with vmcnt(0) at the head of a layer,
         // i.e. right behind the store the previous layer has just issued; stored here instead, everything that wait covers is a layer old).
         // Here the wait cannot simply go in front of the store at the END of the layer: the layers of these tables are short and the
         // prefetch issued at their head would not be back yet.
-        constexpr bool kDeferStore = DVBS2_PR_DEFER_STORE != 0;
         uint32_t pend[RW];
         int pend_i = 0;
         bool pend_on = false; // uniform
@@ -492,12 +482,10 @@ __global__ __launch_bounds__(kThreads, 6) void ldpc_layered_pr_kernel(
                 for (int w = 0; w < MW; w++) { mw[w] = work ? pre1[w] : 0x80808080u; pre1[w] = pre2[w]; }
             }
             const int own_in = (int)(pre1[PW] >> 24); // top byte of record i+1 = P[i] (not used by the last layer)
-            if constexpr (kDeferStore) {
-                asm volatile("" ::: "memory"); __builtin_amdgcn_s_waitcnt(0x0f70); asm volatile("" ::: "memory"); // vmcnt(0), on every path
-                if (pend_on) { // (pend_on: work && i > 0, the record of layer i - 1)
+            asm volatile("" ::: "memory"); __builtin_amdgcn_s_waitcnt(0x0f70); asm volatile("" ::: "memory"); // vmcnt(0), on every path
+            if (pend_on) { // (pend_on: work && i > 0, the record of layer i - 1)
 #pragma unroll
-                    for (int w = 0; w < RW; w++) pr_st(mp - (RW - w) * kMsgStride, roff, pend[w]);
-                }
+                for (int w = 0; w < RW; w++) pr_st(mp - (RW - w) * kMsgStride, roff, pend[w]);
             }
             if (work && i + 2 < q) {
 #pragma unroll
@@ -529,27 +517,18 @@ __global__ __launch_bounds__(kThreads, 6) void ldpc_layered_pr_kernel(
                 DVBS2_PRH_SWITCH
             }
             if (work) {
-                if constexpr (kDeferStore) {
-                    if constexpr (W1) pend[0] = have_y6 ? y6 : pr_w1_compress(nm);
-                    else {
-#pragma unroll
-                        for (int w = 0; w < MW; w++) pend[w] = nm[w];
-                    }
-                    pend_i = i; pend_on = true;
-                } else
-                if constexpr (W1) mp[jj] = have_y6 ? y6 : pr_w1_compress(nm);
+                if constexpr (W1) pend[0] = have_y6 ? y6 : pr_w1_compress(nm);
                 else {
 #pragma unroll
-                    for (int w = 0; w < MW; w++) mp[w * kMsgStride + jj] = nm[w];
+                    for (int w = 0; w < MW; w++) pend[w] = nm[w];
                 }
+                pend_i = i; pend_on = true;
             }
         }
-        if constexpr (kDeferStore) {
-            if (pend_on) { // the last layer's record
-                uint32_t* pp = msg_base + (size_t)pend_i * RW * kMsgStride;
+        if (pend_on) { // the last layer's record
+            uint32_t* pp = msg_base + (size_t)pend_i * RW * kMsgStride;
 #pragma unroll
-                for (int w = 0; w < RW; w++) pp[w * kMsgStride + row] = pend[w];
-            }
+            for (int w = 0; w < RW; w++) pp[w * kMsgStride + row] = pend[w];
         }
         __syncthreads();
         if (!finished) it++;
@@ -568,31 +547,35 @@ __global__ __launch_bounds__(kThreads, 6) void ldpc_layered_pr_kernel(
 
 #endif // DVBS2_LDPC_INSTANTIATE_PR
 
-hipError_t ldpc_pr_prepare(size_t lds_bytes);
-void ldpc_pr_launch(const LdpcLaunch& a); // a.v2 = one-dword records (check degree <= 4)
+// the parity-in-records builds (LdpcBuild::pr, pr_w1, pr_packed); prepare fails when `build` is not one of them
+hipError_t ldpc_pr_prepare(LdpcBuild build, size_t lds_bytes);
+void ldpc_pr_launch(const LdpcLaunch& a);
 
 #ifdef DVBS2_LDPC_INSTANTIATE_PR
-hipError_t ldpc_pr_prepare(size_t lds_bytes)
+typedef void (*PrKernel)(const uint32_t*, const uint32_t*, const int8_t*, uint8_t*, uint32_t*, int*, int*, const int*, int, int, int, int, int, int);
+static PrKernel pr_kernel(LdpcBuild b)
 {
-    hipError_t e = hipFuncSetAttribute((const void*)ldpc_layered_pr_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ldpc_layered_pr_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)ldpc_layered_pr_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e == hipSuccess && getenv("DVBS2_OCC")) {
-        int nb = -1;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ldpc_layered_pr_kernel<false>, kThreads, lds_bytes);
-        fprintf(stderr, "[pr kernel] lds %zu bytes, occupancy API: %d workgroups per CU\n", lds_bytes, nb);
+    switch (b) {
+    case LdpcBuild::pr: return ldpc_layered_pr_kernel<false>;
+    case LdpcBuild::pr_w1: return ldpc_layered_pr_kernel<true>;
+    case LdpcBuild::pr_packed: return ldpc_layered_pr_kernel<false, true>;
+    default: return nullptr;
     }
+}
+hipError_t ldpc_pr_prepare(LdpcBuild build, size_t lds_bytes)
+{
+    if (!pr_kernel(build)) return hipErrorInvalidDeviceFunction;
+    hipError_t e = hipSuccess;
+    for (int b = 0; b < kLdpcBuilds && e == hipSuccess; b++)
+        if (const PrKernel k = pr_kernel((LdpcBuild)b)) e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     return e;
 }
 void ldpc_pr_launch(const LdpcLaunch& a)
 {
-    if (a.v2) hipLaunchKernelGGL(ldpc_layered_pr_kernel<true>, dim3((a.n_frames + 1) / 2), dim3(kThreads), a.lds_bytes, a.stream, a.recs, a.wrecs, a.llr_in, a.state, a.msgs,
-                                 a.iters, a.good, a.target, a.n_frames, a.N, a.K, a.q, a.cap, a.stop_on_good);
-    else if (a.pr_packed)
-        hipLaunchKernelGGL((ldpc_layered_pr_kernel<false, true>), dim3((a.n_frames + 1) / 2), dim3(kThreads), a.lds_bytes, a.stream, a.recs, a.wrecs, a.llr_in, a.state, a.msgs,
-                           a.iters, a.good, a.target, a.n_frames, a.N, a.K, a.q, a.cap, a.stop_on_good);
-    else hipLaunchKernelGGL(ldpc_layered_pr_kernel<false>, dim3((a.n_frames + 1) / 2), dim3(kThreads), a.lds_bytes, a.stream, a.recs, a.wrecs, a.llr_in, a.state, a.msgs,
-                            a.iters, a.good, a.target, a.n_frames, a.N, a.K, a.q, a.cap, a.stop_on_good);
+    const PrKernel k = pr_kernel(a.build);
+    if (!k) return; // (ldpc_pr_prepare refused such a build)
+    hipLaunchKernelGGL(k, dim3((a.n_frames + 1) / 2), dim3(kThreads), a.lds_bytes, a.stream, a.recs, a.wrecs, a.llr_in, a.state, a.msgs,
+                       a.iters, a.good, a.target, a.n_frames, a.N, a.K, a.q, a.cap, a.stop_on_good);
 }
 #endif
 

@@ -13,7 +13,7 @@ for t in tables:
     res = {}
     for v2 in (1, 0):
         for solo in (1, 0):
-            env = dict(os.environ, DVBS2_V2=str(v2), DVBS2_CHAIN_V2=str(v2), DVBS2_SOLO=str(solo), WARM_S="0.2")
+            env = dict(os.environ, DVBS2_V2=str(v2), DVBS2_SOLO=str(solo), WARM_S="0.2")
             out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "exp_tables.py"), f"{t}:{cap}:{nf}"], capture_output=True, text=True, env=env).stdout
             w = out.strip().split("\n")[-1].split()
             res[(v2, solo)] = float(w[w.index("fr/s") - 1]) if "fr/s" in w else 0.0

@@ -52,10 +52,10 @@ def short(mangled):
     m = re.search(r"ldpc_layered_pr_kernelILb([01])ELb([01])E", mangled)  # <W1, V2>
     if m:
         return "ldpc_layered_pr_kernel<w1>" if m.group(1) == "1" else "ldpc_layered_pr_kernel<packed>" if m.group(2) == "1" else "ldpc_layered_pr_kernel"
-    m = re.search(r"ldpc_layered_kernelILi(\d+)ELb([01])ELi(\d+)ELb([01])ELb([01])ELb([01])ELb([01])ELb([01])E", mangled)
+    m = re.search(r"ldpc_layered_kernelILi(\d+)ELb([01])ELi(\d+)ELb([01])ELb([01])ELb([01])ELb([01])E", mangled)  # <DMAX, TIMING, MINW, V2, SOLO, HZ2, SOFT>
     if not m:
         return None
-    d, timing, minw, v2, solo, chain, hz2, soft = m.groups()
+    d, timing, minw, v2, solo, hz2, soft = m.groups()
     if timing == "1":
         return None
     if minw != "1":
