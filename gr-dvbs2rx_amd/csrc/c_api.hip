@@ -15,6 +15,7 @@
 #include "bch_hip.h"
 #include "demap_hip.h"
 #include "plpayload_hip.h"
+#include "plframe_hip.h"
 #include "bbdeheader_hip.h"
 #include "device_guard.h"
 #include "demap_math.hpp"
@@ -1000,6 +1001,7 @@ int dvbs2_chain_ldpc_profile(dvbs2_chain_t* h, int enable, double* total_ms, int
 }
 
 const char* dvbs2_chain_ldpc_kernel_name(const dvbs2_chain_t* h) { return h ? h->ldpc->dec->kernel_name() : nullptr; }
+int dvbs2_chain_ldpc_fallback_rounds(const dvbs2_chain_t* h) { return h ? h->ldpc->dec->fallback_rounds() : -1; }
 
 int dvbs2_chain_finish(dvbs2_chain_t* h)
 {
@@ -1296,6 +1298,192 @@ int dvbs2_plpayload_process(dvbs2_plpayload_t* h, const float* payload, int n_fr
     HCHK(hipMemcpyAsync(xfecframes, h->d_out, nf * xl * 8, hipMemcpyDeviceToHost, h->stream));
     HCHK(hipStreamSynchronize(h->stream));
     return DVBS2_OK;
+    API_CATCH
+}
+
+} // extern "C"
+
+/* ------------------------------------------------------------------ PLFRAME front end: PLSC, phases, fine offset */
+struct dvbs2_plframe {
+    PlFrameHip* pf = nullptr;
+    // staging of the host entries
+    float* d_in = nullptr; float* d_out = nullptr; float* d_cf = nullptr; int32_t* d_cc = nullptr;
+    float* d_est = nullptr; // sof | plheader | fine | pilot phases | fine_valid (int32) | plsc (uint8)
+    hipStream_t stream = nullptr;
+    int device = 0;
+};
+
+static int plframe_check(const dvbs2_plframe* h, const void* plframes, int n_frames, const void* cc, const void* cf)
+{
+    if (!h) return fail(DVBS2_EINVAL, "null handle");
+    if (n_frames < 0 || (n_frames && (!plframes || !cc))) return fail(DVBS2_EINVAL, "bad argument");
+    if (n_frames && h->pf->pls().n_pilots == 0 && !cf) return fail(DVBS2_EINVAL, "a pilotless handle needs coarse_foffset");
+    if (n_frames > h->pf->max_frames()) return fail(DVBS2_ESIZE, "n_frames exceeds max_frames");
+    return DVBS2_OK;
+}
+
+static PlFrameEstimates plframe_est(const dvbs2_plframe_estimates_t* e)
+{
+    PlFrameEstimates o;
+    if (e) { o.plsc_decoded = e->plsc_decoded; o.sof_phase = e->sof_phase; o.plheader_phase = e->plheader_phase;
+             o.pilot_phase = e->pilot_phase; o.fine_foffset = e->fine_foffset; o.fine_valid = e->fine_valid; }
+    return o;
+}
+
+// host entry: stage in, run, copy back what the caller asked for
+static int plframe_host(dvbs2_plframe* h, const float* plframes, int n_frames, int trailing, const int32_t* cc, const float* cf,
+                        float* xfecframes, const dvbs2_plframe_estimates_t* est)
+{
+    if (int rc = plframe_check(h, plframes, n_frames, cc, cf)) return rc;
+    if (n_frames == 0) return DVBS2_OK;
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(DVBS2_EDEVICE, "hipSetDevice failed");
+    const PlsInfo& p = h->pf->pls();
+    const size_t mf = h->pf->max_frames(), fl = p.plframe_len, xl = p.xfecframe_len, nf = n_frames, np = p.n_pilots;
+    if (!h->stream) HCHK(hipStreamCreate(&h->stream));
+    if (!h->d_in) HCHK(hipMalloc(&h->d_in, (mf * fl + 90) * 8));
+    if (!h->d_out) HCHK(hipMalloc(&h->d_out, mf * xl * 8));
+    if (!h->d_cf) HCHK(hipMalloc(&h->d_cf, mf * 4));
+    if (!h->d_cc) HCHK(hipMalloc(&h->d_cc, mf * 4));
+    if (!h->d_est) HCHK(hipMalloc(&h->d_est, mf * (4 + (np ? np : 1)) * 4 + mf));
+    PlFrameEstimates d;
+    d.sof_phase = h->d_est; d.plheader_phase = h->d_est + mf; d.fine_foffset = h->d_est + 2 * mf; d.pilot_phase = h->d_est + 3 * mf;
+    d.fine_valid = reinterpret_cast<int32_t*>(h->d_est + (3 + (np ? np : 1)) * mf);
+    d.plsc_decoded = reinterpret_cast<uint8_t*>(h->d_est + (4 + (np ? np : 1)) * mf);
+    HCHK(hipMemcpyAsync(h->d_in, plframes, (nf * fl + (trailing ? 90 : 0)) * 8, hipMemcpyHostToDevice, h->stream));
+    HCHK(hipMemcpyAsync(h->d_cc, cc, nf * 4, hipMemcpyHostToDevice, h->stream));
+    if (cf) HCHK(hipMemcpyAsync(h->d_cf, cf, nf * 4, hipMemcpyHostToDevice, h->stream));
+    if (h->pf->run_device(h->d_in, n_frames, trailing, h->d_cc, cf ? h->d_cf : nullptr, xfecframes ? h->d_out : nullptr, d, h->stream))
+        return fail(DVBS2_EDEVICE, h->pf->error());
+    if (xfecframes) HCHK(hipMemcpyAsync(xfecframes, h->d_out, nf * xl * 8, hipMemcpyDeviceToHost, h->stream));
+    if (est) {
+        if (est->sof_phase) HCHK(hipMemcpyAsync(est->sof_phase, d.sof_phase, nf * 4, hipMemcpyDeviceToHost, h->stream));
+        if (est->plheader_phase) HCHK(hipMemcpyAsync(est->plheader_phase, d.plheader_phase, nf * 4, hipMemcpyDeviceToHost, h->stream));
+        if (est->fine_foffset) HCHK(hipMemcpyAsync(est->fine_foffset, d.fine_foffset, nf * 4, hipMemcpyDeviceToHost, h->stream));
+        if (est->pilot_phase && np) HCHK(hipMemcpyAsync(est->pilot_phase, d.pilot_phase, nf * np * 4, hipMemcpyDeviceToHost, h->stream));
+        if (est->fine_valid) HCHK(hipMemcpyAsync(est->fine_valid, d.fine_valid, nf * 4, hipMemcpyDeviceToHost, h->stream));
+        if (est->plsc_decoded) HCHK(hipMemcpyAsync(est->plsc_decoded, d.plsc_decoded, nf, hipMemcpyDeviceToHost, h->stream));
+    }
+    HCHK(hipStreamSynchronize(h->stream));
+    return DVBS2_OK;
+}
+
+extern "C" {
+
+int dvbs2_plheader_symbols(int plsc, float* syms90)
+{
+    if (!syms90 || plsc < 0 || plsc > 127) return fail(DVBS2_EINVAL, "bad argument");
+    plheader_symbols(plsc, syms90);
+    return DVBS2_OK;
+}
+
+int dvbs2_pls_parse(int plsc, int* plframe_len, int* payload_len, int* xfecframe_len, int* n_slots, int* n_pilots, int* n_mod)
+{
+    if (plsc < 0 || plsc > 127) return fail(DVBS2_EINVAL, "plsc out of range (0..127)");
+    const PlsInfo p = pls_parse(plsc);
+    if (plframe_len) *plframe_len = p.plframe_len;
+    if (payload_len) *payload_len = p.payload_len;
+    if (xfecframe_len) *xfecframe_len = p.xfecframe_len;
+    if (n_slots) *n_slots = p.n_slots;
+    if (n_pilots) *n_pilots = p.n_pilots;
+    if (n_mod) *n_mod = p.n_mod;
+    return DVBS2_OK;
+}
+
+int dvbs2_plframe_create(dvbs2_plframe_t** h, int gold_code, int plsc, int max_frames, int device)
+{
+    API_TRY
+    if (!h) return fail(DVBS2_EINVAL, "null handle pointer");
+    *h = nullptr;
+    // arguments first: a bad PLSC is the caller's mistake on any machine
+    if (plsc < 0 || plsc > 127) return fail(DVBS2_EINVAL, "plsc out of range (0..127)");
+    { const PlsInfo p = pls_parse(plsc); if (p.n_mod == 0 && !p.dummy_frame) return fail(DVBS2_EINVAL, "plsc names a reserved MODCOD (29..31)"); }
+    if (gold_code < 0 || gold_code >= (1 << 18) - 1) return fail(DVBS2_EINVAL, "gold code out of range");
+    if (int rc = check_device(device)) return rc;
+    dvbs2_plframe* o = new (std::nothrow) dvbs2_plframe();
+    if (!o) return fail(DVBS2_EDEVICE, "out of memory");
+    o->device = device;
+    o->pf = new (std::nothrow) PlFrameHip(gold_code, plsc, max_frames, device);
+    if (!o->pf || !o->pf->ok()) { std::string msg = o->pf ? o->pf->error() : "out of memory"; delete o->pf; delete o; return fail(DVBS2_EINVAL, msg); }
+    *h = o;
+    return DVBS2_OK;
+    API_CATCH
+}
+
+void dvbs2_plframe_destroy(dvbs2_plframe_t* h)
+{
+    if (!h) return;
+    DeviceGuard guard(h->device);
+    (void)hipFree(h->d_in); (void)hipFree(h->d_out); (void)hipFree(h->d_cf); (void)hipFree(h->d_cc); (void)hipFree(h->d_est);
+    if (h->stream) (void)hipStreamDestroy(h->stream);
+    delete h->pf;
+    delete h;
+}
+
+int dvbs2_plframe_params(const dvbs2_plframe_t* h, int* plframe_len, int* payload_len, int* xfecframe_len, int* n_slots, int* n_pilots,
+                         int* n_mod)
+{
+    if (!h) return fail(DVBS2_EINVAL, "null handle");
+    return dvbs2_pls_parse(h->pf->pls().plsc, plframe_len, payload_len, xfecframe_len, n_slots, n_pilots, n_mod);
+}
+
+int dvbs2_plframe_set_plsc_mode(dvbs2_plframe_t* h, int coherent, int soft)
+{
+    if (!h) return fail(DVBS2_EINVAL, "null handle");
+    h->pf->set_plsc_mode(coherent, soft);
+    return DVBS2_OK;
+}
+
+int dvbs2_plframe_set_expected_pls(dvbs2_plframe_t* h, const uint8_t* plsc_list, int n)
+{
+    API_TRY
+    if (!h) return fail(DVBS2_EINVAL, "null handle");
+    if (n < 0 || (n > 0 && !plsc_list)) return fail(DVBS2_EINVAL, "bad argument");
+    if (int rc = h->pf->set_expected_pls(plsc_list, n)) return fail(rc == -1 ? DVBS2_EINVAL : DVBS2_EDEVICE, h->pf->error());
+    return DVBS2_OK;
+    API_CATCH
+}
+
+int dvbs2_plframe_estimate_device(dvbs2_plframe_t* h, const float* d_plframes, int n_frames, int has_trailing_header,
+                                  const int32_t* d_coarse_corrected, const float* d_coarse_foffset,
+                                  const dvbs2_plframe_estimates_t* d_est, void* stream)
+{
+    API_TRY
+    if (int rc = plframe_check(h, d_plframes, n_frames, d_coarse_corrected, d_coarse_foffset)) return rc;
+    if (h->pf->run_device(d_plframes, n_frames, has_trailing_header, d_coarse_corrected, d_coarse_foffset, nullptr, plframe_est(d_est),
+                          (hipStream_t)stream)) return fail(DVBS2_EDEVICE, h->pf->error());
+    return DVBS2_OK;
+    API_CATCH
+}
+
+int dvbs2_plframe_process_device(dvbs2_plframe_t* h, const float* d_plframes, int n_frames, int has_trailing_header,
+                                 const int32_t* d_coarse_corrected, const float* d_coarse_foffset, float* d_xfecframes,
+                                 const dvbs2_plframe_estimates_t* d_est, void* stream)
+{
+    API_TRY
+    if (int rc = plframe_check(h, d_plframes, n_frames, d_coarse_corrected, d_coarse_foffset)) return rc;
+    if (n_frames && !d_xfecframes) return fail(DVBS2_EINVAL, "bad argument");
+    if (h->pf->run_device(d_plframes, n_frames, has_trailing_header, d_coarse_corrected, d_coarse_foffset, d_xfecframes, plframe_est(d_est),
+                          (hipStream_t)stream)) return fail(DVBS2_EDEVICE, h->pf->error());
+    return DVBS2_OK;
+    API_CATCH
+}
+
+int dvbs2_plframe_estimate(dvbs2_plframe_t* h, const float* plframes, int n_frames, int has_trailing_header,
+                           const int32_t* coarse_corrected, const float* coarse_foffset, const dvbs2_plframe_estimates_t* est)
+{
+    API_TRY
+    return plframe_host(h, plframes, n_frames, has_trailing_header, coarse_corrected, coarse_foffset, nullptr, est);
+    API_CATCH
+}
+
+int dvbs2_plframe_process(dvbs2_plframe_t* h, const float* plframes, int n_frames, int has_trailing_header,
+                          const int32_t* coarse_corrected, const float* coarse_foffset, float* xfecframes,
+                          const dvbs2_plframe_estimates_t* est)
+{
+    API_TRY
+    if (n_frames > 0 && !xfecframes) return fail(DVBS2_EINVAL, "bad argument");
+    return plframe_host(h, plframes, n_frames, has_trailing_header, coarse_corrected, coarse_foffset, xfecframes, est);
     API_CATCH
 }
 

@@ -1,0 +1,63 @@
+// plframe_hip.h -- PLFRAME front end on the device: everything that PRODUCES the per-frame parameters
+// of the payload step once frame boundaries are known -- PLSC decoding of the frame's own header (reference
+// lib/plsync_cc_impl.cc:582-590, lib/pl_signaling.cc:114-167, lib/reed_muller.cc:120-210, lib/pi2_bpsk.cc:45-196), the
+// data-aided phases of SOF / PLHEADER / pilot blocks (lib/pl_freq_sync.cc:201-273) and the fine frequency offset
+// (:275-349) -- followed by the payload step itself (plpayload_hip.h) reading whole PLFRAMEs.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+#include <string>
+#include "plpayload_hip.h"
+
+namespace dvbs2 {
+
+constexpr uint32_t kSofWord = 0x18D2E82u;                  // 26 bits, first transmitted bit is bit 25 (lib/pl_defs.h:42)
+constexpr uint64_t kPlscScrambler = 0x719d83c953422dfaull; // lib/pl_defs.h:44
+
+// pls_info_t::parse (lib/pl_signaling.cc:19-61)
+struct PlsInfo {
+    int plsc, modcod, short_fecframe, has_pilots, dummy_frame, n_mod, n_slots, n_pilots, plframe_len, payload_len, xfecframe_len;
+};
+PlsInfo pls_parse(int plsc);
+// the interleaved (64,7) Reed-Muller codeword of a PLSC, first transmitted bit in bit 63 (lib/reed_muller.cc:57-96)
+uint64_t plsc_codeword(int plsc);
+// the 90 expected PLHEADER symbols (re, im): SOF + scrambled PLSC codeword, pi/2-BPSK (lib/pi2_bpsk.cc:18-43)
+void plheader_symbols(int plsc, float* syms90);
+
+// device (or host-staged) outputs of the estimate kernel, each nullable
+struct PlFrameEstimates {
+    uint8_t* plsc_decoded = nullptr;
+    float* sof_phase = nullptr;
+    float* plheader_phase = nullptr;
+    float* pilot_phase = nullptr;
+    float* fine_foffset = nullptr;
+    int32_t* fine_valid = nullptr;
+};
+
+class PlFrameHip {
+public:
+    PlFrameHip(int gold_code, int plsc, int max_frames, int device);
+    ~PlFrameHip();
+    bool ok() const { return err_.empty(); }
+    const std::string& error() const { return call_err_.empty() ? err_ : call_err_; }
+    const PlsInfo& pls() const { return pls_; }
+    int max_frames() const { return max_frames_; }
+    void set_plsc_mode(int coherent, int soft) { coherent_ = coherent ? 1 : 0; soft_ = soft ? 1 : 0; }
+    // the enabled-codeword list of the reference's second plsc_decoder constructor, in the caller's order (n = 0: all 128)
+    int set_expected_pls(const uint8_t* list, int n);
+    // DEVICE pointers. d_plframes: n_frames * plframe_len complex (+ 90 when has_trailing_header); d_coarse_corrected:
+    // n_frames int32; d_coarse_foffset: n_frames float, needed only by pilotless handles. d_out (nullable = estimates
+    // only): n_frames * xfecframe_len complex.
+    int run_device(const float* d_plframes, int n_frames, int has_trailing_header, const int32_t* d_coarse_corrected,
+                   const float* d_coarse_foffset, float* d_out, const PlFrameEstimates& est, hipStream_t stream);
+
+private:
+    PlsInfo pls_{};
+    int max_frames_, device_, coherent_ = 1, soft_ = 1;
+    PlPayloadHip* pp_ = nullptr; // owns the Rn table and the payload kernel launch
+    uint8_t* d_rank_ = nullptr;  // 128 bytes: position of each codeword in the enabled list, 255 = disabled
+    float* d_par_ = nullptr;     // what the payload step reads: plheader_phase | phase_inc | pilot_phase
+    std::string err_, call_err_;
+};
+
+} // namespace dvbs2

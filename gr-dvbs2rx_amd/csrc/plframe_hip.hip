@@ -1,0 +1,283 @@
+// plframe_hip.hip -- see plframe_hip.h. The estimate kernel runs ONE WAVEFRONT PER FRAME (a 64-thread workgroup): the
+// PLSC is 64 symbols and the RM(64,7) transform has 64 points, so every step is one value per lane and every
+// reduction a butterfly of cross-lane exchanges -- no LDS, no barrier. It reads 90 + 36 n_pilots symbols of a frame;
+// the streaming payload step (plpayload_hip.hip) follows as a second launch on the same stream.
+#include "plframe_hip.h"
+#include <cmath>
+#include <vector>
+
+#include "device_guard.h"
+namespace dvbs2 {
+
+PlsInfo pls_parse(int plsc)
+{
+    PlsInfo p{};
+    p.plsc = plsc; p.modcod = plsc >> 2; p.short_fecframe = (plsc >> 1) & 1; p.has_pilots = plsc & 1;
+    p.dummy_frame = p.modcod == 0;
+    if (p.dummy_frame) p.has_pilots = 0; // a dummy frame cannot have pilots (lib/pl_signaling.cc:25-26)
+    if (p.modcod >= 1 && p.modcod <= 11) { p.n_mod = 2; p.n_slots = 360; }
+    else if (p.modcod >= 12 && p.modcod <= 17) { p.n_mod = 3; p.n_slots = 240; }
+    else if (p.modcod >= 18 && p.modcod <= 23) { p.n_mod = 4; p.n_slots = 180; }
+    else if (p.modcod >= 24 && p.modcod <= 28) { p.n_mod = 5; p.n_slots = 144; }
+    else { p.n_mod = 0; p.n_slots = 36; }
+    if (p.short_fecframe && !p.dummy_frame) p.n_slots >>= 2;
+    p.n_pilots = p.has_pilots ? ((p.n_slots - 1) >> 4) : 0;
+    p.plframe_len = (p.n_slots + 1) * 90 + 36 * p.n_pilots;
+    p.payload_len = p.plframe_len - 90;
+    p.xfecframe_len = p.n_slots * 90;
+    return p;
+}
+
+uint64_t plsc_codeword(int plsc)
+{
+    static const uint32_t G[6] = { 0x55555555u, 0x33333333u, 0x0f0f0f0fu, 0x00ff00ffu, 0x0000ffffu, 0xffffffffu };
+    const int i = (plsc >> 1) & 63;
+    uint32_t code32 = 0;
+    for (int row = 0; row < 6; row++) if (i & (0x20 >> row)) code32 ^= G[row];
+    const uint32_t b = (plsc & 1) ? ~code32 : code32; // (y1 !y1 y2 !y2 ...) when b7 = 1, (y1 y1 y2 y2 ...) otherwise
+    uint64_t cw = 0;
+    for (int t = 0; t < 32; t++) {
+        cw |= (uint64_t)((code32 >> t) & 1) << (2 * t + 1);
+        cw |= (uint64_t)((b >> t) & 1) << (2 * t);
+    }
+    return cw;
+}
+
+void plheader_symbols(int plsc, float* syms90)
+{
+    const double S = 0.7071067811865476;
+    const uint64_t cw = plsc_codeword(plsc) ^ kPlscScrambler;
+    for (int k = 0; k < 90; k++) {
+        const int bit = k < 26 ? (int)((kSofWord >> (25 - k)) & 1) : (int)((cw >> (89 - k)) & 1);
+        const double sg = bit ? -1.0 : 1.0;
+        syms90[2 * k] = (float)((k & 1) ? -S * sg : S * sg);
+        syms90[2 * k + 1] = (float)(S * sg);
+    }
+}
+
+namespace {
+
+constexpr float kS = 0.7071067811865476f;
+constexpr double kPi = 3.14159265358979323846;
+
+__device__ inline float wave_sum(float v)
+{
+    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m); // a + b is commutative: every lane ends with the same bits
+    return v;
+}
+
+// x_k * conj(h_k): conj(h_k) = rot[k & 1] * (1 - 2 bit), rot = { (S, -S), (-S, -S) } (lib/pi2_bpsk.cc:23-34, :57-60)
+__device__ inline float2 remove_modulation(float2 x, int k, int bit)
+{
+    const float sg = bit ? -1.0f : 1.0f;
+    const float cr = ((k & 1) ? -kS : kS) * sg, ci = -kS * sg;
+    return make_float2(x.x * cr - x.y * ci, x.x * ci + x.y * cr);
+}
+
+// the three data-aided sums over one PLHEADER (lib/pl_freq_sync.cc:201-226, :263-266); lane l holds symbols l and 64 + l
+__device__ inline void header_sums(const float2* __restrict__ x, int l, uint64_t cw, float2* sof, float2* hdr, float2* last36)
+{
+    const int bit0 = l < 26 ? (int)((kSofWord >> (25 - l)) & 1) : (int)((cw >> (89 - l)) & 1);
+    const float2 t0 = remove_modulation(x[l], l, bit0);
+    float2 t1 = make_float2(0.0f, 0.0f);
+    if (l < 26) t1 = remove_modulation(x[64 + l], 64 + l, (int)((cw >> (25 - l)) & 1));
+    const bool in_sof = l < 26, in_last = l >= 54;
+    *sof = make_float2(wave_sum(in_sof ? t0.x : 0.0f), wave_sum(in_sof ? t0.y : 0.0f));
+    *hdr = make_float2(wave_sum(t0.x + t1.x), wave_sum(t0.y + t1.y));
+    *last36 = make_float2(wave_sum((in_last ? t0.x : 0.0f) + t1.x), wave_sum((in_last ? t0.y : 0.0f) + t1.y));
+}
+
+__device__ inline float wrap_pi(float d) // lib/pl_freq_sync.cc:280-285: the correction is made in double, the value kept as float
+{
+    if ((double)d > kPi) d = (float)((double)d - 2.0 * kPi);
+    else if ((double)d < -kPi) d = (float)((double)d + 2.0 * kPi);
+    return d;
+}
+
+// one wavefront per frame
+__global__ __launch_bounds__(64) void pl_estimate_kernel(const float2* __restrict__ in, const uint8_t* __restrict__ rn,
+                                                         const uint8_t* __restrict__ rank, const int32_t* __restrict__ cc,
+                                                         const float* __restrict__ cf, uint64_t hdr_cw, int plframe_len, int n_pilots,
+                                                         int n_frames, int has_trailing, int coherent, int soft,
+                                                         float* __restrict__ o_hph, float* __restrict__ o_inc, float* __restrict__ o_pil,
+                                                         PlFrameEstimates est)
+{
+    const int f = blockIdx.x, l = threadIdx.x;
+    const float2* __restrict__ x = in + (size_t)f * plframe_len;
+
+    float2 sof, hdr, last36;
+    header_sums(x, l, hdr_cw, &sof, &hdr, &last36);
+    const float sof_phase = atan2f(sof.y, sof.x), hph = atan2f(hdr.y, hdr.x);
+
+    // ---- PLSC of the frame's own header (lib/plsync_cc_impl.cc:582-590): de-rotate by the SOF phase
+    // (lib/pl_freq_sync.cc:429-436), lane j takes PLSC symbol j = PLHEADER symbol 26 + j
+    float sn, cs;
+    sincosf(-sof_phase, &sn, &cs);
+    const float2 xa = x[26 + l], xb = x[25 + l];
+    const float2 ya = make_float2(xa.x * cs - xa.y * sn, xa.x * sn + xa.y * cs);
+    const int scr = (int)((kPlscScrambler >> (63 - l)) & 1);
+    float v; // the descrambled soft decision, or +-1 for a descrambled hard decision
+    if (coherent) {
+        const float rr = (l & 1) ? -kS : kS, ri = -kS;
+        const float sd = ya.x * rr - ya.y * ri; // real(x rot[j & 1]) (lib/pi2_bpsk.cc:45-74, :181-196)
+        if (soft) v = scr ? -sd : sd;
+        else v = ((sd < 0.0f) != (scr != 0)) ? -1.0f : 1.0f;
+    } else {
+        // differential: bit_j = bit_{j-1} ^ (imag(conj(y_{j+1}) y_j) < 0) ^ (j & 1), starting from the last SOF bit 0
+        // (lib/pi2_bpsk.cc:165-176): a prefix parity over the lanes
+        const float2 yb = make_float2(xb.x * cs - xb.y * sn, xb.x * sn + xb.y * cs);
+        const float dim = ya.x * yb.y - ya.y * yb.x;
+        const unsigned long long flips = __ballot(((dim < 0.0f) ? 1 : 0) ^ (l & 1));
+        const unsigned long long upto = l == 63 ? ~0ull : ((2ull << l) - 1ull);
+        const int bit = __popcll(flips & upto) & 1;
+        v = (bit != scr) ? -1.0f : 1.0f;
+    }
+    // RM(64,7) as a transform (lib/reed_muller.cc:72-96): the first stage forms the pair sums (even lanes, b7 = 0) and
+    // pair differences (odd lanes, b7 = 1); five more stages are a 32-point Walsh-Hadamard transform over lane bits
+    // 1..5. Lane 2 w + b7 then holds the metric of codeword (bitrev5(w) << 2) | b7, and its negative that of the
+    // codeword with bit 1 (the all-ones row) set. On +-1 inputs every value is a small integer: exact in float.
+    for (int m = 1; m < 64; m <<= 1) {
+        const float o = __shfl_xor(v, m);
+        v = (l & m) ? o - v : v + o;
+    }
+    const int c0 = (int)((__brev((unsigned)(l >> 1)) >> 27) << 2) | (l & 1), c1 = c0 | 2;
+    const int r0 = rank[c0], r1 = rank[c1];
+    int decoded;
+    if (coherent && soft) {
+        // maximum inner product over ALL 128 entries, those of disabled codewords being 0.0; first maximum wins
+        // (lib/reed_muller.cc:203-209)
+        const float m0 = r0 != 255 ? v : 0.0f, m1 = r1 != 255 ? -v : 0.0f;
+        float bv = m1 > m0 ? m1 : m0; int bi = m1 > m0 ? c1 : c0;
+        for (int m = 1; m < 64; m <<= 1) {
+            const float ov = __shfl_xor(bv, m); const int oi = __shfl_xor(bi, m);
+            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+        }
+        decoded = bi;
+    } else {
+        // minimum Hamming distance, FIRST minimum in the order of the enabled list (lib/reed_muller.cc:128-141):
+        // distance = (64 -+ W) / 2; key = distance | position in the list | codeword
+        const int w = (int)v;
+        const unsigned k0 = r0 != 255 ? (unsigned)(((64 - w) >> 1) << 16 | r0 << 8 | c0) : 0xffffffffu;
+        const unsigned k1 = r1 != 255 ? (unsigned)(((64 + w) >> 1) << 16 | r1 << 8 | c1) : 0xffffffffu;
+        unsigned key = k0 < k1 ? k0 : k1;
+        for (int m = 1; m < 64; m <<= 1) { const unsigned o = __shfl_xor(key, m); key = o < key ? o : key; }
+        decoded = (int)(key & 127u);
+    }
+
+    // ---- fine frequency offset
+    const bool coarse = cc[f] != 0;
+    float fine = 0.0f; int valid = 0;
+    if (n_pilots > 0) {
+        // lane 0: the last 36 PLHEADER symbols; lane i + 1: descrambled pilot block i (lib/pl_freq_sync.cc:263-273)
+        float ar = last36.x, ai = last36.y;
+        for (int i = 0; i < n_pilots; i++) {
+            const int k = (i + 1) * 1476 - 36 + l; // payload offset
+            float dr = 0.0f, di = 0.0f;
+            if (l < 36) {
+                const float2 p = x[90 + k];
+                switch (rn[k]) { case 0: dr = p.x; di = p.y; break; case 1: dr = p.y; di = -p.x; break;
+                                 case 2: dr = -p.x; di = -p.y; break; default: dr = -p.y; di = p.x; break; }
+            }
+            const float sr = wave_sum(dr), si = wave_sum(di);
+            if (l == i + 1) { ar = sr; ai = si; }
+        }
+        float a = 0.0f;
+        if (l <= n_pilots) {
+            a = atan2f(ai, ar);
+            if (l > 0) a = wrap_pi((float)((double)a - kPi / 4.0)); // the pilots sit at pi/4 (:243-249)
+        }
+        const float prev = __shfl_up(a, 1);
+        const float d = (l >= 1 && l <= n_pilots) ? wrap_pi(a - prev) : 0.0f;
+        const float sum_diff = wave_sum(d);
+        if (coarse) { fine = (float)((double)sum_diff / (2.0 * kPi * 1476.0 * (double)n_pilots)); valid = 1; } // :299
+        if (l >= 1 && l <= n_pilots) {
+            o_pil[(size_t)f * n_pilots + l - 1] = a;
+            if (est.pilot_phase) est.pilot_phase[(size_t)f * n_pilots + l - 1] = a;
+        }
+    } else if (coarse && (f + 1 < n_frames || has_trailing) && fabs((double)cf[f]) <= 1.0 / (2.0 * (double)plframe_len)) {
+        // PLHEADER to PLHEADER (lib/pl_freq_sync.cc:325-343); the next header's phase is recomputed here with the same
+        // arithmetic the next frame's own wavefront uses
+        float2 s2, h2, l2;
+        header_sums(x + plframe_len, l, hdr_cw, &s2, &h2, &l2);
+        double delta = (double)(atan2f(h2.y, h2.x) - hph);
+        if (delta > kPi) delta -= 2.0 * kPi; else if (delta < -kPi) delta += 2.0 * kPi;
+        fine = (float)(delta / (2.0 * kPi * (double)plframe_len));
+        valid = 1;
+    }
+    if (l == 0) {
+        o_hph[f] = hph;
+        o_inc[f] = coarse ? (float)(2.0 * kPi * (double)fine) : 0.0f; // lib/plsync_cc_impl.cc:725-726
+        if (est.plsc_decoded) est.plsc_decoded[f] = (uint8_t)decoded;
+        if (est.sof_phase) est.sof_phase[f] = sof_phase;
+        if (est.plheader_phase) est.plheader_phase[f] = hph;
+        if (est.fine_foffset) est.fine_foffset[f] = fine;
+        if (est.fine_valid) est.fine_valid[f] = valid;
+    }
+}
+
+} // namespace
+
+PlFrameHip::PlFrameHip(int gold_code, int plsc, int max_frames, int device) : max_frames_(max_frames), device_(device)
+{
+    if (plsc < 0 || plsc > 127) { err_ = "plsc out of range (0..127)"; return; }
+    pls_ = pls_parse(plsc);
+    if (pls_.n_mod == 0 && !pls_.dummy_frame) { err_ = "plsc names a reserved MODCOD (29..31)"; return; }
+    pp_ = new (std::nothrow) PlPayloadHip(gold_code, pls_.n_slots, pls_.has_pilots, max_frames, device);
+    if (!pp_) { err_ = "out of memory"; return; }
+    if (!pp_->ok()) { err_ = pp_->error(); return; }
+    DeviceGuard dev_guard(device_);
+    const size_t npar = (size_t)max_frames_ * (2 + (pls_.n_pilots ? pls_.n_pilots : 1));
+    if (!dev_guard.ok || hipMalloc(&d_rank_, 128) != hipSuccess || hipMalloc(&d_par_, npar * sizeof(float)) != hipSuccess) {
+        err_ = "device setup failed"; return;
+    }
+    if (set_expected_pls(nullptr, 0)) { err_ = call_err_; call_err_.clear(); }
+}
+
+PlFrameHip::~PlFrameHip()
+{
+    DeviceGuard dev_guard(device_);
+    (void)hipFree(d_rank_); (void)hipFree(d_par_);
+    delete pp_;
+}
+
+int PlFrameHip::set_expected_pls(const uint8_t* list, int n)
+{
+    call_err_.clear();
+    uint8_t rank[128];
+    if (n == 0) { for (int i = 0; i < 128; i++) rank[i] = (uint8_t)i; }
+    else {
+        for (int i = 0; i < 128; i++) rank[i] = 255;
+        int next = 0;
+        for (int i = 0; i < n; i++) {
+            if (list[i] >= 128) { call_err_ = "codeword indexes must be within [0, 128)"; return -1; } // lib/reed_muller.cc:48-52
+            if (rank[list[i]] == 255) rank[list[i]] = (uint8_t)next++; // a repeated entry never wins over its first occurrence
+        }
+    }
+    DeviceGuard dev_guard(device_);
+    if (!dev_guard.ok || hipMemcpy(d_rank_, rank, 128, hipMemcpyHostToDevice) != hipSuccess) { call_err_ = "copy of the codeword list failed"; return -2; }
+    return 0;
+}
+
+int PlFrameHip::run_device(const float* d_plframes, int n_frames, int has_trailing_header, const int32_t* d_coarse_corrected,
+                           const float* d_coarse_foffset, float* d_out, const PlFrameEstimates& est, hipStream_t stream)
+{
+    if (!ok()) return -1;
+    call_err_.clear();
+    if (n_frames < 0 || n_frames > max_frames_) { call_err_ = "n_frames exceeds max_frames"; return -1; }
+    if (n_frames == 0) return 0;
+    DeviceGuard dev_guard(device_);
+    if (!dev_guard.ok) { call_err_ = "hipSetDevice failed"; return -1; }
+    float* d_hph = d_par_; float* d_inc = d_par_ + max_frames_; float* d_pil = d_par_ + 2 * (size_t)max_frames_;
+    hipLaunchKernelGGL(pl_estimate_kernel, dim3(n_frames), dim3(64), 0, stream, reinterpret_cast<const float2*>(d_plframes), pp_->d_rn(),
+                       d_rank_, d_coarse_corrected, d_coarse_foffset, plsc_codeword(pls_.plsc) ^ kPlscScrambler, pls_.plframe_len,
+                       pls_.n_pilots, n_frames, has_trailing_header ? 1 : 0, coherent_, soft_, d_hph, d_inc, d_pil, est);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { call_err_ = std::string("pl estimate kernel launch: ") + hipGetErrorString(e); return -1; }
+    if (!d_out) return 0;
+    if (pp_->process_device_strided(d_plframes, pls_.plframe_len, 90, n_frames, d_hph, d_inc, d_coarse_corrected, d_pil, d_out, stream)) {
+        call_err_ = pp_->error(); return -1;
+    }
+    return 0;
+}
+
+} // namespace dvbs2

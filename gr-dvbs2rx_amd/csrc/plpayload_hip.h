@@ -31,6 +31,11 @@ public:
     // phases (ignored without pilots / when not coarse-corrected); d_out: n_frames * xfecframe_len complex.
     int process_device(const float* d_payload, int n_frames, const float* d_plheader_phase, const float* d_phase_inc,
                        const int32_t* d_coarse_corrected, const float* d_pilot_phase, float* d_out, hipStream_t stream);
+    // the same with frame f's payload at d_in + f * frame_stride + in_offset (complex symbols): whole PLFRAMEs (plframe_hip.h)
+    int process_device_strided(const float* d_in, int frame_stride, int in_offset, int n_frames, const float* d_plheader_phase,
+                               const float* d_phase_inc, const int32_t* d_coarse_corrected, const float* d_pilot_phase, float* d_out,
+                               hipStream_t stream);
+    const uint8_t* d_rn() const { return d_rn_; } // Rn(i), i < payload_len, on the device
 
 private:
     int n_slots_, n_pilots_, has_pilots_, max_frames_, device_;

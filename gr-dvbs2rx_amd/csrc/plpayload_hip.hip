@@ -18,13 +18,14 @@ void pl_scrambling_rn(int gold_code, uint8_t* rn, int n)
     for (int i = 0; i < n; i++) rn[i] = (uint8_t)(2 * z((long)i + 131072) + z(i));
 }
 
-// one thread per output (data) symbol; grid.y = frame
+// one thread per output (data) symbol; grid.y = frame. Frame f's payload starts at in[f * frame_stride + in_offset]:
+// (payload_len, 0) for payloads back to back, (plframe_len, 90) for whole PLFRAMEs (plframe_hip.hip)
 __global__ void pl_payload_kernel(const float2* __restrict__ in, const uint8_t* __restrict__ rn, const float* __restrict__ hphase,
                                   const float* __restrict__ pinc, const int32_t* __restrict__ cc, const float* __restrict__ pphase,
-                                  float2* __restrict__ out, int n_slots, int n_pilots, int has_pilots)
+                                  float2* __restrict__ out, int n_slots, int n_pilots, int has_pilots, int frame_stride, int in_offset)
 {
     const int f = blockIdx.y;
-    const int n_out = n_slots * 90, payload_len = n_out + n_pilots * 36;
+    const int n_out = n_slots * 90;
     const bool coarse = cc[f] != 0;
     const double inc = coarse ? (double)pinc[f] : 0.0;
     for (int o = blockIdx.x * blockDim.x + threadIdx.x; o < n_out; o += gridDim.x * blockDim.x) {
@@ -38,7 +39,7 @@ __global__ void pl_payload_kernel(const float2* __restrict__ in, const uint8_t* 
         else { theta0 = (double)hphase[f]; steps = o; }
         double s, c;
         sincos(-(theta0 + inc * (double)steps), &s, &c);
-        const float2 x = in[(size_t)f * payload_len + k];
+        const float2 x = in[(size_t)f * frame_stride + in_offset + k];
         float dr, di; // descrambling: multiply by conj(exp(j Rn pi/2)) in {1, -j, -1, j} (lib/pl_descrambler.cc:56-58)
         switch (rn[k]) { case 0: dr = x.x; di = x.y; break; case 1: dr = x.y; di = -x.x; break;
                          case 2: dr = -x.x; di = -x.y; break; default: dr = -x.y; di = x.x; break; }
@@ -66,6 +67,14 @@ PlPayloadHip::~PlPayloadHip() { DeviceGuard dev_guard(device_); (void)hipFree(d_
 int PlPayloadHip::process_device(const float* d_payload, int n_frames, const float* d_plheader_phase, const float* d_phase_inc,
                                  const int32_t* d_coarse_corrected, const float* d_pilot_phase, float* d_out, hipStream_t stream)
 {
+    return process_device_strided(d_payload, payload_len(), 0, n_frames, d_plheader_phase, d_phase_inc, d_coarse_corrected, d_pilot_phase,
+                                  d_out, stream);
+}
+
+int PlPayloadHip::process_device_strided(const float* d_in, int frame_stride, int in_offset, int n_frames, const float* d_plheader_phase,
+                                         const float* d_phase_inc, const int32_t* d_coarse_corrected, const float* d_pilot_phase,
+                                         float* d_out, hipStream_t stream)
+{
     if (!ok()) return -1;
     call_err_.clear();
     if (n_frames < 0 || n_frames > max_frames_) { call_err_ = "n_frames exceeds max_frames"; return -1; }
@@ -73,8 +82,8 @@ int PlPayloadHip::process_device(const float* d_payload, int n_frames, const flo
     DeviceGuard dev_guard(device_);
     if (!dev_guard.ok) { call_err_ = "hipSetDevice failed"; return -1; }
     hipLaunchKernelGGL(pl_payload_kernel, dim3((xfecframe_len() + 255) / 256, n_frames), dim3(256), 0, stream,
-                       reinterpret_cast<const float2*>(d_payload), d_rn_, d_plheader_phase, d_phase_inc, d_coarse_corrected,
-                       d_pilot_phase, reinterpret_cast<float2*>(d_out), n_slots_, n_pilots_, has_pilots_);
+                       reinterpret_cast<const float2*>(d_in), d_rn_, d_plheader_phase, d_phase_inc, d_coarse_corrected,
+                       d_pilot_phase, reinterpret_cast<float2*>(d_out), n_slots_, n_pilots_, has_pilots_, frame_stride, in_offset);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { call_err_ = std::string("pl payload kernel launch: ") + hipGetErrorString(e); return -1; }
     return 0;

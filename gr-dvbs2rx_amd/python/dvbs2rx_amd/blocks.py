@@ -15,7 +15,7 @@ from .capi import lib, check
 
 __all__ = ["get_fec_info", "rate_id", "LdpcDecoder", "BchDecoder", "Demapper", "FecChain", "BbDeheader", "ldpc_table_info", "ldpc_layer_info",
            "ldpc_table_names", "bb_descramble_sequence", "PlPayload",
-           "pl_scrambling_rn", "HostBuffer"]
+           "pl_scrambling_rn", "HostBuffer", "PlFrontEnd", "plheader_symbols", "pls_parse"]
 
 DEFAULT_TRIALS = 25  # reference lib/ldpc_decoder_bb_impl.cc:391
 
@@ -333,6 +333,125 @@ class PlPayload:
         return out
 
 
+def plheader_symbols(plsc):
+    """The 90 expected PLHEADER symbols of a PLSC (SOF + scrambled RM(64,7) codeword, pi/2 BPSK). Host only."""
+    out = np.empty(90, np.complex64)
+    check(lib.dvbs2_plheader_symbols(int(plsc), out.ctypes.data))
+    return out
+
+
+def pls_parse(plsc):
+    """pls_info_t::parse as data (reference lib/pl_signaling.cc:19-61). Host only."""
+    v = [C.c_int() for _ in range(6)]
+    check(lib.dvbs2_pls_parse(int(plsc), *v))
+    return dict(zip(("plframe_len", "payload_len", "xfecframe_len", "n_slots", "n_pilots", "n_mod"), (x.value for x in v)))
+
+
+class PlFrontEnd:
+    """PLFRAME front end: per frame the PLSC of its own header, the SOF / PLHEADER / pilot phases and the fine frequency
+    offset (reference lib/plsync_cc_impl.cc:582-590, :634-636, :665-680; lib/pl_freq_sync.cc:201-349), then the payload step
+    of PlPayload with those estimates. One object = one gold code and one PLSC (frame geometry)."""
+
+    EST = (("plsc_decoded", np.uint8), ("sof_phase", np.float32), ("plheader_phase", np.float32), ("pilot_phase", np.float32),
+           ("fine_foffset", np.float32), ("fine_valid", np.int32))
+
+    def __init__(self, gold_code=0, plsc=0, max_frames=16, device=0, coherent=True, soft=True, expected_pls=None):
+        self._h = C.c_void_p()
+        check(lib.dvbs2_plframe_create(C.byref(self._h), gold_code, plsc, max_frames, device))
+        v = [C.c_int() for _ in range(6)]
+        check(lib.dvbs2_plframe_params(self._h, *v))
+        self.plframe_len, self.payload_len, self.xfecframe_len, self.n_slots, self.n_pilots, self.n_mod = (x.value for x in v)
+        self.plsc, self.max_frames = plsc, max_frames
+        self.set_plsc_mode(coherent, soft)
+        if expected_pls is not None:
+            self.set_expected_pls(expected_pls)
+
+    def close(self):
+        if self._h:
+            lib.dvbs2_plframe_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_plsc_mode(self, coherent=True, soft=True):
+        check(lib.dvbs2_plframe_set_plsc_mode(self._h, int(bool(coherent)), int(bool(soft))))
+
+    def set_expected_pls(self, plsc_list):
+        """The enabled-codeword list, in the given order (empty: all 128)."""
+        lst = np.asarray(plsc_list)
+        if lst.size and (lst.dtype.kind not in "iu" or lst.min() < 0 or lst.max() > 255):
+            raise ValueError("expected_pls: integers in 0..127")
+        lst = np.ascontiguousarray(lst, np.uint8)
+        check(lib.dvbs2_plframe_set_expected_pls(self._h, lst.ctypes.data if lst.size else None, int(lst.size)))
+
+    def _inputs(self, plframes, coarse_corrected, coarse_foffset, trailing_header):
+        x = np.asarray(plframes)
+        if x.dtype != np.complex64:
+            raise TypeError(f"plframes must be complex64, not {x.dtype}")
+        if not x.flags.c_contiguous:
+            raise ValueError("plframes must be C-contiguous")
+        if x.ndim == 2 and x.shape[1] != self.plframe_len or x.ndim not in (1, 2) or x.size % self.plframe_len:
+            raise ValueError(f"plframes: expected whole frames of {self.plframe_len} symbols, got shape {x.shape}")
+        nf = x.size // self.plframe_len
+        if nf > self.max_frames:
+            raise ValueError(f"{nf} frames exceed max_frames = {self.max_frames}")
+        if trailing_header is not None:
+            t = np.asarray(trailing_header)
+            if t.dtype != np.complex64 or t.shape != (90,):
+                raise ValueError("trailing_header: 90 complex64 symbols")
+            x = np.concatenate([x.reshape(-1), t])
+        cc = np.asarray(coarse_corrected)
+        if cc.shape != (nf,) or cc.dtype.kind not in "biu":
+            raise ValueError(f"coarse_corrected: {nf} integers or booleans")
+        cc = np.ascontiguousarray(cc, np.int32)
+        cf = None
+        if coarse_foffset is not None:
+            cf = np.asarray(coarse_foffset)
+            if cf.shape != (nf,) or cf.dtype.kind != "f":
+                raise ValueError(f"coarse_foffset: {nf} floats")
+            cf = np.ascontiguousarray(cf, np.float32)
+        elif self.n_pilots == 0:
+            raise ValueError("a pilotless front end needs coarse_foffset")
+        return x, nf, cc, cf
+
+    def _est_arrays(self, nf):
+        arrs = {k: np.empty((nf, self.n_pilots) if k == "pilot_phase" else (nf,), dt) for k, dt in self.EST}
+        e = capi.PlFrameEstimates(**{k: (a.ctypes.data if a.size else None) for k, a in arrs.items()})
+        return arrs, e
+
+    def estimate(self, plframes, coarse_corrected, coarse_foffset=None, trailing_header=None):
+        """HOST buffers: plframes complex64 [n_frames, plframe_len] (or flat). Returns the dict of per-frame estimates."""
+        x, nf, cc, cf = self._inputs(plframes, coarse_corrected, coarse_foffset, trailing_header)
+        arrs, e = self._est_arrays(nf)
+        check(lib.dvbs2_plframe_estimate(self._h, x.ctypes.data, nf, int(trailing_header is not None), cc.ctypes.data,
+                                         cf.ctypes.data if cf is not None else None, C.byref(e)))
+        return arrs
+
+    def work(self, plframes, coarse_corrected, coarse_foffset=None, trailing_header=None):
+        """As estimate(), plus the payload step: returns (xfecframes complex64 [n_frames, xfecframe_len], estimates)."""
+        x, nf, cc, cf = self._inputs(plframes, coarse_corrected, coarse_foffset, trailing_header)
+        arrs, e = self._est_arrays(nf)
+        out = np.empty((nf, self.xfecframe_len), np.complex64)
+        check(lib.dvbs2_plframe_process(self._h, x.ctypes.data, nf, int(trailing_header is not None), cc.ctypes.data,
+                                        cf.ctypes.data if cf is not None else None, out.ctypes.data, C.byref(e)))
+        return out, arrs
+
+    def work_device(self, d_plframes, n_frames, has_trailing_header, d_coarse_corrected, d_coarse_foffset=0, d_xfecframes=0,
+                    stream=0, **d_est):
+        """DEVICE addresses, asynchronous on `stream`; d_xfecframes = 0: estimates only. d_est: addresses by field name."""
+        e = capi.PlFrameEstimates(**{k: (v or None) for k, v in d_est.items()})
+        if d_xfecframes:
+            check(lib.dvbs2_plframe_process_device(self._h, d_plframes, n_frames, int(has_trailing_header), d_coarse_corrected,
+                                                   d_coarse_foffset or None, d_xfecframes, C.byref(e), stream or None))
+        else:
+            check(lib.dvbs2_plframe_estimate_device(self._h, d_plframes, n_frames, int(has_trailing_header), d_coarse_corrected,
+                                                    d_coarse_foffset or None, C.byref(e), stream or None))
+
+
 def pl_scrambling_rn(gold_code, n):
     rn = np.zeros(n, np.uint8)
     check(lib.dvbs2_pl_scrambling_rn(gold_code, rn.ctypes.data, n))
@@ -484,6 +603,11 @@ class FecChain:
     @property
     def kernel_name(self):
         return lib.dvbs2_chain_ldpc_kernel_name(self._h).decode()
+
+    @property
+    def fallback_rounds(self):
+        """host-driven resolution rounds of the LDPC stage's group stop since creation (zero in normal operation)"""
+        return lib.dvbs2_chain_ldpc_fallback_rounds(self._h)
 
     def profile(self, enable=True):
         ms, n = C.c_double(), C.c_int()

@@ -37,6 +37,12 @@ class BbDeheaderCounters(C.Structure):
                 ("gaps", C.c_uint64), ("overruns", C.c_uint64), ("synched", C.c_int32), ("partial_ts_bytes", C.c_int32)]
 
 
+class PlFrameEstimates(C.Structure):
+    """dvbs2_plframe_estimates_t: addresses (device or host, by entry point), 0 = not wanted."""
+    _fields_ = [("plsc_decoded", C.c_void_p), ("sof_phase", C.c_void_p), ("plheader_phase", C.c_void_p),
+                ("pilot_phase", C.c_void_p), ("fine_foffset", C.c_void_p), ("fine_valid", C.c_void_p)]
+
+
 # every symbol include/dvbs2_fec_hip.h declares: name -> (restype, argtypes)
 _vp, _i, _ip = C.c_void_p, C.c_int, C.POINTER(C.c_int)
 SYMBOLS = {
@@ -91,6 +97,17 @@ SYMBOLS = {
     "dvbs2_plpayload_process": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "dvbs2_plpayload_process_device": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dvbs2_pl_scrambling_rn": (_i, [_i, _vp, _i]),
+    "dvbs2_plframe_create": (_i, [C.POINTER(_vp), _i, _i, _i, _i]),
+    "dvbs2_plframe_destroy": (None, [_vp]),
+    "dvbs2_plframe_params": (_i, [_vp, _ip, _ip, _ip, _ip, _ip, _ip]),
+    "dvbs2_plframe_set_plsc_mode": (_i, [_vp, _i, _i]),
+    "dvbs2_plframe_set_expected_pls": (_i, [_vp, _vp, _i]),
+    "dvbs2_plframe_estimate": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "dvbs2_plframe_estimate_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "dvbs2_plframe_process": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "dvbs2_plframe_process_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dvbs2_plheader_symbols": (_i, [_i, _vp]),
+    "dvbs2_pls_parse": (_i, [_i, _ip, _ip, _ip, _ip, _ip, _ip]),
     "dvbs2_bbdeheader_create": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i]),
     "dvbs2_bbdeheader_create_raw": (_i, [C.POINTER(_vp), _i, _i, _i]),
     "dvbs2_bbdeheader_destroy": (None, [_vp]),
@@ -115,6 +132,7 @@ SYMBOLS = {
     "dvbs2_chain_decode_llr": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "dvbs2_chain_ldpc_profile": (_i, [_vp, _i, C.POINTER(C.c_double), _ip]),
     "dvbs2_chain_ldpc_kernel_name": (C.c_char_p, [_vp]),
+    "dvbs2_chain_ldpc_fallback_rounds": (_i, [_vp]),
 }
 
 if not os.path.exists(LIB_PATH):

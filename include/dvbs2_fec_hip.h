@@ -285,6 +285,8 @@ int dvbs2_chain_decode_llr(dvbs2_chain_t* h, const int8_t* llr, int n_frames, in
 /* dvbs2_ldpc_profile / dvbs2_ldpc_kernel_name of the chain's LDPC stage (the dominant kernel) */
 int dvbs2_chain_ldpc_profile(dvbs2_chain_t* h, int enable, double* total_ms, int* launches);
 const char* dvbs2_chain_ldpc_kernel_name(const dvbs2_chain_t* h);
+/* dvbs2_ldpc_fallback_rounds of the chain's LDPC stage: zero in normal operation */
+int dvbs2_chain_ldpc_fallback_rounds(const dvbs2_chain_t* h);
 
 /* ---- upstream neighbour: the PLFRAME payload step of plsync_cc_impl::handle_payload()
  * (reference lib/plsync_cc_impl.cc:644-653, :727-795): PL descrambling (lib/pl_descrambler.cc:36-105), pilot
@@ -313,6 +315,78 @@ int dvbs2_plpayload_process_device(dvbs2_plpayload_t* h, const float* d_payload,
 /* the PL scrambling sequence Rn(i) in 0..3 (ETSI EN 302 307-1 clause 5.5.4; reference lib/pl_descrambler.cc:62-98),
  * host only; n <= 33192 */
 int dvbs2_pl_scrambling_rn(int gold_code, uint8_t* rn, int n);
+
+/* ---- PLFRAME front end (completed): everything that PRODUCES the parameters of the payload step above once frame
+ * boundaries are known, and the payload step itself from whole PLFRAMEs. What stays in the block: frame synchronisation (SOF search,
+ * lock state machine), the coarse frequency estimate (freq_sync::estimate_coarse, a multi-frame accumulator with feedback), the
+ * open-loop PLHEADER de-rotation and the rotator control messages.
+ * One handle = one gold code and one PLSC (one frame geometry, pls_info_t::parse, reference lib/pl_signaling.cc:19-61); a dummy frame
+ * (MODCOD 0) has no pilots whatever bit 0 says (:25-26); the reserved MODCODs 29..31 are refused.
+ * plframes    n_frames whole PLFRAMEs back to back as they lie in the frame-aligned symbol stream, plframe_len = 90 (n_slots + 1) +
+ *             36 n_pilots complex symbols (re, im) each, followed -- when has_trailing_header != 0 -- by the 90 PLHEADER symbols of
+ *             the frame after the batch (the pilotless estimator needs them for the last frame)
+ * coarse_corrected[f]  plframe_info_t::coarse_corrected of the frame (lib/plsync_cc_impl.cc:665); coarse_foffset[f] its coarse
+ *             frequency offset estimate (:610), read by pilotless handles only (nullable otherwise)
+ * Per frame (one wavefront each):
+ *   sof_phase       arg sum_{k<26} x_k conj(sof_k)                   freq_sync::estimate_sof_phase, lib/pl_freq_sync.cc:217-220
+ *   plheader_phase  arg sum_{k<90} x_k conj(h_k), h = PLHEADER of the HANDLE's PLSC   estimate_plheader_phase, :222-226; the CCM path
+ *                   of lib/plsync_cc_impl.cc:595-605, :634-636
+ *   pilot_phase[f * n_pilots + i] = get_pilot_phase of block i: arg of the sum of the 36 PL-descrambled pilots at payload offset
+ *                   (i + 1) 1476 - 36, minus pi/4, wrapped into [-pi, pi]   estimate_pilot_phase, :228-253, :268-273
+ *   fine_foffset    pilot mode: sum_i wrap(angle_pilot[i + 1] - angle_pilot[i]) / (2 pi 1476 n_pilots), angle_pilot[0] being the phase of
+ *                   the LAST 36 PLHEADER symbols (:263-266, :275-300); pilotless: wrap(plheader_phase[f + 1] - plheader_phase[f]) /
+ *                   (2 pi plframe_len) when |coarse_foffset[f]| <= 1 / (2 plframe_len) (:325-343). Only for coarse-corrected frames
+ *                   (lib/plsync_cc_impl.cc:665-680); otherwise fine_foffset = 0 and fine_valid = 0 (new_fine_est = false), as for the
+ *                   last frame of a pilotless batch without trailing header. This is the value control_rotator_freq takes (:683-691).
+ *   plsc_decoded    the frame's OWN PLSC, closed-loop path of lib/plsync_cc_impl.cc:582-590: PLHEADER times exp(-j sof_phase)
+ *                   (lib/pl_freq_sync.cc:429-436), then plsc_decoder::decode (lib/pl_signaling.cc:114-167) in the mode set with
+ *                   set_plsc_mode: coherent soft (default; lib/pi2_bpsk.cc:181-196, lib/reed_muller.cc:203-209), coherent hard
+ *                   (lib/pi2_bpsk.cc:45-74) or differential hard (:76-179; soft is ignored when coherent = 0), hard decisions decoded by
+ *                   minimum Hamming distance, first minimum in list order (lib/reed_muller.cc:128-141). A report: the caller drops frames
+ *                   whose PLSC is not the handle's.
+ *   set_expected_pls: the enabled-codeword list of the reference's second constructor (lib/reed_muller.cc:42-55), in the caller's order;
+ *                   n = 0 enables all 128; an index >= 128 is refused. In soft mode the metrics of disabled codewords stay 0.0 and the
+ *                   maximum runs over all 128 entries, as in the reference: a disabled index is returned when every enabled metric is
+ *                   negative. The two setters are configuration calls: not while work of the handle is in flight.
+ * xfecframes  n_frames * 90 n_slots complex symbols, bit for bit what the payload step above gives for the payload slices with
+ *             plheader_phase, pilot_phase as estimated and phase_inc = (float)(2 pi fine_foffset).
+ * Accuracy: the hard PLSC modes are exact (integer arithmetic) wherever the decision variables are not within rounding of zero. The soft
+ * mode, the phases and the frequency offset are float sums in butterfly order with atan2f, where the reference uses VOLK kernels and GNU
+ * Radio's table-driven fast_atan2f, neither of which is part of the reference tree: they are tested against a float64 model under
+ * bounds derived from the float32 format, and are UNPINNED against the genuine reference.
+ * Every array of the estimates structure is nullable (= not wanted): device pointers for the _device entries, host pointers otherwise. */
+typedef struct dvbs2_plframe dvbs2_plframe_t;
+typedef struct {
+    uint8_t* plsc_decoded;   /* n_frames */
+    float* sof_phase;        /* n_frames */
+    float* plheader_phase;   /* n_frames */
+    float* pilot_phase;      /* n_frames * n_pilots */
+    float* fine_foffset;     /* n_frames */
+    int32_t* fine_valid;     /* n_frames */
+} dvbs2_plframe_estimates_t;
+int dvbs2_plframe_create(dvbs2_plframe_t** h, int gold_code, int plsc, int max_frames, int device);
+void dvbs2_plframe_destroy(dvbs2_plframe_t* h);
+int dvbs2_plframe_params(const dvbs2_plframe_t* h, int* plframe_len, int* payload_len, int* xfecframe_len, int* n_slots, int* n_pilots,
+                         int* n_mod);
+int dvbs2_plframe_set_plsc_mode(dvbs2_plframe_t* h, int coherent, int soft);
+int dvbs2_plframe_set_expected_pls(dvbs2_plframe_t* h, const uint8_t* plsc_list, int n);
+/* estimates only */
+int dvbs2_plframe_estimate(dvbs2_plframe_t* h, const float* plframes, int n_frames, int has_trailing_header,
+                           const int32_t* coarse_corrected, const float* coarse_foffset, const dvbs2_plframe_estimates_t* est);
+int dvbs2_plframe_estimate_device(dvbs2_plframe_t* h, const float* d_plframes, int n_frames, int has_trailing_header,
+                                  const int32_t* d_coarse_corrected, const float* d_coarse_foffset,
+                                  const dvbs2_plframe_estimates_t* d_est, void* stream);
+/* estimates (est nullable) + payload step */
+int dvbs2_plframe_process(dvbs2_plframe_t* h, const float* plframes, int n_frames, int has_trailing_header,
+                          const int32_t* coarse_corrected, const float* coarse_foffset, float* xfecframes,
+                          const dvbs2_plframe_estimates_t* est);
+int dvbs2_plframe_process_device(dvbs2_plframe_t* h, const float* d_plframes, int n_frames, int has_trailing_header,
+                                 const int32_t* d_coarse_corrected, const float* d_coarse_foffset, float* d_xfecframes,
+                                 const dvbs2_plframe_estimates_t* d_est, void* stream);
+/* host only, no device needed: the 90 expected PLHEADER symbols (re, im) of a PLSC -- SOF 0x18D2E82, RM(64,7) codeword xor
+ * 0x719d83c953422dfa, pi/2 BPSK (lib/pi2_bpsk.cc:18-43, lib/pl_signaling.cc:69-73) -- and pls_info_t::parse as data */
+int dvbs2_plheader_symbols(int plsc, float* syms90);
+int dvbs2_pls_parse(int plsc, int* plframe_len, int* payload_len, int* xfecframe_len, int* n_slots, int* n_pilots, int* n_mod);
 
 /* ---- downstream neighbour: BBFRAME de-header, replaces bbdeheader_bb_impl::general_work (reference
  * lib/bbdeheader_bb_impl.cc:144-264) with parse_bbheader (:77-136) and check_crc8 (:138-142, generator
