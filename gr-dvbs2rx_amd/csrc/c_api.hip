@@ -19,7 +19,9 @@
 #include "bbdeheader_hip.h"
 #include "device_guard.h"
 #include "demap_math.hpp"
+#include "host_plan.h"
 #include <algorithm>
+#include <functional>
 
 using namespace dvbs2;
 
@@ -29,27 +31,6 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 #define HCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(DVBS2_EDEVICE, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
 #define API_TRY try {
 #define API_CATCH } catch (const std::exception& e) { return fail(DVBS2_EDEVICE, e.what()); } catch (...) { return fail(DVBS2_EDEVICE, "unknown exception"); }
-
-struct dvbs2_ldpc {
-    LdpcDecoderHip* dec = nullptr;
-    // host staging (dvbs2_ldpc_decode): device copies of the caller's buffers and two streams, so that the transfer of
-    // chunk c + 1 runs under the decode of chunk c
-    int8_t* d_in = nullptr; uint8_t* d_bits = nullptr; int8_t* d_llr = nullptr; int32_t* d_ret = nullptr;
-    // pinned landing buffers for the outputs: a device-to-host copy into pageable memory blocks the calling thread until
-    // the chunk's kernels are done, which would serialise the chunks
-    uint8_t* p_bits = nullptr; int8_t* p_llr = nullptr; int32_t* p_ret = nullptr;
-    hipStream_t stream[LdpcDecoderHip::kSlots] = {};
-    // inputs go through ONE copy stream, chunk after chunk (each copy at the full link rate, chunk 0 first), and the chunk's compute
-    // stream waits for its event: with the copies on the four compute streams a page-locked caller's chunks 0..3 shared the link and
-    // the first kernel started after FOUR chunks had arrived instead of one (round 3: page-locked callers 8 % slower than pageable ones)
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t in_ready[LdpcDecoderHip::kSlots] = {};
-    int device = 0;
-    // experiment / test knobs of the host entry, read ONCE when the handle is created (no getenv per decode call)
-    std::string host_plan;      // DVBS2_HOST_PLAN: comma list of chunk sizes, the last one repeats
-    int host_chunk = 0;         // DVBS2_HOST_CHUNK: one chunk size for the whole call (0: the measured plan)
-    int host_copy_stream = -1;  // DVBS2_HOST_COPY_STREAM: 0 / 1 force the copies off / onto the copy stream (-1: by kind of input buffer)
-};
 
 // Is [p, p + bytes) ONE page-locked host range the copy engine can address (hipHostMalloc'ed, or registered with dvbs2_host_register /
 // hipHostRegister)? Decided from the runtime's own record of the allocation that holds p -- its start and size
@@ -71,6 +52,172 @@ static bool host_range_page_locked(const void* p, size_t bytes)
     const char* lo = (const char*)start; const char* q = (const char*)p;
     return q >= lo && (size_t)(q - lo) + bytes <= size;
 }
+
+static int check_device(int device)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(DVBS2_EDEVICE, "no HIP device (this library has no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(DVBS2_EINVAL, "device index out of range");
+    return DVBS2_OK;
+}
+
+// The create sequence of every handle type H: make(o) constructs the implementation with new (std::nothrow), stores it in o and returns it.
+// A constructor that failed says so through ok() / error(): DVBS2_EINVAL, or, where hip_is_edevice, DVBS2_EDEVICE when the text names a hip call.
+template <class H, class Make> static int make_handle(H** h, int device, bool hip_is_edevice, Make make)
+{
+    if (!h) return fail(DVBS2_EINVAL, "null handle pointer");
+    *h = nullptr;
+    if (int rc = check_device(device)) return rc;
+    H* o = new (std::nothrow) H();
+    if (!o) return fail(DVBS2_EDEVICE, "out of memory");
+    o->device = device;
+    auto* impl = make(o);
+    if (!impl || !impl->ok()) {
+        const std::string msg = impl ? impl->error() : "out of memory";
+        delete impl; delete o;
+        return fail(hip_is_edevice && msg.find("hip") != std::string::npos ? DVBS2_EDEVICE : DVBS2_EINVAL, msg);
+    }
+    *h = o;
+    return DVBS2_OK;
+}
+
+static int host_chunk_env() { const char* e = getenv("DVBS2_HOST_CHUNK"); return e ? std::max(2, atoi(e)) : 0; } // 0: unset
+
+/* ------------------------------------------------------------------ chunked host pipeline (dvbs2_ldpc_decode, dvbs2_chain_decode[_llr]) */
+constexpr int kSlots = LdpcDecoderHip::kSlots;
+
+// what a handle keeps for its host-buffer entry, created on first use
+struct HostPipe {
+    hipStream_t stream[kSlots] = {}; // one per chunk slot, so that the transfer of chunk c + 1 runs under the decode of chunk c
+    // inputs go through ONE copy stream, chunk after chunk (each copy at the full link rate, chunk 0 first), and the chunk's compute
+    // stream waits for its event: with the copies on the four compute streams a page-locked caller's chunks 0..3 shared the link and
+    // the first kernel started after FOUR chunks had arrived instead of one (round 3: page-locked callers 8 % slower than pageable ones)
+    hipStream_t copy_stream = nullptr;
+    hipEvent_t in_ready[kSlots] = {};
+    // pinned landing buffers for the outputs (in the order of HostCall::outs): a device-to-host copy into pageable memory blocks the
+    // calling thread until the chunk's kernels are done, which would serialise the chunks
+    void* pinned[3] = {};
+};
+
+static int host_pipe_init(HostPipe& p)
+{
+    for (hipStream_t& st : p.stream) if (!st) HCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    if (!p.copy_stream) HCHK(hipStreamCreateWithFlags(&p.copy_stream, hipStreamNonBlocking));
+    for (hipEvent_t& ev : p.in_ready) if (!ev) HCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    return DVBS2_OK;
+}
+
+static void host_pipe_destroy(HostPipe& p) // (under the handle's DeviceGuard)
+{
+    for (hipStream_t st : p.stream) if (st) (void)hipStreamDestroy(st);
+    if (p.copy_stream) (void)hipStreamDestroy(p.copy_stream);
+    for (hipEvent_t ev : p.in_ready) if (ev) (void)hipEventDestroy(ev);
+    for (void* b : p.pinned) if (b) (void)hipHostFree(b);
+}
+
+// one output of a call, from the device staging `dev` to `user` (null: not asked for) by way of `land`: one unit of `unit_bytes` per
+// `frames_per_unit` frames (1, or the LDPC group size for the decoder's return words)
+struct HostOut { const char* dev; char* user; char* land; size_t unit_bytes; int frames_per_unit; };
+
+// what one call hands to host_pipe_run; the callables enqueue on the stream they are given and return a DVBS2_* code
+struct HostCall {
+    std::vector<std::pair<int, int>> plan; // host_chunk_plan()
+    std::vector<HostOut> outs;             // host_add_output(); fetched in this order
+    bool use_copy_stream = false;          // inputs through the copy stream + event (page-locked input), else on the chunk's own stream
+    bool shared_input = false;             // chunk 0's copy_in also brings an input that every chunk reads (the chain's single N0)
+    std::function<int(int c, int f0, int nf, hipStream_t cs)> copy_in;
+    std::function<int(int c, int f0, int nf, hipStream_t st)> enqueue; // up to and including the LDPC decode in slot c % kSlots
+    std::function<int(int f0, int nf, hipStream_t st)> after_ldpc;     // what follows it on the stream (may be empty); again after extra rounds
+};
+
+// Results land where the DMA engine can write them: straight in the caller's buffer when it is page-locked (hipHostMalloc'ed, or
+// registered once with dvbs2_host_register -- what a block does with its item buffers; the WHOLE range has to lie inside one allocation
+// / registration: host_range_page_locked), else in a pinned buffer of the handle (pinned_bytes: for max_frames) that is copied out when
+// the chunk has finished.
+static int host_add_output(HostPipe& p, HostCall& call, int n_frames, const void* dev, void* user, size_t unit_bytes, int frames_per_unit, size_t pinned_bytes)
+{
+    void*& pinned = p.pinned[call.outs.size()];
+    char* land = (char*)user;
+    if (user && !host_range_page_locked(user, (size_t)((n_frames + frames_per_unit - 1) / frames_per_unit) * unit_bytes)) {
+        if (!pinned) HCHK(hipHostMalloc(&pinned, pinned_bytes));
+        land = (char*)pinned;
+    }
+    call.outs.push_back({ (const char*)dev, (char*)user, land, unit_bytes, frames_per_unit });
+    return DVBS2_OK;
+}
+
+// The pipeline: chunk c of the plan uses slot and stream c % kSlots (its own range of the decoder's state and message buffers); its input
+// copy runs under the kernels of chunk c - 1 and its results go back while chunk c + 1 decodes.
+static int host_pipe_run(HostPipe& p, LdpcDecoderHip* dec, const HostCall& call)
+{
+    const int n_chunks = (int)call.plan.size();
+    auto span = [&](const HostOut& o, int c) { // (byte offset, bytes) of chunk c in output o
+        const int f0 = call.plan[c].first, nf = call.plan[c].second, per = o.frames_per_unit;
+        return std::pair<size_t, size_t>((size_t)(f0 / per) * o.unit_bytes, (size_t)((nf + per - 1) / per) * o.unit_bytes);
+    };
+    auto copy_out = [&](int c) -> int {
+        for (const HostOut& o : call.outs)
+            if (o.user) HCHK(hipMemcpyAsync(o.land + span(o, c).first, o.dev + span(o, c).first, span(o, c).second, hipMemcpyDeviceToHost, p.stream[c % kSlots]));
+        return DVBS2_OK;
+    };
+    auto finish = [&](int c) -> int {
+        hipStream_t st = p.stream[c % kSlots];
+        const int r = dec->finish(c % kSlots);
+        if (r < 0) return fail(DVBS2_EDEVICE, dec->error());
+        if (r > 0) { // the LDPC needed rounds beyond the enqueued ones and rewrote its output: what follows it again, and the copies
+            if (call.after_ldpc) if (int rc = call.after_ldpc(call.plan[c].first, call.plan[c].second, st)) return rc;
+            if (int rc = copy_out(c)) return rc;
+        }
+        HCHK(hipStreamSynchronize(st));
+        for (const HostOut& o : call.outs)
+            if (o.land != o.user) std::memcpy(o.user + span(o, c).first, o.land + span(o, c).first, span(o, c).second);
+        return DVBS2_OK;
+    };
+    // (a failure in the middle of the pipeline must not leave chunks in flight or slots busy: the handle stays usable)
+    auto run = [&]() -> int {
+        for (int c = 0; c < n_chunks; c++) {
+            if (c >= kSlots) if (int rc = finish(c - kSlots)) return rc;
+            const int f0 = call.plan[c].first, nf = call.plan[c].second;
+            hipStream_t st = p.stream[c % kSlots];
+            // (pageable input: the runtime stages the copy while the caller waits; the chunk's own stream)
+            if (int rc = call.copy_in(c, f0, nf, call.use_copy_stream ? p.copy_stream : st)) return rc;
+            if (call.use_copy_stream) {
+                HCHK(hipEventRecord(p.in_ready[c % kSlots], p.copy_stream));
+                HCHK(hipStreamWaitEvent(st, p.in_ready[c % kSlots], 0));
+            } else if (call.shared_input) {
+                // (the shared input travelled on chunk 0's stream: the first chunks on the other streams wait for it)
+                if (c == 0) HCHK(hipEventRecord(p.in_ready[0], st));
+                else if (c < kSlots) HCHK(hipStreamWaitEvent(st, p.in_ready[0], 0));
+            }
+            if (int rc = call.enqueue(c, f0, nf, st)) return rc;
+            if (call.after_ldpc) if (int rc = call.after_ldpc(f0, nf, st)) return rc;
+            if (int rc = copy_out(c)) return rc;
+        }
+        for (int c = std::max(0, n_chunks - kSlots); c < n_chunks; c++) if (int rc = finish(c)) return rc;
+        return DVBS2_OK;
+    };
+    const int rc = run();
+    if (rc != DVBS2_OK) { // nothing of this call stays in flight (copies into the caller's buffers included)
+        const std::string keep = g_err;
+        dec->abort_all();
+        (void)hipStreamSynchronize(p.copy_stream);
+        for (hipStream_t st : p.stream) (void)hipStreamSynchronize(st);
+        g_err = keep;
+    }
+    return rc;
+}
+
+struct dvbs2_ldpc {
+    LdpcDecoderHip* dec = nullptr;
+    // host staging (dvbs2_ldpc_decode): device copies of the caller's buffers, the pipeline's streams and pinned buffers
+    int8_t* d_in = nullptr; uint8_t* d_bits = nullptr; int8_t* d_llr = nullptr; int32_t* d_ret = nullptr;
+    HostPipe pipe;
+    int device = 0;
+    // experiment / test knobs of the host entry, read ONCE when the handle is created (no getenv per decode call)
+    std::string host_plan;      // DVBS2_HOST_PLAN: comma list of chunk sizes, the last one repeats
+    int host_chunk = 0;         // DVBS2_HOST_CHUNK: one chunk size for the whole call (0: the measured plan)
+    int host_copy_stream = -1;  // DVBS2_HOST_COPY_STREAM: 0 / 1 force the copies off / onto the copy stream (-1: by kind of input buffer)
+};
 
 extern "C" {
 
@@ -174,23 +321,12 @@ static int ldpc_make(dvbs2_ldpc_t** h, const LdpcTableDesc* t, int message_bits,
     if (!h) return fail(DVBS2_EINVAL, "null handle pointer");
     *h = nullptr;
     if (!t) return fail(DVBS2_EINVAL, "unknown LDPC table");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(DVBS2_EDEVICE, "no HIP device (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(DVBS2_EINVAL, "device index out of range");
-    dvbs2_ldpc* o = new (std::nothrow) dvbs2_ldpc();
-    if (!o) return fail(DVBS2_EDEVICE, "out of memory");
-    o->device = device;
-    if (const char* e = getenv("DVBS2_HOST_PLAN")) o->host_plan = e;
-    if (const char* e = getenv("DVBS2_HOST_CHUNK")) o->host_chunk = std::max(2, atoi(e));
-    if (const char* e = getenv("DVBS2_HOST_COPY_STREAM")) o->host_copy_stream = atoi(e) != 0 ? 1 : 0;
-    o->dec = new (std::nothrow) LdpcDecoderHip(t, message_bits, G, max_frames, device);
-    if (!o->dec || !o->dec->ok()) {
-        std::string m = o->dec ? o->dec->error() : "out of memory";
-        delete o->dec; delete o;
-        return fail(m.find("hip") != std::string::npos ? DVBS2_EDEVICE : DVBS2_EINVAL, m);
-    }
-    *h = o;
-    return DVBS2_OK;
+    return make_handle(h, device, true, [&](dvbs2_ldpc* o) {
+        if (const char* e = getenv("DVBS2_HOST_PLAN")) o->host_plan = e;
+        o->host_chunk = host_chunk_env();
+        if (const char* e = getenv("DVBS2_HOST_COPY_STREAM")) o->host_copy_stream = atoi(e) != 0 ? 1 : 0;
+        return o->dec = new (std::nothrow) LdpcDecoderHip(t, message_bits, G, max_frames, device);
+    });
 }
 
 int dvbs2_ldpc_create(dvbs2_ldpc_t** h, int standard, int framesize, int rate, int group_size, int max_frames, int device)
@@ -214,12 +350,7 @@ void dvbs2_ldpc_destroy(dvbs2_ldpc_t* h)
     if (!h) return;
     DeviceGuard g(h->device);
     (void)hipFree(h->d_in); (void)hipFree(h->d_bits); (void)hipFree(h->d_llr); (void)hipFree(h->d_ret);
-    if (h->p_bits) (void)hipHostFree(h->p_bits);
-    if (h->p_llr) (void)hipHostFree(h->p_llr);
-    if (h->p_ret) (void)hipHostFree(h->p_ret);
-    for (hipStream_t st : h->stream) if (st) (void)hipStreamDestroy(st);
-    if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
-    for (hipEvent_t ev : h->in_ready) if (ev) (void)hipEventDestroy(ev);
+    host_pipe_destroy(h->pipe);
     delete h->dec;
     delete h;
 }
@@ -284,113 +415,34 @@ int dvbs2_ldpc_decode(dvbs2_ldpc_t* h, const int8_t* llr_in, int n_frames, int m
     if (n_frames == 0) return DVBS2_OK;
     DeviceGuard guard(h->device);
     if (!guard.ok) return fail(DVBS2_EDEVICE, "hipSetDevice failed");
-    const size_t N = h->dec->N(), mf = h->dec->max_frames();
-    const int G = h->dec->group_size();
-    for (hipStream_t& st : h->stream) if (!st) HCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    if (!h->copy_stream) HCHK(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-    for (hipEvent_t& ev : h->in_ready) if (!ev) HCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    LdpcDecoderHip* dec = h->dec;
+    const size_t N = dec->N(), mf = dec->max_frames();
+    const int G = dec->group_size();
+    const size_t ret_bytes = ((mf + G - 1) / G + kSlots) * 4;
+    if (int rc = host_pipe_init(h->pipe)) return rc;
     if (!h->d_in) HCHK(hipMalloc(&h->d_in, mf * N));
     if (!h->d_bits) HCHK(hipMalloc(&h->d_bits, mf * (N / 8)));
     if (!h->d_llr) HCHK(hipMalloc(&h->d_llr, mf * N));
-    if (!h->d_ret) HCHK(hipMalloc(&h->d_ret, ((mf + G - 1) / G + LdpcDecoderHip::kSlots) * 4));
-    const size_t out_bytes = (out_mode ? h->dec->out_bits_message() : (int)N) / 8;
-    // Results land where the DMA engine can write them: straight in the caller's buffer when it is page-locked (hipHostMalloc'ed, or
-    // registered once with dvbs2_host_register -- what a block does with its item buffers), else in a pinned buffer of the handle
-    // that is copied out when the chunk has finished.
-    // (the WHOLE range has to lie inside one page-locked allocation / registration: host_range_page_locked)
-    auto page_locked = [](const void* p, size_t bytes) { return host_range_page_locked(p, bytes); };
-    const size_t n_groups = ((size_t)n_frames + G - 1) / G;
-    uint8_t* bits_land = page_locked(bits_out, (size_t)n_frames * out_bytes) ? bits_out : nullptr;
-    int8_t* llr_land = page_locked(llr_out, (size_t)n_frames * N) ? llr_out : nullptr;
-    int32_t* ret_land = page_locked(ret, n_groups * 4) ? ret : nullptr;
-    if (!bits_land) { if (!h->p_bits) HCHK(hipHostMalloc(&h->p_bits, mf * (N / 8))); bits_land = h->p_bits; }
-    if (ret && !ret_land) { if (!h->p_ret) HCHK(hipHostMalloc(&h->p_ret, ((mf + G - 1) / G + LdpcDecoderHip::kSlots) * 4)); ret_land = h->p_ret; }
-    if (llr_out && !llr_land) { if (!h->p_llr) HCHK(hipHostMalloc(&h->p_llr, mf * N)); llr_land = h->p_llr; }
-    // The call is cut into chunks of whole groups (an even number of frames: two frames per workgroup); chunk c uses slot and stream
-    // c % kSlots (its own range of the state and message buffers), so that transfers and decodes of neighbouring chunks overlap.
-    int unit = G % 2 ? 2 * G : G;
-    const bool in_locked = page_locked(llr_in, (size_t)n_frames * N);
-    // Plan of the call, as (first frame, frames) chunks of whole groups. The decode of a chunk starts when its input has arrived and a
-    // launch of up to 512 frames (one frame pair per CU) takes as long as a smaller one, so the FIRST chunk is 512 frames; every further
-    // chunk boundary costs a launch gap that the single resident launch does not have. Pageable input: the runtime stages the copy
-    // through its own pinned buffer while the calling thread waits, so the copy of chunk c + 1 has to run under the decode of chunk c:
-    // chunks of 1024. Page-locked input (dvbs2_host_register / hipHostMalloc): the link moves 57 GB/s (bench.py host_link), the whole
-    // input of 4096 normal frames arrives in under 5 ms through the copy stream: one large middle chunk, and a small last one so that
-    // little output is left to fetch when the decode ends.
-    std::vector<std::pair<int, int>> plan;
-    auto round_unit = [&](int x) { return std::max(unit, (x + unit - 1) / unit * unit); };
-    if (!h->host_plan.empty()) { // experiments: comma list of chunk sizes, the last one repeats
-        int f0 = 0, last = 512;
-        for (const char* q = h->host_plan.c_str(); f0 < n_frames;) {
-            if (*q) { last = std::max(2, atoi(q)); while (*q && *q != ',') q++; if (*q == ',') q++; }
-            const int nf = std::min(round_unit(last), n_frames - f0);
-            plan.push_back({ f0, nf }); f0 += nf;
-        }
-    } else if (in_locked && n_frames > 1024 && !h->host_chunk) {
-        // measured (MI355X, 4096 frames of table B4, tools/host_entry_ab.py): 512 | 3072 | 512 -> 97.3 % of the resident rate, 512 | 3584
-        // 97.3 %, 512 | 1536 | 1536 | 512 96.7 %, eight chunks of 512 93.6 %, four of 1024 95.0 %
-        // every boundary is a multiple of `unit` (frame_base of enqueue()) and none lies past the call's last frame (a group size above
-        // 512 -- or an odd one above 256 -- makes `unit` larger than the first chunk: ADVICE r4)
-        const int b1 = std::min(round_unit(512), n_frames);
-        const int b2 = std::min(std::max(b1, (n_frames - 512) / unit * unit), n_frames);
-        const int bounds[4] = { 0, b1, b2, n_frames };
-        for (int k = 0; k < 3; k++) if (bounds[k + 1] > bounds[k]) plan.push_back({ bounds[k], bounds[k + 1] - bounds[k] });
-    } else {
-        // pageable input (measured as above): 512, then chunks of 1024 -> 96.0-96.5 %; eight equal chunks of 512 95.0-95.4 %
-        int first = 512, chunk = std::max(1024, (n_frames + 7) / 8);
-        if (h->host_chunk) first = chunk = h->host_chunk; // experiments, tests
-        first = round_unit(first); chunk = round_unit(chunk);
-        for (int f0 = 0; f0 < n_frames;) { const int nf = std::min(f0 ? chunk : first, n_frames - f0); plan.push_back({ f0, nf }); f0 += nf; }
-    }
-    const int n_chunks = (int)plan.size();
-    bool use_copy_stream = in_locked;
-    if (h->host_copy_stream >= 0) use_copy_stream = h->host_copy_stream != 0; // experiments
-    auto copy_out = [&](int c) -> int {
-        const int f0 = plan[c].first, nf = plan[c].second;
-        hipStream_t st = h->stream[c % LdpcDecoderHip::kSlots];
-        HCHK(hipMemcpyAsync(bits_land + (size_t)f0 * out_bytes, h->d_bits + (size_t)f0 * out_bytes, (size_t)nf * out_bytes, hipMemcpyDeviceToHost, st));
-        if (llr_out) HCHK(hipMemcpyAsync(llr_land + (size_t)f0 * N, h->d_llr + (size_t)f0 * N, (size_t)nf * N, hipMemcpyDeviceToHost, st));
-        if (ret) HCHK(hipMemcpyAsync(ret_land + f0 / G, h->d_ret + f0 / G, (size_t)((nf + G - 1) / G) * 4, hipMemcpyDeviceToHost, st));
+    if (!h->d_ret) HCHK(hipMalloc(&h->d_ret, ret_bytes));
+    const size_t out_bytes = (out_mode ? dec->out_bits_message() : (int)N) / 8;
+    HostCall call;
+    if (int rc = host_add_output(h->pipe, call, n_frames, h->d_bits, bits_out, out_bytes, 1, mf * (N / 8))) return rc;
+    if (int rc = host_add_output(h->pipe, call, n_frames, h->d_llr, llr_out, N, 1, mf * N)) return rc;
+    if (int rc = host_add_output(h->pipe, call, n_frames, h->d_ret, ret, 4, G, ret_bytes)) return rc;
+    const bool in_locked = host_range_page_locked(llr_in, (size_t)n_frames * N);
+    call.plan = host_chunk_plan(n_frames, G, in_locked, false, h->host_chunk, h->host_plan);
+    call.use_copy_stream = h->host_copy_stream >= 0 ? h->host_copy_stream != 0 : in_locked; // (DVBS2_HOST_COPY_STREAM: experiments)
+    call.copy_in = [&](int, int f0, int nf, hipStream_t cs) -> int {
+        HCHK(hipMemcpyAsync(h->d_in + (size_t)f0 * N, llr_in + (size_t)f0 * N, (size_t)nf * N, hipMemcpyHostToDevice, cs));
         return DVBS2_OK;
     };
-    auto finish = [&](int c) -> int {
-        const int r = h->dec->finish(c % LdpcDecoderHip::kSlots);
-        if (r < 0) return fail(DVBS2_EDEVICE, h->dec->error());
-        if (r > 0) { if (int rc = copy_out(c)) return rc; } // outputs rewritten by the extra rounds: fetch them again
-        HCHK(hipStreamSynchronize(h->stream[c % LdpcDecoderHip::kSlots]));
-        const int f0 = plan[c].first, nf = plan[c].second;
-        if (bits_land != bits_out) std::memcpy(bits_out + (size_t)f0 * out_bytes, bits_land + (size_t)f0 * out_bytes, (size_t)nf * out_bytes);
-        if (llr_out && llr_land != llr_out) std::memcpy(llr_out + (size_t)f0 * N, llr_land + (size_t)f0 * N, (size_t)nf * N);
-        if (ret && ret_land != ret) std::memcpy(ret + f0 / G, ret_land + f0 / G, (size_t)((nf + G - 1) / G) * 4);
+    call.enqueue = [&](int c, int f0, int nf, hipStream_t st) -> int {
+        if (dec->enqueue(h->d_in + (size_t)f0 * N, nf, max_trials, out_mode, h->d_bits + (size_t)f0 * out_bytes,
+                         llr_out ? h->d_llr + (size_t)f0 * N : nullptr, h->d_ret + f0 / G, st, c % kSlots, f0))
+            return fail(DVBS2_EDEVICE, dec->error());
         return DVBS2_OK;
     };
-    // (a failure in the middle of the pipeline must not leave chunks in flight or slots busy: the handle stays usable)
-    auto run = [&]() -> int {
-        for (int c = 0; c < n_chunks; c++) {
-            if (c >= LdpcDecoderHip::kSlots) if (int rc = finish(c - LdpcDecoderHip::kSlots)) return rc;
-            const int f0 = plan[c].first, nf = plan[c].second;
-            hipStream_t st = h->stream[c % LdpcDecoderHip::kSlots];
-            if (use_copy_stream) {
-                HCHK(hipMemcpyAsync(h->d_in + (size_t)f0 * N, llr_in + (size_t)f0 * N, (size_t)nf * N, hipMemcpyHostToDevice, h->copy_stream));
-                HCHK(hipEventRecord(h->in_ready[c % LdpcDecoderHip::kSlots], h->copy_stream));
-                HCHK(hipStreamWaitEvent(st, h->in_ready[c % LdpcDecoderHip::kSlots], 0));
-            } else
-                HCHK(hipMemcpyAsync(h->d_in + (size_t)f0 * N, llr_in + (size_t)f0 * N, (size_t)nf * N, hipMemcpyHostToDevice, st));
-            if (h->dec->enqueue(h->d_in + (size_t)f0 * N, nf, max_trials, out_mode, h->d_bits + (size_t)f0 * out_bytes,
-                                llr_out ? h->d_llr + (size_t)f0 * N : nullptr, h->d_ret + f0 / G, st, c % LdpcDecoderHip::kSlots, f0))
-                return fail(DVBS2_EDEVICE, h->dec->error());
-            if (int rc = copy_out(c)) return rc;
-        }
-        for (int c = std::max(0, n_chunks - LdpcDecoderHip::kSlots); c < n_chunks; c++) if (int rc = finish(c)) return rc;
-        return DVBS2_OK;
-    };
-    const int rc = run();
-    if (rc != DVBS2_OK) { // nothing of this call stays in flight (copies into the caller's buffers included)
-        h->dec->abort_all();
-        (void)hipStreamSynchronize(h->copy_stream);
-        for (hipStream_t st : h->stream) (void)hipStreamSynchronize(st);
-    }
-    return rc;
+    return host_pipe_run(h->pipe, dec, call); // (nothing after the LDPC: outputs that extra rounds rewrote are only fetched again)
     API_CATCH
 }
 
@@ -562,30 +614,9 @@ struct dvbs2_bch {
     int device = 0;
 };
 
-static int check_device(int device)
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(DVBS2_EDEVICE, "no HIP device (this library has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(DVBS2_EINVAL, "device index out of range");
-    return DVBS2_OK;
-}
-
 static int bch_make(dvbs2_bch_t** h, int m, uint32_t prim_poly, int t, int n, int max_frames, int device)
 {
-    if (!h) return fail(DVBS2_EINVAL, "null handle pointer");
-    *h = nullptr;
-    if (int rc = check_device(device)) return rc;
-    dvbs2_bch* o = new (std::nothrow) dvbs2_bch();
-    if (!o) return fail(DVBS2_EDEVICE, "out of memory");
-    o->device = device;
-    o->dec = new (std::nothrow) BchDecoderHip(m, prim_poly, t, n, max_frames, device);
-    if (!o->dec || !o->dec->ok()) {
-        std::string msg = o->dec ? o->dec->error() : "out of memory";
-        delete o->dec; delete o;
-        return fail(msg.find("hip") != std::string::npos ? DVBS2_EDEVICE : DVBS2_EINVAL, msg);
-    }
-    *h = o;
-    return DVBS2_OK;
+    return make_handle(h, device, true, [&](dvbs2_bch* o) { return o->dec = new (std::nothrow) BchDecoderHip(m, prim_poly, t, n, max_frames, device); });
 }
 
 static void bch_field(int framesize, int* m, uint32_t* prim)
@@ -707,16 +738,7 @@ extern "C" {
 int dvbs2_demap_create(dvbs2_demap_t** h, int framesize, int rate, int constellation, int max_frames, int device)
 {
     API_TRY
-    if (!h) return fail(DVBS2_EINVAL, "null handle pointer");
-    *h = nullptr;
-    if (int rc = check_device(device)) return rc;
-    dvbs2_demap* o = new (std::nothrow) dvbs2_demap();
-    if (!o) return fail(DVBS2_EDEVICE, "out of memory");
-    o->device = device;
-    o->dm = new (std::nothrow) DemapperHip(framesize, rate, constellation, max_frames, device);
-    if (!o->dm || !o->dm->ok()) { std::string msg = o->dm ? o->dm->error() : "out of memory"; delete o->dm; delete o; return fail(DVBS2_EINVAL, msg); }
-    *h = o;
-    return DVBS2_OK;
+    return make_handle(h, device, false, [&](dvbs2_demap* o) { return o->dm = new (std::nothrow) DemapperHip(framesize, rate, constellation, max_frames, device); });
     API_CATCH
 }
 
@@ -843,12 +865,9 @@ struct dvbs2_chain {
     // the call between enqueue and finish
     bool pending = false; int n_frames = 0; uint8_t* d_msg = nullptr; int32_t* d_bch_corr = nullptr; void* stream = nullptr;
     // host-pointer entries (dvbs2_chain_decode / dvbs2_chain_decode_llr): device copies of the caller's buffers, pinned landing buffers for
-    // the outputs of a pageable caller, one stream per chunk slot + one copy stream (the plan of dvbs2_ldpc_decode)
+    // the outputs of a pageable caller and the streams in `pipe` (as dvbs2_ldpc_decode)
     float* hd_syms = nullptr; int8_t* hd_llr = nullptr; float* hd_n0 = nullptr; uint8_t* hd_msg = nullptr; int32_t* hd_ret = nullptr; int32_t* hd_corr = nullptr;
-    uint8_t* p_msg = nullptr; int32_t* p_ret = nullptr; int32_t* p_corr = nullptr;
-    hipStream_t hstream[LdpcDecoderHip::kSlots] = {};
-    hipStream_t hcopy = nullptr;
-    hipEvent_t h_in_ready[LdpcDecoderHip::kSlots] = {};
+    HostPipe pipe;
     int host_chunk = 0; // DVBS2_HOST_CHUNK (experiments, tests), read once at create
 };
 
@@ -860,7 +879,7 @@ static int chain_make(dvbs2_chain_t** h, int standard, int framesize, int rate, 
     dvbs2_chain* o = new (std::nothrow) dvbs2_chain();
     if (!o) return fail(DVBS2_EDEVICE, "out of memory");
     o->device = device; o->max_frames = max_frames;
-    if (const char* e = getenv("DVBS2_HOST_CHUNK")) o->host_chunk = std::max(2, atoi(e));
+    o->host_chunk = host_chunk_env();
     int rc = DVBS2_OK;
     if (with_demap) rc = dvbs2_demap_create(&o->dm, framesize, rate, constellation, max_frames, device);
     if (rc == DVBS2_OK) rc = dvbs2_ldpc_create(&o->ldpc, standard, framesize, rate, group_size, max_frames, device);
@@ -919,12 +938,7 @@ void dvbs2_chain_destroy(dvbs2_chain_t* h)
     dvbs2_demap_destroy(h->dm); dvbs2_ldpc_destroy(h->ldpc); dvbs2_bch_destroy(h->bch);
     (void)hipFree(h->d_llr); (void)hipFree(h->d_bits); (void)hipFree(h->d_corr);
     (void)hipFree(h->hd_syms); (void)hipFree(h->hd_llr); (void)hipFree(h->hd_n0); (void)hipFree(h->hd_msg); (void)hipFree(h->hd_ret); (void)hipFree(h->hd_corr);
-    if (h->p_msg) (void)hipHostFree(h->p_msg);
-    if (h->p_ret) (void)hipHostFree(h->p_ret);
-    if (h->p_corr) (void)hipHostFree(h->p_corr);
-    for (hipStream_t st : h->hstream) if (st) (void)hipStreamDestroy(st);
-    if (h->hcopy) (void)hipStreamDestroy(h->hcopy);
-    for (hipEvent_t ev : h->h_in_ready) if (ev) (void)hipEventDestroy(ev);
+    host_pipe_destroy(h->pipe);
     delete h;
 }
 
@@ -1040,8 +1054,8 @@ int dvbs2_chain_decode_llr_device(dvbs2_chain_t* h, const int8_t* d_llr, int n_f
 
 // Host-pointer form of the fused chain (SURVEY 8(b) "dvbs2_fec_chain_decode(syms -> msg bytes)"): what the three blocks do with the
 // item buffers GNU Radio hands them (lib/xfecframe_demapper_cb_impl.cc:101-186 -> lib/ldpc_decoder_bb_impl.cc:394-455 ->
-// lib/bch_decoder_bb_impl.cc:84-117), as ONE call. The call is cut into chunks of whole LDPC groups exactly like dvbs2_ldpc_decode:
-// chunk c runs on stream c mod kSlots in its own range of the LDPC state / message buffers and of the BCH syndrome words, its input
+// lib/bch_decoder_bb_impl.cc:84-117), as ONE call. The call is cut into chunks of whole LDPC groups and goes through host_pipe_run like
+// dvbs2_ldpc_decode: chunk c runs on stream c mod kSlots in its own range of the LDPC state / message buffers and of the BCH syndrome words, its input
 // copy (through one copy stream when the caller's buffer is page-locked) runs under the kernels of chunk c - 1 and its results go
 // back while chunk c + 1 decodes. An 8PSK normal frame is 172.8 KB of symbols in and ~6 KB out: at the ~57 GB/s of the host link the
 // chain is LINK-bound near 320 k frames/s -- below what the kernels do at a receiver's operating point (bench.py config3_host).
@@ -1058,126 +1072,53 @@ static int chain_decode_host(dvbs2_chain_t* h, const float* in_syms, const int8_
     if (n_frames == 0) return DVBS2_OK;
     DeviceGuard guard(h->device);
     if (!guard.ok) return fail(DVBS2_EDEVICE, "hipSetDevice failed");
-    constexpr int kSl = LdpcDecoderHip::kSlots;
     LdpcDecoderHip* dec = h->ldpc->dec;
     const size_t N = (size_t)dec->N(), mf = (size_t)h->max_frames, mb = (size_t)h->msg_bytes;
     const size_t ns = h->dm ? (size_t)h->dm->dm->n_syms() : 0;
     const int G = dec->group_size();
-    for (hipStream_t& st : h->hstream) if (!st) HCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    if (!h->hcopy) HCHK(hipStreamCreateWithFlags(&h->hcopy, hipStreamNonBlocking));
-    for (hipEvent_t& ev : h->h_in_ready) if (!ev) HCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    const size_t ret_bytes = ((mf + G - 1) / G + kSlots) * 4;
+    if (int rc = host_pipe_init(h->pipe)) return rc;
     const bool fused = in_syms && dec->fused_demap_supported(); // symbols -> LDS inside the sweep kernel; else demapper launch -> LLR buffer
     if (in_syms && !h->hd_syms) HCHK(hipMalloc(&h->hd_syms, mf * ns * 8));
     if (in_syms && !h->hd_n0) HCHK(hipMalloc(&h->hd_n0, mf * 4));
     if ((in_llr || !fused) && !h->hd_llr) HCHK(hipMalloc(&h->hd_llr, mf * N));
     if (!h->hd_msg) HCHK(hipMalloc(&h->hd_msg, mf * mb));
-    if (!h->hd_ret) HCHK(hipMalloc(&h->hd_ret, ((mf + G - 1) / G + kSl) * 4));
+    if (!h->hd_ret) HCHK(hipMalloc(&h->hd_ret, ret_bytes));
     if (!h->hd_corr) HCHK(hipMalloc(&h->hd_corr, mf * 4));
-    const size_t n_groups = ((size_t)n_frames + G - 1) / G;
-    uint8_t* msg_land = host_range_page_locked(msg, (size_t)n_frames * mb) ? msg : nullptr;
-    int32_t* ret_land = host_range_page_locked(ldpc_ret, n_groups * 4) ? ldpc_ret : nullptr;
-    int32_t* corr_land = host_range_page_locked(bch_corr, (size_t)n_frames * 4) ? bch_corr : nullptr;
-    if (!msg_land) { if (!h->p_msg) HCHK(hipHostMalloc(&h->p_msg, mf * mb)); msg_land = h->p_msg; }
-    if (ldpc_ret && !ret_land) { if (!h->p_ret) HCHK(hipHostMalloc(&h->p_ret, ((mf + G - 1) / G + kSl) * 4)); ret_land = h->p_ret; }
-    if (bch_corr && !corr_land) { if (!h->p_corr) HCHK(hipHostMalloc(&h->p_corr, mf * 4)); corr_land = h->p_corr; }
+    HostCall call;
+    if (int rc = host_add_output(h->pipe, call, n_frames, h->hd_msg, msg, mb, 1, mf * mb)) return rc;
+    if (int rc = host_add_output(h->pipe, call, n_frames, h->hd_ret, ldpc_ret, 4, G, ret_bytes)) return rc;
+    if (int rc = host_add_output(h->pipe, call, n_frames, h->hd_corr, bch_corr, 4, 1, mf * 4)) return rc;
     const void* in_ptr = in_syms ? (const void*)in_syms : (const void*)in_llr;
     const size_t in_frame_bytes = in_syms ? ns * 8 : N;
     const bool in_locked = host_range_page_locked(in_ptr, (size_t)n_frames * in_frame_bytes);
-    // chunk plan: as dvbs2_ldpc_decode (first chunk 512 frames = one launch wave of frame pairs; page-locked input: one large middle chunk
-    // and a small last one; pageable input: chunks of 1024 so that the staged copy of chunk c + 1 runs under the decode of chunk c)
-    const int unit = G % 2 ? 2 * G : G;
-    auto round_unit = [&](int x) { return std::max(unit, (x + unit - 1) / unit * unit); };
-    std::vector<std::pair<int, int>> plan;
-    if (in_syms && in_locked && !h->host_chunk) {
-        // SYMBOL input is 8 bytes per symbol (172.8 KB per 8PSK normal frame, 2.7 x the LLR bytes): at a receiver's operating point the copy of a
-        // chunk takes longer than its kernels, so page-locked input goes in uniform chunks of 512 frames (one launch wave of the GPU) -- the copy of
-        // chunk c + 1 runs under the kernels of chunk c and the call ends one chunk's kernels after its last byte arrived. Measured (MI355X, 4096
-        // frames of 8PSK 3/4 normal, page-locked buffers): 512 | 3072 | 512 (the LDPC entry's plan) 221 k frames/s at Es/N0 8.5 dB = 0.67 of the link
-        // bound -- the GPU idles while 531 MB arrive -- and 0.853 of the resident rate on never-converging input; uniform 512: 291 k (0.88 of the
-        // link bound) and 0.899. Chunks of 128 for 512-frame calls LOSE (a launch of 128 frames takes as long as one of 512): 181 -> 144 k.
-        const int chunk = round_unit(512);
-        for (int f0 = 0; f0 < n_frames; f0 += chunk) plan.push_back({ f0, std::min(chunk, n_frames - f0) });
-    } else if (in_locked && n_frames > 1024 && !h->host_chunk) {
-        const int b1 = std::min(round_unit(512), n_frames);
-        const int b2 = std::min(std::max(b1, (n_frames - 512) / unit * unit), n_frames);
-        const int bounds[4] = { 0, b1, b2, n_frames };
-        for (int k = 0; k < 3; k++) if (bounds[k + 1] > bounds[k]) plan.push_back({ bounds[k], bounds[k + 1] - bounds[k] });
-    } else {
-        int first = 512, chunk = std::max(1024, (n_frames + 7) / 8);
-        if (h->host_chunk) first = chunk = h->host_chunk;
-        first = round_unit(first); chunk = round_unit(chunk);
-        for (int f0 = 0; f0 < n_frames;) { const int nf = std::min(f0 ? chunk : first, n_frames - f0); plan.push_back({ f0, nf }); f0 += nf; }
-    }
-    const int n_chunks = (int)plan.size();
-    auto copy_out = [&](int c) -> int {
-        const int f0 = plan[c].first, nf = plan[c].second;
-        hipStream_t st = h->hstream[c % kSl];
-        HCHK(hipMemcpyAsync(msg_land + (size_t)f0 * mb, h->hd_msg + (size_t)f0 * mb, (size_t)nf * mb, hipMemcpyDeviceToHost, st));
-        if (ldpc_ret) HCHK(hipMemcpyAsync(ret_land + f0 / G, h->hd_ret + f0 / G, (size_t)((nf + G - 1) / G) * 4, hipMemcpyDeviceToHost, st));
-        if (bch_corr) HCHK(hipMemcpyAsync(corr_land + f0, h->hd_corr + f0, (size_t)nf * 4, hipMemcpyDeviceToHost, st));
+    call.plan = host_chunk_plan(n_frames, G, in_locked, in_syms != nullptr, h->host_chunk, "");
+    call.use_copy_stream = in_locked;
+    call.shared_input = in_syms && n0_count == 1;
+    call.copy_in = [&](int c, int f0, int nf, hipStream_t cs) -> int {
+        if (in_syms) {
+            HCHK(hipMemcpyAsync(h->hd_syms + (size_t)f0 * ns * 2, in_syms + (size_t)f0 * ns * 2, (size_t)nf * ns * 8, hipMemcpyHostToDevice, cs));
+            if (n0_count > 1) HCHK(hipMemcpyAsync(h->hd_n0 + f0, n0 + f0, (size_t)nf * 4, hipMemcpyHostToDevice, cs));
+            else if (c == 0) HCHK(hipMemcpyAsync(h->hd_n0, n0, 4, hipMemcpyHostToDevice, cs));
+        } else
+            HCHK(hipMemcpyAsync(h->hd_llr + (size_t)f0 * N, in_llr + (size_t)f0 * N, (size_t)nf * N, hipMemcpyHostToDevice, cs));
         return DVBS2_OK;
     };
-    auto finish = [&](int c) -> int {
-        const int f0 = plan[c].first, nf = plan[c].second;
-        hipStream_t st = h->hstream[c % kSl];
-        const int r = dec->finish(c % kSl);
-        if (r < 0) return fail(DVBS2_EDEVICE, dec->error());
-        if (r > 0) { // the LDPC needed rounds beyond the enqueued ones and rewrote its state: BCH and the copies again
-            if (int rc = chain_bch_range(h, f0, nf, h->hd_msg + (size_t)f0 * mb, h->hd_corr + f0, st)) return rc;
-            if (int rc = copy_out(c)) return rc;
+    call.enqueue = [&](int c, int f0, int nf, hipStream_t st) -> int {
+        const float* dn0 = n0_count > 1 ? h->hd_n0 + f0 : h->hd_n0;
+        const float* dsy = in_syms ? h->hd_syms + (size_t)f0 * ns * 2 : nullptr;
+        int erc;
+        if (fused) {
+            const DemapFused dm = h->dm->dm->fused(dsy, dn0, n0_count > 1 ? nf : 1);
+            erc = dec->enqueue(nullptr, nf, max_trials, DVBS2_OM_MESSAGE, nullptr, nullptr, h->hd_ret + f0 / G, st, c % kSlots, f0, &dm);
+        } else {
+            if (in_syms && h->dm->dm->soft_device(dsy, nf, dn0, n0_count > 1 ? nf : 1, h->hd_llr + (size_t)f0 * N, st)) return fail(DVBS2_EDEVICE, h->dm->dm->error());
+            erc = dec->enqueue(h->hd_llr + (size_t)f0 * N, nf, max_trials, DVBS2_OM_MESSAGE, nullptr, nullptr, h->hd_ret + f0 / G, st, c % kSlots, f0, nullptr);
         }
-        HCHK(hipStreamSynchronize(st));
-        if (msg_land != msg) std::memcpy(msg + (size_t)f0 * mb, msg_land + (size_t)f0 * mb, (size_t)nf * mb);
-        if (ldpc_ret && ret_land != ldpc_ret) std::memcpy(ldpc_ret + f0 / G, ret_land + f0 / G, (size_t)((nf + G - 1) / G) * 4);
-        if (bch_corr && corr_land != bch_corr) std::memcpy(bch_corr + f0, corr_land + f0, (size_t)nf * 4);
-        return DVBS2_OK;
+        return erc ? fail(DVBS2_EDEVICE, dec->error()) : DVBS2_OK;
     };
-    auto run = [&]() -> int {
-        for (int c = 0; c < n_chunks; c++) {
-            if (c >= kSl) if (int rc = finish(c - kSl)) return rc;
-            const int f0 = plan[c].first, nf = plan[c].second;
-            hipStream_t st = h->hstream[c % kSl];
-            hipStream_t cs = in_locked ? h->hcopy : st; // (pageable input: the runtime stages the copy while the caller waits; its own stream)
-            if (in_syms) {
-                HCHK(hipMemcpyAsync(h->hd_syms + (size_t)f0 * ns * 2, in_syms + (size_t)f0 * ns * 2, (size_t)nf * ns * 8, hipMemcpyHostToDevice, cs));
-                if (n0_count > 1) HCHK(hipMemcpyAsync(h->hd_n0 + f0, n0 + f0, (size_t)nf * 4, hipMemcpyHostToDevice, cs));
-                else if (c == 0) HCHK(hipMemcpyAsync(h->hd_n0, n0, 4, hipMemcpyHostToDevice, cs));
-            } else
-                HCHK(hipMemcpyAsync(h->hd_llr + (size_t)f0 * N, in_llr + (size_t)f0 * N, (size_t)nf * N, hipMemcpyHostToDevice, cs));
-            if (cs != st) {
-                HCHK(hipEventRecord(h->h_in_ready[c % kSl], cs));
-                HCHK(hipStreamWaitEvent(st, h->h_in_ready[c % kSl], 0));
-            } else if (in_syms && n0_count == 1 && c > 0 && c < kSl) {
-                // (the single N0 travelled on chunk 0's stream: the first chunks on the other streams wait for it)
-                HCHK(hipStreamWaitEvent(st, h->h_in_ready[0], 0));
-            }
-            if (cs == st && in_syms && n0_count == 1 && c == 0) HCHK(hipEventRecord(h->h_in_ready[0], st));
-            const float* dn0 = n0_count > 1 ? h->hd_n0 + f0 : h->hd_n0;
-            const float* dsy = in_syms ? h->hd_syms + (size_t)f0 * ns * 2 : nullptr;
-            int erc;
-            if (fused) {
-                const DemapFused dm = h->dm->dm->fused(dsy, dn0, n0_count > 1 ? nf : 1);
-                erc = dec->enqueue(nullptr, nf, max_trials, DVBS2_OM_MESSAGE, nullptr, nullptr, h->hd_ret + f0 / G, st, c % kSl, f0, &dm);
-            } else {
-                if (in_syms && h->dm->dm->soft_device(dsy, nf, dn0, n0_count > 1 ? nf : 1, h->hd_llr + (size_t)f0 * N, st)) return fail(DVBS2_EDEVICE, h->dm->dm->error());
-                erc = dec->enqueue(h->hd_llr + (size_t)f0 * N, nf, max_trials, DVBS2_OM_MESSAGE, nullptr, nullptr, h->hd_ret + f0 / G, st, c % kSl, f0, nullptr);
-            }
-            if (erc) return fail(DVBS2_EDEVICE, dec->error());
-            if (int rc = chain_bch_range(h, f0, nf, h->hd_msg + (size_t)f0 * mb, h->hd_corr + f0, st)) return rc;
-            if (int rc = copy_out(c)) return rc;
-        }
-        for (int c = std::max(0, n_chunks - kSl); c < n_chunks; c++) if (int rc = finish(c)) return rc;
-        return DVBS2_OK;
-    };
-    const int rc = run();
-    if (rc != DVBS2_OK) { // nothing of this call stays in flight (copies into the caller's buffers included)
-        const std::string keep = g_err;
-        dec->abort_all();
-        (void)hipStreamSynchronize(h->hcopy);
-        for (hipStream_t st : h->hstream) (void)hipStreamSynchronize(st);
-        g_err = keep;
-    }
-    return rc;
+    call.after_ldpc = [&](int f0, int nf, hipStream_t st) -> int { return chain_bch_range(h, f0, nf, h->hd_msg + (size_t)f0 * mb, h->hd_corr + f0, st); };
+    return host_pipe_run(h->pipe, dec, call);
 }
 
 extern "C" {
@@ -1223,16 +1164,7 @@ int dvbs2_pl_scrambling_rn(int gold_code, uint8_t* rn, int n)
 int dvbs2_plpayload_create(dvbs2_plpayload_t** h, int gold_code, int n_slots, int has_pilots, int max_frames, int device)
 {
     API_TRY
-    if (!h) return fail(DVBS2_EINVAL, "null handle pointer");
-    *h = nullptr;
-    if (int rc = check_device(device)) return rc;
-    dvbs2_plpayload* o = new (std::nothrow) dvbs2_plpayload();
-    if (!o) return fail(DVBS2_EDEVICE, "out of memory");
-    o->device = device;
-    o->pp = new (std::nothrow) PlPayloadHip(gold_code, n_slots, has_pilots, max_frames, device);
-    if (!o->pp || !o->pp->ok()) { std::string msg = o->pp ? o->pp->error() : "out of memory"; delete o->pp; delete o; return fail(DVBS2_EINVAL, msg); }
-    *h = o;
-    return DVBS2_OK;
+    return make_handle(h, device, false, [&](dvbs2_plpayload* o) { return o->pp = new (std::nothrow) PlPayloadHip(gold_code, n_slots, has_pilots, max_frames, device); });
     API_CATCH
 }
 
@@ -1399,14 +1331,7 @@ int dvbs2_plframe_create(dvbs2_plframe_t** h, int gold_code, int plsc, int max_f
     if (plsc < 0 || plsc > 127) return fail(DVBS2_EINVAL, "plsc out of range (0..127)");
     { const PlsInfo p = pls_parse(plsc); if (p.n_mod == 0 && !p.dummy_frame) return fail(DVBS2_EINVAL, "plsc names a reserved MODCOD (29..31)"); }
     if (gold_code < 0 || gold_code >= (1 << 18) - 1) return fail(DVBS2_EINVAL, "gold code out of range");
-    if (int rc = check_device(device)) return rc;
-    dvbs2_plframe* o = new (std::nothrow) dvbs2_plframe();
-    if (!o) return fail(DVBS2_EDEVICE, "out of memory");
-    o->device = device;
-    o->pf = new (std::nothrow) PlFrameHip(gold_code, plsc, max_frames, device);
-    if (!o->pf || !o->pf->ok()) { std::string msg = o->pf ? o->pf->error() : "out of memory"; delete o->pf; delete o; return fail(DVBS2_EINVAL, msg); }
-    *h = o;
-    return DVBS2_OK;
+    return make_handle(h, device, false, [&](dvbs2_plframe* o) { return o->pf = new (std::nothrow) PlFrameHip(gold_code, plsc, max_frames, device); });
     API_CATCH
 }
 
@@ -1502,16 +1427,7 @@ extern "C" {
 int dvbs2_bbdeheader_create_raw(dvbs2_bbdeheader_t** h, int kbch_bits, int max_frames, int device)
 {
     API_TRY
-    if (!h) return fail(DVBS2_EINVAL, "null handle pointer");
-    *h = nullptr;
-    if (int rc = check_device(device)) return rc;
-    dvbs2_bbdeheader* o = new (std::nothrow) dvbs2_bbdeheader();
-    if (!o) return fail(DVBS2_EDEVICE, "out of memory");
-    o->device = device;
-    o->bb = new (std::nothrow) BbDeheaderHip(kbch_bits, max_frames, device);
-    if (!o->bb || !o->bb->ok()) { std::string msg = o->bb ? o->bb->error() : "out of memory"; delete o->bb; delete o; return fail(DVBS2_EINVAL, msg); }
-    *h = o;
-    return DVBS2_OK;
+    return make_handle(h, device, false, [&](dvbs2_bbdeheader* o) { return o->bb = new (std::nothrow) BbDeheaderHip(kbch_bits, max_frames, device); });
     API_CATCH
 }
 
