@@ -584,7 +584,7 @@ int dvbs2_debug_cu_slot_table(int device, int device_key, unsigned long long* ta
     if (!t) return fail(DVBS2_EDEVICE, e);
     *table_address = (unsigned long long)(uintptr_t)t;
     if (nonzero_words) {
-        std::vector<int> hv(kCuSlotWords);
+        std::vector<int> hv(kCuSlots);
         HCHK(hipMemcpy(hv.data(), t, hv.size() * 4, hipMemcpyDeviceToHost));
         int nz = 0;
         for (int v : hv) nz += v != 0;

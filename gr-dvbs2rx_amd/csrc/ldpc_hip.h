@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <string>
+#include "ldpc_layout.h"
 #include "ldpc_schedule.h"
 #include "demap_math.hpp"
 
@@ -10,8 +11,6 @@ namespace dvbs2 {
 
 // per-CU wave-pattern counters of the one-frame sweep kernels: one device array per device key (ldpc_hip.hip)
 int* cu_slot_table(int device_key, std::string* err);
-constexpr int kCuSlotWords = 16 * 8 * 2 * 16;
-enum class LdpcBuild : uint8_t; // the builds of the sweep kernel (ldpc_kernel.hpp)
 
 class LdpcDecoderHip {
 public:
@@ -39,7 +38,7 @@ public:
     // d_llr_out (nullable): n_frames*N decoded LLRs (what the reference publishes as llr_pdu).
     // d_ret (nullable): one int32 per group = the reference decode() return value (trials left, or -1).
     //
-    // enqueue() puts the whole decode on `stream` WITHOUT any host synchronisation: the first pass, kResolveRounds
+    // enqueue() puts the whole decode on `stream` WITHOUT any host synchronisation: the first pass, resolve_rounds_ (ldpc_plan.h)
     // rounds of (group targets, resume launch -- workgroups with nothing to do leave at once) that resolve the
     // batch-coupled stopping rule on the device, the output stage, and an asynchronous read-back of the "groups still
     // unresolved" counter. finish() waits for the stream and, only if that counter is not zero (a group needed more
@@ -48,7 +47,6 @@ public:
     // `slot` (< kSlots) selects the per-call flag storage and `frame_base` the range [frame_base, frame_base + n_frames)
     // of the handle's state/message buffers, so that several chunks can be in flight on different streams.
     // decode_device() = enqueue() + finish().
-    static constexpr int kResolveRounds = 2;
     static constexpr int kSlots = 4;
     // dm (optional): take XFECFRAME symbols instead of LLRs and demap while the frames are loaded (d_llr_in is ignored then);
     // only the classic sweep kernels do that (fused_demap_supported()). d_bits_out may be null when neither packed bits nor
@@ -80,12 +78,12 @@ private:
     int out_bits_message_, G_, max_frames_, device_;
     int words_per_check_ = 0; // message dwords per check (4 int8 messages per dword)
     int dmax_ = 0;            // kernel variant: handles check degrees dmax-7 .. dmax (8, 12, ..., 32)
-    uint32_t* d_recs_ = nullptr;  // per-layer records (ldpc_hip.hip); kRecHeaderWords of header in front of them (d_recs_alloc_)
+    uint32_t* d_recs_ = nullptr;  // per-layer records (ldpc_plan.cpp); kRecHeaderWords of header in front of them (d_recs_alloc_)
     uint32_t* d_recs_alloc_ = nullptr;
     uint32_t* d_wrecs_ = nullptr; // per-(layer, wave) sweep records of the classic kernel
     size_t lds_bytes_ = 0;
     std::string kname_;
-    LdpcBuild build_{};           // the build of the sweep kernel this handle runs (decided in the constructor)
+    LdpcBuild build_{};           // the build of the sweep kernel this handle runs (decided by plan_ldpc, ldpc_plan.h)
     int fallback_rounds_ = 0;
     int* d_cu_slots_ = nullptr;   // per-CU pattern counters of the solo kernels
     bool pr_ = false;             // parity-in-records kernel variant selected (ldpc_kernel_pr.hpp)
@@ -103,10 +101,11 @@ private:
     struct Pending { bool active = false; int n_frames = 0, max_trials = 0, out_mode = 0, frame_base = 0;
                      uint8_t* bits = nullptr; int8_t* llr_out = nullptr; int32_t* ret = nullptr; hipStream_t stream = nullptr; };
     Pending pend_[kSlots];
-    int resolve_rounds_ = kResolveRounds;
+    int resolve_rounds_ = 0;      // resolution rounds enqueued ahead of time (ldpc_plan.h)
     void launch_sweep(const int8_t* in, bool resume, int stop_on_good, int n_frames, int max_trials, int frame_base, hipStream_t stream, const DemapFused* dm = nullptr);
     void launch_targets(int n_frames, int max_trials, int frame_base, int32_t* d_ret, int slot, hipStream_t stream);
     void launch_finalize(const Pending& p);
+    int dump_timing(int n_frames, int max_trials, hipStream_t stream);
     bool profiling_ = false;
     double prof_ms_ = 0;
     int prof_launches_ = 0;

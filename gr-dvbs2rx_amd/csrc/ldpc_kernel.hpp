@@ -1,10 +1,11 @@
-// ldpc_kernel.hpp -- device code of the layered LDPC decoder (included by ldpc_hip.hip for the constants and by
-// the per-variant translation units ldpc_inst_*.hip, which instantiate one DMAX each so that the seven kernel
-// variants compile in parallel).
+// ldpc_kernel.hpp -- device code of the layered LDPC decoder (included by ldpc_hip.hip for the launch interface and by
+// the per-variant translation units ldpc_inst_*.hip, which instantiate one DMAX each so that the kernel
+// variants compile in parallel). The record format and the constants shared with the host planner: ldpc_layout.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "demap_math.hpp"
+#include "ldpc_layout.h"
 
 // s_waitcnt vmcnt(0) (expcnt, lgkmcnt untouched) that memory operations are not moved across, in front of the stores of a layer's new
 // messages. The compiler waits for the NEXT layer's prefetched messages (loaded at the head of this layer) with vmcnt(0) -- loads and
@@ -25,31 +26,7 @@ namespace dvbs2 {
 // land 2,2,1,1 on the SIMDs and spend a quarter of their time waiting for the doubly loaded ones).
 constexpr int kHalf = 384;          // threads per frame (6 wavefronts; threads 0..359 active)
 constexpr int kThreads = 2 * kHalf; // 12 wavefronts
-constexpr int kM = 360;
-constexpr int kMsgStride = 384;     // message slots per (layer, word)
-constexpr int kSvWords = 14;        // sign-vector dwords per 360-bit group (360 bits + 32-bit wrap extension, even for b64 stores)
 
-// Layer record (uniform data, read with scalar loads): RS = 2*DMAX + 4 dwords.
-//   word 0: cnt | sync_before << 15 | block << 16
-//   words 4+2k, 5+2k (k < deg): entry k as  S0 = 360*g + rot  and  thr = 360 - rot
-// Entry k addresses the LDS window [360*g, 360*g + 360) rotated by rot: check row j touches byte
-// 360*g + (j + rot) mod 360 = (j < thr ? S0 + j : S0 + j - 360).
-__host__ __device__ constexpr int rec_stride(int dmax) { return 2 * dmax + 4; }       // per-layer records (recs)
-__host__ __device__ constexpr int rec_stride_wave(int dmax) { return 2 * dmax + 12; } // per-(layer, wave) records of the packed builds (wrecs)
-// In FRONT of the per-layer records (recs[-kRecHeaderWords ..]): what the group-synchronous stop needs (group_decide) -- the base of the
-// handle's `iters` array (the kernel's own `iters` argument minus it = the first frame of this launch), the base of the per-group words
-// and the group size. Kept out of the kernel's argument list on purpose: arguments stay live in SGPRs for the whole kernel, and the
-// one-frame builds of the degree class 16 answered three more of them with 25 more spilled scalars and 2-3 % (measured); here they are
-// fetched with two scalar loads once per update, by the lane that reports.
-constexpr int kRecHeaderWords = 8; // [0,1] iters base, [2,3] base of the per-frame status words (group_decide), [4] group size, [5] polls before a waiting member gives up, rest unused
-// per frame: N LLR bytes, then the sign-vector area (syndrome test; scratch of the ordered hazard phases during a sweep:
-// at least kChainScratchWords dwords, which is what short frames get instead of their small sign-vector area), then 8 flag words
-// largest block walked as a register chain -- round 4: 128 -> 180 (blocks 129..180 are three-step block-scheme layers otherwise): 3/4 normal
-// +1.6 %, 3/5 +1.3 %, B4 / 2/5 normal +0.4 %
-constexpr int kChainMaxBlock = 180;
-constexpr int kChainScratchWords = (kM + kChainMaxBlock) * 5 + 4;               // (360 + block) x (16-byte record + 4-byte log) + 16 bytes: the records are 16-byte aligned and the area starts at N, which is 8 mod 16 for short frames
-__host__ __device__ constexpr int sv_area_words(int N) { return (N / kM) * kSvWords > kChainScratchWords ? (N / kM) * kSvWords : kChainScratchWords; }
-__host__ __device__ constexpr size_t half_lds_bytes(int N) { return ((size_t)N + (size_t)sv_area_words(N) * 4 + 32 + 15) / 16 * 16; }
 
 // EVERY access to LDS goes through a pointer whose TYPE says address space 3. A generic pointer that the compiler cannot trace back
 // to the shared array (a function parameter, a pointer rebuilt from an integer for alignment, any `volatile` access) becomes a FLAT
@@ -116,7 +93,6 @@ __device__ __forceinline__ void frame_barrier_lds(volatile lds_i32_t* ctr, int& 
 // at its own good point like in rounds 1-2 and the host-side resolution, ldpc_group_targets_kernel + resume launches, finishes the
 // group -- a frame only ever advances past a count at which some member is known to have failed, so it can never overshoot).
 // Called by ALL lanes of the frame's first wave (wave-uniform arguments); groups of at most 64 frames.
-constexpr int kGroupSpinMax = 1 << 12; // polls of ~2 us
 __device__ __forceinline__ int group_decide(int* st /*status words of this frame's group*/, int members, int me /*this frame's index in its group*/,
                                             int it, bool good, int lane, int spin_max = kGroupSpinMax)
 {
@@ -313,21 +289,7 @@ __device__ __forceinline__ void check_node(uint8_t* __restrict__ lds /*the whole
     }
 }
 
-// two-level lane chain (check_node_hazard): the degree class 32 without the heavy-hazard paths (9/10 normal); not in the builds with software
-// frame barriers, which only tables without hazard layers run (S2X 154/180 lost 2.5 % to the larger kernel)
-// Which degree classes carry it is MEASURED (MI355X, interleaved A/B of whole tables, notes/r03_experiments.md): at run time the chain is
-// never slower than the ordered steps it replaces (9/10 normal + 13 %, 3/5 normal + 10 %, short 5/6 + 4 %, 3/4 normal + 2.4 %), but
-// compiling it in costs the packed / one-frame builds of the classes 12 and 28 eight percent on every table (2/3, T2 2/3, 8/9 normal)
-// and the class 20 what its one table gains -- so: 16 (3/4 normal + 5 % net, short 5/6 + 2 %, short 2/3 - 4 %), 24 (5/6 normal + 1.3 %),
-// 32 (9/10 normal + 8 %).
-template <int DMAX, bool HZ2> constexpr bool kTlc = (DMAX == 16 || DMAX == 24 || DMAX == 32) && !HZ2;
-// Hazard layers with the packed first / last phase (check_node_hazard<..., V2P>, round 5): compiled into the packed builds of the degree
-// classes from 20 up -- the classes whose hazard layers all took the plain node (no packed chain node there).
-__host__ __device__ constexpr bool v2p_class(int dmax) { return dmax >= 20; }
-// "pure" packed builds (kPure in ldpc_layered_kernel) -- measured (round 5, interleaved A/B): class 32 (9/10 normal) 80.2 -> 83.9 k;
-// 28 (8/9) 95.9 -> 91.2 k, 24 (5/6) 76.9 -> 74.2 k
-__host__ __device__ constexpr bool v2_pure_class(int dmax) { return dmax >= 32; }
-__host__ __device__ constexpr bool tlc_class(int dmax) { return dmax == 16 || dmax == 24 || dmax == 32; }
+template <int DMAX, bool HZ2> constexpr bool kTlc = tlc_class(DMAX) && !HZ2; // two-level lane chain (check_node_hazard): the classes of tlc_class (ldpc_layout.h)
 constexpr int kTlcLowRegMinDmax = 24; // from this degree class on a two-level-chain layer keeps its regular entries in the low-register form
 __device__ __forceinline__ int pm_pack(int magp, int d) { return (int)__builtin_amdgcn_perm((uint32_t)magp, (uint32_t)d, 0x0c0c0400u); } // d.b0 | magp.b0 << 8
 __device__ __forceinline__ int pm_inp(int pm) { return __builtin_amdgcn_sbfe(pm, 0, 8); }
@@ -370,10 +332,6 @@ __device__ __forceinline__ int fix_wrap(int ad, uint32_t mlo, uint32_t mhi)
                  : "+v"(ad), "=&s"(save) : "s"(mask) : "scc");
     return ad;
 }
-
-// fix slots per record: masks live in record words 4 + dmax + 2 k. The degree class 32 has ten: with them every wave record of S2X 154/180
-// fits the packed format (with 8 two of its 150 did not).
-__host__ __device__ constexpr int v2_nfix(int dmax) { return dmax == 32 ? 10 : dmax / 4; }
 
 // Message storage of the packed nodes: one byte per message (R7 clamps a stored message to six bits, clamp(out, -32, 31)), pair j in
 // bytes (j & 1) and (j & 1) + 2 of word j / 2. (Six-bit fields, five per dword, measured slower on table B4, 4096 frames: 107 k frames/s
@@ -707,20 +665,10 @@ __device__ __forceinline__ void check_node_chain_v2(const uint32_t* ent /*S0w[DM
 // a regular entry's bits are touched by exactly one row of the layer.
 // NC (2, 4 or 8) is the number of entries handled in P2: the hazard entries, rounded up with regular data entries
 // (moving a regular entry into the ordered part does not change the result).
-// LDS scratch of a lane chain with block size B: (360 + B) per-row records (dwords) + as many log bytes
-__host__ __device__ constexpr int lane_chain_words(int block) { return (kM + block) + (kM + block + 3) / 4; }
-constexpr int kLaneChainMaxDeg = 28;                                  // not instantiated for the big variants nor for the
-                                                                      // 80-VGPR parity-in-records kernel (registers); hazard nodes with
-                                                                      // the packed first / last phase (their state is smaller) have it at
-                                                                      // every degree: 9/10 normal 83.9 -> 86.3 k (round 5)
 constexpr int kFwalkMaxDeg = 12;     // largest check degree of a single-pair lane chain walked in float (kFloatWalk)
 constexpr int kTlcFwalkMinDmax = 24; // the near pair of a two-level lane chain walked in float (six instructions per row, 16-byte operand records)
                                      // in the packed hazard nodes from this degree class up -- measured (round 5): 5/6 normal +3.1 %, 9/10 normal
                                      // +0.35 %; 3/4 normal (class 16) -2.0 %
-constexpr int kMaxHazard = 8;     // ordered entries per check in the common builds, kMaxHazardHz2 in the HZ2 builds (ldpc_layered_kernel)
-constexpr int kMaxHazardHz2 = 12;
-constexpr int kMaxHazard12Dmax = 28; // (the degree class 32 has the two-level walk only: twelve ordered entries on top of 30 edges do not fit its registers)
-constexpr int kHazardWalk = 15; // header code: too many hazard entries, fall back to the single-wave chunk walk
 template <int DEG, int NC, bool LAYER0, bool PR = false, bool LAST = false, bool TWO = false /*two-level walk compiled in*/,
           bool LR = false /*low-register form: a regular entry keeps ONE word pm = |Lb - mb| << 8 | (inp & 0xff) between the phases and its address is computed twice (two-level-chain layers of the classes >= 24)*/,
           bool TLC = false /*two-level walk with the near pair as a LANE CHAIN (round 3), see below*/,
@@ -1458,7 +1406,7 @@ __device__ __forceinline__ void check_node_hazard(uint8_t* __restrict__ lds, con
         default: break; }
 
 // MINW = 6 ("dense"): compiled for 80 VGPRs so that two pair-workgroups share a CU when the frames are short enough for
-// LDS. It spills and only pays where ordered hazard steps dominate (ldpc_hip.hip picks it).
+// LDS. It spills and only pays where ordered hazard steps dominate (ldpc_plan.cpp picks it).
 // V2: the packed nodes (check_node_v2, check_node_chain_v2) are compiled in; a table runs the build that measured faster for it
 // (compiling both families into one kernel costs each of them 4-7 % through register allocation).
 // SOLO: ONE frame per workgroup, two (or more) independent workgroups per CU. The pair workgroup exists only to put three
@@ -1498,7 +1446,6 @@ __device__ __forceinline__ uint32_t hw_cu_index()
     // HW_ID: simd_id[5:4] cu_id[11:8] sh_id[12] se_id[15:13]
     return ((((xcc & 0xfu) * 8u + ((hw >> 13) & 7u)) * 2u + ((hw >> 12) & 1u)) * 16u + ((hw >> 8) & 0xfu));
 }
-constexpr int kCuSlots = 16 * 8 * 2 * 16;
 
 template <int DMAX, bool TIMING, int MINW = 1, bool V2 = false, bool SOLO = false, bool HZ2 = false, bool SOFT = false /*SOFT: frame barriers in software -- a build of its own: the barrier state in every barrier of
                              every build cost the 80-VGPR build 25-30 % (54 -> 199 spilled VGPRs) and the degree classes 20..32 4-10 %*/
@@ -1529,7 +1476,7 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
     constexpr int MW = DMAX / 4; // message dwords per check (fixed per kernel variant)
     // "pure" packed builds (v2_pure_class): the plain nodes are compiled for layer 0 only -- the plain hazard
     // nodes of the degree class 32 cost the packed ones around them 5 % through register allocation --; the host runs such a build only
-    // for tables whose every (layer > 0, wave) record fits the packed format (ldpc_hip.hip)
+    // for tables whose every (layer > 0, wave) record fits the packed format (ldpc_plan.cpp)
     // (also the software-barrier packed build of the pure classes: S2X 154/180 131.8 -> 133.9 k with ten fix slots, round 5)
     constexpr bool kPure = V2 && v2_pure_class(DMAX);
     constexpr bool TC = V2 && DMAX <= kTcMaxDmax;        // LLR bytes in LDS as two's complement (see lds_rdx)
@@ -1965,23 +1912,6 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
 
 
 // ---- host-side launch interface of one kernel variant (defined in ldpc_inst_*.hip) ----
-// The build of the sweep kernel a handle runs, decided once per table by the host (ldpc_hip.hip). The classic kernel's builds exist
-// in the degree classes the k*Built rules below give; the parity-in-records builds (ldpc_kernel_pr.hpp) in the class 8 only.
-enum class LdpcBuild : uint8_t {
-    plain,       // pair workgroups, scalar nodes
-    packed,      // pair workgroups with the packed nodes (check_node_v2, check_node_chain_v2)
-    solo,        // one frame per workgroup (kSoloBuilt)
-    packed_solo,
-    hz2,         // the heavy-hazard paths (kHz2Built)
-    soft,        // software frame barriers (kSoftBuilt)
-    packed_soft,
-    dense,       // 80 VGPRs, two workgroups per CU (kDenseBuilt)
-    pr,          // parity in records: two-dword records, plain nodes
-    pr_w1,       //                    one-dword records (check degree <= 4)
-    pr_packed,   //                    two-dword records, packed nodes in the regular middle layers
-};
-constexpr int kLdpcBuilds = (int)LdpcBuild::pr_packed + 1;
-__host__ __device__ constexpr bool is_solo(LdpcBuild b) { return b == LdpcBuild::solo || b == LdpcBuild::packed_solo; }
 struct LdpcLaunch {
     const uint32_t* recs; const uint32_t* wrecs; const int8_t* llr_in; uint8_t* state; uint32_t* msgs; int* iters; int* good; const int* target;
     int n_frames, N, K, q, cap, stop_on_good; unsigned long long* tdbg /*non-null: the cycle-stamped build where it exists*/;
@@ -1993,7 +1923,6 @@ struct LdpcLaunch {
 // prepare: sets the dynamic-LDS limit of every build of the class (one-frame builds take solo_lds_bytes); fails when `build` is not one of them
 template <int DMAX> hipError_t ldpc_variant_prepare(LdpcBuild build, size_t pair_lds_bytes, size_t solo_lds_bytes);
 template <int DMAX> void ldpc_variant_launch(const LdpcLaunch& a);
-constexpr int kSoloMaxDmax = 16; // one-frame workgroups (128 VGPRs) up to this degree class (round 6 bound, notes/r06_experiments.md)
 template <int DMAX> constexpr bool kSoloBuilt = (DMAX <= kSoloMaxDmax);
 template <int DMAX> constexpr bool kHz2Built = (DMAX >= 12);
 template <int DMAX> constexpr bool kSoftBuilt = (DMAX >= 20); // pays where layers are long and barriers few (measured: S2X B10, B20, B21, B24)

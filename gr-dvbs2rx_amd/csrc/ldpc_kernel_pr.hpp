@@ -30,11 +30,6 @@
 
 namespace dvbs2 {
 
-__host__ __device__ constexpr size_t pr_half_bytes(int K) { return ((size_t)K + kM + 15) / 16 * 16; }
-// two frames + sign-vector areas: one PER FRAME (round 5: the frames run their full syndrome tests at the same time), or ONE shared by the
-// workgroup where two do not fit twice into the 160 KB of a CU (normal frames forced onto this kernel: the frames then take turns; bit 3 of the flag word)
-__host__ __device__ constexpr size_t pr_lds_bytes(int N, int K, bool shared_sv = false) { return 2 * pr_half_bytes(K) + (shared_sv ? 1 : 2) * (size_t)(N / kM) * kSvWords * 4 + 64; }
-
 #ifdef DVBS2_LDPC_INSTANTIATE_PR
 #define DVBS2_PR_CASE(D) case D: { \
         if (first_layer) check_node<D, true, true, false>(lds_all, ent, jj, lb, mw, nm, own_in, &carry); \

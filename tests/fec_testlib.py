@@ -247,6 +247,39 @@ VARIANTS = {  # every build of the sweep kernel gives the same bits (environment
 }
 
 
+def build_ldpc_planner(out_dir, main=None):
+    """The host-only LDPC planner (csrc/ldpc_plan.cpp) behind tests/ldpc_plan_main.cpp, compiled with the host compiler alone."""
+    csrc = os.path.join(ROOT, "gr-dvbs2rx_amd", "csrc")
+    exe = os.path.join(str(out_dir), "ldpc_plan_main")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", main or os.path.join(ROOT, "tests", "ldpc_plan_main.cpp")] +
+                          [os.path.join(csrc, f) for f in ("ldpc_plan.cpp", "ldpc_schedule.cpp", "fec_tables.cpp")] + ["-o", exe])
+    return exe
+
+
+def run_ldpc_planner(exe, rows, group_size=32):
+    """rows: (table, {override: value}). One dict per row: {"error": text}, or name / dmax / words_per_check / pr_shared_sv / lds_bytes /
+    gsync_on, `check` (first broken format invariant, "" = none) and recs / wrecs, the truncated sha256 of the record words."""
+    text = "".join("%s %d %s\n" % (t, group_size, " ".join("%s=%s" % kv for kv in sorted(env.items()))) for t, env in rows)
+    r = subprocess.run([exe], input=text.encode(), capture_output=True)
+    assert r.returncode == 0, r.stderr
+    out, pos, plans = r.stdout, 0, []
+    while pos < len(out):
+        end = out.index(b"\n", pos)
+        kind, line = out[pos:pos + 1], out[pos + 2:end].decode()
+        pos = end + 1
+        if kind == b"E":
+            plans.append({"error": line})
+            continue
+        f = line.split("|")
+        n_recs, n_wrecs = int(f[6]), int(f[7])
+        recs, wrecs = out[pos:pos + 4 * n_recs], out[pos + 4 * n_recs:pos + 4 * (n_recs + n_wrecs)]
+        pos += 4 * (n_recs + n_wrecs)
+        plans.append({"name": f[0], "dmax": int(f[1]), "words_per_check": int(f[2]), "pr_shared_sv": int(f[3]), "lds_bytes": int(f[4]), "gsync_on": int(f[5]),
+                      "check": f[8] if len(f) > 8 else "", "recs": hashlib.sha256(recs).hexdigest()[:12], "wrecs": hashlib.sha256(wrecs).hexdigest()[:12]})
+    assert len(plans) == len(rows)
+    return plans
+
+
 # ------------------------------------------------------------------ input generators
 def llr_noise(n_frames, N, seed, sigma=8.0):
     """Never-converging input of SURVEY 8(d): i.i.d. clamp(round(N(0, sigma^2)))."""

@@ -268,6 +268,17 @@ def test_kernel_variant_policy(monkeypatch):
     assert name("S2_TABLE_B1", DVBS2_PR="1") == "ldpc_layered_pr_kernel<w1>"
 
 
+def test_handle_runs_the_planners_build(tmp_path):
+    """The seam between the host-only planner (tests/test_ldpc_plan.py checks it on the CPU) and the handle: same kernel name."""
+    tables = ["S2_TABLE_B4", "S2_TABLE_B11", "S2_TABLE_C1"]
+    plans = T.run_ldpc_planner(T.build_ldpc_planner(tmp_path), [(t, {}) for t in tables])
+    for table, plan in zip(tables, plans):
+        dec = LdpcDecoder(table=table, message_bits=T.ldpc_info(table)[1], group_size=32, max_frames=32, max_trials=5)
+        n = dec.kernel_name
+        dec.close()
+        assert n == plan["name"], table
+
+
 @pytest.mark.parametrize("table,nf,trials,amp,sigma", [("S2_TABLE_B4", 4096, 50, 6, 4.6), ("S2_TABLE_C1", 16384, 25, 5, 4.0)])
 def test_full_batch_properties(table, nf, trials, amp, sigma):
     """BASELINE.json batch sizes (4096 normal / 16384 short frames per GPU), checked through size-independent properties:
