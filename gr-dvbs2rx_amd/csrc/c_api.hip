@@ -1,6 +1,7 @@
 // c_api.hip -- extern "C" boundary (include/dvbs2_fec_hip.h). No exceptions leave this file.
 #include "../../include/dvbs2_fec_hip.h"
 #include <hip/hip_runtime.h>
+#include <cstddef>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -16,6 +17,7 @@
 #include "demap_hip.h"
 #include "plpayload_hip.h"
 #include "plframe_hip.h"
+#include "plsync_hip.h"
 #include "bbdeheader_hip.h"
 #include "device_guard.h"
 #include "demap_math.hpp"
@@ -1409,6 +1411,150 @@ int dvbs2_plframe_process(dvbs2_plframe_t* h, const float* plframes, int n_frame
     API_TRY
     if (n_frames > 0 && !xfecframes) return fail(DVBS2_EINVAL, "bad argument");
     return plframe_host(h, plframes, n_frames, has_trailing_header, coarse_corrected, coarse_foffset, xfecframes, est);
+    API_CATCH
+}
+
+} // extern "C"
+
+/* ------------------------------------------------------------------ PLFRAME search: timing metric, lock state machine, gather */
+struct dvbs2_plsync {
+    PlSyncHip* ps = nullptr;
+    float* d_in = nullptr; PlSyncFrame* d_frames = nullptr; // staging of the host entry
+    hipStream_t stream = nullptr;
+    int device = 0;
+};
+static_assert(sizeof(dvbs2_plsync_frame_t) == sizeof(PlSyncFrame) && offsetof(dvbs2_plsync_frame_t, metric) == offsetof(PlSyncFrame, metric) &&
+              offsetof(dvbs2_plsync_frame_t, plsc) == offsetof(PlSyncFrame, plsc) && offsetof(dvbs2_plsync_frame_t, flags) == offsetof(PlSyncFrame, flags),
+              "the public frame record is the kernel's");
+
+extern "C" {
+
+int dvbs2_plsync_taps(float* sof25, float* plsc32)
+{
+    if (!sof25 || !plsc32) return fail(DVBS2_EINVAL, "bad argument");
+    plsync_taps(sof25, plsc32);
+    return DVBS2_OK;
+}
+
+int dvbs2_plsync_thresholds(float* unlocked, float* locked)
+{
+    if (unlocked) *unlocked = kPlsyncThresholdUnlocked;
+    if (locked) *locked = kPlsyncThresholdLocked;
+    return DVBS2_OK;
+}
+
+int dvbs2_plsync_create(dvbs2_plsync_t** h, int plsc_or_minus1, int unlock_thresh, int max_symbols, int max_frames, int device)
+{
+    API_TRY
+    if (!h) return fail(DVBS2_EINVAL, "null handle pointer");
+    *h = nullptr;
+    // arguments first: a bad argument is the caller's mistake on any machine
+    if (plsc_or_minus1 < -1 || plsc_or_minus1 > 127) return fail(DVBS2_EINVAL, "plsc out of range (-1 = decode every header, 0..127)");
+    if (unlock_thresh < 1 || unlock_thresh > 255) return fail(DVBS2_EINVAL, "unlock_thresh out of range (1..255)");
+    if (max_symbols < kPlsyncMinSymbols) return fail(DVBS2_EINVAL, "max_symbols must be at least 33282 + 90");
+    if (max_frames < 1 || max_frames > (1 << 20)) return fail(DVBS2_EINVAL, "max_frames out of range (1..1048576)");
+    return make_handle(h, device, false, [&](dvbs2_plsync* o) { return o->ps = new (std::nothrow) PlSyncHip(plsc_or_minus1, unlock_thresh, max_symbols, max_frames, device); });
+    API_CATCH
+}
+
+void dvbs2_plsync_destroy(dvbs2_plsync_t* h)
+{
+    if (!h) return;
+    DeviceGuard guard(h->device);
+    (void)hipFree(h->d_in); (void)hipFree(h->d_frames);
+    if (h->stream) (void)hipStreamDestroy(h->stream);
+    delete h->ps;
+    delete h;
+}
+
+int dvbs2_plsync_reset(dvbs2_plsync_t* h)
+{
+    API_TRY
+    if (!h) return fail(DVBS2_EINVAL, "null handle");
+    if (h->ps->reset()) return fail(DVBS2_EDEVICE, h->ps->error());
+    return DVBS2_OK;
+    API_CATCH
+}
+
+int dvbs2_plsync_set_plsc_mode(dvbs2_plsync_t* h, int coherent, int soft)
+{
+    if (!h) return fail(DVBS2_EINVAL, "null handle");
+    h->ps->set_plsc_mode(coherent, soft);
+    return DVBS2_OK;
+}
+
+int dvbs2_plsync_set_expected_pls(dvbs2_plsync_t* h, const uint8_t* plsc_list, int n)
+{
+    API_TRY
+    if (!h) return fail(DVBS2_EINVAL, "null handle");
+    if (n < 0 || (n > 0 && !plsc_list)) return fail(DVBS2_EINVAL, "bad argument");
+    if (int rc = h->ps->set_expected_pls(plsc_list, n)) return fail(rc == -1 ? DVBS2_EINVAL : DVBS2_EDEVICE, h->ps->error());
+    return DVBS2_OK;
+    API_CATCH
+}
+
+int dvbs2_plsync_metric_device(dvbs2_plsync_t* h, const float* d_syms, int n_syms, float* d_metric, void* stream)
+{
+    API_TRY
+    if (!h) return fail(DVBS2_EINVAL, "null handle");
+    if (n_syms < 0 || (n_syms && (!d_syms || !d_metric))) return fail(DVBS2_EINVAL, "bad argument");
+    if (h->ps->metric_device(d_syms, n_syms, d_metric, (hipStream_t)stream)) return fail(DVBS2_EDEVICE, h->ps->error());
+    return DVBS2_OK;
+    API_CATCH
+}
+
+int dvbs2_plsync_search_device(dvbs2_plsync_t* h, const float* d_syms, int n_syms, dvbs2_plsync_frame_t* d_frames, void* stream)
+{
+    API_TRY
+    if (!h) return fail(DVBS2_EINVAL, "null handle");
+    if (n_syms < 0 || !d_frames || (n_syms && !d_syms)) return fail(DVBS2_EINVAL, "bad argument");
+    if (n_syms > h->ps->max_symbols()) return fail(DVBS2_ESIZE, "n_syms exceeds max_symbols");
+    if (h->ps->search_device(d_syms, n_syms, reinterpret_cast<PlSyncFrame*>(d_frames), (hipStream_t)stream)) return fail(DVBS2_EDEVICE, h->ps->error());
+    return DVBS2_OK;
+    API_CATCH
+}
+
+int dvbs2_plsync_finish(dvbs2_plsync_t* h, int* n_frames, int* consumed, int* state)
+{
+    API_TRY
+    if (!h) return fail(DVBS2_EINVAL, "null handle");
+    if (h->ps->finish(n_frames, consumed, state)) return fail(DVBS2_EDEVICE, h->ps->error());
+    return DVBS2_OK;
+    API_CATCH
+}
+
+int dvbs2_plsync_search(dvbs2_plsync_t* h, const float* syms, int n_syms, dvbs2_plsync_frame_t* frames, int* n_frames, int* consumed, int* state)
+{
+    API_TRY
+    if (!h) return fail(DVBS2_EINVAL, "null handle");
+    if (n_syms < 0 || !frames || (n_syms && !syms)) return fail(DVBS2_EINVAL, "bad argument");
+    if (n_syms > h->ps->max_symbols()) return fail(DVBS2_ESIZE, "n_syms exceeds max_symbols");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(DVBS2_EDEVICE, "hipSetDevice failed");
+    if (!h->stream) HCHK(hipStreamCreate(&h->stream));
+    if (!h->d_in) HCHK(hipMalloc(&h->d_in, (size_t)h->ps->max_symbols() * 8));
+    if (!h->d_frames) HCHK(hipMalloc(&h->d_frames, (size_t)h->ps->max_frames() * sizeof(PlSyncFrame)));
+    if (n_syms) HCHK(hipMemcpyAsync(h->d_in, syms, (size_t)n_syms * 8, hipMemcpyHostToDevice, h->stream));
+    if (h->ps->search_device(h->d_in, n_syms, h->d_frames, h->stream)) return fail(DVBS2_EDEVICE, h->ps->error());
+    int nf = 0;
+    if (h->ps->finish(&nf, consumed, state)) return fail(DVBS2_EDEVICE, h->ps->error());
+    if (nf) HCHK(hipMemcpy(frames, h->d_frames, (size_t)nf * sizeof(PlSyncFrame), hipMemcpyDeviceToHost));
+    if (n_frames) *n_frames = nf;
+    return DVBS2_OK;
+    API_CATCH
+}
+
+int dvbs2_plsync_gather_device(dvbs2_plsync_t* h, const float* d_syms, const dvbs2_plsync_frame_t* d_frames, int n_frames, int wanted_plsc,
+                               float* d_plframes, int32_t* d_count, void* stream)
+{
+    API_TRY
+    if (!h) return fail(DVBS2_EINVAL, "null handle");
+    if (wanted_plsc < 0 || wanted_plsc > 127) return fail(DVBS2_EINVAL, "plsc out of range (0..127)");
+    if (n_frames < 0 || !d_count || (n_frames && (!d_syms || !d_frames || !d_plframes))) return fail(DVBS2_EINVAL, "bad argument");
+    if (n_frames > h->ps->max_frames()) return fail(DVBS2_ESIZE, "n_frames exceeds max_frames");
+    if (h->ps->gather_device(d_syms, reinterpret_cast<const PlSyncFrame*>(d_frames), n_frames, wanted_plsc, d_plframes, d_count, (hipStream_t)stream))
+        return fail(DVBS2_EDEVICE, h->ps->error());
+    return DVBS2_OK;
     API_CATCH
 }
 

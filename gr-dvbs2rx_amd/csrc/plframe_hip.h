@@ -8,11 +8,9 @@
 #include <cstdint>
 #include <string>
 #include "plpayload_hip.h"
+#include "plsc_decode.hpp" // kSofWord, kPlscScrambler and the one-wavefront PLSC decoder
 
 namespace dvbs2 {
-
-constexpr uint32_t kSofWord = 0x18D2E82u;                  // 26 bits, first transmitted bit is bit 25 (lib/pl_defs.h:42)
-constexpr uint64_t kPlscScrambler = 0x719d83c953422dfaull; // lib/pl_defs.h:44
 
 // pls_info_t::parse (lib/pl_signaling.cc:19-61)
 struct PlsInfo {
@@ -23,6 +21,9 @@ PlsInfo pls_parse(int plsc);
 uint64_t plsc_codeword(int plsc);
 // the 90 expected PLHEADER symbols (re, im): SOF + scrambled PLSC codeword, pi/2-BPSK (lib/pi2_bpsk.cc:18-43)
 void plheader_symbols(int plsc, float* syms90);
+// rank[c] = position of codeword c in the enabled list (n = 0: all 128, in order), 255 = disabled; a repeated entry never
+// wins over its first occurrence. Returns false for an index >= 128 (lib/reed_muller.cc:48-52)
+bool pls_rank_table(const uint8_t* list, int n, uint8_t rank[128]);
 
 // device (or host-staged) outputs of the estimate kernel, each nullable
 struct PlFrameEstimates {

@@ -55,24 +55,24 @@ void plheader_symbols(int plsc, float* syms90)
     }
 }
 
+bool pls_rank_table(const uint8_t* list, int n, uint8_t rank[128])
+{
+    if (n == 0) { for (int i = 0; i < 128; i++) rank[i] = (uint8_t)i; return true; }
+    for (int i = 0; i < 128; i++) rank[i] = 255;
+    int next = 0;
+    for (int i = 0; i < n; i++) {
+        if (list[i] >= 128) return false;
+        if (rank[list[i]] == 255) rank[list[i]] = (uint8_t)next++;
+    }
+    return true;
+}
+
 namespace {
 
-constexpr float kS = 0.7071067811865476f;
+using plsc::kS;
+using plsc::remove_modulation;
+using plsc::wave_sum;
 constexpr double kPi = 3.14159265358979323846;
-
-__device__ inline float wave_sum(float v)
-{
-    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m); // a + b is commutative: every lane ends with the same bits
-    return v;
-}
-
-// x_k * conj(h_k): conj(h_k) = rot[k & 1] * (1 - 2 bit), rot = { (S, -S), (-S, -S) } (lib/pi2_bpsk.cc:23-34, :57-60)
-__device__ inline float2 remove_modulation(float2 x, int k, int bit)
-{
-    const float sg = bit ? -1.0f : 1.0f;
-    const float cr = ((k & 1) ? -kS : kS) * sg, ci = -kS * sg;
-    return make_float2(x.x * cr - x.y * ci, x.x * ci + x.y * cr);
-}
 
 // the three data-aided sums over one PLHEADER (lib/pl_freq_sync.cc:201-226, :263-266); lane l holds symbols l and 64 + l
 __device__ inline void header_sums(const float2* __restrict__ x, int l, uint64_t cw, float2* sof, float2* hdr, float2* last36)
@@ -110,59 +110,8 @@ __global__ __launch_bounds__(64) void pl_estimate_kernel(const float2* __restric
     const float sof_phase = atan2f(sof.y, sof.x), hph = atan2f(hdr.y, hdr.x);
 
     // ---- PLSC of the frame's own header (lib/plsync_cc_impl.cc:582-590): de-rotate by the SOF phase
-    // (lib/pl_freq_sync.cc:429-436), lane j takes PLSC symbol j = PLHEADER symbol 26 + j
-    float sn, cs;
-    sincosf(-sof_phase, &sn, &cs);
-    const float2 xa = x[26 + l], xb = x[25 + l];
-    const float2 ya = make_float2(xa.x * cs - xa.y * sn, xa.x * sn + xa.y * cs);
-    const int scr = (int)((kPlscScrambler >> (63 - l)) & 1);
-    float v; // the descrambled soft decision, or +-1 for a descrambled hard decision
-    if (coherent) {
-        const float rr = (l & 1) ? -kS : kS, ri = -kS;
-        const float sd = ya.x * rr - ya.y * ri; // real(x rot[j & 1]) (lib/pi2_bpsk.cc:45-74, :181-196)
-        if (soft) v = scr ? -sd : sd;
-        else v = ((sd < 0.0f) != (scr != 0)) ? -1.0f : 1.0f;
-    } else {
-        // differential: bit_j = bit_{j-1} ^ (imag(conj(y_{j+1}) y_j) < 0) ^ (j & 1), starting from the last SOF bit 0
-        // (lib/pi2_bpsk.cc:165-176): a prefix parity over the lanes
-        const float2 yb = make_float2(xb.x * cs - xb.y * sn, xb.x * sn + xb.y * cs);
-        const float dim = ya.x * yb.y - ya.y * yb.x;
-        const unsigned long long flips = __ballot(((dim < 0.0f) ? 1 : 0) ^ (l & 1));
-        const unsigned long long upto = l == 63 ? ~0ull : ((2ull << l) - 1ull);
-        const int bit = __popcll(flips & upto) & 1;
-        v = (bit != scr) ? -1.0f : 1.0f;
-    }
-    // RM(64,7) as a transform (lib/reed_muller.cc:72-96): the first stage forms the pair sums (even lanes, b7 = 0) and
-    // pair differences (odd lanes, b7 = 1); five more stages are a 32-point Walsh-Hadamard transform over lane bits
-    // 1..5. Lane 2 w + b7 then holds the metric of codeword (bitrev5(w) << 2) | b7, and its negative that of the
-    // codeword with bit 1 (the all-ones row) set. On +-1 inputs every value is a small integer: exact in float.
-    for (int m = 1; m < 64; m <<= 1) {
-        const float o = __shfl_xor(v, m);
-        v = (l & m) ? o - v : v + o;
-    }
-    const int c0 = (int)((__brev((unsigned)(l >> 1)) >> 27) << 2) | (l & 1), c1 = c0 | 2;
-    const int r0 = rank[c0], r1 = rank[c1];
-    int decoded;
-    if (coherent && soft) {
-        // maximum inner product over ALL 128 entries, those of disabled codewords being 0.0; first maximum wins
-        // (lib/reed_muller.cc:203-209)
-        const float m0 = r0 != 255 ? v : 0.0f, m1 = r1 != 255 ? -v : 0.0f;
-        float bv = m1 > m0 ? m1 : m0; int bi = m1 > m0 ? c1 : c0;
-        for (int m = 1; m < 64; m <<= 1) {
-            const float ov = __shfl_xor(bv, m); const int oi = __shfl_xor(bi, m);
-            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-        }
-        decoded = bi;
-    } else {
-        // minimum Hamming distance, FIRST minimum in the order of the enabled list (lib/reed_muller.cc:128-141):
-        // distance = (64 -+ W) / 2; key = distance | position in the list | codeword
-        const int w = (int)v;
-        const unsigned k0 = r0 != 255 ? (unsigned)(((64 - w) >> 1) << 16 | r0 << 8 | c0) : 0xffffffffu;
-        const unsigned k1 = r1 != 255 ? (unsigned)(((64 + w) >> 1) << 16 | r1 << 8 | c1) : 0xffffffffu;
-        unsigned key = k0 < k1 ? k0 : k1;
-        for (int m = 1; m < 64; m <<= 1) { const unsigned o = __shfl_xor(key, m); key = o < key ? o : key; }
-        decoded = (int)(key & 127u);
-    }
+    // (lib/pl_freq_sync.cc:429-436), lane j takes PLSC symbol j = PLHEADER symbol 26 + j (plsc_decode.hpp)
+    const int decoded = plsc::decode_wave(x[26 + l], x[25 + l], sof_phase, l, rank, coherent, soft);
 
     // ---- fine frequency offset
     const bool coarse = cc[f] != 0;
@@ -244,15 +193,7 @@ int PlFrameHip::set_expected_pls(const uint8_t* list, int n)
 {
     call_err_.clear();
     uint8_t rank[128];
-    if (n == 0) { for (int i = 0; i < 128; i++) rank[i] = (uint8_t)i; }
-    else {
-        for (int i = 0; i < 128; i++) rank[i] = 255;
-        int next = 0;
-        for (int i = 0; i < n; i++) {
-            if (list[i] >= 128) { call_err_ = "codeword indexes must be within [0, 128)"; return -1; } // lib/reed_muller.cc:48-52
-            if (rank[list[i]] == 255) rank[list[i]] = (uint8_t)next++; // a repeated entry never wins over its first occurrence
-        }
-    }
+    if (!pls_rank_table(list, n, rank)) { call_err_ = "codeword indexes must be within [0, 128)"; return -1; } // lib/reed_muller.cc:48-52
     DeviceGuard dev_guard(device_);
     if (!dev_guard.ok || hipMemcpy(d_rank_, rank, 128, hipMemcpyHostToDevice) != hipSuccess) { call_err_ = "copy of the codeword list failed"; return -2; }
     return 0;

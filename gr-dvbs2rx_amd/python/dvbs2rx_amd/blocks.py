@@ -15,7 +15,8 @@ from .capi import lib, check
 
 __all__ = ["get_fec_info", "rate_id", "LdpcDecoder", "BchDecoder", "Demapper", "FecChain", "BbDeheader", "ldpc_table_info", "ldpc_layer_info",
            "ldpc_table_names", "bb_descramble_sequence", "PlPayload",
-           "pl_scrambling_rn", "HostBuffer", "PlFrontEnd", "plheader_symbols", "pls_parse"]
+           "pl_scrambling_rn", "HostBuffer", "PlFrontEnd", "plheader_symbols", "pls_parse",
+           "PlSync", "plsync_taps", "plsync_thresholds"]
 
 DEFAULT_TRIALS = 25  # reference lib/ldpc_decoder_bb_impl.cc:391
 
@@ -450,6 +451,98 @@ class PlFrontEnd:
         else:
             check(lib.dvbs2_plframe_estimate_device(self._h, d_plframes, n_frames, int(has_trailing_header), d_coarse_corrected,
                                                     d_coarse_foffset or None, C.byref(e), stream or None))
+
+
+class PlSync:
+    """PLFRAME search on a raw symbol stream (reference lib/pl_frame_sync.cc:66-243): the timing metric for every symbol, the
+    searching / found / locked state machine with PLSC decoding at every header, and the gather step that lays the locked
+    frames of one PLSC out the way PlFrontEnd reads them. The handle keeps the machine's state and the 89 symbols before the
+    consumed point between calls; present the stream again from `consumed`, as with GNU Radio's consume()."""
+
+    FRAME_DTYPE = np.dtype(capi.PLSYNC_FRAME_DTYPE)
+    MIN_SYMBOLS = 33282 + 90
+
+    def __init__(self, plsc=-1, unlock_thresh=3, max_symbols=1 << 20, max_frames=1024, device=0, coherent=True, soft=True,
+                 expected_pls=None):
+        """plsc = -1: decode the PLSC of every header; 0..127: the fixed-PLSC (CCM/SIS) mode."""
+        self._h = C.c_void_p()
+        check(lib.dvbs2_plsync_create(C.byref(self._h), int(plsc), int(unlock_thresh), int(max_symbols), int(max_frames), device))
+        self.plsc, self.unlock_thresh, self.max_symbols, self.max_frames = plsc, unlock_thresh, max_symbols, max_frames
+        self.set_plsc_mode(coherent, soft)
+        if expected_pls is not None:
+            self.set_expected_pls(expected_pls)
+
+    def close(self):
+        if self._h:
+            lib.dvbs2_plsync_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        check(lib.dvbs2_plsync_reset(self._h))
+
+    def set_plsc_mode(self, coherent=True, soft=True):
+        check(lib.dvbs2_plsync_set_plsc_mode(self._h, int(bool(coherent)), int(bool(soft))))
+
+    def set_expected_pls(self, plsc_list):
+        """The enabled-codeword list, in the given order (empty: all 128)."""
+        lst = np.asarray(plsc_list)
+        if lst.size and (lst.dtype.kind not in "iu" or lst.min() < 0 or lst.max() > 127):
+            raise ValueError("expected_pls: integers in 0..127")
+        lst = np.ascontiguousarray(lst, np.uint8)
+        check(lib.dvbs2_plsync_set_expected_pls(self._h, lst.ctypes.data if lst.size else None, int(lst.size)))
+
+    def metric_device(self, d_syms, n_syms, d_metric, stream=0):
+        """DEVICE addresses; the timing metric of every index with the handle's history. Does not advance the handle."""
+        check(lib.dvbs2_plsync_metric_device(self._h, d_syms, n_syms, d_metric, stream or None))
+
+    def work_device(self, d_syms, n_syms, d_frames, stream=0):
+        """DEVICE addresses, asynchronous on `stream`; d_frames: max_frames records of FRAME_DTYPE. Read the result with finish()."""
+        check(lib.dvbs2_plsync_search_device(self._h, d_syms, n_syms, d_frames, stream or None))
+
+    def finish(self):
+        """Waits for the last work_device(); returns (n_frames, consumed, state)."""
+        v = [C.c_int() for _ in range(3)]
+        check(lib.dvbs2_plsync_finish(self._h, *v))
+        return tuple(x.value for x in v)
+
+    def work(self, syms):
+        """HOST buffer of complex64 symbols. Returns (frames as a FRAME_DTYPE array, consumed, state)."""
+        x = np.asarray(syms)
+        if x.dtype != np.complex64:
+            raise TypeError(f"syms must be complex64, not {x.dtype}")
+        if x.ndim != 1 or not x.flags.c_contiguous:
+            raise ValueError("syms must be a C-contiguous vector")
+        if x.size > self.max_symbols:
+            raise ValueError(f"{x.size} symbols exceed max_symbols = {self.max_symbols}")
+        frames = np.zeros(self.max_frames, self.FRAME_DTYPE)
+        v = [C.c_int() for _ in range(3)]
+        check(lib.dvbs2_plsync_search(self._h, x.ctypes.data if x.size else None, int(x.size), frames.ctypes.data, *v))
+        return frames[:v[0].value].copy(), v[1].value, v[2].value
+
+    def gather_device(self, d_syms, d_frames, n_frames, wanted_plsc, d_plframes, d_count, stream=0):
+        """DEVICE addresses: the locked frames of wanted_plsc among the first n_frames records of the LAST work_device(), back
+        to back, then the 90 symbols after the last one (PlFrontEnd's layout with a trailing header); *d_count = frames."""
+        check(lib.dvbs2_plsync_gather_device(self._h, d_syms, d_frames, int(n_frames), int(wanted_plsc), d_plframes, d_count, stream or None))
+
+
+def plsync_taps():
+    """Imaginary parts (+-1) of the 25 SOF taps and the 32 PLSC taps of the timing metric, in header order. Host only."""
+    sof, pl = np.empty(25, np.float32), np.empty(32, np.float32)
+    check(lib.dvbs2_plsync_taps(sof.ctypes.data, pl.ctypes.data))
+    return sof, pl
+
+
+def plsync_thresholds():
+    """(unlocked, locked) timing-metric thresholds (reference lib/pl_frame_sync.h:160-162). Host only."""
+    u, lk = C.c_float(), C.c_float()
+    check(lib.dvbs2_plsync_thresholds(C.byref(u), C.byref(lk)))
+    return u.value, lk.value
 
 
 def pl_scrambling_rn(gold_code, n):

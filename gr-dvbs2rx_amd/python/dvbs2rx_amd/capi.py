@@ -43,6 +43,16 @@ class PlFrameEstimates(C.Structure):
                 ("pilot_phase", C.c_void_p), ("fine_foffset", C.c_void_p), ("fine_valid", C.c_void_p)]
 
 
+class PlSyncFrame(C.Structure):
+    """dvbs2_plsync_frame_t; PLSYNC_FRAME_DTYPE below is the same record for numpy."""
+    _fields_ = [("sof_index", C.c_int64), ("metric", C.c_float), ("plsc", C.c_uint8), ("flags", C.c_uint8), ("reserved", C.c_uint8 * 2)]
+
+
+PLSYNC_FRAME_DTYPE = [("sof_index", "<i8"), ("metric", "<f4"), ("plsc", "u1"), ("flags", "u1"), ("reserved", "u1", (2,))]
+PLSYNC_SEARCHING, PLSYNC_FOUND, PLSYNC_LOCKED = 0, 1, 2
+PLSYNC_REAL_PEAK, PLSYNC_FLAG_LOCKED = 1, 2
+
+
 # every symbol include/dvbs2_fec_hip.h declares: name -> (restype, argtypes)
 _vp, _i, _ip = C.c_void_p, C.c_int, C.POINTER(C.c_int)
 SYMBOLS = {
@@ -108,6 +118,18 @@ SYMBOLS = {
     "dvbs2_plframe_process_device": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "dvbs2_plheader_symbols": (_i, [_i, _vp]),
     "dvbs2_pls_parse": (_i, [_i, _ip, _ip, _ip, _ip, _ip, _ip]),
+    "dvbs2_plsync_create": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i]),
+    "dvbs2_plsync_destroy": (None, [_vp]),
+    "dvbs2_plsync_reset": (_i, [_vp]),
+    "dvbs2_plsync_set_plsc_mode": (_i, [_vp, _i, _i]),
+    "dvbs2_plsync_set_expected_pls": (_i, [_vp, _vp, _i]),
+    "dvbs2_plsync_metric_device": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "dvbs2_plsync_search_device": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "dvbs2_plsync_finish": (_i, [_vp, _ip, _ip, _ip]),
+    "dvbs2_plsync_search": (_i, [_vp, _vp, _i, _vp, _ip, _ip, _ip]),
+    "dvbs2_plsync_gather_device": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "dvbs2_plsync_taps": (_i, [_vp, _vp]),
+    "dvbs2_plsync_thresholds": (_i, [_vp, _vp]),
     "dvbs2_bbdeheader_create": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i]),
     "dvbs2_bbdeheader_create_raw": (_i, [C.POINTER(_vp), _i, _i, _i]),
     "dvbs2_bbdeheader_destroy": (None, [_vp]),

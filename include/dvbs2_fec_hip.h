@@ -388,6 +388,79 @@ int dvbs2_plframe_process_device(dvbs2_plframe_t* h, const float* d_plframes, in
 int dvbs2_plheader_symbols(int plsc, float* syms90);
 int dvbs2_pls_parse(int plsc, int* plframe_len, int* payload_len, int* xfecframe_len, int* n_slots, int* n_pilots, int* n_mod);
 
+/* ---- PLFRAME search (the frame_sync part of plsync_cc): finds the PLFRAMEs of a RAW symbol stream, so that the entries above no
+ * longer need a frame-aligned input. It restates frame_sync::step (reference lib/pl_frame_sync.cc:66-243) as three kernels:
+ *   metric   for EVERY symbol index n: d[n] = conj(x[n]) x[n-1] (:99), S[n] = the 25 differentials at PLHEADER positions 1..25
+ *            times the SOF taps, P[n] = the 32 differentials at positions 27, 29 .. 89 (the second symbol of each PLSC pair) times
+ *            the PLSC taps, metric[n] = max(|S + P|, |S - P|) (:130-150). It peaks (57 for unit-energy symbols) on the LAST PLHEADER
+ *            symbol and depends on x[n-89 .. n] only. The taps are +-j; dvbs2_plsync_taps returns their imaginary parts in header
+ *            order, derived from the expected PLHEADER symbols of PLSC 0 (bit 0 of a PLSC flips all 32 PLSC taps, which the
+ *            maximum over S +- P absorbs; no other PLSC bit changes them). The reference's folded tables (:39-52) are not copied.
+ *   tracker  the state machine of :168-243 with threshold_u = 30 while searching / found and threshold_l = 25 once locked
+ *            (lib/pl_frame_sync.h:160-162; dvbs2_plsync_thresholds). searching -> found on a peak; found -> locked on a peak exactly
+ *            one frame length after the last one; once locked only the expected index is looked at, a miss there counts towards
+ *            unlock_thresh consecutive misses (reference default 3) and the unlock_thresh-th returns to searching. Every accepted
+ *            peak, and every expected peak that failed the threshold while the lock holds (an INFERRED peak, :232-242), is the last
+ *            symbol of a PLHEADER: its PLSC is decoded from the 90 symbols ending there (lib/plsync_cc_impl.cc:880, :582-594) with
+ *            the decoder of dvbs2_plframe_* -- closed loop, i.e. de-rotated by the SOF phase, NOT the block's open-loop path that
+ *            needs the coarse frequency estimate -- and sets the frame length. set_plsc_mode / set_expected_pls as for
+ *            dvbs2_plframe_*: configuration calls, not while work of the handle is in flight. With plsc_or_minus1 >= 0 nothing is
+ *            decoded and every frame has that PLSC's length (the CCM/SIS path, lib/plsync_cc_impl.cc:145-159).
+ *            Reserved MODCODs 29..31: pls_info_t::parse gives them the 36-slot geometry (lib/pl_signaling.cc:41-54), so
+ *            set_frame_len never refuses a decoded PLSC; the tracker likewise takes dvbs2_pls_parse's plframe_len.
+ *   gather   copies the reported frames that are locked and carry wanted_plsc, in stream order, into back-to-back PLFRAMEs followed
+ *            by the 90 symbols after the last of them: the layout dvbs2_plframe_process_device reads with has_trailing_header = 1.
+ *            When other frames lie between two gathered ones, the "next header" a pilotless front end sees is not the adjacent one.
+ * syms       n_syms complex symbols (re, im), n_syms <= max_symbols; max_symbols >= 33282 + 90 (the longest PLFRAME and a PLHEADER)
+ * metric     n_syms floats. dvbs2_plsync_metric_device uses the handle's history and does not advance the handle (diagnostics).
+ * frames     max_frames records, written in stream order:
+ *              sof_index  absolute index (symbols since create / reset) of the first PLHEADER symbol
+ *              metric     the timing metric on the last PLHEADER symbol
+ *              plsc       the decoded (or fixed) PLSC
+ *              flags      bit 0: a real peak (not inferred); bit 1: the state was `locked` after this header
+ * Buffer-end rule: a frame is reported once, when its whole PLFRAME and the 90 symbols after it lie inside the buffer. *consumed is
+ * the buffer index of the first unreported frame's SOF (0 if that SOF lies before the buffer), or n_syms when none is pending; a frame
+ * that finds max_frames records written is left pending in the same way. The caller presents the stream again from there, as with
+ * GNU Radio's consume(). The handle carries
+ * state, frame length, unlock count, absolute offset, where to resume, and the 89 symbols before the consumed point (zeros after
+ * create / reset: the reference's cleared delay lines and d_last_in = 0). *state: 0 searching, 1 found, 2 locked.
+ * dvbs2_plsync_search_device is asynchronous on `stream`; dvbs2_plsync_finish waits for it and returns its counts. dvbs2_plsync_gather_device
+ * refers to the buffer of the LAST search; n_frames may be max_frames when the count is not known on the host yet (the device count
+ * bounds it); d_plframes needs room for the selected frames + 90 symbols and should be 16-byte aligned; *d_count = frames written.
+ * One defined difference: the reference selects its even / odd PLSC delay line by d_sym_cnt & 1 (:118-121) and restarts d_sym_cnt at
+ * every peak (:229); after a peak accepted at an odd count outside lock its PLSC correlation is not the sliding one for the next 63
+ * symbols. PLFRAME lengths are even, so lock is never affected. Outside lock, a threshold crossing within 63 symbols of an earlier
+ * one accepted at an odd count can differ. When the earlier crossing was a true header the later one cannot be a frame; when it was a
+ * FALSE crossing (plentiful at low Es/N0 without an AGC), a true header ending within those 63 symbols sees a corrupted PLSC
+ * correlation in the reference and may be missed there, while it is detected here. The metric here is the clean sliding correlation.
+ * A call that ends before the index at which a pending frame's header is to be looked at again (e.g. fewer than 90 symbols presented
+ * from a pending SOF) consumes nothing and reports nothing.
+ * Accuracy: the metric is a float sum in ascending header position where the reference uses VOLK's dot product: tested against a
+ * float64 model under 65 * 2^-23 * sum |x_k| |x_{k-1}| over the header, UNPINNED against the genuine reference, like the plframe
+ * estimates. A value is the same bits wherever its index falls in a call, so cutting a stream into calls does not change decisions. */
+typedef struct dvbs2_plsync dvbs2_plsync_t;
+typedef struct {
+    int64_t sof_index;
+    float metric;
+    uint8_t plsc, flags, reserved[2];
+} dvbs2_plsync_frame_t;
+int dvbs2_plsync_create(dvbs2_plsync_t** h, int plsc_or_minus1, int unlock_thresh, int max_symbols, int max_frames, int device);
+void dvbs2_plsync_destroy(dvbs2_plsync_t* h);
+int dvbs2_plsync_reset(dvbs2_plsync_t* h);
+int dvbs2_plsync_set_plsc_mode(dvbs2_plsync_t* h, int coherent, int soft);
+int dvbs2_plsync_set_expected_pls(dvbs2_plsync_t* h, const uint8_t* plsc_list, int n);
+int dvbs2_plsync_metric_device(dvbs2_plsync_t* h, const float* d_syms, int n_syms, float* d_metric, void* stream);
+int dvbs2_plsync_search_device(dvbs2_plsync_t* h, const float* d_syms, int n_syms, dvbs2_plsync_frame_t* d_frames, void* stream);
+int dvbs2_plsync_finish(dvbs2_plsync_t* h, int* n_frames, int* consumed, int* state);
+/* host pointers, synchronous */
+int dvbs2_plsync_search(dvbs2_plsync_t* h, const float* syms, int n_syms, dvbs2_plsync_frame_t* frames, int* n_frames, int* consumed,
+                        int* state);
+int dvbs2_plsync_gather_device(dvbs2_plsync_t* h, const float* d_syms, const dvbs2_plsync_frame_t* d_frames, int n_frames,
+                               int wanted_plsc, float* d_plframes, int32_t* d_count, void* stream);
+/* host only, no device needed: imaginary parts (+-1) of the 25 SOF taps and the 32 PLSC taps in header order; the two thresholds */
+int dvbs2_plsync_taps(float* sof25, float* plsc32);
+int dvbs2_plsync_thresholds(float* unlocked, float* locked);
+
 /* ---- downstream neighbour: BBFRAME de-header, replaces bbdeheader_bb_impl::general_work (reference
  * lib/bbdeheader_bb_impl.cc:144-264) with parse_bbheader (:77-136) and check_crc8 (:138-142, generator
  * x^8 + x^7 + x^6 + x^4 + x^2 + 1, :55). Input: whole descrambled BBFRAMEs of kbch / 8 bytes (what dvbs2_bch_decode /
