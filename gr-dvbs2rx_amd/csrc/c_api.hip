@@ -18,6 +18,8 @@
 #include "plpayload_hip.h"
 #include "plframe_hip.h"
 #include "plsync_hip.h"
+#include "plcoarse_hip.h"
+#include "rotator_hip.h"
 #include "bbdeheader_hip.h"
 #include "device_guard.h"
 #include "demap_math.hpp"
@@ -1554,6 +1556,246 @@ int dvbs2_plsync_gather_device(dvbs2_plsync_t* h, const float* d_syms, const dvb
     if (n_frames > h->ps->max_frames()) return fail(DVBS2_ESIZE, "n_frames exceeds max_frames");
     if (h->ps->gather_device(d_syms, reinterpret_cast<const PlSyncFrame*>(d_frames), n_frames, wanted_plsc, d_plframes, d_count, (hipStream_t)stream))
         return fail(DVBS2_EDEVICE, h->ps->error());
+    return DVBS2_OK;
+    API_CATCH
+}
+
+} // extern "C"
+
+/* ------------------------------------------------------------------ coarse frequency offset estimate */
+struct dvbs2_plcoarse {
+    PlCoarseHip* pc = nullptr;
+    float* d_hdr = nullptr; uint8_t* d_plsc = nullptr; float* d_out = nullptr; // staging of the host entry
+    hipStream_t stream = nullptr;
+    int device = 0;
+};
+
+static int plcoarse_check(const dvbs2_plcoarse* h, const void* src, int n_frames)
+{
+    if (!h) return fail(DVBS2_EINVAL, "null handle");
+    if (n_frames < 0 || (n_frames && !src)) return fail(DVBS2_EINVAL, "bad argument");
+    if (n_frames > h->pc->max_frames()) return fail(DVBS2_ESIZE, "n_frames exceeds max_frames");
+    return DVBS2_OK;
+}
+
+static PlCoarseOut plcoarse_out(float* foffset, int32_t* corrected, int32_t* new_est)
+{
+    PlCoarseOut o;
+    o.foffset = foffset; o.corrected = corrected; o.new_est = new_est;
+    return o;
+}
+
+extern "C" {
+
+int dvbs2_plcoarse_weights(int full, float* w)
+{
+    if (!w) return fail(DVBS2_EINVAL, "bad argument");
+    return plcoarse_weights(full, w);
+}
+
+int dvbs2_plcoarse_create(dvbs2_plcoarse_t** h, int period, int plsc_or_minus1, int max_frames, int device)
+{
+    API_TRY
+    if (!h) return fail(DVBS2_EINVAL, "null handle pointer");
+    *h = nullptr;
+    // arguments first: a bad argument is the caller's mistake on any machine
+    if (period < 1) return fail(DVBS2_EINVAL, "period must be at least 1");
+    if (plsc_or_minus1 < -1 || plsc_or_minus1 > 127) return fail(DVBS2_EINVAL, "plsc out of range (-1 = not known, 0..127)");
+    if (max_frames < 1 || max_frames > (1 << 20)) return fail(DVBS2_EINVAL, "max_frames out of range (1..1048576)");
+    return make_handle(h, device, false, [&](dvbs2_plcoarse* o) { return o->pc = new (std::nothrow) PlCoarseHip(period, plsc_or_minus1, max_frames, device); });
+    API_CATCH
+}
+
+void dvbs2_plcoarse_destroy(dvbs2_plcoarse_t* h)
+{
+    if (!h) return;
+    DeviceGuard guard(h->device);
+    (void)hipFree(h->d_hdr); (void)hipFree(h->d_plsc); (void)hipFree(h->d_out);
+    if (h->stream) (void)hipStreamDestroy(h->stream);
+    delete h->pc;
+    delete h;
+}
+
+int dvbs2_plcoarse_reset(dvbs2_plcoarse_t* h)
+{
+    API_TRY
+    if (!h) return fail(DVBS2_EINVAL, "null handle");
+    if (h->pc->reset()) return fail(DVBS2_EDEVICE, h->pc->error());
+    return DVBS2_OK;
+    API_CATCH
+}
+
+int dvbs2_plcoarse_estimate_device(dvbs2_plcoarse_t* h, const float* d_plframes, int64_t stride_syms, const uint8_t* d_plsc, int n_frames,
+                                   float* d_coarse_foffset, int32_t* d_coarse_corrected, int32_t* d_new_est, void* stream)
+{
+    API_TRY
+    if (int rc = plcoarse_check(h, d_plframes, n_frames)) return rc;
+    if (stride_syms < 90) return fail(DVBS2_EINVAL, "stride below the 90 header symbols");
+    if (!d_plsc && h->pc->fixed_plsc() < 0) return fail(DVBS2_EINVAL, "a handle without a fixed PLSC needs the per-frame PLSC array");
+    if (h->pc->frames_device(d_plframes, stride_syms, d_plsc, n_frames, plcoarse_out(d_coarse_foffset, d_coarse_corrected, d_new_est),
+                             (hipStream_t)stream)) return fail(DVBS2_EDEVICE, h->pc->error());
+    return DVBS2_OK;
+    API_CATCH
+}
+
+int dvbs2_plcoarse_estimate_records_device(dvbs2_plcoarse_t* h, const float* d_syms, int n_syms, int64_t base_index,
+                                           const dvbs2_plsync_frame_t* d_frames, int n_frames, float* d_coarse_foffset,
+                                           int32_t* d_coarse_corrected, int32_t* d_new_est, void* stream)
+{
+    API_TRY
+    if (int rc = plcoarse_check(h, d_frames, n_frames)) return rc;
+    if (n_syms < 0 || (n_frames && !d_syms)) return fail(DVBS2_EINVAL, "bad argument");
+    if (h->pc->records_device(d_syms, n_syms, reinterpret_cast<const PlSyncFrame*>(d_frames), n_frames, base_index,
+                              plcoarse_out(d_coarse_foffset, d_coarse_corrected, d_new_est), (hipStream_t)stream))
+        return fail(DVBS2_EDEVICE, h->pc->error());
+    return DVBS2_OK;
+    API_CATCH
+}
+
+// host entry: stage the 90 header symbols of every frame, run, copy back what the caller asked for
+int dvbs2_plcoarse_estimate(dvbs2_plcoarse_t* h, const float* plframes, int64_t stride_syms, const uint8_t* plsc, int n_frames,
+                            float* coarse_foffset, int32_t* coarse_corrected, int32_t* new_est)
+{
+    API_TRY
+    if (int rc = plcoarse_check(h, plframes, n_frames)) return rc;
+    if (stride_syms < 90) return fail(DVBS2_EINVAL, "stride below the 90 header symbols");
+    if (!plsc && h->pc->fixed_plsc() < 0) return fail(DVBS2_EINVAL, "a handle without a fixed PLSC needs the per-frame PLSC array");
+    if (n_frames == 0) return DVBS2_OK;
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(DVBS2_EDEVICE, "hipSetDevice failed");
+    const size_t mf = h->pc->max_frames(), nf = n_frames;
+    if (!h->stream) HCHK(hipStreamCreate(&h->stream));
+    if (!h->d_hdr) HCHK(hipMalloc(&h->d_hdr, mf * 90 * 8));
+    if (!h->d_plsc) HCHK(hipMalloc(&h->d_plsc, mf));
+    if (!h->d_out) HCHK(hipMalloc(&h->d_out, mf * 3 * 4));
+    HCHK(hipMemcpy2DAsync(h->d_hdr, 90 * 8, plframes, (size_t)stride_syms * 8, 90 * 8, nf, hipMemcpyHostToDevice, h->stream));
+    if (plsc) HCHK(hipMemcpyAsync(h->d_plsc, plsc, nf, hipMemcpyHostToDevice, h->stream));
+    float* d_fo = h->d_out; int32_t* d_cc = reinterpret_cast<int32_t*>(h->d_out + mf); int32_t* d_ne = reinterpret_cast<int32_t*>(h->d_out + 2 * mf);
+    if (h->pc->frames_device(h->d_hdr, 90, plsc ? h->d_plsc : nullptr, n_frames, plcoarse_out(d_fo, d_cc, d_ne), h->stream))
+        return fail(DVBS2_EDEVICE, h->pc->error());
+    if (coarse_foffset) HCHK(hipMemcpyAsync(coarse_foffset, d_fo, nf * 4, hipMemcpyDeviceToHost, h->stream));
+    if (coarse_corrected) HCHK(hipMemcpyAsync(coarse_corrected, d_cc, nf * 4, hipMemcpyDeviceToHost, h->stream));
+    if (new_est) HCHK(hipMemcpyAsync(new_est, d_ne, nf * 4, hipMemcpyDeviceToHost, h->stream));
+    HCHK(hipStreamSynchronize(h->stream));
+    return DVBS2_OK;
+    API_CATCH
+}
+
+} // extern "C"
+
+/* ------------------------------------------------------------------ rotator */
+struct dvbs2_rotator {
+    RotatorHip* rot = nullptr;
+    float* d_buf = nullptr; size_t cap = 0; // staging of the host entry, grown on demand
+    hipStream_t stream = nullptr;
+    int device = 0;
+};
+
+extern "C" {
+
+int dvbs2_rotator_create(dvbs2_rotator_t** h, double phase_inc, int device)
+{
+    API_TRY
+    if (!h) return fail(DVBS2_EINVAL, "null handle pointer");
+    *h = nullptr;
+    if (!(phase_inc == phase_inc) || phase_inc - phase_inc != 0.0) return fail(DVBS2_EINVAL, "phase_inc must be finite");
+    return make_handle(h, device, false, [&](dvbs2_rotator* o) { return o->rot = new (std::nothrow) RotatorHip(phase_inc, device); });
+    API_CATCH
+}
+
+void dvbs2_rotator_destroy(dvbs2_rotator_t* h)
+{
+    if (!h) return;
+    DeviceGuard guard(h->device);
+    (void)hipFree(h->d_buf);
+    if (h->stream) (void)hipStreamDestroy(h->stream);
+    delete h->rot;
+    delete h;
+}
+
+int dvbs2_rotator_reset(dvbs2_rotator_t* h)
+{
+    if (!h) return fail(DVBS2_EINVAL, "null handle");
+    h->rot->reset();
+    return DVBS2_OK;
+}
+
+int dvbs2_rotator_set_phase_inc(dvbs2_rotator_t* h, double phase_inc)
+{
+    API_TRY
+    if (!h) return fail(DVBS2_EINVAL, "null handle");
+    if (h->rot->set_phase_inc(phase_inc)) return fail(DVBS2_EINVAL, h->rot->error());
+    return DVBS2_OK;
+    API_CATCH
+}
+
+int dvbs2_rotator_schedule(dvbs2_rotator_t* h, int64_t offset, double phase_inc)
+{
+    API_TRY
+    if (!h) return fail(DVBS2_EINVAL, "null handle");
+    if (h->rot->schedule(offset, phase_inc)) return fail(DVBS2_EINVAL, h->rot->error());
+    return DVBS2_OK;
+    API_CATCH
+}
+
+int dvbs2_rotator_seek(dvbs2_rotator_t* h, int64_t n_syms)
+{
+    API_TRY
+    if (!h) return fail(DVBS2_EINVAL, "null handle");
+    if (h->rot->seek(n_syms)) return fail(DVBS2_EINVAL, h->rot->error());
+    return DVBS2_OK;
+    API_CATCH
+}
+
+int dvbs2_rotator_position(const dvbs2_rotator_t* h, int64_t* n_syms, int* queued)
+{
+    if (!h) return fail(DVBS2_EINVAL, "null handle");
+    if (n_syms) *n_syms = h->rot->position();
+    if (queued) *queued = h->rot->queued();
+    return DVBS2_OK;
+}
+
+int dvbs2_rotator_rotate_device(dvbs2_rotator_t* h, const float* d_in, int n_syms, float* d_out, void* stream)
+{
+    API_TRY
+    if (!h) return fail(DVBS2_EINVAL, "null handle");
+    if (n_syms < 0 || (n_syms && (!d_in || !d_out))) return fail(DVBS2_EINVAL, "bad argument");
+    if (((uintptr_t)d_in | (uintptr_t)d_out) & 7) return fail(DVBS2_EINVAL, "symbol buffers must be 8-byte aligned");
+    if (h->rot->rotate_device(d_in, n_syms, d_out, (hipStream_t)stream)) return fail(DVBS2_EDEVICE, h->rot->error());
+    return DVBS2_OK;
+    API_CATCH
+}
+
+int dvbs2_rotator_measure(int device, int n_syms, int regions, double* rotate_ms, double* copy_ms)
+{
+    API_TRY
+    if (!rotate_ms || !copy_ms) return fail(DVBS2_EINVAL, "bad argument");
+    if (int rc = check_device(device)) return rc;
+    std::string err;
+    if (rotator_measure(device, n_syms, regions, rotate_ms, copy_ms, &err)) return fail(err == "bad argument" ? DVBS2_EINVAL : DVBS2_EDEVICE, err);
+    return DVBS2_OK;
+    API_CATCH
+}
+
+int dvbs2_rotator_rotate(dvbs2_rotator_t* h, const float* in, int n_syms, float* out)
+{
+    API_TRY
+    if (!h) return fail(DVBS2_EINVAL, "null handle");
+    if (n_syms < 0 || (n_syms && (!in || !out))) return fail(DVBS2_EINVAL, "bad argument");
+    if (n_syms == 0) return DVBS2_OK;
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(DVBS2_EDEVICE, "hipSetDevice failed");
+    const size_t bytes = (size_t)n_syms * 8;
+    if (!h->stream) HCHK(hipStreamCreate(&h->stream));
+    if (h->cap < bytes) {
+        (void)hipFree(h->d_buf); h->d_buf = nullptr; h->cap = 0;
+        HCHK(hipMalloc(&h->d_buf, bytes));
+        h->cap = bytes;
+    }
+    HCHK(hipMemcpyAsync(h->d_buf, in, bytes, hipMemcpyHostToDevice, h->stream));
+    if (h->rot->rotate_device(h->d_buf, n_syms, h->d_buf, h->stream)) return fail(DVBS2_EDEVICE, h->rot->error());
+    HCHK(hipMemcpyAsync(out, h->d_buf, bytes, hipMemcpyDeviceToHost, h->stream));
+    HCHK(hipStreamSynchronize(h->stream));
     return DVBS2_OK;
     API_CATCH
 }

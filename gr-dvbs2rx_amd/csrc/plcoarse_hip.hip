@@ -1,0 +1,230 @@
+// plcoarse_hip.hip -- see plcoarse_hip.h.
+#include "plcoarse_hip.h"
+#include <cmath>
+#include <cstring>
+#include <new>
+
+#include "device_guard.h"
+namespace dvbs2 {
+
+int plcoarse_weights(int full, float* w)
+{
+    const unsigned L = full ? 89 : 25; // lib/pl_freq_sync.cc:74-85, the same expression in double, kept as float
+    for (unsigned m = 0; m < L; m++)
+        w[m] = (float)(3.0 * ((2 * L + 1.0) * (2 * L + 1.0) - (2 * m + 1.0) * (2 * m + 1.0)) / (((2 * L + 1.0) * (2 * L + 1.0) - 1) * (2 * L + 1)));
+    return (int)L;
+}
+
+namespace {
+
+using plsc::wave_sum;
+constexpr double kPi = 3.14159265358979323846;
+constexpr int kBatch = 16; // frames the window kernel loads ahead of the serial walk
+
+// x_k conj(h_k) sqrt(2): conj(h_k) sqrt(2) = ((k odd ? -1 : 1), -1) (1 - 2 bit) (lib/pi2_bpsk.cc:18-43), so each component is one
+// sum or difference of the two input components: one rounding, no multiply
+__device__ inline float2 unmod(float2 x, int k, int bit)
+{
+    const float sg = bit ? -1.0f : 1.0f;
+    const float cr = (k & 1) ? -sg : sg, ci = -sg;
+    return make_float2(x.x * cr - x.y * ci, x.x * ci + x.y * cr);
+}
+
+// One pass over a header of N symbols held as z0 (symbols 0..63 in lanes 0..63) and z1 (symbols 64..N-1 in lanes 0..N-65): lane l
+// leaves lag l in *a (sum over u = 0 .. N-l-1 of z[u+l] conj(z[u]), ascending u) and lag N - l in *b (u = N-l .. N-1 of
+// z[u] conj(z[u+l-N]), ascending u). All 64 lanes take part in every exchange.
+template <int N> __device__ inline void lag_pair(float2 z0, float2 z1, int l, float2* a, float2* b)
+{
+    float2 sa = make_float2(0.0f, 0.0f), sb = make_float2(0.0f, 0.0f);
+#pragma unroll
+    for (int u = 0; u < N; u++) {
+        const float2 zu = u < 64 ? make_float2(__shfl(z0.x, u), __shfl(z0.y, u)) : make_float2(__shfl(z1.x, u - 64), __shfl(z1.y, u - 64));
+        int idx = u + l;
+        const bool wrapped = idx >= N;
+        if (wrapped) idx -= N;
+        const int src = idx & 63;
+        float2 zo = make_float2(__shfl(z0.x, src), __shfl(z0.y, src));
+        if (N > 64) {
+            const float2 hi = make_float2(__shfl(z1.x, src), __shfl(z1.y, src));
+            if (idx >= 64) zo = hi;
+        }
+        const float re = zo.x * zu.x + zo.y * zu.y, im = zo.y * zu.x - zo.x * zu.y; // zo conj(zu)
+        if (!wrapped) { sa.x += re; sa.y += im; } else { sb.x += re; sb.y -= im; }  // after the wrap the pair is zu conj(zo)
+    }
+    *a = sa; *b = sb;
+}
+
+// one wavefront per header; r: kPlcoarseRecord float2 per frame, [0].x = 1 when the record holds a frame
+__global__ __launch_bounds__(64) void plcoarse_autocorr_kernel(const float2* __restrict__ x, long long stride, const uint8_t* __restrict__ plsc,
+                                                               int fixed_plsc, const PlSyncFrame* __restrict__ rec, int n_syms, long long base,
+                                                               const uint64_t* __restrict__ cwtab, float2* __restrict__ r)
+{
+    const int f = blockIdx.x, l = threadIdx.x;
+    float2* __restrict__ R = r + (size_t)f * kPlcoarseRecord;
+    const float2* __restrict__ h;
+    int p;
+    if (rec) {
+        const PlSyncFrame q = rec[f];
+        const long long rel = q.sof_index - base;
+        if (rel < 0 || rel + 90 > (long long)n_syms) { if (l == 0) R[0] = make_float2(0.0f, 0.0f); return; } // the whole wavefront leaves
+        h = x + rel; p = q.plsc & 127;
+    } else {
+        h = x + (long long)f * stride; p = plsc ? (plsc[f] & 127) : fixed_plsc;
+    }
+    const uint64_t cw = cwtab[p];
+    const int bit0 = l < 26 ? (int)((kSofWord >> (25 - l)) & 1) : (int)((cw >> (89 - l)) & 1);
+    const float2 z0 = unmod(h[l], l, bit0);
+    float2 z1 = make_float2(0.0f, 0.0f);
+    if (l < 26) z1 = unmod(h[64 + l], 64 + l, (int)((cw >> (25 - l)) & 1));
+
+    float2 a, b;
+    lag_pair<90>(z0, z1, l, &a, &b);
+    if (l >= 1 && l <= 45) R[l] = a;
+    if (l >= 1 && l <= 44) R[90 - l] = b; // lane 45's second half is lag 45 again: the same pairs, not written
+    lag_pair<26>(z0, z1, l, &a, &b);
+    if (l >= 1 && l <= 13) R[90 + l] = a;
+    if (l >= 1 && l <= 12) R[90 + 26 - l] = b;
+    if (l == 0) { R[0] = make_float2(1.0f, 0.0f); R[90] = make_float2(0.0f, 0.0f); }
+}
+
+__device__ inline float wrap_pi(float d) // lib/pl_freq_sync.cc:166-171: compared and corrected in double, kept as float
+{
+    if ((double)d > kPi) d = (float)((double)d - 2.0 * kPi);
+    else if ((double)d < -kPi) d = (float)((double)d + 2.0 * kPi);
+    return d;
+}
+
+// one wavefront; lane l holds lags l + 1 and l + 65
+__global__ __launch_bounds__(64) void plcoarse_window_kernel(const float2* __restrict__ r, int n_frames, int period, int always_full,
+                                                             const float* __restrict__ w, PlCoarseState* __restrict__ st, PlCoarseOut out)
+{
+    const int l = threadIdx.x;
+    const bool hi = l < 25; // the lane has a second lag (full form) / a lag at all (SOF form)
+    float2 a0 = st->acc[l + 1], a1 = hi ? st->acc[l + 65] : make_float2(0.0f, 0.0f);
+    int i_frame = st->i_frame, corrected = st->corrected;
+    float fo = st->foffset;
+    const float wf0 = w[l], wf1 = hi ? w[64 + l] : 0.0f, ws0 = hi ? w[89 + l] : 0.0f;
+
+    for (int f0 = 0; f0 < n_frames; f0 += kBatch) {
+        float2 v0[kBatch], v1[kBatch], vs[kBatch];
+        float valid[kBatch];
+#pragma unroll
+        for (int i = 0; i < kBatch; i++) { // the loads do not depend on the state: all in flight before the serial part
+            const int f = f0 + i < n_frames ? f0 + i : n_frames - 1;
+            const float2* __restrict__ R = r + (size_t)f * kPlcoarseRecord;
+            valid[i] = R[0].x;
+            v0[i] = R[l + 1];
+            v1[i] = hi ? R[l + 65] : make_float2(0.0f, 0.0f);
+            vs[i] = hi ? R[90 + l + 1] : make_float2(0.0f, 0.0f);
+        }
+#pragma unroll
+        for (int i = 0; i < kBatch; i++) {
+            const int f = f0 + i;
+            int new_est = 0;
+            if (f < n_frames && valid[i] != 0.0f) { // uniform over the wavefront
+                const bool full = always_full || corrected; // lib/plsync_cc_impl.cc:567-569
+                if (full) { a0.x += v0[i].x; a0.y += v0[i].y; a1.x += v1[i].x; a1.y += v1[i].y; }
+                else { a0.x += vs[i].x; a0.y += vs[i].y; }
+                if (++i_frame >= period) {
+                    const int L = full ? 89 : 25;
+                    const bool on0 = l + 1 <= L, on1 = full && hi;
+                    const float th0 = on0 ? atan2f(a0.y, a0.x) : 0.0f, th1 = on1 ? atan2f(a1.y, a1.x) : 0.0f;
+                    float p0 = __shfl_up(th0, 1), p1 = __shfl_up(th1, 1);
+                    const float th64 = __shfl(th0, 63);
+                    if (l == 0) { p0 = 0.0f; p1 = th64; } // angle_corr[0] = 0; lag 65 follows lag 64
+                    const float d0 = on0 ? wrap_pi(th0 - p0) : 0.0f, d1 = on1 ? wrap_pi(th1 - p1) : 0.0f;
+                    const float t0 = (full ? wf0 : ws0) * d0, t1 = wf1 * d1;
+                    const float s = wave_sum(t0 + t1);
+                    float e = (float)((double)s / (2.0 * kPi));
+                    e = e > 0.5f ? 0.5f : (e < -0.5f ? -0.5f : e);
+                    fo = e;
+                    corrected = fabs((double)e) < kFineFoffsetCorrRange ? 1 : 0;
+                    a0 = make_float2(0.0f, 0.0f); a1 = make_float2(0.0f, 0.0f);
+                    i_frame = 0; new_est = 1;
+                }
+            }
+            if (l == 0 && f < n_frames) {
+                if (out.foffset) out.foffset[f] = fo;
+                if (out.corrected) out.corrected[f] = corrected;
+                if (out.new_est) out.new_est[f] = new_est;
+            }
+        }
+    }
+    st->acc[l + 1] = a0;
+    if (hi) st->acc[l + 65] = a1;
+    if (l == 0) { st->i_frame = i_frame; st->corrected = corrected; st->foffset = fo; }
+}
+
+} // namespace
+
+PlCoarseHip::PlCoarseHip(int period, int plsc_or_minus1, int max_frames, int device)
+    : period_(period), fixed_plsc_(plsc_or_minus1), max_frames_(max_frames), device_(device)
+{
+    if (period_ < 1) { err_ = "period must be at least 1"; return; }
+    if (fixed_plsc_ < -1 || fixed_plsc_ > 127) { err_ = "plsc out of range (-1 = not known, 0..127)"; return; }
+    if (max_frames_ < 1 || max_frames_ > (1 << 20)) { err_ = "max_frames out of range (1..1048576)"; return; }
+    uint64_t cw[128];
+    for (int p = 0; p < 128; p++) cw[p] = plsc_codeword(p) ^ kPlscScrambler;
+    float w[89 + 25];
+    plcoarse_weights(1, w); plcoarse_weights(0, w + 89);
+    DeviceGuard dev_guard(device_);
+    if (!dev_guard.ok || hipMalloc(&d_cw_, sizeof(cw)) != hipSuccess || hipMalloc(&d_w_, sizeof(w)) != hipSuccess ||
+        hipMalloc(&d_r_, (size_t)max_frames_ * kPlcoarseRecord * sizeof(float2)) != hipSuccess ||
+        hipMalloc(&d_state_, sizeof(PlCoarseState)) != hipSuccess ||
+        hipMemcpy(d_cw_, cw, sizeof(cw), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_w_, w, sizeof(w), hipMemcpyHostToDevice) != hipSuccess) {
+        err_ = "device setup failed"; return;
+    }
+    if (reset()) { err_ = call_err_; call_err_.clear(); }
+}
+
+PlCoarseHip::~PlCoarseHip()
+{
+    DeviceGuard dev_guard(device_);
+    (void)hipFree(d_cw_); (void)hipFree(d_w_); (void)hipFree(d_r_); (void)hipFree(d_state_);
+}
+
+int PlCoarseHip::reset()
+{
+    call_err_.clear();
+    DeviceGuard dev_guard(device_);
+    // all zero: no frame counted, empty accumulator, estimate 0, not coarse-corrected (lib/pl_freq_sync.cc:24-31)
+    if (!dev_guard.ok || hipDeviceSynchronize() != hipSuccess || hipMemset(d_state_, 0, sizeof(PlCoarseState)) != hipSuccess) {
+        call_err_ = "reset of the device state failed"; return -2;
+    }
+    return 0;
+}
+
+int PlCoarseHip::launch(const float2* x, int64_t stride, const uint8_t* plsc, const PlSyncFrame* rec, int n_syms, int64_t base, int n_frames,
+                        const PlCoarseOut& out, hipStream_t stream)
+{
+    if (!ok()) return -1;
+    call_err_.clear();
+    if (n_frames < 0 || n_frames > max_frames_) { call_err_ = "n_frames exceeds max_frames"; return -1; }
+    if (n_frames == 0) return 0;
+    DeviceGuard dev_guard(device_);
+    if (!dev_guard.ok) { call_err_ = "hipSetDevice failed"; return -1; }
+    hipLaunchKernelGGL(plcoarse_autocorr_kernel, dim3(n_frames), dim3(64), 0, stream, x, (long long)stride, plsc, fixed_plsc_ < 0 ? 0 : fixed_plsc_,
+                       rec, n_syms, (long long)base, d_cw_, d_r_);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { call_err_ = std::string("plcoarse autocorrelation kernel launch: ") + hipGetErrorString(e); return -1; }
+    hipLaunchKernelGGL(plcoarse_window_kernel, dim3(1), dim3(64), 0, stream, d_r_, n_frames, period_, fixed_plsc_ >= 0 ? 1 : 0, d_w_, d_state_, out);
+    e = hipGetLastError();
+    if (e != hipSuccess) { call_err_ = std::string("plcoarse window kernel launch: ") + hipGetErrorString(e); return -1; }
+    return 0;
+}
+
+int PlCoarseHip::frames_device(const float* d_plframes, int64_t stride_syms, const uint8_t* d_plsc, int n_frames, const PlCoarseOut& out,
+                               hipStream_t stream)
+{
+    if (ok() && !d_plsc && fixed_plsc_ < 0) { call_err_ = "a handle without a fixed PLSC needs the per-frame PLSC array"; return -1; }
+    if (ok() && stride_syms < 90) { call_err_ = "stride below the 90 header symbols"; return -1; }
+    return launch(reinterpret_cast<const float2*>(d_plframes), stride_syms, d_plsc, nullptr, 0, 0, n_frames, out, stream);
+}
+
+int PlCoarseHip::records_device(const float* d_syms, int n_syms, const PlSyncFrame* d_records, int n_frames, int64_t base, const PlCoarseOut& out,
+                                hipStream_t stream)
+{
+    return launch(reinterpret_cast<const float2*>(d_syms), 0, nullptr, d_records, n_syms, base, n_frames, out, stream);
+}
+
+} // namespace dvbs2

@@ -6,6 +6,7 @@
 //   gr::dvbs2rx::bch_decoder_bb         include/gnuradio/dvbs2rx/bch_decoder_bb.h,        lib/bch_decoder_bb_impl.cc
 //   gr::dvbs2rx::xfecframe_demapper_cb  include/gnuradio/dvbs2rx/xfecframe_demapper_cb.h, lib/xfecframe_demapper_cb_impl.cc
 //   gr::dvbs2rx::bbdeheader_bb          include/gnuradio/dvbs2rx/bbdeheader_bb.h,         lib/bbdeheader_bb_impl.cc
+//   gr::dvbs2rx::rotator_cc             include/gnuradio/dvbs2rx/rotator_cc.h,            lib/rotator_cc_impl.cc
 //
 // It deliberately does NOT depend on GNU Radio (absent from the build image): the classes expose the
 // gr::block work-function signature with plain std::vector arguments, so that the reference's *_impl classes can
@@ -318,6 +319,37 @@ private:
     std::vector<uint64_t> d_saved; // frame number held by each pool slot
     std::vector<float> d_pool;     // saved XFECFRAMEs, interleaved (re, im)
     size_t d_pool_idx = 0;
+};
+
+// ---------------------------------------------------------------------------------------------- rotator
+// gr::dvbs2rx::rotator_cc (include/gnuradio/dvbs2rx/rotator_cc.h, lib/rotator_cc_impl.cc:36-128): a sync block, one output
+// item per input item. The "cmd" message of :41-71 is the cmd() call here: `inc` with an optional absolute `offset`; without
+// one the update is scheduled at the current item count (nitems_written(0), :61-63). Tagging of the updates (tag_inc_updates)
+// stays with GNU Radio. The phase is evaluated in closed form on the device (include/dvbs2_fec_hip.h), not by gr::rotator's
+// phasor recurrence.
+class rotator_cc {
+public:
+    typedef std::shared_ptr<rotator_cc> sptr;
+    static sptr make(double phase_inc = 0.0, bool /*tag_inc_updates*/ = false, int device = 0) { return sptr(new rotator_cc(phase_inc, device)); }
+    ~rotator_cc() { dvbs2_rotator_destroy(d_h); }
+    void set_phase_inc(double phase_inc) { check(dvbs2_rotator_set_phase_inc(d_h, phase_inc)); }                 // :36-39
+    void cmd(double inc) { check(dvbs2_rotator_schedule(d_h, (int64_t)nitems_written(), inc)); }                 // :61-64, no offset key
+    void cmd(double inc, uint64_t offset) { check(dvbs2_rotator_schedule(d_h, (int64_t)offset, inc)); }
+    uint64_t nitems_written() const
+    {
+        int64_t n = 0;
+        check(dvbs2_rotator_position(d_h, &n, nullptr));
+        return (uint64_t)n;
+    }
+    int work(int noutput_items, gr_vector_const_void_star& input_items, gr_vector_void_star& output_items)       // :73-128
+    {
+        check(dvbs2_rotator_rotate(d_h, static_cast<const float*>(input_items[0]), noutput_items, static_cast<float*>(output_items[0])));
+        return noutput_items;
+    }
+
+private:
+    rotator_cc(double phase_inc, int device) { check(dvbs2_rotator_create(&d_h, phase_inc, device)); }
+    dvbs2_rotator_t* d_h = nullptr;
 };
 
 } // namespace dvbs2rx_hip

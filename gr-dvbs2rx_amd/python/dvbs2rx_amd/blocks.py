@@ -16,7 +16,7 @@ from .capi import lib, check
 __all__ = ["get_fec_info", "rate_id", "LdpcDecoder", "BchDecoder", "Demapper", "FecChain", "BbDeheader", "ldpc_table_info", "ldpc_layer_info",
            "ldpc_table_names", "bb_descramble_sequence", "PlPayload",
            "pl_scrambling_rn", "HostBuffer", "PlFrontEnd", "plheader_symbols", "pls_parse",
-           "PlSync", "plsync_taps", "plsync_thresholds"]
+           "PlSync", "plsync_taps", "plsync_thresholds", "PlCoarse", "plcoarse_weights", "Rotator"]
 
 DEFAULT_TRIALS = 25  # reference lib/ldpc_decoder_bb_impl.cc:391
 
@@ -543,6 +543,133 @@ def plsync_thresholds():
     u, lk = C.c_float(), C.c_float()
     check(lib.dvbs2_plsync_thresholds(C.byref(u), C.byref(lk)))
     return u.value, lk.value
+
+
+def plcoarse_weights(full=True):
+    """The weighting window of the coarse estimate (reference lib/pl_freq_sync.cc:74-85) as float32: 89 values for the full
+    PLHEADER, 25 for the SOF. Host only."""
+    w = np.empty(89, np.float32)
+    n = check(lib.dvbs2_plcoarse_weights(int(bool(full)), w.ctypes.data))
+    return w[:n].copy()
+
+
+class PlCoarse:
+    """Coarse frequency offset estimate (reference lib/pl_freq_sync.cc:93-199, lib/plsync_cc_impl.cc:567-606): per frame the
+    autocorrelation of the modulation-removed PLHEADER (or SOF while not coarse-corrected and the PLSC is not known), summed
+    over `period` frames; on a window's last frame the estimate and the coarse-corrected flag. The handle keeps the window's
+    state on the device between calls. Outputs per frame: coarse_foffset float32, coarse_corrected int32, new_est int32."""
+
+    def __init__(self, period=1, plsc=-1, max_frames=1024, device=0):
+        """plsc = -1: the PLSC comes with every frame (SOF form until coarse-corrected); 0..127: known, always the full form."""
+        self._h = C.c_void_p()
+        check(lib.dvbs2_plcoarse_create(C.byref(self._h), int(period), int(plsc), int(max_frames), device))
+        self.period, self.plsc, self.max_frames = period, plsc, max_frames
+
+    def close(self):
+        if self._h:
+            lib.dvbs2_plcoarse_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        check(lib.dvbs2_plcoarse_reset(self._h))
+
+    def work(self, plframes, plsc=None):
+        """HOST buffer: complex64 [n_frames, stride] with stride >= 90 (only the first 90 symbols of a row are read); plsc: one
+        integer per frame, or None for the handle's fixed PLSC. Returns dict(coarse_foffset, coarse_corrected, new_est)."""
+        x = np.asarray(plframes)
+        if x.dtype != np.complex64:
+            raise TypeError(f"plframes must be complex64, not {x.dtype}")
+        if x.ndim != 2 or x.shape[1] < 90 or not x.flags.c_contiguous:
+            raise ValueError(f"plframes: a C-contiguous [n_frames, >= 90] array, got shape {x.shape}")
+        nf = x.shape[0]
+        if nf > self.max_frames:
+            raise ValueError(f"{nf} frames exceed max_frames = {self.max_frames}")
+        p = None
+        if plsc is not None:
+            p = np.asarray(plsc)
+            if p.shape != (nf,) or p.dtype.kind not in "iu" or (p.size and (p.min() < 0 or p.max() > 127)):
+                raise ValueError(f"plsc: {nf} integers in 0..127")
+            p = np.ascontiguousarray(p, np.uint8)
+        elif self.plsc < 0:
+            raise ValueError("a PlCoarse without a fixed PLSC needs plsc per frame")
+        fo, cc, ne = np.zeros(nf, np.float32), np.zeros(nf, np.int32), np.zeros(nf, np.int32)
+        check(lib.dvbs2_plcoarse_estimate(self._h, x.ctypes.data if nf else None, int(x.shape[1]), p.ctypes.data if p is not None and nf else None,
+                                          nf, fo.ctypes.data, cc.ctypes.data, ne.ctypes.data))
+        return dict(coarse_foffset=fo, coarse_corrected=cc, new_est=ne)
+
+    def work_device(self, d_plframes, stride_syms, n_frames, d_plsc=0, d_coarse_foffset=0, d_coarse_corrected=0, d_new_est=0, stream=0):
+        """DEVICE addresses, asynchronous on `stream`: frame f starts at symbol f * stride_syms; d_plsc = 0: the fixed PLSC."""
+        check(lib.dvbs2_plcoarse_estimate_device(self._h, d_plframes, int(stride_syms), d_plsc or None, int(n_frames), d_coarse_foffset or None,
+                                                 d_coarse_corrected or None, d_new_est or None, stream or None))
+
+    def work_records_device(self, d_syms, n_syms, base_index, d_frames, n_frames, d_coarse_foffset=0, d_coarse_corrected=0, d_new_est=0,
+                            stream=0):
+        """DEVICE addresses: a raw symbol buffer whose first symbol has absolute index base_index, and the first n_frames records
+        PlSync.work_device left for it."""
+        check(lib.dvbs2_plcoarse_estimate_records_device(self._h, d_syms, int(n_syms), int(base_index), d_frames, int(n_frames),
+                                                         d_coarse_foffset or None, d_coarse_corrected or None, d_new_est or None, stream or None))
+
+
+class Rotator:
+    """Frequency-correcting rotator (reference lib/rotator_cc_impl.cc:36-128): out[n] = in[n] exp(j phi[n]), phi advancing by the
+    phase increment per sample; increments change at once (set_phase_inc) or at scheduled absolute sample indices (schedule).
+    Evaluated in closed form from a 64-bit fixed-point phase, not by the reference's phasor recurrence."""
+
+    def __init__(self, phase_inc=0.0, device=0):
+        self._h = C.c_void_p()
+        check(lib.dvbs2_rotator_create(C.byref(self._h), float(phase_inc), device))
+
+    def close(self):
+        if self._h:
+            lib.dvbs2_rotator_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        check(lib.dvbs2_rotator_reset(self._h))
+
+    def set_phase_inc(self, phase_inc):
+        check(lib.dvbs2_rotator_set_phase_inc(self._h, float(phase_inc)))
+
+    def schedule(self, offset, phase_inc):
+        """Queue `phase_inc` for the absolute sample index `offset`."""
+        check(lib.dvbs2_rotator_schedule(self._h, int(offset), float(phase_inc)))
+
+    def seek(self, n_syms):
+        """Advance counter and phase over n_syms samples as calls would, without data."""
+        check(lib.dvbs2_rotator_seek(self._h, int(n_syms)))
+
+    def position(self):
+        """(sample counter, queued updates)."""
+        n, q = C.c_int64(), C.c_int()
+        check(lib.dvbs2_rotator_position(self._h, C.byref(n), C.byref(q)))
+        return n.value, q.value
+
+    def work(self, syms):
+        """HOST buffer of complex64 symbols; returns the rotated copy."""
+        x = np.asarray(syms)
+        if x.dtype != np.complex64:
+            raise TypeError(f"syms must be complex64, not {x.dtype}")
+        if x.ndim != 1 or not x.flags.c_contiguous:
+            raise ValueError("syms must be a C-contiguous vector")
+        out = np.empty_like(x)
+        check(lib.dvbs2_rotator_rotate(self._h, x.ctypes.data if x.size else None, int(x.size), out.ctypes.data if x.size else None))
+        return out
+
+    def work_device(self, d_in, n_syms, d_out, stream=0):
+        """DEVICE addresses (8-byte aligned), asynchronous on `stream`; d_out == d_in rotates in place."""
+        check(lib.dvbs2_rotator_rotate_device(self._h, d_in, int(n_syms), d_out, stream or None))
 
 
 def pl_scrambling_rn(gold_code, n):

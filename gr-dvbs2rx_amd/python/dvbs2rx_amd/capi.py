@@ -130,6 +130,23 @@ SYMBOLS = {
     "dvbs2_plsync_gather_device": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "dvbs2_plsync_taps": (_i, [_vp, _vp]),
     "dvbs2_plsync_thresholds": (_i, [_vp, _vp]),
+    "dvbs2_plcoarse_create": (_i, [C.POINTER(_vp), _i, _i, _i, _i]),
+    "dvbs2_plcoarse_destroy": (None, [_vp]),
+    "dvbs2_plcoarse_reset": (_i, [_vp]),
+    "dvbs2_plcoarse_estimate_device": (_i, [_vp, _vp, C.c_int64, _vp, _i, _vp, _vp, _vp, _vp]),
+    "dvbs2_plcoarse_estimate_records_device": (_i, [_vp, _vp, _i, C.c_int64, _vp, _i, _vp, _vp, _vp, _vp]),
+    "dvbs2_plcoarse_estimate": (_i, [_vp, _vp, C.c_int64, _vp, _i, _vp, _vp, _vp]),
+    "dvbs2_plcoarse_weights": (_i, [_i, _vp]),
+    "dvbs2_rotator_create": (_i, [C.POINTER(_vp), C.c_double, _i]),
+    "dvbs2_rotator_destroy": (None, [_vp]),
+    "dvbs2_rotator_reset": (_i, [_vp]),
+    "dvbs2_rotator_set_phase_inc": (_i, [_vp, C.c_double]),
+    "dvbs2_rotator_schedule": (_i, [_vp, C.c_int64, C.c_double]),
+    "dvbs2_rotator_seek": (_i, [_vp, C.c_int64]),
+    "dvbs2_rotator_position": (_i, [_vp, C.POINTER(C.c_int64), _ip]),
+    "dvbs2_rotator_rotate_device": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "dvbs2_rotator_rotate": (_i, [_vp, _vp, _i, _vp]),
+    "dvbs2_rotator_measure": (_i, [_i, _i, _i, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "dvbs2_bbdeheader_create": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i]),
     "dvbs2_bbdeheader_create_raw": (_i, [C.POINTER(_vp), _i, _i, _i]),
     "dvbs2_bbdeheader_destroy": (None, [_vp]),

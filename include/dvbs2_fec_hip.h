@@ -461,6 +461,89 @@ int dvbs2_plsync_gather_device(dvbs2_plsync_t* h, const float* d_syms, const dvb
 int dvbs2_plsync_taps(float* sof25, float* plsc32);
 int dvbs2_plsync_thresholds(float* unlocked, float* locked);
 
+/* ---- coarse frequency offset estimate: freq_sync::estimate_coarse (reference lib/pl_freq_sync.cc:93-199) with the mode rule of
+ * its caller (lib/plsync_cc_impl.cc:567-606). It PRODUCES the coarse_corrected / coarse_foffset arrays dvbs2_plframe_*_device reads.
+ * Per frame: z[k] = x[k] conj(h[k]) with h the expected PLHEADER of the frame's PLSC (dvbs2_plheader_symbols; a common positive
+ * scale is dropped), R[m] = sum_{k=0}^{N-m-1} z[k+m] conj(z[k]) for m = 1..L, with N = 90, L = 89 (full PLHEADER) or N = 26, L = 25
+ * (SOF only), accumulated over the `period` consecutive frames of a window. On a window's last frame: theta[m] = atan2(R[m]),
+ * theta[0] = 0; d[m] = theta[m+1] - theta[m] for m = 0..L-1, wrapped by one step of +-2 pi; f = clip(sum w[m] d[m] / 2 pi, +-0.5)
+ * with w[m] = 3 ((2L+1)^2 - (2m+1)^2) / (((2L+1)^2 - 1)(2L+1)) (dvbs2_plcoarse_weights); coarse_corrected = |f| < 3.3875e-4; the
+ * accumulator and the frame counter restart. A frame uses the full PLHEADER when the state was coarse-corrected before it, or when
+ * the handle was created with a known PLSC (plsc_or_minus1 >= 0: the reference's "PLSC decoder disabled"), and the SOF otherwise; the
+ * state changes on a window's last frame only, so the form is constant within a window.
+ * Outputs per frame, each nullable: coarse_foffset (float: the latest estimate, 0 before the first), coarse_corrected (int32: the
+ * state AFTER this frame), new_est (int32: 1 on a window's last frame). The state -- frame counter, accumulator, f, corrected flag --
+ * lives on the device and carries over from call to call: a frame sequence cut into several calls (on one stream) gives the same
+ * bits as one call. dvbs2_plcoarse_reset waits for the device and gives the handle as created.
+ * Two ways to name the headers, both DEVICE pointers, asynchronous on `stream`:
+ *   dvbs2_plcoarse_estimate_device          frame f starts at symbol f * stride_syms of d_plframes (stride_syms >= 90; the layout
+ *                                           dvbs2_plsync_gather_device writes has stride = plframe_len); d_plsc: one byte per frame,
+ *                                           or NULL for the handle's fixed PLSC.
+ *   dvbs2_plcoarse_estimate_records_device  a raw symbol buffer and the records dvbs2_plsync_search_device left for it; base_index
+ *                                           is the absolute index of d_syms[0] (0 for the first search after create / reset, then the
+ *                                           sum of the `consumed` values so far), the PLSC is the record's. EVERY record is a frame
+ *                                           (the reference estimates at every handled PLHEADER, locked or not). A record whose 90
+ *                                           symbols do not all lie inside [0, n_syms) is passed over: it does not count towards the
+ *                                           window, and its outputs repeat the state with new_est = 0.
+ * dvbs2_plcoarse_estimate is the host-buffer form of the first (synchronous; it stages the 90 header symbols of each frame).
+ * n_frames <= max_frames. There is no CPU fallback. dvbs2_plcoarse_weights (host only) writes the 89 (full != 0) or 25 window
+ * weights as the floats the kernel uses and returns their count.
+ * What stays in the GNU Radio block: the message to the rotator (control_rotator_freq, tag calibration) and the open-loop
+ * de-rotation inside the tracker's PLSC decode.
+ * Accuracy: the sums are float, each lag in ascending symbol order and the frames in order, where the reference uses VOLK's dot
+ * product; the angles are atan2f where it uses gr::fast_atan2f (a table). Neither is available to compare with, so the estimate is
+ * tested against a float64 model under a derived float32 bound and is UNPINNED against the genuine reference, like the plframe
+ * estimates. At the three decision points -- a difference at +-pi, f at +-0.5, |f| at 3.3875e-4 -- a float evaluation may
+ * legitimately decide otherwise than the model. */
+typedef struct dvbs2_plcoarse dvbs2_plcoarse_t;
+int dvbs2_plcoarse_create(dvbs2_plcoarse_t** h, int period, int plsc_or_minus1, int max_frames, int device);
+void dvbs2_plcoarse_destroy(dvbs2_plcoarse_t* h);
+int dvbs2_plcoarse_reset(dvbs2_plcoarse_t* h);
+int dvbs2_plcoarse_estimate_device(dvbs2_plcoarse_t* h, const float* d_plframes, int64_t stride_syms, const uint8_t* d_plsc, int n_frames,
+                                   float* d_coarse_foffset, int32_t* d_coarse_corrected, int32_t* d_new_est, void* stream);
+int dvbs2_plcoarse_estimate_records_device(dvbs2_plcoarse_t* h, const float* d_syms, int n_syms, int64_t base_index,
+                                           const dvbs2_plsync_frame_t* d_frames, int n_frames, float* d_coarse_foffset,
+                                           int32_t* d_coarse_corrected, int32_t* d_new_est, void* stream);
+/* host pointers, synchronous */
+int dvbs2_plcoarse_estimate(dvbs2_plcoarse_t* h, const float* plframes, int64_t stride_syms, const uint8_t* plsc, int n_frames,
+                            float* coarse_foffset, int32_t* coarse_corrected, int32_t* new_est);
+int dvbs2_plcoarse_weights(int full, float* w);
+
+/* ---- rotator: rotator_cc::work (reference lib/rotator_cc_impl.cc:36-128). out[n] = in[n] e^{j phi[n]}, phi[n+1] = phi[n] + inc[n],
+ * phi = 0 at the first sample after create / reset. dvbs2_rotator_set_phase_inc takes effect at once; dvbs2_rotator_schedule queues
+ * an update for an ABSOLUTE sample index (counted from create / reset), across which the phase stays continuous. An update whose
+ * index is already behind the handle's sample counter when a call reaches it is dropped (:92-95); one at or beyond the end of a call
+ * stays queued. Updates with EQUAL indices are applied in the order they were scheduled, so the last one wins (the reference's
+ * priority queue leaves that order open; this is the defined choice here). The counter is int64 and advances by n_syms per call.
+ * dvbs2_rotator_seek(n) advances counter and phase over n samples exactly as calls would -- applying and dropping updates on the
+ * way -- without touching data. dvbs2_rotator_reset gives the handle as created: counter 0, phase 0, the increment of create, an
+ * empty queue. dvbs2_rotator_position returns the counter and the number of queued updates.
+ * Buffers: complex float (re, im), 8-byte aligned; d_out == d_in is allowed, any other overlap is not. The device entry is
+ * asynchronous on `stream`; schedule / set_phase_inc / seek are host-side and apply to calls made after them.
+ * CLOSED FORM, not the reference's recurrence: gr::rotator multiplies a float phasor by e^{j inc} per sample and renormalises it
+ * every 512 samples (volk_32fc_s32fc_x2_rotator_32fc); its error grows along the stream and one thread must walk it. Here the phase
+ * is unsigned 64-bit fixed point in turns (2^64 = one turn), an increment is converted once in extended precision, the start phase
+ * of every constant-increment segment is a prefix sum on the host, and sample n of a segment (n_s, P_s, I_s) has the phase
+ * P_s + (n - n_s) I_s in exact integer arithmetic; its upper 32 bits go to sincospif as a float in half-turns. Hence a sample's
+ * result does not depend on how the stream is cut into calls or on addresses (pieces == one call, in place == out of place, bit for
+ * bit), and the phase error is at most 2^-26 + 2^-32 turns from the conversion to float plus, per sample of its segment,
+ * (|inc| / 2 pi) 2^-63 + 2^-65 turns from the one rounding of the increment. VOLK is not available to compare the recurrence with:
+ * the output is tested against a float64 evaluation of the exact phase under a derived bound, UNPINNED against the genuine reference. */
+typedef struct dvbs2_rotator dvbs2_rotator_t;
+int dvbs2_rotator_create(dvbs2_rotator_t** h, double phase_inc, int device);
+void dvbs2_rotator_destroy(dvbs2_rotator_t* h);
+int dvbs2_rotator_reset(dvbs2_rotator_t* h);
+int dvbs2_rotator_set_phase_inc(dvbs2_rotator_t* h, double phase_inc);
+int dvbs2_rotator_schedule(dvbs2_rotator_t* h, int64_t offset, double phase_inc);
+int dvbs2_rotator_seek(dvbs2_rotator_t* h, int64_t n_syms);
+int dvbs2_rotator_position(const dvbs2_rotator_t* h, int64_t* n_syms, int* queued);
+int dvbs2_rotator_rotate_device(dvbs2_rotator_t* h, const float* d_in, int n_syms, float* d_out, void* stream);
+/* host pointers, synchronous */
+int dvbs2_rotator_rotate(dvbs2_rotator_t* h, const float* in, int n_syms, float* out);
+/* measurement aid (tools/plcoarse_time.py): median over `regions` HIP-event regions of one rotation of n_syms symbols and, in the same
+ * run, of a plain 16-byte-per-lane copy kernel over the same bytes on the same grid; it allocates 2 * 8 * n_syms bytes for the run */
+int dvbs2_rotator_measure(int device, int n_syms, int regions, double* rotate_ms, double* copy_ms);
+
 /* ---- downstream neighbour: BBFRAME de-header, replaces bbdeheader_bb_impl::general_work (reference
  * lib/bbdeheader_bb_impl.cc:144-264) with parse_bbheader (:77-136) and check_crc8 (:138-142, generator
  * x^8 + x^7 + x^6 + x^4 + x^2 + 1, :55). Input: whole descrambled BBFRAMEs of kbch / 8 bytes (what dvbs2_bch_decode /
