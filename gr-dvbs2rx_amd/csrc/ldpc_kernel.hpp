@@ -626,18 +626,18 @@ __device__ __forceinline__ void check_node_chain_v2(const uint32_t* ent /*S0w[DM
         two_smallest<4>(m4, n0, n1);
         n0 &= 0x7f00; n1 &= 0x7f00;
         const int n0m = (int)__builtin_elementwise_sub_sat((uint32_t)n0, 256u), n1m = (int)__builtin_elementwise_sub_sat((uint32_t)n1, 256u);
-        const int B0 = n0, B1 = n0 + n1m - n0m, T = n1m + n0;
-        const v2s16 B0p = { (short)B0, (short)B0 }, B1p = { (short)B1, (short)B1 }, Tp = { (short)T, (short)T };
+        // outputs in the pair form of check_node_v2 (pair_out: min(a, B1) for the clamp -- every real half, the pair's included, is >= n0 --,
+        // the sign applied before the subtraction, one shift for both LLR bytes) and its one-v_perm message packing
+        const int B1 = n0 + n1m - n0m, T = n1m + n0;
+        const v2s16 B1p = { (short)B1, (short)B1 };
         const uint32_t tm = (uint32_t)((int)(sxp ^ (sxp << 16)) >> 31);
+        const uint32_t Tt = __builtin_amdgcn_perm((uint32_t)T, (uint32_t)T, 0x01000100u) ^ tm;
         uint32_t R[NP];
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int j = 0; j < NP; j++) {
-            const v2s16 cl = __builtin_elementwise_min(__builtin_elementwise_max(a[j], B0p), B1p);
-            const v2s16 other = Tp - cl;
-            const v2s16 sg = as_v2s(as_u32(d[j]) ^ tm) >> (v2s16){ 15, 15 };
-            const v2s16 out = as_v2s(as_u32(other) ^ as_u32(sg)) - sg;
-            const uint32_t nl = (as_u32(__builtin_elementwise_add_sat(d[j], out)) ^ kObPair<TC>) >> 8;
+            uint32_t nl;
+            pair_out<TC>(d[j], a[j], B1p, Tt, tm, nl, R[j]);
             if (j == 0) {
                 if (jj + B >= kM) lds_wr(ad[0], (int)nl);   // a tail row is the last writer of its X bit (the others handed X down the chain)
                 if (body) lds_wr_hi(ad[1], nl);             // heads wrote Y in P1 (by now a tail row may have replaced it)
@@ -645,11 +645,9 @@ __device__ __forceinline__ void check_node_chain_v2(const uint32_t* ent /*S0w[DM
                 lds_wr(ad[2 * j], (int)nl);
                 if (!(ODD && j == NP - 1)) lds_wr_hi(ad[2 * j + 1], nl);
             }
-            R[j] = as_u32(__builtin_elementwise_min(__builtin_elementwise_max(out, (v2s16){ -32 * 256, -32 * 256 }), (v2s16){ 31 * 256, 31 * 256 }));
         }
         __builtin_amdgcn_s_setprio(3);
-        if (ODD) R[NP - 1] &= 0x0000ffffu;
-        msg_pack16<NP>(R, nm);
+        msg_pack16_hb<NP, ODD>(R, nm);
     }
 }
 
@@ -1344,23 +1342,26 @@ __device__ __forceinline__ void check_node_hazard(uint8_t* __restrict__ lds, con
 
 // degrees DMAX-7 .. DMAX are instantiated for kernel variant DMAX
 #define DVBS2_DEG_CASE(D) case D: if constexpr (D >= 3 && D <= DMAX && D > DMAX - 8) { \
-        { if (layer0) check_node<(D >= 3 ? D : 3), true, false, false, TC>(lds_all, ent, jj, lb, mw, nm); else { if constexpr (!kPure) check_node<(D >= 3 ? D : 3), false, false, false, TC>(lds_all, ent, jj, lb, mw, nm); } } } break;
+        { if (layer0) check_node<(D >= 3 ? D : 3), true, false, false, TC>(lds_all, ent, jj, lb, mw, nm); else { if constexpr (!kPure) check_node<(D >= 3 ? D : 3), false, false, false, TC>(lds_all, ent, jj, lb, mw, nm); } } } else DVBS2_NM_CLEAR break;
 #define DVBS2_DEG_SWITCH switch (deg) { \
         DVBS2_DEG_CASE(3) DVBS2_DEG_CASE(4) DVBS2_DEG_CASE(5) DVBS2_DEG_CASE(6) DVBS2_DEG_CASE(7) DVBS2_DEG_CASE(8) \
         DVBS2_DEG_CASE(9) DVBS2_DEG_CASE(10) DVBS2_DEG_CASE(11) DVBS2_DEG_CASE(12) DVBS2_DEG_CASE(13) DVBS2_DEG_CASE(14) \
         DVBS2_DEG_CASE(15) DVBS2_DEG_CASE(16) DVBS2_DEG_CASE(17) DVBS2_DEG_CASE(18) DVBS2_DEG_CASE(19) DVBS2_DEG_CASE(20) \
         DVBS2_DEG_CASE(21) DVBS2_DEG_CASE(22) DVBS2_DEG_CASE(23) DVBS2_DEG_CASE(24) DVBS2_DEG_CASE(25) DVBS2_DEG_CASE(26) \
         DVBS2_DEG_CASE(27) DVBS2_DEG_CASE(28) DVBS2_DEG_CASE(29) DVBS2_DEG_CASE(30) DVBS2_DEG_CASE(31) DVBS2_DEG_CASE(32) \
-        default: break; }
+        default: DVBS2_NM_CLEAR break; }
 
-#define DVBS2_V2_CASE(D) case D: if constexpr (D >= 3 && D <= DMAX && D > DMAX - 8) { check_node_v2<(D >= 3 ? D : 3), DMAX, TC>(ent, jj + lb, mw, nm, prefetch); } break;
+#define DVBS2_V2_CASE(D) case D: if constexpr (D >= 3 && D <= DMAX && D > DMAX - 8) { check_node_v2<(D >= 3 ? D : 3), DMAX, TC>(ent, jj + lb, mw, nm, prefetch); } else DVBS2_NM_CLEAR break;
 #define DVBS2_V2_SWITCH switch (deg) { \
         DVBS2_V2_CASE(3) DVBS2_V2_CASE(4) DVBS2_V2_CASE(5) DVBS2_V2_CASE(6) DVBS2_V2_CASE(7) DVBS2_V2_CASE(8) \
         DVBS2_V2_CASE(9) DVBS2_V2_CASE(10) DVBS2_V2_CASE(11) DVBS2_V2_CASE(12) DVBS2_V2_CASE(13) DVBS2_V2_CASE(14) \
         DVBS2_V2_CASE(15) DVBS2_V2_CASE(16) DVBS2_V2_CASE(17) DVBS2_V2_CASE(18) DVBS2_V2_CASE(19) DVBS2_V2_CASE(20) \
         DVBS2_V2_CASE(21) DVBS2_V2_CASE(22) DVBS2_V2_CASE(23) DVBS2_V2_CASE(24) DVBS2_V2_CASE(25) DVBS2_V2_CASE(26) \
         DVBS2_V2_CASE(27) DVBS2_V2_CASE(28) DVBS2_V2_CASE(29) DVBS2_V2_CASE(30) DVBS2_V2_CASE(31) DVBS2_V2_CASE(32) \
-        default: break; }
+        default: DVBS2_NM_CLEAR break; }
+// (a degree the build does not instantiate -- a case without a body, or the default -- never occurs in a record. Left undefined there, nm became a value carried round the
+// layer loop: one 64-bit register copy per layer on EVERY path. Defined there, it costs the paths that run nothing.)
+#define DVBS2_NM_CLEAR { _Pragma("unroll") for (int w_ = 0; w_ < MW; w_++) nm[w_] = 0u; }
 
 #define DVBS2_CHAIN_CASE(D) case D: if constexpr (D >= 4 && D <= DMAX && D > DMAX - 8) { check_node_chain_v2<(D >= 4 ? D : 4), DMAX, TC>(ent, jj, jj + lb, work, block, mw, nm, htab16, hb_ctr, hb_epoch, hb_lane); } break;
 #define DVBS2_CHAIN_SWITCH switch (deg) { \
@@ -1438,6 +1439,7 @@ __device__ __attribute__((noinline)) int syndrome_sign_vectors(const lds_byte_t*
 }
 
 constexpr int kSoloThreads = 512;
+static_assert(kCuSlots == 16 * 8 * 2 * 16, "the per-CU counter table (ldpc_layout.h) must hold every index hw_cu_index() can return: XCC x SE x SH x CU");
 __device__ __forceinline__ uint32_t hw_cu_index()
 {
     uint32_t hw, xcc;
@@ -1617,6 +1619,20 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
 #pragma unroll
         for (int w = 0; w < MW; w++) MSG_ST(src[w], soff, w, r4);
     };
+    // The messages of the layer at hand (mw <- pre) and the load of the next layer's (byte offset `next`) into pre. In a frame's first sweep
+    // (zero) nothing is loaded and mw is the zero message of the layer's format. The first-sweep arm is a real branch (the empty asm
+    // statement cannot be speculated, so the arm is not turned into selects), and the load is unconditional in every other sweep -- the
+    // last layer fetches layer 0's record again, whose store is 89 layers and as many vmcnt(0) waits old, and drops it --: with a load
+    // that may not happen the old pre had to survive it, which cost a second 64-bit copy per layer.
+    auto take_msgs = [&](uint32_t* mw, uint32_t* pre, bool zero, uint32_t zero_word, int next, int r4) {
+#pragma unroll
+        for (int w = 0; w < MW; w++) mw[w] = pre[w];
+        if (zero) {
+            asm volatile("" ::: "memory");
+#pragma unroll
+            for (int w = 0; w < MW; w++) mw[w] = zero_word;
+        } else msg_load(pre, next, r4);
+    };
     // bnl = 0 before the first update (layered_decoder.hh:27-31,149): a frame's first sweep (it == 0, in the first pass or
     // when a frame that stopped at once is resumed) takes offset-binary zero bytes instead of loading them -- no memset
     // of the record area, no read traffic in sweep 0
@@ -1758,7 +1774,9 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
         const bool work = __builtin_amdgcn_readfirstlane(finished ? 0 : 1) != 0; // uniform over the wave, and the compiler knows it
         const int row = tid < kM ? tid : kM - 1;
         const int row4 = row * 4;
-        const bool zero_msgs = it == 0; // uniform over the half
+        // uniform over the half, and the compiler knows it: the zero messages of a frame's first sweep are a scalar branch per layer
+        // (take_msgs), not a compare mask and one v_cndmask per message word in every layer of every sweep
+        const bool zero_msgs = __builtin_amdgcn_readfirstlane(it) == 0;
         // timing builds: cycles per phase of the hazard nodes, frame 0, lane 0 of waves 0 and 5 (slots 256.. and 272.. after the per-layer sums)
         unsigned long long* const hz_ph = (TIMING && tdbg && f == 0 && (tid == 0 || tid == 320)) ? tdbg + (size_t)n_frames * 48 + 256 + (tid ? 16 : 0) : nullptr;
         uint32_t pre[MW]; // messages of the next layer for check tid, loaded one layer ahead
@@ -1799,7 +1817,8 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
             uint32_t ent[2 * DMAX];
 #pragma unroll
             for (int k = 0; k < 2 * DMAX; k++) ent[k] = (PF <= 2 * DMAX - 1 && k % PF == 0) ? nent[k] : wr[(size_t)i * RSW + 4 + k];
-            const uint32_t* nrec = wr + (size_t)(i + 1 < q ? i + 1 : 0) * RSW;
+            const int inext = i + 1 < q ? i + 1 : 0; // the layer whose record and messages are fetched ahead
+            const uint32_t* nrec = wr + (size_t)inext * RSW;
             auto prefetch = [&](uint32_t after) {
                 const uint32_t* p = nrec; (void)after;
                 nhdr = p[0];
@@ -1834,9 +1853,7 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
                     const bool v2 = V2 && ((hdr >> 13) & 1u);
                     // v2: this wave's record is in the packed node's format (two's complement messages)
                     uint32_t mw[MW], nm[MW];
-#pragma unroll
-                    for (int w = 0; w < MW; w++) mw[w] = zero_msgs ? (v2 ? 0u : 0x80808080u) : pre[w];
-                    if (i + 1 < q && !zero_msgs) msg_load(pre, mso + kLayerBytes, row4);
+                    take_msgs(mw, pre, zero_msgs, v2 ? 0u : 0x80808080u, inext * kLayerBytes, row4);
                     if constexpr (V2) { if (v2) { DVBS2_V2_SWITCH } else DVBS2_DEG_SWITCH } else DVBS2_DEG_SWITCH
                     DVBS2_WAIT_VM0();
                     msg_store(nm, mso, row4);

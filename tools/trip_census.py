@@ -1,0 +1,196 @@
+#!/usr/bin/env python3
+"""tools/trip_census.py -- STATIC census of what a wave issues per trip in three places of a packed sweep-kernel build, from the device
+code of gr-dvbs2rx_amd/build/ldpc_inst_<DMAX>.o, by the issue-rate classes of tools/valu_census.py (sibling of tools/node_census.py,
+which counts the regular node alone).
+
+  python tools/trip_census.py                       # <8, packed, solo> (table B4's build), degree 7
+  python tools/trip_census.py --obj OTHER.o --kernel "ldpc_layered_kernel<8, packed>" --deg 7
+
+ (a) one REGULAR layer trip of the given degree: the cycle of basic blocks through the packed node (check_node_v2, found by its issue
+     priority marks as in node_census.py) that a layer of that degree runs in every sweep but a frame's first -- the cheapest cycle of the
+     control-flow graph through the node's block that loads messages, stores messages (a frame's first sweep loads none) and meets
+     no barrier; the blocks it takes are printed, so the choice can be checked against the disassembly. Split into "node"
+     (s_setprio 0 .. the end of the node's block: the node and its message packing, what node_census.py calls total) and "else"
+     (everything outside: the layer head, the switch, message load / store, the copies at the loop's back edge).
+ (b) one HAZARD layer of the single-pair lane-chain form (check_node_chain_v2) of that degree: the text between the node's first
+     s_setprio 0 and the message packing behind its last phase, split at its two barriers into P1 (regular entries read and reduced,
+     heads' pair, chain operands published), walk (per chain: prologue + ONE four-step trip of the walk loop + the three tail steps)
+     and P3 (pair completed, minima merged, outputs, packing). This is text in address order: every arm of a lane-divergent branch
+     counts once, as every wave with rows of both kinds issues it.
+ (c) one trip of the syndrome PRE-TEST (four edges of one layer's 360 checks).
+Cycles are per wave at the saturated rates (cycles per wave-instruction per SIMD).
+"""
+import argparse
+import heapq
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from node_census import tally  # noqa: E402
+from valu_census import B, RATES, short  # noqa: E402
+
+
+def disassemble(obj):
+    """as node_census.disassemble, with branch targets as labels"""
+    with tempfile.TemporaryDirectory() as td:
+        fb, elf = os.path.join(td, "k.fatbin"), os.path.join(td, "k.elf")
+        subprocess.check_call([B + "llvm-objcopy", "-O", "binary", "--only-section=.hip_fatbin", obj, fb])
+        subprocess.check_call([B + "clang-offload-bundler", "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
+                               "--input=" + fb, "--output=" + elf])
+        return subprocess.run([B + "llvm-objdump", "-d", "--symbolize-operands", elf], capture_output=True, text=True, check=True).stdout
+
+
+def blocks_of(dis, want):
+    """basic blocks of kernel `want`: list of [ops], label -> block index"""
+    ops, labels, name = [], {}, None
+    for line in dis.split("\n"):
+        m = re.match(r"^[0-9a-f]+ <(\S+)>:", line)
+        if m:
+            if m.group(1).startswith("_Z"):
+                name = short(m.group(1))
+            elif name == want:
+                labels[m.group(1)] = len(ops)
+            continue
+        if name != want:
+            continue
+        m = re.match(r"^\s+([a-z_0-9]+)\s*(.*?)\s*(//.*)?$", line)
+        if m:
+            ops.append((m.group(1), m.group(2)))
+    starts = set(labels.values()) | {0}
+    for i, (o, _) in enumerate(ops):
+        if "branch" in o or o == "s_endpgm":
+            starts.add(i + 1)
+    order = sorted(s for s in starts if s < len(ops))
+    blk = [ops[a:b] for a, b in zip(order, order[1:] + [len(ops)])]
+    at = {s: k for k, s in enumerate(order)}
+    succ = []
+    for k, b in enumerate(blk):
+        o, a = b[-1]
+        s = []
+        if "branch" in o:
+            s.append(at[labels[a.split()[-1]]])
+        if o not in ("s_branch", "s_endpgm") and k + 1 < len(blk):
+            s.append(k + 1)
+        succ.append(s)
+    names = {at[v]: k for k, v in labels.items()}
+    return blk, succ, names
+
+
+def find_node(blk, deg):
+    for k, b in enumerate(blk):
+        for i, (o, a) in enumerate(b):
+            if o == "s_setprio" and a.startswith("0"):
+                rest = b[i:]
+                if any(x == "s_setprio" and y.startswith("3") for x, y in rest) and any(x.startswith("v_pk_") for x, _ in rest) \
+                        and sum(1 for x, _ in rest if x == "ds_read_u8") == deg and not any(x == "s_barrier" for x, _ in rest):
+                    return k, i
+    return None, None
+
+
+def cheapest_cycle(blk, succ, k0):
+    """cheapest cycle (instructions) through block k0 that loads messages, stores messages and meets no barrier"""
+    bar = [any(o == "s_barrier" for o, _ in b) for b in blk]
+    ld = [any(o.startswith("buffer_load") for o, _ in b) for b in blk]
+    st = [any(o.startswith("buffer_store") for o, _ in b) for b in blk]
+    f0 = (ld[k0], st[k0])
+    dist, prev, heap = {}, {}, [(0, s, f0, (k0, f0)) for s in succ[k0]]
+    goal = None
+    while heap:
+        d, k, f, p = heapq.heappop(heap)
+        if (k, f) in dist or (bar[k] and k != k0):
+            continue
+        dist[(k, f)], prev[(k, f)] = d, p
+        if k == k0:
+            if f == (True, True):
+                goal = (k, f)
+                break
+            continue
+        g = (f[0] or ld[k], f[1] or st[k])
+        for s in succ[k]:
+            heapq.heappush(heap, (d + len(blk[k]), s, g, (k, f)))
+    if goal is None:
+        return None
+    path, n = [], prev[goal]
+    while n != (k0, f0):
+        path.append(n[0])
+        n = prev[n]
+    return path[::-1]
+
+
+def row(name, c):
+    return (f"{name:22s} {c['valu']:5d} {c['full']:5d} {c['half']:5d} {c['quarter']:5d} {c['lds']:4d} {c['salu']:5d} {c['cycles']:8.1f}")
+
+
+def span_tally(ops):
+    c = tally(ops)
+    c["vmem"] = sum(1 for o, _ in ops if o.startswith("buffer_"))
+    return c
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--obj", default=os.path.join(ROOT, "gr-dvbs2rx_amd", "build", "ldpc_inst_8.o"))
+    ap.add_argument("--kernel", default="ldpc_layered_kernel<8, packed, solo>")
+    ap.add_argument("--deg", type=int, default=7)
+    a = ap.parse_args()
+    blk, succ, names = blocks_of(disassemble(a.obj), a.kernel)
+    if not blk:
+        sys.exit(f"{a.kernel} not found in {a.obj}")
+    print(f"{a.kernel}  ({os.path.relpath(a.obj, ROOT)}; rates {RATES})")
+    print(f"{'part':22s} {'valu':>5} {'full':>5} {'half':>5} {'quart':>5} {'lds':>4} {'salu':>5} {'cycles':>8}")
+    # (a)
+    k0, i0 = find_node(blk, a.deg)
+    if k0 is None:
+        sys.exit(f"no packed regular node of degree {a.deg}")
+    path = cheapest_cycle(blk, succ, k0)
+    if path is None:
+        sys.exit("no cycle through the node")
+    node = span_tally(blk[k0][i0:])
+    rest_ops = blk[k0][:i0] + [op for k in path for op in blk[k]]
+    rest = span_tally(rest_ops)
+    print(f"(a) regular layer trip, degree {a.deg}; blocks " + " ".join(names.get(k, f"+{k}") for k in [k0] + path))
+    print(row("  node + packing", node))
+    print(row("  else", rest))
+    print("      else VALU: " + " ".join(o for o, _ in rest_ops if o.startswith("v_")))
+    print(f"      else: {rest['vmem']} buffer instructions, {sum(1 for o, _ in rest_ops if o == 's_waitcnt')} s_waitcnt")
+    # (b) the chain node: two barriers with a float walk (v_med3_f32) between them, DEG - 2 + 3 LLR byte reads in front
+    flat = [op for b in blk for op in b]
+    bars = [i for i, (o, _) in enumerate(flat) if o == "s_barrier"]
+    done = False
+    for b0, b1 in zip(bars, bars[1:]):
+        if not any(o == "v_med3_f32" for o, _ in flat[b0:b1]):
+            continue
+        # the node's own s_setprio 0 is the last one in front of its first barrier
+        cand = [i for i in range(b0) if flat[i][0] == "s_setprio" and flat[i][1].startswith("0")]
+        if not cand:
+            continue
+        p = max(cand)
+        if sum(1 for o, _ in flat[p:b0] if o == "ds_read_u8") != a.deg + 1:
+            continue
+        e = next(i for i in range(b1, len(flat)) if flat[i][0] == "s_setprio" and flat[i][1].startswith("3"))
+        while "branch" not in flat[e][0] and flat[e][0] != "s_waitcnt":
+            e += 1
+        print(f"(b) hazard layer, single-pair lane chain, degree {a.deg} (text in address order)")
+        print(row("  P1", span_tally(flat[p:b0])))
+        print(row("  walk", span_tally(flat[b0 + 1:b1])))
+        print(row("  P3", span_tally(flat[b1 + 1:e])))
+        done = True
+        break
+    if not done:
+        print(f"(b) no single-pair lane-chain node of degree {a.deg} in this kernel")
+    # (c) the pre-test loop: one block that branches back to itself, with four LLR byte reads
+    for k, b in enumerate(blk):
+        if k in succ[k] and sum(1 for o, _ in b if o == "ds_read_u8") == 4 and not any(o.startswith("v_pk_") for o, _ in b):
+            print("(c) syndrome pre-test trip (four edges)")
+            print(row("  trip", span_tally(b)))
+            break
+    else:
+        print("(c) pre-test loop not found as a single block")
+
+
+if __name__ == "__main__":
+    main()

@@ -4,8 +4,8 @@
 STATIC census of the VALU instructions of every sweep-kernel build (the device code objects inside gr-dvbs2rx_amd/build/ldpc_inst_*.o,
 `llvm-objdump -d`), by the issue-rate classes measured on the MI355X with tools/ubench/valu_rate.hip (notes/r04_experiments.md, "VALU rates,
 second look"; cycles per wave-instruction per SIMD, eight waves per SIMD, at the clock of that run):
-    full     2.65  add / sub / and / or / xor / not / mov / v_lshrrev / v_ashrrev / v_bitop3 / v_add3 / saturating subtract / fp32 add, mul, fma / v_min_u16
-    half     4.3   every 32-bit and fp32 min / max / med3 / min3 / max3, v_sad_*, v_bfe, v_perm, v_lshlrev, conversions, SDWA forms, v_pk_*, compares, v_cndmask
+    full     2.65  add / sub / and / or / xor / not / mov / v_lshrrev / v_ashrrev / v_bitop3 / saturating subtract / fp32 add, mul, fma / v_min_u16
+    half     4.3   every 32-bit and fp32 min / max / med3 / min3 / max3, v_sad_*, v_bfe, v_perm, v_lshlrev, v_add3_u32 (tools/ubench/node_rates.hip, notes/r07_packed_node.md), conversions, SDWA forms, v_pk_*, compares, v_cndmask
     quarter  8.2   v_med3_i16, v_min3_i16, v_add_i16 clamp
 bench.py turns the SQ pass's instruction count into ISSUE CYCLES with this mix (roofline.limiter) instead of the flat "4 cycles per
 instruction" of round 5. The mix is the whole kernel's text, not the executed path's: layer 0, the syndrome test and rarely taken branches
@@ -27,8 +27,8 @@ from bench import csrc_sha256  # noqa: E402
 B = "/opt/rocm/lib/llvm/bin/"
 RATES = {"full": 2.65, "half": 4.3, "quarter": 8.2}
 QUARTER = re.compile(r"^v_(med3_i16|min3_i16|max3_i16|med3_u16|min3_u16|max3_u16)")
-HALF = re.compile(r"^v_(min|max|med3|min3|max3|sad|msad|bfe|perm|lshlrev|cvt|pk_|dot|cmp|cmpx|cndmask|alignbit|alignbyte|mul_|mad_|bfi|ffb|bcnt|mbcnt|lshl_add|lshl_or|add_lshl|readlane|writelane|readfirstlane)")
-FULL = re.compile(r"^v_(add|sub|subrev|and|or|xor|not|mov|lshrrev|ashrrev|bitop3|add3|or3|xor3|and_or|fma_f32|mul_f32|fmac|nop|accvgpr|swap)")
+HALF = re.compile(r"^v_(min|max|med3|min3|max3|sad|msad|bfe|perm|lshlrev|cvt|pk_|dot|cmp|cmpx|cndmask|alignbit|alignbyte|mul_|mad_|bfi|ffb|bcnt|mbcnt|lshl_add|lshl_or|add_lshl|readlane|writelane|readfirstlane|add3)")
+FULL = re.compile(r"^v_(add|sub|subrev|and|or|xor|not|mov|lshrrev|ashrrev|bitop3|or3|xor3|and_or|fma_f32|mul_f32|fmac|nop|accvgpr|swap)")
 
 
 def classify(op):
