@@ -20,6 +20,7 @@
 #include "plsync_hip.h"
 #include "plcoarse_hip.h"
 #include "rotator_hip.h"
+#include "symsync_hip.h"
 #include "bbdeheader_hip.h"
 #include "device_guard.h"
 #include "demap_math.hpp"
@@ -1796,6 +1797,186 @@ int dvbs2_rotator_rotate(dvbs2_rotator_t* h, const float* in, int n_syms, float*
     if (h->rot->rotate_device(h->d_buf, n_syms, h->d_buf, h->stream)) return fail(DVBS2_EDEVICE, h->rot->error());
     HCHK(hipMemcpyAsync(out, h->d_buf, bytes, hipMemcpyDeviceToHost, h->stream));
     HCHK(hipStreamSynchronize(h->stream));
+    return DVBS2_OK;
+    API_CATCH
+}
+
+} // extern "C"
+
+/* ------------------------------------------------------------------ symbol timing recovery */
+struct dvbs2_symsync {
+    SymSyncHip* ss = nullptr;
+    float* d_in = nullptr; float* d_out = nullptr; int64_t* d_idx = nullptr; double* d_mu = nullptr; // staging of the host entry
+    size_t in_cap = 0, out_cap = 0;
+    hipStream_t stream = nullptr;
+    int device = 0;
+};
+
+static int symsync_make(dvbs2_symsync_t** h, int sps, float loop_bw, float damping, float rolloff, int rrc_delay, int n_subfilt, int interp_method,
+                        const float* bank, int max_streams, int max_samples, int device)
+{
+    if (!h) return fail(DVBS2_EINVAL, "null handle pointer");
+    *h = nullptr;
+    // arguments first: a bad argument is the caller's mistake on any machine
+    const std::string bad = SymSyncHip::check_args(sps, loop_bw, damping, rolloff, rrc_delay, n_subfilt, interp_method, max_streams, max_samples);
+    if (!bad.empty()) return fail(DVBS2_EINVAL, bad);
+    return make_handle(h, device, false, [&](dvbs2_symsync* o) {
+        return o->ss = new (std::nothrow) SymSyncHip(sps, loop_bw, damping, rolloff, rrc_delay, n_subfilt, interp_method, bank, max_streams, max_samples, device);
+    });
+}
+
+extern "C" {
+
+int dvbs2_symsync_loop_constants(int sps, float loop_bw, float damping, float rolloff, float* Kp, float* K1, float* K2)
+{
+    if (sps < 2 || (sps & 1)) return fail(DVBS2_EINVAL, "sps has to be an even integer >= 2");
+    symsync_loop_constants(sps, loop_bw, damping, rolloff, Kp, K1, K2);
+    return DVBS2_OK;
+}
+
+int dvbs2_symsync_geometry(int sps, int rrc_delay, int n_subfilt, int interp_method, int* subfilt_len, int* subfilt_delay, int* history)
+{
+    if (symsync_geometry(sps, rrc_delay, n_subfilt, interp_method, subfilt_len, subfilt_delay, history)) return fail(DVBS2_EINVAL, "bad argument");
+    return DVBS2_OK;
+}
+
+int dvbs2_symsync_taps(int sps, float rolloff, int rrc_delay, int n_subfilt, float* bank)
+{
+    API_TRY
+    if (symsync_taps(sps, rolloff, rrc_delay, n_subfilt, bank)) return fail(DVBS2_EINVAL, "bad argument");
+    return DVBS2_OK;
+    API_CATCH
+}
+
+int dvbs2_symsync_create(dvbs2_symsync_t** h, int sps, float loop_bw, float damping, float rolloff, int rrc_delay, int n_subfilt, int interp_method,
+                         int max_streams, int max_samples, int device)
+{
+    API_TRY
+    return symsync_make(h, sps, loop_bw, damping, rolloff, rrc_delay, n_subfilt, interp_method, nullptr, max_streams, max_samples, device);
+    API_CATCH
+}
+
+int dvbs2_symsync_create_taps(dvbs2_symsync_t** h, int sps, float loop_bw, float damping, float rolloff, int rrc_delay, int n_subfilt,
+                              int interp_method, const float* bank, int max_streams, int max_samples, int device)
+{
+    API_TRY
+    if (h) *h = nullptr;
+    if (!bank) return fail(DVBS2_EINVAL, "null bank");
+    return symsync_make(h, sps, loop_bw, damping, rolloff, rrc_delay, n_subfilt, interp_method, bank, max_streams, max_samples, device);
+    API_CATCH
+}
+
+void dvbs2_symsync_destroy(dvbs2_symsync_t* h)
+{
+    if (!h) return;
+    DeviceGuard guard(h->device);
+    (void)hipFree(h->d_in); (void)hipFree(h->d_out); (void)hipFree(h->d_idx); (void)hipFree(h->d_mu);
+    if (h->stream) (void)hipStreamDestroy(h->stream);
+    delete h->ss;
+    delete h;
+}
+
+int dvbs2_symsync_reset(dvbs2_symsync_t* h)
+{
+    API_TRY
+    if (!h) return fail(DVBS2_EINVAL, "null handle");
+    if (h->ss->reset()) return fail(DVBS2_EDEVICE, h->ss->error());
+    return DVBS2_OK;
+    API_CATCH
+}
+
+int dvbs2_symsync_params(const dvbs2_symsync_t* h, int* subfilt_len, int* subfilt_delay, int* history, float* Kp, float* K1, float* K2)
+{
+    if (!h) return fail(DVBS2_EINVAL, "null handle");
+    const SymSyncGeom& g = h->ss->geom();
+    if (subfilt_len) *subfilt_len = g.subfilt_len;
+    if (subfilt_delay) *subfilt_delay = g.subfilt_delay;
+    if (history) *history = g.history;
+    if (Kp) *Kp = h->ss->Kp();
+    if (K1) *K1 = g.K1;
+    if (K2) *K2 = g.K2;
+    return DVBS2_OK;
+}
+
+int dvbs2_symsync_work_device(dvbs2_symsync_t* h, const float* d_in, int64_t in_stride, const int* n_in, int n_streams, float* d_out,
+                              int64_t out_stride, int max_out, int64_t* d_strobe_idx, double* d_mu, void* stream)
+{
+    API_TRY
+    if (!h) return fail(DVBS2_EINVAL, "null handle");
+    if (n_streams < 1 || !n_in || !d_in || max_out < 0 || (max_out && !d_out)) return fail(DVBS2_EINVAL, "bad argument");
+    if (n_streams > h->ss->max_streams()) return fail(DVBS2_ESIZE, "n_streams exceeds max_streams");
+    if (((uintptr_t)d_in | (uintptr_t)d_out | (uintptr_t)d_strobe_idx | (uintptr_t)d_mu) & 7) return fail(DVBS2_EINVAL, "buffers must be 8-byte aligned");
+    int most = 0;
+    for (int s = 0; s < n_streams; s++) {
+        if (n_in[s] < 0) return fail(DVBS2_EINVAL, "negative sample count");
+        if (n_in[s] > h->ss->max_samples()) return fail(DVBS2_ESIZE, "n_in exceeds max_samples");
+        most = std::max(most, n_in[s]);
+    }
+    if (n_streams > 1 && (in_stride < most || out_stride < max_out)) return fail(DVBS2_EINVAL, "a stride below the length of a stream");
+    if (h->ss->work_device(reinterpret_cast<const float2*>(d_in), in_stride, n_in, n_streams, reinterpret_cast<float2*>(d_out), out_stride, max_out,
+                           d_strobe_idx, d_mu, (hipStream_t)stream)) return fail(DVBS2_EDEVICE, h->ss->error());
+    return DVBS2_OK;
+    API_CATCH
+}
+
+int dvbs2_symsync_finish(dvbs2_symsync_t* h, int* n_out, int* consumed, int* status)
+{
+    API_TRY
+    if (!h) return fail(DVBS2_EINVAL, "null handle");
+    if (h->ss->finish(n_out, consumed, status) < 0) return fail(DVBS2_EDEVICE, h->ss->error());
+    return DVBS2_OK;
+    API_CATCH
+}
+
+int dvbs2_symsync_state(dvbs2_symsync_t* h, int stream_index, dvbs2_symsync_state_t* out)
+{
+    API_TRY
+    if (!h || !out) return fail(DVBS2_EINVAL, "bad argument");
+    if (stream_index < 0 || stream_index >= h->ss->max_streams()) return fail(DVBS2_EINVAL, "stream index out of range");
+    SymSyncState s;
+    if (h->ss->state(stream_index, &s)) return fail(DVBS2_EDEVICE, h->ss->error());
+    out->vi = s.vi; out->cnt = s.cnt; out->mu = s.mu; out->n_read = s.n_read; out->last_xi_re = s.last_xi.x; out->last_xi_im = s.last_xi.y;
+    out->jump = s.jump; out->init = s.init; out->status = s.status; out->reserved = 0;
+    return DVBS2_OK;
+    API_CATCH
+}
+
+// host entry, stream 0 of the handle: stage, run, copy back what the caller asked for
+int dvbs2_symsync_work(dvbs2_symsync_t* h, const float* in, int n_in, float* out, int max_out, int64_t* strobe_idx, double* mu, int* n_out,
+                       int* consumed, int* status)
+{
+    API_TRY
+    if (!h) return fail(DVBS2_EINVAL, "null handle");
+    if (n_in < 0 || max_out < 0 || (n_in && !in) || (max_out && !out)) return fail(DVBS2_EINVAL, "bad argument");
+    if (n_in > h->ss->max_samples()) return fail(DVBS2_ESIZE, "n_in exceeds max_samples");
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(DVBS2_EDEVICE, "hipSetDevice failed");
+    if (!h->stream) HCHK(hipStreamCreate(&h->stream));
+    const size_t ni = std::max(n_in, 1), no = std::max(max_out, 1);
+    if (h->in_cap < ni) {
+        (void)hipFree(h->d_in); h->d_in = nullptr; h->in_cap = 0;
+        HCHK(hipMalloc(&h->d_in, ni * 8));
+        h->in_cap = ni;
+    }
+    if (h->out_cap < no) {
+        (void)hipFree(h->d_out); (void)hipFree(h->d_idx); (void)hipFree(h->d_mu);
+        h->d_out = nullptr; h->d_idx = nullptr; h->d_mu = nullptr; h->out_cap = 0;
+        HCHK(hipMalloc(&h->d_out, no * 8)); HCHK(hipMalloc(&h->d_idx, no * 8)); HCHK(hipMalloc(&h->d_mu, no * 8));
+        h->out_cap = no;
+    }
+    if (n_in) HCHK(hipMemcpyAsync(h->d_in, in, (size_t)n_in * 8, hipMemcpyHostToDevice, h->stream));
+    if (h->ss->work_device(reinterpret_cast<const float2*>(h->d_in), n_in, &n_in, 1, reinterpret_cast<float2*>(h->d_out), max_out, max_out,
+                           h->d_idx, h->d_mu, h->stream)) return fail(DVBS2_EDEVICE, h->ss->error());
+    int k = 0, c = 0, st = 0;
+    if (h->ss->finish(&k, &c, &st) < 0) return fail(DVBS2_EDEVICE, h->ss->error());
+    if (k) {
+        HCHK(hipMemcpy(out, h->d_out, (size_t)k * 8, hipMemcpyDeviceToHost));
+        if (strobe_idx) HCHK(hipMemcpy(strobe_idx, h->d_idx, (size_t)k * 8, hipMemcpyDeviceToHost));
+        if (mu) HCHK(hipMemcpy(mu, h->d_mu, (size_t)k * 8, hipMemcpyDeviceToHost));
+    }
+    if (n_out) *n_out = k;
+    if (consumed) *consumed = c;
+    if (status) *status = st;
     return DVBS2_OK;
     API_CATCH
 }

@@ -7,6 +7,7 @@
 //   gr::dvbs2rx::xfecframe_demapper_cb  include/gnuradio/dvbs2rx/xfecframe_demapper_cb.h, lib/xfecframe_demapper_cb_impl.cc
 //   gr::dvbs2rx::bbdeheader_bb          include/gnuradio/dvbs2rx/bbdeheader_bb.h,         lib/bbdeheader_bb_impl.cc
 //   gr::dvbs2rx::rotator_cc             include/gnuradio/dvbs2rx/rotator_cc.h,            lib/rotator_cc_impl.cc
+//   gr::dvbs2rx::symbol_sync_cc         include/gnuradio/dvbs2rx/symbol_sync_cc.h,        lib/symbol_sync_cc_impl.cc
 //
 // It deliberately does NOT depend on GNU Radio (absent from the build image): the classes expose the
 // gr::block work-function signature with plain std::vector arguments, so that the reference's *_impl classes can
@@ -350,6 +351,74 @@ public:
 private:
     rotator_cc(double phase_inc, int device) { check(dvbs2_rotator_create(&d_h, phase_inc, device)); }
     dvbs2_rotator_t* d_h = nullptr;
+};
+
+// ---------------------------------------------------------------------------------------------- symbol synchronizer
+// gr::dvbs2rx::symbol_sync_cc (include/gnuradio/dvbs2rx/symbol_sync_cc.h, lib/symbol_sync_cc_impl.cc): a general block. GNU Radio
+// hands general_work the input WITH the block's history in front; this mirror keeps the history in the handle on the device, so
+// input_items[0] points at the first NEW sample and ninput_items[0] counts new samples only. Tag propagation is TPP_DONT in the
+// reference (:265): general_work leaves the strobe indices of the call behind and map_tag_offsets() does the upper_bound placement
+// of :471-487 on them -- call it after every general_work with the offsets of the tags in [nitems_read before the call,
+// nitems_read after it), get the output offsets of the tags that found a strobe, and the rest stay pending for the next call.
+class symbol_sync_cc {
+public:
+    typedef std::shared_ptr<symbol_sync_cc> sptr;
+    static sptr make(float sps, float loop_bw, float damping_factor, float rolloff, int rrc_delay = 5, int n_subfilt = 128, int interp_method = 0,
+                     int max_samples = 1 << 20, int device = 0)
+    {
+        return sptr(new symbol_sync_cc(sps, loop_bw, damping_factor, rolloff, rrc_delay, n_subfilt, interp_method, max_samples, device));
+    }
+    ~symbol_sync_cc() { dvbs2_symsync_destroy(d_h); }
+    int history() const { return d_history; }
+    uint64_t nitems_read() const { return d_n_read; }
+    uint64_t nitems_written() const { return d_n_written; }
+    int last_consumed() const { return d_last_consumed; }
+    size_t pending_tags() const { return d_pending_tags.size(); }
+    void forecast(int noutput_items, gr_vector_int& ninput_items_required) { ninput_items_required[0] = d_sps * noutput_items; } // :276-280, history apart
+    int general_work(int noutput_items, gr_vector_int& ninput_items, gr_vector_const_void_star& input_items, gr_vector_void_star& output_items) // :426-495
+    {
+        d_strobe_idx.resize((size_t)std::max(noutput_items, 1));
+        int k = 0, consumed = 0, status = 0;
+        check(dvbs2_symsync_work(d_h, static_cast<const float*>(input_items[0]), ninput_items[0], static_cast<float*>(output_items[0]), noutput_items,
+                                 d_strobe_idx.data(), nullptr, &k, &consumed, &status));
+        if (status) throw std::runtime_error("symbol_sync_cc: the loop stopped (W1 or W2 not positive: the loop bandwidth is too wide)");
+        d_strobe_idx.resize((size_t)k);
+        d_read_before = d_n_read; d_written_before = d_n_written;
+        d_n_read += (uint64_t)consumed; d_n_written += (uint64_t)k; d_last_consumed = consumed;
+        return k;
+    }
+    // :446-488 for the last general_work: tag_offsets are absolute input offsets; returns the absolute output offsets of the tags placed
+    std::vector<uint64_t> map_tag_offsets(const std::vector<uint64_t>& tag_offsets)
+    {
+        std::vector<uint64_t> tags(d_pending_tags), placed;
+        tags.insert(tags.end(), tag_offsets.begin(), tag_offsets.end());
+        d_pending_tags.clear();
+        // the strobe indices of the handle are absolute and oblivious to the history, as the tag offsets are: of the reference's
+        // strobe offset (history + subfilt_delay - 1 for polyphase, history otherwise, :471-473) the history term has cancelled
+        const int64_t strobe_offset = d_interp_method == 0 ? d_subfilt_delay - 1 : 0;
+        for (uint64_t t : tags) {
+            const int64_t target = (int64_t)t + strobe_offset;
+            const auto it = std::lower_bound(d_strobe_idx.begin(), d_strobe_idx.end(), target); // the first strobe index past or equal the target
+            if (it != d_strobe_idx.end()) placed.push_back(d_written_before + (uint64_t)(it - d_strobe_idx.begin()));
+            else d_pending_tags.push_back(t);
+        }
+        return placed;
+    }
+
+private:
+    symbol_sync_cc(float sps, float loop_bw, float damping, float rolloff, int rrc_delay, int n_subfilt, int interp_method, int max_samples, int device)
+        : d_sps((int)sps), d_interp_method(interp_method)
+    {
+        if ((std::ceil(sps) != sps) || (std::floor(sps) != sps) || ((int)sps % 2 != 0) || (sps < 2.0f)) throw std::runtime_error("sps has to be an even integer >= 2"); // :229-232
+        if (interp_method < 0 || interp_method > 3) throw std::runtime_error("Invalid interpolation method (choose from 0 to 3)");                         // :258
+        check(dvbs2_symsync_create(&d_h, d_sps, loop_bw, damping, rolloff, rrc_delay, n_subfilt, interp_method, 1, max_samples, device));
+        check(dvbs2_symsync_params(d_h, nullptr, &d_subfilt_delay, &d_history, nullptr, nullptr, nullptr));
+    }
+    dvbs2_symsync_t* d_h = nullptr;
+    int d_sps, d_interp_method, d_history = 0, d_subfilt_delay = 0, d_last_consumed = 0;
+    uint64_t d_n_read = 0, d_n_written = 0, d_read_before = 0, d_written_before = 0;
+    std::vector<int64_t> d_strobe_idx;     // absolute basepoint indices of the last general_work
+    std::vector<uint64_t> d_pending_tags;  // tags without a strobe yet
 };
 
 } // namespace dvbs2rx_hip

@@ -16,7 +16,8 @@ from .capi import lib, check
 __all__ = ["get_fec_info", "rate_id", "LdpcDecoder", "BchDecoder", "Demapper", "FecChain", "BbDeheader", "ldpc_table_info", "ldpc_layer_info",
            "ldpc_table_names", "bb_descramble_sequence", "PlPayload",
            "pl_scrambling_rn", "HostBuffer", "PlFrontEnd", "plheader_symbols", "pls_parse",
-           "PlSync", "plsync_taps", "plsync_thresholds", "PlCoarse", "plcoarse_weights", "Rotator"]
+           "PlSync", "plsync_taps", "plsync_thresholds", "PlCoarse", "plcoarse_weights", "Rotator",
+           "SymbolSync", "symsync_loop_constants", "symsync_geometry", "symsync_taps"]
 
 DEFAULT_TRIALS = 25  # reference lib/ldpc_decoder_bb_impl.cc:391
 
@@ -670,6 +671,110 @@ class Rotator:
     def work_device(self, d_in, n_syms, d_out, stream=0):
         """DEVICE addresses (8-byte aligned), asynchronous on `stream`; d_out == d_in rotates in place."""
         check(lib.dvbs2_rotator_rotate_device(self._h, d_in, int(n_syms), d_out, stream or None))
+
+
+def symsync_loop_constants(sps, loop_bw, damping, rolloff):
+    """(Kp, K1, K2) of the timing loop (reference lib/symbol_sync_cc_impl.cc:156-199) as float32. Host only."""
+    v = [C.c_float() for _ in range(3)]
+    check(lib.dvbs2_symsync_loop_constants(int(sps), float(loop_bw), float(damping), float(rolloff), *[C.byref(x) for x in v]))
+    return tuple(np.float32(x.value) for x in v)
+
+
+def symsync_geometry(sps, rrc_delay, n_subfilt, interp_method):
+    """(subfilt_len, subfilt_delay, history) (reference lib/symbol_sync_cc_impl.cc:68-80, :244-256). Host only."""
+    v = [C.c_int() for _ in range(3)]
+    check(lib.dvbs2_symsync_geometry(int(sps), int(rrc_delay), int(n_subfilt), int(interp_method), *[C.byref(x) for x in v]))
+    return tuple(x.value for x in v)
+
+
+def symsync_taps(sps, rolloff, rrc_delay, n_subfilt):
+    """The polyphase RRC bank as float32 [n_subfilt, subfilt_len], each subfilter flipped (reference
+    lib/symbol_sync_cc_impl.cc:82-110); the prototype is this library's own closed-form design. Host only."""
+    L = symsync_geometry(sps, rrc_delay, n_subfilt, 0)[0]
+    bank = np.empty((n_subfilt, L), np.float32)
+    check(lib.dvbs2_symsync_taps(int(sps), float(rolloff), int(rrc_delay), int(n_subfilt), bank.ctypes.data))
+    return bank
+
+
+class SymbolSync:
+    """Symbol timing recovery (reference lib/symbol_sync_cc_impl.cc): Gardner detector, PI loop, modulo-1 counter and one of four
+    interpolators (0 polyphase RRC bank = the matched filter, 1 linear, 2 quadratic, 3 cubic), on samples at `sps` per symbol.
+    A call takes a batch of independent streams; the handle keeps each stream's loop state and history on the device between
+    calls. Present a stream again from `consumed`, as with GNU Radio's consume()."""
+
+    POLYPHASE, LINEAR, QUADRATIC, CUBIC = 0, 1, 2, 3
+
+    def __init__(self, sps=2, loop_bw=0.01, damping=1.0, rolloff=0.2, rrc_delay=5, n_subfilt=128, interp_method=0, max_streams=1,
+                 max_samples=1 << 20, device=0, taps=None):
+        """taps: a float32 [n_subfilt, subfilt_len] bank to use instead of the library's design (symsync_taps' layout)."""
+        self._h = C.c_void_p()
+        args = (int(sps), float(loop_bw), float(damping), float(rolloff), int(rrc_delay), int(n_subfilt), int(interp_method))
+        if taps is None:
+            check(lib.dvbs2_symsync_create(C.byref(self._h), *args, int(max_streams), int(max_samples), device))
+        else:
+            t = np.ascontiguousarray(taps, np.float32)
+            if t.shape != (n_subfilt, 2 * sps * rrc_delay + 1):
+                raise ValueError(f"taps: [n_subfilt, subfilt_len] = {(n_subfilt, 2 * sps * rrc_delay + 1)}, got {t.shape}")
+            check(lib.dvbs2_symsync_create_taps(C.byref(self._h), *args, t.ctypes.data, int(max_streams), int(max_samples), device))
+        self.sps, self.interp_method, self.max_streams, self.max_samples = sps, interp_method, max_streams, max_samples
+        v, f = [C.c_int() for _ in range(3)], [C.c_float() for _ in range(3)]
+        check(lib.dvbs2_symsync_params(self._h, *[C.byref(x) for x in v], *[C.byref(x) for x in f]))
+        self.subfilt_len, self.subfilt_delay, self.history = (x.value for x in v)
+        self.Kp, self.K1, self.K2 = (np.float32(x.value) for x in f)
+        self._n = 0
+
+    def close(self):
+        if self._h:
+            lib.dvbs2_symsync_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        check(lib.dvbs2_symsync_reset(self._h))
+
+    def work_device(self, d_in, in_stride, n_in, d_out, out_stride, max_out, d_strobe_idx=0, d_mu=0, stream=0):
+        """DEVICE addresses, asynchronous on `stream`; n_in: one sample count per stream (host). Stream s reads complex64 samples
+        from d_in + 8 * s * in_stride and writes at most max_out symbols at d_out + 8 * s * out_stride (and int64 strobe indices /
+        float64 mu at the same element stride). Read the result with finish()."""
+        n = np.ascontiguousarray(np.atleast_1d(n_in), np.int32)
+        self._n = n.size
+        check(lib.dvbs2_symsync_work_device(self._h, d_in, int(in_stride), n.ctypes.data, int(n.size), d_out or None, int(out_stride), int(max_out),
+                                            d_strobe_idx or None, d_mu or None, stream or None))
+
+    def finish(self):
+        """Waits for the last work_device(); returns (n_out, consumed, status), one int32 array each, per stream."""
+        v = [np.zeros(max(self._n, 1), np.int32) for _ in range(3)]
+        check(lib.dvbs2_symsync_finish(self._h, *[x.ctypes.data for x in v]))
+        return tuple(x[:self._n] for x in v)
+
+    def state(self, stream_index=0):
+        """dict(vi, cnt, mu, n_read, last_xi, jump, init, status) of one stream; waits for the device."""
+        s = capi.SymSyncState()
+        check(lib.dvbs2_symsync_state(self._h, int(stream_index), C.byref(s)))
+        return dict(vi=s.vi, cnt=s.cnt, mu=s.mu, n_read=s.n_read, last_xi=np.complex64(complex(s.last_xi_re, s.last_xi_im)), jump=s.jump,
+                    init=s.init, status=s.status)
+
+    def work(self, samples, max_out=None):
+        """HOST buffer of complex64 samples of stream 0. Returns (symbols, strobe_idx int64, mu float64, consumed, status)."""
+        x = np.asarray(samples)
+        if x.dtype != np.complex64:
+            raise TypeError(f"samples must be complex64, not {x.dtype}")
+        if x.ndim != 1 or not x.flags.c_contiguous:
+            raise ValueError("samples must be a C-contiguous vector")
+        if x.size > self.max_samples:
+            raise ValueError(f"{x.size} samples exceed max_samples = {self.max_samples}")
+        cap = x.size if max_out is None else int(max_out)
+        out, idx, mu = np.zeros(cap, np.complex64), np.zeros(cap, np.int64), np.zeros(cap, np.float64)
+        v = [C.c_int() for _ in range(3)]
+        check(lib.dvbs2_symsync_work(self._h, x.ctypes.data if x.size else None, int(x.size), out.ctypes.data if cap else None, cap,
+                                     idx.ctypes.data, mu.ctypes.data, *[C.byref(q) for q in v]))
+        k = v[0].value
+        return out[:k].copy(), idx[:k].copy(), mu[:k].copy(), v[1].value, v[2].value
 
 
 def pl_scrambling_rn(gold_code, n):

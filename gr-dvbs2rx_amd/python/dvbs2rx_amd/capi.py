@@ -48,6 +48,12 @@ class PlSyncFrame(C.Structure):
     _fields_ = [("sof_index", C.c_int64), ("metric", C.c_float), ("plsc", C.c_uint8), ("flags", C.c_uint8), ("reserved", C.c_uint8 * 2)]
 
 
+class SymSyncState(C.Structure):
+    """dvbs2_symsync_state_t"""
+    _fields_ = [("vi", C.c_double), ("cnt", C.c_double), ("mu", C.c_double), ("n_read", C.c_int64), ("last_xi_re", C.c_float),
+                ("last_xi_im", C.c_float), ("jump", C.c_int32), ("init", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
 PLSYNC_FRAME_DTYPE = [("sof_index", "<i8"), ("metric", "<f4"), ("plsc", "u1"), ("flags", "u1"), ("reserved", "u1", (2,))]
 PLSYNC_SEARCHING, PLSYNC_FOUND, PLSYNC_LOCKED = 0, 1, 2
 PLSYNC_REAL_PEAK, PLSYNC_FLAG_LOCKED = 1, 2
@@ -55,6 +61,7 @@ PLSYNC_REAL_PEAK, PLSYNC_FLAG_LOCKED = 1, 2
 
 # every symbol include/dvbs2_fec_hip.h declares: name -> (restype, argtypes)
 _vp, _i, _ip = C.c_void_p, C.c_int, C.POINTER(C.c_int)
+_f, _fp = C.c_float, C.POINTER(C.c_float)
 SYMBOLS = {
     "dvbs2_last_error": (C.c_char_p, []),
     "dvbs2_device_count": (_i, []),
@@ -147,6 +154,18 @@ SYMBOLS = {
     "dvbs2_rotator_rotate_device": (_i, [_vp, _vp, _i, _vp, _vp]),
     "dvbs2_rotator_rotate": (_i, [_vp, _vp, _i, _vp]),
     "dvbs2_rotator_measure": (_i, [_i, _i, _i, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "dvbs2_symsync_loop_constants": (_i, [_i, _f, _f, _f, _fp, _fp, _fp]),
+    "dvbs2_symsync_geometry": (_i, [_i, _i, _i, _i, _ip, _ip, _ip]),
+    "dvbs2_symsync_taps": (_i, [_i, _f, _i, _i, _vp]),
+    "dvbs2_symsync_create": (_i, [C.POINTER(_vp), _i, _f, _f, _f, _i, _i, _i, _i, _i, _i]),
+    "dvbs2_symsync_create_taps": (_i, [C.POINTER(_vp), _i, _f, _f, _f, _i, _i, _i, _vp, _i, _i, _i]),
+    "dvbs2_symsync_destroy": (None, [_vp]),
+    "dvbs2_symsync_reset": (_i, [_vp]),
+    "dvbs2_symsync_params": (_i, [_vp, _ip, _ip, _ip, _fp, _fp, _fp]),
+    "dvbs2_symsync_work_device": (_i, [_vp, _vp, C.c_int64, _vp, _i, _vp, C.c_int64, _i, _vp, _vp, _vp]),
+    "dvbs2_symsync_finish": (_i, [_vp, _vp, _vp, _vp]),
+    "dvbs2_symsync_state": (_i, [_vp, _i, C.POINTER(SymSyncState)]),
+    "dvbs2_symsync_work": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _ip, _ip, _ip]),
     "dvbs2_bbdeheader_create": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i]),
     "dvbs2_bbdeheader_create_raw": (_i, [C.POINTER(_vp), _i, _i, _i]),
     "dvbs2_bbdeheader_destroy": (None, [_vp]),

@@ -544,6 +544,68 @@ int dvbs2_rotator_rotate(dvbs2_rotator_t* h, const float* in, int n_syms, float*
  * run, of a plain 16-byte-per-lane copy kernel over the same bytes on the same grid; it allocates 2 * 8 * n_syms bytes for the run */
 int dvbs2_rotator_measure(int device, int n_syms, int regions, double* rotate_ms, double* copy_ms);
 
+/* ---- symbol timing recovery: symbol_sync_cc_impl::loop (reference lib/symbol_sync_cc_impl.cc:283-401) with its four interpolators
+ * (:23-66, :122-132: polyphase RRC bank = the matched filter, linear, quadratic and cubic Farrow), its loop constants (:156-199), its
+ * state kept across calls and the strobe indices general_work uses to move tags (:446-488). In the reference flowgraph it follows the
+ * rotator and feeds plsync_cc (apps/dvbs2-rx:873-926); it takes samples at `sps` per symbol and gives symbols.
+ * A call takes a BATCH of independent streams, one wavefront each (the loop is a feedback loop and cannot be cut across time): stream
+ * s reads n_in[s] samples at d_in + 2 * s * in_stride floats and writes at most max_out symbols at d_out + 2 * s * out_stride floats,
+ * with -- each nullable -- d_strobe_idx[s * out_stride + k] = the basepoint m_k of symbol k as an ABSOLUTE sample index of the stream
+ * since create / reset, and d_mu[s * out_stride + k] = the mu used for symbol k. n_in is a HOST array. in_stride >= max n_in and
+ * out_stride >= max_out when n_streams > 1. dvbs2_symsync_finish waits for the last call and returns per stream n_out, consumed and
+ * status (each array nullable, n_streams entries). A handle has ONE set of per-call buffers (sample counts, results) besides the
+ * per-stream state: calls on the same HIP stream may follow each other without a finish (finish then reports the last), a call on
+ * another HIP stream needs dvbs2_symsync_finish first.
+ * Semantics, the reference's: the history (dvbs2_symsync_geometry) starts as zeros; on a stream's first call last_xi is its first
+ * sample and the loop starts at n = history + 1; the loop runs while n + jump < history + n_in and k < max_out; consumed =
+ * n + 1 - history. The handle keeps, per stream and on the device, the `history` samples before the first unconsumed one and vi, cnt,
+ * mu (double), jump, init, last_xi: present the stream again from `consumed`, as the GNU Radio scheduler would, and any cut of a
+ * stream into calls gives the bits of one call. dvbs2_symsync_reset gives every stream as created.
+ * Defined where the reference only asserts: floor(n_subfilt * mu) is clamped to 0..n_subfilt-1. A stream stops at the strobe where W1
+ * or W2 is not positive (status 1) or NaN (status 2), or where the next jump is not in 1..2^30 (status 3): that strobe's symbol is
+ * written and counted, n_out and consumed are reported, and later calls return at once (n_out = consumed = 0, the same status) until
+ * reset; the other streams of the batch are not affected. A stream that has not started consumes nothing from a call with fewer than
+ * 2 samples. Every iteration advances by at least one sample, so a call always ends.
+ * Arithmetic: polyphase dot products in float, lane j of a 32-lane half summing taps j, j + 32, ... in ascending order and the halves
+ * combined by a xor butterfly (16, 8, 4, 2, 1), where the reference calls VOLK; the Farrow interpolants, the Gardner error, K1 e and
+ * K2 e in float in the reference's order of operations without contraction; the PI filter and the modulo-1 counter in IEEE double
+ * with true divisions, as the reference. tests/symsync_model.py restates exactly this and the device is tested bit for bit against it.
+ * Host only, no device needed: dvbs2_symsync_loop_constants (:156-199 with the reference's float / double mix; damping = 0 gives
+ * K1 = K2 = 0, the open loop), dvbs2_symsync_geometry (history = interpolator history 1 / 3 / 3 / subfilt_len - 1 plus sps / 2;
+ * subfilt_len = 2 sps rrc_delay + 1), dvbs2_symsync_taps (n_subfilt * subfilt_len floats, [subfilter][tap]: the prototype zero padded
+ * to a multiple of n_subfilt, subfilter i = taps i + j n_subfilt, each subfilter flipped, :82-110). The prototype is designed from the
+ * closed-form RRC impulse response with its two singular points by their limits and scaled so that the taps sum to n_subfilt
+ * (firdes's convention); firdes::root_raised_cosine belongs to GNU Radio and is not available to compare with, so the bank is UNPINNED
+ * against it. dvbs2_symsync_create_taps takes a caller's bank instead (firdes's own taps, laid out as above).
+ * sps: an even integer 2..64; interp_method 0..3 = polyphase, linear, quadratic, cubic; rrc_delay 1..64; n_subfilt 2..4096. A bank
+ * that does not fit the LDS next to the sample ring (n_subfilt * subfilt_len * 4 > 57344 bytes) or a history above 768 samples is
+ * DVBS2_EINVAL. dvbs2_symsync_work is the host-buffer form for one stream (stream 0 of the handle), synchronous. */
+typedef struct dvbs2_symsync dvbs2_symsync_t;
+typedef struct {
+    double vi, cnt, mu;
+    int64_t n_read; /* samples consumed since create / reset */
+    float last_xi_re, last_xi_im;
+    int32_t jump, init, status, reserved;
+} dvbs2_symsync_state_t;
+int dvbs2_symsync_loop_constants(int sps, float loop_bw, float damping, float rolloff, float* Kp, float* K1, float* K2);
+int dvbs2_symsync_geometry(int sps, int rrc_delay, int n_subfilt, int interp_method, int* subfilt_len, int* subfilt_delay, int* history);
+int dvbs2_symsync_taps(int sps, float rolloff, int rrc_delay, int n_subfilt, float* bank);
+int dvbs2_symsync_create(dvbs2_symsync_t** h, int sps, float loop_bw, float damping, float rolloff, int rrc_delay, int n_subfilt, int interp_method,
+                         int max_streams, int max_samples, int device);
+int dvbs2_symsync_create_taps(dvbs2_symsync_t** h, int sps, float loop_bw, float damping, float rolloff, int rrc_delay, int n_subfilt,
+                              int interp_method, const float* bank, int max_streams, int max_samples, int device);
+void dvbs2_symsync_destroy(dvbs2_symsync_t* h);
+int dvbs2_symsync_reset(dvbs2_symsync_t* h);
+int dvbs2_symsync_params(const dvbs2_symsync_t* h, int* subfilt_len, int* subfilt_delay, int* history, float* Kp, float* K1, float* K2);
+int dvbs2_symsync_work_device(dvbs2_symsync_t* h, const float* d_in, int64_t in_stride, const int* n_in, int n_streams, float* d_out,
+                              int64_t out_stride, int max_out, int64_t* d_strobe_idx, double* d_mu, void* stream);
+int dvbs2_symsync_finish(dvbs2_symsync_t* h, int* n_out, int* consumed, int* status);
+/* waits for the device; the state of one stream after the calls made so far */
+int dvbs2_symsync_state(dvbs2_symsync_t* h, int stream_index, dvbs2_symsync_state_t* out);
+/* host pointers, synchronous */
+int dvbs2_symsync_work(dvbs2_symsync_t* h, const float* in, int n_in, float* out, int max_out, int64_t* strobe_idx, double* mu, int* n_out,
+                       int* consumed, int* status);
+
 /* ---- downstream neighbour: BBFRAME de-header, replaces bbdeheader_bb_impl::general_work (reference
  * lib/bbdeheader_bb_impl.cc:144-264) with parse_bbheader (:77-136) and check_crc8 (:138-142, generator
  * x^8 + x^7 + x^6 + x^4 + x^2 + 1, :55). Input: whole descrambled BBFRAMEs of kbch / 8 bytes (what dvbs2_bch_decode /
