@@ -757,6 +757,14 @@ void dvbs2_demap_destroy(dvbs2_demap_t* h)
     delete h;
 }
 
+int dvbs2_apsk_points(int constellation, int rate, float* re_im)
+{
+    if (!re_im) return fail(DVBS2_EINVAL, "bad argument");
+    if (constellation != DVBS2_MOD_16APSK && constellation != DVBS2_MOD_32APSK) return fail(DVBS2_EINVAL, "Unsupported constellation");
+    if (!apsk_points(constellation, rate, re_im)) return fail(DVBS2_EINVAL, "Unsupported code rate for 16APSK / 32APSK");
+    return DVBS2_OK;
+}
+
 int dvbs2_demap_params(const dvbs2_demap_t* h, int* n_syms, int* n_llr, int* n_mod, int* column_order)
 {
     if (!h) return fail(DVBS2_EINVAL, "null handle");
@@ -989,7 +997,7 @@ int dvbs2_chain_enqueue_device(dvbs2_chain_t* h, const float* d_syms, int n_fram
     if (n_frames < 0 || max_trials <= 0 || (n_frames && !d_msg)) return fail(DVBS2_EINVAL, "bad argument");
     if (n_frames == 0) return DVBS2_OK;
     if (!d_syms || !d_n0 || (n0_count != 1 && n0_count != n_frames)) return fail(DVBS2_EINVAL, "bad argument");
-    if (h->ldpc->dec->fused_demap_supported()) { // symbols -> LDS inside the LDPC sweep kernel: no demapper launch, no LLR buffer
+    if (h->ldpc->dec->fused_demap_supported() && h->dm->dm->fusable()) { // symbols -> LDS inside the LDPC sweep kernel: no demapper launch, no LLR buffer
         const DemapFused dm = h->dm->dm->fused(d_syms, d_n0, n0_count);
         return chain_enqueue_tail(h, nullptr, &dm, n_frames, max_trials, d_msg, d_ldpc_ret, d_bch_corr, stream);
     }
@@ -1083,7 +1091,7 @@ static int chain_decode_host(dvbs2_chain_t* h, const float* in_syms, const int8_
     const int G = dec->group_size();
     const size_t ret_bytes = ((mf + G - 1) / G + kSlots) * 4;
     if (int rc = host_pipe_init(h->pipe)) return rc;
-    const bool fused = in_syms && dec->fused_demap_supported(); // symbols -> LDS inside the sweep kernel; else demapper launch -> LLR buffer
+    const bool fused = in_syms && dec->fused_demap_supported() && h->dm->dm->fusable(); // symbols -> LDS inside the sweep kernel; else demapper launch -> LLR buffer
     if (in_syms && !h->hd_syms) HCHK(hipMalloc(&h->hd_syms, mf * ns * 8));
     if (in_syms && !h->hd_n0) HCHK(hipMalloc(&h->hd_n0, mf * 4));
     if ((in_llr || !fused) && !h->hd_llr) HCHK(hipMalloc(&h->hd_llr, mf * N));

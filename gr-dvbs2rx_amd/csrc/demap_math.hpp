@@ -46,6 +46,43 @@ __device__ __forceinline__ void psk8_llr(float re, float im, float rr, float ri,
     b0 = quant8(dp, __fmul_rn(rcp_sqrt_2, __fsub_rn(fabsf(cr), fabsf(ci))));
 }
 
+// 16APSK / 32APSK (EN 302 307-1 5.4.3 / 5.4.4; no counterpart in the reference, notes/apsk_demap.md): exact max-log over ALL M = 2^NMOD
+// points, L_b = (min_{s: bit b = 1} |y - s|^2 - min_{s: bit b = 0} |y - s|^2) / N0 in natural-log units (QPSK's scale).
+// The table travels as a kernel argument: every index below is a compile-time constant after unrolling, so the points stay in SGPRs.
+struct ApskTable {
+    float re[32], im[32]; // entry i = the point whose label is i; label bit NMOD-1 (the most significant) is the first interleaver column
+};
+typedef float apsk_f2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ float apsk_inv_n0(float N0) { return (float)(1.0 / (double)N0); }
+// Two symbols at once (re = {re_a, re_b}, im likewise): the subtractions, products and the sum are element-wise IEEE operations (no
+// contraction), which the compiler may issue as v_pk_add_f32 / v_pk_mul_f32; the minima are scalar. llr[c] = column c = label bit NMOD-1-c.
+template <int NMOD>
+__device__ __forceinline__ void apsk_llr2(const ApskTable& t, apsk_f2 re, apsk_f2 im, float inv_n0, int8_t (&la)[NMOD], int8_t (&lb)[NMOD])
+{
+#pragma clang fp contract(off)
+    constexpr int M = 1 << NMOD;
+    float m0a[NMOD], m1a[NMOD], m0b[NMOD], m1b[NMOD];
+#pragma unroll
+    for (int i = 0; i < M; i++) {
+        const apsk_f2 dr = re - t.re[i], di = im - t.im[i];
+        const apsk_f2 d = dr * dr + di * di;
+#pragma unroll
+        for (int c = 0; c < NMOD; c++) {
+            const int bit = 1 << (NMOD - 1 - c);
+            if (i == 0) { m0a[c] = d.x; m0b[c] = d.y; }           // the first point with a 0 in column c
+            else if (i == bit) { m1a[c] = d.x; m1b[c] = d.y; }    // the first with a 1
+            else if (i & bit) { m1a[c] = fminf(m1a[c], d.x); m1b[c] = fminf(m1b[c], d.y); }
+            else { m0a[c] = fminf(m0a[c], d.x); m0b[c] = fminf(m0b[c], d.y); }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < NMOD; c++) {
+        la[c] = sat8_rint(__fmul_rn(__fsub_rn(m1a[c], m0a[c]), inv_n0));
+        lb[c] = sat8_rint(__fmul_rn(__fsub_rn(m1b[c], m0b[c]), inv_n0));
+    }
+}
+
 // What a sweep kernel needs to demap while loading (passed by value; mode 0 = LLR input)
 struct DemapFused {
     const float* syms;  // n_frames * n_syms complex symbols (re, im)

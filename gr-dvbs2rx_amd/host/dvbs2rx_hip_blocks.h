@@ -231,6 +231,8 @@ private:
 };
 
 // ---------------------------------------------------------------------------------------------- demapper
+// constellation: MOD_QPSK and MOD_8PSK as in the reference; MOD_16APSK and MOD_32APSK (DVB-S2 rates, normal and short frames) are
+// this library's own -- forecast() and output_multiple() follow n_mod 4 / 5, the refinement re-maps through the natural column order.
 class xfecframe_demapper_cb {
 public:
     typedef std::shared_ptr<xfecframe_demapper_cb> sptr;
@@ -305,7 +307,7 @@ public:
 private:
     xfecframe_demapper_cb(dvb_framesize_t framesize, dvb_code_rate_t rate, dvb_constellation_t constellation, int batch_frames, int device) : d_batch(batch_frames)
     {
-        check(dvbs2_demap_create(&d_h, framesize, rate, constellation, batch_frames, device)); // throws "Unsupported constellation"
+        check(dvbs2_demap_create(&d_h, framesize, rate, constellation, batch_frames, device)); // throws "Unsupported constellation" (or a rate / frame size message for 16APSK / 32APSK)
         int order;
         check(dvbs2_demap_params(d_h, &d_xfecframe_len, &d_fecframe_len, &d_n_mod, &order));
         d_saved.assign(std::max(64, 2 * batch_frames), std::numeric_limits<uint64_t>::max()); // XFECFRAME_POOL_SIZE, .h:28-32

@@ -15,7 +15,7 @@ from .capi import lib, check
 
 __all__ = ["get_fec_info", "rate_id", "LdpcDecoder", "BchDecoder", "Demapper", "FecChain", "BbDeheader", "ldpc_table_info", "ldpc_layer_info",
            "ldpc_table_names", "bb_descramble_sequence", "PlPayload",
-           "pl_scrambling_rn", "HostBuffer", "PlFrontEnd", "plheader_symbols", "pls_parse",
+           "pl_scrambling_rn", "HostBuffer", "PlFrontEnd", "plheader_symbols", "pls_parse", "apsk_points",
            "PlSync", "plsync_taps", "plsync_thresholds", "PlCoarse", "plcoarse_weights", "Rotator",
            "SymbolSync", "symsync_loop_constants", "symsync_geometry", "symsync_taps"]
 
@@ -245,7 +245,8 @@ class BchDecoder:
 
 
 class Demapper:
-    """xfecframe_demapper_cb's compute (reference lib/xfecframe_demapper_cb_impl.cc:101-186)."""
+    """xfecframe_demapper_cb's compute (reference lib/xfecframe_demapper_cb_impl.cc:101-186): QPSK and 8PSK as in the reference,
+    and capi.MOD_16APSK / capi.MOD_32APSK at their DVB-S2 rates (exact max-log, natural column order; notes/apsk_demap.md)."""
 
     def __init__(self, framesize=capi.FECFRAME_NORMAL, rate="C1_2", constellation=capi.MOD_QPSK, max_frames=64, device=0):
         self._h = C.c_void_p()
@@ -333,6 +334,13 @@ class PlPayload:
         check(lib.dvbs2_plpayload_process(self._h, payload.ctypes.data, nf, hph.ctypes.data, inc.ctypes.data, cc.ctypes.data,
                                           pp.ctypes.data, out.ctypes.data))
         return out
+
+
+def apsk_points(constellation, rate):
+    """The 16 (capi.MOD_16APSK) or 32 (capi.MOD_32APSK) points of a DVB-S2 code rate, entry i = label i, Es = 1. Host only."""
+    out = np.empty(16 if constellation == capi.MOD_16APSK else 32, np.complex64)
+    check(lib.dvbs2_apsk_points(int(constellation), rate_id(rate), out.ctypes.data))
+    return out
 
 
 def plheader_symbols(plsc):
@@ -837,7 +845,8 @@ class BbDeheader:
 
 
 class FecChain:
-    """demapper -> LDPC (OM_MESSAGE) -> BCH on the device, as wired in apps/dvbs2-rx:853-863."""
+    """demapper -> LDPC (OM_MESSAGE) -> BCH on the device, as wired in apps/dvbs2-rx:853-863. constellation: capi.MOD_QPSK,
+    MOD_8PSK, MOD_16APSK or MOD_32APSK (the APSK chains run demapper -> LLR buffer -> LDPC, never the fused load)."""
 
     def __init__(self, standard=capi.STANDARD_DVBS2, framesize=capi.FECFRAME_NORMAL, rate="C3_4",
                  constellation=capi.MOD_8PSK, group_size=32, max_frames=64, max_trials=0, device=0, from_llr=False):

@@ -23,7 +23,7 @@ OK, EINVAL, EDEVICE, ESIZE = 0, -1, -2, -3
 STANDARD_DVBS2, STANDARD_DVBT2 = 0, 1
 FECFRAME_SHORT, FECFRAME_NORMAL, FECFRAME_MEDIUM = 0, 1, 2
 OM_CODEWORD, OM_MESSAGE = 0, 1
-MOD_QPSK, MOD_8PSK = 0, 4
+MOD_QPSK, MOD_8PSK, MOD_16APSK, MOD_32APSK = 0, 4, 6, 8
 
 
 class FecInfo(C.Structure):
@@ -102,6 +102,7 @@ SYMBOLS = {
     "dvbs2_demap_create": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i]),
     "dvbs2_demap_destroy": (None, [_vp]),
     "dvbs2_demap_params": (_i, [_vp, _ip, _ip, _ip, _ip]),
+    "dvbs2_apsk_points": (_i, [_i, _i, _vp]),
     "dvbs2_demap_soft": (_i, [_vp, _vp, _i, _vp, _i, _vp]),
     "dvbs2_demap_soft_device": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp]),
     "dvbs2_demap_estimate_snr": (_i, [_vp, _vp, _i, _vp]),

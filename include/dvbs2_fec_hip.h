@@ -40,11 +40,14 @@ extern "C" {
 /* dvb_outputmode_t */
 #define DVBS2_OM_CODEWORD 0
 #define DVBS2_OM_MESSAGE 1
-/* dvb_constellation_t (dvb_config.h:80-101: QPSK 0, 16QAM 1, 64QAM 2, 256QAM 3, 8PSK 4, ...); only the two the
- * reference demapper supports are accepted (lib/xfecframe_demapper_cb_impl.cc:45-72). Pinned against the reference
- * header by tests/test_oracle_kat.py::test_enums_match_reference (tests/golden/dvb_config_enums.json). */
+/* dvb_constellation_t (dvb_config.h:80-101: QPSK 0, 16QAM 1, 64QAM 2, 256QAM 3, 8PSK 4, 8APSK 5, 16APSK 6, 8+8APSK 7,
+ * 32APSK 8, ...). The reference demapper supports the first two below (lib/xfecframe_demapper_cb_impl.cc:45-72); 16APSK
+ * and 32APSK are this library's own (DVB-S2 rates only, see the soft demapper below). Values pinned against the reference
+ * header by tests/test_oracle_kat.py::test_enums_match_reference and tests/test_apsk_model.py (tests/golden/dvb_config_enums.json). */
 #define DVBS2_MOD_QPSK 0
 #define DVBS2_MOD_8PSK 4
+#define DVBS2_MOD_16APSK 6
+#define DVBS2_MOD_32APSK 8
 
 const char* dvbs2_last_error(void);
 int dvbs2_device_count(void);
@@ -202,9 +205,18 @@ int dvbs2_bch_decode_device(dvbs2_bch_t* h, const uint8_t* d_cw, int n_frames, u
 /* ---- soft demapper: replaces QpskConstellation::demap_soft (reference lib/qpsk.h:208-214) and the
  * PhaseShiftKeying<8>::soft loop + column de-interleave (lib/psk.hh:143-150,
  * lib/xfecframe_demapper_cb_impl.cc:152-176) inside xfecframe_demapper_cb_impl::general_work ----
- * constellation: DVBS2_MOD_QPSK or DVBS2_MOD_8PSK; anything else fails with DVBS2_EINVAL
- * ("Unsupported constellation", lib/xfecframe_demapper_cb_impl.cc:70-72). */
+ * constellation: DVBS2_MOD_QPSK or DVBS2_MOD_8PSK as in the reference, and beyond it DVBS2_MOD_16APSK (rates C2_3, C3_4, C4_5,
+ * C5_6, C8_9, C9_10) and DVBS2_MOD_32APSK (C3_4 .. C9_10) on normal and short frames (9/10: normal only), i.e. DVB-S2 MODCODs
+ * 18-28; anything else fails with DVBS2_EINVAL ("Unsupported constellation", lib/xfecframe_demapper_cb_impl.cc:70-72, or a
+ * rate / frame size message). The S2X APSK variants are not covered.
+ * 16APSK / 32APSK: exact max-log LLRs over all points at QPSK's scale, L_b = (min_{bit b = 1} |y - s|^2 - min_{bit b = 0} |y - s|^2) / N0,
+ * llr = sat8(rint(L_b)); the LLR of label bit c (0 = most significant = first interleaver column) of symbol j is byte c * n_syms + j
+ * of the frame (EN 302 307-1 5.3.2 undone; column_order 0). The constellation tables are restated from EN 302 307-1 5.4.3 / 5.4.4
+ * and NOT pinned against another implementation (the reference has none). */
 typedef struct dvbs2_demap dvbs2_demap_t;
+/* the table itself, host only (no device needed): 2 * 2^n_mod floats (re, im), entry i = the point with label i, Es = 1.
+ * DVBS2_EINVAL for another constellation or a rate that DVB-S2 does not combine with it. */
+int dvbs2_apsk_points(int constellation, int rate, float* re_im);
 int dvbs2_demap_create(dvbs2_demap_t** h, int framesize, int rate, int constellation, int max_frames, int device);
 void dvbs2_demap_destroy(dvbs2_demap_t* h);
 /* symbols per frame (d_xfecframe_len), LLRs per frame (d_fecframe_len), bits per symbol, 8PSK column
@@ -244,9 +256,9 @@ int dvbs2_chain_create(dvbs2_chain_t** h, int standard, int framesize, int rate,
 void dvbs2_chain_destroy(dvbs2_chain_t* h);
 /* bytes per frame out (bch k / 8), symbols per frame in */
 int dvbs2_chain_params(const dvbs2_chain_t* h, int* n_syms, int* msg_bytes);
-/* The chain from LLRs (ldpc_decoder_bb -> bch_decoder_bb, apps/dvbs2-rx:857-863): for constellations whose soft demapper
- * is not part of the reference (lib/xfecframe_demapper_cb_impl.cc:70-72 rejects everything but QPSK and 8PSK) the LLRs
- * come from elsewhere; this is BASELINE config "9/10 normal" run from int8 LLRs. */
+/* The chain from LLRs (ldpc_decoder_bb -> bch_decoder_bb, apps/dvbs2-rx:857-863): for constellations without a soft demapper
+ * here (the reference rejects everything but QPSK and 8PSK, lib/xfecframe_demapper_cb_impl.cc:70-72; this library adds 16APSK
+ * and 32APSK) the LLRs come from elsewhere; this is BASELINE config "9/10 normal" run from int8 LLRs. */
 int dvbs2_chain_create_llr(dvbs2_chain_t** h, int standard, int framesize, int rate, int group_size, int max_frames,
                            int device);
 /* LLRs per frame in (N), bytes per frame out (bch k / 8), group size */
