@@ -22,6 +22,35 @@ __all__ = ["get_fec_info", "rate_id", "LdpcDecoder", "BchDecoder", "Demapper", "
 DEFAULT_TRIALS = 25  # reference lib/ldpc_decoder_bb_impl.cc:391
 
 
+def _ints(k, entry, *args):
+    """The k ints that `entry` writes through its last k pointer arguments."""
+    v = [C.c_int() for _ in range(k)]
+    check(entry(*args, *v))
+    return tuple(x.value for x in v)
+
+
+class _Handle:
+    """One C handle: self._h is there (null) before a subclass's constructor runs and creates it; the subclass names the destroy entry.
+    close() may be called again, and runs when the object is dropped."""
+    _destroy = None
+
+    def __new__(cls, *args, **kwargs):
+        self = super().__new__(cls)
+        self._h = C.c_void_p()
+        return self
+
+    def close(self):
+        if self._h:
+            self._destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def rate_id(rate):
     if isinstance(rate, str):
         r = lib.dvbs2_rate_from_name(rate.encode())
@@ -39,9 +68,7 @@ def get_fec_info(standard, framesize, rate):
 
 
 def ldpc_table_info(table):
-    v = [C.c_int() for _ in range(5)]
-    check(lib.dvbs2_ldpc_table_info(table.encode(), *v))
-    return dict(zip(("N", "K", "q", "links_total", "conflict_layers"), (x.value for x in v)))
+    return dict(zip(("N", "K", "q", "links_total", "conflict_layers"), _ints(5, lib.dvbs2_ldpc_table_info, table.encode())))
 
 
 def bb_descramble_sequence(n_bytes):
@@ -101,22 +128,20 @@ def ldpc_layer_info(table, layer):
     return dict(cnt=cnt, block=blk.value, groups=g[:cnt].tolist(), shifts=s[:cnt].tolist())
 
 
-class LdpcDecoder:
+class LdpcDecoder(_Handle):
     """ldpc_decoder_bb's compute: batches of int8 LLR frames -> packed hard bits (+ decoded LLRs)."""
+    _destroy = lib.dvbs2_ldpc_destroy
 
     def __init__(self, standard=capi.STANDARD_DVBS2, framesize=capi.FECFRAME_NORMAL, rate="C1_2",
                  outputmode=capi.OM_MESSAGE, max_trials=0, group_size=32, max_frames=64, device=0,
                  table=None, message_bits=None):
-        self._h = C.c_void_p()
         if table is not None:
             check(lib.dvbs2_ldpc_create_table(C.byref(self._h), table.encode(), int(message_bits),
                                               group_size, max_frames, device))
         else:
             check(lib.dvbs2_ldpc_create(C.byref(self._h), standard, framesize, rate_id(rate),
                                         group_size, max_frames, device))
-        v = [C.c_int() for _ in range(5)]
-        check(lib.dvbs2_ldpc_params(self._h, *v))
-        self.N, self.K, self.message_bits, self.q, self.group_size = (x.value for x in v)
+        self.N, self.K, self.message_bits, self.q, self.group_size = _ints(5, lib.dvbs2_ldpc_params, self._h)
         self.outputmode = outputmode
         self.max_trials = DEFAULT_TRIALS if max_trials == 0 else max_trials
         self.max_frames = max_frames
@@ -124,17 +149,6 @@ class LdpcDecoder:
         self.total_trials = 0
         self.batch_cnt = 0
         self.frame_cnt = 0
-
-    def close(self):
-        if self._h:
-            lib.dvbs2_ldpc_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @property
     def out_bytes(self):
@@ -191,34 +205,21 @@ class LdpcDecoder:
         return lib.dvbs2_ldpc_fallback_rounds(self._h)
 
 
-class BchDecoder:
+class BchDecoder(_Handle):
     """bch_decoder_bb's compute (reference lib/bch_decoder_bb_impl.cc:84-117): n/8-byte codewords -> k/8-byte messages."""
+    _destroy = lib.dvbs2_bch_destroy
 
     def __init__(self, standard=capi.STANDARD_DVBS2, framesize=capi.FECFRAME_NORMAL, rate="C1_2", max_frames=64,
                  device=0, raw=None):
-        self._h = C.c_void_p()
         if raw is not None:
             m, prim, t, n = raw
             check(lib.dvbs2_bch_create_raw(C.byref(self._h), m, prim, t, n, max_frames, device))
         else:
             check(lib.dvbs2_bch_create(C.byref(self._h), standard, framesize, rate_id(rate), max_frames, device))
-        v = [C.c_int() for _ in range(3)]
-        check(lib.dvbs2_bch_params(self._h, *v))
-        self.n, self.k, self.t = (x.value for x in v)
+        self.n, self.k, self.t = _ints(3, lib.dvbs2_bch_params, self._h)
         # counters behind get_frame_count / get_error_count (lib/bch_decoder_bb_impl.h:46-47)
         self.frame_cnt = 0
         self.frame_error_cnt = 0
-
-    def close(self):
-        if self._h:
-            lib.dvbs2_bch_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_descramble(self, enable=True):
         """Fuse bbdescrambler_bb (reference lib/bbdescrambler_bb_impl.cc:67-82) into the output stage."""
@@ -244,27 +245,14 @@ class BchDecoder:
         check(lib.dvbs2_bch_decode_device(self._h, d_cw, n_frames, d_msg, d_corr, stream or None))
 
 
-class Demapper:
+class Demapper(_Handle):
     """xfecframe_demapper_cb's compute (reference lib/xfecframe_demapper_cb_impl.cc:101-186): QPSK and 8PSK as in the reference,
     and capi.MOD_16APSK / capi.MOD_32APSK at their DVB-S2 rates (exact max-log, natural column order; notes/apsk_demap.md)."""
+    _destroy = lib.dvbs2_demap_destroy
 
     def __init__(self, framesize=capi.FECFRAME_NORMAL, rate="C1_2", constellation=capi.MOD_QPSK, max_frames=64, device=0):
-        self._h = C.c_void_p()
         check(lib.dvbs2_demap_create(C.byref(self._h), framesize, rate_id(rate), constellation, max_frames, device))
-        v = [C.c_int() for _ in range(4)]
-        check(lib.dvbs2_demap_params(self._h, *v))
-        self.n_syms, self.n_llr, self.n_mod, self.column_order = (x.value for x in v)
-
-    def close(self):
-        if self._h:
-            lib.dvbs2_demap_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self.n_syms, self.n_llr, self.n_mod, self.column_order = _ints(4, lib.dvbs2_demap_params, self._h)
 
     def work(self, syms, n0):
         """syms: (n_frames, n_syms) complex (converted to complex64); n0: scalar or (n_frames,) float32 -> (n_frames, n_llr) int8."""
@@ -299,27 +287,14 @@ class Demapper:
         check(lib.dvbs2_demap_soft_device(self._h, d_syms, n_frames, d_n0, n0_count, d_llr, stream or None))
 
 
-class PlPayload:
+class PlPayload(_Handle):
     """PLFRAME payload step of the PL synchroniser (reference lib/plsync_cc_impl.cc:644-653, :727-795): descramble,
     drop the pilot blocks, de-rotate; produces the XFECFRAME symbols the demapper consumes."""
+    _destroy = lib.dvbs2_plpayload_destroy
 
     def __init__(self, gold_code=0, n_slots=360, has_pilots=True, max_frames=16, device=0):
-        self._h = C.c_void_p()
         check(lib.dvbs2_plpayload_create(C.byref(self._h), gold_code, n_slots, int(bool(has_pilots)), max_frames, device))
-        v = [C.c_int() for _ in range(3)]
-        check(lib.dvbs2_plpayload_params(self._h, *v))
-        self.payload_len, self.xfecframe_len, self.n_pilots = (x.value for x in v)
-
-    def close(self):
-        if self._h:
-            lib.dvbs2_plpayload_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self.payload_len, self.xfecframe_len, self.n_pilots = _ints(3, lib.dvbs2_plpayload_params, self._h)
 
     def work(self, payload, plheader_phase, fine_foffset, coarse_corrected, pilot_phase=None):
         """payload: (n_frames, payload_len) complex64; per-frame arrays as in plframe_info_t / pl_freq_sync."""
@@ -352,40 +327,25 @@ def plheader_symbols(plsc):
 
 def pls_parse(plsc):
     """pls_info_t::parse as data (reference lib/pl_signaling.cc:19-61). Host only."""
-    v = [C.c_int() for _ in range(6)]
-    check(lib.dvbs2_pls_parse(int(plsc), *v))
-    return dict(zip(("plframe_len", "payload_len", "xfecframe_len", "n_slots", "n_pilots", "n_mod"), (x.value for x in v)))
+    return dict(zip(("plframe_len", "payload_len", "xfecframe_len", "n_slots", "n_pilots", "n_mod"), _ints(6, lib.dvbs2_pls_parse, int(plsc))))
 
 
-class PlFrontEnd:
+class PlFrontEnd(_Handle):
     """PLFRAME front end: per frame the PLSC of its own header, the SOF / PLHEADER / pilot phases and the fine frequency
     offset (reference lib/plsync_cc_impl.cc:582-590, :634-636, :665-680; lib/pl_freq_sync.cc:201-349), then the payload step
     of PlPayload with those estimates. One object = one gold code and one PLSC (frame geometry)."""
+    _destroy = lib.dvbs2_plframe_destroy
 
     EST = (("plsc_decoded", np.uint8), ("sof_phase", np.float32), ("plheader_phase", np.float32), ("pilot_phase", np.float32),
            ("fine_foffset", np.float32), ("fine_valid", np.int32))
 
     def __init__(self, gold_code=0, plsc=0, max_frames=16, device=0, coherent=True, soft=True, expected_pls=None):
-        self._h = C.c_void_p()
         check(lib.dvbs2_plframe_create(C.byref(self._h), gold_code, plsc, max_frames, device))
-        v = [C.c_int() for _ in range(6)]
-        check(lib.dvbs2_plframe_params(self._h, *v))
-        self.plframe_len, self.payload_len, self.xfecframe_len, self.n_slots, self.n_pilots, self.n_mod = (x.value for x in v)
+        self.plframe_len, self.payload_len, self.xfecframe_len, self.n_slots, self.n_pilots, self.n_mod = _ints(6, lib.dvbs2_plframe_params, self._h)
         self.plsc, self.max_frames = plsc, max_frames
         self.set_plsc_mode(coherent, soft)
         if expected_pls is not None:
             self.set_expected_pls(expected_pls)
-
-    def close(self):
-        if self._h:
-            lib.dvbs2_plframe_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_plsc_mode(self, coherent=True, soft=True):
         check(lib.dvbs2_plframe_set_plsc_mode(self._h, int(bool(coherent)), int(bool(soft))))
@@ -462,11 +422,12 @@ class PlFrontEnd:
                                                     d_coarse_foffset or None, C.byref(e), stream or None))
 
 
-class PlSync:
+class PlSync(_Handle):
     """PLFRAME search on a raw symbol stream (reference lib/pl_frame_sync.cc:66-243): the timing metric for every symbol, the
     searching / found / locked state machine with PLSC decoding at every header, and the gather step that lays the locked
     frames of one PLSC out the way PlFrontEnd reads them. The handle keeps the machine's state and the 89 symbols before the
     consumed point between calls; present the stream again from `consumed`, as with GNU Radio's consume()."""
+    _destroy = lib.dvbs2_plsync_destroy
 
     FRAME_DTYPE = np.dtype(capi.PLSYNC_FRAME_DTYPE)
     MIN_SYMBOLS = 33282 + 90
@@ -474,23 +435,11 @@ class PlSync:
     def __init__(self, plsc=-1, unlock_thresh=3, max_symbols=1 << 20, max_frames=1024, device=0, coherent=True, soft=True,
                  expected_pls=None):
         """plsc = -1: decode the PLSC of every header; 0..127: the fixed-PLSC (CCM/SIS) mode."""
-        self._h = C.c_void_p()
         check(lib.dvbs2_plsync_create(C.byref(self._h), int(plsc), int(unlock_thresh), int(max_symbols), int(max_frames), device))
         self.plsc, self.unlock_thresh, self.max_symbols, self.max_frames = plsc, unlock_thresh, max_symbols, max_frames
         self.set_plsc_mode(coherent, soft)
         if expected_pls is not None:
             self.set_expected_pls(expected_pls)
-
-    def close(self):
-        if self._h:
-            lib.dvbs2_plsync_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def reset(self):
         check(lib.dvbs2_plsync_reset(self._h))
@@ -516,9 +465,7 @@ class PlSync:
 
     def finish(self):
         """Waits for the last work_device(); returns (n_frames, consumed, state)."""
-        v = [C.c_int() for _ in range(3)]
-        check(lib.dvbs2_plsync_finish(self._h, *v))
-        return tuple(x.value for x in v)
+        return _ints(3, lib.dvbs2_plsync_finish, self._h)
 
     def work(self, syms):
         """HOST buffer of complex64 symbols. Returns (frames as a FRAME_DTYPE array, consumed, state)."""
@@ -530,9 +477,8 @@ class PlSync:
         if x.size > self.max_symbols:
             raise ValueError(f"{x.size} symbols exceed max_symbols = {self.max_symbols}")
         frames = np.zeros(self.max_frames, self.FRAME_DTYPE)
-        v = [C.c_int() for _ in range(3)]
-        check(lib.dvbs2_plsync_search(self._h, x.ctypes.data if x.size else None, int(x.size), frames.ctypes.data, *v))
-        return frames[:v[0].value].copy(), v[1].value, v[2].value
+        nf, consumed, state = _ints(3, lib.dvbs2_plsync_search, self._h, x.ctypes.data if x.size else None, int(x.size), frames.ctypes.data)
+        return frames[:nf].copy(), consumed, state
 
     def gather_device(self, d_syms, d_frames, n_frames, wanted_plsc, d_plframes, d_count, stream=0):
         """DEVICE addresses: the locked frames of wanted_plsc among the first n_frames records of the LAST work_device(), back
@@ -562,28 +508,17 @@ def plcoarse_weights(full=True):
     return w[:n].copy()
 
 
-class PlCoarse:
+class PlCoarse(_Handle):
     """Coarse frequency offset estimate (reference lib/pl_freq_sync.cc:93-199, lib/plsync_cc_impl.cc:567-606): per frame the
     autocorrelation of the modulation-removed PLHEADER (or SOF while not coarse-corrected and the PLSC is not known), summed
     over `period` frames; on a window's last frame the estimate and the coarse-corrected flag. The handle keeps the window's
     state on the device between calls. Outputs per frame: coarse_foffset float32, coarse_corrected int32, new_est int32."""
+    _destroy = lib.dvbs2_plcoarse_destroy
 
     def __init__(self, period=1, plsc=-1, max_frames=1024, device=0):
         """plsc = -1: the PLSC comes with every frame (SOF form until coarse-corrected); 0..127: known, always the full form."""
-        self._h = C.c_void_p()
         check(lib.dvbs2_plcoarse_create(C.byref(self._h), int(period), int(plsc), int(max_frames), device))
         self.period, self.plsc, self.max_frames = period, plsc, max_frames
-
-    def close(self):
-        if self._h:
-            lib.dvbs2_plcoarse_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def reset(self):
         check(lib.dvbs2_plcoarse_reset(self._h))
@@ -625,25 +560,14 @@ class PlCoarse:
                                                          d_coarse_foffset or None, d_coarse_corrected or None, d_new_est or None, stream or None))
 
 
-class Rotator:
+class Rotator(_Handle):
     """Frequency-correcting rotator (reference lib/rotator_cc_impl.cc:36-128): out[n] = in[n] exp(j phi[n]), phi advancing by the
     phase increment per sample; increments change at once (set_phase_inc) or at scheduled absolute sample indices (schedule).
     Evaluated in closed form from a 64-bit fixed-point phase, not by the reference's phasor recurrence."""
+    _destroy = lib.dvbs2_rotator_destroy
 
     def __init__(self, phase_inc=0.0, device=0):
-        self._h = C.c_void_p()
         check(lib.dvbs2_rotator_create(C.byref(self._h), float(phase_inc), device))
-
-    def close(self):
-        if self._h:
-            lib.dvbs2_rotator_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def reset(self):
         check(lib.dvbs2_rotator_reset(self._h))
@@ -690,9 +614,7 @@ def symsync_loop_constants(sps, loop_bw, damping, rolloff):
 
 def symsync_geometry(sps, rrc_delay, n_subfilt, interp_method):
     """(subfilt_len, subfilt_delay, history) (reference lib/symbol_sync_cc_impl.cc:68-80, :244-256). Host only."""
-    v = [C.c_int() for _ in range(3)]
-    check(lib.dvbs2_symsync_geometry(int(sps), int(rrc_delay), int(n_subfilt), int(interp_method), *[C.byref(x) for x in v]))
-    return tuple(x.value for x in v)
+    return _ints(3, lib.dvbs2_symsync_geometry, int(sps), int(rrc_delay), int(n_subfilt), int(interp_method))
 
 
 def symsync_taps(sps, rolloff, rrc_delay, n_subfilt):
@@ -704,18 +626,18 @@ def symsync_taps(sps, rolloff, rrc_delay, n_subfilt):
     return bank
 
 
-class SymbolSync:
+class SymbolSync(_Handle):
     """Symbol timing recovery (reference lib/symbol_sync_cc_impl.cc): Gardner detector, PI loop, modulo-1 counter and one of four
     interpolators (0 polyphase RRC bank = the matched filter, 1 linear, 2 quadratic, 3 cubic), on samples at `sps` per symbol.
     A call takes a batch of independent streams; the handle keeps each stream's loop state and history on the device between
     calls. Present a stream again from `consumed`, as with GNU Radio's consume()."""
+    _destroy = lib.dvbs2_symsync_destroy
 
     POLYPHASE, LINEAR, QUADRATIC, CUBIC = 0, 1, 2, 3
 
     def __init__(self, sps=2, loop_bw=0.01, damping=1.0, rolloff=0.2, rrc_delay=5, n_subfilt=128, interp_method=0, max_streams=1,
                  max_samples=1 << 20, device=0, taps=None):
         """taps: a float32 [n_subfilt, subfilt_len] bank to use instead of the library's design (symsync_taps' layout)."""
-        self._h = C.c_void_p()
         args = (int(sps), float(loop_bw), float(damping), float(rolloff), int(rrc_delay), int(n_subfilt), int(interp_method))
         if taps is None:
             check(lib.dvbs2_symsync_create(C.byref(self._h), *args, int(max_streams), int(max_samples), device))
@@ -730,17 +652,6 @@ class SymbolSync:
         self.subfilt_len, self.subfilt_delay, self.history = (x.value for x in v)
         self.Kp, self.K1, self.K2 = (np.float32(x.value) for x in f)
         self._n = 0
-
-    def close(self):
-        if self._h:
-            lib.dvbs2_symsync_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def reset(self):
         check(lib.dvbs2_symsync_reset(self._h))
@@ -778,11 +689,9 @@ class SymbolSync:
             raise ValueError(f"{x.size} samples exceed max_samples = {self.max_samples}")
         cap = x.size if max_out is None else int(max_out)
         out, idx, mu = np.zeros(cap, np.complex64), np.zeros(cap, np.int64), np.zeros(cap, np.float64)
-        v = [C.c_int() for _ in range(3)]
-        check(lib.dvbs2_symsync_work(self._h, x.ctypes.data if x.size else None, int(x.size), out.ctypes.data if cap else None, cap,
-                                     idx.ctypes.data, mu.ctypes.data, *[C.byref(q) for q in v]))
-        k = v[0].value
-        return out[:k].copy(), idx[:k].copy(), mu[:k].copy(), v[1].value, v[2].value
+        k, consumed, status = _ints(3, lib.dvbs2_symsync_work, self._h, x.ctypes.data if x.size else None, int(x.size),
+                                    out.ctypes.data if cap else None, cap, idx.ctypes.data, mu.ctypes.data)
+        return out[:k].copy(), idx[:k].copy(), mu[:k].copy(), consumed, status
 
 
 def pl_scrambling_rn(gold_code, n):
@@ -791,31 +700,18 @@ def pl_scrambling_rn(gold_code, n):
     return rn
 
 
-class BbDeheader:
+class BbDeheader(_Handle):
     """bbdeheader_bb (reference lib/bbdeheader_bb_impl.cc): descrambled BBFRAMEs in, 188-byte MPEG-TS packets out. The block's
     state (synchronised flag, partial packet, counters) is kept in the handle between calls, as between work() calls."""
+    _destroy = lib.dvbs2_bbdeheader_destroy
 
     def __init__(self, standard=capi.STANDARD_DVBS2, framesize=capi.FECFRAME_NORMAL, rate="C1_2", max_frames=64, device=0,
                  kbch_bits=None):
-        self._h = C.c_void_p()
         if kbch_bits is not None:
             check(lib.dvbs2_bbdeheader_create_raw(C.byref(self._h), kbch_bits, max_frames, device))
         else:
             check(lib.dvbs2_bbdeheader_create(C.byref(self._h), standard, framesize, rate_id(rate), max_frames, device))
-        v = [C.c_int() for _ in range(3)]
-        check(lib.dvbs2_bbdeheader_params(self._h, *v))
-        self.kbch_bytes, self.max_dfl, self.max_out_bytes_per_frame = (x.value for x in v)
-
-    def close(self):
-        if self._h:
-            lib.dvbs2_bbdeheader_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self.kbch_bytes, self.max_dfl, self.max_out_bytes_per_frame = _ints(3, lib.dvbs2_bbdeheader_params, self._h)
 
     def work(self, bbframes):
         """bbframes: (n_frames, kbch_bytes) uint8 -> the TS bytes produced (general_work's output items)."""
@@ -844,13 +740,13 @@ class BbDeheader:
         check(lib.dvbs2_bbdeheader_reset(self._h, stream))
 
 
-class FecChain:
+class FecChain(_Handle):
     """demapper -> LDPC (OM_MESSAGE) -> BCH on the device, as wired in apps/dvbs2-rx:853-863. constellation: capi.MOD_QPSK,
     MOD_8PSK, MOD_16APSK or MOD_32APSK (the APSK chains run demapper -> LLR buffer -> LDPC, never the fused load)."""
+    _destroy = lib.dvbs2_chain_destroy
 
     def __init__(self, standard=capi.STANDARD_DVBS2, framesize=capi.FECFRAME_NORMAL, rate="C3_4",
                  constellation=capi.MOD_8PSK, group_size=32, max_frames=64, max_trials=0, device=0, from_llr=False):
-        self._h = C.c_void_p()
         if from_llr:  # ldpc_decoder_bb -> bch_decoder_bb only (LLRs in)
             check(lib.dvbs2_chain_create_llr(C.byref(self._h), standard, framesize, rate_id(rate), group_size, max_frames, device))
         else:
@@ -863,17 +759,6 @@ class FecChain:
         self.n_llr = a.value
         self.group_size = group_size
         self.max_trials = DEFAULT_TRIALS if max_trials == 0 else max_trials
-
-    def close(self):
-        if self._h:
-            lib.dvbs2_chain_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_descramble(self, enable=True):
         check(lib.dvbs2_chain_set_descramble(self._h, int(bool(enable))))

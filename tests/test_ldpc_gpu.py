@@ -394,7 +394,7 @@ def test_enqueue_finish_contract():
 
 @pytest.mark.parametrize("nf,chunk,rounds", [(416, "64", None), (416, "64", "0"), (1088, None, None), (1088, None, "0"), (200, "66", "0")])
 def test_host_entry_multi_chunk(monkeypatch, nf, chunk, rounds):
-    """The chunked pipeline of the host-buffer entry dvbs2_ldpc_decode (csrc/c_api.hip): frame_base > 0, all four slots and
+    """The chunked pipeline of the host-buffer entry dvbs2_ldpc_decode (csrc/c_api_ldpc.hip, csrc/host_pipe.hip): frame_base > 0, all four slots and
     streams, slot re-use after finish(c - kSlots) (seven chunks of 64 frames), the pinned landing buffers, and -- with no
     device-side resolution rounds (DVBS2_RESOLVE_ROUNDS=0) on near-threshold input -- the re-fetch of a chunk's outputs when
     finish() had to run host-driven rounds. 1088 frames take the DEFAULT chunking (512 + 512 + 64); chunk 66 with G = 32 is
