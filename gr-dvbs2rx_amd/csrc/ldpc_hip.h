@@ -93,7 +93,7 @@ private:
     int* d_iters_ = nullptr;      // per frame: updates done
     int* d_good_ = nullptr;       // per frame: syndrome satisfied at the current state
     int* d_target_ = nullptr;     // per frame: updates to reach in a resume pass
-    int* d_gsync_ = nullptr;      // one status word per frame: group-synchronous stop inside the first pass (ldpc_kernel.hpp, group_decide)
+    int* d_gsync_ = nullptr;      // one status word per frame: group-synchronous stop inside the first pass (ldpc_prims.hpp, group_decide)
     bool gsync_on_ = false;
     bool pr_shared_sv_ = false;   // parity-in-records kernel: one sign-vector area per workgroup (two do not fit twice into a CU's LDS)
     int* d_flag_ = nullptr;       // [slot] = number of unresolved groups

@@ -17,8 +17,7 @@
 //     ordered update) are processed in ascending lane blocks of B_i (ldpc_schedule.h).
 #include "ldpc_hip.h"
 #include "ldpc_plan.h"
-#include "ldpc_kernel.hpp"
-#include "ldpc_kernel_pr.hpp"
+#include "ldpc_launch.h"
 #include "device_guard.h"
 #include <algorithm>
 #include <cstdio>

@@ -1,3 +1,3 @@
-// one kernel variant per translation unit (parallel build); see ldpc_kernel.hpp
+// one kernel variant per translation unit (parallel build); see ldpc_inst.hpp
 #define DVBS2_LDPC_INSTANTIATE 28
-#include "ldpc_kernel.hpp"
+#include "ldpc_inst.hpp"

@@ -5,7 +5,7 @@
 // to two pairs per CU gained 1.45-1.5x on short frames. What limits normal frames to one pair per CU is LDS:
 // 64800 LLR bytes per frame. But parity row i is only ever touched by thread j of layers i and i+1 (own parity,
 // then previous parity), so it can live in registers between those two layers and in byte 7 of the per-thread
-// message record in between sweeps (ldpc_kernel.hpp, check_node<.., PR>). LDS then holds K + 360 bytes per frame
+// message record in between sweeps (ldpc_node_plain.hpp, check_node<.., PR>). LDS then holds K + 360 bytes per frame
 // (information LLRs + parity row q-1) and, for K <= 32400 (rates up to 1/2) with check degree <= 7, TWO pair
 // workgroups fit a CU: 24 waves, 6 per SIMD, at 80 VGPRs.
 //
@@ -17,7 +17,11 @@
 // for 4-5 useful ones and run at ~4.9 TB/s of real traffic (short 1/4: 2.3 x the algorithmic bytes): halving the record is worth
 // the ~18 VALU instructions of the conversion around the node.
 #pragma once
-#include "ldpc_kernel.hpp"
+#include "ldpc_launch.h"
+#include "ldpc_prims.hpp"
+#include "ldpc_node_plain.hpp"
+#include "ldpc_node_packed.hpp"
+#include "ldpc_node_hazard.hpp"
 
 // Round 6: the degree-3 / 4 node of the one-dword-record kernel takes the minimum over the OTHER links directly (see check_node_pr6). Interleaved A/B against
 // "two smallest + select" (three repetitions, gpurun_out/r6m): short 1/4 1059.8 -> 1074.1 k (+1.3 %), S2X short 1220 -> 1232 k, medium 1/5 and 11/45 +1.0 / +1.1 %,
@@ -35,13 +39,15 @@ namespace dvbs2 {
         if (first_layer) check_node<D, true, true, false>(lds_all, ent, jj, lb, mw, nm, own_in, &carry); \
         else if (last_layer) check_node<D, false, true, true>(lds_all, ent, jj, lb, mw, nm, own_in, &carry); \
         else check_node<D, false, true, false>(lds_all, ent, jj, lb, mw, nm, own_in, &carry); } break;
-#define DVBS2_PR_SWITCH switch (deg) { DVBS2_PR_CASE(3) DVBS2_PR_CASE(4) DVBS2_PR_CASE(5) DVBS2_PR_CASE(6) DVBS2_PR_CASE(7) default: break; }
+#define DVBS2_PR_SWITCH switch (deg) { DVBS2_DEGREES_3_7(DVBS2_PR_CASE) default: break; }
+#define DVBS2_PRH_NODE(D, NCV, ...) \
+        check_node_hazard<D, NCV, HazardCfg<hz::pr<true>, __VA_ARGS__>>(lds_all, ent, jj, lb, work, block, 0, mw, nm, own_in, &carry, nullptr, nullptr, pr_epoch, 0);
 #define DVBS2_PRH_CALL(D, NCV) { if constexpr (D - 2 >= NCV) { \
-        if (first_layer) check_node_hazard<D, NCV, true, true, false>(lds_all, ent, jj, lb, work, block, 0, mw, nm, own_in, &carry, nullptr, nullptr, pr_epoch, 0); \
-        else if (last_layer) check_node_hazard<D, NCV, false, true, true>(lds_all, ent, jj, lb, work, block, 0, mw, nm, own_in, &carry, nullptr, nullptr, pr_epoch, 0); \
-        else check_node_hazard<D, NCV, false, true, false>(lds_all, ent, jj, lb, work, block, 0, mw, nm, own_in, &carry, nullptr, nullptr, pr_epoch, 0); } }
+        if (first_layer) DVBS2_PRH_NODE(D, NCV, hz::layer0<true>, hz::last<false>) \
+        else if (last_layer) DVBS2_PRH_NODE(D, NCV, hz::layer0<false>, hz::last<true>) \
+        else DVBS2_PRH_NODE(D, NCV, hz::layer0<false>, hz::last<false>) } }
 #define DVBS2_PRH_CASE(D) case D: { if (nc == 2) DVBS2_PRH_CALL(D, 2) else if (nc == 4) DVBS2_PRH_CALL(D, 4) } break;
-#define DVBS2_PRH_SWITCH switch (deg) { DVBS2_PRH_CASE(4) DVBS2_PRH_CASE(5) DVBS2_PRH_CASE(6) DVBS2_PRH_CASE(7) default: break; }
+#define DVBS2_PRH_SWITCH switch (deg) { DVBS2_DEGREES_4_7(DVBS2_PRH_CASE) default: break; }
 
 // 6-bit record <-> the byte format the check nodes take (mw[0] = four offset-binary message bytes, byte 3 of mw[1] = parity LLR)
 __device__ __forceinline__ void pr_w1_expand(uint32_t x, uint32_t* mw)
@@ -58,7 +64,7 @@ __device__ __forceinline__ uint32_t pr_w1_compress(const uint32_t* nm)
     return (y & 0x3fu) | ((y >> 2) & 0xfc0u) | ((y >> 4) & 0x3f000u) | ((y >> 6) & 0xfc0000u) | (nm[1] & 0xff000000u);
 }
 
-// check_node<DEG, LAYER0, PR = true, LAST> (ldpc_kernel.hpp) on the one-dword record itself: messages come out of and go back into
+// check_node<DEG, LAYER0, PR = true, LAST> (ldpc_node_plain.hpp) on the one-dword record itself: messages come out of and go back into
 // the 6-bit fields without the detour through byte words (two instructions per message each way instead of ~4.5).
 __device__ __forceinline__ uint32_t vmin3_u32(uint32_t a, uint32_t b, uint32_t c) { uint32_t r; asm("v_min3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(c)); return r; }
 __device__ __forceinline__ uint32_t usub_sat1(uint32_t a) { uint32_t r; asm("v_sub_u32_e64 %0, %1, 1 clamp" : "=v"(r) : "v"(a)); return r; } // max(a - 1, 0)
@@ -130,7 +136,7 @@ __device__ __forceinline__ uint32_t check_node_pr6(uint8_t* __restrict__ lds, co
     return y | ((uint32_t)spare << 24);
 }
 
-// check_node_v2 (ldpc_kernel.hpp: pairs of edges in the 16-bit halves of a register, one-add addresses from the wave's record) for the regular middle
+// check_node_v2 (ldpc_node_packed.hpp: pairs of edges in the 16-bit halves of a register, one-add addresses from the wave's record) for the regular middle
 // layers of the two-dword-record kernel (round 6, last session). Differences: the two parity entries DEG-2 (own) and DEG-1 (previous) come from and go
 // back to registers (own_in / carry / byte 3 of word 1), LDS holds offset-binary bytes (the plain nodes of layer 0, the last layer and the hazard layers
 // share it), and word 1's byte 3 is the parity LLR -- at degree 7 that is where the pad half of pair 3 would keep its (always zero) message, so the pair is
@@ -247,7 +253,7 @@ template <bool W1, bool V2 = false /*packed nodes in the regular middle layers (
 __global__ __launch_bounds__(kThreads, 6) void ldpc_layered_pr_kernel(
     const uint32_t* __restrict__ recs, const uint32_t* __restrict__ wrecs, const int8_t* __restrict__ llr_in, uint8_t* __restrict__ state,
     uint32_t* __restrict__ msgs, int* __restrict__ iters, int* __restrict__ good, const int* __restrict__ target,
-    int n_frames, int N, int K, int q, int cap, int stop_on_good /*bit 0: stop at a good syndrome, bit 2: group-synchronous stop (ldpc_kernel.hpp, group_decide), bit 3: one sign-vector area per workgroup*/)
+    int n_frames, int N, int K, int q, int cap, int stop_on_good /*bit 0: stop at a good syndrome, bit 2: group-synchronous stop (ldpc_prims.hpp, group_decide), bit 3: one sign-vector area per workgroup*/)
 {
     if (!llr_in) { // resume launch: a workgroup whose frames are both at their target leaves before touching LDS
         const int fa = 2 * (int)blockIdx.x, fb = fa + 1;
@@ -265,7 +271,7 @@ __global__ __launch_bounds__(kThreads, 6) void ldpc_layered_pr_kernel(
     const int tid = threadIdx.x - half * kHalf;
     const int lb_rel = half * (int)pr_half_bytes(K);
     const int lb = lb_rel + lds_address_of(lds_all); // absolute LDS address of this frame's region
-    lds_byte_t* lds = (lds_byte_t*)lds_all + lb_rel; // (address-space-3 typed pointers: ldpc_kernel.hpp, lds_byte_t)
+    lds_byte_t* lds = (lds_byte_t*)lds_all + lb_rel; // (address-space-3 typed pointers: ldpc_prims.hpp, lds_byte_t)
     // Round 5: a sign-vector area per FRAME. With one area per workgroup the two frames took turns through the full syndrome test (three
     // barriers each), and a full test cost both of them 27 us -- three quarters of an update sweep of short 1/4 (measured with a build that
     // runs it after every update): at the operating point, where converged frames pass the pre-test until their group stops, that was a
@@ -420,7 +426,7 @@ __global__ __launch_bounds__(kThreads, 6) void ldpc_layered_pr_kernel(
             }
             if (tid == 0) { flags[0] = 0; flags[2] = 0; flags[1] = fin; }
         }
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); // LDS only: the group report above is not waited for (ldpc_kernel.hpp, frame_barrier_lds)
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); // LDS only: the group report above is not waited for (ldpc_prims.hpp, frame_barrier_lds)
         if (gs) finished = flags[1] != 0;
         if (finished && other_flags[1]) break;
 
@@ -439,7 +445,7 @@ __global__ __launch_bounds__(kThreads, 6) void ldpc_layered_pr_kernel(
 #pragma unroll
         for (int k = 0; k < 2 * DMAX; k++) nent[k] = srec[4 + k];
         // The record a layer produces is STORED at the head of the next layer, behind an explicit s_waitcnt vmcnt(0) (see
-        // DVBS2_WAIT_VM0 in ldpc_kernel.hpp: the compiler waits for the prefetched record with vmcnt(0) at the head of a layer,
+        // DVBS2_WAIT_VM0 in ldpc_prims.hpp: the compiler waits for the prefetched record with vmcnt(0) at the head of a layer,
         // i.e. right behind the store the previous layer has just issued; stored here instead, everything that wait covers is a layer old).
         // Here the wait cannot simply go in front of the store at the END of the layer: the layers of these tables are short and the
         // prefetch issued at their head would not be back yet.
@@ -540,13 +546,7 @@ __global__ __launch_bounds__(kThreads, 6) void ldpc_layered_pr_kernel(
     }
 }
 
-#endif // DVBS2_LDPC_INSTANTIATE_PR
-
-// the parity-in-records builds (LdpcBuild::pr, pr_w1, pr_packed); prepare fails when `build` is not one of them
-hipError_t ldpc_pr_prepare(LdpcBuild build, size_t lds_bytes);
-void ldpc_pr_launch(const LdpcLaunch& a);
-
-#ifdef DVBS2_LDPC_INSTANTIATE_PR
+// the launch interface of ldpc_launch.h
 typedef void (*PrKernel)(const uint32_t*, const uint32_t*, const int8_t*, uint8_t*, uint32_t*, int*, int*, const int*, int, int, int, int, int, int);
 static PrKernel pr_kernel(LdpcBuild b)
 {

@@ -82,7 +82,7 @@ constexpr int kHazardWalk = 15; // header code: too many hazard entries, fall ba
 constexpr int kCuSlots = 16 * 8 * 2 * 16; // per-CU pattern counters of the one-frame builds, indexed by hw_cu_index() (ldpc_kernel.hpp)
 
 // The build of the sweep kernel a handle runs, decided once per table by the host (ldpc_plan.cpp). The classic kernel's builds exist
-// in the degree classes the k*Built rules of ldpc_kernel.hpp give; the parity-in-records builds (ldpc_kernel_pr.hpp) in the class 8 only.
+// in the degree classes the k*Built rules of ldpc_launch.h and ldpc_inst.hpp give; the parity-in-records builds (ldpc_kernel_pr.hpp) in the class 8 only.
 enum class LdpcBuild : uint8_t {
     plain,       // pair workgroups, scalar nodes
     packed,      // pair workgroups with the packed nodes (check_node_v2, check_node_chain_v2)

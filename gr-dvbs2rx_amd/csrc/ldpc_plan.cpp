@@ -58,7 +58,7 @@ Choice select_build(const LdpcSchedule& s, const char* table_name, const LdpcOve
     // parity-in-records kernel: the 80-VGPR build puts a second workgroup on the CU (measured: short 3/5 and 2/3 +34 %;
     // it costs 6-18 % where regular layers dominate, hence the 70 % threshold; degree classes above 12 do not fit 80 VGPRs).
     // It has no two-level lane chain (76 -> 349 spilled registers, round 3) and, since round 4, no single-pair lane chain either -- with
-    // its tables addressed as LDS (typed pointers, ldpc_kernel.hpp) the chain code made that build spill ten times as much (72 -> 725)
+    // its tables addressed as LDS (typed pointers, ldpc_prims.hpp) the chain code made that build spill ten times as much (72 -> 725)
     // and short 3/5 / 2/3 lost 30 %; its layers take the block scheme.
     c.dense = !c.pr && c.dmax == 12 && 4 * half_lds_bytes(s.N) <= 160 * 1024 &&
               pick(ov.dense, s.N < 64800 && 10 * s.conflict_layers >= 7 * s.q);
@@ -83,7 +83,7 @@ Choice select_build(const LdpcSchedule& s, const char* table_name, const LdpcOve
     }
     c.hz2 = !c.dense && c.dmax >= 12 && pick(ov.hz2, pol_hz2);
     c.solo = !c.pr && !c.dense && !c.hz2 && c.dmax <= kSoloMaxDmax && !ov.timing && pick(ov.solo, pol_solo);
-    // frame barriers in software (ldpc_kernel.hpp): by rule where no layer has hazards; with hazard layers only for the tables listed in
+    // frame barriers in software (ldpc_prims.hpp, frame_barrier): by rule where no layer has hazards; with hazard layers only for the tables listed in
     // ldpc_policy_soft.inc (measured on two leases, tools/soft_sweep.py)
     bool pol_soft = s.conflict_layers == 0;
     {
@@ -235,7 +235,7 @@ LayerRecords layer_records(const LdpcSchedule& s, const Choice& c)
 }
 
 // ---- per-(layer, wave) records ----
-// Sweep records per (layer, wave) for the classic kernel (check_node_v2 in ldpc_kernel.hpp). A regular layer i > 0 gets,
+// Sweep records per (layer, wave) for the classic kernel (check_node_v2 in ldpc_node_packed.hpp). A regular layer i > 0 gets,
 // for each of the six waves of a frame, its data entries reordered "mixed first" (split_wave), window offsets pre-adjusted for the
 // wave, and the lane masks of the mixed entries; a wave with more mixed entries than fix slots, layer 0 and hazard layers keep the
 // classic record (replicated).
@@ -254,7 +254,7 @@ std::vector<uint32_t> wave_records(const LdpcSchedule& s, const Choice& c, const
         for (int w = 0; chain_order >= 0 && w < 6; w++)
             if ((int)split_wave(s, L, nullptr, 2, w).mixed.size() > v2_nfix(dmax)) chain_order = -1;
         const bool chain2 = chain_order >= 0;
-        // hazard layers of the packed builds whose ordered phase is the generic one (check_node_hazard<..., V2P>, ldpc_kernel.hpp): the NC
+        // hazard layers of the packed builds whose ordered phase is the generic one (check_node_hazard with packed_phases, ldpc_node_hazard.hpp): the NC
         // ordered entries keep their record order in the first fix slots, the mixed regular entries follow; dmax / 2 fix slots in all
         const int ncv = lr.nc[i];
         const bool v2p = c.packed && c.v2p_on && v2p_class(dmax) && hazard && !chain2 && (ncv == 2 || ncv == 4 || ncv == 8) && (int)L.cnt >= ncv;
@@ -333,7 +333,7 @@ LdpcPlan plan_ldpc(const LdpcSchedule& s, const char* table_name, int group_size
     p.recs = lr.recs;
     p.build = build_of(c);
     p.pr = c.pr; p.pr_shared_sv = c.pr_shared_sv; p.dmax = c.dmax; p.words_per_check = c.words_per_check;
-    // Group-synchronous stop (ldpc_kernel.hpp, group_decide): the frames of a group agree after every syndrome test, so the whole
+    // Group-synchronous stop (ldpc_prims.hpp, group_decide): the frames of a group agree after every syndrome test, so the whole
     // group stops at the reference's count inside the first pass and the resolution rounds have nothing left to do (they stay as
     // the fallback; with the rule on, none is enqueued ahead of time). Needs the members of a group resident together: groups of up
     // to 64 frames (at most 32 pair workgroups of 256 CUs). DVBS2_GROUP_SYNC=0 / 1 overrides (tests run both).

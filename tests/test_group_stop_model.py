@@ -1,4 +1,4 @@
-"""CPU model of the group-synchronous stopping rule (csrc/ldpc_kernel.hpp, group_decide + the host-side resolution of
+"""CPU model of the group-synchronous stopping rule (csrc/ldpc_prims.hpp, group_decide + the host-side resolution of
 csrc/ldpc_hip.hip): the PROTOCOL is checked here under random interleavings -- the kernel's implementation of it is checked
 bit for bit against the reference on the GPU (tests/test_ldpc_gpu.py).
 

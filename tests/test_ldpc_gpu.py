@@ -549,7 +549,7 @@ def test_two_devices_from_one_process():
 
 @pytest.mark.parametrize("table,amp,sigma", [("S2_TABLE_B4", 6, 5.2), ("S2_TABLE_C1", 5, 6.0)])
 def test_group_stop_fallback_when_members_give_up(monkeypatch, table, amp, sigma):
-    """The group-synchronous stop (csrc/ldpc_kernel.hpp, group_decide) lets a frame that passes its test wait for the other frames of
+    """The group-synchronous stop (csrc/ldpc_prims.hpp, group_decide) lets a frame that passes its test wait for the other frames of
     its group; if they do not report in time it stops at its own good point and the host-side resolution (targets kernel + resume
     launches, finish()) completes the group. DVBS2_GROUP_SPIN_MAX=0 makes every waiting frame give up at once: near-threshold
     groups (frames converge at different counts) must still come out exactly like the reference's lockstep batch, for G = 32 and 16,

@@ -1,5 +1,5 @@
 // Micro-benchmark (gfx950): what a barrier of SIX of a workgroup's twelve waves costs -- the per-frame software barrier of the
-// LDPC sweep kernels (ldpc_kernel.hpp, frame_barrier) against the hardware barrier of all twelve, and whether S_WAKEUP (the ISA's
+// LDPC sweep kernels (ldpc_prims.hpp, frame_barrier) against the hardware barrier of all twelve, and whether S_WAKEUP (the ISA's
 // "fBarrier speedup": a wave pings the sleeping waves of its workgroup) shortens it.
 // One workgroup of 12 waves per CU, two halves of six waves; every wave runs REPS episodes of { W dependent VALU instructions; barrier }.
 // The waves of a half arrive together (same work), so an episode costs W x ~4.5 cycles + the barrier's own latency.
