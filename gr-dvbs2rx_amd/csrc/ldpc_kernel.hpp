@@ -23,6 +23,8 @@ namespace dvbs2 {
 // (a degree the build does not instantiate -- a case without a body, or the default -- never occurs in a record. Left undefined there, nm became a value carried round the
 // layer loop: one 64-bit register copy per layer on EVERY path. Defined there, it costs the paths that run nothing.)
 #define DVBS2_NM_CLEAR { _Pragma("unroll") for (int w_ = 0; w_ < MW; w_++) nm[w_] = 0u; }
+// the run loop of the degree classes up to 8 (kRun in the kernel): one dispatch per RUN of regular packed layers, on the header's count field
+#define DVBS2_RUN_CASE(D) case D - 2: if constexpr (D >= 3 && D <= DMAX && D > DMAX - 8) { run(std::integral_constant<int, (D >= 3 ? D : 3)>{}); } break;
 
 #define DVBS2_CHAIN_CASE(D) case D: if constexpr (D >= 4 && D <= DMAX && D > DMAX - 8) { check_node_chain_v2<(D >= 4 ? D : 4), DMAX, TC>(ent, jj, jj + lb, work, block, mw, nm, htab16, hb_ctr, hb_epoch, hb_lane); } break;
 #define DVBS2_CHAIN_SWITCH switch (deg) { DVBS2_DEGREES_4_32(DVBS2_CHAIN_CASE) default: break; }
@@ -444,8 +446,14 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
         // at every layer head, and the records of a table (5-7 KB) stay in the scalar cache anyway.)
         // Up to kPfSmallMaxDmax the whole record is double-buffered in scalar registers. Measured: class 8 loses 2-3 % without it
         // (B4 119.7 -> 117.1 k), class 12 GAINS 1-3 % without it (3/5, 2/3 normal, S2X 11/20, T2 2/3, short 2/3; short 3/5 -0.7 %)
+        // Run loop: the packed builds of the degree classes up to 8 run their regular packed layers in a loop of their own (at the head
+        // of the layer loop). At three waves per SIMD a wave is limited by its own instruction stream, scalar instructions included, and
+        // the layer loop spent 67 of them per regular trip on the record double buffer's moves, the header decode and the degree switch as
+        // a compare chain -- for a degree and a record format that change nine times in B4's 90 layers (notes/r09_run_loop.md).
+        constexpr bool kRun = V2 && DMAX <= 8;
         constexpr int kPfSmallMaxDmax = 8;
         constexpr int PF = DMAX <= kPfSmallMaxDmax ? 1 : 2 * DMAX;
+        static_assert(!kRun || PF == 1, "the run loop takes over whole records fetched ahead into scalar registers");
         // the sweep reads the records of its own WAVE (check_node_v2): wrecs[(layer * 6 + wave) * RS]
         const uint32_t* wr = V2 ? wrecs + (size_t)wave_u * rec_stride_wave(DMAX) : recs; // builds without packed nodes read the per-layer records
         // (word 1 carries nothing: it is loaded with the header only for the first record, which keeps the scalar loads of the kernel as measured)
@@ -461,6 +469,72 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
         // 115.9 k without it; re-measured once B4 ran the packed one-frame build: B4 133.2 -> 134.5 k, 2/5 normal +0.7 %, 3/5 +1 %, others +-0.5 %.
         asm volatile("" : "+s"(nhdr), "+s"(nw1), "+s"(nent[0]));
         for (int i = 0; i < q; i++) {
+            if constexpr (kRun) {
+                // Run loop (see kRun): a maximal stretch of consecutive regular layers whose record of THIS wave is packed and has one degree.
+                // The degree dispatch and the header decode happen once per run, and the trip is unrolled by two over ping-pong registers:
+                // the record (A / B) and the messages (pre / pb) a trip has fetched ahead are what the next trip works on, where it lies.
+                // What a trip keeps of the layer loop: the per-layer barrier bit, the prefetch behind the barrier, the vmcnt(0) in front
+                // of the stores. A run ends at the first prefetched header that does not continue it (or at the last layer: the record
+                // fetched ahead is layer 0's then, which is never packed -- ldpc_plan.cpp --, so the wrap ends a run by itself; the
+                // test on the layer index only tells the compiler). Waves of a frame may cut their runs differently (bit 13 is per wave);
+                // the barrier bit is the layer's, so every wave meets the same barriers on either path.
+                if (work && (nhdr & kRecPacked) && (nhdr >> kRecBlockShift) >= (uint32_t)kM) {
+                    auto run = [&](auto degc) {
+                        constexpr int D = decltype(degc)::value;
+                        uint32_t ha = nhdr, hb = 0u, ea[2 * DMAX], eb[2 * DMAX], pb[MW];
+#pragma unroll
+                        for (int k = 0; k < 2 * DMAX; k++) { ea[k] = nent[k]; eb[k] = 0u; }
+#pragma unroll
+                        for (int w = 0; w < MW; w++) pb[w] = 0u;
+                        bool more;
+// one trip: the layer of record (H, E) with the messages P; the next layer's record goes to (NH, NE), its messages to NP
+#define DVBS2_RUN_TRIP(H, E, P, NH, NE, NP) { \
+                            const int inext = i + 1 < q ? i + 1 : 0; \
+                            const uint32_t* nrec = wr + (size_t)inext * RSW; \
+                            TSTAMP(tA); \
+                            if (H & (1u << kRecSyncShift)) lds_barrier(); \
+                            asm volatile("" ::: "memory"); \
+                            NH = nrec[0]; \
+                            _Pragma("unroll") for (int k = 0; k < 2 * DMAX; k++) NE[k] = nrec[4 + k]; \
+                            TSTAMP(tB); tm_bar += tB - tA; \
+                            uint32_t mw[MW], nm[MW]; \
+                            _Pragma("unroll") for (int w = 0; w < MW; w++) mw[w] = P[w]; \
+                            if (zero_msgs) { \
+                                asm volatile("" ::: "memory"); \
+                                _Pragma("unroll") for (int w = 0; w < MW; w++) mw[w] = 0u; \
+                            } else msg_load(NP, inext * kLayerBytes, row4); \
+                            check_node_v2<D, DMAX, TC>(E, row + lb, mw, nm, 0); \
+                            DVBS2_WAIT_VM0(); \
+                            msg_store(nm, i * kLayerBytes, row4); \
+                            TSTAMP(tC); tm_body += tC - tB; \
+                            if (TIMING && tdbg && f == 0 && tid == 0) tdbg[(size_t)n_frames * 48 + i] += tC - tA; \
+                            more = inext != 0 && ((NH ^ H) & (0xffu | kRecPacked)) == 0u && (NH >> kRecBlockShift) >= (uint32_t)kM; }
+                        for (;;) {
+                            DVBS2_RUN_TRIP(ha, ea, pre, hb, eb, pb)
+                            if (!more) { // the run ends behind an odd trip: what was fetched ahead moves to where the layer loop expects it
+                                nhdr = hb;
+#pragma unroll
+                                for (int k = 0; k < 2 * DMAX; k++) nent[k] = eb[k];
+#pragma unroll
+                                for (int w = 0; w < MW; w++) pre[w] = pb[w];
+                                break;
+                            }
+                            i++;
+                            DVBS2_RUN_TRIP(hb, eb, pb, ha, ea, pre)
+                            if (!more) {
+                                nhdr = ha;
+#pragma unroll
+                                for (int k = 0; k < 2 * DMAX; k++) nent[k] = ea[k];
+                                break;
+                            }
+                            i++;
+                        }
+#undef DVBS2_RUN_TRIP
+                    };
+                    switch (nhdr & 0xffu) { DVBS2_DEGREES_3_7(DVBS2_RUN_CASE) DVBS2_RUN_CASE(8) default: break; }
+                    continue;
+                }
+            }
             const uint32_t hdr = nhdr;
             uint32_t ent[2 * DMAX];
 #pragma unroll
@@ -502,7 +576,8 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
                     // v2: this wave's record is in the packed node's format (two's complement messages)
                     uint32_t mw[MW], nm[MW];
                     take_msgs(mw, pre, zero_msgs, v2 ? 0u : 0x80808080u, inext * kLayerBytes, row4);
-                    if constexpr (V2) { if (v2) { DVBS2_V2_SWITCH } else DVBS2_DEG_SWITCH } else DVBS2_DEG_SWITCH
+                    // (kRun: a packed record of a working wave never gets here -- the run loop at the head of the layer loop took it)
+                    if constexpr (V2 && !kRun) { if (v2) { DVBS2_V2_SWITCH } else DVBS2_DEG_SWITCH } else DVBS2_DEG_SWITCH
                     DVBS2_WAIT_VM0();
                     msg_store(nm, mso, row4);
                 }

@@ -12,6 +12,8 @@ which counts the regular node alone).
      no barrier; the blocks it takes are printed, so the choice can be checked against the disassembly. Split into "node"
      (s_setprio 0 .. the end of the node's block: the node and its message packing, what node_census.py calls total) and "else"
      (everything outside: the layer head, the switch, message load / store, the copies at the loop's back edge).
+ (a') where the build has the run loop (two node bodies of the degree): one line per half of the loop unrolled by two -- everything a
+     wave issues from the head of one node to the head of the other (VALU, SALU, branches taken), by the cheapest barrier-free way.
  (b) one HAZARD layer of the single-pair lane-chain form (check_node_chain_v2) of that degree: the text between the node's first
      s_setprio 0 and the message packing behind its last phase, split at its two barriers into P1 (regular entries read and reduced,
      heads' pair, chain operands published), walk (per chain: prologue + ONE four-step trip of the walk loop + the three tail steps)
@@ -80,8 +82,20 @@ def blocks_of(dis, want):
     return blk, succ, names
 
 
-def find_node(blk, deg):
+def find_nodes(blk, deg):
+    """every packed regular node of the degree: [(block, index of its s_setprio 0)]"""
+    out = []
+    for k in range(len(blk)):
+        kk, i = find_node(blk, deg, k)
+        if kk == k:
+            out.append((k, i))
+    return out
+
+
+def find_node(blk, deg, first=0):
     for k, b in enumerate(blk):
+        if k < first:
+            continue
         for i, (o, a) in enumerate(b):
             if o == "s_setprio" and a.startswith("0"):
                 rest = b[i:]
@@ -121,6 +135,31 @@ def cheapest_cycle(blk, succ, k0):
     return path[::-1]
 
 
+def cheapest_path(blk, succ, src, dst):
+    """cheapest way (instructions) from the end of block src to the head of block dst that meets no barrier: [blocks between them]"""
+    bar = [any(o == "s_barrier" for o, _ in b) for b in blk]
+    dist, prev, heap = {}, {}, [(0, s, src) for s in succ[src]]
+    while heap:
+        d, k, p = heapq.heappop(heap)
+        if k in dist or (bar[k] and k != dst):
+            continue
+        dist[k], prev[k] = d, p
+        if k == dst:
+            path, n = [], prev[k]
+            while n != src:
+                path.append(n)
+                n = prev[n]
+            return path[::-1]
+        for s in succ[k]:
+            heapq.heappush(heap, (d + len(blk[k]), s, k))
+    return None
+
+
+def taken(seq):
+    """branches TAKEN along a sequence of blocks: transitions that are not a fall-through into the next block in address order"""
+    return sum(1 for a, b in zip(seq, seq[1:]) if b != a + 1)
+
+
 def row(name, c):
     return (f"{name:22s} {c['valu']:5d} {c['full']:5d} {c['half']:5d} {c['quarter']:5d} {c['lds']:4d} {c['salu']:5d} {c['cycles']:8.1f}")
 
@@ -157,6 +196,20 @@ def main():
     print(row("  else", rest))
     print("      else VALU: " + " ".join(o for o, _ in rest_ops if o.startswith("v_")))
     print(f"      else: {rest['vmem']} buffer instructions, {sum(1 for o, _ in rest_ops if o == 's_waitcnt')} s_waitcnt")
+    # (a') the run loop (degree classes up to 8): the node is instantiated twice per degree, one body per half of the loop unrolled by two
+    # over ping-pong record registers; a trip is one node and the way to the other one (the cheapest one: no barrier, not a frame's first sweep)
+    nodes = find_nodes(blk, a.deg)
+    if len(nodes) == 2:
+        print(f"(a') run loop, degree {a.deg}: two halves (node -> way to the other node)")
+        for h, ((ka, ia), (kb, ib)) in enumerate((nodes, nodes[::-1])):
+            way = cheapest_path(blk, succ, ka, kb)
+            if way is None:
+                print(f"  half {'AB'[h]}: no barrier-free way from {names.get(ka, ka)} to {names.get(kb, kb)}")
+                continue
+            ops = blk[ka][ia:] + [op for k in way for op in blk[k]] + blk[kb][:ib]
+            c = span_tally(ops)
+            print(row(f"  half {'AB'[h]}", c) + f"   branches taken {taken([ka] + way + [kb])}, {c['vmem']} buffer instructions, "
+                  f"{sum(1 for o, _ in ops if o == 's_waitcnt')} s_waitcnt; blocks " + " ".join(names.get(k, f"+{k}") for k in [ka] + way + [kb]))
     # (b) the chain node: two barriers with a float walk (v_med3_f32) between them, DEG - 2 + 3 LLR byte reads in front
     flat = [op for b in blk for op in b]
     bars = [i for i, (o, _) in enumerate(flat) if o == "s_barrier"]
