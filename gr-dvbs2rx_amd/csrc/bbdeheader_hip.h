@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <string>
+#include "device_stage.h"
 
 namespace dvbs2 {
 
@@ -28,12 +29,9 @@ struct BbdhPlan { // per BBFRAME of a call, written by the scan
     int out_base;  // index of its first packet in the output
 };
 
-class BbDeheaderHip {
+class BbDeheaderHip : public DeviceStage {
 public:
     BbDeheaderHip(int kbch_bits, int max_frames, int device);
-    ~BbDeheaderHip();
-    bool ok() const { return err_.empty(); }
-    const std::string& error() const { return call_err_.empty() ? err_ : call_err_; }
     int kbch_bytes() const { return kbch_bytes_; }
     int max_dfl() const { return max_dfl_; }
     int max_frames() const { return max_frames_; }
@@ -47,11 +45,10 @@ public:
     int reset(hipStream_t stream);                 // the block as constructed: not synched, no partial packet, counters zero
 
 private:
-    int kbch_bytes_, max_dfl_, max_frames_, device_;
+    int kbch_bytes_, max_dfl_, max_frames_;
     BbdhState* d_state_ = nullptr;
     BbdhPlan* d_plan_ = nullptr;
     int* d_hdr_ = nullptr; // per frame: valid | dfl/8 << 1 | syncd/8 << 16
-    std::string err_, call_err_;
 };
 
 } // namespace dvbs2

@@ -9,7 +9,6 @@
 // The byte work is tiny next to the decoders in front of it (kbch / 8 bytes per frame in, about as many out): no tuning beyond
 // keeping everything on the device and asynchronous.
 #include "bbdeheader_hip.h"
-#include "device_guard.h"
 
 namespace dvbs2 {
 
@@ -211,65 +210,49 @@ __global__ void bbdh_save_partial_kernel(const uint8_t* __restrict__ in, int n_f
 }
 
 BbDeheaderHip::BbDeheaderHip(int kbch_bits, int max_frames, int device)
-    : kbch_bytes_(kbch_bits / 8), max_dfl_(kbch_bits - 80), max_frames_(max_frames), device_(device)
+    : DeviceStage(device), kbch_bytes_(kbch_bits / 8), max_dfl_(kbch_bits - 80), max_frames_(max_frames)
 {
     if (kbch_bits < 88 || kbch_bits % 8 != 0 || kbch_bits - 80 > 0xffff) { err_ = "unsupported BCH message length"; return; }
     if (max_frames_ < 1 || max_frames_ > 65535) { err_ = "max_frames must be in 1..65535"; return; }
     if (max_out_bytes_per_frame() / kTsLen > 64) { err_ = "more than 64 packets per BBFRAME"; return; }
     DeviceGuard guard(device_);
     if (!guard.ok) { err_ = "hipSetDevice failed"; return; }
-    hipError_t e = hipMalloc(&d_state_, sizeof(BbdhState));
+    hipError_t e = alloc(&d_state_, 1);
     if (e == hipSuccess) e = hipMemset(d_state_, 0, sizeof(BbdhState));
-    if (e == hipSuccess) e = hipMalloc(&d_plan_, (size_t)(max_frames_ + 1) * sizeof(BbdhPlan));
-    if (e == hipSuccess) e = hipMalloc(&d_hdr_, (size_t)max_frames_ * 4);
-    if (e != hipSuccess) err_ = std::string("bbdeheader buffers: ") + hipGetErrorString(e);
-}
-
-BbDeheaderHip::~BbDeheaderHip()
-{
-    DeviceGuard guard(device_);
-    (void)hipFree(d_state_); (void)hipFree(d_plan_); (void)hipFree(d_hdr_);
+    if (e == hipSuccess) e = alloc(&d_plan_, (size_t)max_frames_ + 1);
+    if (e == hipSuccess) e = alloc(&d_hdr_, max_frames_);
+    hip_ok(e, "bbdeheader buffers", err_);
 }
 
 int BbDeheaderHip::process_device(const uint8_t* d_bbframes, int n_frames, uint8_t* d_out, hipStream_t stream)
 {
-    if (!ok()) return -1;
-    call_err_.clear();
+    Entry on(*this);
+    if (!on.ok) return -1;
     if (n_frames < 0 || n_frames > max_frames_) { call_err_ = "n_frames exceeds max_frames"; return -1; }
-    DeviceGuard guard(device_);
-    if (!guard.ok) { call_err_ = "hipSetDevice failed"; return -1; }
     hipLaunchKernelGGL(bbdh_header_kernel, dim3((n_frames + 255) / 256 + (n_frames == 0)), dim3(256), 0, stream, d_bbframes, n_frames, kbch_bytes_, max_dfl_, d_hdr_);
     hipLaunchKernelGGL(bbdh_scan_kernel, dim3(1), dim3(kScanThreads), 0, stream, d_hdr_, n_frames, kbch_bytes_, d_state_, d_plan_);
     if (n_frames > 0) {
         hipLaunchKernelGGL(bbdh_packet_kernel, dim3(n_frames), dim3(64), 0, stream, d_bbframes, n_frames, kbch_bytes_, d_state_, d_plan_, d_out);
         hipLaunchKernelGGL(bbdh_save_partial_kernel, dim3(1), dim3(192), 0, stream, d_bbframes, n_frames, kbch_bytes_, d_state_, d_plan_);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { call_err_ = std::string("bbdeheader launch: ") + hipGetErrorString(e); return -1; }
-    return 0;
+    return launched("bbdeheader launch");
 }
 
 int BbDeheaderHip::state(BbdhState* out, hipStream_t stream)
 {
-    if (!ok()) return -1;
-    call_err_.clear();
-    DeviceGuard guard(device_);
-    if (!guard.ok) { call_err_ = "hipSetDevice failed"; return -1; }
+    Entry on(*this);
+    if (!on.ok) return -1;
     hipError_t e = hipMemcpyAsync(out, d_state_, sizeof(BbdhState), hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) { call_err_ = std::string("bbdeheader state: ") + hipGetErrorString(e); return -1; }
-    return 0;
+    return hip_ok(e, "bbdeheader state", call_err_) ? 0 : -1;
 }
 
 int BbDeheaderHip::reset(hipStream_t stream)
 {
-    if (!ok()) return -1;
-    call_err_.clear();
-    DeviceGuard guard(device_);
-    if (!guard.ok) { call_err_ = "hipSetDevice failed"; return -1; }
+    Entry on(*this);
+    if (!on.ok) return -1;
     hipError_t e = hipMemsetAsync(d_state_, 0, sizeof(BbdhState), stream);
-    if (e != hipSuccess) { call_err_ = std::string("bbdeheader reset: ") + hipGetErrorString(e); return -1; }
-    return 0;
+    return hip_ok(e, "bbdeheader reset", call_err_) ? 0 : -1;
 }
 
 } // namespace dvbs2

@@ -4,6 +4,7 @@
 #include <cstdint>
 #include <string>
 #include <vector>
+#include "device_stage.h"
 
 namespace dvbs2 {
 
@@ -21,13 +22,10 @@ struct BchCode {
     bool build(int m, uint32_t prim_poly, int t, int n, std::string* err);
 };
 
-class BchDecoderHip {
+class BchDecoderHip : public DeviceStage {
 public:
     BchDecoderHip(int m, uint32_t prim_poly, int t, int n, int max_frames, int device);
     ~BchDecoderHip();
-    bool ok() const { return err_.empty(); }
-    // ok() reports the constructor; a failed call leaves its text in error() without disabling the handle
-    const std::string& error() const { return call_err_.empty() ? err_ : call_err_; }
     const BchCode& code() const { return code_; }
     int max_frames() const { return max_frames_; }
     // DEVICE pointers. d_cw: n_frames * n/8 bytes (first bit = x^(n-1), reference lib/bch.cc:436-449);
@@ -46,7 +44,7 @@ public:
 
 private:
     BchCode code_;
-    int max_frames_, device_;
+    int max_frames_;
     uint16_t* d_antilog_ = nullptr;
     uint16_t* d_log_ = nullptr;
     uint16_t* d_quad_ = nullptr;
@@ -63,8 +61,6 @@ private:
     static constexpr int kTrack = 8;
     InFlight track_[kTrack];   // the last kTrack calls: stream, syndrome range, completion event
     int track_next_ = 0;
-    std::string err_;      // set by the constructor only
-    std::string call_err_; // last failed call
 };
 
 // the BBFRAME energy-dispersal sequence as packed bytes (host), lib/bbdescrambler_bb_impl.cc:51-65

@@ -17,7 +17,6 @@
 //               exponents [s+1, n+s] (lib/bch.cc:376-384, lib/gf.cc:376-401), all threads, LDS gathers.
 //   correction  message bits only, network bit order (lib/bch.cc:429-452).
 #include "bch_hip.h"
-#include "device_guard.h"
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -458,20 +457,19 @@ __global__ __launch_bounds__(kBchThreads) void bch_decode_kernel(BchArgs a)
 }
 
 BchDecoderHip::BchDecoderHip(int m, uint32_t prim_poly, int t, int n, int max_frames, int device)
-    : max_frames_(max_frames), device_(device)
+    : DeviceStage(device), max_frames_(max_frames)
 {
     if (!code_.build(m, prim_poly, t, n, &err_)) return;
     if (code_.n % 8 || code_.k % 8) { err_ = "u8 array messages are only supported for n and k multiple of 8."; return; } // lib/bch.cc:19-24
     if (max_frames_ < 1 || max_frames_ > 65535) { err_ = "max_frames must be in 1..65535 (frames are one launch dimension)"; return; }
-#define HIP_OK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { err_ = std::string(#x) + ": " + hipGetErrorString(e_); return; } } while (0)
     DeviceGuard dev_guard(device_); // restored on return (device_guard.h)
     if (!dev_guard.ok) { err_ = "hipSetDevice failed"; return; }
     hipDeviceProp_t pr;
     HIP_OK(hipGetDeviceProperties(&pr, device_));
     n_cus_ = pr.multiProcessorCount;
-    HIP_OK(hipMalloc(&d_antilog_, code_.antilog.size() * 2));
-    HIP_OK(hipMalloc(&d_log_, code_.log.size() * 2));
-    HIP_OK(hipMalloc(&d_quad_, code_.quad.size() * 2));
+    HIP_OK_AS("hipMalloc(&d_antilog_, code_.antilog.size() * 2)", alloc(&d_antilog_, code_.antilog.size()));
+    HIP_OK_AS("hipMalloc(&d_log_, code_.log.size() * 2)", alloc(&d_log_, code_.log.size()));
+    HIP_OK_AS("hipMalloc(&d_quad_, code_.quad.size() * 2)", alloc(&d_quad_, code_.quad.size()));
     HIP_OK(hipMemcpy(d_antilog_, code_.antilog.data(), code_.antilog.size() * 2, hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(d_log_, code_.log.data(), code_.log.size() * 2, hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(d_quad_, code_.quad.data(), code_.quad.size() * 2, hipMemcpyHostToDevice));
@@ -479,7 +477,7 @@ BchDecoderHip::BchDecoderHip(int m, uint32_t prim_poly, int t, int n, int max_fr
         std::vector<uint16_t> hc((size_t)code_.n * 16, 0);
         for (int e = 0; e < code_.n; e++)
             for (int u = 0; u < code_.t; u++) hc[(size_t)e * 16 + u] = code_.antilog[(uint32_t)(((uint64_t)(2 * u + 1) * (uint64_t)e) % (uint64_t)code_.P)];
-        HIP_OK(hipMalloc(&d_hcol_, hc.size() * 2));
+        HIP_OK_AS("hipMalloc(&d_hcol_, hc.size() * 2)", alloc(&d_hcol_, hc.size()));
         HIP_OK(hipMemcpy(d_hcol_, hc.data(), hc.size() * 2, hipMemcpyHostToDevice));
     }
     {   // ... and by rows as 0 / 1 bytes for the batched product: row 16 u + b = bit b of alpha^((2u+1) e), column = stream position
@@ -495,15 +493,14 @@ BchDecoderHip::BchDecoderHip(int m, uint32_t prim_poly, int t, int n, int max_fr
                 for (int b = 0; b < code_.m; b++) hr[(size_t)(16 * u + b) * synd_kp_ + p] = (int8_t)((v >> b) & 1u);
             }
         }
-        HIP_OK(hipMalloc(&d_hrows_, hr.size()));
+        HIP_OK_AS("hipMalloc(&d_hrows_, hr.size())", alloc(&d_hrows_, hr.size()));
         HIP_OK(hipMemcpy(d_hrows_, hr.data(), hr.size(), hipMemcpyHostToDevice));
-        HIP_OK(hipMalloc(&d_synd_, (size_t)max_frames_ * 32));
+        HIP_OK_AS("hipMalloc(&d_synd_, (size_t)max_frames_ * 32)", alloc(&d_synd_, (size_t)max_frames_ * 8));
         synd_min_frames_ = 32;
         if (const char* ev = getenv("DVBS2_BCH_SYND_MIN")) synd_min_frames_ = std::max(1, atoi(ev)); // tests: 1 = always the product, 1000000 = never
     }
     lds_bytes_ = (((size_t)code_.P * 2 + 15) & ~(size_t)15) + kBchWorkWords * 4 + (size_t)((code_.n / 8 + 15) & ~15);
     HIP_OK(hipFuncSetAttribute((const void*)bch_decode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes_));
-#undef HIP_OK
 }
 
 // lib/bbdescrambler_bb_impl.cc:51-65: PRBS 1 + x^14 + x^15, register loaded with 100101010000000, MSB-first bytes.
@@ -523,14 +520,12 @@ void bb_derandomise_sequence(uint8_t* seq, int n_bytes)
 
 int BchDecoderHip::set_descramble(bool enable)
 {
-    if (!ok()) return -1;
-    call_err_.clear();
-    DeviceGuard dev_guard(device_);
-    if (!dev_guard.ok) { call_err_ = "hipSetDevice failed"; return -1; }
+    Entry on(*this);
+    if (!on.ok) return -1;
     if (enable && !d_scramble_) {
         std::vector<uint8_t> seq(code_.k / 8);
         bb_derandomise_sequence(seq.data(), (int)seq.size());
-        if (hipMalloc(&d_scramble_, seq.size()) != hipSuccess ||
+        if (alloc(&d_scramble_, seq.size()) != hipSuccess ||
             hipMemcpy(d_scramble_, seq.data(), seq.size(), hipMemcpyHostToDevice) != hipSuccess) { call_err_ = "descramble sequence upload failed"; return -1; }
     }
     descramble_ = enable;
@@ -539,21 +534,17 @@ int BchDecoderHip::set_descramble(bool enable)
 
 BchDecoderHip::~BchDecoderHip()
 {
-    DeviceGuard dev_guard(device_);
-    (void)hipFree(d_scramble_);
-    (void)hipFree(d_antilog_); (void)hipFree(d_log_); (void)hipFree(d_quad_); (void)hipFree(d_hcol_); (void)hipFree(d_hrows_); (void)hipFree(d_synd_);
+    DeviceGuard dev_guard(device_); // (the device buffers: ~DeviceStage)
     for (InFlight& t : track_) if (t.done) (void)hipEventDestroy(t.done);
 }
 
 int BchDecoderHip::decode_device(const uint8_t* d_cw, int n_frames, uint8_t* d_msg, int32_t* d_corr, hipStream_t stream,
                                  const uint8_t* d_llr_state, int llr_stride, int frame_base)
 {
-    if (!ok()) return -1;
-    call_err_.clear();
+    Entry on(*this);
+    if (!on.ok) return -1;
     if (n_frames < 0 || frame_base < 0 || frame_base + n_frames > max_frames_) { call_err_ = "n_frames exceeds max_frames"; return -1; }
     if (n_frames == 0) return 0;
-    DeviceGuard dev_guard(device_);
-    if (!dev_guard.ok) { call_err_ = "hipSetDevice failed"; return -1; }
     // the syndrome words of [frame_base, frame_base + n_frames) belong to this call until its per-frame kernel has read them: an earlier
     // call on ANOTHER stream that used an overlapping range is waited for on the device (same stream: stream order already does it)
     for (const InFlight& t : track_)
@@ -588,8 +579,7 @@ int BchDecoderHip::decode_device(const uint8_t* d_cw, int n_frames, uint8_t* d_m
     }
     const int grid = std::min(n_frames, std::max(1, n_cus_));
     hipLaunchKernelGGL(bch_decode_kernel, dim3(grid), dim3(kBchThreads), lds_bytes_, stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { call_err_ = std::string("bch kernel launch: ") + hipGetErrorString(e); return -1; }
+    if (launched("bch kernel launch")) return -1;
     {
         InFlight& t = track_[track_next_];
         track_next_ = (track_next_ + 1) % kTrack;

@@ -4,19 +4,17 @@
 #include <cstdint>
 #include <string>
 #include "demap_math.hpp"
+#include "device_stage.h"
 
 namespace dvbs2 {
 
-class DemapperHip {
+class DemapperHip : public DeviceStage {
 public:
     // framesize / rate / constellation: reference enums (dvb_config.h). Mirrors the constructor of
     // xfecframe_demapper_cb_impl (lib/xfecframe_demapper_cb_impl.cc:27-91): frame length by framesize,
     // QPSK or 8PSK ("Unsupported constellation" otherwise, :70-72), 8PSK column order by rate (:50-69). Beyond the reference:
     // 16APSK and 32APSK with the DVB-S2 rates of EN 302 307-1 table 9 / 10, normal and short frames (notes/apsk_demap.md).
     DemapperHip(int framesize, int rate, int constellation, int max_frames, int device);
-    bool ok() const { return err_.empty(); }
-    // ok() reports the constructor; a failed call leaves its text in error() without disabling the handle
-    const std::string& error() const { return call_err_.empty() ? err_ : call_err_; }
     int n_llr() const { return n_llr_; }
     int n_mod() const { return n_mod_; }
     int n_syms() const { return n_llr_ / n_mod_; }
@@ -37,9 +35,7 @@ public:
 private:
     bool is_apsk() const { return n_mod_ >= 4; }
     ApskTable apsk_{}; // 16APSK / 32APSK: the points of this rate, handed to the kernels by value
-    int n_llr_ = 0, n_mod_ = 0, order_ = 0, constellation_ = 0, max_frames_ = 0, device_ = 0;
-    std::string err_;      // set by the constructor only
-    std::string call_err_; // last failed call
+    int n_llr_ = 0, n_mod_ = 0, order_ = 0, constellation_ = 0, max_frames_ = 0;
 };
 
 // The 2^n_mod points of 16APSK (DVBS2_MOD_16APSK) / 32APSK for a DVB-S2 code rate as interleaved (re, im), entry i = label i, Es = 1.

@@ -13,7 +13,6 @@
 #include <cmath>
 #include "../../include/dvbs2_fec_hip.h"
 
-#include "device_guard.h"
 namespace dvbs2 {
 
 __global__ void demap_qpsk_kernel(const float4* __restrict__ syms, const float* __restrict__ n0, int n0_count,
@@ -218,7 +217,7 @@ bool apsk_points(int constellation, int rate, float* re_im)
 }
 
 DemapperHip::DemapperHip(int framesize, int rate, int constellation, int max_frames, int device)
-    : constellation_(constellation), max_frames_(max_frames), device_(device)
+    : DeviceStage(device), constellation_(constellation), max_frames_(max_frames)
 {
     n_llr_ = framesize == DVBS2_FECFRAME_NORMAL ? 64800 : framesize == DVBS2_FECFRAME_MEDIUM ? 32400 : 16200;
     if (constellation == DVBS2_MOD_QPSK) n_mod_ = 2;
@@ -242,12 +241,10 @@ DemapperHip::DemapperHip(int framesize, int rate, int constellation, int max_fra
 
 int DemapperHip::soft_device(const float* d_syms, int n_frames, const float* d_n0, int n0_count, int8_t* d_llr, hipStream_t stream)
 {
-    if (!ok()) return -1;
-    call_err_.clear();
+    Entry on(*this);
+    if (!on.ok) return -1;
     if (n_frames < 0 || n_frames > max_frames_) { call_err_ = "n_frames exceeds max_frames"; return -1; }
     if (n_frames == 0) return 0;
-    DeviceGuard dev_guard(device_);
-    if (!dev_guard.ok) { call_err_ = "hipSetDevice failed"; return -1; }
     if (constellation_ == DVBS2_MOD_QPSK) {
         const int quads = n_llr_ / 4;
         hipLaunchKernelGGL(demap_qpsk_kernel, dim3((quads + 255) / 256, n_frames), dim3(256), 0, stream,
@@ -267,9 +264,7 @@ int DemapperHip::soft_device(const float* d_syms, int n_frames, const float* d_n
         hipLaunchKernelGGL(demap_8psk_kernel, dim3((quads + 255) / 256, n_frames), dim3(256), 0, stream,
                            reinterpret_cast<const float4*>(d_syms), d_n0, n0_count, reinterpret_cast<uint32_t*>(d_llr), quads, ra0, ra1, ra2, rr, ri);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { call_err_ = std::string("demap kernel launch: ") + hipGetErrorString(e); return -1; }
-    return 0;
+    return launched("demap kernel launch");
 }
 
 DemapFused DemapperHip::fused(const float* d_syms, const float* d_n0, int n0_count) const
@@ -287,12 +282,10 @@ DemapFused DemapperHip::fused(const float* d_syms, const float* d_n0, int n0_cou
 
 int DemapperHip::snr_device(const float* d_syms, const int8_t* d_ref_llr, int n_frames, float* d_snr, hipStream_t stream)
 {
-    if (!ok()) return -1;
-    call_err_.clear();
+    Entry on(*this);
+    if (!on.ok) return -1;
     if (n_frames < 0 || n_frames > max_frames_) { call_err_ = "n_frames exceeds max_frames"; return -1; }
     if (n_frames == 0) return 0;
-    DeviceGuard dev_guard(device_);
-    if (!dev_guard.ok) { call_err_ = "hipSetDevice failed"; return -1; }
     const float rr = (float)std::cos(-M_PI / 8), ri = (float)std::sin(-M_PI / 8);
     const int rows = n_syms();
     int ra0 = 0, ra1 = rows, ra2 = 2 * rows;
@@ -305,9 +298,7 @@ int DemapperHip::snr_device(const float* d_syms, const int8_t* d_ref_llr, int n_
     else
         hipLaunchKernelGGL(demap_snr_kernel, dim3(n_frames), dim3(256), 0, stream,
                            reinterpret_cast<const float2*>(d_syms), d_ref_llr, d_snr, rows, constellation_, ra0, ra1, ra2, rr, ri);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { call_err_ = std::string("snr kernel launch: ") + hipGetErrorString(e); return -1; }
-    return 0;
+    return launched("snr kernel launch");
 }
 
 } // namespace dvbs2

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <string>
+#include "device_stage.h"
 #include "ldpc_layout.h"
 #include "ldpc_schedule.h"
 #include "demap_math.hpp"
@@ -12,16 +13,13 @@ namespace dvbs2 {
 // per-CU wave-pattern counters of the one-frame sweep kernels: one device array per device key (ldpc_hip.hip)
 int* cu_slot_table(int device_key, std::string* err);
 
-class LdpcDecoderHip {
+class LdpcDecoderHip : public DeviceStage {
 public:
     // group_size G: frames [G*g, G*g+G) share one iteration count, exactly like one SIMD batch of the
     // reference (lib/ldpc_decoder_bb_impl.cc:406-410, lib/ldpc_decoder/layered_decoder.hh:153). G = 1
     // stops every frame on its own.
     LdpcDecoderHip(const LdpcTableDesc* table, int out_bits_message, int group_size, int max_frames, int device);
     ~LdpcDecoderHip();
-    bool ok() const { return err_.empty(); }
-    // ok() reports the constructor; a failed call leaves its text in error() without disabling the handle
-    const std::string& error() const { return call_err_.empty() ? err_ : call_err_; }
 
     int N() const { return sched_.N; }
     int K() const { return sched_.K; }
@@ -75,7 +73,7 @@ public:
 
 private:
     LdpcSchedule sched_;
-    int out_bits_message_, G_, max_frames_, device_;
+    int out_bits_message_, G_, max_frames_;
     int words_per_check_ = 0; // message dwords per check (4 int8 messages per dword)
     int dmax_ = 0;            // kernel variant: handles check degrees dmax-7 .. dmax (8, 12, ..., 32)
     uint32_t* d_recs_ = nullptr;  // per-layer records (ldpc_plan.cpp); kRecHeaderWords of header in front of them (d_recs_alloc_)
@@ -110,8 +108,6 @@ private:
     double prof_ms_ = 0;
     int prof_launches_ = 0;
     hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
-    std::string err_;      // set by the constructor only
-    std::string call_err_; // last failed call
 };
 
 } // namespace dvbs2

@@ -18,7 +18,6 @@
 #include "ldpc_hip.h"
 #include "ldpc_plan.h"
 #include "ldpc_launch.h"
-#include "device_guard.h"
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -27,9 +26,6 @@
 #include <vector>
 
 namespace dvbs2 {
-
-#define HIP_OK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { err_ = std::string(#x) + ": " + hipGetErrorString(e_); return; } } while (0)
-#define HIP_RET(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { call_err_ = std::string(#x) + ": " + hipGetErrorString(e_); return -1; } } while (0)
 
 // Per-group stopping rule of one reference SIMD batch: while (bad(any lane) && --trials >= 0) update(all lanes)
 // (layered_decoder.hh:153). After a pass, every frame f sits at iters[f] updates with good[f] known there.
@@ -124,7 +120,7 @@ const SweepOps& sweep_ops(bool pr, int dmax)
 } // namespace
 
 LdpcDecoderHip::LdpcDecoderHip(const LdpcTableDesc* table, int out_bits_message, int group_size, int max_frames, int device)
-    : out_bits_message_(out_bits_message), G_(group_size), max_frames_(max_frames), device_(device)
+    : DeviceStage(device), out_bits_message_(out_bits_message), G_(group_size), max_frames_(max_frames)
 {
     if (!compile_ldpc_schedule(table, &sched_)) { err_ = "unknown or inconsistent LDPC table"; return; }
     if (G_ < 1 || max_frames_ < 1 || max_frames_ > 65535) { err_ = "bad group_size/max_frames (max_frames 1..65535: frames are one launch dimension)"; return; }
@@ -138,27 +134,27 @@ LdpcDecoderHip::LdpcDecoderHip(const LdpcTableDesc* table, int out_bits_message,
 
     DeviceGuard dev_guard(device_); // the caller's current device is restored when the constructor returns (device_guard.h)
     if (!dev_guard.ok) { err_ = "hipSetDevice failed"; return; }
-    HIP_OK(hipMalloc(&d_recs_alloc_, (plan.recs.size() + kRecHeaderWords) * 4)); // header (group-synchronous stop, filled below) + records
+    HIP_OK_AS("hipMalloc(&d_recs_alloc_, (plan.recs.size() + kRecHeaderWords) * 4)", alloc(&d_recs_alloc_, plan.recs.size() + kRecHeaderWords)); // header (group-synchronous stop, filled below) + records
     d_recs_ = d_recs_alloc_ + kRecHeaderWords;
     HIP_OK(hipMemcpy(d_recs_, plan.recs.data(), plan.recs.size() * 4, hipMemcpyHostToDevice));
-    HIP_OK(hipMalloc(&d_wrecs_, plan.wrecs.size() * 4));
+    HIP_OK_AS("hipMalloc(&d_wrecs_, plan.wrecs.size() * 4)", alloc(&d_wrecs_, plan.wrecs.size()));
     HIP_OK(hipMemcpy(d_wrecs_, plan.wrecs.data(), plan.wrecs.size() * 4, hipMemcpyHostToDevice));
-    HIP_OK(hipMalloc(&d_state_, (size_t)max_frames_ * sched_.N));
-    HIP_OK(hipMalloc(&d_msgs_, (size_t)max_frames_ * sched_.q * words_per_check_ * kMsgStride * 4));
-    HIP_OK(hipMalloc(&d_iters_, (size_t)max_frames_ * 4));
-    HIP_OK(hipMalloc(&d_good_, (size_t)max_frames_ * 4));
-    HIP_OK(hipMalloc(&d_target_, (size_t)max_frames_ * 4));
+    HIP_OK_AS("hipMalloc(&d_state_, (size_t)max_frames_ * sched_.N)", alloc(&d_state_, (size_t)max_frames_ * sched_.N));
+    HIP_OK_AS("hipMalloc(&d_msgs_, (size_t)max_frames_ * sched_.q * words_per_check_ * kMsgStride * 4)", alloc(&d_msgs_, (size_t)max_frames_ * sched_.q * words_per_check_ * kMsgStride));
+    HIP_OK_AS("hipMalloc(&d_iters_, (size_t)max_frames_ * 4)", alloc(&d_iters_, (size_t)max_frames_));
+    HIP_OK_AS("hipMalloc(&d_good_, (size_t)max_frames_ * 4)", alloc(&d_good_, (size_t)max_frames_));
+    HIP_OK_AS("hipMalloc(&d_target_, (size_t)max_frames_ * 4)", alloc(&d_target_, (size_t)max_frames_));
     if (gsync_on_) { // group-synchronous stop (ldpc_plan.cpp, group_decide): its words and the header in front of the records
-        HIP_OK(hipMalloc(&d_gsync_, (size_t)(max_frames_ + 64) * 4)); // one status word per frame (group_decide)
+        HIP_OK_AS("hipMalloc(&d_gsync_, (size_t)(max_frames_ + 64) * 4)", alloc(&d_gsync_, (size_t)(max_frames_ + 64))); // one status word per frame (group_decide)
         const unsigned long long a = (unsigned long long)d_iters_, b = (unsigned long long)d_gsync_;
         const uint32_t hd[kRecHeaderWords] = { (uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32), (uint32_t)G_, (uint32_t)plan.spin_max, 0, 0 };
         HIP_OK(hipMemcpy(d_recs_alloc_, hd, sizeof(hd), hipMemcpyHostToDevice));
     }
-    HIP_OK(hipMalloc(&d_flag_, 4 * kSlots));
+    HIP_OK_AS("hipMalloc(&d_flag_, 4 * kSlots)", alloc(&d_flag_, kSlots));
     HIP_OK(hipHostMalloc(&h_flag_, 4 * kSlots));
     HIP_OK(hipEventCreate(&ev0_));
     HIP_OK(hipEventCreate(&ev1_));
-    if (ov.timing) { HIP_OK(hipMalloc(&d_tdbg_, ((size_t)max_frames_ * 48 + 512) * 8)); HIP_OK(hipMemset(d_tdbg_, 0, ((size_t)max_frames_ * 48 + 512) * 8)); }
+    if (ov.timing) { HIP_OK_AS("hipMalloc(&d_tdbg_, ((size_t)max_frames_ * 48 + 512) * 8)", alloc(&d_tdbg_, (size_t)max_frames_ * 48 + 512)); HIP_OK(hipMemset(d_tdbg_, 0, ((size_t)max_frames_ * 48 + 512) * 8)); }
     if (is_solo(build_)) {
         // The per-CU pattern counters of the one-frame builds are shared by ALL handles of a device: two workgroups on a CU take
         // complementary wave patterns through them, whichever launch (handle, stream) they belong to. With one array per handle two
@@ -179,9 +175,7 @@ LdpcDecoderHip::LdpcDecoderHip(const LdpcTableDesc* table, int out_bits_message,
 
 LdpcDecoderHip::~LdpcDecoderHip()
 {
-    DeviceGuard dev_guard(device_);
-    (void)hipFree(d_recs_alloc_); (void)hipFree(d_wrecs_); (void)hipFree(d_state_); (void)hipFree(d_msgs_);
-    (void)hipFree(d_iters_); (void)hipFree(d_good_); (void)hipFree(d_target_); (void)hipFree(d_flag_); (void)hipFree(d_gsync_);
+    DeviceGuard dev_guard(device_); // (the device buffers: ~DeviceStage)
     if (h_flag_) (void)hipHostFree(h_flag_);
     if (ev0_) (void)hipEventDestroy(ev0_);
     if (ev1_) (void)hipEventDestroy(ev1_);
@@ -284,8 +278,8 @@ int LdpcDecoderHip::enqueue(const int8_t* d_llr_in, int n_frames, int max_trials
     p.bits = d_bits_out; p.llr_out = d_llr_out; p.ret = d_ret; p.stream = stream;
     h_flag_[slot] = 0;
     if (n_frames == 0) { release.armed = false; return 0; }
-    DeviceGuard dev_guard(device_);
-    if (!dev_guard.ok) { call_err_ = "hipSetDevice failed"; return -1; }
+    Entry on(*this);
+    if (!on.ok) return -1;
     if (dm && dm->mode && pr_) { call_err_ = "this sweep kernel does not demap while loading"; return -1; }
     release.launched = true;
     launch_sweep(d_llr_in, false, 1, n_frames, max_trials, frame_base, stream, dm);
@@ -312,8 +306,8 @@ int LdpcDecoderHip::finish(int slot)
     if (!p.active) return 0;
     p.active = false;
     if (p.n_frames == 0) return 0;
-    DeviceGuard dev_guard(device_);
-    if (!dev_guard.ok) { call_err_ = "hipSetDevice failed"; return -1; }
+    Entry on(*this);
+    if (!on.ok) return -1;
     HIP_RET(hipStreamSynchronize(p.stream));
     if (h_flag_[slot] == 0) return 0;
     struct Drain { hipStream_t st; bool armed = true; ~Drain() { if (armed) (void)hipStreamSynchronize(st); } } drain{ p.stream }; // a failing round leaves nothing in flight

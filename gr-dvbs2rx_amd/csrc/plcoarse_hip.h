@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <string>
+#include "device_stage.h"
 #include "plsync_hip.h"
 
 namespace dvbs2 {
@@ -43,17 +44,15 @@ struct PlCoarseOut {
     int32_t* new_est = nullptr;   // 1 on the last frame of a window
 };
 
-class PlCoarseHip {
+class PlCoarseHip : public DeviceStage {
 public:
+    // the ranges of the arguments are checked by dvbs2_plcoarse_create, which alone constructs this
     PlCoarseHip(int period, int plsc_or_minus1, int max_frames, int device);
-    ~PlCoarseHip();
-    bool ok() const { return err_.empty(); }
-    const std::string& error() const { return call_err_.empty() ? err_ : call_err_; }
     int max_frames() const { return max_frames_; }
     int fixed_plsc() const { return fixed_plsc_; }
     int reset();
     // DEVICE pointers. Frame f starts at d_plframes + 2 * f * stride_syms floats; d_plsc: one byte per frame, or null for
-    // the handle's fixed PLSC
+    // the handle's fixed PLSC (the caller has checked that one of the two is there and that stride_syms >= 90)
     int frames_device(const float* d_plframes, int64_t stride_syms, const uint8_t* d_plsc, int n_frames, const PlCoarseOut& out,
                       hipStream_t stream);
     // d_syms[0] has absolute index `base`; record f names the header at sof_index - base and its PLSC. A record whose 90
@@ -64,12 +63,11 @@ public:
 private:
     int launch(const float2* x, int64_t stride, const uint8_t* plsc, const PlSyncFrame* rec, int n_syms, int64_t base, int n_frames,
                const PlCoarseOut& out, hipStream_t stream);
-    int period_, fixed_plsc_, max_frames_, device_;
+    int period_, fixed_plsc_, max_frames_;
     uint64_t* d_cw_ = nullptr;   // 128 scrambled PLSC codewords
     float* d_w_ = nullptr;       // 89 + 25 window weights
     float2* d_r_ = nullptr;      // max_frames * kPlcoarseRecord
     PlCoarseState* d_state_ = nullptr;
-    std::string err_, call_err_;
 };
 
 } // namespace dvbs2

@@ -4,7 +4,6 @@
 #include <cstring>
 #include <new>
 
-#include "device_guard.h"
 namespace dvbs2 {
 
 int plcoarse_weights(int full, float* w)
@@ -158,37 +157,26 @@ __global__ __launch_bounds__(64) void plcoarse_window_kernel(const float2* __res
 } // namespace
 
 PlCoarseHip::PlCoarseHip(int period, int plsc_or_minus1, int max_frames, int device)
-    : period_(period), fixed_plsc_(plsc_or_minus1), max_frames_(max_frames), device_(device)
+    : DeviceStage(device), period_(period), fixed_plsc_(plsc_or_minus1), max_frames_(max_frames)
 {
-    if (period_ < 1) { err_ = "period must be at least 1"; return; }
-    if (fixed_plsc_ < -1 || fixed_plsc_ > 127) { err_ = "plsc out of range (-1 = not known, 0..127)"; return; }
-    if (max_frames_ < 1 || max_frames_ > (1 << 20)) { err_ = "max_frames out of range (1..1048576)"; return; }
     uint64_t cw[128];
     for (int p = 0; p < 128; p++) cw[p] = plsc_codeword(p) ^ kPlscScrambler;
     float w[89 + 25];
     plcoarse_weights(1, w); plcoarse_weights(0, w + 89);
     DeviceGuard dev_guard(device_);
-    if (!dev_guard.ok || hipMalloc(&d_cw_, sizeof(cw)) != hipSuccess || hipMalloc(&d_w_, sizeof(w)) != hipSuccess ||
-        hipMalloc(&d_r_, (size_t)max_frames_ * kPlcoarseRecord * sizeof(float2)) != hipSuccess ||
-        hipMalloc(&d_state_, sizeof(PlCoarseState)) != hipSuccess ||
+    if (!dev_guard.ok || alloc(&d_cw_, 128) != hipSuccess || alloc(&d_w_, 89 + 25) != hipSuccess ||
+        alloc(&d_r_, (size_t)max_frames_ * kPlcoarseRecord) != hipSuccess || alloc(&d_state_, 1) != hipSuccess ||
         hipMemcpy(d_cw_, cw, sizeof(cw), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_w_, w, sizeof(w), hipMemcpyHostToDevice) != hipSuccess) {
         err_ = "device setup failed"; return;
     }
     if (reset()) { err_ = call_err_; call_err_.clear(); }
 }
 
-PlCoarseHip::~PlCoarseHip()
-{
-    DeviceGuard dev_guard(device_);
-    (void)hipFree(d_cw_); (void)hipFree(d_w_); (void)hipFree(d_r_); (void)hipFree(d_state_);
-}
-
 int PlCoarseHip::reset()
 {
-    call_err_.clear();
-    DeviceGuard dev_guard(device_);
+    Entry on(*this);
     // all zero: no frame counted, empty accumulator, estimate 0, not coarse-corrected (lib/pl_freq_sync.cc:24-31)
-    if (!dev_guard.ok || hipDeviceSynchronize() != hipSuccess || hipMemset(d_state_, 0, sizeof(PlCoarseState)) != hipSuccess) {
+    if (!on.ok || hipDeviceSynchronize() != hipSuccess || hipMemset(d_state_, 0, sizeof(PlCoarseState)) != hipSuccess) {
         call_err_ = "reset of the device state failed"; return -2;
     }
     return 0;
@@ -197,27 +185,20 @@ int PlCoarseHip::reset()
 int PlCoarseHip::launch(const float2* x, int64_t stride, const uint8_t* plsc, const PlSyncFrame* rec, int n_syms, int64_t base, int n_frames,
                         const PlCoarseOut& out, hipStream_t stream)
 {
-    if (!ok()) return -1;
-    call_err_.clear();
+    Entry on(*this);
+    if (!on.ok) return -1;
     if (n_frames < 0 || n_frames > max_frames_) { call_err_ = "n_frames exceeds max_frames"; return -1; }
     if (n_frames == 0) return 0;
-    DeviceGuard dev_guard(device_);
-    if (!dev_guard.ok) { call_err_ = "hipSetDevice failed"; return -1; }
     hipLaunchKernelGGL(plcoarse_autocorr_kernel, dim3(n_frames), dim3(64), 0, stream, x, (long long)stride, plsc, fixed_plsc_ < 0 ? 0 : fixed_plsc_,
                        rec, n_syms, (long long)base, d_cw_, d_r_);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { call_err_ = std::string("plcoarse autocorrelation kernel launch: ") + hipGetErrorString(e); return -1; }
+    if (launched("plcoarse autocorrelation kernel launch")) return -1;
     hipLaunchKernelGGL(plcoarse_window_kernel, dim3(1), dim3(64), 0, stream, d_r_, n_frames, period_, fixed_plsc_ >= 0 ? 1 : 0, d_w_, d_state_, out);
-    e = hipGetLastError();
-    if (e != hipSuccess) { call_err_ = std::string("plcoarse window kernel launch: ") + hipGetErrorString(e); return -1; }
-    return 0;
+    return launched("plcoarse window kernel launch");
 }
 
 int PlCoarseHip::frames_device(const float* d_plframes, int64_t stride_syms, const uint8_t* d_plsc, int n_frames, const PlCoarseOut& out,
                                hipStream_t stream)
 {
-    if (ok() && !d_plsc && fixed_plsc_ < 0) { call_err_ = "a handle without a fixed PLSC needs the per-frame PLSC array"; return -1; }
-    if (ok() && stride_syms < 90) { call_err_ = "stride below the 90 header symbols"; return -1; }
     return launch(reinterpret_cast<const float2*>(d_plframes), stride_syms, d_plsc, nullptr, 0, 0, n_frames, out, stream);
 }
 

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <string>
+#include "device_stage.h"
 #include "plpayload_hip.h"
 #include "plsc_decode.hpp" // kSofWord, kPlscScrambler and the one-wavefront PLSC decoder
 
@@ -35,12 +36,11 @@ struct PlFrameEstimates {
     int32_t* fine_valid = nullptr;
 };
 
-class PlFrameHip {
+class PlFrameHip : public DeviceStage {
 public:
+    // plsc is checked by dvbs2_plframe_create, which alone constructs this: within 0..127 and no reserved MODCOD
     PlFrameHip(int gold_code, int plsc, int max_frames, int device);
     ~PlFrameHip();
-    bool ok() const { return err_.empty(); }
-    const std::string& error() const { return call_err_.empty() ? err_ : call_err_; }
     const PlsInfo& pls() const { return pls_; }
     int max_frames() const { return max_frames_; }
     void set_plsc_mode(int coherent, int soft) { coherent_ = coherent ? 1 : 0; soft_ = soft ? 1 : 0; }
@@ -54,11 +54,10 @@ public:
 
 private:
     PlsInfo pls_{};
-    int max_frames_, device_, coherent_ = 1, soft_ = 1;
+    int max_frames_, coherent_ = 1, soft_ = 1;
     PlPayloadHip* pp_ = nullptr; // owns the Rn table and the payload kernel launch
     uint8_t* d_rank_ = nullptr;  // 128 bytes: position of each codeword in the enabled list, 255 = disabled
     float* d_par_ = nullptr;     // what the payload step reads: plheader_phase | phase_inc | pilot_phase
-    std::string err_, call_err_;
 };
 
 } // namespace dvbs2

@@ -6,7 +6,6 @@
 #include <cmath>
 #include <vector>
 
-#include "device_guard.h"
 namespace dvbs2 {
 
 PlsInfo pls_parse(int plsc)
@@ -166,54 +165,43 @@ __global__ __launch_bounds__(64) void pl_estimate_kernel(const float2* __restric
 
 } // namespace
 
-PlFrameHip::PlFrameHip(int gold_code, int plsc, int max_frames, int device) : max_frames_(max_frames), device_(device)
+PlFrameHip::PlFrameHip(int gold_code, int plsc, int max_frames, int device) : DeviceStage(device), max_frames_(max_frames)
 {
-    if (plsc < 0 || plsc > 127) { err_ = "plsc out of range (0..127)"; return; }
     pls_ = pls_parse(plsc);
-    if (pls_.n_mod == 0 && !pls_.dummy_frame) { err_ = "plsc names a reserved MODCOD (29..31)"; return; }
     pp_ = new (std::nothrow) PlPayloadHip(gold_code, pls_.n_slots, pls_.has_pilots, max_frames, device);
     if (!pp_) { err_ = "out of memory"; return; }
     if (!pp_->ok()) { err_ = pp_->error(); return; }
     DeviceGuard dev_guard(device_);
     const size_t npar = (size_t)max_frames_ * (2 + (pls_.n_pilots ? pls_.n_pilots : 1));
-    if (!dev_guard.ok || hipMalloc(&d_rank_, 128) != hipSuccess || hipMalloc(&d_par_, npar * sizeof(float)) != hipSuccess) {
+    if (!dev_guard.ok || alloc(&d_rank_, 128) != hipSuccess || alloc(&d_par_, npar) != hipSuccess) {
         err_ = "device setup failed"; return;
     }
     if (set_expected_pls(nullptr, 0)) { err_ = call_err_; call_err_.clear(); }
 }
 
-PlFrameHip::~PlFrameHip()
-{
-    DeviceGuard dev_guard(device_);
-    (void)hipFree(d_rank_); (void)hipFree(d_par_);
-    delete pp_;
-}
+PlFrameHip::~PlFrameHip() { delete pp_; }
 
 int PlFrameHip::set_expected_pls(const uint8_t* list, int n)
 {
-    call_err_.clear();
+    Entry on(*this);
     uint8_t rank[128];
     if (!pls_rank_table(list, n, rank)) { call_err_ = "codeword indexes must be within [0, 128)"; return -1; } // lib/reed_muller.cc:48-52
-    DeviceGuard dev_guard(device_);
-    if (!dev_guard.ok || hipMemcpy(d_rank_, rank, 128, hipMemcpyHostToDevice) != hipSuccess) { call_err_ = "copy of the codeword list failed"; return -2; }
+    if (!on.ok || hipMemcpy(d_rank_, rank, 128, hipMemcpyHostToDevice) != hipSuccess) { call_err_ = "copy of the codeword list failed"; return -2; }
     return 0;
 }
 
 int PlFrameHip::run_device(const float* d_plframes, int n_frames, int has_trailing_header, const int32_t* d_coarse_corrected,
                            const float* d_coarse_foffset, float* d_out, const PlFrameEstimates& est, hipStream_t stream)
 {
-    if (!ok()) return -1;
-    call_err_.clear();
+    Entry on(*this);
+    if (!on.ok) return -1;
     if (n_frames < 0 || n_frames > max_frames_) { call_err_ = "n_frames exceeds max_frames"; return -1; }
     if (n_frames == 0) return 0;
-    DeviceGuard dev_guard(device_);
-    if (!dev_guard.ok) { call_err_ = "hipSetDevice failed"; return -1; }
     float* d_hph = d_par_; float* d_inc = d_par_ + max_frames_; float* d_pil = d_par_ + 2 * (size_t)max_frames_;
     hipLaunchKernelGGL(pl_estimate_kernel, dim3(n_frames), dim3(64), 0, stream, reinterpret_cast<const float2*>(d_plframes), pp_->d_rn(),
                        d_rank_, d_coarse_corrected, d_coarse_foffset, plsc_codeword(pls_.plsc) ^ kPlscScrambler, pls_.plframe_len,
                        pls_.n_pilots, n_frames, has_trailing_header ? 1 : 0, coherent_, soft_, d_hph, d_inc, d_pil, est);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { call_err_ = std::string("pl estimate kernel launch: ") + hipGetErrorString(e); return -1; }
+    if (launched("pl estimate kernel launch")) return -1;
     if (!d_out) return 0;
     if (pp_->process_device_strided(d_plframes, pls_.plframe_len, 90, n_frames, d_hph, d_inc, d_coarse_corrected, d_pil, d_out, stream)) {
         call_err_ = pp_->error(); return -1;

@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <string>
 #include <vector>
+#include "device_stage.h"
 
 namespace dvbs2 {
 
@@ -14,13 +15,9 @@ namespace dvbs2 {
 // Rn(i) = 2 z_n((i + 131072) mod (2^18 - 1)) + z_n(i). (The reference reaches the same numbers with register masks.)
 void pl_scrambling_rn(int gold_code, uint8_t* rn, int n);
 
-class PlPayloadHip {
+class PlPayloadHip : public DeviceStage {
 public:
     PlPayloadHip(int gold_code, int n_slots, int has_pilots, int max_frames, int device);
-    ~PlPayloadHip();
-    bool ok() const { return err_.empty(); }
-    // ok() reports the constructor; a failed call leaves its text in error() without disabling the handle
-    const std::string& error() const { return call_err_.empty() ? err_ : call_err_; }
     int n_slots() const { return n_slots_; }
     int n_pilots() const { return n_pilots_; }
     int payload_len() const { return n_slots_ * 90 + n_pilots_ * 36; }
@@ -38,10 +35,8 @@ public:
     const uint8_t* d_rn() const { return d_rn_; } // Rn(i), i < payload_len, on the device
 
 private:
-    int n_slots_, n_pilots_, has_pilots_, max_frames_, device_;
+    int n_slots_, n_pilots_, has_pilots_, max_frames_;
     uint8_t* d_rn_ = nullptr;
-    std::string err_;      // set by the constructor only
-    std::string call_err_; // last failed call
 };
 
 } // namespace dvbs2

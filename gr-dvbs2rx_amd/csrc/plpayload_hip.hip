@@ -2,7 +2,6 @@
 #include "plpayload_hip.h"
 #include <cmath>
 
-#include "device_guard.h"
 namespace dvbs2 {
 
 void pl_scrambling_rn(int gold_code, uint8_t* rn, int n)
@@ -49,7 +48,7 @@ __global__ void pl_payload_kernel(const float2* __restrict__ in, const uint8_t* 
 }
 
 PlPayloadHip::PlPayloadHip(int gold_code, int n_slots, int has_pilots, int max_frames, int device)
-    : n_slots_(n_slots), has_pilots_(has_pilots ? 1 : 0), max_frames_(max_frames), device_(device)
+    : DeviceStage(device), n_slots_(n_slots), has_pilots_(has_pilots ? 1 : 0), max_frames_(max_frames)
 {
     n_pilots_ = has_pilots_ ? ((n_slots_ - 1) >> 4) : 0; // lib/pl_signaling.cc:51
     if (n_slots_ < 36 || n_slots_ > 360) { err_ = "n_slots out of range (36..360)"; return; } // lib/pl_defs.h:19-20
@@ -58,11 +57,9 @@ PlPayloadHip::PlPayloadHip(int gold_code, int n_slots, int has_pilots, int max_f
     std::vector<uint8_t> rn(payload_len());
     pl_scrambling_rn(gold_code, rn.data(), (int)rn.size());
     DeviceGuard dev_guard(device_); // the caller's current device is restored on return
-    if (!dev_guard.ok || hipMalloc(&d_rn_, rn.size()) != hipSuccess ||
+    if (!dev_guard.ok || alloc(&d_rn_, rn.size()) != hipSuccess ||
         hipMemcpy(d_rn_, rn.data(), rn.size(), hipMemcpyHostToDevice) != hipSuccess) { err_ = "device setup failed"; return; }
 }
-
-PlPayloadHip::~PlPayloadHip() { DeviceGuard dev_guard(device_); (void)hipFree(d_rn_); }
 
 int PlPayloadHip::process_device(const float* d_payload, int n_frames, const float* d_plheader_phase, const float* d_phase_inc,
                                  const int32_t* d_coarse_corrected, const float* d_pilot_phase, float* d_out, hipStream_t stream)
@@ -75,18 +72,14 @@ int PlPayloadHip::process_device_strided(const float* d_in, int frame_stride, in
                                          const float* d_phase_inc, const int32_t* d_coarse_corrected, const float* d_pilot_phase,
                                          float* d_out, hipStream_t stream)
 {
-    if (!ok()) return -1;
-    call_err_.clear();
+    Entry on(*this);
+    if (!on.ok) return -1;
     if (n_frames < 0 || n_frames > max_frames_) { call_err_ = "n_frames exceeds max_frames"; return -1; }
     if (n_frames == 0) return 0;
-    DeviceGuard dev_guard(device_);
-    if (!dev_guard.ok) { call_err_ = "hipSetDevice failed"; return -1; }
     hipLaunchKernelGGL(pl_payload_kernel, dim3((xfecframe_len() + 255) / 256, n_frames), dim3(256), 0, stream,
                        reinterpret_cast<const float2*>(d_in), d_rn_, d_plheader_phase, d_phase_inc, d_coarse_corrected,
                        d_pilot_phase, reinterpret_cast<float2*>(d_out), n_slots_, n_pilots_, has_pilots_, frame_stride, in_offset);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { call_err_ = std::string("pl payload kernel launch: ") + hipGetErrorString(e); return -1; }
-    return 0;
+    return launched("pl payload kernel launch");
 }
 
 } // namespace dvbs2

@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <string>
+#include "device_stage.h"
 #include "plframe_hip.h"
 
 namespace dvbs2 {
@@ -77,12 +78,10 @@ struct PlSyncState { // lives on the device; read back by finish()
     int32_t hold;          // abs_base is the resume point of a pending frame: nothing is consumed before that frame is looked at again
 };
 
-class PlSyncHip {
+class PlSyncHip : public DeviceStage {
 public:
+    // the ranges of the arguments are checked by dvbs2_plsync_create, which alone constructs this
     PlSyncHip(int plsc_or_minus1, int unlock_thresh, int max_symbols, int max_frames, int device);
-    ~PlSyncHip();
-    bool ok() const { return err_.empty(); }
-    const std::string& error() const { return call_err_.empty() ? err_ : call_err_; }
     int max_symbols() const { return max_symbols_; }
     int max_frames() const { return max_frames_; }
     void set_plsc_mode(int coherent, int soft) { coherent_ = coherent ? 1 : 0; soft_ = soft ? 1 : 0; }
@@ -98,13 +97,12 @@ public:
                       int32_t* d_count, hipStream_t stream);
 
 private:
-    int fixed_plsc_, unlock_thresh_, max_symbols_, max_frames_, device_, coherent_ = 1, soft_ = 1;
+    int fixed_plsc_, unlock_thresh_, max_symbols_, max_frames_, coherent_ = 1, soft_ = 1;
     uint8_t* d_rank_ = nullptr;
     float* d_metric_ = nullptr;     // max_symbols floats
     float2* d_hist_ = nullptr;      // 2 x 89 symbols, the tracker writes the one the state does not select
     PlSyncState* d_state_ = nullptr;
     hipStream_t last_stream_ = nullptr;
-    std::string err_, call_err_;
 };
 
 } // namespace dvbs2

@@ -11,7 +11,6 @@
 #include <cmath>
 #include <cstring>
 
-#include "device_guard.h"
 namespace dvbs2 {
 
 void plsync_taps(float* sof25, float* plsc32)
@@ -226,12 +225,8 @@ __global__ __launch_bounds__(256) void plsync_gather_kernel(const float2* __rest
 } // namespace
 
 PlSyncHip::PlSyncHip(int plsc_or_minus1, int unlock_thresh, int max_symbols, int max_frames, int device)
-    : fixed_plsc_(plsc_or_minus1), unlock_thresh_(unlock_thresh), max_symbols_(max_symbols), max_frames_(max_frames), device_(device)
+    : DeviceStage(device), fixed_plsc_(plsc_or_minus1), unlock_thresh_(unlock_thresh), max_symbols_(max_symbols), max_frames_(max_frames)
 {
-    if (fixed_plsc_ < -1 || fixed_plsc_ > 127) { err_ = "plsc out of range (-1 = decode, 0..127)"; return; }
-    if (unlock_thresh_ < 1 || unlock_thresh_ > 255) { err_ = "unlock_thresh out of range (1..255)"; return; }
-    if (max_symbols_ < kPlsyncMinSymbols) { err_ = "max_symbols must be at least 33282 + 90"; return; }
-    if (max_frames_ < 1 || max_frames_ > (1 << 20)) { err_ = "max_frames out of range (1..1048576)"; return; }
     // the compile-time tap signs against the expected symbols, the device's frame length against pls_parse
     float sof[25], pl[32];
     plsync_taps(sof, pl);
@@ -239,79 +234,62 @@ PlSyncHip::PlSyncHip(int plsc_or_minus1, int unlock_thresh, int max_symbols, int
     for (int i = 0; i < 32; i++) if ((pl[i] < 0.0f) != tap_minus(27 + 2 * i)) { err_ = "PLSC tap signs disagree with the PLHEADER"; return; }
     for (int p = 0; p < 128; p++) if (plsync_frame_len(p) != pls_parse(p).plframe_len) { err_ = "frame length disagrees with pls_parse"; return; }
     DeviceGuard dev_guard(device_);
-    if (!dev_guard.ok || hipMalloc(&d_rank_, 128) != hipSuccess || hipMalloc(&d_metric_, (size_t)max_symbols_ * sizeof(float)) != hipSuccess ||
-        hipMalloc(&d_hist_, 2 * kHist * sizeof(float2)) != hipSuccess || hipMalloc(&d_state_, sizeof(PlSyncState)) != hipSuccess) {
+    if (!dev_guard.ok || alloc(&d_rank_, 128) != hipSuccess || alloc(&d_metric_, (size_t)max_symbols_) != hipSuccess ||
+        alloc(&d_hist_, 2 * kHist) != hipSuccess || alloc(&d_state_, 1) != hipSuccess) {
         err_ = "device setup failed"; return;
     }
     if (set_expected_pls(nullptr, 0) || reset()) { err_ = call_err_; call_err_.clear(); }
 }
 
-PlSyncHip::~PlSyncHip()
-{
-    DeviceGuard dev_guard(device_);
-    (void)hipFree(d_rank_); (void)hipFree(d_metric_); (void)hipFree(d_hist_); (void)hipFree(d_state_);
-}
-
 int PlSyncHip::set_expected_pls(const uint8_t* list, int n)
 {
-    call_err_.clear();
+    Entry on(*this);
     uint8_t rank[128];
     if (!pls_rank_table(list, n, rank)) { call_err_ = "codeword indexes must be within [0, 128)"; return -1; } // lib/reed_muller.cc:48-52
-    DeviceGuard dev_guard(device_);
-    if (!dev_guard.ok || hipMemcpy(d_rank_, rank, 128, hipMemcpyHostToDevice) != hipSuccess) { call_err_ = "copy of the codeword list failed"; return -2; }
+    if (!on.ok || hipMemcpy(d_rank_, rank, 128, hipMemcpyHostToDevice) != hipSuccess) { call_err_ = "copy of the codeword list failed"; return -2; }
     return 0;
 }
 
 int PlSyncHip::reset()
 {
-    call_err_.clear();
+    Entry on(*this);
     PlSyncState s;
     std::memset(&s, 0, sizeof(s));
     s.abs_last_peak = -1; // d_sym_cnt = 0 before the first symbol (lib/pl_frame_sync.cc:23)
     s.frame_len = fixed_plsc_ >= 0 ? plsync_frame_len(fixed_plsc_) : 0; // lib/plsync_cc_impl.cc:159, lib/pl_frame_sync.cc:28
-    DeviceGuard dev_guard(device_);
-    if (!dev_guard.ok || hipMemcpy(d_state_, &s, sizeof(s), hipMemcpyHostToDevice) != hipSuccess ||
+    if (!on.ok || hipMemcpy(d_state_, &s, sizeof(s), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemset(d_hist_, 0, 2 * kHist * sizeof(float2)) != hipSuccess) { call_err_ = "reset of the device state failed"; return -2; }
     return 0;
 }
 
 int PlSyncHip::metric_device(const float* d_syms, int n_syms, float* d_metric, hipStream_t stream)
 {
-    if (!ok()) return -1;
-    call_err_.clear();
+    Entry on(*this);
+    if (!on.ok) return -1;
     if (n_syms <= 0) return 0;
-    DeviceGuard dev_guard(device_);
-    if (!dev_guard.ok) { call_err_ = "hipSetDevice failed"; return -1; }
     hipLaunchKernelGGL(plsync_metric_kernel, dim3((n_syms + kTile - 1) / kTile), dim3(kThreads), 0, stream,
                        reinterpret_cast<const float2*>(d_syms), n_syms, d_hist_, d_state_, d_metric);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { call_err_ = std::string("plsync metric kernel launch: ") + hipGetErrorString(e); return -1; }
-    return 0;
+    return launched("plsync metric kernel launch");
 }
 
 int PlSyncHip::search_device(const float* d_syms, int n_syms, PlSyncFrame* d_frames, hipStream_t stream)
 {
-    if (!ok()) return -1;
-    call_err_.clear();
+    Entry on(*this);
+    if (!on.ok) return -1;
     if (n_syms < 0 || n_syms > max_symbols_) { call_err_ = "n_syms exceeds max_symbols"; return -1; }
     if (metric_device(d_syms, n_syms, d_metric_, stream)) return -1;
-    DeviceGuard dev_guard(device_);
-    if (!dev_guard.ok) { call_err_ = "hipSetDevice failed"; return -1; }
     hipLaunchKernelGGL(plsync_track_kernel, dim3(1), dim3(64), 0, stream, reinterpret_cast<const float2*>(d_syms), n_syms, d_metric_, d_hist_,
                        d_state_, d_rank_, d_frames, max_frames_, fixed_plsc_, unlock_thresh_, coherent_, soft_);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { call_err_ = std::string("plsync tracker kernel launch: ") + hipGetErrorString(e); return -1; }
+    if (launched("plsync tracker kernel launch")) return -1;
     last_stream_ = stream;
     return 0;
 }
 
 int PlSyncHip::finish(int* n_frames, int* consumed, int* state)
 {
-    if (!ok()) return -1;
-    call_err_.clear();
-    DeviceGuard dev_guard(device_);
+    Entry on(*this);
     PlSyncState s;
-    if (!dev_guard.ok || hipStreamSynchronize(last_stream_) != hipSuccess ||
+    if (!on.ok || hipStreamSynchronize(last_stream_) != hipSuccess ||
         hipMemcpy(&s, d_state_, sizeof(s), hipMemcpyDeviceToHost) != hipSuccess) { call_err_ = "reading the device state failed"; return -1; }
     if (n_frames) *n_frames = s.last_n_frames;
     if (consumed) *consumed = s.last_consumed;
@@ -322,20 +300,16 @@ int PlSyncHip::finish(int* n_frames, int* consumed, int* state)
 int PlSyncHip::gather_device(const float* d_syms, const PlSyncFrame* d_frames, int n_frames, int wanted_plsc, float* d_plframes,
                              int32_t* d_count, hipStream_t stream)
 {
-    if (!ok()) return -1;
-    call_err_.clear();
+    Entry on(*this);
+    if (!on.ok) return -1;
     if (n_frames < 0 || n_frames > max_frames_) { call_err_ = "n_frames exceeds max_frames"; return -1; }
-    DeviceGuard dev_guard(device_);
-    if (!dev_guard.ok) { call_err_ = "hipSetDevice failed"; return -1; }
     if (n_frames == 0) {
         if (hipMemsetAsync(d_count, 0, sizeof(int32_t), stream) != hipSuccess) { call_err_ = "clearing the frame count failed"; return -1; }
         return 0;
     }
     hipLaunchKernelGGL(plsync_gather_kernel, dim3(n_frames), dim3(256), 0, stream, reinterpret_cast<const float2*>(d_syms), d_frames, n_frames,
                        d_state_, wanted_plsc, reinterpret_cast<float2*>(d_plframes), d_count);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { call_err_ = std::string("plsync gather kernel launch: ") + hipGetErrorString(e); return -1; }
-    return 0;
+    return launched("plsync gather kernel launch");
 }
 
 } // namespace dvbs2

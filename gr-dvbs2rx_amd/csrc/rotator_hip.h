@@ -23,6 +23,7 @@
 #include <cstdint>
 #include <string>
 #include <vector>
+#include "device_stage.h"
 
 namespace dvbs2 {
 
@@ -33,11 +34,9 @@ uint64_t rotator_inc_turns(double inc);
 // plain 16-byte-per-lane copy of the same bytes on the same grid
 int rotator_measure(int device, int n_syms, int regions, double* rot_ms, double* copy_ms, std::string* err);
 
-class RotatorHip {
+class RotatorHip : public DeviceStage {
 public:
     RotatorHip(double phase_inc, int device);
-    bool ok() const { return err_.empty(); }
-    const std::string& error() const { return call_err_.empty() ? err_ : call_err_; }
     void reset(); // the handle as constructed: counter 0, phase 0, the constructor's increment, empty queue
     int set_phase_inc(double inc);
     int schedule(int64_t offset, double inc);
@@ -54,11 +53,9 @@ private:
     struct Segment { int64_t start; uint64_t phase, inc; }; // start relative to the call
     void advance(int64_t n, std::vector<Segment>* segs);
     double inc0_;
-    int device_;
     int64_t counter_ = 0;
     uint64_t phase_ = 0, inc_ = 0;
     std::vector<Update> queue_; // ascending offset, equal offsets in scheduling order
-    std::string err_, call_err_;
 };
 
 } // namespace dvbs2

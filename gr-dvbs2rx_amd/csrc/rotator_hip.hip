@@ -5,7 +5,6 @@
 #include <climits>
 #include <cmath>
 
-#include "device_guard.h"
 namespace dvbs2 {
 
 #ifndef __HIP_DEVICE_COMPILE__ // host code only: the device pass of this file has no extended type and never runs this
@@ -119,7 +118,7 @@ int rotator_measure(int device, int n_syms, int regions, double* rot_ms, double*
     return 0;
 }
 
-RotatorHip::RotatorHip(double phase_inc, int device) : inc0_(phase_inc), device_(device)
+RotatorHip::RotatorHip(double phase_inc, int device) : DeviceStage(device), inc0_(phase_inc)
 {
     if (!std::isfinite(phase_inc)) { err_ = "phase_inc must be finite"; return; }
     reset();
@@ -184,13 +183,11 @@ int RotatorHip::seek(int64_t n)
 
 int RotatorHip::rotate_device(const float* d_in, int n_syms, float* d_out, hipStream_t stream)
 {
-    if (!ok()) return -1;
-    call_err_.clear();
+    Entry on(*this);
+    if (!on.ok) return -1;
     if (n_syms < 0 || (int64_t)n_syms > INT64_MAX - counter_) { call_err_ = "n_syms out of range"; return -1; }
     if (n_syms == 0) return 0;
     if (((uintptr_t)d_in | (uintptr_t)d_out) & 7) { call_err_ = "symbol buffers must be 8-byte aligned"; return -1; }
-    DeviceGuard dev_guard(device_);
-    if (!dev_guard.ok) { call_err_ = "hipSetDevice failed"; return -1; }
     std::vector<Segment> segs;
     advance(n_syms, &segs);
     const float2* in = reinterpret_cast<const float2*>(d_in);
@@ -209,8 +206,7 @@ int RotatorHip::rotate_device(const float* d_in, int n_syms, float* d_out, hipSt
         const int blocks = (int)std::min<int64_t>(((int64_t)n / 2 + 256) / 256, 4096);
         if (cnt == 1) hipLaunchKernelGGL(rotator_kernel<false>, dim3(blocks), dim3(256), 0, stream, in + a, out + a, n, g);
         else hipLaunchKernelGGL(rotator_kernel<true>, dim3(blocks), dim3(256), 0, stream, in + a, out + a, n, g);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { call_err_ = std::string("rotator kernel launch: ") + hipGetErrorString(e); return -1; }
+        if (launched("rotator kernel launch")) return -1;
     }
     return 0;
 }

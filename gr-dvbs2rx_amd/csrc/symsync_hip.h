@@ -29,6 +29,7 @@
 #include <cstdint>
 #include <string>
 #include <vector>
+#include "device_stage.h"
 
 namespace dvbs2 {
 
@@ -58,17 +59,14 @@ int symsync_geometry(int sps, int rrc_delay, int n_subfilt, int interp, int* sub
 // n_subfilt * subfilt_len floats, [subfilter][tap], each subfilter flipped (:82-110); -1 on a bad argument
 int symsync_taps(int sps, float rolloff, int rrc_delay, int n_subfilt, float* bank);
 
-class SymSyncHip {
+class SymSyncHip : public DeviceStage {
 public:
     // bank: n_subfilt * subfilt_len floats as symsync_taps lays them out, or null to design them here
     SymSyncHip(int sps, float loop_bw, float damping, float rolloff, int rrc_delay, int n_subfilt, int interp, const float* bank,
                int max_streams, int max_samples, int device);
-    ~SymSyncHip();
     // empty when the arguments are acceptable, else what is wrong with them (no device needed)
     static std::string check_args(int sps, float loop_bw, float damping, float rolloff, int rrc_delay, int n_subfilt, int interp, int max_streams,
                                   int max_samples);
-    bool ok() const { return err_.empty(); }
-    const std::string& error() const { return call_err_.empty() ? err_ : call_err_; }
     const SymSyncGeom& geom() const { return g_; }
     float Kp() const { return Kp_; }
     int max_streams() const { return max_streams_; }
@@ -87,7 +85,7 @@ public:
 private:
     SymSyncGeom g_{};
     float Kp_ = 0.0f;
-    int max_streams_, max_samples_, device_;
+    int max_streams_, max_samples_;
     int last_streams_ = 0;
     hipStream_t last_stream_ = nullptr;
     float* d_bank_ = nullptr;
@@ -96,7 +94,6 @@ private:
     SymSyncResult* d_res_ = nullptr;
     int* d_nin_ = nullptr;
     std::vector<SymSyncResult> res_;
-    std::string err_, call_err_;
 };
 
 } // namespace dvbs2

@@ -4,7 +4,6 @@
 #include <cstring>
 #include <new>
 
-#include "device_guard.h"
 namespace dvbs2 {
 
 void symsync_loop_constants(int sps, float loop_bw, float damping, float rolloff, float* Kp, float* K1, float* K2)
@@ -248,7 +247,7 @@ std::string SymSyncHip::check_args(int sps, float loop_bw, float damping, float 
 
 SymSyncHip::SymSyncHip(int sps, float loop_bw, float damping, float rolloff, int rrc_delay, int n_subfilt, int interp, const float* bank,
                        int max_streams, int max_samples, int device)
-    : max_streams_(max_streams), max_samples_(max_samples), device_(device)
+    : DeviceStage(device), max_streams_(max_streams), max_samples_(max_samples)
 {
     err_ = check_args(sps, loop_bw, damping, rolloff, rrc_delay, n_subfilt, interp, max_streams, max_samples);
     if (!err_.empty()) return;
@@ -261,11 +260,8 @@ SymSyncHip::SymSyncHip(int sps, float loop_bw, float damping, float rolloff, int
     if (bank) memcpy(taps.data(), bank, bank_bytes);
     else symsync_taps(sps, rolloff, rrc_delay, n_subfilt, taps.data());
     DeviceGuard dev_guard(device_);
-    if (!dev_guard.ok || hipMalloc(&d_bank_, bank_bytes) != hipSuccess ||
-        hipMalloc(&d_hist_, (size_t)max_streams_ * 2 * H * sizeof(float2)) != hipSuccess ||
-        hipMalloc(&d_state_, (size_t)max_streams_ * sizeof(SymSyncState)) != hipSuccess ||
-        hipMalloc(&d_res_, (size_t)max_streams_ * sizeof(SymSyncResult)) != hipSuccess ||
-        hipMalloc(&d_nin_, (size_t)max_streams_ * sizeof(int)) != hipSuccess ||
+    if (!dev_guard.ok || alloc(&d_bank_, taps.size()) != hipSuccess || alloc(&d_hist_, (size_t)max_streams_ * 2 * H) != hipSuccess ||
+        alloc(&d_state_, max_streams_) != hipSuccess || alloc(&d_res_, max_streams_) != hipSuccess || alloc(&d_nin_, max_streams_) != hipSuccess ||
         hipMemcpy(d_bank_, taps.data(), bank_bytes, hipMemcpyHostToDevice) != hipSuccess) {
         err_ = "device setup failed"; return;
     }
@@ -273,22 +269,15 @@ SymSyncHip::SymSyncHip(int sps, float loop_bw, float damping, float rolloff, int
     if (reset()) { err_ = call_err_; call_err_.clear(); }
 }
 
-SymSyncHip::~SymSyncHip()
-{
-    DeviceGuard dev_guard(device_);
-    (void)hipFree(d_bank_); (void)hipFree(d_hist_); (void)hipFree(d_state_); (void)hipFree(d_res_); (void)hipFree(d_nin_);
-}
-
 int SymSyncHip::reset()
 {
-    call_err_.clear();
+    Entry on(*this);
     SymSyncState s0;
     memset(&s0, 0, sizeof(s0));
     s0.cnt = 1.0 - 1.0 / (double)(float)g_.sps; // :219-225: vi 0, mu 0, jump sps, not initialised, last_xi 0
     s0.jump = g_.sps;
     std::vector<SymSyncState> all(max_streams_, s0);
-    DeviceGuard dev_guard(device_);
-    if (!dev_guard.ok || hipDeviceSynchronize() != hipSuccess ||
+    if (!on.ok || hipDeviceSynchronize() != hipSuccess ||
         hipMemcpy(d_state_, all.data(), all.size() * sizeof(SymSyncState), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemset(d_hist_, 0, (size_t)max_streams_ * 2 * g_.history * sizeof(float2)) != hipSuccess || // the history starts as zeros
         hipMemset(d_res_, 0, (size_t)max_streams_ * sizeof(SymSyncResult)) != hipSuccess) {
@@ -301,10 +290,8 @@ int SymSyncHip::reset()
 int SymSyncHip::work_device(const float2* d_in, int64_t in_stride, const int* n_in, int n_streams, float2* d_out, int64_t out_stride, int max_out,
                             int64_t* d_strobe_idx, double* d_mu, hipStream_t stream)
 {
-    if (!ok()) return -1;
-    call_err_.clear();
-    DeviceGuard dev_guard(device_);
-    if (!dev_guard.ok) { call_err_ = "hipSetDevice failed"; return -1; }
+    Entry on(*this);
+    if (!on.ok) return -1;
     if (hipMemcpyAsync(d_nin_, n_in, (size_t)n_streams * sizeof(int), hipMemcpyHostToDevice, stream) != hipSuccess) {
         call_err_ = "copy of the sample counts failed"; return -1;
     }
@@ -317,18 +304,15 @@ int SymSyncHip::work_device(const float2* d_in, int64_t in_stride, const int* n_
     case 2: hipLaunchKernelGGL(symsync_kernel<2>, grid, block, lds, stream, io, g_, d_bank_, d_hist_, d_state_, d_res_); break;
     default: hipLaunchKernelGGL(symsync_kernel<3>, grid, block, lds, stream, io, g_, d_bank_, d_hist_, d_state_, d_res_); break;
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { call_err_ = std::string("symsync kernel launch: ") + hipGetErrorString(e); return -1; }
+    if (launched("symsync kernel launch")) return -1;
     last_streams_ = n_streams; last_stream_ = stream;
     return 0;
 }
 
 int SymSyncHip::finish(int* n_out, int* consumed, int* status)
 {
-    if (!ok()) return -1;
-    call_err_.clear();
-    DeviceGuard dev_guard(device_);
-    if (!dev_guard.ok || hipStreamSynchronize(last_stream_) != hipSuccess ||
+    Entry on(*this);
+    if (!on.ok || hipStreamSynchronize(last_stream_) != hipSuccess ||
         (last_streams_ && hipMemcpy(res_.data(), d_res_, (size_t)last_streams_ * sizeof(SymSyncResult), hipMemcpyDeviceToHost) != hipSuccess)) {
         call_err_ = "reading the results failed"; return -1;
     }
@@ -342,10 +326,8 @@ int SymSyncHip::finish(int* n_out, int* consumed, int* status)
 
 int SymSyncHip::state(int s, SymSyncState* out)
 {
-    if (!ok()) return -1;
-    call_err_.clear();
-    DeviceGuard dev_guard(device_);
-    if (!dev_guard.ok || hipDeviceSynchronize() != hipSuccess || hipMemcpy(out, d_state_ + s, sizeof(SymSyncState), hipMemcpyDeviceToHost) != hipSuccess) {
+    Entry on(*this);
+    if (!on.ok || hipDeviceSynchronize() != hipSuccess || hipMemcpy(out, d_state_ + s, sizeof(SymSyncState), hipMemcpyDeviceToHost) != hipSuccess) {
         call_err_ = "reading the state failed"; return -1;
     }
     return 0;
