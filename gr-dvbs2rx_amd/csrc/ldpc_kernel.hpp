@@ -449,7 +449,7 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
         // Run loop: the packed builds of the degree classes up to 8 run their regular packed layers in a loop of their own (at the head
         // of the layer loop). At three waves per SIMD a wave is limited by its own instruction stream, scalar instructions included, and
         // the layer loop spent 67 of them per regular trip on the record double buffer's moves, the header decode and the degree switch as
-        // a compare chain -- for a degree and a record format that change nine times in B4's 90 layers (notes/r09_run_loop.md).
+        // a compare chain -- for a degree and a record format that change nine times in B4's 90 layers (notes/r09_run_loop.md, r10_straight_trip.md).
         constexpr bool kRun = V2 && DMAX <= 8;
         constexpr int kPfSmallMaxDmax = 8;
         constexpr int PF = DMAX <= kPfSmallMaxDmax ? 1 : 2 * DMAX;
@@ -474,60 +474,68 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
                 // The degree dispatch and the header decode happen once per run, and the trip is unrolled by two over ping-pong registers:
                 // the record (A / B) and the messages (pre / pb) a trip has fetched ahead are what the next trip works on, where it lies.
                 // What a trip keeps of the layer loop: the per-layer barrier bit, the prefetch behind the barrier, the vmcnt(0) in front
-                // of the stores. A run ends at the first prefetched header that does not continue it (or at the last layer: the record
-                // fetched ahead is layer 0's then, which is never packed -- ldpc_plan.cpp --, so the wrap ends a run by itself; the
-                // test on the layer index only tells the compiler). Waves of a frame may cut their runs differently (bit 13 is per wave);
-                // the barrier bit is the layer's, so every wave meets the same barriers on either path.
-                if (work && (nhdr & kRecPacked) && (nhdr >> kRecBlockShift) >= (uint32_t)kM) {
+                // of the stores. What it does not hold (notes/r10_straight_trip.md): a frame's first sweep -- it loads no messages, and as
+                // an arm of the trip it cost every trip a message copy and three flag registers; that sweep takes the packed arm of the
+                // layer loop below --, a layer index (the message offset is the induction variable, the record to fetch ahead a running
+                // pointer) and the table's last layer, behind which that pointer would have to wrap: a run ends in front of it. A run
+                // ends at the first prefetched header that differs from the run's first one in degree, format or block. Waves of a frame
+                // may cut their runs differently (bit 13 is per wave); the barrier bit is the layer's, so every wave meets the same
+                // barriers on either path.
+                if (work && !zero_msgs && i + 1 < q && (nhdr & kRecPacked) && (nhdr >> kRecBlockShift) >= (uint32_t)kM) {
                     auto run = [&](auto degc) {
                         constexpr int D = decltype(degc)::value;
-                        uint32_t ha = nhdr, hb = 0u, ea[2 * DMAX], eb[2 * DMAX], pb[MW];
+                        // what a header must share with the run's first one to continue it: degree, format and block (equal blocks: both regular)
+                        constexpr uint32_t kKeyMask = (~0u << kRecBlockShift) | kRecPacked | 0xffu;
+                        const uint32_t key = nhdr & kKeyMask;
+                        uint32_t ha = nhdr, hb, ea[2 * DMAX], eb[2 * DMAX], pb[MW];
 #pragma unroll
-                        for (int k = 0; k < 2 * DMAX; k++) { ea[k] = nent[k]; eb[k] = 0u; }
-#pragma unroll
-                        for (int w = 0; w < MW; w++) pb[w] = 0u;
-                        bool more;
-// one trip: the layer of record (H, E) with the messages P; the next layer's record goes to (NH, NE), its messages to NP
-#define DVBS2_RUN_TRIP(H, E, P, NH, NE, NP) { \
-                            const int inext = i + 1 < q ? i + 1 : 0; \
-                            const uint32_t* nrec = wr + (size_t)inext * RSW; \
+                        for (int k = 0; k < 2 * DMAX; k++) ea[k] = nent[k];
+                        const uint32_t* nrec = wr + (size_t)(i + 1) * RSW; // the record the next trip fetches ahead: a running pointer
+                        int sa = i * kLayerBytes, sb;                       // scalar byte offset of a trip's messages
+                        const int s_last = (q - 1) * kLayerBytes;           // the last layer's: never reached inside a run
+// one trip: the layer of record (H, E) with the messages P at offset S; the next layer's record goes to (NH, NE), its messages to NP, its offset to NS
+// (message word w is addressed as (row4 + w * stride) + S: the per-lane part is loop invariant, so the trip has no scalar add per load and store)
+#define DVBS2_RUN_TRIP(H, E, P, S, NH, NE, NP, NS) { \
                             TSTAMP(tA); \
-                            if (H & (1u << kRecSyncShift)) lds_barrier(); \
+                            NS = S + kLayerBytes; \
+                            if (__builtin_expect((H & (1u << kRecSyncShift)) != 0u, 1)) lds_barrier(); \
                             asm volatile("" ::: "memory"); \
                             NH = nrec[0]; \
                             _Pragma("unroll") for (int k = 0; k < 2 * DMAX; k++) NE[k] = nrec[4 + k]; \
+                            nrec += RSW; \
                             TSTAMP(tB); tm_bar += tB - tA; \
-                            uint32_t mw[MW], nm[MW]; \
-                            _Pragma("unroll") for (int w = 0; w < MW; w++) mw[w] = P[w]; \
-                            if (zero_msgs) { \
-                                asm volatile("" ::: "memory"); \
-                                _Pragma("unroll") for (int w = 0; w < MW; w++) mw[w] = 0u; \
-                            } else msg_load(NP, inext * kLayerBytes, row4); \
-                            check_node_v2<D, DMAX, TC>(E, row + lb, mw, nm, 0); \
+                            uint32_t nm[MW]; \
+                            _Pragma("unroll") for (int w = 0; w < MW; w++) NP[w] = __builtin_amdgcn_raw_buffer_load_b32(mrs, row4 + w * (kMsgStride * 4), NS, 0); \
+                            check_node_v2<D, DMAX, TC>(E, row + lb, P, nm, 0); \
                             DVBS2_WAIT_VM0(); \
-                            msg_store(nm, i * kLayerBytes, row4); \
+                            _Pragma("unroll") for (int w = 0; w < MW; w++) __builtin_amdgcn_raw_buffer_store_b32(nm[w], mrs, row4 + w * (kMsgStride * 4), S, 0); \
                             TSTAMP(tC); tm_body += tC - tB; \
-                            if (TIMING && tdbg && f == 0 && tid == 0) tdbg[(size_t)n_frames * 48 + i] += tC - tA; \
-                            more = inext != 0 && ((NH ^ H) & (0xffu | kRecPacked)) == 0u && (NH >> kRecBlockShift) >= (uint32_t)kM; }
+                            if (TIMING && tdbg && f == 0 && tid == 0) tdbg[(size_t)n_frames * 48 + S / kLayerBytes] += tC - tA; }
+                        // two tests, two branches that are not taken inside a run (the empty statement keeps them from being merged into flag arithmetic)
+                        auto run_ends = [&](uint32_t h, int s) {
+                            if (__builtin_expect((h & kKeyMask) != key, 0)) return true;
+                            asm volatile("");
+                            return (bool)__builtin_expect(s >= s_last, 0);
+                        };
                         for (;;) {
-                            DVBS2_RUN_TRIP(ha, ea, pre, hb, eb, pb)
-                            if (!more) { // the run ends behind an odd trip: what was fetched ahead moves to where the layer loop expects it
+                            DVBS2_RUN_TRIP(ha, ea, pre, sa, hb, eb, pb, sb)
+                            if (run_ends(hb, sb)) { // the run ends behind an odd trip: what was fetched ahead moves to where the layer loop expects it
                                 nhdr = hb;
 #pragma unroll
                                 for (int k = 0; k < 2 * DMAX; k++) nent[k] = eb[k];
 #pragma unroll
                                 for (int w = 0; w < MW; w++) pre[w] = pb[w];
+                                i = sa / kLayerBytes;
                                 break;
                             }
-                            i++;
-                            DVBS2_RUN_TRIP(hb, eb, pb, ha, ea, pre)
-                            if (!more) {
+                            DVBS2_RUN_TRIP(hb, eb, pb, sb, ha, ea, pre, sa)
+                            if (run_ends(ha, sa)) {
                                 nhdr = ha;
 #pragma unroll
                                 for (int k = 0; k < 2 * DMAX; k++) nent[k] = ea[k];
+                                i = sb / kLayerBytes;
                                 break;
                             }
-                            i++;
                         }
 #undef DVBS2_RUN_TRIP
                     };
@@ -576,8 +584,8 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
                     // v2: this wave's record is in the packed node's format (two's complement messages)
                     uint32_t mw[MW], nm[MW];
                     take_msgs(mw, pre, zero_msgs, v2 ? 0u : 0x80808080u, inext * kLayerBytes, row4);
-                    // (kRun: a packed record of a working wave never gets here -- the run loop at the head of the layer loop took it)
-                    if constexpr (V2 && !kRun) { if (v2) { DVBS2_V2_SWITCH } else DVBS2_DEG_SWITCH } else DVBS2_DEG_SWITCH
+                    // (kRun: a packed record of a working wave gets here in a frame's first sweep and at the table's last layer only -- the run loop took the others)
+                    if constexpr (V2) { if (v2) { DVBS2_V2_SWITCH } else DVBS2_DEG_SWITCH } else DVBS2_DEG_SWITCH
                     DVBS2_WAIT_VM0();
                     msg_store(nm, mso, row4);
                 }

@@ -12,8 +12,10 @@ which counts the regular node alone).
      no barrier; the blocks it takes are printed, so the choice can be checked against the disassembly. Split into "node"
      (s_setprio 0 .. the end of the node's block: the node and its message packing, what node_census.py calls total) and "else"
      (everything outside: the layer head, the switch, message load / store, the copies at the loop's back edge).
- (a') where the build has the run loop (two node bodies of the degree): one line per half of the loop unrolled by two -- everything a
-     wave issues from the head of one node to the head of the other (VALU, SALU, branches taken), by the cheapest barrier-free way.
+ (a') where the build has the run loop (two node bodies of the degree in a loop; a third one may serve a frame's first sweep in the
+     layer loop): per half of the loop unrolled by two everything a wave issues from the head of one node to the head of the other
+     (VALU, SALU, branches taken), by the cheapest way that issues the message loads -- once without a barrier, once through one --
+     and the register moves and lane accesses it meets between the two node bodies.
  (b) one HAZARD layer of the single-pair lane-chain form (check_node_chain_v2) of that degree: the text between the node's first
      s_setprio 0 and the message packing behind its last phase, split at its two barriers into P1 (regular entries read and reduced,
      heads' pair, chain operands published), walk (per chain: prologue + ONE four-step trip of the walk loop + the three tail steps)
@@ -135,24 +137,56 @@ def cheapest_cycle(blk, succ, k0):
     return path[::-1]
 
 
-def cheapest_path(blk, succ, src, dst):
-    """cheapest way (instructions) from the end of block src to the head of block dst that meets no barrier: [blocks between them]"""
+def cheapest_path(blk, succ, src, i_src, dst, i_dst, barrier=False):
+    """cheapest way (instructions) from the end of block src to the head of block dst that issues message loads (a buffer_load in the
+    node's own block behind its head at i_src, in a block on the way, or in dst in front of its node's head at i_dst: the way of every sweep
+    but a frame's first) and meets no barrier -- or, with `barrier`, at least one: [blocks between them]"""
+    # (the sweep is wave-uniform code with EXEC restored behind every masked add: the compiler's guards "s_cbranch_execz" around the
+    # hand-over blocks at a run's end are never taken, "s_cbranch_execnz" always -- without this the cheapest way leads through them)
+    def live(k):
+        o = blk[k][-1][0]
+        return succ[k][1:] if o == "s_cbranch_execz" and len(succ[k]) == 2 else succ[k][:1] if o == "s_cbranch_execnz" else succ[k]
     bar = [any(o == "s_barrier" for o, _ in b) for b in blk]
-    dist, prev, heap = {}, {}, [(0, s, src) for s in succ[src]]
+    ld = [any(o.startswith("buffer_load") for o, _ in b) for b in blk]
+    ld_src = any(o.startswith("buffer_load") for o, _ in blk[src][i_src:])
+    ld_dst = any(o.startswith("buffer_load") for o, _ in blk[dst][:i_dst])
+    bar_dst = any(o == "s_barrier" for o, _ in blk[dst][:i_dst])
+    start = (src, ld_src, False)
+    dist, prev, heap = {}, {}, [(0, (s, ld_src, False), start) for s in live(src)]
     while heap:
-        d, k, p = heapq.heappop(heap)
-        if k in dist or (bar[k] and k != dst):
-            continue
-        dist[k], prev[k] = d, p
+        d, n, p = heapq.heappop(heap)
+        k, l, b = n
         if k == dst:
-            path, n = [], prev[k]
-            while n != src:
-                path.append(n)
-                n = prev[n]
-            return path[::-1]
-        for s in succ[k]:
-            heapq.heappush(heap, (d + len(blk[k]), s, k))
+            l, b = l or ld_dst, b or bar_dst
+            if l and b == barrier:
+                path = []
+                while p != start:
+                    path.append(p[0])
+                    p = prev[p]
+                return path[::-1]
+            continue
+        if n in dist or (bar[k] and not barrier):
+            continue
+        dist[n], prev[n] = d, p
+        for s in live(k):
+            heapq.heappush(heap, (d + len(blk[k]), (s, l or ld[k], b or bar[k]), n))
     return None
+
+
+def run_loop_pair(blk, succ, nodes):
+    """the two node bodies of the run loop among the packed regular nodes of the degree: the pair with the shortest way round (a build may
+    keep a third body in the layer loop, for a frame's first sweep)"""
+    best = None
+    for x in range(len(nodes)):
+        for y in range(x + 1, len(nodes)):
+            (ka, ia), (kb, ib) = nodes[x], nodes[y]
+            ab, ba = cheapest_path(blk, succ, ka, ia, kb, ib), cheapest_path(blk, succ, kb, ib, ka, ia)
+            if ab is None or ba is None:
+                continue
+            n = sum(len(blk[k]) for k in ab + ba)
+            if best is None or n < best[0]:
+                best = (n, [nodes[x], nodes[y]])
+    return best[1] if best else None
 
 
 def taken(seq):
@@ -199,17 +233,23 @@ def main():
     # (a') the run loop (degree classes up to 8): the node is instantiated twice per degree, one body per half of the loop unrolled by two
     # over ping-pong record registers; a trip is one node and the way to the other one (the cheapest one: no barrier, not a frame's first sweep)
     nodes = find_nodes(blk, a.deg)
-    if len(nodes) == 2:
-        print(f"(a') run loop, degree {a.deg}: two halves (node -> way to the other node)")
+    nodes = run_loop_pair(blk, succ, nodes) if len(nodes) >= 2 else None
+    if nodes:
+        print(f"(a') run loop, degree {a.deg}: two halves (node -> way to the other node through the message loads; +bar: the way through a barrier)")
         for h, ((ka, ia), (kb, ib)) in enumerate((nodes, nodes[::-1])):
-            way = cheapest_path(blk, succ, ka, kb)
-            if way is None:
-                print(f"  half {'AB'[h]}: no barrier-free way from {names.get(ka, ka)} to {names.get(kb, kb)}")
-                continue
-            ops = blk[ka][ia:] + [op for k in way for op in blk[k]] + blk[kb][:ib]
-            c = span_tally(ops)
-            print(row(f"  half {'AB'[h]}", c) + f"   branches taken {taken([ka] + way + [kb])}, {c['vmem']} buffer instructions, "
-                  f"{sum(1 for o, _ in ops if o == 's_waitcnt')} s_waitcnt; blocks " + " ".join(names.get(k, f"+{k}") for k in [ka] + way + [kb]))
+            for barrier in (False, True):
+                way = cheapest_path(blk, succ, ka, ia, kb, ib, barrier)
+                tag = f"  half {'AB'[h]}" + (" +bar" if barrier else "")
+                if way is None:
+                    print(f"{tag}: no such way from {names.get(ka, ka)} to {names.get(kb, kb)}")
+                    continue
+                ops = blk[ka][ia:] + [op for k in way for op in blk[k]] + blk[kb][:ib]
+                c = span_tally(ops)
+                moves = [f"{o} {x}" for o, x in ops[len(blk[ka][ia:]):] if o.startswith(("v_mov_b32", "v_readfirstlane", "v_readlane", "v_writelane"))]
+                print(row(tag, c) + f"   branches taken {taken([ka] + way + [kb])}, {c['vmem']} buffer instructions, "
+                      f"{sum(1 for o, _ in ops if o == 's_waitcnt')} s_waitcnt; blocks " + " ".join(names.get(k, f"+{k}") for k in [ka] + way + [kb]))
+                if not barrier:
+                    print(f"      moves and lane accesses between the node bodies: {len(moves)}" + ("".join("\n        " + m for m in moves)))
     # (b) the chain node: two barriers with a float walk (v_med3_f32) between them, DEG - 2 + 3 LLR byte reads in front
     flat = [op for b in blk for op in b]
     bars = [i for i, (o, _) in enumerate(flat) if o == "s_barrier"]
