@@ -212,23 +212,23 @@ __global__ void bbdh_save_partial_kernel(const uint8_t* __restrict__ in, int n_f
 BbDeheaderHip::BbDeheaderHip(int kbch_bits, int max_frames, int device)
     : DeviceStage(device), kbch_bytes_(kbch_bits / 8), max_dfl_(kbch_bits - 80), max_frames_(max_frames)
 {
-    if (kbch_bits < 88 || kbch_bits % 8 != 0 || kbch_bits - 80 > 0xffff) { err_ = "unsupported BCH message length"; return; }
-    if (max_frames_ < 1 || max_frames_ > 65535) { err_ = "max_frames must be in 1..65535"; return; }
-    if (max_out_bytes_per_frame() / kTsLen > 64) { err_ = "more than 64 packets per BBFRAME"; return; }
+    if (kbch_bits < 88 || kbch_bits % 8 != 0 || kbch_bits - 80 > 0xffff) { err_.argument("unsupported BCH message length"); return; }
+    if (max_frames_ < 1 || max_frames_ > 65535) { err_.argument("max_frames must be in 1..65535"); return; }
+    if (max_out_bytes_per_frame() / kTsLen > 64) { err_.argument("more than 64 packets per BBFRAME"); return; }
     DeviceGuard guard(device_);
-    if (!guard.ok) { err_ = "hipSetDevice failed"; return; }
+    if (!guard.ok) { err_.argument("hipSetDevice failed"); return; } // (device failure, kArgument: notes/stage_error_codes.md)
     hipError_t e = alloc(&d_state_, 1);
     if (e == hipSuccess) e = hipMemset(d_state_, 0, sizeof(BbdhState));
     if (e == hipSuccess) e = alloc(&d_plan_, (size_t)max_frames_ + 1);
     if (e == hipSuccess) e = alloc(&d_hdr_, max_frames_);
-    hip_ok(e, "bbdeheader buffers", err_);
+    hip_ok(e, "bbdeheader buffers", err_, kArgument); // (device failure, kArgument: notes/stage_error_codes.md)
 }
 
 int BbDeheaderHip::process_device(const uint8_t* d_bbframes, int n_frames, uint8_t* d_out, hipStream_t stream)
 {
     Entry on(*this);
     if (!on.ok) return -1;
-    if (n_frames < 0 || n_frames > max_frames_) { call_err_ = "n_frames exceeds max_frames"; return -1; }
+    if (n_frames < 0 || n_frames > max_frames_) { call_err_.device("n_frames exceeds max_frames"); return -1; } // (argument text, kDevice: notes/stage_error_codes.md)
     hipLaunchKernelGGL(bbdh_header_kernel, dim3((n_frames + 255) / 256 + (n_frames == 0)), dim3(256), 0, stream, d_bbframes, n_frames, kbch_bytes_, max_dfl_, d_hdr_);
     hipLaunchKernelGGL(bbdh_scan_kernel, dim3(1), dim3(kScanThreads), 0, stream, d_hdr_, n_frames, kbch_bytes_, d_state_, d_plan_);
     if (n_frames > 0) {

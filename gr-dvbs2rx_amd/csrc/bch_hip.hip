@@ -459,11 +459,11 @@ __global__ __launch_bounds__(kBchThreads) void bch_decode_kernel(BchArgs a)
 BchDecoderHip::BchDecoderHip(int m, uint32_t prim_poly, int t, int n, int max_frames, int device)
     : DeviceStage(device), max_frames_(max_frames)
 {
-    if (!code_.build(m, prim_poly, t, n, &err_)) return;
-    if (code_.n % 8 || code_.k % 8) { err_ = "u8 array messages are only supported for n and k multiple of 8."; return; } // lib/bch.cc:19-24
-    if (max_frames_ < 1 || max_frames_ > 65535) { err_ = "max_frames must be in 1..65535 (frames are one launch dimension)"; return; }
+    if (std::string bad; !code_.build(m, prim_poly, t, n, &bad)) { err_.argument(bad); return; }
+    if (code_.n % 8 || code_.k % 8) { err_.argument("u8 array messages are only supported for n and k multiple of 8."); return; } // lib/bch.cc:19-24
+    if (max_frames_ < 1 || max_frames_ > 65535) { err_.argument("max_frames must be in 1..65535 (frames are one launch dimension)"); return; }
     DeviceGuard dev_guard(device_); // restored on return (device_guard.h)
-    if (!dev_guard.ok) { err_ = "hipSetDevice failed"; return; }
+    if (!dev_guard.ok) { err_.device("hipSetDevice failed"); return; }
     hipDeviceProp_t pr;
     HIP_OK(hipGetDeviceProperties(&pr, device_));
     n_cus_ = pr.multiProcessorCount;
@@ -526,7 +526,7 @@ int BchDecoderHip::set_descramble(bool enable)
         std::vector<uint8_t> seq(code_.k / 8);
         bb_derandomise_sequence(seq.data(), (int)seq.size());
         if (alloc(&d_scramble_, seq.size()) != hipSuccess ||
-            hipMemcpy(d_scramble_, seq.data(), seq.size(), hipMemcpyHostToDevice) != hipSuccess) { call_err_ = "descramble sequence upload failed"; return -1; }
+            hipMemcpy(d_scramble_, seq.data(), seq.size(), hipMemcpyHostToDevice) != hipSuccess) { call_err_.device("descramble sequence upload failed"); return -1; }
     }
     descramble_ = enable;
     return 0;
@@ -543,13 +543,13 @@ int BchDecoderHip::decode_device(const uint8_t* d_cw, int n_frames, uint8_t* d_m
 {
     Entry on(*this);
     if (!on.ok) return -1;
-    if (n_frames < 0 || frame_base < 0 || frame_base + n_frames > max_frames_) { call_err_ = "n_frames exceeds max_frames"; return -1; }
+    if (n_frames < 0 || frame_base < 0 || frame_base + n_frames > max_frames_) { call_err_.device("n_frames exceeds max_frames"); return -1; } // (argument text, kDevice: notes/stage_error_codes.md)
     if (n_frames == 0) return 0;
     // the syndrome words of [frame_base, frame_base + n_frames) belong to this call until its per-frame kernel has read them: an earlier
     // call on ANOTHER stream that used an overlapping range is waited for on the device (same stream: stream order already does it)
     for (const InFlight& t : track_)
         if (t.done && t.stream != stream && t.base < frame_base + n_frames && frame_base < t.base + t.n)
-            if (hipStreamWaitEvent(stream, t.done, 0) != hipSuccess) { call_err_ = "hipStreamWaitEvent failed"; return -1; }
+            if (hipStreamWaitEvent(stream, t.done, 0) != hipSuccess) { call_err_.device("hipStreamWaitEvent failed"); return -1; }
     uint32_t* const synd = d_synd_ + (size_t)frame_base * 8;
     BchArgs a;
     a.antilog = d_antilog_; a.log = d_log_; a.quad = d_quad_; a.hcol = reinterpret_cast<const uint4*>(d_hcol_); a.cw = d_cw; a.msg = d_msg; a.corr = d_corr; a.llr_state = d_llr_state; a.llr_stride = llr_stride;
@@ -563,7 +563,7 @@ int BchDecoderHip::decode_device(const uint8_t* d_cw, int n_frames, uint8_t* d_m
         const int chunks = std::max(1, std::min(steps, (8 * std::max(1, n_cus_) + tiles - 1) / tiles));
         const int spc = (steps + chunks - 1) / chunks;
         const dim3 sgrid((tiles + 3) / 4, (steps + spc - 1) / spc);
-        if (hipMemsetAsync(synd, 0, (size_t)n_frames * 32, stream) != hipSuccess) { call_err_ = "bch syndrome buffer reset failed"; return -1; }
+        if (hipMemsetAsync(synd, 0, (size_t)n_frames * 32, stream) != hipSuccess) { call_err_.device("bch syndrome buffer reset failed"); return -1; }
         const bool packed = d_cw != nullptr;
         const uint8_t* src = packed ? d_cw : d_llr_state;
         const size_t stride = packed ? (size_t)(code_.n / 8) : (size_t)llr_stride;
@@ -583,9 +583,9 @@ int BchDecoderHip::decode_device(const uint8_t* d_cw, int n_frames, uint8_t* d_m
     {
         InFlight& t = track_[track_next_];
         track_next_ = (track_next_ + 1) % kTrack;
-        if (!t.done && hipEventCreateWithFlags(&t.done, hipEventDisableTiming) != hipSuccess) { t.done = nullptr; call_err_ = "hipEventCreate failed"; (void)hipStreamSynchronize(stream); return -1; }
+        if (!t.done && hipEventCreateWithFlags(&t.done, hipEventDisableTiming) != hipSuccess) { t.done = nullptr; call_err_.device("hipEventCreate failed"); (void)hipStreamSynchronize(stream); return -1; }
         t.stream = stream; t.base = frame_base; t.n = n_frames;
-        if (hipEventRecord(t.done, stream) != hipSuccess) { call_err_ = "hipEventRecord failed"; (void)hipStreamSynchronize(stream); return -1; }
+        if (hipEventRecord(t.done, stream) != hipSuccess) { call_err_.device("hipEventRecord failed"); (void)hipStreamSynchronize(stream); return -1; }
     }
     return 0;
 }

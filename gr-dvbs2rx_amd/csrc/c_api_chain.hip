@@ -165,7 +165,7 @@ int dvbs2_chain_finish(dvbs2_chain_t* h)
     if (!h->pending) return DVBS2_OK;
     h->pending = false;
     const int r = h->ldpc->impl->finish(0); // waits for the stream: demapper, LDPC and BCH of this call are done
-    if (r < 0) return fail(DVBS2_EDEVICE, h->ldpc->impl->error());
+    if (r < 0) return impl_rc(h->ldpc, true);
     if (r > 0) { // the LDPC needed rounds beyond the enqueued ones and rewrote its output: run the BCH stage again
         int rc = chain_bch(h);
         if (rc != DVBS2_OK) return rc;
@@ -253,10 +253,10 @@ static int chain_decode_host(dvbs2_chain_t* h, const float* in_syms, const int8_
             const DemapFused dm = h->dm->impl->fused(dsy, dn0, n0_count > 1 ? nf : 1);
             erc = dec->enqueue(nullptr, nf, max_trials, DVBS2_OM_MESSAGE, nullptr, nullptr, hd_ret + f0 / G, st, c % kSlots, f0, &dm);
         } else {
-            if (in_syms && h->dm->impl->soft_device(dsy, nf, dn0, n0_count > 1 ? nf : 1, hd_llr + (size_t)f0 * N, st)) return fail(DVBS2_EDEVICE, h->dm->impl->error());
+            if (in_syms && h->dm->impl->soft_device(dsy, nf, dn0, n0_count > 1 ? nf : 1, hd_llr + (size_t)f0 * N, st)) return impl_rc(h->dm, true);
             erc = dec->enqueue(hd_llr + (size_t)f0 * N, nf, max_trials, DVBS2_OM_MESSAGE, nullptr, nullptr, hd_ret + f0 / G, st, c % kSlots, f0, nullptr);
         }
-        return erc ? fail(DVBS2_EDEVICE, dec->error()) : DVBS2_OK;
+        return impl_rc(h->ldpc, erc != 0);
     };
     call.after_ldpc = [&](int f0, int nf, hipStream_t st) -> int { return chain_bch_range(h, f0, nf, hd_msg + (size_t)f0 * mb, hd_corr + f0, st); };
     return host_pipe_run(h->pipe, dec, call);

@@ -7,9 +7,10 @@
 #include <cstdint>
 #include <new>
 #include <string>
-#include "device_guard.h"
+#include "device_stage.h"
 
 namespace dvbs2 {
+static_assert(kArgument == DVBS2_EINVAL && kDevice == DVBS2_EDEVICE && kSize == DVBS2_ESIZE, "the stage classes record the codes of the C ABI");
 
 extern thread_local std::string g_api_error; // the ONE string behind dvbs2_last_error, defined in c_api_core.hip
 inline int fail(int code, const std::string& msg) { g_api_error = msg; return code; }
@@ -67,9 +68,11 @@ template <class H> int null_out(H** h)
     return DVBS2_OK;
 }
 
-// The create sequence of every handle type H: make() constructs the implementation with new (std::nothrow). A constructor that failed
-// says so through ok() / error(): DVBS2_EINVAL, or, where hip_is_edevice, DVBS2_EDEVICE when the text names a hip call.
-template <class H, class Make> int make_handle(H** h, int device, bool hip_is_edevice, Make make)
+// failed: what a call into h->impl returned (non-zero: it left its code and text in error_code() / error())
+template <class H> int impl_rc(const H* h, bool failed) { return failed ? fail(h->impl->error_code(), h->impl->error()) : DVBS2_OK; }
+
+// The create sequence of every handle type H: make() constructs the implementation with new (std::nothrow); !ok(): its constructor failed.
+template <class H, class Make> int make_handle(H** h, int device, Make make)
 {
     if (int rc = null_out(h)) return rc;
     if (int rc = check_device(device)) return rc;
@@ -78,9 +81,9 @@ template <class H, class Make> int make_handle(H** h, int device, bool hip_is_ed
     o->device = device;
     o->impl = make();
     if (!o->impl || !o->impl->ok()) {
-        const std::string msg = o->impl ? o->impl->error() : "out of memory";
+        const int rc = o->impl ? impl_rc(o, true) : fail(DVBS2_EINVAL, "out of memory");
         delete o->impl; delete o;
-        return fail(hip_is_edevice && msg.find("hip") != std::string::npos ? DVBS2_EDEVICE : DVBS2_EINVAL, msg);
+        return rc;
     }
     *h = o;
     return DVBS2_OK;
@@ -104,8 +107,5 @@ template <class H> int check_frames(const H* h, int n_frames, bool buffers_ok, b
     if (n_frames > h->impl->max_frames()) return fail(DVBS2_ESIZE, "n_frames exceeds max_frames");
     return DVBS2_OK;
 }
-
-// failed: what a call into h->impl returned (non-zero: it left its text in error())
-template <class H> int impl_rc(const H* h, bool failed) { return failed ? fail(DVBS2_EDEVICE, h->impl->error()) : DVBS2_OK; }
 
 } // namespace dvbs2

@@ -8,7 +8,7 @@ using namespace dvbs2;
 /* ------------------------------------------------------------------ BCH */
 static int bch_make(dvbs2_bch_t** h, int m, uint32_t prim_poly, int t, int n, int max_frames, int device)
 {
-    return make_handle(h, device, true, [&] { return new (std::nothrow) BchDecoderHip(m, prim_poly, t, n, max_frames, device); });
+    return make_handle(h, device, [&] { return new (std::nothrow) BchDecoderHip(m, prim_poly, t, n, max_frames, device); });
 }
 
 static void bch_field(int framesize, int* m, uint32_t* prim)
@@ -103,7 +103,7 @@ int dvbs2_bch_decode(dvbs2_bch_t* h, const uint8_t* cw, int n_frames, uint8_t* m
 int dvbs2_demap_create(dvbs2_demap_t** h, int framesize, int rate, int constellation, int max_frames, int device)
 {
     API_TRY
-    return make_handle(h, device, false, [&] { return new (std::nothrow) DemapperHip(framesize, rate, constellation, max_frames, device); });
+    return make_handle(h, device, [&] { return new (std::nothrow) DemapperHip(framesize, rate, constellation, max_frames, device); });
     API_CATCH
 }
 

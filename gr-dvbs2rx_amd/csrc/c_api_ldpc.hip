@@ -10,7 +10,7 @@ static int ldpc_make(dvbs2_ldpc_t** h, const LdpcTableDesc* t, int message_bits,
 {
     if (int rc = null_out(h)) return rc;
     if (!t) return fail(DVBS2_EINVAL, "unknown LDPC table");
-    if (int rc = make_handle(h, device, true, [&] { return new (std::nothrow) LdpcDecoderHip(t, message_bits, G, max_frames, device); })) return rc;
+    if (int rc = make_handle(h, device, [&] { return new (std::nothrow) LdpcDecoderHip(t, message_bits, G, max_frames, device); })) return rc;
     if (const char* e = getenv("DVBS2_HOST_PLAN")) (*h)->host_plan = e;
     if (const char* e = getenv("DVBS2_HOST_CHUNK")) (*h)->host_chunk = std::max(2, atoi(e));
     if (const char* e = getenv("DVBS2_HOST_COPY_STREAM")) (*h)->host_copy_stream = atoi(e) != 0 ? 1 : 0;

@@ -29,7 +29,7 @@ int dvbs2_pl_scrambling_rn(int gold_code, uint8_t* rn, int n)
 int dvbs2_plpayload_create(dvbs2_plpayload_t** h, int gold_code, int n_slots, int has_pilots, int max_frames, int device)
 {
     API_TRY
-    return make_handle(h, device, false, [&] { return new (std::nothrow) PlPayloadHip(gold_code, n_slots, has_pilots, max_frames, device); });
+    return make_handle(h, device, [&] { return new (std::nothrow) PlPayloadHip(gold_code, n_slots, has_pilots, max_frames, device); });
     API_CATCH
 }
 
@@ -174,7 +174,7 @@ int dvbs2_plframe_create(dvbs2_plframe_t** h, int gold_code, int plsc, int max_f
     if (plsc < 0 || plsc > 127) return fail(DVBS2_EINVAL, "plsc out of range (0..127)");
     { const PlsInfo p = pls_parse(plsc); if (p.n_mod == 0 && !p.dummy_frame) return fail(DVBS2_EINVAL, "plsc names a reserved MODCOD (29..31)"); }
     if (gold_code < 0 || gold_code >= (1 << 18) - 1) return fail(DVBS2_EINVAL, "gold code out of range");
-    return make_handle(h, device, false, [&] { return new (std::nothrow) PlFrameHip(gold_code, plsc, max_frames, device); });
+    return make_handle(h, device, [&] { return new (std::nothrow) PlFrameHip(gold_code, plsc, max_frames, device); });
     API_CATCH
 }
 
@@ -199,8 +199,7 @@ int dvbs2_plframe_set_expected_pls(dvbs2_plframe_t* h, const uint8_t* plsc_list,
     API_TRY
     NEED_HANDLE(h);
     if (n < 0 || (n > 0 && !plsc_list)) return fail(DVBS2_EINVAL, "bad argument");
-    if (int rc = h->impl->set_expected_pls(plsc_list, n)) return fail(rc == -1 ? DVBS2_EINVAL : DVBS2_EDEVICE, h->impl->error());
-    return DVBS2_OK;
+    return impl_rc(h, h->impl->set_expected_pls(plsc_list, n));
     API_CATCH
 }
 
@@ -282,7 +281,7 @@ int dvbs2_plsync_create(dvbs2_plsync_t** h, int plsc_or_minus1, int unlock_thres
     if (unlock_thresh < 1 || unlock_thresh > 255) return fail(DVBS2_EINVAL, "unlock_thresh out of range (1..255)");
     if (max_symbols < kPlsyncMinSymbols) return fail(DVBS2_EINVAL, "max_symbols must be at least 33282 + 90");
     if (max_frames < 1 || max_frames > (1 << 20)) return fail(DVBS2_EINVAL, "max_frames out of range (1..1048576)");
-    return make_handle(h, device, false, [&] { return new (std::nothrow) PlSyncHip(plsc_or_minus1, unlock_thresh, max_symbols, max_frames, device); });
+    return make_handle(h, device, [&] { return new (std::nothrow) PlSyncHip(plsc_or_minus1, unlock_thresh, max_symbols, max_frames, device); });
     API_CATCH
 }
 
@@ -308,8 +307,7 @@ int dvbs2_plsync_set_expected_pls(dvbs2_plsync_t* h, const uint8_t* plsc_list, i
     API_TRY
     NEED_HANDLE(h);
     if (n < 0 || (n > 0 && !plsc_list)) return fail(DVBS2_EINVAL, "bad argument");
-    if (int rc = h->impl->set_expected_pls(plsc_list, n)) return fail(rc == -1 ? DVBS2_EINVAL : DVBS2_EDEVICE, h->impl->error());
-    return DVBS2_OK;
+    return impl_rc(h, h->impl->set_expected_pls(plsc_list, n));
     API_CATCH
 }
 
@@ -404,7 +402,7 @@ int dvbs2_plcoarse_create(dvbs2_plcoarse_t** h, int period, int plsc_or_minus1, 
     if (period < 1) return fail(DVBS2_EINVAL, "period must be at least 1");
     if (plsc_or_minus1 < -1 || plsc_or_minus1 > 127) return fail(DVBS2_EINVAL, "plsc out of range (-1 = not known, 0..127)");
     if (max_frames < 1 || max_frames > (1 << 20)) return fail(DVBS2_EINVAL, "max_frames out of range (1..1048576)");
-    return make_handle(h, device, false, [&] { return new (std::nothrow) PlCoarseHip(period, plsc_or_minus1, max_frames, device); });
+    return make_handle(h, device, [&] { return new (std::nothrow) PlCoarseHip(period, plsc_or_minus1, max_frames, device); });
     API_CATCH
 }
 

@@ -23,7 +23,7 @@ int dvbs2_rotator_create(dvbs2_rotator_t** h, double phase_inc, int device)
     API_TRY
     if (int rc = null_out(h)) return rc;
     if (!(phase_inc == phase_inc) || phase_inc - phase_inc != 0.0) return fail(DVBS2_EINVAL, "phase_inc must be finite");
-    return make_handle(h, device, false, [&] { return new (std::nothrow) RotatorHip(phase_inc, device); });
+    return make_handle(h, device, [&] { return new (std::nothrow) RotatorHip(phase_inc, device); });
     API_CATCH
 }
 
@@ -40,8 +40,7 @@ int dvbs2_rotator_set_phase_inc(dvbs2_rotator_t* h, double phase_inc)
 {
     API_TRY
     NEED_HANDLE(h);
-    if (h->impl->set_phase_inc(phase_inc)) return fail(DVBS2_EINVAL, h->impl->error());
-    return DVBS2_OK;
+    return impl_rc(h, h->impl->set_phase_inc(phase_inc));
     API_CATCH
 }
 
@@ -49,8 +48,7 @@ int dvbs2_rotator_schedule(dvbs2_rotator_t* h, int64_t offset, double phase_inc)
 {
     API_TRY
     NEED_HANDLE(h);
-    if (h->impl->schedule(offset, phase_inc)) return fail(DVBS2_EINVAL, h->impl->error());
-    return DVBS2_OK;
+    return impl_rc(h, h->impl->schedule(offset, phase_inc));
     API_CATCH
 }
 
@@ -58,8 +56,7 @@ int dvbs2_rotator_seek(dvbs2_rotator_t* h, int64_t n_syms)
 {
     API_TRY
     NEED_HANDLE(h);
-    if (h->impl->seek(n_syms)) return fail(DVBS2_EINVAL, h->impl->error());
-    return DVBS2_OK;
+    return impl_rc(h, h->impl->seek(n_syms));
     API_CATCH
 }
 
@@ -87,7 +84,7 @@ int dvbs2_rotator_measure(int device, int n_syms, int regions, double* rotate_ms
     if (!rotate_ms || !copy_ms) return fail(DVBS2_EINVAL, "bad argument");
     if (int rc = check_device(device)) return rc;
     std::string err;
-    if (rotator_measure(device, n_syms, regions, rotate_ms, copy_ms, &err)) return fail(err == "bad argument" ? DVBS2_EINVAL : DVBS2_EDEVICE, err);
+    if (int rc = rotator_measure(device, n_syms, regions, rotate_ms, copy_ms, &err)) return fail(rc, err);
     return DVBS2_OK;
     API_CATCH
 }
@@ -127,7 +124,7 @@ static int symsync_make(dvbs2_symsync_t** h, int sps, float loop_bw, float dampi
     // arguments first: a bad argument is the caller's mistake on any machine
     const std::string bad = SymSyncHip::check_args(sps, loop_bw, damping, rolloff, rrc_delay, n_subfilt, interp_method, max_streams, max_samples);
     if (!bad.empty()) return fail(DVBS2_EINVAL, bad);
-    return make_handle(h, device, false, [&] {
+    return make_handle(h, device, [&] {
         return new (std::nothrow) SymSyncHip(sps, loop_bw, damping, rolloff, rrc_delay, n_subfilt, interp_method, bank, max_streams, max_samples, device);
     });
 }
@@ -281,7 +278,7 @@ extern "C" {
 int dvbs2_bbdeheader_create_raw(dvbs2_bbdeheader_t** h, int kbch_bits, int max_frames, int device)
 {
     API_TRY
-    return make_handle(h, device, false, [&] { return new (std::nothrow) BbDeheaderHip(kbch_bits, max_frames, device); });
+    return make_handle(h, device, [&] { return new (std::nothrow) BbDeheaderHip(kbch_bits, max_frames, device); });
     API_CATCH
 }
 

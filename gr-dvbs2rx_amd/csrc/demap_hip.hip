@@ -230,20 +230,20 @@ DemapperHip::DemapperHip(int framesize, int rate, int constellation, int max_fra
     } else if (constellation == DVBS2_MOD_16APSK || constellation == DVBS2_MOD_32APSK) {
         n_mod_ = constellation == DVBS2_MOD_16APSK ? 4 : 5;
         float p[64];
-        if (framesize == DVBS2_FECFRAME_MEDIUM) { err_ = "Unsupported frame size for 16APSK / 32APSK (normal and short only)"; return; }
+        if (framesize == DVBS2_FECFRAME_MEDIUM) { err_.argument("Unsupported frame size for 16APSK / 32APSK (normal and short only)"); return; }
         if (!apsk_points(constellation, rate, p) || (rate == 11 && framesize != DVBS2_FECFRAME_NORMAL)) {
-            err_ = "Unsupported code rate for 16APSK / 32APSK (DVB-S2: 16APSK 2/3 .. 9/10, 32APSK 3/4 .. 9/10; 9/10 normal frames only)"; return;
+            err_.argument("Unsupported code rate for 16APSK / 32APSK (DVB-S2: 16APSK 2/3 .. 9/10, 32APSK 3/4 .. 9/10; 9/10 normal frames only)"); return;
         }
         for (int i = 0; i < (1 << n_mod_); i++) { apsk_.re[i] = p[2 * i]; apsk_.im[i] = p[2 * i + 1]; }
-    } else { err_ = "Unsupported constellation"; return; }
-    if (max_frames_ < 1 || max_frames_ > 65535) { err_ = "max_frames must be in 1..65535 (frames are one launch dimension)"; return; }
+    } else { err_.argument("Unsupported constellation"); return; }
+    if (max_frames_ < 1 || max_frames_ > 65535) { err_.argument("max_frames must be in 1..65535 (frames are one launch dimension)"); return; }
 }
 
 int DemapperHip::soft_device(const float* d_syms, int n_frames, const float* d_n0, int n0_count, int8_t* d_llr, hipStream_t stream)
 {
     Entry on(*this);
     if (!on.ok) return -1;
-    if (n_frames < 0 || n_frames > max_frames_) { call_err_ = "n_frames exceeds max_frames"; return -1; }
+    if (n_frames < 0 || n_frames > max_frames_) { call_err_.device("n_frames exceeds max_frames"); return -1; } // (argument text, kDevice: notes/stage_error_codes.md)
     if (n_frames == 0) return 0;
     if (constellation_ == DVBS2_MOD_QPSK) {
         const int quads = n_llr_ / 4;
@@ -284,7 +284,7 @@ int DemapperHip::snr_device(const float* d_syms, const int8_t* d_ref_llr, int n_
 {
     Entry on(*this);
     if (!on.ok) return -1;
-    if (n_frames < 0 || n_frames > max_frames_) { call_err_ = "n_frames exceeds max_frames"; return -1; }
+    if (n_frames < 0 || n_frames > max_frames_) { call_err_.device("n_frames exceeds max_frames"); return -1; } // (argument text, kDevice: notes/stage_error_codes.md)
     if (n_frames == 0) return 0;
     const float rr = (float)std::cos(-M_PI / 8), ri = (float)std::sin(-M_PI / 8);
     const int rows = n_syms();

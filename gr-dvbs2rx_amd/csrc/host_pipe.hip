@@ -64,7 +64,7 @@ int host_pipe_run(HostPipe& p, LdpcDecoderHip* dec, const HostCall& call)
     auto finish = [&](int c) -> int {
         hipStream_t st = p.stream[c % kSlots];
         const int r = dec->finish(c % kSlots);
-        if (r < 0) return fail(DVBS2_EDEVICE, dec->error());
+        if (r < 0) return fail(dec->error_code(), dec->error());
         if (r > 0) { // the LDPC needed rounds beyond the enqueued ones and rewrote its output: what follows it again, and the copies
             if (call.after_ldpc) if (int rc = call.after_ldpc(call.plan[c].first, call.plan[c].second, st)) return rc;
             if (int rc = copy_out(c)) return rc;

@@ -122,18 +122,18 @@ const SweepOps& sweep_ops(bool pr, int dmax)
 LdpcDecoderHip::LdpcDecoderHip(const LdpcTableDesc* table, int out_bits_message, int group_size, int max_frames, int device)
     : DeviceStage(device), out_bits_message_(out_bits_message), G_(group_size), max_frames_(max_frames)
 {
-    if (!compile_ldpc_schedule(table, &sched_)) { err_ = "unknown or inconsistent LDPC table"; return; }
-    if (G_ < 1 || max_frames_ < 1 || max_frames_ > 65535) { err_ = "bad group_size/max_frames (max_frames 1..65535: frames are one launch dimension)"; return; }
-    if (out_bits_message_ <= 0 || out_bits_message_ > sched_.N || out_bits_message_ % 8) { err_ = "bad message length"; return; }
+    if (!compile_ldpc_schedule(table, &sched_)) { err_.argument("unknown or inconsistent LDPC table"); return; }
+    if (G_ < 1 || max_frames_ < 1 || max_frames_ > 65535) { err_.argument("bad group_size/max_frames (max_frames 1..65535: frames are one launch dimension)"); return; }
+    if (out_bits_message_ <= 0 || out_bits_message_ > sched_.N || out_bits_message_ % 8) { err_.argument("bad message length"); return; }
     // which build of the sweep kernel, and the records laid out for it: the host-only planner (ldpc_plan.cpp)
     const LdpcOverrides ov = LdpcOverrides::from_env();
     const LdpcPlan plan = plan_ldpc(sched_, table->name, G_, ov);
-    if (!plan.error.empty()) { err_ = plan.error; return; }
+    if (!plan.error.empty()) { err_.argument(plan.error); return; }
     build_ = plan.build; pr_ = plan.pr; pr_shared_sv_ = plan.pr_shared_sv; gsync_on_ = plan.gsync_on; dmax_ = plan.dmax; words_per_check_ = plan.words_per_check;
     resolve_rounds_ = plan.resolve_rounds; lds_bytes_ = plan.lds_bytes; kname_ = plan.kernel_name;
 
     DeviceGuard dev_guard(device_); // the caller's current device is restored when the constructor returns (device_guard.h)
-    if (!dev_guard.ok) { err_ = "hipSetDevice failed"; return; }
+    if (!dev_guard.ok) { err_.device("hipSetDevice failed"); return; }
     HIP_OK_AS("hipMalloc(&d_recs_alloc_, (plan.recs.size() + kRecHeaderWords) * 4)", alloc(&d_recs_alloc_, plan.recs.size() + kRecHeaderWords)); // header (group-synchronous stop, filled below) + records
     d_recs_ = d_recs_alloc_ + kRecHeaderWords;
     HIP_OK(hipMemcpy(d_recs_, plan.recs.data(), plan.recs.size() * 4, hipMemcpyHostToDevice));
@@ -167,10 +167,10 @@ LdpcDecoderHip::LdpcDecoderHip(const LdpcTableDesc* table, int out_bits_message,
         HIP_OK(hipGetDevice(&dv));
         std::string e;
         int* slots = cu_slot_table(dv, &e);
-        if (!slots) { err_ = e; return; }
+        if (!slots) { err_.device(e); return; }
         d_cu_slots_ = slots;
     }
-    HIP_OK(sweep_ops(pr_, dmax_).prepare(build_, lds_bytes_, plan.solo_lds_bytes));
+    if (!hip_ok(sweep_ops(pr_, dmax_).prepare(build_, lds_bytes_, plan.solo_lds_bytes), "sweep_ops(pr_, dmax_).prepare(build_, lds_bytes_, plan.solo_lds_bytes)", err_, kArgument)) return; // (device failure, kArgument: notes/stage_error_codes.md)
 }
 
 LdpcDecoderHip::~LdpcDecoderHip()
@@ -264,12 +264,12 @@ int LdpcDecoderHip::enqueue(const int8_t* d_llr_in, int n_frames, int max_trials
                             int32_t* d_ret, hipStream_t stream, int slot, int frame_base, const DemapFused* dm)
 {
     if (!ok()) return -1;
-    call_err_.clear();
-    if (slot < 0 || slot >= kSlots) { call_err_ = "bad slot"; return -1; }
-    if (pend_[slot].active) { call_err_ = "slot busy: finish() the previous decode first"; return -1; }
-    if (n_frames < 0 || frame_base < 0 || frame_base + n_frames > max_frames_) { call_err_ = "n_frames exceeds max_frames"; return -1; }
-    if (frame_base % 2 || (frame_base && frame_base % G_)) { call_err_ = "frame_base must be a multiple of the group size and even"; return -1; }
-    if (max_trials < 0) { call_err_ = "max_trials < 0"; return -1; }
+    call_err_ = {};
+    if (slot < 0 || slot >= kSlots) { call_err_.device("bad slot"); return -1; } // (argument text, kDevice: notes/stage_error_codes.md)
+    if (pend_[slot].active) { call_err_.device("slot busy: finish() the previous decode first"); return -1; } // (argument text, kDevice: notes/stage_error_codes.md)
+    if (n_frames < 0 || frame_base < 0 || frame_base + n_frames > max_frames_) { call_err_.device("n_frames exceeds max_frames"); return -1; } // (argument text, kDevice: notes/stage_error_codes.md)
+    if (frame_base % 2 || (frame_base && frame_base % G_)) { call_err_.device("frame_base must be a multiple of the group size and even"); return -1; } // (argument text, kDevice: notes/stage_error_codes.md)
+    if (max_trials < 0) { call_err_.device("max_trials < 0"); return -1; } // (argument text, kDevice: notes/stage_error_codes.md)
     Pending& p = pend_[slot];
     // a call that fails below leaves the slot free again (the handle stays usable: "a failed call does not disable the handle")
     // (and nothing of it stays in flight: kernels and copies already queued on the stream are waited for before the slot is given up)
@@ -280,7 +280,7 @@ int LdpcDecoderHip::enqueue(const int8_t* d_llr_in, int n_frames, int max_trials
     if (n_frames == 0) { release.armed = false; return 0; }
     Entry on(*this);
     if (!on.ok) return -1;
-    if (dm && dm->mode && pr_) { call_err_ = "this sweep kernel does not demap while loading"; return -1; }
+    if (dm && dm->mode && pr_) { call_err_.device("this sweep kernel does not demap while loading"); return -1; } // (argument text, kDevice: notes/stage_error_codes.md)
     release.launched = true;
     launch_sweep(d_llr_in, false, 1, n_frames, max_trials, frame_base, stream, dm);
     if (d_tdbg_ && dump_timing(n_frames, max_trials, stream)) return -1;
@@ -301,7 +301,7 @@ int LdpcDecoderHip::enqueue(const int8_t* d_llr_in, int n_frames, int max_trials
 int LdpcDecoderHip::finish(int slot)
 {
     if (!ok()) return -1;
-    if (slot < 0 || slot >= kSlots) { call_err_ = "bad slot"; return -1; }
+    if (slot < 0 || slot >= kSlots) { call_err_.device("bad slot"); return -1; } // (argument text, kDevice: notes/stage_error_codes.md)
     Pending& p = pend_[slot];
     if (!p.active) return 0;
     p.active = false;
@@ -312,7 +312,7 @@ int LdpcDecoderHip::finish(int slot)
     if (h_flag_[slot] == 0) return 0;
     struct Drain { hipStream_t st; bool armed = true; ~Drain() { if (armed) (void)hipStreamSynchronize(st); } } drain{ p.stream }; // a failing round leaves nothing in flight
     for (int round = 0; h_flag_[slot] != 0; round++) { // the rare leftovers, one host round trip each
-        if (round > 2 * p.max_trials + 2) { call_err_ = "group resolution did not converge"; return -1; }
+        if (round > 2 * p.max_trials + 2) { call_err_.device("group resolution did not converge"); return -1; }
         fallback_rounds_++;
         launch_sweep(nullptr, true, 0, p.n_frames, p.max_trials, p.frame_base, p.stream);
         launch_targets(p.n_frames, p.max_trials, p.frame_base, p.ret, slot, p.stream);

@@ -167,9 +167,9 @@ PlCoarseHip::PlCoarseHip(int period, int plsc_or_minus1, int max_frames, int dev
     if (!dev_guard.ok || alloc(&d_cw_, 128) != hipSuccess || alloc(&d_w_, 89 + 25) != hipSuccess ||
         alloc(&d_r_, (size_t)max_frames_ * kPlcoarseRecord) != hipSuccess || alloc(&d_state_, 1) != hipSuccess ||
         hipMemcpy(d_cw_, cw, sizeof(cw), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_w_, w, sizeof(w), hipMemcpyHostToDevice) != hipSuccess) {
-        err_ = "device setup failed"; return;
+        err_.argument("device setup failed"); return; // (device failure, kArgument: notes/stage_error_codes.md)
     }
-    if (reset()) { err_ = call_err_; call_err_.clear(); }
+    if (reset()) { err_.argument(call_err_.text); call_err_ = {}; } // (device failure, kArgument: notes/stage_error_codes.md)
 }
 
 int PlCoarseHip::reset()
@@ -177,7 +177,7 @@ int PlCoarseHip::reset()
     Entry on(*this);
     // all zero: no frame counted, empty accumulator, estimate 0, not coarse-corrected (lib/pl_freq_sync.cc:24-31)
     if (!on.ok || hipDeviceSynchronize() != hipSuccess || hipMemset(d_state_, 0, sizeof(PlCoarseState)) != hipSuccess) {
-        call_err_ = "reset of the device state failed"; return -2;
+        call_err_.device("reset of the device state failed"); return -1;
     }
     return 0;
 }
@@ -187,7 +187,7 @@ int PlCoarseHip::launch(const float2* x, int64_t stride, const uint8_t* plsc, co
 {
     Entry on(*this);
     if (!on.ok) return -1;
-    if (n_frames < 0 || n_frames > max_frames_) { call_err_ = "n_frames exceeds max_frames"; return -1; }
+    if (n_frames < 0 || n_frames > max_frames_) { call_err_.device("n_frames exceeds max_frames"); return -1; } // (argument text, kDevice: notes/stage_error_codes.md)
     if (n_frames == 0) return 0;
     hipLaunchKernelGGL(plcoarse_autocorr_kernel, dim3(n_frames), dim3(64), 0, stream, x, (long long)stride, plsc, fixed_plsc_ < 0 ? 0 : fixed_plsc_,
                        rec, n_syms, (long long)base, d_cw_, d_r_);

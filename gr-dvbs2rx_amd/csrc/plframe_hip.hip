@@ -169,14 +169,14 @@ PlFrameHip::PlFrameHip(int gold_code, int plsc, int max_frames, int device) : De
 {
     pls_ = pls_parse(plsc);
     pp_ = new (std::nothrow) PlPayloadHip(gold_code, pls_.n_slots, pls_.has_pilots, max_frames, device);
-    if (!pp_) { err_ = "out of memory"; return; }
-    if (!pp_->ok()) { err_ = pp_->error(); return; }
+    if (!pp_) { err_.argument("out of memory"); return; } // (no argument, kArgument: notes/stage_error_codes.md)
+    if (!pp_->ok()) { err_ = { pp_->error_code(), pp_->error() }; return; }
     DeviceGuard dev_guard(device_);
     const size_t npar = (size_t)max_frames_ * (2 + (pls_.n_pilots ? pls_.n_pilots : 1));
     if (!dev_guard.ok || alloc(&d_rank_, 128) != hipSuccess || alloc(&d_par_, npar) != hipSuccess) {
-        err_ = "device setup failed"; return;
+        err_.argument("device setup failed"); return; // (device failure, kArgument: notes/stage_error_codes.md)
     }
-    if (set_expected_pls(nullptr, 0)) { err_ = call_err_; call_err_.clear(); }
+    if (set_expected_pls(nullptr, 0)) { err_.argument(call_err_.text); call_err_ = {}; } // (device failure, kArgument: notes/stage_error_codes.md)
 }
 
 PlFrameHip::~PlFrameHip() { delete pp_; }
@@ -185,8 +185,8 @@ int PlFrameHip::set_expected_pls(const uint8_t* list, int n)
 {
     Entry on(*this);
     uint8_t rank[128];
-    if (!pls_rank_table(list, n, rank)) { call_err_ = "codeword indexes must be within [0, 128)"; return -1; } // lib/reed_muller.cc:48-52
-    if (!on.ok || hipMemcpy(d_rank_, rank, 128, hipMemcpyHostToDevice) != hipSuccess) { call_err_ = "copy of the codeword list failed"; return -2; }
+    if (!pls_rank_table(list, n, rank)) { call_err_.argument("codeword indexes must be within [0, 128)"); return -1; } // lib/reed_muller.cc:48-52
+    if (!on.ok || hipMemcpy(d_rank_, rank, 128, hipMemcpyHostToDevice) != hipSuccess) { call_err_.device("copy of the codeword list failed"); return -1; }
     return 0;
 }
 
@@ -195,7 +195,7 @@ int PlFrameHip::run_device(const float* d_plframes, int n_frames, int has_traili
 {
     Entry on(*this);
     if (!on.ok) return -1;
-    if (n_frames < 0 || n_frames > max_frames_) { call_err_ = "n_frames exceeds max_frames"; return -1; }
+    if (n_frames < 0 || n_frames > max_frames_) { call_err_.device("n_frames exceeds max_frames"); return -1; } // (argument text, kDevice: notes/stage_error_codes.md)
     if (n_frames == 0) return 0;
     float* d_hph = d_par_; float* d_inc = d_par_ + max_frames_; float* d_pil = d_par_ + 2 * (size_t)max_frames_;
     hipLaunchKernelGGL(pl_estimate_kernel, dim3(n_frames), dim3(64), 0, stream, reinterpret_cast<const float2*>(d_plframes), pp_->d_rn(),
@@ -203,10 +203,9 @@ int PlFrameHip::run_device(const float* d_plframes, int n_frames, int has_traili
                        pls_.n_pilots, n_frames, has_trailing_header ? 1 : 0, coherent_, soft_, d_hph, d_inc, d_pil, est);
     if (launched("pl estimate kernel launch")) return -1;
     if (!d_out) return 0;
-    if (pp_->process_device_strided(d_plframes, pls_.plframe_len, 90, n_frames, d_hph, d_inc, d_coarse_corrected, d_pil, d_out, stream)) {
-        call_err_ = pp_->error(); return -1;
-    }
-    return 0;
+    if (!pp_->process_device_strided(d_plframes, pls_.plframe_len, 90, n_frames, d_hph, d_inc, d_coarse_corrected, d_pil, d_out, stream)) return 0;
+    call_err_ = { pp_->error_code(), pp_->error() }; // what the payload stage recorded
+    return -1;
 }
 
 } // namespace dvbs2

@@ -51,14 +51,14 @@ PlPayloadHip::PlPayloadHip(int gold_code, int n_slots, int has_pilots, int max_f
     : DeviceStage(device), n_slots_(n_slots), has_pilots_(has_pilots ? 1 : 0), max_frames_(max_frames)
 {
     n_pilots_ = has_pilots_ ? ((n_slots_ - 1) >> 4) : 0; // lib/pl_signaling.cc:51
-    if (n_slots_ < 36 || n_slots_ > 360) { err_ = "n_slots out of range (36..360)"; return; } // lib/pl_defs.h:19-20
-    if (gold_code < 0 || gold_code >= (1 << 18) - 1) { err_ = "gold code out of range"; return; }
-    if (max_frames_ < 1 || max_frames_ > 65535) { err_ = "max_frames must be in 1..65535 (frames are one launch dimension)"; return; }
+    if (n_slots_ < 36 || n_slots_ > 360) { err_.argument("n_slots out of range (36..360)"); return; } // lib/pl_defs.h:19-20
+    if (gold_code < 0 || gold_code >= (1 << 18) - 1) { err_.argument("gold code out of range"); return; }
+    if (max_frames_ < 1 || max_frames_ > 65535) { err_.argument("max_frames must be in 1..65535 (frames are one launch dimension)"); return; }
     std::vector<uint8_t> rn(payload_len());
     pl_scrambling_rn(gold_code, rn.data(), (int)rn.size());
     DeviceGuard dev_guard(device_); // the caller's current device is restored on return
     if (!dev_guard.ok || alloc(&d_rn_, rn.size()) != hipSuccess ||
-        hipMemcpy(d_rn_, rn.data(), rn.size(), hipMemcpyHostToDevice) != hipSuccess) { err_ = "device setup failed"; return; }
+        hipMemcpy(d_rn_, rn.data(), rn.size(), hipMemcpyHostToDevice) != hipSuccess) { err_.argument("device setup failed"); return; } // (device failure, kArgument: notes/stage_error_codes.md)
 }
 
 int PlPayloadHip::process_device(const float* d_payload, int n_frames, const float* d_plheader_phase, const float* d_phase_inc,
@@ -74,7 +74,7 @@ int PlPayloadHip::process_device_strided(const float* d_in, int frame_stride, in
 {
     Entry on(*this);
     if (!on.ok) return -1;
-    if (n_frames < 0 || n_frames > max_frames_) { call_err_ = "n_frames exceeds max_frames"; return -1; }
+    if (n_frames < 0 || n_frames > max_frames_) { call_err_.device("n_frames exceeds max_frames"); return -1; } // (argument text, kDevice: notes/stage_error_codes.md)
     if (n_frames == 0) return 0;
     hipLaunchKernelGGL(pl_payload_kernel, dim3((xfecframe_len() + 255) / 256, n_frames), dim3(256), 0, stream,
                        reinterpret_cast<const float2*>(d_in), d_rn_, d_plheader_phase, d_phase_inc, d_coarse_corrected,

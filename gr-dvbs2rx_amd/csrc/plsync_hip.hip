@@ -230,23 +230,23 @@ PlSyncHip::PlSyncHip(int plsc_or_minus1, int unlock_thresh, int max_symbols, int
     // the compile-time tap signs against the expected symbols, the device's frame length against pls_parse
     float sof[25], pl[32];
     plsync_taps(sof, pl);
-    for (int k = 1; k <= 25; k++) if ((sof[k - 1] < 0.0f) != tap_minus(k)) { err_ = "SOF tap signs disagree with the PLHEADER"; return; }
-    for (int i = 0; i < 32; i++) if ((pl[i] < 0.0f) != tap_minus(27 + 2 * i)) { err_ = "PLSC tap signs disagree with the PLHEADER"; return; }
-    for (int p = 0; p < 128; p++) if (plsync_frame_len(p) != pls_parse(p).plframe_len) { err_ = "frame length disagrees with pls_parse"; return; }
+    for (int k = 1; k <= 25; k++) if ((sof[k - 1] < 0.0f) != tap_minus(k)) { err_.argument("SOF tap signs disagree with the PLHEADER"); return; }
+    for (int i = 0; i < 32; i++) if ((pl[i] < 0.0f) != tap_minus(27 + 2 * i)) { err_.argument("PLSC tap signs disagree with the PLHEADER"); return; }
+    for (int p = 0; p < 128; p++) if (plsync_frame_len(p) != pls_parse(p).plframe_len) { err_.argument("frame length disagrees with pls_parse"); return; }
     DeviceGuard dev_guard(device_);
     if (!dev_guard.ok || alloc(&d_rank_, 128) != hipSuccess || alloc(&d_metric_, (size_t)max_symbols_) != hipSuccess ||
         alloc(&d_hist_, 2 * kHist) != hipSuccess || alloc(&d_state_, 1) != hipSuccess) {
-        err_ = "device setup failed"; return;
+        err_.argument("device setup failed"); return; // (device failure, kArgument: notes/stage_error_codes.md)
     }
-    if (set_expected_pls(nullptr, 0) || reset()) { err_ = call_err_; call_err_.clear(); }
+    if (set_expected_pls(nullptr, 0) || reset()) { err_.argument(call_err_.text); call_err_ = {}; } // (device failure, kArgument: notes/stage_error_codes.md)
 }
 
 int PlSyncHip::set_expected_pls(const uint8_t* list, int n)
 {
     Entry on(*this);
     uint8_t rank[128];
-    if (!pls_rank_table(list, n, rank)) { call_err_ = "codeword indexes must be within [0, 128)"; return -1; } // lib/reed_muller.cc:48-52
-    if (!on.ok || hipMemcpy(d_rank_, rank, 128, hipMemcpyHostToDevice) != hipSuccess) { call_err_ = "copy of the codeword list failed"; return -2; }
+    if (!pls_rank_table(list, n, rank)) { call_err_.argument("codeword indexes must be within [0, 128)"); return -1; } // lib/reed_muller.cc:48-52
+    if (!on.ok || hipMemcpy(d_rank_, rank, 128, hipMemcpyHostToDevice) != hipSuccess) { call_err_.device("copy of the codeword list failed"); return -1; }
     return 0;
 }
 
@@ -258,7 +258,7 @@ int PlSyncHip::reset()
     s.abs_last_peak = -1; // d_sym_cnt = 0 before the first symbol (lib/pl_frame_sync.cc:23)
     s.frame_len = fixed_plsc_ >= 0 ? plsync_frame_len(fixed_plsc_) : 0; // lib/plsync_cc_impl.cc:159, lib/pl_frame_sync.cc:28
     if (!on.ok || hipMemcpy(d_state_, &s, sizeof(s), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemset(d_hist_, 0, 2 * kHist * sizeof(float2)) != hipSuccess) { call_err_ = "reset of the device state failed"; return -2; }
+        hipMemset(d_hist_, 0, 2 * kHist * sizeof(float2)) != hipSuccess) { call_err_.device("reset of the device state failed"); return -1; }
     return 0;
 }
 
@@ -276,7 +276,7 @@ int PlSyncHip::search_device(const float* d_syms, int n_syms, PlSyncFrame* d_fra
 {
     Entry on(*this);
     if (!on.ok) return -1;
-    if (n_syms < 0 || n_syms > max_symbols_) { call_err_ = "n_syms exceeds max_symbols"; return -1; }
+    if (n_syms < 0 || n_syms > max_symbols_) { call_err_.device("n_syms exceeds max_symbols"); return -1; } // (argument text, kDevice: notes/stage_error_codes.md)
     if (metric_device(d_syms, n_syms, d_metric_, stream)) return -1;
     hipLaunchKernelGGL(plsync_track_kernel, dim3(1), dim3(64), 0, stream, reinterpret_cast<const float2*>(d_syms), n_syms, d_metric_, d_hist_,
                        d_state_, d_rank_, d_frames, max_frames_, fixed_plsc_, unlock_thresh_, coherent_, soft_);
@@ -290,7 +290,7 @@ int PlSyncHip::finish(int* n_frames, int* consumed, int* state)
     Entry on(*this);
     PlSyncState s;
     if (!on.ok || hipStreamSynchronize(last_stream_) != hipSuccess ||
-        hipMemcpy(&s, d_state_, sizeof(s), hipMemcpyDeviceToHost) != hipSuccess) { call_err_ = "reading the device state failed"; return -1; }
+        hipMemcpy(&s, d_state_, sizeof(s), hipMemcpyDeviceToHost) != hipSuccess) { call_err_.device("reading the device state failed"); return -1; }
     if (n_frames) *n_frames = s.last_n_frames;
     if (consumed) *consumed = s.last_consumed;
     if (state) *state = s.state;
@@ -302,9 +302,9 @@ int PlSyncHip::gather_device(const float* d_syms, const PlSyncFrame* d_frames, i
 {
     Entry on(*this);
     if (!on.ok) return -1;
-    if (n_frames < 0 || n_frames > max_frames_) { call_err_ = "n_frames exceeds max_frames"; return -1; }
+    if (n_frames < 0 || n_frames > max_frames_) { call_err_.device("n_frames exceeds max_frames"); return -1; } // (argument text, kDevice: notes/stage_error_codes.md)
     if (n_frames == 0) {
-        if (hipMemsetAsync(d_count, 0, sizeof(int32_t), stream) != hipSuccess) { call_err_ = "clearing the frame count failed"; return -1; }
+        if (hipMemsetAsync(d_count, 0, sizeof(int32_t), stream) != hipSuccess) { call_err_.device("clearing the frame count failed"); return -1; }
         return 0;
     }
     hipLaunchKernelGGL(plsync_gather_kernel, dim3(n_frames), dim3(256), 0, stream, reinterpret_cast<const float2*>(d_syms), d_frames, n_frames,

@@ -31,7 +31,7 @@ namespace dvbs2 {
 uint64_t rotator_inc_turns(double inc);
 
 // median over `regions` HIP-event regions of one rotation of n_syms symbols (one segment, out of place) and, in the same run, of a
-// plain 16-byte-per-lane copy of the same bytes on the same grid
+// plain 16-byte-per-lane copy of the same bytes on the same grid; 0, or the StageCode of the failure with its text in *err
 int rotator_measure(int device, int n_syms, int regions, double* rot_ms, double* copy_ms, std::string* err);
 
 class RotatorHip : public DeviceStage {

@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256) void copy16_kernel(const float4* __restrict__ 
 
 int rotator_measure(int device, int n_syms, int regions, double* rot_ms, double* copy_ms, std::string* err)
 {
-    if (n_syms < 2 || regions < 1 || regions > 64) { *err = "bad argument"; return -1; }
+    if (n_syms < 2 || regions < 1 || regions > 64) { *err = "bad argument"; return kArgument; }
     DeviceGuard dev_guard(device);
     RotatorHip rot(0.0123, device);
     float *d_in = nullptr, *d_out = nullptr;
@@ -112,7 +112,7 @@ int rotator_measure(int device, int n_syms, int regions, double* rot_ms, double*
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
     (void)hipFree(d_in); (void)hipFree(d_out);
-    if (!good) { *err = "device setup or launch failed"; return -1; }
+    if (!good) { *err = "device setup or launch failed"; return kDevice; }
     std::sort(tr.begin(), tr.end()); std::sort(tc.begin(), tc.end());
     *rot_ms = tr[tr.size() / 2]; *copy_ms = tc[tc.size() / 2];
     return 0;
@@ -120,30 +120,30 @@ int rotator_measure(int device, int n_syms, int regions, double* rot_ms, double*
 
 RotatorHip::RotatorHip(double phase_inc, int device) : DeviceStage(device), inc0_(phase_inc)
 {
-    if (!std::isfinite(phase_inc)) { err_ = "phase_inc must be finite"; return; }
+    if (!std::isfinite(phase_inc)) { err_.argument("phase_inc must be finite"); return; }
     reset();
 }
 
 void RotatorHip::reset()
 {
-    call_err_.clear();
+    call_err_ = {};
     counter_ = 0; phase_ = 0; inc_ = rotator_inc_turns(inc0_);
     queue_.clear();
 }
 
 int RotatorHip::set_phase_inc(double inc)
 {
-    call_err_.clear();
-    if (!std::isfinite(inc)) { call_err_ = "phase_inc must be finite"; return -1; }
+    call_err_ = {};
+    if (!std::isfinite(inc)) { call_err_.argument("phase_inc must be finite"); return -1; }
     inc_ = rotator_inc_turns(inc);
     return 0;
 }
 
 int RotatorHip::schedule(int64_t offset, double inc)
 {
-    call_err_.clear();
-    if (!std::isfinite(inc)) { call_err_ = "phase_inc must be finite"; return -1; }
-    if (offset < 0) { call_err_ = "offset must not be negative"; return -1; }
+    call_err_ = {};
+    if (!std::isfinite(inc)) { call_err_.argument("phase_inc must be finite"); return -1; }
+    if (offset < 0) { call_err_.argument("offset must not be negative"); return -1; }
     // after every queued update of the same or a smaller offset: equal offsets keep their scheduling order
     auto it = std::upper_bound(queue_.begin(), queue_.end(), offset, [](int64_t o, const Update& u) { return o < u.offset; });
     queue_.insert(it, Update{ offset, inc });
@@ -175,8 +175,8 @@ void RotatorHip::advance(int64_t n, std::vector<Segment>* segs)
 int RotatorHip::seek(int64_t n)
 {
     if (!ok()) return -1;
-    call_err_.clear();
-    if (n < 0 || n > INT64_MAX - counter_) { call_err_ = "seek distance out of range"; return -1; }
+    call_err_ = {};
+    if (n < 0 || n > INT64_MAX - counter_) { call_err_.argument("seek distance out of range"); return -1; }
     advance(n, nullptr);
     return 0;
 }
@@ -185,9 +185,9 @@ int RotatorHip::rotate_device(const float* d_in, int n_syms, float* d_out, hipSt
 {
     Entry on(*this);
     if (!on.ok) return -1;
-    if (n_syms < 0 || (int64_t)n_syms > INT64_MAX - counter_) { call_err_ = "n_syms out of range"; return -1; }
+    if (n_syms < 0 || (int64_t)n_syms > INT64_MAX - counter_) { call_err_.device("n_syms out of range"); return -1; } // (argument text, kDevice: notes/stage_error_codes.md)
     if (n_syms == 0) return 0;
-    if (((uintptr_t)d_in | (uintptr_t)d_out) & 7) { call_err_ = "symbol buffers must be 8-byte aligned"; return -1; }
+    if (((uintptr_t)d_in | (uintptr_t)d_out) & 7) { call_err_.device("symbol buffers must be 8-byte aligned"); return -1; } // (argument text, kDevice: notes/stage_error_codes.md)
     std::vector<Segment> segs;
     advance(n_syms, &segs);
     const float2* in = reinterpret_cast<const float2*>(d_in);

@@ -249,8 +249,7 @@ SymSyncHip::SymSyncHip(int sps, float loop_bw, float damping, float rolloff, int
                        int max_streams, int max_samples, int device)
     : DeviceStage(device), max_streams_(max_streams), max_samples_(max_samples)
 {
-    err_ = check_args(sps, loop_bw, damping, rolloff, rrc_delay, n_subfilt, interp, max_streams, max_samples);
-    if (!err_.empty()) return;
+    if (const std::string bad = check_args(sps, loop_bw, damping, rolloff, rrc_delay, n_subfilt, interp, max_streams, max_samples); !bad.empty()) { err_.argument(bad); return; }
     int L, D, H;
     symsync_geometry(sps, rrc_delay, n_subfilt, interp, &L, &D, &H);
     const size_t bank_bytes = (size_t)n_subfilt * L * sizeof(float);
@@ -263,10 +262,10 @@ SymSyncHip::SymSyncHip(int sps, float loop_bw, float damping, float rolloff, int
     if (!dev_guard.ok || alloc(&d_bank_, taps.size()) != hipSuccess || alloc(&d_hist_, (size_t)max_streams_ * 2 * H) != hipSuccess ||
         alloc(&d_state_, max_streams_) != hipSuccess || alloc(&d_res_, max_streams_) != hipSuccess || alloc(&d_nin_, max_streams_) != hipSuccess ||
         hipMemcpy(d_bank_, taps.data(), bank_bytes, hipMemcpyHostToDevice) != hipSuccess) {
-        err_ = "device setup failed"; return;
+        err_.argument("device setup failed"); return; // (device failure, kArgument: notes/stage_error_codes.md)
     }
     res_.resize(max_streams_);
-    if (reset()) { err_ = call_err_; call_err_.clear(); }
+    if (reset()) { err_.argument(call_err_.text); call_err_ = {}; } // (device failure, kArgument: notes/stage_error_codes.md)
 }
 
 int SymSyncHip::reset()
@@ -281,7 +280,7 @@ int SymSyncHip::reset()
         hipMemcpy(d_state_, all.data(), all.size() * sizeof(SymSyncState), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemset(d_hist_, 0, (size_t)max_streams_ * 2 * g_.history * sizeof(float2)) != hipSuccess || // the history starts as zeros
         hipMemset(d_res_, 0, (size_t)max_streams_ * sizeof(SymSyncResult)) != hipSuccess) {
-        call_err_ = "reset of the device state failed"; return -2;
+        call_err_.device("reset of the device state failed"); return -1;
     }
     last_streams_ = 0;
     return 0;
@@ -293,7 +292,7 @@ int SymSyncHip::work_device(const float2* d_in, int64_t in_stride, const int* n_
     Entry on(*this);
     if (!on.ok) return -1;
     if (hipMemcpyAsync(d_nin_, n_in, (size_t)n_streams * sizeof(int), hipMemcpyHostToDevice, stream) != hipSuccess) {
-        call_err_ = "copy of the sample counts failed"; return -1;
+        call_err_.device("copy of the sample counts failed"); return -1;
     }
     SymSyncIo io = { d_in, (long long)in_stride, d_nin_, d_out, (long long)out_stride, max_out, reinterpret_cast<long long*>(d_strobe_idx), d_mu };
     const size_t lds = kSymsyncRing * sizeof(float2) + (g_.interp == 0 ? (size_t)g_.n_subfilt * g_.subfilt_len * sizeof(float) : 0);
@@ -314,7 +313,7 @@ int SymSyncHip::finish(int* n_out, int* consumed, int* status)
     Entry on(*this);
     if (!on.ok || hipStreamSynchronize(last_stream_) != hipSuccess ||
         (last_streams_ && hipMemcpy(res_.data(), d_res_, (size_t)last_streams_ * sizeof(SymSyncResult), hipMemcpyDeviceToHost) != hipSuccess)) {
-        call_err_ = "reading the results failed"; return -1;
+        call_err_.device("reading the results failed"); return -1;
     }
     for (int s = 0; s < last_streams_; s++) {
         if (n_out) n_out[s] = res_[s].n_out;
@@ -328,7 +327,7 @@ int SymSyncHip::state(int s, SymSyncState* out)
 {
     Entry on(*this);
     if (!on.ok || hipDeviceSynchronize() != hipSuccess || hipMemcpy(out, d_state_ + s, sizeof(SymSyncState), hipMemcpyDeviceToHost) != hipSuccess) {
-        call_err_ = "reading the state failed"; return -1;
+        call_err_.device("reading the state failed"); return -1;
     }
     return 0;
 }
