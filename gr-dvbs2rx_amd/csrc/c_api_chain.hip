@@ -17,15 +17,18 @@ struct dvbs2_chain {
     HostPipe pipe;
 };
 
+// table != nullptr: the demapper of a caller's table (dvbs2_demap_create_table), `constellation` unused
+struct ChainTable { int n_mod; const float* points_re_im; const uint8_t* column; };
 static int chain_make(dvbs2_chain_t** h, int standard, int framesize, int rate, int constellation, bool with_demap,
-                      int group_size, int max_frames, int device)
+                      int group_size, int max_frames, int device, const ChainTable* table = nullptr)
 {
     if (int rc = null_out(h)) return rc;
     dvbs2_chain* o = new (std::nothrow) dvbs2_chain();
     if (!o) return fail(DVBS2_EDEVICE, "out of memory");
     o->device = device; o->max_frames = max_frames;
     int rc = DVBS2_OK;
-    if (with_demap) rc = dvbs2_demap_create(&o->dm, framesize, rate, constellation, max_frames, device);
+    if (table) rc = dvbs2_demap_create_table(&o->dm, framesize, table->n_mod, table->points_re_im, table->column, max_frames, device);
+    else if (with_demap) rc = dvbs2_demap_create(&o->dm, framesize, rate, constellation, max_frames, device);
     if (rc == DVBS2_OK) rc = dvbs2_ldpc_create(&o->ldpc, standard, framesize, rate, group_size, max_frames, device);
     if (rc == DVBS2_OK) rc = dvbs2_bch_create(&o->bch, standard, framesize, rate, max_frames, device);
     if (rc != DVBS2_OK) { std::string keep = g_api_error; dvbs2_chain_destroy(o); return fail(rc, keep); }
@@ -87,6 +90,15 @@ int dvbs2_chain_create(dvbs2_chain_t** h, int standard, int framesize, int rate,
 {
     API_TRY
     return chain_make(h, standard, framesize, rate, constellation, true, group_size, max_frames, device);
+    API_CATCH
+}
+
+int dvbs2_chain_create_table(dvbs2_chain_t** h, int standard, int framesize, int rate, int n_mod, const float* points_re_im,
+                             const uint8_t* column, int group_size, int max_frames, int device)
+{
+    API_TRY
+    const ChainTable table = { n_mod, points_re_im, column };
+    return chain_make(h, standard, framesize, rate, 0, true, group_size, max_frames, device, &table);
     API_CATCH
 }
 

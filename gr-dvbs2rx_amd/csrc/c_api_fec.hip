@@ -107,6 +107,31 @@ int dvbs2_demap_create(dvbs2_demap_t** h, int framesize, int rate, int constella
     API_CATCH
 }
 
+int dvbs2_demap_table_check(int n_mod, const float* points_re_im, const uint8_t* column)
+{
+    API_TRY
+    std::string why;
+    return demap_table_check(n_mod, points_re_im, column, &why) ? DVBS2_OK : fail(DVBS2_EINVAL, why);
+    API_CATCH
+}
+
+int dvbs2_demap_create_table(dvbs2_demap_t** h, int framesize, int n_mod, const float* points_re_im, const uint8_t* column, int max_frames, int device)
+{
+    API_TRY
+    if (int rc = null_out(h)) return rc;
+    if (int rc = dvbs2_demap_table_check(n_mod, points_re_im, column)) return rc; // before any device is touched
+    return make_handle(h, device, [&] { return new (std::nothrow) DemapperHip(framesize, n_mod, points_re_im, column, max_frames, device); });
+    API_CATCH
+}
+
+int dvbs2_demap_table(const dvbs2_demap_t* h, int* n_mod, float* points_re_im, uint8_t* column)
+{
+    NEED_HANDLE(h);
+    if (!h->impl->is_table()) return fail(DVBS2_EINVAL, "not a table handle (dvbs2_demap_create_table)");
+    h->impl->table(n_mod, points_re_im, column);
+    return DVBS2_OK;
+}
+
 void dvbs2_demap_destroy(dvbs2_demap_t* h) { destroy_handle(h); }
 
 int dvbs2_apsk_points(int constellation, int rate, float* re_im)

@@ -99,16 +99,6 @@ __global__ void __launch_bounds__(256) demap_apsk_kernel(const float* __restrict
     }
 }
 
-// the tail of both SNR kernels: block sum of the two powers, snr = signal / noise
-__device__ __forceinline__ void snr_block_reduce(float sp, float np, float* ssp, float* snp, float* snr)
-{
-    const int tid = threadIdx.x;
-    ssp[tid] = sp; snp[tid] = np;
-    __syncthreads();
-    for (int s = 128; s; s >>= 1) { if (tid < s) { ssp[tid] += ssp[tid + s]; snp[tid] += snp[tid + s]; } __syncthreads(); }
-    if (tid == 0) { float n = snp[0]; if (!(n > 0)) n = 1e-12f; *snr = ssp[0] / n; }
-}
-
 // One workgroup per frame. llr == nullptr: reference point = hard slice of the symbol (pre-decoder estimate);
 // otherwise the reference point is re-mapped from the signs of the decoded LLRs (post-decoder refinement,
 // lib/xfecframe_demapper_cb_impl.cc:268-307, lib/qpsk.h:266-281): LLR < 0 -> -1, else +1; 8PSK bits are picked
@@ -249,7 +239,8 @@ int DemapperHip::soft_device(const float* d_syms, int n_frames, const float* d_n
         const int quads = n_llr_ / 4;
         hipLaunchKernelGGL(demap_qpsk_kernel, dim3((quads + 255) / 256, n_frames), dim3(256), 0, stream,
                            reinterpret_cast<const float4*>(d_syms), d_n0, n0_count, reinterpret_cast<uint32_t*>(d_llr), quads, n_frames);
-    } else if (is_apsk()) {
+    } else if (table_ && !table_as_apsk_) launch_table(d_syms, n_frames, d_n0, n0_count, d_llr, stream);
+    else if (is_apsk() || table_as_apsk_) {
         const int rows = n_syms(), quads = (rows + 3) / 4; // 16200 / 4050 (16APSK), 12960 / 3240 (32APSK)
         const dim3 grid((quads + 255) / 256, n_frames);
         if (n_mod_ == 4) hipLaunchKernelGGL(demap_apsk_kernel<4>, grid, dim3(256), 0, stream, d_syms, d_n0, n0_count, d_llr, rows, apsk_);
@@ -291,7 +282,8 @@ int DemapperHip::snr_device(const float* d_syms, const int8_t* d_ref_llr, int n_
     int ra0 = 0, ra1 = rows, ra2 = 2 * rows;
     if (order_ == 1) { ra0 = 2 * rows; ra1 = rows; ra2 = 0; }
     else if (order_ == 2) { ra0 = rows; ra1 = 0; ra2 = 2 * rows; }
-    if (is_apsk() && n_mod_ == 4)
+    if (table_) launch_table_snr(d_syms, d_ref_llr, n_frames, d_snr, stream);
+    else if (is_apsk() && n_mod_ == 4)
         hipLaunchKernelGGL(demap_snr_apsk_kernel<4>, dim3(n_frames), dim3(256), 0, stream, reinterpret_cast<const float2*>(d_syms), d_ref_llr, d_snr, rows, apsk_);
     else if (is_apsk())
         hipLaunchKernelGGL(demap_snr_apsk_kernel<5>, dim3(n_frames), dim3(256), 0, stream, reinterpret_cast<const float2*>(d_syms), d_ref_llr, d_snr, rows, apsk_);

@@ -83,6 +83,16 @@ __device__ __forceinline__ void apsk_llr2(const ApskTable& t, apsk_f2 re, apsk_f
     }
 }
 
+// the tail of every SNR kernel (demap_hip.hip, demap_table_hip.hip): block sum of the two powers, snr = signal / noise
+__device__ __forceinline__ void snr_block_reduce(float sp, float np, float* ssp, float* snp, float* snr)
+{
+    const int tid = threadIdx.x;
+    ssp[tid] = sp; snp[tid] = np;
+    __syncthreads();
+    for (int s = 128; s; s >>= 1) { if (tid < s) { ssp[tid] += ssp[tid + s]; snp[tid] += snp[tid + s]; } __syncthreads(); }
+    if (tid == 0) { float n = snp[0]; if (!(n > 0)) n = 1e-12f; *snr = ssp[0] / n; }
+}
+
 // What a sweep kernel needs to demap while loading (passed by value; mode 0 = LLR input)
 struct DemapFused {
     const float* syms;  // n_frames * n_syms complex symbols (re, im)

@@ -233,12 +233,19 @@ private:
 // ---------------------------------------------------------------------------------------------- demapper
 // constellation: MOD_QPSK and MOD_8PSK as in the reference; MOD_16APSK and MOD_32APSK (DVB-S2 rates, normal and short frames) are
 // this library's own -- forecast() and output_multiple() follow n_mod 4 / 5, the refinement re-maps through the natural column order.
+// make_table: the caller's table of 2^n_mod points (n_mod 2, 3, 4, 5, 6 or 8; points as (re, im) floats, entry i = label i) and column
+// order (column[c] = the label bit, 0 = most significant, in column c; nullptr = natural) -- dvbs2_demap_create_table. The same
+// general_work and llr_pdu refinement, which re-maps through column[]. The table is the caller's: unpinned, no S2X PL signalling.
 class xfecframe_demapper_cb {
 public:
     typedef std::shared_ptr<xfecframe_demapper_cb> sptr;
     static sptr make(dvb_framesize_t framesize, dvb_code_rate_t rate, dvb_constellation_t constellation, int batch_frames = 512, int device = 0)
     {
         return sptr(new xfecframe_demapper_cb(framesize, rate, constellation, batch_frames, device));
+    }
+    static sptr make_table(dvb_framesize_t framesize, int n_mod, const float* points, const uint8_t* column, int batch_frames = 512, int device = 0)
+    {
+        return sptr(new xfecframe_demapper_cb(framesize, n_mod, points, column, batch_frames, device));
     }
     ~xfecframe_demapper_cb() { dvbs2_demap_destroy(d_h); }
     void forecast(int noutput_items, gr_vector_int& req) const { req[0] = noutput_items / d_n_mod; } // :95-99
@@ -308,6 +315,15 @@ private:
     xfecframe_demapper_cb(dvb_framesize_t framesize, dvb_code_rate_t rate, dvb_constellation_t constellation, int batch_frames, int device) : d_batch(batch_frames)
     {
         check(dvbs2_demap_create(&d_h, framesize, rate, constellation, batch_frames, device)); // throws "Unsupported constellation" (or a rate / frame size message for 16APSK / 32APSK)
+        init_pool(batch_frames);
+    }
+    xfecframe_demapper_cb(dvb_framesize_t framesize, int n_mod, const float* points, const uint8_t* column, int batch_frames, int device) : d_batch(batch_frames)
+    {
+        check(dvbs2_demap_create_table(&d_h, framesize, n_mod, points, column, batch_frames, device)); // throws with the text that names the refused argument
+        init_pool(batch_frames);
+    }
+    void init_pool(int batch_frames)
+    {
         int order;
         check(dvbs2_demap_params(d_h, &d_xfecframe_len, &d_fecframe_len, &d_n_mod, &order));
         d_saved.assign(std::max(64, 2 * batch_frames), std::numeric_limits<uint64_t>::max()); // XFECFRAME_POOL_SIZE, .h:28-32

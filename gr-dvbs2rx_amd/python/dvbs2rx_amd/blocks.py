@@ -15,7 +15,7 @@ from .capi import lib, check
 
 __all__ = ["get_fec_info", "rate_id", "LdpcDecoder", "BchDecoder", "Demapper", "FecChain", "BbDeheader", "ldpc_table_info", "ldpc_layer_info",
            "ldpc_table_names", "bb_descramble_sequence", "PlPayload",
-           "pl_scrambling_rn", "HostBuffer", "PlFrontEnd", "plheader_symbols", "pls_parse", "apsk_points",
+           "pl_scrambling_rn", "HostBuffer", "PlFrontEnd", "plheader_symbols", "pls_parse", "apsk_points", "demap_table_check",
            "PlSync", "plsync_taps", "plsync_thresholds", "PlCoarse", "plcoarse_weights", "Rotator",
            "SymbolSync", "symsync_loop_constants", "symsync_geometry", "symsync_taps"]
 
@@ -245,14 +245,54 @@ class BchDecoder(_Handle):
         check(lib.dvbs2_bch_decode_device(self._h, d_cw, n_frames, d_msg, d_corr, stream or None))
 
 
+def _table_args(points, column):
+    """(n_mod, points as complex64, column as uint8 or None) for the table entries; the C side judges the values."""
+    pts = np.ascontiguousarray(points, np.complex64).reshape(-1)
+    n_mod = int(pts.size).bit_length() - 1
+    if pts.size < 2 or pts.size != 1 << n_mod:
+        raise ValueError(f"points: a power of two of them, got {pts.size}")
+    col = None
+    if column is not None:
+        col = np.ascontiguousarray(column, np.uint8)
+        if col.shape != (n_mod,):
+            raise ValueError(f"column: {n_mod} entries, got shape {col.shape}")
+    return n_mod, pts, col
+
+
+def demap_table_check(points, column=None):
+    """Whether Demapper.from_table / FecChain.from_table take this table (dvbs2_demap_table_check; raises Dvbs2Error with the text
+    that names the argument). points: 2^n_mod complex values, entry i = label i; column as for from_table. Host only."""
+    n_mod, pts, col = _table_args(points, column)
+    check(lib.dvbs2_demap_table_check(n_mod, pts.ctypes.data, col.ctypes.data if col is not None else None))
+
+
 class Demapper(_Handle):
     """xfecframe_demapper_cb's compute (reference lib/xfecframe_demapper_cb_impl.cc:101-186): QPSK and 8PSK as in the reference,
-    and capi.MOD_16APSK / capi.MOD_32APSK at their DVB-S2 rates (exact max-log, natural column order; notes/apsk_demap.md)."""
+    and capi.MOD_16APSK / capi.MOD_32APSK at their DVB-S2 rates (exact max-log, natural column order; notes/apsk_demap.md).
+    from_table(): the same max-log for a caller's table of 4 .. 256 points (notes/demap_table.md)."""
     _destroy = lib.dvbs2_demap_destroy
 
     def __init__(self, framesize=capi.FECFRAME_NORMAL, rate="C1_2", constellation=capi.MOD_QPSK, max_frames=64, device=0):
         check(lib.dvbs2_demap_create(C.byref(self._h), framesize, rate_id(rate), constellation, max_frames, device))
         self.n_syms, self.n_llr, self.n_mod, self.column_order = _ints(4, lib.dvbs2_demap_params, self._h)
+
+    @classmethod
+    def from_table(cls, framesize, points, column=None, max_frames=64, device=0):
+        """points: 2^n_mod complex values (n_mod in 2, 3, 4, 5, 6, 8), entry i = the point with label i, used as given. column[c]: the
+        label bit (0 = most significant) whose LLRs fill column c of a frame; None = the natural order. column_order is 0 for the
+        natural order and -1 otherwise."""
+        n_mod, pts, col = _table_args(points, column)
+        self = cls.__new__(cls)
+        check(lib.dvbs2_demap_create_table(C.byref(self._h), framesize, n_mod, pts.ctypes.data, col.ctypes.data if col is not None else None,
+                                           max_frames, device))
+        self.n_syms, self.n_llr, self.n_mod, self.column_order = _ints(4, lib.dvbs2_demap_params, self._h)
+        return self
+
+    def table(self):
+        """(points complex64, column uint8) as a from_table() handle was given them (dvbs2_demap_table)."""
+        pts, col = np.empty(1 << self.n_mod, np.complex64), np.empty(self.n_mod, np.uint8)
+        check(lib.dvbs2_demap_table(self._h, None, pts.ctypes.data, col.ctypes.data))
+        return pts, col
 
     def work(self, syms, n0):
         """syms: (n_frames, n_syms) complex (converted to complex64); n0: scalar or (n_frames,) float32 -> (n_frames, n_llr) int8."""
@@ -752,6 +792,21 @@ class FecChain(_Handle):
         else:
             check(lib.dvbs2_chain_create(C.byref(self._h), standard, framesize, rate_id(rate), constellation,
                                          group_size, max_frames, device))
+        self._created(group_size, max_trials)
+
+    @classmethod
+    def from_table(cls, standard=capi.STANDARD_DVBS2, framesize=capi.FECFRAME_NORMAL, rate="C3_4", points=None, column=None, group_size=32,
+                   max_frames=64, max_trials=0, device=0):
+        """The chain with the demapper of a caller's table (Demapper.from_table: points, column); standard, framesize and rate
+        choose the codes. Runs demapper -> LLR buffer -> LDPC -> BCH, never the fused load."""
+        n_mod, pts, col = _table_args(points, column)
+        self = cls.__new__(cls)
+        check(lib.dvbs2_chain_create_table(C.byref(self._h), standard, framesize, rate_id(rate), n_mod, pts.ctypes.data,
+                                           col.ctypes.data if col is not None else None, group_size, max_frames, device))
+        self._created(group_size, max_trials)
+        return self
+
+    def _created(self, group_size, max_trials):
         a, b = C.c_int(), C.c_int()
         check(lib.dvbs2_chain_params(self._h, a, b))
         self.n_syms, self.msg_bytes = a.value, b.value

@@ -208,7 +208,8 @@ int dvbs2_bch_decode_device(dvbs2_bch_t* h, const uint8_t* d_cw, int n_frames, u
  * constellation: DVBS2_MOD_QPSK or DVBS2_MOD_8PSK as in the reference, and beyond it DVBS2_MOD_16APSK (rates C2_3, C3_4, C4_5,
  * C5_6, C8_9, C9_10) and DVBS2_MOD_32APSK (C3_4 .. C9_10) on normal and short frames (9/10: normal only), i.e. DVB-S2 MODCODs
  * 18-28; anything else fails with DVBS2_EINVAL ("Unsupported constellation", lib/xfecframe_demapper_cb_impl.cc:70-72, or a
- * rate / frame size message). The S2X APSK variants are not covered.
+ * rate / frame size message). The S2X constellations (8APSK, 8+8APSK, 4+12+16rbAPSK, 64/128/256APSK) and QAM have no built-in table:
+ * they go through dvbs2_demap_create_table below with the caller's table.
  * 16APSK / 32APSK: exact max-log LLRs over all points at QPSK's scale, L_b = (min_{bit b = 1} |y - s|^2 - min_{bit b = 0} |y - s|^2) / N0,
  * llr = sat8(rint(L_b)); the LLR of label bit c (0 = most significant = first interleaver column) of symbol j is byte c * n_syms + j
  * of the frame (EN 302 307-1 5.3.2 undone; column_order 0). The constellation tables are restated from EN 302 307-1 5.4.3 / 5.4.4
@@ -219,8 +220,27 @@ typedef struct dvbs2_demap dvbs2_demap_t;
 int dvbs2_apsk_points(int constellation, int rate, float* re_im);
 int dvbs2_demap_create(dvbs2_demap_t** h, int framesize, int rate, int constellation, int max_frames, int device);
 void dvbs2_demap_destroy(dvbs2_demap_t* h);
+/* A demapper for the CALLER's constellation table of 4 .. 256 labelled points: the same exact max-log LLR as 16APSK / 32APSK above, over
+ * all 2^n_mod points, L_b = (min_{bit b = 1} |y - s|^2 - min_{bit b = 0} |y - s|^2) / N0, llr = sat8(rint(L_b)) (notes/demap_table.md).
+ * n_mod          one of 2, 3, 4, 5, 6, 8. 7 is refused: no DVB frame length (16200, 32400, 64800) is a multiple of 7.
+ * points_re_im   2 * 2^n_mod floats (re, im); entry i is the point with label i. Used as given: not scaled, Es = 1 is not required
+ *                (N0 is in the table's units). Every value must be finite. The table is the caller's and is NOT pinned against anything.
+ * column         n_mod bytes, a permutation of 0 .. n_mod-1: column[c] is the label bit (0 = most significant) whose LLRs fill column c
+ *                of a frame, i.e. byte c * n_syms + j of a frame is the LLR of label bit column[c] of symbol j. NULL: column[c] = c.
+ *                Translating a standard's interleaver column pattern for a rate into this array is the caller's business.
+ * n_llr follows from framesize alone (short 16200, normal 64800, medium 32400), n_syms = n_llr / n_mod.
+ * A refusal is DVBS2_EINVAL with a text that names the argument; dvbs2_demap_table_check gives the same verdict without a device (host
+ * only). Every entry that takes a dvbs2_demap_t* works on such a handle; dvbs2_demap_params reports column_order 0 for the natural
+ * order and -1 for any other. SNR estimates: the nearest of all points before the decoder (lowest label on a tie), after it the point
+ * whose label the LLR signs spell through column[]. dvbs2_demap_table reads back what the handle was given (each pointer nullable;
+ * DVBS2_EINVAL on a handle of dvbs2_demap_create). S2X PL signalling is not part of this: dvbs2_plframe_* / dvbs2_plsync_* know the
+ * 7-bit DVB-S2 PLSC only. */
+int dvbs2_demap_table_check(int n_mod, const float* points_re_im, const uint8_t* column);
+int dvbs2_demap_create_table(dvbs2_demap_t** h, int framesize, int n_mod, const float* points_re_im,
+                             const uint8_t* column, int max_frames, int device);
+int dvbs2_demap_table(const dvbs2_demap_t* h, int* n_mod, float* points_re_im, uint8_t* column);
 /* symbols per frame (d_xfecframe_len), LLRs per frame (d_fecframe_len), bits per symbol, 8PSK column
- * order (0 = "012", 1 = "210", 2 = "102") */
+ * order (0 = "012", 1 = "210", 2 = "102"; a table handle: 0 = natural, -1 = another) */
 int dvbs2_demap_params(const dvbs2_demap_t* h, int* n_syms, int* n_llr, int* n_mod, int* column_order);
 /*
  * syms      n_frames * n_syms complex symbols as interleaved (re, im) floats (gr_complex layout)
@@ -253,6 +273,11 @@ int dvbs2_demap_refine_snr_device(dvbs2_demap_t* h, const float* d_syms, const i
 typedef struct dvbs2_chain dvbs2_chain_t;
 int dvbs2_chain_create(dvbs2_chain_t** h, int standard, int framesize, int rate, int constellation,
                        int group_size, int max_frames, int device);
+/* The chain with the demapper of a caller's table (dvbs2_demap_create_table: n_mod, points_re_im, column as there); standard, framesize
+ * and rate choose the LDPC and BCH codes. Every chain entry works on it. It is never fused into the LDPC sweep kernel: it runs
+ * demapper -> LLR buffer -> LDPC -> BCH. */
+int dvbs2_chain_create_table(dvbs2_chain_t** h, int standard, int framesize, int rate, int n_mod,
+                             const float* points_re_im, const uint8_t* column, int group_size, int max_frames, int device);
 void dvbs2_chain_destroy(dvbs2_chain_t* h);
 /* bytes per frame out (bch k / 8), symbols per frame in */
 int dvbs2_chain_params(const dvbs2_chain_t* h, int* n_syms, int* msg_bytes);
