@@ -17,7 +17,7 @@ __all__ = ["get_fec_info", "rate_id", "LdpcDecoder", "BchDecoder", "Demapper", "
            "ldpc_table_names", "bb_descramble_sequence", "PlPayload",
            "pl_scrambling_rn", "HostBuffer", "PlFrontEnd", "plheader_symbols", "pls_parse", "apsk_points", "demap_table_check",
            "PlSync", "plsync_taps", "plsync_thresholds", "PlCoarse", "plcoarse_weights", "Rotator",
-           "SymbolSync", "symsync_loop_constants", "symsync_geometry", "symsync_taps"]
+           "SymbolSync", "symsync_loop_constants", "symsync_geometry", "symsync_taps", "FecEncoder", "enc_check"]
 
 DEFAULT_TRIALS = 25  # reference lib/ldpc_decoder_bb_impl.cc:391
 
@@ -887,3 +887,73 @@ class FecChain(_Handle):
         ms, n = C.c_double(), C.c_int()
         check(lib.dvbs2_chain_ldpc_profile(self._h, 1 if enable else 0, ms, n))
         return ms.value, n.value
+
+
+def enc_check(standard=capi.STANDARD_DVBS2, framesize=capi.FECFRAME_NORMAL, rate="C1_2", constellation=capi.ENC_NO_MAPPER):
+    """Whether FecEncoder takes this MODCOD (dvbs2_enc_check; raises Dvbs2Error with the text that names the argument). Host only."""
+    check(lib.dvbs2_enc_check(standard, framesize, rate_id(rate), constellation))
+
+
+class FecEncoder(_Handle):
+    """The forward direction of FecChain on the device: BBFRAME bytes -> [BB scrambler] -> BCH -> LDPC -> mapper, every result bit
+    for bit (notes/encoder.md). constellation: capi.MOD_QPSK, MOD_8PSK, MOD_16APSK, MOD_32APSK or capi.ENC_NO_MAPPER. PL framing
+    is not part of it. The reference has no transmit blocks to mirror."""
+    _destroy = lib.dvbs2_enc_destroy
+    OUTPUTS = ("bch_cw", "ldpc_cw", "syms")
+
+    def __init__(self, standard=capi.STANDARD_DVBS2, framesize=capi.FECFRAME_NORMAL, rate="C1_2", constellation=capi.MOD_QPSK,
+                 max_frames=64, device=0):
+        check(lib.dvbs2_enc_create(C.byref(self._h), standard, framesize, rate_id(rate), constellation, max_frames, device))
+        self._created()
+
+    @classmethod
+    def from_table(cls, standard=capi.STANDARD_DVBS2, framesize=capi.FECFRAME_NORMAL, rate="C1_2", points=None, column=None,
+                   max_frames=64, device=0):
+        """The encoder with the mapper of a caller's table (points, column as for Demapper.from_table)."""
+        n_mod, pts, col = _table_args(points, column)
+        self = cls.__new__(cls)
+        check(lib.dvbs2_enc_create_table(C.byref(self._h), standard, framesize, rate_id(rate), n_mod, pts.ctypes.data,
+                                         col.ctypes.data if col is not None else None, max_frames, device))
+        self._created()
+        return self
+
+    @classmethod
+    def from_parts(cls, bch=None, ldpc_table=None, max_frames=64, device=0):
+        """Single stages of any code the library knows: bch = (m, prim_poly, t, n) or None, ldpc_table = a table name or None.
+        No mapper."""
+        m, prim, t, n = bch if bch is not None else (0, 0, 0, 0)
+        self = cls.__new__(cls)
+        check(lib.dvbs2_enc_create_parts(C.byref(self._h), m, prim, t, n, ldpc_table.encode() if ldpc_table is not None else None,
+                                         max_frames, device))
+        self._created()
+        return self
+
+    def _created(self):
+        self.in_bits, self.bch_n, self.ldpc_n, self.n_syms, self.n_mod = _ints(5, lib.dvbs2_enc_params, self._h)
+        self.in_bytes = self.in_bits // 8
+
+    def set_scramble(self, enable=True):
+        """Fuse the BB scrambler (in ^= bb_descramble_sequence) into the BCH stage's load."""
+        check(lib.dvbs2_enc_set_scramble(self._h, int(bool(enable))))
+
+    def work(self, frames, want=None):
+        """HOST buffers (dvbs2_enc_encode): frames uint8 [n_frames, in_bytes]. want: names out of OUTPUTS (default: every stage
+        the encoder has). Returns a dict name -> array: bch_cw / ldpc_cw uint8 [n_frames, n / 8], syms complex64 [n_frames, n_syms]."""
+        frames = np.ascontiguousarray(frames, np.uint8)
+        nf = frames.shape[0]
+        if frames.shape != (nf, self.in_bytes):
+            raise ValueError(f"frames: expected (n_frames, {self.in_bytes}) bytes, got shape {frames.shape}")
+        if want is None:
+            want = [n for n, have in zip(self.OUTPUTS, (self.bch_n, self.ldpc_n, self.n_syms)) if have]
+        out = {}
+        for name in want:
+            if name not in self.OUTPUTS:
+                raise ValueError(f"unknown output {name}")
+            out[name] = (np.empty((nf, self.n_syms), np.complex64) if name == "syms" else
+                         np.empty((nf, (self.bch_n if name == "bch_cw" else self.ldpc_n) // 8), np.uint8))
+        ptrs = [out[n].ctypes.data if n in out else None for n in self.OUTPUTS]
+        check(lib.dvbs2_enc_encode(self._h, frames.ctypes.data, nf, *ptrs))
+        return out
+
+    def work_device(self, d_in, n_frames, d_bch_cw=0, d_ldpc_cw=0, d_syms=0, stream=0):
+        check(lib.dvbs2_enc_encode_device(self._h, d_in, n_frames, d_bch_cw or None, d_ldpc_cw or None, d_syms or None, stream or None))

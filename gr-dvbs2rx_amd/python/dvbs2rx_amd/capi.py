@@ -24,6 +24,7 @@ STANDARD_DVBS2, STANDARD_DVBT2 = 0, 1
 FECFRAME_SHORT, FECFRAME_NORMAL, FECFRAME_MEDIUM = 0, 1, 2
 OM_CODEWORD, OM_MESSAGE = 0, 1
 MOD_QPSK, MOD_8PSK, MOD_16APSK, MOD_32APSK = 0, 4, 6, 8
+ENC_NO_MAPPER = -1
 
 
 class FecInfo(C.Structure):
@@ -206,6 +207,15 @@ SYMBOLS = {
     "dvbs2_chain_ldpc_profile": (_i, [_vp, _i, C.POINTER(C.c_double), _ip]),
     "dvbs2_chain_ldpc_kernel_name": (C.c_char_p, [_vp]),
     "dvbs2_chain_ldpc_fallback_rounds": (_i, [_vp]),
+    "dvbs2_enc_create": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i, _i]),
+    "dvbs2_enc_create_table": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _vp, _vp, _i, _i]),
+    "dvbs2_enc_create_parts": (_i, [C.POINTER(_vp), _i, C.c_uint32, _i, _i, C.c_char_p, _i, _i]),
+    "dvbs2_enc_destroy": (None, [_vp]),
+    "dvbs2_enc_params": (_i, [_vp, _ip, _ip, _ip, _ip, _ip]),
+    "dvbs2_enc_set_scramble": (_i, [_vp, _i]),
+    "dvbs2_enc_check": (_i, [_i, _i, _i, _i]),
+    "dvbs2_enc_encode_device": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "dvbs2_enc_encode": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
 }
 
 if not os.path.exists(LIB_PATH):

@@ -325,6 +325,55 @@ const char* dvbs2_chain_ldpc_kernel_name(const dvbs2_chain_t* h);
 /* dvbs2_ldpc_fallback_rounds of the chain's LDPC stage: zero in normal operation */
 int dvbs2_chain_ldpc_fallback_rounds(const dvbs2_chain_t* h);
 
+/* ---- the forward direction: BBFRAME bytes -> [BB scrambler] -> systematic BCH -> systematic LDPC -> bit interleaver and mapper ->
+ * XFECFRAME symbols, the exact inverse of what the chain above undoes, every result bit for bit. The reference has no counterpart
+ * beyond bch_codec::encode (lib/bch.cc:158-173); its transmit application takes its FEC from gr-dtv. PL framing (PLHEADER, pilots,
+ * PL scrambling) is NOT part of this: it is the step that is left between these symbols and a PLFRAME.
+ * input       in_bits / 8 bytes per frame, first bit = bit 7; with every stage present a BBFRAME of bch_k / 8 bytes
+ * BCH cw      bch_n / 8 bytes: the message unchanged (scrambled if scrambling is on), then the remainder of m(x) x^(n-k) mod g(x), highest
+ *             power first -- the layout dvbs2_bch_decode reads (lib/bch.cc:158-173, :436-449). n and k are multiples of 8 (medium
+ *             frames are refused as the decoder refuses them)
+ * LDPC cw     N / 8 bytes, bit i = the bit whose LLR the decoder reads at index i (what DVBS2_OM_CODEWORD emits): the K systematic bits,
+ *             then the N - K parity bits of p[(x + m q) mod (N - K)] ^= information bit 360 g + m for every address x of group g, and
+ *             p[r] ^= p[r - 1]
+ * symbols     n_syms interleaved (re, im) floats per frame, the buffer dvbs2_chain_decode_device takes.
+ *             QPSK: symbol j carries bits 2 j (I) and 2 j + 1 (Q) as +-0.70710678118654752440f, bit 0 positive.
+ *             8PSK: bit b_k of symbol s is codeword bit ra_k + s (the column order dvbs2_demap_params reports for the rate); the point is
+ *             the one the demapper's SNR refinement re-maps from b0 b1 b2 (lib/psk.hh:152-157).
+ *             16APSK, 32APSK, a caller's table: label bit column[c] of symbol j is codeword bit c * n_syms + j; the symbol is the table
+ *             entry of that label, copied bit for bit (dvbs2_apsk_points, or the caller's floats).
+ * Refused with DVBS2_EINVAL and a text that names the argument: a row whose bch_n is not the LDPC table's K (the shortened / punctured
+ * VL-SNR and medium rows: their pattern is not in the reference and cannot be pinned; dvbs2_enc_create_parts with the table name still
+ * encodes the mother code), a 16APSK / 32APSK rate DVB-S2 does not have, a built-in constellation on a DVB-T2 row (DVBS2_ENC_NO_MAPPER
+ * and a caller's table are accepted there), n_mod 7, a table dvbs2_demap_table_check refuses. ---- */
+typedef struct dvbs2_enc dvbs2_enc_t;
+#define DVBS2_ENC_NO_MAPPER (-1)
+/* the whole chain of one MODCOD; constellation: a DVBS2_MOD_* value or DVBS2_ENC_NO_MAPPER (no symbols) */
+int dvbs2_enc_create(dvbs2_enc_t** h, int standard, int framesize, int rate, int constellation, int max_frames, int device);
+/* the same with the caller's constellation table: n_mod, points_re_im and column as for dvbs2_demap_create_table, by the same rules */
+int dvbs2_enc_create_table(dvbs2_enc_t** h, int standard, int framesize, int rate, int n_mod, const float* points_re_im,
+                           const uint8_t* column, int max_frames, int device);
+/* parts, for any code the library knows. bch_m == 0: no BCH stage (else as dvbs2_bch_create_raw); ldpc_table == NULL: no LDPC stage
+ * (else a name of dvbs2_ldpc_table_name). At least one stage; both: bch_n must be the table's K. There is no mapper. */
+int dvbs2_enc_create_parts(dvbs2_enc_t** h, int bch_m, uint32_t bch_prim_poly, int bch_t, int bch_n, const char* ldpc_table,
+                           int max_frames, int device);
+void dvbs2_enc_destroy(dvbs2_enc_t* h);
+/* in_bits = k of the first stage present; 0 for a stage that is absent; each nullable */
+int dvbs2_enc_params(const dvbs2_enc_t* h, int* in_bits, int* bch_n, int* ldpc_n, int* n_syms, int* n_mod);
+/* bbscrambler: in ^= PRBS (dvbs2_bb_descramble_sequence) before BCH, fused into the BCH stage's load. Off by default. */
+int dvbs2_enc_set_scramble(dvbs2_enc_t* h, int enable);
+/* host only, no device needed: the verdict dvbs2_enc_create would give (DVBS2_OK, or DVBS2_EINVAL and its text) */
+int dvbs2_enc_check(int standard, int framesize, int rate, int constellation);
+/* DEVICE pointers, asynchronous on `stream`: no host synchronisation, no allocation; calls on one handle are ordered by the caller (as
+ * for dvbs2_bch_decode_device). Each output is nullable and then not written: the handle keeps what the next stage needs, and stages
+ * behind the last requested output do not run. A requested output whose stage is absent, no output at all, and d_in overlapping an
+ * output (encoding in place is not supported) are DVBS2_EINVAL; n_frames > max_frames is DVBS2_ESIZE. d_syms 16-byte aligned gets
+ * 16-byte stores. */
+int dvbs2_enc_encode_device(dvbs2_enc_t* h, const uint8_t* d_in, int n_frames, uint8_t* d_bch_cw, uint8_t* d_ldpc_cw,
+                            float* d_syms, void* stream);
+/* the same on HOST pointers, synchronous, staged through buffers of the handle */
+int dvbs2_enc_encode(dvbs2_enc_t* h, const uint8_t* in, int n_frames, uint8_t* bch_cw, uint8_t* ldpc_cw, float* syms);
+
 /* ---- upstream neighbour: the PLFRAME payload step of plsync_cc_impl::handle_payload()
  * (reference lib/plsync_cc_impl.cc:644-653, :727-795): PL descrambling (lib/pl_descrambler.cc:36-105), pilot
  * block removal (:480-485) and phase de-rotation, restarted at every 16-slot segment of a coarse-corrected frame
