@@ -17,7 +17,8 @@ __all__ = ["get_fec_info", "rate_id", "LdpcDecoder", "BchDecoder", "Demapper", "
            "ldpc_table_names", "bb_descramble_sequence", "PlPayload",
            "pl_scrambling_rn", "HostBuffer", "PlFrontEnd", "plheader_symbols", "pls_parse", "apsk_points", "demap_table_check",
            "PlSync", "plsync_taps", "plsync_thresholds", "PlCoarse", "plcoarse_weights", "Rotator",
-           "SymbolSync", "symsync_loop_constants", "symsync_geometry", "symsync_taps", "FecEncoder", "enc_check"]
+           "SymbolSync", "symsync_loop_constants", "symsync_geometry", "symsync_taps", "FecEncoder", "enc_check",
+           "PlFramer", "plframer_layout"]
 
 DEFAULT_TRIALS = 25  # reference lib/ldpc_decoder_bb_impl.cc:391
 
@@ -897,7 +898,7 @@ def enc_check(standard=capi.STANDARD_DVBS2, framesize=capi.FECFRAME_NORMAL, rate
 class FecEncoder(_Handle):
     """The forward direction of FecChain on the device: BBFRAME bytes -> [BB scrambler] -> BCH -> LDPC -> mapper, every result bit
     for bit (notes/encoder.md). constellation: capi.MOD_QPSK, MOD_8PSK, MOD_16APSK, MOD_32APSK or capi.ENC_NO_MAPPER. PL framing
-    is not part of it. The reference has no transmit blocks to mirror."""
+    is not part of it (PlFramer takes the symbols on). The reference has no transmit blocks to mirror."""
     _destroy = lib.dvbs2_enc_destroy
     OUTPUTS = ("bch_cw", "ldpc_cw", "syms")
 
@@ -957,3 +958,63 @@ class FecEncoder(_Handle):
 
     def work_device(self, d_in, n_frames, d_bch_cw=0, d_ldpc_cw=0, d_syms=0, stream=0):
         check(lib.dvbs2_enc_encode_device(self._h, d_in, n_frames, d_bch_cw or None, d_ldpc_cw or None, d_syms or None, stream or None))
+
+
+def _plsc_array(plscs):
+    a = np.asarray(plscs)
+    if a.ndim != 1 or (a.size and (a.dtype.kind not in "iu" or a.min() < 0 or a.max() > 255)):
+        raise ValueError("plscs: a vector of integers in 0..127")
+    return np.ascontiguousarray(a, np.uint8)
+
+
+def plframer_layout(plscs):
+    """Where PlFramer reads and writes the frames of a sequence (dvbs2_plframer_layout): a dict of in_offset, out_offset (int64 per
+    frame, in complex symbols; a dummy frame reads nothing) and the totals in_syms, out_syms. Host only."""
+    a = _plsc_array(plscs)
+    ino, outo = np.zeros(a.size, np.int64), np.zeros(a.size, np.int64)
+    tin, tout = C.c_int64(), C.c_int64()
+    check(lib.dvbs2_plframer_layout(a.ctypes.data if a.size else None, int(a.size), ino.ctypes.data, outo.ctypes.data, C.byref(tin), C.byref(tout)))
+    return dict(in_offset=ino, out_offset=outo, in_syms=tin.value, out_syms=tout.value)
+
+
+class PlFramer(_Handle):
+    """PL framing, the step behind FecEncoder: PLHEADER, pilot blocks and PL scrambling of a sequence of frames with mixed MODCODs and
+    dummy frames, every output bit for bit (notes/plframer.md). The input is the XFECFRAMEs of the non-dummy frames back to back."""
+    _destroy = lib.dvbs2_plframer_destroy
+
+    def __init__(self, gold_code=0, max_frames=16, device=0):
+        check(lib.dvbs2_plframer_create(C.byref(self._h), int(gold_code), int(max_frames), device))
+        self.gold_code, self.max_frames, self.plscs = gold_code, max_frames, np.zeros(0, np.uint8)
+        self._params()
+
+    def _params(self):
+        n, tin, tout = C.c_int(), C.c_int64(), C.c_int64()
+        check(lib.dvbs2_plframer_params(self._h, C.byref(n), C.byref(tin), C.byref(tout)))
+        self.n_frames, self.in_syms, self.out_syms = n.value, tin.value, tout.value
+
+    def set_sequence(self, plscs):
+        """The PLSCs of the frames of one call, in stream order. Not while work of the handle is in flight."""
+        a = _plsc_array(plscs)
+        check(lib.dvbs2_plframer_set_sequence(self._h, a.ctypes.data if a.size else None, int(a.size)))
+        self.plscs = a
+        self._params()
+
+    def work(self, xfecframes, n_frames=None, closing_plsc=-1):
+        """HOST buffer: complex64, the XFECFRAMEs the first n_frames (default: all) of the sequence read, flat or any shape. Returns
+        the PLFRAMEs back to back (+ the closing header) as a complex64 vector."""
+        nf = self.n_frames if n_frames is None else int(n_frames)
+        if not 0 <= nf <= self.n_frames:
+            raise ValueError(f"n_frames: 0..{self.n_frames}")
+        lay = plframer_layout(self.plscs[:nf])
+        x = np.asarray(xfecframes)
+        if x.dtype != np.complex64:
+            raise TypeError(f"xfecframes must be complex64, not {x.dtype}")
+        if not x.flags.c_contiguous or x.size != lay["in_syms"]:
+            raise ValueError(f"xfecframes: expected {lay['in_syms']} C-contiguous symbols, got shape {x.shape}")
+        out = np.empty(lay["out_syms"] + (90 if closing_plsc >= 0 and nf else 0), np.complex64)
+        check(lib.dvbs2_plframer_frame(self._h, x.ctypes.data if x.size else None, nf, int(closing_plsc), out.ctypes.data if out.size else None))
+        return out
+
+    def work_device(self, d_xfecframes, n_frames, closing_plsc, d_plframes, stream=0):
+        """DEVICE addresses, asynchronous on `stream`: writes out_offset[n_frames] (+ 90 with a closing header) symbols."""
+        check(lib.dvbs2_plframer_frame_device(self._h, d_xfecframes or None, int(n_frames), int(closing_plsc), d_plframes or None, stream or None))

@@ -216,6 +216,13 @@ SYMBOLS = {
     "dvbs2_enc_check": (_i, [_i, _i, _i, _i]),
     "dvbs2_enc_encode_device": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "dvbs2_enc_encode": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    "dvbs2_plframer_layout": (_i, [_vp, _i, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "dvbs2_plframer_create": (_i, [C.POINTER(_vp), _i, _i, _i]),
+    "dvbs2_plframer_destroy": (None, [_vp]),
+    "dvbs2_plframer_set_sequence": (_i, [_vp, _vp, _i]),
+    "dvbs2_plframer_params": (_i, [_vp, _ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "dvbs2_plframer_frame_device": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "dvbs2_plframer_frame": (_i, [_vp, _vp, _i, _i, _vp]),
 }
 
 if not os.path.exists(LIB_PATH):

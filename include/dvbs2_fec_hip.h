@@ -328,7 +328,8 @@ int dvbs2_chain_ldpc_fallback_rounds(const dvbs2_chain_t* h);
 /* ---- the forward direction: BBFRAME bytes -> [BB scrambler] -> systematic BCH -> systematic LDPC -> bit interleaver and mapper ->
  * XFECFRAME symbols, the exact inverse of what the chain above undoes, every result bit for bit. The reference has no counterpart
  * beyond bch_codec::encode (lib/bch.cc:158-173); its transmit application takes its FEC from gr-dtv. PL framing (PLHEADER, pilots,
- * PL scrambling) is NOT part of this: it is the step that is left between these symbols and a PLFRAME.
+ * PL scrambling) is NOT part of this: dvbs2_plframer_* below takes these symbols to PLFRAMEs. What is left of a transmitter is BB
+ * framing (BBHEADER, TS framing) in front of it and pulse shaping behind the PLFRAMEs.
  * input       in_bits / 8 bytes per frame, first bit = bit 7; with every stage present a BBFRAME of bch_k / 8 bytes
  * BCH cw      bch_n / 8 bytes: the message unchanged (scrambled if scrambling is on), then the remainder of m(x) x^(n-k) mod g(x), highest
  *             power first -- the layout dvbs2_bch_decode reads (lib/bch.cc:158-173, :436-449). n and k are multiples of 8 (medium
@@ -373,6 +374,51 @@ int dvbs2_enc_encode_device(dvbs2_enc_t* h, const uint8_t* d_in, int n_frames, u
                             float* d_syms, void* stream);
 /* the same on HOST pointers, synchronous, staged through buffers of the handle */
 int dvbs2_enc_encode(dvbs2_enc_t* h, const uint8_t* in, int n_frames, uint8_t* bch_cw, uint8_t* ldpc_cw, float* syms);
+
+/* ---- PL framer: XFECFRAME symbols -> PLFRAMEs (ETSI EN 302 307-1 clauses 5.5.1 - 5.5.4), the stage dvbs2_physical_cc has in the
+ * reference's transmit flowgraph (apps/dvbs2-tx:619-636; the block is gr-dtv's). The exact inverse of the payload step below with zero
+ * phases: multiplying by j^Rn is a swap and a sign flip, PLHEADER symbols and pilots are constants, so every output is defined bit for
+ * bit. One streaming kernel, one launch per call.
+ * A handle holds a gold code and a SEQUENCE: the PLSCs of the frames of one call, in stream order (mixed MODCODs and dummy frames).
+ * Frame f, with the geometry dvbs2_pls_parse reports for plsc[f], occupies plframe_len output symbols from out_offset[f]:
+ *   PLHEADER  90 symbols, the floats of dvbs2_plheader_symbols(plsc[f]) unchanged; not PL-scrambled
+ *   payload   payload_len symbols. Payload index k lies in pilot block k / 1476 when n_pilots > 0, k % 1476 >= 1440 and k / 1476 <
+ *             n_pilots (n_pilots = (n_slots - 1) >> 4: a frame whose slot count is a multiple of 16 has NO pilot block after its last
+ *             segment). Before scrambling the symbol is the pilot (S, S), S = 0.70710678118654752440f, or symbol k - 36 (k / 1476)
+ *             (k without pilots) of the frame's XFECFRAME at in_offset[f].
+ *   dummy     MODCOD 0: 36 slots, never pilots whatever bit 0 of the PLSC says (bit 0 still selects the header); it consumes NO input
+ *             and all 3240 payload symbols are (S, S) before scrambling (clause 5.5.1)
+ *   PL scrambling of the payload by Rn(k) (dvbs2_pl_scrambling_rn), k restarting at 0 in every frame: (a, b) becomes (a, b), (-b, a),
+ *             (-a, -b), (b, -a) for Rn = 0, 1, 2, 3. Negation is a sign flip (0.0 becomes -0.0); no multiplication takes place.
+ *   closing   closing_plsc >= 0: after the last framed frame, the 90 PLHEADER symbols of that PLSC -- the layout
+ *             dvbs2_plframe_process_device reads with has_trailing_header = 1, and what dvbs2_plsync_search_device needs to report the
+ *             last frame under its buffer-end rule. -1: none.
+ * Input: the XFECFRAMEs of the non-dummy frames back to back in sequence order; output: the PLFRAMEs back to back. Every frame length,
+ * 90, 1440 and 1476 is even, so every offset is a multiple of two symbols and, from a 16-byte-aligned base, of 16 bytes: such buffers
+ * get 16-byte loads and stores, 8-byte aligned ones an 8-byte path with the same bits. A caller with several MODCODs lets each
+ * dvbs2_enc_* handle write its runs of frames at in_offset of the shared input buffer (dvbs2_enc_encode_device with d_syms there).
+ * Refused with DVBS2_EINVAL and a text that names the argument and the frame index: a PLSC above 127 or one with a reserved MODCOD
+ * (29..31), in layout, set_sequence and closing_plsc, as dvbs2_plframe_create refuses them. gold_code 0 .. 2^18-2, max_frames 1..65535. ---- */
+typedef struct dvbs2_plframer dvbs2_plframer_t;
+/* host only, no device needed: in_offset[n_frames], out_offset[n_frames] and the two totals; every output nullable */
+int dvbs2_plframer_layout(const uint8_t* plsc, int n_frames, int64_t* in_offset, int64_t* out_offset, int64_t* in_syms,
+                          int64_t* out_syms);
+/* a fresh handle has an empty sequence */
+int dvbs2_plframer_create(dvbs2_plframer_t** h, int gold_code, int max_frames, int device);
+void dvbs2_plframer_destroy(dvbs2_plframer_t* h);
+/* configuration call, synchronous, not while work of the handle is in flight; n_frames 0..max_frames (above: DVBS2_ESIZE). A refused
+ * call leaves the sequence as it was. */
+int dvbs2_plframer_set_sequence(dvbs2_plframer_t* h, const uint8_t* plsc, int n_frames);
+/* of the sequence; each nullable */
+int dvbs2_plframer_params(const dvbs2_plframer_t* h, int* n_frames, int64_t* in_syms, int64_t* out_syms);
+/* DEVICE pointers, 8-byte aligned. Frames the FIRST n_frames of the sequence (above its length: DVBS2_ESIZE) and writes exactly
+ * out_offset[n_frames] symbols, plus 90 for the closing header, and nothing else. Asynchronous on `stream`, no allocation, no host
+ * synchronisation. n_frames == 0 returns DVBS2_OK and writes nothing; a null buffer with n_frames > 0 is DVBS2_EINVAL, but d_xfecframes
+ * may be null when the framed prefix holds dummy frames only. The buffers must not overlap. */
+int dvbs2_plframer_frame_device(dvbs2_plframer_t* h, const float* d_xfecframes, int n_frames, int closing_plsc,
+                                float* d_plframes, void* stream);
+/* the same on HOST pointers, synchronous, staged through buffers of the handle */
+int dvbs2_plframer_frame(dvbs2_plframer_t* h, const float* xfecframes, int n_frames, int closing_plsc, float* plframes);
 
 /* ---- upstream neighbour: the PLFRAME payload step of plsync_cc_impl::handle_payload()
  * (reference lib/plsync_cc_impl.cc:644-653, :727-795): PL descrambling (lib/pl_descrambler.cc:36-105), pilot

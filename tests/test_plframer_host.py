@@ -1,0 +1,104 @@
+"""CPU: the host side of the PL framer -- dvbs2_plframer_layout over the whole PLSC range and a named sequence, the null-handle answers
+of every dvbs2_plframer_* handle entry, and the layout code once more in a stand-alone program built with the host sanitizers."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import fec_testlib as T
+import plframe_model as M
+import plframer_model as F
+import plsync_model as PS
+from dvbs2rx_amd import capi, plframer_layout, pls_parse
+
+CSRC = os.path.join(T.ROOT, "gr-dvbs2rx_amd", "csrc")
+
+
+def _err():
+    return capi.lib.dvbs2_last_error().decode()
+
+
+def _layout_rc(plscs):
+    a = np.ascontiguousarray(plscs, np.uint8)
+    return capi.lib.dvbs2_plframer_layout(a.ctypes.data, int(a.size), None, None, None, None)
+
+
+def test_layout_over_the_whole_plsc_range():
+    for plsc in range(128):
+        if plsc >> 2 in F.RESERVED:
+            assert _layout_rc([plsc]) == capi.EINVAL and _err() == "plsc[0] names a reserved MODCOD (29..31)", plsc
+            assert _layout_rc([4, 4, plsc]) == capi.EINVAL and _err() == "plsc[2] names a reserved MODCOD (29..31)", plsc
+            continue
+        lay, p = plframer_layout([plsc]), pls_parse(plsc)
+        assert lay["in_offset"].tolist() == [0] and lay["out_offset"].tolist() == [0]
+        assert lay["out_syms"] == p["plframe_len"] == M.pls_parse(plsc)["plframe_len"]
+        assert lay["in_syms"] == (0 if plsc >> 2 == 0 else p["xfecframe_len"])
+    assert _layout_rc([128]) == capi.EINVAL and _err() == "plsc[0] out of range (0..127)"
+    assert _layout_rc([4, 255]) == capi.EINVAL and _err() == "plsc[1] out of range (0..127)"
+    assert capi.lib.dvbs2_plframer_layout(None, 1, None, None, None, None) == capi.EINVAL
+    empty = plframer_layout([])
+    assert (empty["in_syms"], empty["out_syms"], empty["in_offset"].size) == (0, 0, 0)
+
+
+def test_layout_of_the_named_sequence_is_the_running_sums():
+    lay, want = plframer_layout(PS.ACM_PLSCS), F.layout(PS.ACM_PLSCS)
+    infos = [M.pls_parse(p) for p in PS.ACM_PLSCS]
+    run_in = np.concatenate([[0], np.cumsum([0 if i["dummy_frame"] else i["xfecframe_len"] for i in infos])])
+    run_out = np.concatenate([[0], np.cumsum([i["plframe_len"] for i in infos])])
+    assert lay["in_offset"].tolist() == run_in[:-1].tolist() == want["in_offset"].tolist()
+    assert lay["out_offset"].tolist() == run_out[:-1].tolist() == want["out_offset"].tolist()
+    assert (lay["in_syms"], lay["out_syms"]) == (run_in[-1], run_out[-1]) == (want["in_syms"], want["out_syms"])
+    assert sum(i["dummy_frame"] for i in infos) == 2  # the sequence does hold frames that read nothing
+
+
+def test_null_handle():
+    lib = capi.lib
+    names = [n for n in capi.SYMBOLS if n.startswith("dvbs2_plframer_") and n not in ("dvbs2_plframer_layout", "dvbs2_plframer_create")]
+    assert sorted(names) == ["dvbs2_plframer_destroy", "dvbs2_plframer_frame", "dvbs2_plframer_frame_device", "dvbs2_plframer_params",
+                             "dvbs2_plframer_set_sequence"]
+    for name in names:
+        zero = [0 if a in (C.c_int, C.c_int64) else None for a in capi.SYMBOLS[name][1]]
+        assert lib.dvbs2_get_fec_info(0, 0, 0, None) == capi.EINVAL  # leaves another text behind: the one below is this entry's own
+        ret = getattr(lib, name)(*zero)
+        if name.endswith("_destroy"):
+            assert ret is None  # void: a null handle is ignored
+        else:
+            assert (ret, _err()) == (capi.EINVAL, "null handle"), name
+    assert lib.dvbs2_plframer_create(None, 0, 1, 0) == capi.EINVAL and _err() == "null handle pointer"
+
+
+@pytest.fixture(scope="module")
+def layout_exe(tmp_path_factory):
+    """tests/plframer_host_main.cpp with the host source it calls, host code under AddressSanitizer and UBSan (device code is not
+    instrumented and none of it runs)."""
+    exe = str(tmp_path_factory.mktemp("plframer") / "plframer_host_main")
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined"]
+    subprocess.check_call([hipcc, "-x", "hip", "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", *san,
+                           os.path.join(T.ROOT, "tests", "plframer_host_main.cpp"), os.path.join(CSRC, "plframe_hip.hip"),
+                           os.path.join(CSRC, "plpayload_hip.hip"), "-o", exe])
+    return exe
+
+
+def test_layout_program_under_the_host_sanitizers(layout_exe):
+    seqs = [[p] for p in range(129)] + [list(PS.ACM_PLSCS), PS.ACM_PLSCS[:5] + [29 << 2] + PS.ACM_PLSCS[5:], PS.ACM_PLSCS * 40, []]
+    text = "".join(" ".join(map(str, s)) + "\n" for s in seqs)
+    r = subprocess.run([layout_exe], input=text, capture_output=True, text=True)
+    assert r.returncode == 0 and r.stderr == "", r.stderr  # a sanitizer report goes to stderr and ends the program
+    lines = r.stdout.splitlines()
+    assert len(lines) == len(seqs)
+    n_refused = 0
+    for seq, line in zip(seqs, lines):
+        bad = [i for i, p in enumerate(seq) if p > 127 or p >> 2 in F.RESERVED]
+        if bad:
+            why = "out of range (0..127)" if seq[bad[0]] > 127 else "names a reserved MODCOD (29..31)"
+            assert line == "refused: plsc[%d] %s" % (bad[0], why), seq
+            n_refused += 1
+            continue
+        want = F.layout(seq)
+        offs, totals = line.split("|")
+        assert [tuple(map(int, t.split(":"))) for t in offs.split()] == list(zip(want["in_offset"].tolist(), want["out_offset"].tolist())), seq
+        assert tuple(map(int, totals.split())) == (want["in_syms"], want["out_syms"]), seq
+    assert n_refused == 12 + 1 + 1

@@ -3,7 +3,13 @@
 (scrambler on) -> AWGN added on the device with torch (fixed seed) -> FecChain.work_device (descrambler on) -> compared on the
 device. Only the error counts come back to the host. A tool, not a test: it asserts no error rate.
 
+--pl pilots | nopilots puts the physical layer in between: FecEncoder -> PlFramer (the batch as a CCM sequence plus a closing header,
+PL scrambling code --gold) -> AWGN on the whole PLFRAME stream, headers and pilots included -> PlFrontEnd.work_device (trailing header,
+frames coarse-corrected: PLSC decoding, pilot / header phase estimates, de-rotation, descrambling) -> FecChain. The JSON line then also
+counts the frames whose decoded PLSC was wrong. --pl off (the default) is the path above, unchanged.
+
   python tools/fer_device.py --rate C1_2 --constellation qpsk --esn0 1.2 --frames 1000000 --batch 4096
+  python tools/fer_device.py --rate C1_2 --constellation qpsk --esn0 1.2 --frames 100000 --batch 4096 --pl pilots --gold 5
 Prints one JSON line."""
 import argparse
 import json
@@ -13,6 +19,12 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gr-dvbs2rx_amd", "python"))
+
+# MODCOD numbers of EN 302 307-1 table 12, in order from 1
+MODCODS = ([("qpsk", r) for r in ("C1_4", "C1_3", "C2_5", "C1_2", "C3_5", "C2_3", "C3_4", "C4_5", "C5_6", "C8_9", "C9_10")] +
+           [("8psk", r) for r in ("C3_5", "C2_3", "C3_4", "C5_6", "C8_9", "C9_10")] +
+           [("16apsk", r) for r in ("C2_3", "C3_4", "C4_5", "C5_6", "C8_9", "C9_10")] +
+           [("32apsk", r) for r in ("C3_4", "C4_5", "C5_6", "C8_9", "C9_10")])
 
 
 def main():
@@ -25,9 +37,11 @@ def main():
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--trials", type=int, default=0, help="LDPC iteration cap (0: the reference's 25)")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--pl", choices=("off", "pilots", "nopilots"), default="off", help="frame into PLFRAMEs and receive through PlFrontEnd")
+    ap.add_argument("--gold", type=int, default=0, help="PL scrambling code (with --pl)")
     a = ap.parse_args()
     import torch
-    from dvbs2rx_amd import FecChain, FecEncoder, capi
+    from dvbs2rx_amd import FecChain, FecEncoder, PlFramer, PlFrontEnd, capi
     fs = capi.FECFRAME_NORMAL if a.framesize == "normal" else capi.FECFRAME_SHORT
     mod = {"qpsk": capi.MOD_QPSK, "8psk": capi.MOD_8PSK, "16apsk": capi.MOD_16APSK, "32apsk": capi.MOD_32APSK}[a.constellation]
     batch = min(a.batch, a.frames)
@@ -48,12 +62,37 @@ def main():
     frame_err = torch.zeros((), dtype=torch.int64, device="cuda")
     bit_err = torch.zeros((), dtype=torch.int64, device="cuda")
     bch_fail = torch.zeros((), dtype=torch.int64, device="cuda")
+    plsc_err = torch.zeros((), dtype=torch.int64, device="cuda")
+    if a.pl != "off":
+        if (a.constellation, a.rate) not in MODCODS:
+            sys.exit(f"--pl: DVB-S2 has no MODCOD for {a.constellation} {a.rate}")
+        plsc = ((MODCODS.index((a.constellation, a.rate)) + 1) << 2) | ((a.framesize == "short") << 1) | (a.pl == "pilots")
+        framer = PlFramer(a.gold, max_frames=batch)
+        front = PlFrontEnd(a.gold, plsc, max_frames=batch)
+        assert front.xfecframe_len == enc.n_syms
+        d_xfec = torch.empty((batch, enc.n_syms, 2), dtype=torch.float32, device="cuda")
+        d_pl = torch.empty((batch * front.plframe_len + 90, 2), dtype=torch.float32, device="cuda")
+        d_cc = torch.ones((batch,), dtype=torch.int32, device="cuda")
+        d_cf = torch.zeros((batch,), dtype=torch.float32, device="cuda")  # read by the pilotless front end only
+        d_plsc = torch.empty((batch,), dtype=torch.uint8, device="cuda")
+        framed = 0
     done, t0 = 0, time.time()
     while done < a.frames:
         nf = min(batch, a.frames - done)
         d_in = torch.randint(0, 256, (nf, enc.in_bytes), dtype=torch.uint8, device="cuda", generator=gen)
-        enc.work_device(d_in.data_ptr(), nf, d_syms=d_syms.data_ptr(), stream=st)
-        d_syms[:nf].add_(torch.randn((nf, enc.n_syms, 2), dtype=torch.float32, device="cuda", generator=gen), alpha=sigma)
+        if a.pl == "off":
+            enc.work_device(d_in.data_ptr(), nf, d_syms=d_syms.data_ptr(), stream=st)
+            d_syms[:nf].add_(torch.randn((nf, enc.n_syms, 2), dtype=torch.float32, device="cuda", generator=gen), alpha=sigma)
+        else:
+            if framed != nf:  # the last batch may be shorter
+                framer.set_sequence([plsc] * nf)
+                framed = nf
+            n_pl = nf * front.plframe_len + 90
+            enc.work_device(d_in.data_ptr(), nf, d_syms=d_xfec.data_ptr(), stream=st)
+            framer.work_device(d_xfec.data_ptr(), nf, plsc, d_pl.data_ptr(), st)
+            d_pl[:n_pl].add_(torch.randn((n_pl, 2), dtype=torch.float32, device="cuda", generator=gen), alpha=sigma)
+            front.work_device(d_pl.data_ptr(), nf, 1, d_cc.data_ptr(), d_cf.data_ptr(), d_syms.data_ptr(), st, plsc_decoded=d_plsc.data_ptr())
+            plsc_err += (d_plsc[:nf] != plsc).sum()
         chain.work_device(d_syms.data_ptr(), nf, d_n0.data_ptr(), 1, d_msg.data_ptr(), 0, d_corr.data_ptr(), st)
         diff = popcount[(d_msg[:nf] ^ d_in).long()].sum(dim=1)
         frame_err += (diff != 0).sum()
@@ -63,9 +102,14 @@ def main():
     torch.cuda.synchronize()
     dt = time.time() - t0
     fe, be = int(frame_err.item()), int(bit_err.item())
-    print(json.dumps(dict(framesize=a.framesize, rate=a.rate, constellation=a.constellation, esn0_db=a.esn0, frames=done, batch=batch,
-                          seed=a.seed, frame_errors=fe, bit_errors=be, bch_failures=int(bch_fail.item()), fer=fe / done,
-                          ber=be / (done * enc.in_bits), seconds=dt, frames_per_s=done / dt)))
+    out = dict(framesize=a.framesize, rate=a.rate, constellation=a.constellation, esn0_db=a.esn0, frames=done, batch=batch,
+               seed=a.seed, frame_errors=fe, bit_errors=be, bch_failures=int(bch_fail.item()), fer=fe / done,
+               ber=be / (done * enc.in_bits), seconds=dt, frames_per_s=done / dt)
+    if a.pl != "off":
+        out.update(pl=a.pl, gold=a.gold, plsc=plsc, plsc_errors=int(plsc_err.item()))
+        framer.close()
+        front.close()
+    print(json.dumps(out))
     enc.close()
     chain.close()
 
