@@ -41,8 +41,8 @@ int symsync_geometry(int sps, int rrc_delay, int n_subfilt, int interp, int* sub
     return 0;
 }
 
-// root raised cosine at t symbols, unit symbol rate; the two singular points by their limits
-static double rrc(double t, double a)
+// root raised cosine at t symbols, unit symbol rate; the two singular points by their limits (declared in symsync_hip.h: pulse_taps uses it too)
+double rrc(double t, double a)
 {
     const double pi = M_PI;
     if (t == 0.0) return 1.0 - a + 4.0 * a / pi;

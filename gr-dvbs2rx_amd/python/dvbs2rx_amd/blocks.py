@@ -18,7 +18,7 @@ __all__ = ["get_fec_info", "rate_id", "LdpcDecoder", "BchDecoder", "Demapper", "
            "pl_scrambling_rn", "HostBuffer", "PlFrontEnd", "plheader_symbols", "pls_parse", "apsk_points", "demap_table_check",
            "PlSync", "plsync_taps", "plsync_thresholds", "PlCoarse", "plcoarse_weights", "Rotator",
            "SymbolSync", "symsync_loop_constants", "symsync_geometry", "symsync_taps", "FecEncoder", "enc_check",
-           "PlFramer", "plframer_layout"]
+           "PlFramer", "plframer_layout", "PulseShaper", "pulse_geometry", "pulse_taps", "pulse_scale_taps"]
 
 DEFAULT_TRIALS = 25  # reference lib/ldpc_decoder_bb_impl.cc:391
 
@@ -1018,3 +1018,64 @@ class PlFramer(_Handle):
     def work_device(self, d_xfecframes, n_frames, closing_plsc, d_plframes, stream=0):
         """DEVICE addresses, asynchronous on `stream`: writes out_offset[n_frames] (+ 90 with a closing header) symbols."""
         check(lib.dvbs2_plframer_frame_device(self._h, d_xfecframes or None, int(n_frames), int(closing_plsc), d_plframes or None, stream or None))
+
+
+def pulse_geometry(sps, rrc_delay):
+    """(ntaps, history in symbols, delay in samples) of the pulse shaper's own design (dvbs2_pulse_geometry). Host only."""
+    return _ints(3, lib.dvbs2_pulse_geometry, int(sps), int(rrc_delay))
+
+
+def pulse_taps(sps, rolloff, rrc_delay, tau=0.0, gain=None):
+    """The RRC taps of the pulse shaper as float32 [2 sps rrc_delay + 1]: the closed form behind symsync_taps, shifted by tau symbols
+    (|tau| <= 0.5) and scaled so that the taps at tau = 0 sum to gain (default sps, firdes's convention). Host only."""
+    taps = np.empty(pulse_geometry(sps, rrc_delay)[0], np.float32)
+    check(lib.dvbs2_pulse_taps(int(sps), float(rolloff), int(rrc_delay), float(tau), float(sps if gain is None else gain), taps.ctypes.data))
+    return taps
+
+
+def pulse_scale_taps(taps, sps, fullscale=1.0):
+    """A float32 copy of `taps` scaled by the rule of the reference's scale_rrc_taps (apps/dvbs2-tx:39-81): I and Q of the shaped
+    samples of unit-magnitude symbols stay within +-fullscale. Host only."""
+    t = np.array(taps, np.float32).reshape(-1)
+    check(lib.dvbs2_pulse_scale_taps(t.ctypes.data if t.size else None, int(t.size), int(sps), float(fullscale)))
+    return t
+
+
+class PulseShaper(_Handle):
+    """Pulse shaping, the step behind PlFramer: an interpolating FIR by the integer factor `sps` with real taps over complex symbols,
+    on a batch of independent streams whose histories stay on the device between calls (notes/pulse_shaper.md). n symbols in give
+    n * sps samples out, delayed by `delay` samples; flush with `history` zero symbols."""
+    _destroy = lib.dvbs2_pulse_destroy
+
+    TILE = capi.PULSE_TILE
+
+    def __init__(self, sps=2, rolloff=0.2, rrc_delay=5, max_streams=1, max_symbols=1 << 20, device=0, taps=None):
+        """taps: a float32 vector to use instead of the library's design (pulse_taps with tau = 0, gain = sps)."""
+        if taps is None:
+            check(lib.dvbs2_pulse_create(C.byref(self._h), int(sps), float(rolloff), int(rrc_delay), int(max_streams), int(max_symbols), device))
+        else:
+            t = np.ascontiguousarray(taps, np.float32).reshape(-1)
+            check(lib.dvbs2_pulse_create_taps(C.byref(self._h), int(sps), t.ctypes.data if t.size else None, int(t.size), int(max_streams),
+                                              int(max_symbols), device))
+        self.max_streams, self.max_symbols = max_streams, max_symbols
+        self.sps, self.ntaps, self.history, self.delay = _ints(4, lib.dvbs2_pulse_params, self._h)
+
+    def reset(self):
+        check(lib.dvbs2_pulse_reset(self._h))
+
+    def work(self, syms):
+        """HOST buffer of complex64 symbols of stream 0; returns the syms.size * sps complex64 samples."""
+        x = np.asarray(syms)
+        if x.dtype != np.complex64:
+            raise TypeError(f"syms must be complex64, not {x.dtype}")
+        if x.ndim != 1 or not x.flags.c_contiguous:
+            raise ValueError("syms must be a C-contiguous vector")
+        out = np.empty(x.size * self.sps, np.complex64)
+        check(lib.dvbs2_pulse_shape(self._h, x.ctypes.data if x.size else None, int(x.size), out.ctypes.data if x.size else None))
+        return out
+
+    def work_device(self, d_in, in_stride, n_syms, n_streams, d_out, out_stride, stream=0):
+        """DEVICE addresses (8-byte aligned, not overlapping), asynchronous on `stream`: stream s reads n_syms complex64 symbols at
+        d_in + 8 * s * in_stride and writes n_syms * sps samples at d_out + 8 * s * out_stride. One call in flight per handle."""
+        check(lib.dvbs2_pulse_shape_device(self._h, d_in or None, int(in_stride), int(n_syms), int(n_streams), d_out or None, int(out_stride),
+                                           stream or None))

@@ -25,6 +25,7 @@ FECFRAME_SHORT, FECFRAME_NORMAL, FECFRAME_MEDIUM = 0, 1, 2
 OM_CODEWORD, OM_MESSAGE = 0, 1
 MOD_QPSK, MOD_8PSK, MOD_16APSK, MOD_32APSK = 0, 4, 6, 8
 ENC_NO_MAPPER = -1
+PULSE_TILE = 512  # DVBS2_PULSE_TILE: symbols per workgroup of the pulse shaper's kernel
 
 
 class FecInfo(C.Structure):
@@ -181,6 +182,16 @@ SYMBOLS = {
     "dvbs2_symsync_finish": (_i, [_vp, _vp, _vp, _vp]),
     "dvbs2_symsync_state": (_i, [_vp, _i, C.POINTER(SymSyncState)]),
     "dvbs2_symsync_work": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _ip, _ip, _ip]),
+    "dvbs2_pulse_geometry": (_i, [_i, _i, _ip, _ip, _ip]),
+    "dvbs2_pulse_taps": (_i, [_i, _f, _i, C.c_double, C.c_double, _vp]),
+    "dvbs2_pulse_scale_taps": (_i, [_vp, _i, _i, C.c_double]),
+    "dvbs2_pulse_create": (_i, [C.POINTER(_vp), _i, _f, _i, _i, _i, _i]),
+    "dvbs2_pulse_create_taps": (_i, [C.POINTER(_vp), _i, _vp, _i, _i, _i, _i]),
+    "dvbs2_pulse_destroy": (None, [_vp]),
+    "dvbs2_pulse_reset": (_i, [_vp]),
+    "dvbs2_pulse_params": (_i, [_vp, _ip, _ip, _ip, _ip]),
+    "dvbs2_pulse_shape_device": (_i, [_vp, _vp, C.c_int64, _i, _i, _vp, C.c_int64, _vp]),
+    "dvbs2_pulse_shape": (_i, [_vp, _vp, _i, _vp]),
     "dvbs2_bbdeheader_create": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i]),
     "dvbs2_bbdeheader_create_raw": (_i, [C.POINTER(_vp), _i, _i, _i]),
     "dvbs2_bbdeheader_destroy": (None, [_vp]),

@@ -738,6 +738,56 @@ int dvbs2_symsync_state(dvbs2_symsync_t* h, int stream_index, dvbs2_symsync_stat
 int dvbs2_symsync_work(dvbs2_symsync_t* h, const float* in, int n_in, float* out, int max_out, int64_t* strobe_idx, double* mu, int* n_out,
                        int* consumed, int* status);
 
+/* ---- pulse shaping: PLFRAME symbols -> samples, the step behind dvbs2_plframer_* and the last one before a DAC: an integer-factor
+ * interpolating FIR with real taps over complex symbols. In the reference's transmit flowgraph (apps/dvbs2-tx:638-686) it is GNU Radio's
+ * interp_fir_filter_ccf over firdes.root_raised_cosine taps, optionally scaled by scale_rrc_taps (apps/dvbs2-tx:39-81). Neither block is
+ * in the reference tree: the stage is UNPINNED against them (dvbs2_pulse_create_taps takes firdes's own taps). What is defined, and
+ * tested bit for bit against a float32 restatement (tests/pulse_model.py), is the arithmetic:
+ *   with sps samples per symbol and taps h[0 .. ntaps), sample n = m sps + p of a stream is y[n] = sum over k = 0, 1, ... while
+ *   p + k sps < ntaps of h[p + k sps] * x[m - k]; real and imaginary part apart; each term a float product and then a float addition
+ *   (no fused multiply-add), in ascending k, onto an accumulator that starts at +0.0f. A phase without a tap (ntaps < sps) gives +0.0f.
+ *   x[j] for j < 0 is the stream's history: the symbols of earlier calls, zeros after create / reset.
+ * n_syms symbols in give exactly n_syms sps samples out. The stage delays the signal by (ntaps - 1) / 2 samples and drops nothing: a
+ * caller flushes by feeding `history` zero symbols. However a stream is cut into calls, the bits are those of one call.
+ * A handle works on a batch of independent streams and keeps each stream's history (the last ceil(ntaps / sps) - 1 symbols) on the
+ * device. Stream s of a call reads n_syms symbols at d_in + s in_stride and writes n_syms sps samples at d_out + s out_stride; data are
+ * interleaved (re, im) floats as for dvbs2_rotator_*, strides count complex elements and matter only when n_streams > 1. Buffers are
+ * 8-byte aligned; an output whose streams all start 16-byte aligned gets 16-byte stores, any other an 8-byte path with the same bits.
+ * Input and output must NOT overlap; this is not detected. Two launches per call (the samples, then the new histories), no allocation,
+ * no host synchronisation. ONE CALL IN FLIGHT PER HANDLE: a call reads the histories and rewrites them behind itself, so calls on one
+ * HIP stream may follow each other, and a call on another HIP stream needs the previous one to have finished. The kernel works in tiles
+ * of DVBS2_PULSE_TILE symbols per workgroup.
+ * Refused with DVBS2_ESIZE: n_syms > max_symbols, n_streams > max_streams. Refused with DVBS2_EINVAL and a text that names the argument:
+ * negative counts, a null buffer with n_syms > 0, with n_streams > 1 an in_stride < n_syms or an out_stride < n_syms sps. n_syms == 0 is
+ * a successful call that does nothing. Creation refuses (DVBS2_EINVAL) sps that is not an even integer in 2..64, ntaps < 1 or
+ * ceil(ntaps / sps) > 129, a tap that is not finite, max_streams outside 1..65535, max_symbols outside 1..2^30.
+ * Host only, no device needed: dvbs2_pulse_geometry (ntaps = 2 sps rrc_delay + 1, history = ceil(ntaps / sps) - 1 = 2 rrc_delay symbols,
+ * delay = sps rrc_delay samples; sps an even integer in 2..64, rrc_delay in 1..64, as for dvbs2_symsync_geometry), dvbs2_pulse_taps
+ * (h[i] = rrc((i - (ntaps - 1) / 2) / sps - tau, rolloff) gain / S, rrc the closed form behind dvbs2_symsync_taps and S the sum of the
+ * taps at tau = 0: the taps sum to gain at tau = 0 -- firdes's convention is gain = sps -- and tau, in symbols, |tau| <= 0.5, only
+ * shifts the pulse: a static timing offset; rolloff in [0, 1], gain finite and not zero; designed in double, rounded once) and
+ * dvbs2_pulse_scale_taps (the rule of scale_rrc_taps, in place: every tap times sqrt(2) fullscale / max over p < sps of the sum over k of
+ * |h[p + k sps]|, in double, rounded once). ---- */
+typedef struct dvbs2_pulse dvbs2_pulse_t;
+#define DVBS2_PULSE_TILE 512
+int dvbs2_pulse_geometry(int sps, int rrc_delay, int* ntaps, int* history, int* delay);
+int dvbs2_pulse_taps(int sps, float rolloff, int rrc_delay, double tau, double gain, float* taps);
+int dvbs2_pulse_scale_taps(float* taps, int ntaps, int sps, double fullscale);
+/* the library's design: dvbs2_pulse_taps with tau = 0 and gain = sps */
+int dvbs2_pulse_create(dvbs2_pulse_t** h, int sps, float rolloff, int rrc_delay, int max_streams, int max_symbols, int device);
+/* a caller's taps (firdes's own, scaled or shifted ones): any ntaps >= 1 with ceil(ntaps / sps) <= 129, every tap finite */
+int dvbs2_pulse_create_taps(dvbs2_pulse_t** h, int sps, const float* taps, int ntaps, int max_streams, int max_symbols, int device);
+void dvbs2_pulse_destroy(dvbs2_pulse_t* h);
+/* every history back to zeros; synchronous (waits for the device) */
+int dvbs2_pulse_reset(dvbs2_pulse_t* h);
+/* each nullable; history in symbols, delay = (ntaps - 1) / 2 in samples */
+int dvbs2_pulse_params(const dvbs2_pulse_t* h, int* sps, int* ntaps, int* history, int* delay);
+/* DEVICE pointers, asynchronous on `stream` */
+int dvbs2_pulse_shape_device(dvbs2_pulse_t* h, const float* d_in, int64_t in_stride, int n_syms, int n_streams, float* d_out,
+                             int64_t out_stride, void* stream);
+/* host pointers, synchronous: stream 0 of the handle, staged through buffers of the handle */
+int dvbs2_pulse_shape(dvbs2_pulse_t* h, const float* in, int n_syms, float* out);
+
 /* ---- downstream neighbour: BBFRAME de-header, replaces bbdeheader_bb_impl::general_work (reference
  * lib/bbdeheader_bb_impl.cc:144-264) with parse_bbheader (:77-136) and check_crc8 (:138-142, generator
  * x^8 + x^7 + x^6 + x^4 + x^2 + 1, :55). Input: whole descrambled BBFRAMEs of kbch / 8 bytes (what dvbs2_bch_decode /
