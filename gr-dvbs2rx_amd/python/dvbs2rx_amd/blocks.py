@@ -18,7 +18,8 @@ __all__ = ["get_fec_info", "rate_id", "LdpcDecoder", "BchDecoder", "Demapper", "
            "pl_scrambling_rn", "HostBuffer", "PlFrontEnd", "plheader_symbols", "pls_parse", "apsk_points", "demap_table_check",
            "PlSync", "plsync_taps", "plsync_thresholds", "PlCoarse", "plcoarse_weights", "Rotator",
            "SymbolSync", "symsync_loop_constants", "symsync_geometry", "symsync_taps", "FecEncoder", "enc_check",
-           "PlFramer", "plframer_layout", "PulseShaper", "pulse_geometry", "pulse_taps", "pulse_scale_taps"]
+           "PlFramer", "plframer_layout", "PulseShaper", "pulse_geometry", "pulse_taps", "pulse_scale_taps",
+           "BbFramer", "bbheader_build", "crc8"]
 
 DEFAULT_TRIALS = 25  # reference lib/ldpc_decoder_bb_impl.cc:391
 
@@ -779,6 +780,64 @@ class BbDeheader(_Handle):
 
     def reset(self, stream=0):
         check(lib.dvbs2_bbdeheader_reset(self._h, stream))
+
+
+def bbheader_build(matype1=0xF2, matype2=0, upl_bits=188 * 8, dfl_bits=0, sync=0x47, syncd_bits=0):
+    """Ten BBHEADER bytes with their CRC-8 (host only)."""
+    h = np.zeros(10, np.uint8)
+    check(lib.dvbs2_bbheader_build(h.ctypes.data, matype1, matype2, upl_bits, dfl_bits, sync, syncd_bits))
+    return h
+
+
+def crc8(data):
+    """The CRC-8 check byte of DVB-S2 mode adaptation over a bytes-like (host only)."""
+    d = np.frombuffer(bytes(data), np.uint8)
+    return check(lib.dvbs2_crc8(d.ctypes.data if d.size else None, d.size))
+
+
+class BbFramer(_Handle):
+    """BB framing, the mirror of BbDeheader: 188-byte MPEG-TS packets in, BBFRAMEs out (BBHEADER, a DATAFIELD of the CRC-encoded packet
+    stream, zero padding). The position in the stream, the tail of a partly consumed packet and its CRC are kept in the handle between
+    calls. dfl_bytes = 0: the largest DATAFIELD."""
+    _destroy = lib.dvbs2_bbframer_destroy
+
+    def __init__(self, standard=capi.STANDARD_DVBS2, framesize=capi.FECFRAME_NORMAL, rate="C1_2", max_frames=64, device=0,
+                 kbch_bits=None):
+        if kbch_bits is not None:
+            check(lib.dvbs2_bbframer_create_raw(C.byref(self._h), kbch_bits, max_frames, device))
+        else:
+            check(lib.dvbs2_bbframer_create(C.byref(self._h), standard, framesize, rate_id(rate), max_frames, device))
+        self.kbch_bytes, self.max_dfl_bytes, self.max_packets_per_call = _ints(3, lib.dvbs2_bbframer_params, self._h)
+
+    def set_matype(self, matype1=0xF2, matype2=0):
+        check(lib.dvbs2_bbframer_set_matype(self._h, matype1, matype2))
+
+    def need(self, n_frames, dfl_bytes=0):
+        """Whole packets the next call (n_frames, dfl_bytes) reads (host only)."""
+        return _ints(1, lib.dvbs2_bbframer_need, self._h, n_frames, dfl_bytes)[0]
+
+    def work(self, ts, n_frames, dfl_bytes=0):
+        """ts: at least need(n_frames, dfl_bytes) packets as uint8 -> (n_frames, kbch_bytes) uint8; self.packets_read says how many
+        packets were taken."""
+        t = np.ascontiguousarray(ts, dtype=np.uint8).reshape(-1)
+        assert t.size >= 188 * self.need(n_frames, dfl_bytes)
+        out = np.empty((max(n_frames, 0), self.kbch_bytes), np.uint8)
+        n = C.c_int()
+        check(lib.dvbs2_bbframer_process(self._h, t.ctypes.data if t.size else None, n_frames, dfl_bytes,
+                                         out.ctypes.data if out.size else None, C.byref(n)))
+        self.packets_read = n.value
+        return out
+
+    def work_device(self, d_ts, n_frames, d_bbframes, dfl_bytes=0, stream=0):
+        check(lib.dvbs2_bbframer_process_device(self._h, d_ts, n_frames, dfl_bytes, d_bbframes, stream))
+
+    def counters(self, stream=0):
+        c = capi.BbFramerCounters()
+        check(lib.dvbs2_bbframer_counters(self._h, C.byref(c), stream))
+        return {k: getattr(c, k) for k, _ in c._fields_}
+
+    def reset(self, stream=0):
+        check(lib.dvbs2_bbframer_reset(self._h, stream))
 
 
 class FecChain(_Handle):

@@ -39,6 +39,11 @@ class BbDeheaderCounters(C.Structure):
                 ("gaps", C.c_uint64), ("overruns", C.c_uint64), ("synched", C.c_int32), ("partial_ts_bytes", C.c_int32)]
 
 
+class BbFramerCounters(C.Structure):
+    """dvbs2_bbframer_counters_t"""
+    _fields_ = [("packets", C.c_uint64), ("bbframes", C.c_uint64), ("sync_errors", C.c_uint64)]
+
+
 class PlFrameEstimates(C.Structure):
     """dvbs2_plframe_estimates_t: addresses (device or host, by entry point), 0 = not wanted."""
     _fields_ = [("plsc_decoded", C.c_void_p), ("sof_phase", C.c_void_p), ("plheader_phase", C.c_void_p),
@@ -201,6 +206,18 @@ SYMBOLS = {
     "dvbs2_bbdeheader_finish": (_i, [_vp, C.POINTER(C.c_int64), _vp]),
     "dvbs2_bbdeheader_counters": (_i, [_vp, _vp, _vp]),
     "dvbs2_bbdeheader_reset": (_i, [_vp, _vp]),
+    "dvbs2_bbframer_create": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i]),
+    "dvbs2_bbframer_create_raw": (_i, [C.POINTER(_vp), _i, _i, _i]),
+    "dvbs2_bbframer_destroy": (None, [_vp]),
+    "dvbs2_bbframer_params": (_i, [_vp, _ip, _ip, _ip]),
+    "dvbs2_bbframer_set_matype": (_i, [_vp, _i, _i]),
+    "dvbs2_bbframer_need": (_i, [_vp, _i, _i, _ip]),
+    "dvbs2_bbframer_process_device": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "dvbs2_bbframer_process": (_i, [_vp, _vp, _i, _i, _vp, _ip]),
+    "dvbs2_bbframer_counters": (_i, [_vp, _vp, _vp]),
+    "dvbs2_bbframer_reset": (_i, [_vp, _vp]),
+    "dvbs2_bbheader_build": (_i, [_vp, _i, _i, _i, _i, _i, _i]),
+    "dvbs2_crc8": (_i, [_vp, C.c_size_t]),
     "dvbs2_chain_create": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i, _i, _i]),
     "dvbs2_chain_create_table": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _vp, _vp, _i, _i, _i]),
     "dvbs2_chain_destroy": (None, [_vp]),

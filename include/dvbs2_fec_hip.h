@@ -328,8 +328,8 @@ int dvbs2_chain_ldpc_fallback_rounds(const dvbs2_chain_t* h);
 /* ---- the forward direction: BBFRAME bytes -> [BB scrambler] -> systematic BCH -> systematic LDPC -> bit interleaver and mapper ->
  * XFECFRAME symbols, the exact inverse of what the chain above undoes, every result bit for bit. The reference has no counterpart
  * beyond bch_codec::encode (lib/bch.cc:158-173); its transmit application takes its FEC from gr-dtv. PL framing (PLHEADER, pilots,
- * PL scrambling) is NOT part of this: dvbs2_plframer_* below takes these symbols to PLFRAMEs. What is left of a transmitter is BB
- * framing (BBHEADER, TS framing) in front of it and pulse shaping behind the PLFRAMEs.
+ * PL scrambling) is NOT part of this: dvbs2_plframer_* below takes these symbols to PLFRAMEs. BB framing (BBHEADER, TS framing) in
+ * front of it is dvbs2_bbframer_*, pulse shaping behind the PLFRAMEs is dvbs2_pulse_*: with them the transmit direction is complete.
  * input       in_bits / 8 bytes per frame, first bit = bit 7; with every stage present a BBFRAME of bch_k / 8 bytes
  * BCH cw      bch_n / 8 bytes: the message unchanged (scrambled if scrambling is on), then the remainder of m(x) x^(n-k) mod g(x), highest
  *             power first -- the layout dvbs2_bch_decode reads (lib/bch.cc:158-173, :436-449). n and k are multiples of 8 (medium
@@ -817,6 +817,61 @@ int dvbs2_bbdeheader_process_device(dvbs2_bbdeheader_t* h, const uint8_t* d_bbfr
 int dvbs2_bbdeheader_finish(dvbs2_bbdeheader_t* h, int64_t* produced, void* stream);
 int dvbs2_bbdeheader_counters(dvbs2_bbdeheader_t* h, dvbs2_bbdeheader_counters_t* out, void* stream);
 int dvbs2_bbdeheader_reset(dvbs2_bbdeheader_t* h, void* stream);
+
+/* ---- BB framing: mode adaptation for MPEG-TS (EN 302 307-1 clauses 5.1.4 to 5.1.6), the mirror of dvbs2_bbdeheader_* above. In the
+ * reference's transmit flowgraph the place is held by gr-dtv's dvb_bbheader_bb(..., INPUTMODE_NORMAL, ...) (apps/dvbs2-tx:619-621).
+ * 188-byte TS packets in, BBFRAMEs of kbch_bytes out, every byte defined by the standard. Bytes only: nothing here has a tolerance.
+ *
+ * The handle is created for one kbch_bits: kbch_bytes = kbch_bits / 8, max_dfl_bytes = kbch_bytes - 10. It holds a position pos, the
+ * number of bytes of the CRC-encoded stream E consumed since create or reset. E is defined over the packets P[0], P[1], ... presented
+ * since then:
+ *   E[188 p + i] = P[p][i] for i = 1..187
+ *   E[188 p]     = for p >= 1 the CRC-8 of P[p - 1][1..187] (generator x^8 + x^7 + x^6 + x^4 + x^2 + 1, zero start, no reflection:
+ *                  the byte that makes check_crc8(packet, 188) of lib/bbdeheader_bb_impl.cc:138-142 pass)
+ *   E[0]         = P[0][0] unchanged (the receiver skips that byte when it synchronises)
+ * A call (n_frames, dfl_bytes) writes n_frames BBFRAMEs of kbch_bytes each, back to back. Frame f has s = pos + f * dfl_bytes and holds
+ *   bytes 0..9                  BBHEADER: MATYPE-1, MATYPE-2, UPL = 1504, DFL = 8 * dfl_bytes, SYNC = 0x47,
+ *                               SYNCD = 8 * ((188 - s mod 188) mod 188), then the CRC-8 of those nine bytes
+ *   bytes 10..10 + dfl_bytes-1  E[s .. s + dfl_bytes)
+ *   the rest, up to kbch_bytes  zero padding
+ * After the call pos += n_frames * dfl_bytes. dfl_bytes = 0 means max_dfl_bytes (packets straddle frames, as gr-dtv sends them);
+ * otherwise it lies in 188..max_dfl_bytes, so every DATAFIELD holds a packet start and SYNCD never needs the 0xFFFF case.
+ * (max_dfl_bytes / 188) * 188 gives whole packets per frame with padding; a short value on the last call flushes a stream; dfl_bytes may
+ * change from call to call.
+ * Packets a call reads: already presented P0 = ceil(pos / 188), needed up to P1 = ceil((pos + n_frames * dfl_bytes) / 188); the call
+ * reads exactly P1 - P0 whole 188-byte packets from its input, P[P0] .. P[P1 - 1]. The handle carries between calls on the device the
+ * unconsumed tail of a partly consumed packet (at most 187 bytes) and the CRC of the last packet presented. pos itself is arithmetic on
+ * the call arguments; the handle mirrors it on the host, advanced only when a call was launched, so dvbs2_bbframer_need answers
+ * without a synchronisation.
+ * A presented packet whose byte 0 is not 0x47 is framed all the same (for p >= 1 the byte is replaced anyway) and counted in
+ * sync_errors.
+ * Refusals, each with a text that names the argument: kbch_bits as the de-header's (>= 88, a multiple of 8, kbch_bits - 80 <= 65535)
+ * and max_dfl_bytes >= 188; max_frames in 1..65535; dfl_bytes 0 or in 188..max_dfl_bytes, otherwise DVBS2_EINVAL; matype bytes in
+ * 0..255; n_frames < 0 or n_frames > max_frames is DVBS2_ESIZE; input and output ranges of a call that overlap are DVBS2_EINVAL.
+ * n_frames == 0 is a valid call that changes nothing. */
+typedef struct dvbs2_bbframer dvbs2_bbframer_t;
+typedef struct { uint64_t packets, bbframes, sync_errors; } dvbs2_bbframer_counters_t;
+int dvbs2_bbframer_create(dvbs2_bbframer_t** h, int standard, int framesize, int rate, int max_frames, int device);
+int dvbs2_bbframer_create_raw(dvbs2_bbframer_t** h, int kbch_bits, int max_frames, int device);
+void dvbs2_bbframer_destroy(dvbs2_bbframer_t* h);
+int dvbs2_bbframer_params(const dvbs2_bbframer_t* h, int* kbch_bytes, int* max_dfl_bytes, int* max_packets_per_call);
+/* default 0xF2, 0 (TS, SIS, CCM, roll-off 0.20); applies to later calls */
+int dvbs2_bbframer_set_matype(dvbs2_bbframer_t* h, int matype1, int matype2);
+/* host only: P1 - P0 for the NEXT call */
+int dvbs2_bbframer_need(const dvbs2_bbframer_t* h, int n_frames, int dfl_bytes, int* n_packets);
+/* device pointers, asynchronous on `stream`: no allocation, no host synchronisation, one launch. Calls on one handle are ordered by
+ * the caller, as for dvbs2_enc_encode_device; the output is exactly what dvbs2_enc_encode_device takes as d_in for the same row (the
+ * BB scrambler stays where it is: dvbs2_enc_set_scramble). */
+int dvbs2_bbframer_process_device(dvbs2_bbframer_t* h, const uint8_t* d_ts, int n_frames, int dfl_bytes, uint8_t* d_bbframes, void* stream);
+/* host pointers, synchronous, staged through the handle; *n_packets_read = packets taken from ts */
+int dvbs2_bbframer_process(dvbs2_bbframer_t* h, const uint8_t* ts, int n_frames, int dfl_bytes, uint8_t* bbframes, int* n_packets_read);
+/* synchronises `stream` */
+int dvbs2_bbframer_counters(dvbs2_bbframer_t* h, dvbs2_bbframer_counters_t* out, void* stream);
+/* pos 0, nothing carried, counters zero */
+int dvbs2_bbframer_reset(dvbs2_bbframer_t* h, void* stream);
+/* host only, no device: ten BBHEADER bytes with their CRC-8; the check byte of a string (remainder of data * x^8), or DVBS2_EINVAL */
+int dvbs2_bbheader_build(uint8_t out[10], int matype1, int matype2, int upl_bits, int dfl_bits, int sync, int syncd_bits);
+int dvbs2_crc8(const uint8_t* data, size_t n);
 
 #ifdef __cplusplus
 }
