@@ -1,7 +1,8 @@
 """GPU: every path that turns symbols into LLRs -- the stand-alone demapper kernels, the demapper fused into the LDPC sweep
-kernel's load under every kernel build, the host entry's chunk loop -- and the SNR estimators, against the CPU restatement
-(bit-exact) and against the float64 reference of the formulas (fec_testlib.demap_f64 / snr_f64). Inputs: exact float32 ties,
-saturation edges, +-0, zeros, +-inf (QPSK), very small and very large N0, and one N0 per frame."""
+kernel's load under every kernel build, the APSK demapper launched in front of every build, the host entry's chunk loop -- and the
+SNR estimators, against the CPU restatement (bit-exact) and against the float64 reference of the formulas (fec_testlib.demap_f64 /
+snr_f64). Inputs: exact float32 ties, saturation edges, +-0, zeros, +-inf (QPSK), very small and very large N0, and one N0 per
+frame."""
 import functools
 import json
 import os
@@ -9,8 +10,9 @@ import os
 import numpy as np
 import pytest
 
+import apsk_model
 import fec_testlib as T
-from dvbs2rx_amd import Demapper, FecChain, capi, get_fec_info
+from dvbs2rx_amd import Demapper, FecChain, apsk_points, capi, get_fec_info
 
 pytestmark = pytest.mark.gpu
 
@@ -21,6 +23,29 @@ RATE_OF_ORDER = {0: "C3_4", 1: "C3_5", 2: "C25_36"}  # (the demapper uses the ra
 # float32 search reaches the ties 126.5, 127.5, -127.5, -128.5, +-0.5, +-1.5 (test_demap_reference.TIE_N0)
 EDGE_N0 = {4: (3e-30, 0.005, 0.3, 1.0, 1000.0, 3e30), 8: (1e-30, 0.001, 0.7, 1.0, 50.0, 3e30)}
 CAP, G = 20, 32
+APSK = (capi.MOD_16APSK, capi.MOD_32APSK)
+APSK_NAME = {capi.MOD_16APSK: "16apsk", capi.MOD_32APSK: "32apsk"}
+# Es/N0 [dB] of quasi-error-free operation, EN 302 307-1 table 13
+APSK_QEF_DB = {(capi.MOD_16APSK, "C2_3"): 8.97, (capi.MOD_16APSK, "C3_4"): 10.21, (capi.MOD_16APSK, "C4_5"): 11.03,
+               (capi.MOD_16APSK, "C5_6"): 11.61, (capi.MOD_16APSK, "C8_9"): 12.89, (capi.MOD_16APSK, "C9_10"): 13.13,
+               (capi.MOD_32APSK, "C3_4"): 12.73, (capi.MOD_32APSK, "C4_5"): 13.64, (capi.MOD_32APSK, "C5_6"): 14.28,
+               (capi.MOD_32APSK, "C8_9"): 15.69, (capi.MOD_32APSK, "C9_10"): 16.05}
+APSK_MARGIN_DB = 3.0  # above table 13, as in test_apsk_gpu.py
+# (constellation, rate, frame size) -> margin of a row whose CPU chain alone does not return every decodable frame at 3 dB and
+# cap 20, raised in 0.5 dB steps until it does. Empty: the CPU chain returns all 29 decodable frames of all 20 rows at 3 dB.
+APSK_ROW_MARGIN_DB = {}
+APSK_EDGE_N0 = (0.2, 0.05, 0.01)  # the N0 of test_apsk_gpu.N0_FRAMES: what apsk_model.check_vs_f64 accepts for the restatement
+APSK_ROWS = [(mod, rate, fs) for mod, rates in ((capi.MOD_16APSK, apsk_model.GAMMA_16), (capi.MOD_32APSK, apsk_model.GAMMA_32))
+             for rate in rates for fs in ((capi.FECFRAME_NORMAL,) if rate == "C9_10" else (capi.FECFRAME_NORMAL, capi.FECFRAME_SHORT))]
+
+
+def apsk_edge_frame(ns, n0, points_sent, k, rng):
+    """One frame of point + noise at this N0 with the planted symbols of test_apsk_gpu.demap_case: 0 and (1e3, -1e3) at both ends
+    and in the middle (k moves the middle ones from frame to frame)."""
+    fr = (points_sent + np.sqrt(n0 / 2) * (rng.normal(size=ns) + 1j * rng.normal(size=ns))).astype(np.complex64)
+    fr[[0, ns - 2, 1000 + k % 3]] = 0
+    fr[[1, ns - 1, 2001 + k % 3]] = 1e3 - 1e3j
+    return fr
 
 
 def edge_frame(ns, n0, constellation, rng):
@@ -196,10 +221,12 @@ def threshold_db(rate, c):
 
 @functools.lru_cache(maxsize=4)  # (the sweep-kernel builds reuse one case)
 def chain_case(standard, framesize, rate, constellation, nf, seed):
-    """nf frames for one MODCOD with one N0 per frame: decodable frames (Es/N0 0-1.5 dB above threshold_db), noise-only frames and
-    edge/tie frames in every whole group of 32, decodable frames only in the tail (its CPU decode uses the scalar restatement).
+    """nf frames for one MODCOD with one N0 per frame: decodable frames (Es/N0 0-1.5 dB above threshold_db; 16APSK / 32APSK: above
+    table 13 of EN 302 307-1 + the row's margin), noise-only frames and edge/tie frames (APSK: apsk_edge_frame) in every whole group
+    of 32, decodable frames only in the tail (its CPU decode uses the scalar restatement).
     Returns (symbols, per-frame N0, sent messages, decodable mask, CPU chain for per-frame N0, CPU chain for N0 = n0[0])."""
-    c = CONST_SIZE[constellation]
+    apsk = constellation in APSK
+    c = 2 ** apsk_model.N_MOD[constellation] if apsk else CONST_SIZE[constellation]
     fi = get_fec_info(standard, framesize, rate)
     m, prim = T.BCH_FIELDS[framesize]
     ob = T.OracleBch(m, prim, fi["bch_t"], fi["bch_n"])
@@ -208,13 +235,19 @@ def chain_case(standard, framesize, rate, constellation, nf, seed):
     info = np.zeros((nf, T.ldpc_info(fi["table"])[1]), np.uint8)  # shortened codes (VLSNR): the bits past the BCH codeword are 0
     info[:, :fi["bch_n"]] = np.unpackbits(ob.encode_bytes(sent), axis=1)
     cw = T.ldpc_encode(fi["table"], info)
-    if c == 4:
+    if apsk:
+        pts = apsk_model.map_bits(cw, apsk_model.points(constellation, rate))  # natural column order
+    elif c == 4:
         pts = ((1 - 2.0 * cw[:, 0::2]) + 1j * (1 - 2.0 * cw[:, 1::2])) * np.sqrt(0.5)
     else:
         rows = cw.shape[1] // 3
         pts = T.map_8psk(np.stack([cw[:, a:a + rows] for a in T.column_bases(rows, T.column_order(rate))], axis=-1))
     ns = pts.shape[1]
-    es_n0 = threshold_db(fi["ldpc_k"] / fi["ldpc_n"], c) + rng.uniform(0, 1.5, nf)
+    if apsk:
+        base_db = APSK_QEF_DB[constellation, rate] + APSK_ROW_MARGIN_DB.get((constellation, rate, framesize), APSK_MARGIN_DB)
+    else:
+        base_db = threshold_db(fi["ldpc_k"] / fi["ldpc_n"], c)
+    es_n0 = base_db + rng.uniform(0, 1.5, nf)
     n0 = (10 ** (-es_n0 / 10)).astype(np.float32)
     kind = np.zeros(nf, int)  # 0 decodable, 1 noise, 2 edge / ties; in every whole group of 32
     whole = np.arange(nf - nf % G)
@@ -222,6 +255,11 @@ def chain_case(standard, framesize, rate, constellation, nf, seed):
     kind[whole[np.isin(whole % G, (7, 18, 30))]] = 2
     syms = np.empty((nf, ns), np.complex64)
     for f in range(nf):
+        if kind[f] == 2 and apsk:
+            k = int((kind[:f] == 2).sum())  # the N0 cycles over the edge frames
+            n0[f] = APSK_EDGE_N0[k % 3]
+            syms[f] = apsk_edge_frame(ns, float(n0[f]), pts[f], k, rng)
+            continue
         if kind[f] == 2:
             n0[f] = EDGE_N0[c][1 + f % 4]
             syms[f] = edge_frame(ns, float(n0[f]), c, rng)
@@ -231,7 +269,10 @@ def chain_case(standard, framesize, rate, constellation, nf, seed):
     order = T.column_order(rate) if c == 8 else 0
 
     def cpu(n0_used):
-        llr = T.oracle_demap(syms, n0_used, c, order)
+        if apsk:  # the float32 restatement test_apsk_gpu.py holds the kernel to, on the library's float table
+            llr = apsk_model.demap_f32(syms, n0_used, apsk_points(constellation, rate))[0]
+        else:
+            llr = T.oracle_demap(syms, n0_used, c, order)
         dec, ret = T.cpu_ldpc_decode_ragged(fi["table"], llr, G, CAP)
         msg, corr = ob.decode_bytes(T.pack_bits(dec, fi["bch_n"]))
         return msg, corr, ret
@@ -282,6 +323,20 @@ def test_chain_every_modcod(row, constellation, order, record_property):
     print(f"\n{row['rate']} {FS_NAME[row['framesize_id']]} {'QPSK' if constellation == capi.MOD_QPSK else '8PSK'} order {order}: {path} ({kname})")
 
 
+@pytest.mark.parametrize("constellation,rate,framesize", APSK_ROWS, ids=[f"{APSK_NAME[m]}-{r}-{FS_NAME[f]}" for m, r, f in APSK_ROWS])
+def test_chain_every_apsk_modcod(constellation, rate, framesize, record_property):
+    """Every legal (constellation, rate, frame size) of MODCODs 18-28, the same 35 frames as above: the chain runs the demapper as
+    its own launch into the LLR buffer, then the sweep kernel and BCH from the LDPC state -> messages, BCH corrections and LDPC
+    returns equal to the CPU chain (apsk_model.demap_f32 -> cpu_ldpc_decode_ragged -> OracleBch)."""
+    good = chain_case(capi.STANDARD_DVBS2, framesize, rate, constellation, 35, 1)[3]
+    assert good.sum() >= 26
+    kname = run_modcod(capi.STANDARD_DVBS2, framesize, rate, constellation)
+    record_property("demap_path", f"demapper launch: {kname}")
+    print(f"\n{rate} {FS_NAME[framesize]} {APSK_NAME[constellation]}: demapper launch ({kname})")
+    if framesize == capi.FECFRAME_NORMAL:
+        assert "_pr_" not in kname  # demapper launch + classic kernel
+
+
 def test_chain_medium_frames_refused():
     """Medium frames: the BCH stage cannot take them (k not a multiple of 8, as in the reference), so the chain is refused."""
     rows = json.load(open(os.path.join(T.ROOT, "tests", "golden", "fec_params.json")))["rows"]
@@ -317,21 +372,44 @@ def test_fused_demap_every_build(name, framesize, rate, constellation, variant, 
     print(f"\n{name} {variant}: {'demapper launch' if '_pr_' in kname else 'fused load'} ({kname})")
 
 
+# ------------------------------------------------------------------ every sweep-kernel build behind the demapper launch
+UNFUSED_CONFIGS = [
+    ("16apsk-2_3-normal", capi.FECFRAME_NORMAL, "C2_3", capi.MOD_16APSK),
+    ("32apsk-9_10-normal", capi.FECFRAME_NORMAL, "C9_10", capi.MOD_32APSK),  # degree class 32
+    ("16apsk-8_9-short", capi.FECFRAME_SHORT, "C8_9", capi.MOD_16APSK),      # <28, hz2>
+    ("32apsk-3_4-short", capi.FECFRAME_SHORT, "C3_4", capi.MOD_32APSK),
+]
+
+
+@pytest.mark.parametrize("variant", list(T.VARIANTS))
+@pytest.mark.parametrize("name,framesize,rate,constellation", UNFUSED_CONFIGS, ids=[c[0] for c in UNFUSED_CONFIGS])
+def test_unfused_demap_every_build(name, framesize, rate, constellation, variant, monkeypatch):
+    """Each sweep-kernel build behind the stand-alone APSK demapper (LLR buffer -> int8 load -> BCH from the LDPC state) gives the
+    CPU chain's bytes."""
+    for k, v in T.VARIANTS[variant].items():
+        monkeypatch.setenv(k, v)
+    kname = run_modcod(capi.STANDARD_DVBS2, framesize, rate, constellation, nf=35, seed=7)
+    print(f"\n{name} {variant}: demapper launch ({kname})")
+
+
 # ------------------------------------------------------------------ host entry, chunked, one N0 per frame
-@pytest.mark.parametrize("framesize,rate", [(capi.FECFRAME_NORMAL, "C1_2"), (capi.FECFRAME_SHORT, "C1_4")],
-                         ids=["qpsk-1_2-normal-fused", "qpsk-1_4-short-pr"])
-def test_host_entry_chunks_per_frame_n0(framesize, rate, monkeypatch):
+@pytest.mark.parametrize("framesize,rate,constellation", [(capi.FECFRAME_NORMAL, "C1_2", capi.MOD_QPSK), (capi.FECFRAME_SHORT, "C1_4", capi.MOD_QPSK),
+                                                          (capi.FECFRAME_SHORT, "C3_4", capi.MOD_16APSK)],
+                         ids=["qpsk-1_2-normal-fused", "qpsk-1_4-short-pr", "16apsk-3_4-short-unfused"])
+def test_host_entry_chunks_per_frame_n0(framesize, rate, constellation, monkeypatch):
     """dvbs2_chain_decode in chunks of 32 (six chunks) with a distinct N0 per frame, pageable and page-locked buffers: each chunk
-    must hand its own frames' N0 to the demapper (fused load or launch)."""
+    must hand its own frames' N0 to the demapper (fused load or launch; 16APSK: the launch writes the chunk's place in the LLR
+    buffer and the LDPC stage starts at that frame)."""
     import torch
     monkeypatch.setenv("DVBS2_HOST_CHUNK", "32")
     nf = 163
-    syms, n0, sent, good, (wmsg, wcorr, wret), _ = chain_case(capi.STANDARD_DVBS2, framesize, rate, capi.MOD_QPSK, nf, 11)
+    syms, n0, sent, good, (wmsg, wcorr, wret), _ = chain_case(capi.STANDARD_DVBS2, framesize, rate, constellation, nf, 11)
     assert (wcorr[good] >= 0).all() and np.array_equal(wmsg[good], sent[good])
     assert len(set(n0.tolist())) > nf * 3 // 4
-    chain = FecChain(framesize=framesize, rate=rate, constellation=capi.MOD_QPSK, group_size=G, max_frames=nf, max_trials=CAP)
+    chain = FecChain(framesize=framesize, rate=rate, constellation=constellation, group_size=G, max_frames=nf, max_trials=CAP)
     print(f"\n{rate} {FS_NAME[framesize]}: {chain.kernel_name}")
-    assert ("_pr_" in chain.kernel_name) == (framesize == capi.FECFRAME_SHORT)
+    if constellation == capi.MOD_QPSK:
+        assert ("_pr_" in chain.kernel_name) == (framesize == capi.FECFRAME_SHORT)
     msg, ret, corr = chain.work(syms, n0)
     assert ret.tolist() == list(wret) and corr.tolist() == wcorr.tolist()
     assert np.array_equal(msg, wmsg)

@@ -239,6 +239,34 @@ def test_mapper_every_form(name, constellation, row):
     assert np.array_equal((llr < 0).astype(np.uint8), cw) and (llr != 0).all()
 
 
+APSK_ROWS = [(mod, rate, fs) for mod, rates in ((capi.MOD_16APSK, apsk_model.GAMMA_16), (capi.MOD_32APSK, apsk_model.GAMMA_32))
+             for rate in rates for fs in ((capi.FECFRAME_NORMAL,) if rate == "C9_10" else (capi.FECFRAME_NORMAL, capi.FECFRAME_SHORT))]
+
+
+@pytest.mark.parametrize("constellation,rate,fs", APSK_ROWS, ids=["%dapsk-%s-%s" % (len(apsk_model.ring_angle(m)), r, "short" if f == capi.FECFRAME_SHORT else "normal")
+                                                                  for m, r, f in APSK_ROWS])
+def test_mapper_every_apsk_rate(constellation, rate, fs):
+    """Every legal (constellation, rate, frame size) of MODCODs 18-28, three frames: the symbols as uint32 views against the model's
+    mapper on the rate's own table (the ring ratios differ from rate to rate), and the demapper of the same rate at N0 = 0.01
+    spells every codeword bit."""
+    row = next(r for r in ROWS if r["standard_id"] == capi.STANDARD_DVBS2 and r["framesize_id"] == fs and r["rate"] == rate)
+    msg = _messages(3, row["bch_k"] // 8, 4100 + row["rate_id"])
+    enc = FecEncoder(capi.STANDARD_DVBS2, fs, rate, constellation, max_frames=3)
+    dm = Demapper(fs, rate, constellation, max_frames=3)
+    out = enc.work(msg)
+    assert (enc.n_syms, enc.n_mod) == (dm.n_syms, dm.n_mod) and enc.n_syms * enc.n_mod == row["ldpc_n"]
+    enc.close()
+    cw = np.unpackbits(out["ldpc_cw"], axis=1)
+    want = np.ascontiguousarray(apsk_model.map_bits(cw, apsk_points(constellation, rate))).astype(np.complex64)
+    syms = out["syms"]
+    assert syms.dtype == np.complex64 and syms.shape == want.shape
+    assert np.array_equal(syms.view(np.uint32), want.view(np.uint32))
+    assert np.allclose(want, apsk_model.map_bits(cw, apsk_model.points(constellation, rate)), rtol=0, atol=1e-6)  # the library's table is the rate's
+    llr = dm.work(syms, np.float32(0.01))
+    dm.close()
+    assert np.array_equal((llr < 0).astype(np.uint8), cw) and (llr != 0).all()
+
+
 # ------------------------------------------------------------------ 5. all outputs at once equal each alone; a null output is not written
 GUARD = 64
 
