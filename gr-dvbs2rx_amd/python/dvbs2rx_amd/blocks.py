@@ -16,7 +16,7 @@ from .capi import lib, check
 __all__ = ["get_fec_info", "rate_id", "LdpcDecoder", "BchDecoder", "Demapper", "FecChain", "BbDeheader", "ldpc_table_info", "ldpc_layer_info",
            "ldpc_table_names", "bb_descramble_sequence", "PlPayload",
            "pl_scrambling_rn", "HostBuffer", "PlFrontEnd", "plheader_symbols", "pls_parse", "apsk_points", "demap_table_check",
-           "PlSync", "plsync_taps", "plsync_thresholds", "PlCoarse", "plcoarse_weights", "Rotator",
+           "PlSync", "plsync_taps", "plsync_thresholds", "PlCoarse", "plcoarse_weights", "Agc", "agc_check", "Rotator",
            "SymbolSync", "symsync_loop_constants", "symsync_geometry", "symsync_taps", "FecEncoder", "enc_check",
            "PlFramer", "plframer_layout", "PulseShaper", "pulse_geometry", "pulse_taps", "pulse_scale_taps",
            "BbFramer", "bbheader_build", "crc8"]
@@ -600,6 +600,73 @@ class PlCoarse(_Handle):
         PlSync.work_device left for it."""
         check(lib.dvbs2_plcoarse_estimate_records_device(self._h, d_syms, int(n_syms), int(base_index), d_frames, int(n_frames),
                                                          d_coarse_foffset or None, d_coarse_corrected or None, d_new_est or None, stream or None))
+
+
+def agc_check(rate, reference, gain, max_gain):
+    """Raises Dvbs2Error (EINVAL, the text names the argument) for parameters an Agc refuses: a value that is not finite, a negative
+    rate, a negative max_gain. max_gain == 0 means no cap. Host only."""
+    check(lib.dvbs2_agc_check(float(rate), float(reference), float(gain), float(max_gain)))
+
+
+class Agc(_Handle):
+    """Automatic gain control, the stage in front of Rotator: GNU Radio's analog.agc_cc with max_gain behind an optional swap_iq
+    (reference apps/dvbs2-rx:873-887), on a batch of independent streams whose gains stay on the device between calls
+    (notes/agc.md). Per sample: y = x g; g += rate (reference - |y|); g capped at max_gain when max_gain > 0. All in float32."""
+    _destroy = lib.dvbs2_agc_destroy
+
+    TILE = capi.AGC_TILE
+
+    def __init__(self, rate=1e-5, reference=1.0, gain=1.0, max_gain=65536.0, max_streams=1, max_samples=1 << 20, device=0):
+        check(lib.dvbs2_agc_create(C.byref(self._h), float(rate), float(reference), float(gain), float(max_gain), int(max_streams),
+                                   int(max_samples), device))
+        self.max_streams, self.max_samples = max_streams, max_samples
+
+    def params(self):
+        """dict(rate, reference, max_gain as float32, swap_iq, tile)."""
+        f, v = [C.c_float() for _ in range(3)], [C.c_int() for _ in range(2)]
+        check(lib.dvbs2_agc_params(self._h, *[C.byref(x) for x in f], *[C.byref(x) for x in v]))
+        return dict(rate=np.float32(f[0].value), reference=np.float32(f[1].value), max_gain=np.float32(f[2].value), swap_iq=bool(v[0].value),
+                    tile=v[1].value)
+
+    def reset(self):
+        """Every stream's gain back to the gain of the constructor; waits for the device."""
+        check(lib.dvbs2_agc_reset(self._h))
+
+    def set_params(self, rate, reference, max_gain):
+        """For the calls made after it."""
+        check(lib.dvbs2_agc_set_params(self._h, float(rate), float(reference), float(max_gain)))
+
+    def set_swap_iq(self, enable):
+        check(lib.dvbs2_agc_set_swap_iq(self._h, int(bool(enable))))
+
+    def set_gain(self, stream_index, gain):
+        """One stream's gain (stream_index -1: every stream's); waits for the device."""
+        check(lib.dvbs2_agc_set_gain(self._h, int(stream_index), float(gain)))
+
+    def state(self, n_streams=None):
+        """The gains of streams 0 .. n_streams - 1 (default: all) as float32; waits for the device."""
+        g = np.zeros(self.max_streams if n_streams is None else int(n_streams), np.float32)
+        check(lib.dvbs2_agc_state(self._h, g.ctypes.data if g.size else None, int(g.size)))
+        return g
+
+    def work(self, samples):
+        """HOST buffer of complex64 samples of stream 0. Returns (out complex64, gain float32: what multiplied each sample)."""
+        x = np.asarray(samples)
+        if x.dtype != np.complex64:
+            raise TypeError(f"samples must be complex64, not {x.dtype}")
+        if x.ndim != 1 or not x.flags.c_contiguous:
+            raise ValueError("samples must be a C-contiguous vector")
+        out, gain = np.empty_like(x), np.empty(x.size, np.float32)
+        check(lib.dvbs2_agc_work(self._h, x.ctypes.data if x.size else None, int(x.size), out.ctypes.data if x.size else None,
+                                 gain.ctypes.data if x.size else None))
+        return out, gain
+
+    def work_device(self, d_in, in_stride, n_samples, n_streams, d_out, out_stride, d_gain=0, gain_stride=0, stream=0):
+        """DEVICE addresses (samples 8-byte aligned), asynchronous on `stream`: stream s reads n_samples complex64 samples at
+        d_in + 8 * s * in_stride, writes as many at d_out + 8 * s * out_stride and, when d_gain is given, n_samples float32 gains at
+        d_gain + 4 * s * gain_stride. d_out == d_in with equal strides works in place. One call in flight per handle."""
+        check(lib.dvbs2_agc_work_device(self._h, d_in or None, int(in_stride), int(n_samples), int(n_streams), d_out or None, int(out_stride),
+                                        d_gain or None, int(gain_stride), stream or None))
 
 
 class Rotator(_Handle):

@@ -26,6 +26,7 @@ OM_CODEWORD, OM_MESSAGE = 0, 1
 MOD_QPSK, MOD_8PSK, MOD_16APSK, MOD_32APSK = 0, 4, 6, 8
 ENC_NO_MAPPER = -1
 PULSE_TILE = 512  # DVBS2_PULSE_TILE: symbols per workgroup of the pulse shaper's kernel
+AGC_TILE = 64  # DVBS2_AGC_TILE: samples per stream and tile of the AGC's kernel
 
 
 class FecInfo(C.Structure):
@@ -165,6 +166,17 @@ SYMBOLS = {
     "dvbs2_plcoarse_estimate_records_device": (_i, [_vp, _vp, _i, C.c_int64, _vp, _i, _vp, _vp, _vp, _vp]),
     "dvbs2_plcoarse_estimate": (_i, [_vp, _vp, C.c_int64, _vp, _i, _vp, _vp, _vp]),
     "dvbs2_plcoarse_weights": (_i, [_i, _vp]),
+    "dvbs2_agc_check": (_i, [_f, _f, _f, _f]),
+    "dvbs2_agc_create": (_i, [C.POINTER(_vp), _f, _f, _f, _f, _i, _i, _i]),
+    "dvbs2_agc_destroy": (None, [_vp]),
+    "dvbs2_agc_reset": (_i, [_vp]),
+    "dvbs2_agc_set_params": (_i, [_vp, _f, _f, _f]),
+    "dvbs2_agc_set_swap_iq": (_i, [_vp, _i]),
+    "dvbs2_agc_set_gain": (_i, [_vp, _i, _f]),
+    "dvbs2_agc_params": (_i, [_vp, _fp, _fp, _fp, _ip, _ip]),
+    "dvbs2_agc_state": (_i, [_vp, _vp, _i]),
+    "dvbs2_agc_work_device": (_i, [_vp, _vp, C.c_int64, _i, _i, _vp, C.c_int64, _vp, C.c_int64, _vp]),
+    "dvbs2_agc_work": (_i, [_vp, _vp, _i, _vp, _vp]),
     "dvbs2_rotator_create": (_i, [C.POINTER(_vp), C.c_double, _i]),
     "dvbs2_rotator_destroy": (None, [_vp]),
     "dvbs2_rotator_reset": (_i, [_vp]),

@@ -641,6 +641,55 @@ int dvbs2_plcoarse_estimate(dvbs2_plcoarse_t* h, const float* plframes, int64_t 
                             float* coarse_foffset, int32_t* coarse_corrected, int32_t* new_est);
 int dvbs2_plcoarse_weights(int full, float* w);
 
+/* ---- automatic gain control: the first stage of the receive flowgraph, in front of the rotator. There (apps/dvbs2-rx:873-887) it is GNU
+ * Radio's analog.agc_cc(rate, reference, gain) with set_max_gain(65536) behind an optional blocks.swap_iq; the defaults are rate 1e-5,
+ * reference 1, gain 1 (:1257-1269). The semantics are those of gr::analog::kernel::agc_cc::scale with max_gain, but GNU Radio is not in
+ * the reference tree: the stage is UNPINNED against GNU Radio. What is defined, and tested bit for bit against a float32 restatement
+ * (tests/agc_model.py), is the arithmetic. Per stream, with float32 state g and float32 parameters rate, reference, max_gain, for every
+ * input sample x = (xr, xi) in order:
+ *   yr = xr * g ; yi = xi * g                    (the output sample)
+ *   m  = sqrt(yr*yr + yi*yi)                     two products, one addition, a correctly rounded float32 square root
+ *   g  = g + rate * (reference - m)              subtraction, product, addition
+ *   if (max_gain > 0 && g > max_gain) g = max_gain
+ * Every operation is a single IEEE float32 operation in this order, no fused multiply-add, denormals kept. There is no lower clamp and no
+ * special case for values that are not finite: a NaN or an overflow propagates exactly as IEEE arithmetic says, as in GNU Radio, and
+ * dvbs2_agc_reset is the way out of a gain that is not finite. With swap_iq set, (xr, xi) is read as (xi, xr) before anything else.
+ * A handle works on a batch of independent streams; each stream's gain stays on the device between calls; all streams share rate,
+ * reference, max_gain and swap_iq. Stream s of a call reads n_samples samples at d_in + s in_stride and writes exactly n_samples at
+ * d_out + s out_stride and -- d_gain is nullable -- one float per sample, the gain that multiplied it (g before its update), at
+ * d_gain + s gain_stride. However a stream is cut into calls, the bits are those of one call. Sample buffers are interleaved (re, im)
+ * floats, 8-byte aligned (d_gain: 4-byte); strides count complex elements (floats for d_gain) and matter only when n_streams > 1. Rows
+ * that all start 16-byte aligned get 16-byte loads and stores, any other an 8-byte path with the same bits. d_out == d_in with equal
+ * strides is allowed and gives the bits of an out-of-place call; any other overlap is not allowed and not detected. One launch per
+ * call, no allocation, no host synchronisation. ONE CALL IN FLIGHT PER HANDLE, as for dvbs2_pulse_*: a call reads the gains and writes
+ * them back. The kernel gives every stream a lane and walks tiles of DVBS2_AGC_TILE samples per stream (notes/agc.md).
+ * dvbs2_agc_check (host only) refuses with DVBS2_EINVAL, in a text that names the argument, a rate, reference, gain or max_gain that is
+ * not finite, a negative rate and a negative max_gain; max_gain == 0 means no cap, as in GNU Radio. dvbs2_agc_create applies it and
+ * refuses max_streams outside 1..65535 and max_samples outside 1..2^30; dvbs2_agc_set_params applies it and holds for the calls made
+ * after it, as does dvbs2_agc_set_swap_iq. dvbs2_agc_reset puts every stream's gain back to the gain of create, dvbs2_agc_set_gain sets
+ * one stream's (stream_index -1: every stream's) to a finite value; both wait for the device. dvbs2_agc_state waits for the device and
+ * returns the gains of streams 0 .. n_streams - 1. The work entries refuse with DVBS2_ESIZE n_samples > max_samples and n_streams >
+ * max_streams, and with DVBS2_EINVAL and a text that names the argument negative counts, a null in or out with n_samples > 0, a
+ * misaligned buffer and, with n_streams > 1, a stride below n_samples. n_samples == 0 is a successful call that does nothing. A refused
+ * call changes no state and writes nothing. ---- */
+typedef struct dvbs2_agc dvbs2_agc_t;
+#define DVBS2_AGC_TILE 64
+int dvbs2_agc_check(float rate, float reference, float gain, float max_gain);
+int dvbs2_agc_create(dvbs2_agc_t** h, float rate, float reference, float gain, float max_gain, int max_streams, int max_samples, int device);
+void dvbs2_agc_destroy(dvbs2_agc_t* h);
+int dvbs2_agc_reset(dvbs2_agc_t* h);
+int dvbs2_agc_set_params(dvbs2_agc_t* h, float rate, float reference, float max_gain);
+int dvbs2_agc_set_swap_iq(dvbs2_agc_t* h, int enable);
+int dvbs2_agc_set_gain(dvbs2_agc_t* h, int stream_index, float gain);
+/* each nullable; tile = DVBS2_AGC_TILE */
+int dvbs2_agc_params(const dvbs2_agc_t* h, float* rate, float* reference, float* max_gain, int* swap_iq, int* tile);
+int dvbs2_agc_state(dvbs2_agc_t* h, float* gains, int n_streams);
+/* DEVICE pointers, asynchronous on `stream` */
+int dvbs2_agc_work_device(dvbs2_agc_t* h, const float* d_in, int64_t in_stride, int n_samples, int n_streams, float* d_out, int64_t out_stride,
+                          float* d_gain, int64_t gain_stride, void* stream);
+/* host pointers, synchronous: stream 0 of the handle, staged through buffers of the handle; gain nullable */
+int dvbs2_agc_work(dvbs2_agc_t* h, const float* in, int n_samples, float* out, float* gain);
+
 /* ---- rotator: rotator_cc::work (reference lib/rotator_cc_impl.cc:36-128). out[n] = in[n] e^{j phi[n]}, phi[n+1] = phi[n] + inc[n],
  * phi = 0 at the first sample after create / reset. dvbs2_rotator_set_phase_inc takes effect at once; dvbs2_rotator_schedule queues
  * an update for an ABSOLUTE sample index (counted from create / reset), across which the phase stays continuous. An update whose
