@@ -253,35 +253,46 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
     __syncthreads();
     TSTAMP(tB); tm_load = tB - tA;
 
-    // Messages go through a buffer descriptor based at this frame's records: the per-lane offset (row * 4, plus the
-    // word offset) is loop-invariant and the per-layer offset is a scalar operand, so a message access costs no
+    // Messages go through a buffer descriptor based at this frame's records: the per-lane offset (the row's, rm = row * kMsgRowBytes) is
+    // loop-invariant and the per-layer offset (plus the word's) is a scalar operand, so a message access costs no
     // VALU address arithmetic (a flat 64-bit address costs two to four VALU instructions per access).
+    // Layout: ldpc_layout.h (msg_row_bytes). With two words per check a row's record is loaded and stored with ONE 8-byte access.
     uint32_t* msg_base = msgs + (size_t)(have_frame ? f : 0) * q * MW * kMsgStride;
     const __amdgpu_buffer_rsrc_t mrs = __builtin_amdgcn_make_buffer_rsrc(msg_base, 0, q * MW * kMsgStride * 4, 0x00020000);
     constexpr int kLayerBytes = MW * kMsgStride * 4;
-#define MSG_LD(soff, w, r4) __builtin_amdgcn_raw_buffer_load_b32(mrs, (r4), (soff) + (w) * (kMsgStride * 4), 0)
-#define MSG_ST(v, soff, w, r4) __builtin_amdgcn_raw_buffer_store_b32((v), mrs, (r4), (soff) + (w) * (kMsgStride * 4), 0)
-    auto msg_load = [&](uint32_t* dst, int soff, int r4) {
+    constexpr int kMsgRowBytes = msg_row_bytes(MW), kMsgWordStep = msg_word_step(MW);
+#define MSG_LD(soff, w, rm) __builtin_amdgcn_raw_buffer_load_b32(mrs, (rm), (soff) + (w) * kMsgWordStep, 0)
+#define MSG_ST(v, soff, w, rm) __builtin_amdgcn_raw_buffer_store_b32((v), mrs, (rm), (soff) + (w) * kMsgWordStep, 0)
+    auto msg_load = [&](uint32_t* dst, int soff, int rm) {
+        if constexpr (MW == 2) {
+            const v2u32 v = __builtin_amdgcn_raw_buffer_load_b64(mrs, rm, soff, 0);
+            dst[0] = v.x; dst[1] = v.y;
+        } else {
 #pragma unroll
-        for (int w = 0; w < MW; w++) dst[w] = MSG_LD(soff, w, r4);
+            for (int w = 0; w < MW; w++) dst[w] = MSG_LD(soff, w, rm);
+        }
     };
-    auto msg_store = [&](const uint32_t* src, int soff, int r4) {
+    auto msg_store = [&](const uint32_t* src, int soff, int rm) {
+        if constexpr (MW == 2) {
+            __builtin_amdgcn_raw_buffer_store_b64((v2u32){ src[0], src[1] }, mrs, rm, soff, 0);
+        } else {
 #pragma unroll
-        for (int w = 0; w < MW; w++) MSG_ST(src[w], soff, w, r4);
+            for (int w = 0; w < MW; w++) MSG_ST(src[w], soff, w, rm);
+        }
     };
     // The messages of the layer at hand (mw <- pre) and the load of the next layer's (byte offset `next`) into pre. In a frame's first sweep
     // (zero) nothing is loaded and mw is the zero message of the layer's format. The first-sweep arm is a real branch (the empty asm
     // statement cannot be speculated, so the arm is not turned into selects), and the load is unconditional in every other sweep -- the
     // last layer fetches layer 0's record again, whose store is 89 layers and as many vmcnt(0) waits old, and drops it --: with a load
     // that may not happen the old pre had to survive it, which cost a second 64-bit copy per layer.
-    auto take_msgs = [&](uint32_t* mw, uint32_t* pre, bool zero, uint32_t zero_word, int next, int r4) {
+    auto take_msgs = [&](uint32_t* mw, uint32_t* pre, bool zero, uint32_t zero_word, int next, int rm) {
 #pragma unroll
         for (int w = 0; w < MW; w++) mw[w] = pre[w];
         if (zero) {
             asm volatile("" ::: "memory");
 #pragma unroll
             for (int w = 0; w < MW; w++) mw[w] = zero_word;
-        } else msg_load(pre, next, r4);
+        } else msg_load(pre, next, rm);
     };
     // bnl = 0 before the first update (layered_decoder.hh:27-31,149): a frame's first sweep (it == 0, in the first pass or
     // when a frame that stopped at once is resumed) takes offset-binary zero bytes instead of loading them -- no memset
@@ -423,7 +434,7 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
         // keeps the whole sweep free of per-lane predicates: `work` is wave-uniform.
         const bool work = __builtin_amdgcn_readfirstlane(finished ? 0 : 1) != 0; // uniform over the wave, and the compiler knows it
         const int row = tid < kM ? tid : kM - 1;
-        const int row4 = row * 4;
+        const int rowm = row * kMsgRowBytes; // this row's byte offset in a layer's message records
         // uniform over the half, and the compiler knows it: the zero messages of a frame's first sweep are a scalar branch per layer
         // (take_msgs), not a compare mask and one v_cndmask per message word in every layer of every sweep
         const bool zero_msgs = __builtin_amdgcn_readfirstlane(it) == 0;
@@ -434,7 +445,7 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
         if (work) {
 #pragma unroll
             for (int w = 0; w < MW; w++) {
-                pre[w] = zero_msgs ? 0x80808080u : MSG_LD(0, w, row4);
+                pre[w] = zero_msgs ? 0x80808080u : MSG_LD(0, w, rowm);
             }
         }
         // Layer records are double-buffered in SGPRs: the scalar loads of layer i+1 are issued at the top of layer i
@@ -493,8 +504,19 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
                         const uint32_t* nrec = wr + (size_t)(i + 1) * RSW; // the record the next trip fetches ahead: a running pointer
                         int sa = i * kLayerBytes, sb;                       // scalar byte offset of a trip's messages
                         const int s_last = (q - 1) * kLayerBytes;           // the last layer's: never reached inside a run
+                        const int rowb360 = row + lb + kM;                  // the base of a fix slot's lanes below the wrap point (check_node_v2, RUN)
+                        // Parity carry (check_node_v2, RUN): the first trip's barrier is taken here, then its previous-parity byte is read into the
+                        // carry (a one-wave walk layer in front of the run writes that byte from another wave: not before the barrier); behind the
+                        // run's last trip the own-parity byte that trip kept back goes to LDS, so that every path outside the run finds LDS as ever.
+                        // (Timing builds: this barrier lies in front of the first trip's TSTAMP(tA), so tm_bar and the per-layer sums leave out the barrier of a run's first layer.)
+                        if ((ha & (1u << kRecSyncShift)) != 0u) { lds_barrier(); ha &= ~(1u << kRecSyncShift); }
+                        uint32_t carry = (uint32_t)lds_rd(row + lb + (int)ea[D - 1]) << ((D & 1) ? 24 : 8);
+                        auto flush_parity = [&](const uint32_t* E /*the record of the run's last trip*/) {
+                            const int a = row + lb + (int)E[D - 2];
+                            if constexpr ((D & 1) != 0) lds_wr_hi(a, carry >> 8); else lds_wr(a, (int)(carry >> 8));
+                        };
 // one trip: the layer of record (H, E) with the messages P at offset S; the next layer's record goes to (NH, NE), its messages to NP, its offset to NS
-// (message word w is addressed as (row4 + w * stride) + S: the per-lane part is loop invariant, so the trip has no scalar add per load and store)
+// (a row's messages are addressed as rowm + S: the per-lane part is loop invariant, so the trip has no scalar add per load and store)
 #define DVBS2_RUN_TRIP(H, E, P, S, NH, NE, NP, NS) { \
                             TSTAMP(tA); \
                             NS = S + kLayerBytes; \
@@ -505,10 +527,10 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
                             nrec += RSW; \
                             TSTAMP(tB); tm_bar += tB - tA; \
                             uint32_t nm[MW]; \
-                            _Pragma("unroll") for (int w = 0; w < MW; w++) NP[w] = __builtin_amdgcn_raw_buffer_load_b32(mrs, row4 + w * (kMsgStride * 4), NS, 0); \
-                            check_node_v2<D, DMAX, TC>(E, row + lb, P, nm, 0); \
+                            msg_load(NP, NS, rowm); \
+                            check_node_v2<D, DMAX, TC, true>(E, row + lb, P, nm, 0, rowb360, &carry); \
                             DVBS2_WAIT_VM0(); \
-                            _Pragma("unroll") for (int w = 0; w < MW; w++) __builtin_amdgcn_raw_buffer_store_b32(nm[w], mrs, row4 + w * (kMsgStride * 4), S, 0); \
+                            msg_store(nm, S, rowm); \
                             TSTAMP(tC); tm_body += tC - tB; \
                             if (TIMING && tdbg && f == 0 && tid == 0) tdbg[(size_t)n_frames * 48 + S / kLayerBytes] += tC - tA; }
                         // two tests, two branches that are not taken inside a run (the empty statement keeps them from being merged into flag arithmetic)
@@ -520,6 +542,7 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
                         for (;;) {
                             DVBS2_RUN_TRIP(ha, ea, pre, sa, hb, eb, pb, sb)
                             if (run_ends(hb, sb)) { // the run ends behind an odd trip: what was fetched ahead moves to where the layer loop expects it
+                                flush_parity(ea);
                                 nhdr = hb;
 #pragma unroll
                                 for (int k = 0; k < 2 * DMAX; k++) nent[k] = eb[k];
@@ -530,6 +553,7 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
                             }
                             DVBS2_RUN_TRIP(hb, eb, pb, sb, ha, ea, pre, sa)
                             if (run_ends(ha, sa)) {
+                                flush_parity(eb);
                                 nhdr = ha;
 #pragma unroll
                                 for (int k = 0; k < 2 * DMAX; k++) nent[k] = ea[k];
@@ -583,11 +607,11 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
                     const bool v2 = V2 && ((hdr >> 13) & 1u);
                     // v2: this wave's record is in the packed node's format (two's complement messages)
                     uint32_t mw[MW], nm[MW];
-                    take_msgs(mw, pre, zero_msgs, v2 ? 0u : 0x80808080u, inext * kLayerBytes, row4);
+                    take_msgs(mw, pre, zero_msgs, v2 ? 0u : 0x80808080u, inext * kLayerBytes, rowm);
                     // (kRun: a packed record of a working wave gets here in a frame's first sweep and at the table's last layer only -- the run loop took the others)
                     if constexpr (V2) { if (v2) { DVBS2_V2_SWITCH } else DVBS2_DEG_SWITCH } else DVBS2_DEG_SWITCH
                     DVBS2_WAIT_VM0();
-                    msg_store(nm, mso, row4);
+                    msg_store(nm, mso, rowm);
                 }
                 TSTAMP(tC); tm_body += tC - tB;
                 if (TIMING && tdbg && f == 0 && tid == 0) tdbg[(size_t)n_frames * 48 + i] += tC - tA; // per-layer cycles of frame 0, wave 0 (incl. its barrier)
@@ -600,7 +624,7 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
                     uint32_t mw[MW], nm[MW];
 #pragma unroll
                     for (int w = 0; w < MW; w++) mw[w] = (work && !zero_msgs) ? pre[w] : (hv2 ? 0u : 0x80808080u);
-                    if (work && i + 1 < q && !zero_msgs) msg_load(pre, mso + kLayerBytes, row4);
+                    if (work && i + 1 < q && !zero_msgs) msg_load(pre, mso + kLayerBytes, rowm);
                     // hvp: the generic hazard node with the packed first / last phase (header bit 14 of this wave's record; every wave of the
                     // layer runs the same ordered phase, whichever form its own record has)
                     const bool hvp = V2 && v2p_class(DMAX) && ((hdr >> 14) & 1u);
@@ -612,7 +636,7 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
                     } else if constexpr (V2 && v2p_class(DMAX)) { if (hvp) { DVBS2_HAZP_SWITCH } else DVBS2_HAZ_SWITCH }
                     else DVBS2_HAZ_SWITCH
                     DVBS2_WAIT_VM0(); // (on every path, so that nothing is pending behind it whatever the branch)
-                    if (work) msg_store(nm, mso, row4);
+                    if (work) msg_store(nm, mso, rowm);
                 } else {
                     // too many hazard entries: the first wave of the half walks the 360 checks alone in ascending
                     // chunks of min(B_i, 64) (LDS operations of one wave execute in order: no barrier between chunks)
@@ -623,15 +647,15 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
                             if (lane < chunk && jj < kM) {
                                 uint32_t mw[MW], nm[MW];
 #pragma unroll
-                                for (int w = 0; w < MW; w++) mw[w] = zero_msgs ? 0x80808080u : MSG_LD(mso, w, jj * 4);
+                                for (int w = 0; w < MW; w++) mw[w] = zero_msgs ? 0x80808080u : MSG_LD(mso, w, jj * kMsgRowBytes);
                                 DVBS2_DEG_SWITCH
 #pragma unroll
-                                for (int w = 0; w < MW; w++) MSG_ST(nm[w], mso, w, jj * 4);
+                                for (int w = 0; w < MW; w++) MSG_ST(nm[w], mso, w, jj * kMsgRowBytes);
                             }
                         }
                     }
                     lds_barrier();
-                    if (work && i + 1 < q && !zero_msgs) msg_load(pre, mso + kLayerBytes, row4);
+                    if (work && i + 1 < q && !zero_msgs) msg_load(pre, mso + kLayerBytes, rowm);
                     DVBS2_WAIT_VM0(); // (rare path; keeps "nothing pending at the end of a layer" true on EVERY path, see DVBS2_WAIT_VM0)
                 }
                 TSTAMP(tC); tm_conf += tC - tB;

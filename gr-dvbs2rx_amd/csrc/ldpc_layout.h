@@ -9,6 +9,12 @@ namespace dvbs2 {
 
 constexpr int kM = 360;
 constexpr int kMsgStride = 384;     // message slots per (layer, word)
+// Message records of the classic sweep kernel, per frame: [layer][word][384 rows] dwords -- a wave's access to one word is contiguous --,
+// except with TWO words per check (the degree class 8): [layer][384 rows][2 words], one 8-byte record per row, loaded and stored with one
+// dwordx2 access. Word w of row r of a layer lies at byte  r * msg_row_bytes(mw) + w * msg_word_step(mw)  behind the layer's offset
+// (layer * mw * kMsgStride * 4 in both forms: the allocation is the same).
+constexpr int msg_row_bytes(int mw) { return mw == 2 ? 8 : 4; }
+constexpr int msg_word_step(int mw) { return mw == 2 ? 4 : kMsgStride * 4; }
 constexpr int kSvWords = 14;        // sign-vector dwords per 360-bit group (360 bits + 32-bit wrap extension, even for b64 stores)
 
 // Layer record (uniform data, read with scalar loads): RS = 2*DMAX + 4 dwords.

@@ -99,8 +99,11 @@ __device__ __forceinline__ void two_smallest_pk(const v2s16* a, v2s16& m0, v2s16
 // sg the sign mask of inp, and with S all ones or zero per half  (other ^ S) - S  ==  (T ^ S) - (c ^ S)  for other = T - c: the two
 // xors are one v_bitop3 each and the negation costs no packed instruction of its own. clamp(a, B0, B1) is min(a, B1): a >= min0 >= B0.
 // nl: the new LLR bytes of the pair in bits 0-7 and 16-23 (ds_write_b8 / ds_write_b8_d16_hi); R: the stored messages (R7) << 8.
+// sum_out: where the caller wants the new LLRs of the pair as they go to LDS, still << 8 in the halves (the parity carry of the run loop).
+// (Taking the sign mask once per pair in the caller's input phase, with |d| = sat((d ^ sg) - sg), was built for the run-loop form and
+// measured 0.24 % SLOWER on B4 than this form: notes/r11_parity_carry.md.)
 template <bool TC>
-__device__ __forceinline__ void pair_out(v2s16 d, v2s16 a, v2s16 B1p, uint32_t Tt, uint32_t tm, uint32_t& nl, uint32_t& R)
+__device__ __forceinline__ void pair_out(v2s16 d, v2s16 a, v2s16 B1p, uint32_t Tt, uint32_t tm, uint32_t& nl, uint32_t& R, uint32_t* sum_out = nullptr)
 {
     const v2s16 c = __builtin_elementwise_min(a, B1p);
     const uint32_t sg = as_u32(d >> (v2s16){ 15, 15 });
@@ -111,13 +114,28 @@ __device__ __forceinline__ void pair_out(v2s16 d, v2s16 a, v2s16 B1p, uint32_t T
     // it folds a visible one into the >> 16 of the second byte and stores that with a plain ds_write_b8 behind a second shift.)
     const uint32_t sum = as_u32(__builtin_elementwise_add_sat(d, out)) ^ kObPair<TC>;
     asm("v_lshrrev_b32 %0, 8, %1" : "=v"(nl) : "v"(sum));
+    if (sum_out) *sum_out = sum;
     // R7
     R = as_u32(__builtin_elementwise_min(__builtin_elementwise_max(out, (v2s16){ -32 * 256, -32 * 256 }), (v2s16){ 31 * 256, 31 * 256 }));
 }
 
-template <int DEG, int DMAX, bool TC, class Prefetch>
+// RUN: the form for trips of the run loop (kRun in ldpc_kernel.hpp), same values, fewer issue slots and no scalar bookkeeping in the address phase:
+//   * the wrap fix is a SELECT of the base instead of an add under EXEC: jjb360 = jjb + 360 is loop invariant, a fix slot takes one
+//     v_cndmask_b32 on the record's lane mask and then the one add of every other entry (per slot: 3 scalar instructions fewer, and
+//     no asm statement that fences the scheduler);
+//   * PARITY CARRY. A parity bit lies in two checks, c and c + 1: row j of layer i owns it (slot DEG - 2) and row j of layer i + 1 meets it
+//     again as its previous parity (slot DEG - 1), so the same THREAD writes the byte in one trip and reads it back in the next, and
+//     nobody else touches it in between. Inside a run it stays in a register: `carry` holds the new LLRs of the pair with the own-parity
+//     entry as pair_out adds them up (LDS form, << 8 in the halves; the entry is byte 3 of it for an odd degree, byte 1 for an even one).
+//     The node takes its previous-parity input out of it -- with the v_perm that assembles the pair anyway, which also drops the low
+//     byte a saturated input leaves in a half --, neither reads that byte from LDS nor writes its own parity byte, and leaves the new
+//     carry. The run loop loads the carry in front of a run's first trip and writes the last own-parity byte behind its last one
+//     (ldpc_kernel.hpp); the planner vouches, for every record a run can take, that own parity lies 360 bytes behind previous parity, that
+//     neither is a fix slot, and that the two slots of consecutive records of a run name the same byte (ldpc_plan.cpp, parity_chain_ok).
+template <int DEG, int DMAX, bool TC, bool RUN = false, class Prefetch>
 __device__ __forceinline__ void check_node_v2(const uint32_t* ent /*record words 4..: S0w[DMAX], then (mask lo, mask hi)[NFIX]*/,
-                                              int jjb, const uint32_t* mw, uint32_t* nm, Prefetch prefetch_next_record)
+                                              int jjb, const uint32_t* mw, uint32_t* nm, Prefetch prefetch_next_record, int jjb360 = 0 /*RUN: jjb + 360*/,
+                                              uint32_t* carry = nullptr /*RUN*/)
 {
     constexpr int NP = (DEG + 1) / 2;      // pairs
     constexpr int NFIX = v2_nfix(DMAX) < DEG - 2 ? v2_nfix(DMAX) : DEG - 2; // parity entries never wrap
@@ -125,6 +143,13 @@ __device__ __forceinline__ void check_node_v2(const uint32_t* ent /*record words
     __builtin_amdgcn_s_setprio(0);
     int ad[DEG];
     auto addresses = [&]() {
+        if constexpr (RUN) {
+#pragma unroll
+            for (int k = 0; k < DEG; k++)
+                if (k != DEG - 2) ad[k] = (k < NFIX ? wrap_base(jjb, jjb360, ent[DMAX + 2 * k], ent[DMAX + 2 * k + 1]) : jjb) + (int)ent[k];
+            ad[DEG - 2] = 0; // the own-parity byte is read 360 bytes behind the previous-parity one (parity_chain_ok) and not written: no address of its own
+            return;
+        }
 #pragma unroll
         for (int k = 0; k < DEG; k++) ad[k] = jjb + (int)ent[k];
 #pragma unroll
@@ -133,14 +158,18 @@ __device__ __forceinline__ void check_node_v2(const uint32_t* ent /*record words
     addresses();
     int Lb[DEG];
 #pragma unroll
-    for (int k = 0; k < DEG; k++) Lb[k] = lds_rd(ad[k]);
+    for (int k = 0; k < DEG - (RUN ? 2 : 0); k++) Lb[k] = lds_rd(ad[k]);
+    if constexpr (RUN) { Lb[DEG - 2] = lds_rd_at<kM>(ad[DEG - 1]); Lb[DEG - 1] = 0; } // (the previous-parity byte comes out of the carry)
     v2s16 d[NP], a[NP];
     uint32_t sx = 0;
 #pragma unroll
     for (int j = 0; j < NP; j++) {
         const uint32_t M = msg_pair16(mw, j); // messages of pair j: << 8 in both halves
         const uint32_t hi = (ODD && j == NP - 1) ? (TC ? 0x00u : 0x80u) : (uint32_t)Lb[2 * j + 1];
-        const uint32_t L = __builtin_amdgcn_perm(hi, (uint32_t)Lb[2 * j], 0x040c000cu) ^ kObPair<TC>; // -> two's complement << 8
+        // (RUN, last pair: previous parity is its low half for an odd degree -- byte 3 of the carry -- and its high half for an even one -- byte 1)
+        const uint32_t Lp = !(RUN && j == NP - 1) ? __builtin_amdgcn_perm(hi, (uint32_t)Lb[2 * j], 0x040c000cu)
+                            : ODD ? __builtin_amdgcn_perm(hi, *carry, 0x040c030cu) : __builtin_amdgcn_perm(*carry, (uint32_t)Lb[2 * j], 0x050c000cu);
+        const uint32_t L = Lp ^ kObPair<TC>; // -> two's complement << 8
         d[j] = __builtin_elementwise_sub_sat(as_v2s(L), as_v2s(M));           // R1 (a half that saturates upwards reads 0x7fff)
         sx ^= as_u32(d[j]);                                                   // R4: bits 15 and 31 collect the signs
         a[j] = __builtin_elementwise_max(d[j], __builtin_elementwise_sub_sat(as_v2s(0u), d[j])); // |inp| << 8 (0x7fff for -128 and for saturated halves)
@@ -167,9 +196,9 @@ __device__ __forceinline__ void check_node_v2(const uint32_t* ent /*record words
 #pragma unroll
     for (int j = 0; j < NP; j++) {
         uint32_t nl;
-        pair_out<TC>(d[j], a[j], B1p, Tt, tm, nl, R[j]);
-        lds_wr(ad[2 * j], (int)nl);
-        if (!(ODD && j == NP - 1)) lds_wr_hi(ad[2 * j + 1], nl);
+        pair_out<TC>(d[j], a[j], B1p, Tt, tm, nl, R[j], RUN && j == (DEG - 2) / 2 ? carry : nullptr);
+        if (!(RUN && 2 * j == DEG - 2)) lds_wr(ad[2 * j], (int)nl); // (RUN: the own-parity byte, slot DEG - 2, stays in the carry)
+        if (!(ODD && j == NP - 1) && !(RUN && 2 * j + 1 == DEG - 2)) lds_wr_hi(ad[2 * j + 1], nl);
     }
     __builtin_amdgcn_s_setprio(3);
     msg_pack16_hb<NP, ODD>(R, nm);

@@ -309,6 +309,31 @@ bool has_unpacked_record(const LdpcSchedule& s, const std::vector<uint32_t>& wr,
         }
     return false;
 }
+
+// What the parity carry of the run loop relies on (check_node_v2 with RUN, ldpc_node_packed.hpp; the degree classes up to 8). The run
+// loop takes EVERY packed regular record of a layer 0 < i < q - 1 (ldpc_kernel.hpp, kRun; a run may be that one trip), so each of them
+// must have its own-parity slot 360 bytes behind its previous-parity slot and neither of the two a fix slot (a parity entry has no
+// rotation): the trip reads own parity at offset 360 of the previous-parity address and writes it back through the own-parity slot.
+// Where the next layer's record of the wave continues the run (same block, format and degree, and itself such a record), its
+// previous-parity slot must name the byte of this record's own-parity slot: it takes that byte from the carry. The test looks at the
+// records that were actually BUILT. False: *layer, *wave name the record (of a pair: the first) that breaks it.
+bool parity_chain_ok(const LdpcSchedule& s, const std::vector<uint32_t>& wr, int dmax, int* layer, int* wave)
+{
+    const int RSW = rec_stride_wave(dmax);
+    constexpr uint32_t kKey = (~0u << kRecBlockShift) | kRecPacked | 0xffu; // block, format and degree: the run loop's key
+    auto mask = [&](const uint32_t* r, int slot) { return slot < v2_nfix(dmax) ? r[4 + dmax + 2 * slot] | r[4 + dmax + 2 * slot + 1] : 0u; };
+    for (int i = 1; i + 1 < s.q; i++)
+        for (int w = 0; w < 6; w++) {
+            const uint32_t* a = &wr[((size_t)i * 6 + w) * RSW];
+            const uint32_t* b = a + (size_t)6 * RSW;
+            if (!(a[0] & kRecPacked) || (a[0] >> kRecBlockShift) < 360u) continue;
+            const int own = (int)(a[0] & 0xffu), prev = own + 1; // slots behind the data entries
+            bool ok = a[4 + own] == a[4 + prev] + 360u && !mask(a, own) && !mask(a, prev);
+            if (i + 2 < s.q && (a[0] & kKey) == (b[0] & kKey)) ok = ok && b[4 + prev] == a[4 + own]; // (b is checked as a record in its own turn)
+            if (!ok) { *layer = i; *wave = w; return false; }
+        }
+    return true;
+}
 } // namespace
 
 LdpcPlan plan_ldpc(const LdpcSchedule& s, const char* table_name, int group_size, const LdpcOverrides& ov)
@@ -328,6 +353,10 @@ LdpcPlan plan_ldpc(const LdpcSchedule& s, const char* table_name, int group_size
     }
     if (c.packed && v2_pure_class(c.dmax) && has_unpacked_record(s, p.wrecs, RSW, &bad_layer, &bad_wave)) { // the plan that is returned: refuse loudly
         p.error = "internal: a (layer, wave) record of a pure packed build is not in the packed format (layer " + std::to_string(bad_layer) + ", wave " + std::to_string(bad_wave) + ")";
+        return p;
+    }
+    if (c.packed && !c.pr && c.dmax <= 8 && !parity_chain_ok(s, p.wrecs, c.dmax, &bad_layer, &bad_wave)) { // (the run loop's classes: ldpc_kernel.hpp, kRun)
+        p.error = "internal: the parity slots of a packed regular record do not fit the run loop's parity carry (layer " + std::to_string(bad_layer) + ", wave " + std::to_string(bad_wave) + ")";
         return p;
     }
     p.recs = lr.recs;

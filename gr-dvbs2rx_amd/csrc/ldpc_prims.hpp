@@ -143,6 +143,8 @@ __device__ __forceinline__ int mag_offset(int Lb, int mb)
 // array's address is a link-time constant the compiler cannot fold into an address that inline asm produced.
 __device__ __forceinline__ int lds_rd(int a) { return *reinterpret_cast<const lds_byte_t*>((size_t)(uint32_t)a); }
 __device__ __forceinline__ void lds_wr(int a, int v) { *reinterpret_cast<lds_byte_t*>((size_t)(uint32_t)a) = (uint8_t)v; }
+// the byte OFF behind a, through the typed pointer: the constant goes into the instruction's offset field (ds_read_u8 ... offset:OFF), no add
+template <int OFF> __device__ __forceinline__ int lds_rd_at(int a) { return *(reinterpret_cast<const lds_byte_t*>((size_t)(uint32_t)a) + OFF); }
 // Round 5: the builds with packed nodes keep the LLR bytes in LDS as TWO'S COMPLEMENT (TC): the packed arithmetic works on value << 8 in signed
 // 16-bit halves, and with offset-binary bytes every pair paid one xor after its reads and one before its writes (8 of the ~110 VALU instructions
 // of a degree-7 check). The scalar paths of such a build (layer 0, the ordered phase of hazard layers, waves whose record does not fit the
@@ -226,6 +228,13 @@ __device__ __forceinline__ int fix_wrap(int ad, uint32_t mlo, uint32_t mhi)
     asm volatile("s_mov_b64 %1, exec\n\ts_and_b64 exec, exec, %2\n\tv_add_u32 %0, 0x168, %0\n\ts_mov_b64 exec, %1"
                  : "+v"(ad), "=&s"(save) : "s"(mask) : "scc");
     return ad;
+}
+// The same as a choice of the BASE the window offset is added to: b360 (= b + 360) on the lanes of `mask`, b on the others. One
+// v_cndmask_b32 on the mask in its scalar register pair; EXEC is not touched and nothing here is an asm statement.
+__device__ __forceinline__ int wrap_base(int b, int b360, uint32_t mlo, uint32_t mhi)
+{
+    const unsigned long long mask = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)mhi) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)mlo);
+    return __builtin_amdgcn_inverse_ballot_w64(mask) ? b360 : b;
 }
 
 } // namespace dvbs2

@@ -8,8 +8,9 @@ which counts the regular node alone).
 
  (a) one REGULAR layer trip of the given degree: the cycle of basic blocks through the packed node (check_node_v2, found by its issue
      priority marks as in node_census.py) that a layer of that degree runs in every sweep but a frame's first -- the cheapest cycle of the
-     control-flow graph through the node's block that loads messages, stores messages (a frame's first sweep loads none) and meets
-     no barrier; the blocks it takes are printed, so the choice can be checked against the disassembly. Split into "node"
+     control-flow graph through the node's block (the first body of the degree in address order: the run loop's where the build has
+     one) that loads messages, stores messages (a frame's first sweep loads none) and meets no barrier; the blocks it takes and the
+     form of every body found are printed, so the choice can be checked against the disassembly. Split into "node"
      (s_setprio 0 .. the end of the node's block: the node and its message packing, what node_census.py calls total) and "else"
      (everything outside: the layer head, the switch, message load / store, the copies at the loop's back edge).
  (a') where the build has the run loop (two node bodies of the degree in a loop; a third one may serve a frame's first sweep in the
@@ -94,15 +95,34 @@ def find_nodes(blk, deg):
     return out
 
 
+def node_form(b, i):
+    """"run" / "loop": which form of check_node_v2 the body behind the s_setprio 0 at b[i] is, by its wrap fix -- the run loop's selects the
+    base with a v_cndmask_b32 on the record's lane mask, the layer loop's adds under an EXEC mask (s_and_b64 exec). None: neither mark."""
+    if any(x == "s_and_b64" and y.startswith("exec") for x, y in b[i:]):
+        return "loop"
+    return "run" if any(x.startswith("v_cndmask_b32") for x, _ in b) else None
+
+
 def find_node(blk, deg, first=0):
+    """A packed regular node of the degree, by its LLR byte WRITES between s_setprio 0 and the end of its block: `deg` of them in the
+    layer loop's form, deg - 1 in the run loop's (the own-parity byte stays in the carry; told from the layer loop's form of the next
+    lower degree by node_form). A body with deg - 1 writes and neither mark of a form stops the census: it cannot be told which degree it
+    is. (The byte READS no longer tell: without an asm statement in the address phase the scheduler moves some of them in front of the
+    s_setprio 0.)"""
     for k, b in enumerate(blk):
         if k < first:
             continue
         for i, (o, a) in enumerate(b):
             if o == "s_setprio" and a.startswith("0"):
                 rest = b[i:]
-                if any(x == "s_setprio" and y.startswith("3") for x, y in rest) and any(x.startswith("v_pk_") for x, _ in rest) \
-                        and sum(1 for x, _ in rest if x == "ds_read_u8") == deg and not any(x == "s_barrier" for x, _ in rest):
+                if not (any(x == "s_setprio" and y.startswith("3") for x, y in rest) and any(x.startswith("v_pk_") for x, _ in rest)) \
+                        or any(x == "s_barrier" for x, _ in rest):
+                    continue
+                writes = sum(1 for x, _ in rest if x.startswith("ds_write_b8"))
+                form = node_form(b, i)
+                if form is None and writes in (deg - 1, deg):
+                    sys.exit(f"block {k}: a packed node with {writes} byte writes and the wrap fix of neither form")
+                if writes == (deg - 1 if form == "run" else deg):
                     return k, i
     return None, None
 
@@ -232,8 +252,14 @@ def main():
     print(f"      else: {rest['vmem']} buffer instructions, {sum(1 for o, _ in rest_ops if o == 's_waitcnt')} s_waitcnt")
     # (a') the run loop (degree classes up to 8): the node is instantiated twice per degree, one body per half of the loop unrolled by two
     # over ping-pong record registers; a trip is one node and the way to the other one (the cheapest one: no barrier, not a frame's first sweep)
-    nodes = find_nodes(blk, a.deg)
-    nodes = run_loop_pair(blk, succ, nodes) if len(nodes) >= 2 else None
+    found = find_nodes(blk, a.deg)
+    forms = [node_form(blk[k], i) for k, i in found]
+    print(f"      bodies of degree {a.deg}: " + ", ".join(f"{names.get(k, f'+{k}')} ({f})" for (k, _), f in zip(found, forms)))
+    nodes = run_loop_pair(blk, succ, found) if len(found) >= 2 else None
+    # the run loop has exactly two bodies of a degree, and they are the pair with the shortest way round: anything else is a misreading
+    run_bodies = [n for n, f in zip(found, forms) if f == "run"]
+    if run_bodies and (len(run_bodies) != 2 or nodes is None or sorted(nodes) != sorted(run_bodies)):
+        sys.exit(f"run-loop bodies of degree {a.deg}: found {len(run_bodies)} in the run form, the loop pair is {nodes}")
     if nodes:
         print(f"(a') run loop, degree {a.deg}: two halves (node -> way to the other node through the message loads; +bar: the way through a barrier)")
         for h, ((ka, ia), (kb, ib)) in enumerate((nodes, nodes[::-1])):
