@@ -484,8 +484,11 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
                 // Run loop (see kRun): a maximal stretch of consecutive regular layers whose record of THIS wave is packed and has one degree.
                 // The degree dispatch and the header decode happen once per run, and the trip is unrolled by two over ping-pong registers:
                 // the record (A / B) and the messages (pre / pb) a trip has fetched ahead are what the next trip works on, where it lies.
-                // What a trip keeps of the layer loop: the per-layer barrier bit, the prefetch behind the barrier, the vmcnt(0) in front
-                // of the stores. What it does not hold (notes/r10_straight_trip.md): a frame's first sweep -- it loads no messages, and as
+                // What a trip keeps of the layer loop: the per-layer barrier bit, the message prefetch behind the barrier, the vmcnt(0) in
+                // front of the stores. The next RECORD is fetched from inside the node, behind its input phase (the hook of check_node_v2,
+                // RUN): scalar memory shares its counter with LDS, so at the trip's head the three record loads sat under the node's first
+                // LDS wait, which then could not be counted over the six byte reads either (notes/r12_trip_waits.md).
+                // What it does not hold (notes/r10_straight_trip.md): a frame's first sweep -- it loads no messages, and as
                 // an arm of the trip it cost every trip a message copy and three flag registers; that sweep takes the packed arm of the
                 // layer loop below --, a layer index (the message offset is the induction variable, the record to fetch ahead a running
                 // pointer) and the table's last layer, behind which that pointer would have to wrap: a run ends in front of it. A run
@@ -499,8 +502,12 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
                         constexpr uint32_t kKeyMask = (~0u << kRecBlockShift) | kRecPacked | 0xffu;
                         const uint32_t key = nhdr & kKeyMask;
                         uint32_t ha = nhdr, hb, ea[2 * DMAX], eb[2 * DMAX], pb[MW];
+                        // (readfirstlane: the words are uniform, and the instruction folds away where the layer loop holds them in scalar registers.
+                        // It cuts the register-class link between the layer loop's copy of a record and the run loop's: with the record loads
+                        // issued from inside the node the compiler keeps words 0-3 of BOTH copies in VGPRs without it -- four v_mov per pair of
+                        // trips --; with it the layer loop alone does, and a run pays four lane reads at its entry. notes/r12_trip_waits.md)
 #pragma unroll
-                        for (int k = 0; k < 2 * DMAX; k++) ea[k] = nent[k];
+                        for (int k = 0; k < 2 * DMAX; k++) ea[k] = (uint32_t)__builtin_amdgcn_readfirstlane((int)nent[k]);
                         const uint32_t* nrec = wr + (size_t)(i + 1) * RSW; // the record the next trip fetches ahead: a running pointer
                         int sa = i * kLayerBytes, sb;                       // scalar byte offset of a trip's messages
                         const int s_last = (q - 1) * kLayerBytes;           // the last layer's: never reached inside a run
@@ -521,14 +528,16 @@ __global__ __launch_bounds__(SOLO ? kSoloThreads : kThreads, SOLO ? 4 : MINW) vo
                             TSTAMP(tA); \
                             NS = S + kLayerBytes; \
                             if (__builtin_expect((H & (1u << kRecSyncShift)) != 0u, 1)) lds_barrier(); \
-                            asm volatile("" ::: "memory"); \
-                            NH = nrec[0]; \
-                            _Pragma("unroll") for (int k = 0; k < 2 * DMAX; k++) NE[k] = nrec[4 + k]; \
-                            nrec += RSW; \
                             TSTAMP(tB); tm_bar += tB - tA; \
                             uint32_t nm[MW]; \
                             msg_load(NP, NS, rowm); \
-                            check_node_v2<D, DMAX, TC, true>(E, row + lb, P, nm, 0, rowb360, &carry); \
+                            check_node_v2<D, DMAX, TC, true>(E, row + lb, P, nm, [&]() { \
+                                asm volatile("" ::: "memory"); \
+                                NH = nrec[0]; \
+                                _Pragma("unroll") for (int k = 0; k < 2 * DMAX; k++) NE[k] = nrec[4 + k]; \
+                                nrec += RSW; \
+                                asm volatile("" ::: "memory"); \
+                            }, rowb360, &carry); \
                             DVBS2_WAIT_VM0(); \
                             msg_store(nm, S, rowm); \
                             TSTAMP(tC); tm_body += tC - tB; \

@@ -179,7 +179,10 @@ __device__ __forceinline__ void check_node_v2(const uint32_t* ent /*record words
     // flight turns every LDS wait into "wait for everything" -- was tried with a scheduling barrier and an ordering dependency:
     // it cost 9 % on table B4 and a factor 4 on the degree-30 class through what it does to register allocation. The loads stay
     // at the top of the layer; notes/history.md 3.4.)
-    (void)prefetch_next_record;
+    // RUN: the run loop's trip issues the NEXT record's scalar loads from here, into the ping-pong record set that is dead during the node
+    // (the layer loop has one set and paid sixteen s_mov for the attempt above). The input phase's LDS wait no longer covers scalar loads and
+    // is counted over the byte reads; the header is first needed at the trip's end (notes/r12_trip_waits.md).
+    if constexpr (RUN) prefetch_next_record(); else (void)prefetch_next_record;
     if (ODD) a[NP - 1] = as_v2s(as_u32(a[NP - 1]) | 0x7fff0000u); // the pad's magnitude: above every real one
     v2s16 m0, m1;
     two_smallest_pk<NP>(a, m0, m1);

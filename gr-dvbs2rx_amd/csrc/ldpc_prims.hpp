@@ -231,9 +231,12 @@ __device__ __forceinline__ int fix_wrap(int ad, uint32_t mlo, uint32_t mhi)
 }
 // The same as a choice of the BASE the window offset is added to: b360 (= b + 360) on the lanes of `mask`, b on the others. One
 // v_cndmask_b32 on the mask in its scalar register pair; EXEC is not touched and nothing here is an asm statement.
+// (The mask words are record words of the run loop, uniform to the compiler, and are handed over as they are: a readfirstlane on them is a
+// use that wants a VGPR, and with the record loads issued from inside the node that use made the compiler keep the whole record set of
+// the run loop AND of the layer loop in VGPRs -- 8 v_mov per pair of trips, 16 bytes of scratch: notes/r12_trip_waits.md.)
 __device__ __forceinline__ int wrap_base(int b, int b360, uint32_t mlo, uint32_t mhi)
 {
-    const unsigned long long mask = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)mhi) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)mlo);
+    const unsigned long long mask = ((unsigned long long)mhi << 32) | mlo;
     return __builtin_amdgcn_inverse_ballot_w64(mask) ? b360 : b;
 }
 

@@ -16,7 +16,9 @@ which counts the regular node alone).
  (a') where the build has the run loop (two node bodies of the degree in a loop; a third one may serve a frame's first sweep in the
      layer loop): per half of the loop unrolled by two everything a wave issues from the head of one node to the head of the other
      (VALU, SALU, branches taken), by the cheapest way that issues the message loads -- once without a barrier, once through one --
-     and the register moves and lane accesses it meets between the two node bodies.
+     and the register moves and lane accesses it meets between the two node bodies; then what the half waits for (waits_of): the operand
+     of the node's first LDS wait, where scalar loads and message loads are issued and how many lie in the next trip's head, the
+     vmcnt operands.
  (b) one HAZARD layer of the single-pair lane-chain form (check_node_chain_v2) of that degree: the text between the node's first
      s_setprio 0 and the message packing behind its last phase, split at its two barriers into P1 (regular entries read and reduced,
      heads' pair, chain operands published), walk (per chain: prologue + ONE four-step trip of the walk loop + the three tail steps)
@@ -224,6 +226,22 @@ def span_tally(ops):
     return c
 
 
+def waits_of(ops):
+    """what a half of the run loop waits for, from the head of its node (ops[0], the s_setprio 0) to the head of the other one. A trip's head
+    is what lies between the message store of the trip before and its node's head, so the span holds this node and the NEXT trip's head:
+    the node's first LDS wait with its operand (scalar loads share lgkmcnt with the byte reads and return out of order: one of them in
+    flight makes that wait lgkmcnt(0) and puts a scalar-cache round trip under it), where the scalar loads and the message loads are
+    issued, in instructions from the node's head, how many of each lie in the next trip's head, and every vmcnt operand on the way"""
+    first = next((i for i, (o, a) in enumerate(ops) if o == "s_waitcnt" and "lgkmcnt" in a), None)
+    store = max((i for i, (o, _) in enumerate(ops) if o.startswith("buffer_store")), default=len(ops))
+    sl = [i for i, (o, _) in enumerate(ops) if o.startswith("s_load")]
+    bl = [i for i, (o, _) in enumerate(ops) if o.startswith("buffer_load")]
+    vm = [re.search(r"vmcnt\((\d+)\)", a).group(0) for o, a in ops if o == "s_waitcnt" and "vmcnt" in a]
+    return (f"node's first LDS wait: {ops[first][1] if first is not None else 'none'} at {first}; s_load at {sl or 'none'}, buffer_load at {bl or 'none'}, "
+            f"message store at {store} of {len(ops)} instructions from the node's head; in the next trip's head (behind the store): "
+            f"{sum(1 for i in sl if i > store)} s_load, {sum(1 for i in bl if i > store)} buffer_load; vmcnt waits: {' '.join(vm) or 'none'}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--obj", default=os.path.join(ROOT, "gr-dvbs2rx_amd", "build", "ldpc_inst_8.o"))
@@ -276,6 +294,7 @@ def main():
                       f"{sum(1 for o, _ in ops if o == 's_waitcnt')} s_waitcnt; blocks " + " ".join(names.get(k, f"+{k}") for k in [ka] + way + [kb]))
                 if not barrier:
                     print(f"      moves and lane accesses between the node bodies: {len(moves)}" + ("".join("\n        " + m for m in moves)))
+                    print("      " + waits_of(ops))
     # (b) the chain node: two barriers with a float walk (v_med3_f32) between them, DEG - 2 + 3 LLR byte reads in front
     flat = [op for b in blk for op in b]
     bars = [i for i, (o, _) in enumerate(flat) if o == "s_barrier"]
