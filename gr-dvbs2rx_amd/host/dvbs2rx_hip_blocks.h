@@ -371,6 +371,40 @@ private:
     dvbs2_rotator_t* d_h = nullptr;
 };
 
+// ---------------------------------------------------------------------------------------------- AWGN channel
+// The noise_source_c(GR_GAUSSIAN, sqrt(N0 * sps)) -> add_vcc pair of the transmit flowgraph (apps/dvbs2-tx:572-584) as one sync block
+// of this library's own: one output item per input item, out = in + sigma * noise with the noise of item n a function of (seed,
+// stream_id, n). `amplitude` is GNU Radio's, the standard deviation of the COMPLEX sample; the stage takes it per component,
+// amplitude / sqrt 2. The item count runs in the block (nitems_written), the device keeps nothing. Unpinned against GNU Radio, whose
+// generator is another one (include/dvbs2_fec_hip.h).
+class awgn_cc {
+public:
+    typedef std::shared_ptr<awgn_cc> sptr;
+    static sptr make(double amplitude, uint64_t seed = 0, uint64_t stream_id = 0, int max_items = 1 << 20, int device = 0)
+    {
+        return sptr(new awgn_cc(amplitude, seed, stream_id, max_items, device));
+    }
+    ~awgn_cc() { dvbs2_awgn_destroy(d_h); }
+    void set_amplitude(double amplitude) { check(dvbs2_awgn_set_sigma(d_h, (float)(amplitude / std::sqrt(2.0)))); }
+    void set_seed(uint64_t seed) { check(dvbs2_awgn_set_seed(d_h, seed)); }
+    uint64_t nitems_written() const { return (uint64_t)d_written; }
+    int work(int noutput_items, gr_vector_const_void_star& input_items, gr_vector_void_star& output_items)
+    {
+        check(dvbs2_awgn_add(d_h, static_cast<const float*>(input_items[0]), noutput_items, d_stream_id, d_written, static_cast<float*>(output_items[0])));
+        d_written += noutput_items;
+        return noutput_items;
+    }
+
+private:
+    awgn_cc(double amplitude, uint64_t seed, uint64_t stream_id, int max_items, int device) : d_stream_id(stream_id)
+    {
+        check(dvbs2_awgn_create(&d_h, seed, (float)(amplitude / std::sqrt(2.0)), 1, max_items, device));
+    }
+    dvbs2_awgn_t* d_h = nullptr;
+    uint64_t d_stream_id;
+    int64_t d_written = 0;
+};
+
 // ---------------------------------------------------------------------------------------------- symbol synchronizer
 // gr::dvbs2rx::symbol_sync_cc (include/gnuradio/dvbs2rx/symbol_sync_cc.h, lib/symbol_sync_cc_impl.cc): a general block. GNU Radio
 // hands general_work the input WITH the block's history in front; this mirror keeps the history in the handle on the device, so

@@ -16,7 +16,8 @@ from .capi import lib, check
 __all__ = ["get_fec_info", "rate_id", "LdpcDecoder", "BchDecoder", "Demapper", "FecChain", "BbDeheader", "ldpc_table_info", "ldpc_layer_info",
            "ldpc_table_names", "bb_descramble_sequence", "PlPayload",
            "pl_scrambling_rn", "HostBuffer", "PlFrontEnd", "plheader_symbols", "pls_parse", "apsk_points", "demap_table_check",
-           "PlSync", "plsync_taps", "plsync_thresholds", "PlCoarse", "plcoarse_weights", "Agc", "agc_check", "Rotator",
+           "PlSync", "plsync_taps", "plsync_thresholds", "PlCoarse", "plcoarse_weights", "Agc", "agc_check", "Awgn", "awgn_sigma", "awgn_words",
+           "awgn_sample", "awgn_check", "Rotator",
            "SymbolSync", "symsync_loop_constants", "symsync_geometry", "symsync_taps", "FecEncoder", "enc_check",
            "PlFramer", "plframer_layout", "PulseShaper", "pulse_geometry", "pulse_taps", "pulse_scale_taps",
            "BbFramer", "bbheader_build", "crc8"]
@@ -667,6 +668,97 @@ class Agc(_Handle):
         d_gain + 4 * s * gain_stride. d_out == d_in with equal strides works in place. One call in flight per handle."""
         check(lib.dvbs2_agc_work_device(self._h, d_in or None, int(in_stride), int(n_samples), int(n_streams), d_out or None, int(out_stride),
                                         d_gain or None, int(gain_stride), stream or None))
+
+
+_U64 = (1 << 64) - 1
+
+
+def awgn_sigma(esn0_db, es=1.0, sps=1):
+    """Per-component standard deviation (float32) of the noise that gives Es/N0 = esn0_db for symbol energy es at sps samples per symbol:
+    N0 = es / 10^(esn0_db/10), sigma = sqrt(N0 sps / 2) (reference apps/dvbs2-tx:574-580), in double, rounded once. Host only."""
+    s = C.c_float()
+    check(lib.dvbs2_awgn_sigma(float(esn0_db), float(es), int(sps), C.byref(s)))
+    return np.float32(s.value)
+
+
+def awgn_words(seed, stream_id, index):
+    """(wa, wb): the two Philox4x32-10 words behind complex sample `index` of stream `stream_id` under `seed`. Host only."""
+    w = np.zeros(2, np.uint32)
+    check(lib.dvbs2_awgn_words(int(seed) & _U64, int(stream_id) & _U64, int(index), w.ctypes.data))
+    return int(w[0]), int(w[1])
+
+
+def awgn_sample(seed, stream_id, index):
+    """The unit-variance noise (re, im as float32) of complex sample `index` of stream `stream_id` under `seed`: the host compilation
+    of the device's arithmetic, the same bits. Host only."""
+    v = np.zeros(2, np.float32)
+    check(lib.dvbs2_awgn_sample(int(seed) & _U64, int(stream_id) & _U64, int(index), v.ctypes.data))
+    return v
+
+
+def awgn_check(sigma, max_streams=1, max_samples=1):
+    """Raises Dvbs2Error (EINVAL, the text names the argument) for what an Awgn refuses: a sigma that is negative or not finite,
+    max_streams outside 1..65535, max_samples outside 1..2^30. Host only."""
+    check(lib.dvbs2_awgn_check(float(sigma), int(max_streams), int(max_samples)))
+
+
+class Awgn(_Handle):
+    """Additive white Gaussian noise channel, the stage behind PulseShaper and in front of Rotator (reference apps/dvbs2-tx:572-584):
+    y = x + sigma * noise per component, the noise a pure function of (seed, stream id, absolute sample index) -- Philox4x32-10 words
+    through a float32 Box-Muller (notes/awgn.md). No device state: any number of calls may be in flight, and pieces equal one call.
+    `position` is a host convenience: the first_index of a call that names none, advanced by n_samples by every such call."""
+    _destroy = lib.dvbs2_awgn_destroy
+
+    TILE = capi.AWGN_TILE
+
+    def __init__(self, seed=0, sigma=0.0, max_streams=1, max_samples=1 << 20, device=0):
+        check(lib.dvbs2_awgn_create(C.byref(self._h), int(seed) & _U64, float(sigma), int(max_streams), int(max_samples), device))
+        self.max_streams, self.max_samples = max_streams, max_samples
+        self.position = 0
+
+    def params(self):
+        """dict(seed, sigma as float32, max_streams, max_samples)."""
+        seed, sigma, v = C.c_uint64(), C.c_float(), [C.c_int() for _ in range(2)]
+        check(lib.dvbs2_awgn_params(self._h, C.byref(seed), C.byref(sigma), *[C.byref(x) for x in v]))
+        return dict(seed=seed.value, sigma=np.float32(sigma.value), max_streams=v[0].value, max_samples=v[1].value)
+
+    def set_sigma(self, sigma):
+        """For the calls made after it."""
+        check(lib.dvbs2_awgn_set_sigma(self._h, float(sigma)))
+
+    def set_seed(self, seed):
+        """For the calls made after it."""
+        check(lib.dvbs2_awgn_set_seed(self._h, int(seed) & _U64))
+
+    def work(self, samples, stream_id=0, first_index=None):
+        """HOST buffer of complex64 samples of one stream, or an int: that many samples of the noise alone. Returns complex64."""
+        if isinstance(samples, (int, np.integer)):
+            x, n = None, int(samples)
+        else:
+            x = np.asarray(samples)
+            if x.dtype != np.complex64:
+                raise TypeError(f"samples must be complex64, not {x.dtype}")
+            if x.ndim != 1 or not x.flags.c_contiguous:
+                raise ValueError("samples must be a C-contiguous vector")
+            n = x.size
+        out = np.empty(max(n, 0), np.complex64)
+        first = self.position if first_index is None else int(first_index)
+        check(lib.dvbs2_awgn_add(self._h, x.ctypes.data if x is not None and n else None, n, int(stream_id) & _U64, first,
+                                 out.ctypes.data if n > 0 else None))
+        if first_index is None:
+            self.position += n
+        return out
+
+    def work_device(self, d_in, in_stride, n_samples, n_streams, d_out, out_stride, first_stream=0, first_index=None, d_sigma=0, stream=0):
+        """DEVICE addresses (samples 8-byte aligned), asynchronous on `stream`: row r is stream first_stream + r, reads n_samples
+        complex64 samples at d_in + 8 * r * in_stride (d_in 0: the noise alone) and writes as many at d_out + 8 * r * out_stride; its
+        sample i has the absolute index first_index + i. d_sigma: n_streams float32, one per row, in place of the handle's sigma.
+        d_out == d_in with equal strides works in place."""
+        first = self.position if first_index is None else int(first_index)
+        check(lib.dvbs2_awgn_add_device(self._h, d_in or None, int(in_stride), int(n_samples), int(n_streams), int(first_stream) & _U64, first,
+                                        d_sigma or None, d_out or None, int(out_stride), stream or None))
+        if first_index is None:
+            self.position += int(n_samples)
 
 
 class Rotator(_Handle):

@@ -27,6 +27,7 @@ MOD_QPSK, MOD_8PSK, MOD_16APSK, MOD_32APSK = 0, 4, 6, 8
 ENC_NO_MAPPER = -1
 PULSE_TILE = 512  # DVBS2_PULSE_TILE: symbols per workgroup of the pulse shaper's kernel
 AGC_TILE = 64  # DVBS2_AGC_TILE: samples per stream and tile of the AGC's kernel
+AWGN_TILE = 512  # DVBS2_AWGN_TILE: samples of a row per workgroup of the AWGN channel's kernel
 
 
 class FecInfo(C.Structure):
@@ -177,6 +178,17 @@ SYMBOLS = {
     "dvbs2_agc_state": (_i, [_vp, _vp, _i]),
     "dvbs2_agc_work_device": (_i, [_vp, _vp, C.c_int64, _i, _i, _vp, C.c_int64, _vp, C.c_int64, _vp]),
     "dvbs2_agc_work": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "dvbs2_awgn_sigma": (_i, [C.c_double, C.c_double, _i, _fp]),
+    "dvbs2_awgn_words": (_i, [C.c_uint64, C.c_uint64, C.c_int64, _vp]),
+    "dvbs2_awgn_sample": (_i, [C.c_uint64, C.c_uint64, C.c_int64, _vp]),
+    "dvbs2_awgn_check": (_i, [_f, _i, _i]),
+    "dvbs2_awgn_create": (_i, [C.POINTER(_vp), C.c_uint64, _f, _i, _i, _i]),
+    "dvbs2_awgn_destroy": (None, [_vp]),
+    "dvbs2_awgn_set_sigma": (_i, [_vp, _f]),
+    "dvbs2_awgn_set_seed": (_i, [_vp, C.c_uint64]),
+    "dvbs2_awgn_params": (_i, [_vp, C.POINTER(C.c_uint64), _fp, _ip, _ip]),
+    "dvbs2_awgn_add_device": (_i, [_vp, _vp, C.c_int64, _i, _i, C.c_uint64, C.c_int64, _vp, _vp, C.c_int64, _vp]),
+    "dvbs2_awgn_add": (_i, [_vp, _vp, _i, C.c_uint64, C.c_int64, _vp]),
     "dvbs2_rotator_create": (_i, [C.POINTER(_vp), C.c_double, _i]),
     "dvbs2_rotator_destroy": (None, [_vp]),
     "dvbs2_rotator_reset": (_i, [_vp]),

@@ -641,6 +641,59 @@ int dvbs2_plcoarse_estimate(dvbs2_plcoarse_t* h, const float* plframes, int64_t 
                             float* coarse_foffset, int32_t* coarse_corrected, int32_t* new_est);
 int dvbs2_plcoarse_weights(int full, float* w);
 
+/* ---- additive white Gaussian noise channel: the stage behind the pulse shaper of the transmit flowgraph, in front of the rotator that
+ * applies the frequency offset. There (apps/dvbs2-tx:572-584) it is GNU Radio's analog.noise_source_c(GR_GAUSSIAN, sqrt(N0 * sps)) into
+ * blocks.add_vcc, but GNU Radio is not in the reference tree and its generator is another one: the stage is UNPINNED against GNU Radio.
+ * What is defined, and tested bit for bit against a float32 restatement (tests/awgn_model.py), is the arithmetic. The noise of complex
+ * sample n (int64, >= 0) of stream s (uint64) under seed k (uint64) is a pure function of (k, s, n):
+ *   words      Philox4x32-10 with counter (lo32(n >> 1), hi32(n >> 1), lo32(s), hi32(s)) and key (lo32(k), hi32(k)); sample n takes the
+ *              words (w0, w1) when n is even and (w2, w3) when it is odd: wa and wb. One generator block makes two complex samples.
+ *   transform  Box-Muller of u1 = (wa + 1/2) 2^-32 and u2 = (wb + 1/2) 2^-32: r = sqrt(-2 ln u1), noise = (r cos, r sin)(2 pi u2), built
+ *              from integer steps, float32 polynomials and one correctly rounded float32 square root (notes/awgn.md). All 32 bits of wa
+ *              count at the large end: the largest radius is sqrt(2 * 33 ln 2) = 6.76. The radius is never 0, NaN or infinite.
+ *   channel    y = x + sigma * noise per component: one product, then one addition; without an input y = sigma * noise, the product alone.
+ * Every operation is a single IEEE float32 operation in a written order, no fused multiply-add, denormals kept; values that are not
+ * finite propagate as IEEE arithmetic says. sigma == 0 returns the input, except that a component equal to -0 comes out +0 where
+ * its noise is positive (-0 + +0). sigma is the standard deviation PER COMPONENT. dvbs2_awgn_sigma (host only) gives it by the reference's
+ * rule (:574-580): N0 = es / 10^(esn0_db/10), sigma = sqrt(N0 sps / 2), evaluated in double and rounded once; it refuses arguments that
+ * are not finite, es <= 0 and sps < 1. dvbs2_awgn_words and dvbs2_awgn_sample (host only) are the host compilation of the same
+ * arithmetic: (wa, wb) and the unit-variance noise (re, im) of one sample, which is how one frame's noise is regenerated on the CPU;
+ * they refuse a negative index and a null output.
+ * THERE IS NO DEVICE STATE. The handle holds the seed, the scalar sigma and the checked limits, so ANY NUMBER OF CALLS MAY BE IN FLIGHT
+ * PER HANDLE -- the one difference from dvbs2_agc_* and dvbs2_pulse_* -- and however a stream is cut into calls, the bits are those
+ * of one call: the caller says where a call stands. Row r of a call is stream first_stream + r (wrapping mod 2^64); it reads n_samples
+ * samples at d_in + r in_stride and writes exactly n_samples at d_out + r out_stride; its sample i has the absolute index
+ * first_index + i. d_in == NULL selects the noise-only form. d_sigma is nullable: n_streams floats, 4-byte aligned, one per row, which
+ * replace the handle's sigma for this call and are NOT checked on the device -- a negative or non-finite entry propagates
+ * arithmetically. Buffers are interleaved (re, im) floats, 8-byte aligned; strides count complex elements and matter only when
+ * n_streams > 1. A lane owns one generator block, DVBS2_AWGN_TILE samples of a row to a workgroup; blocks that are 16-byte aligned in
+ * every row get one 16-byte load and store, any other the 8-byte path with the same bits; a call that starts or ends on an odd absolute
+ * index has a half block at that edge. d_out == d_in with equal strides is allowed and gives the bits of an out-of-place call; any other
+ * overlap is not allowed and not detected. One launch per call, no allocation, no host synchronisation.
+ * dvbs2_awgn_check (host only) refuses with DVBS2_EINVAL, in a text that names the argument, a sigma that is negative or not finite,
+ * max_streams outside 1..65535 and max_samples outside 1..2^30; dvbs2_awgn_create applies it; dvbs2_awgn_set_sigma applies its first
+ * part and, like dvbs2_awgn_set_seed, holds for the calls made after it. The add entries refuse with DVBS2_ESIZE n_samples >
+ * max_samples and n_streams > max_streams, and with DVBS2_EINVAL and a text that names the argument negative counts, a negative
+ * first_index or one whose last sample would pass 2^63 - 1, a null out with n_samples > 0, a misaligned buffer and, with n_streams > 1,
+ * a stride below n_samples. n_samples == 0 is a successful call that does nothing. A refused call writes nothing. ---- */
+typedef struct dvbs2_awgn dvbs2_awgn_t;
+#define DVBS2_AWGN_TILE 512
+int dvbs2_awgn_sigma(double esn0_db, double es, int sps, float* sigma);
+int dvbs2_awgn_words(uint64_t seed, uint64_t stream_id, int64_t index, uint32_t* wa_wb);
+int dvbs2_awgn_sample(uint64_t seed, uint64_t stream_id, int64_t index, float* re_im);
+int dvbs2_awgn_check(float sigma, int max_streams, int max_samples);
+int dvbs2_awgn_create(dvbs2_awgn_t** h, uint64_t seed, float sigma, int max_streams, int max_samples, int device);
+void dvbs2_awgn_destroy(dvbs2_awgn_t* h);
+int dvbs2_awgn_set_sigma(dvbs2_awgn_t* h, float sigma);
+int dvbs2_awgn_set_seed(dvbs2_awgn_t* h, uint64_t seed);
+/* each nullable */
+int dvbs2_awgn_params(const dvbs2_awgn_t* h, uint64_t* seed, float* sigma, int* max_streams, int* max_samples);
+/* DEVICE pointers, asynchronous on `stream`; d_in and d_sigma nullable */
+int dvbs2_awgn_add_device(dvbs2_awgn_t* h, const float* d_in, int64_t in_stride, int n_samples, int n_streams, uint64_t first_stream,
+                          int64_t first_index, const float* d_sigma, float* d_out, int64_t out_stride, void* stream);
+/* host pointers, synchronous: one row, staged through a buffer of the handle; in nullable (noise only) */
+int dvbs2_awgn_add(dvbs2_awgn_t* h, const float* in, int n_samples, uint64_t stream_id, int64_t first_index, float* out);
+
 /* ---- automatic gain control: the first stage of the receive flowgraph, in front of the rotator. There (apps/dvbs2-rx:873-887) it is GNU
  * Radio's analog.agc_cc(rate, reference, gain) with set_max_gain(65536) behind an optional blocks.swap_iq; the defaults are rate 1e-5,
  * reference 1, gain 1 (:1257-1269). The semantics are those of gr::analog::kernel::agc_cc::scale with max_gain, but GNU Radio is not in

@@ -3,6 +3,12 @@
 (scrambler on) -> AWGN added on the device with torch (fixed seed) -> FecChain.work_device (descrambler on) -> compared on the
 device. Only the error counts come back to the host. A tool, not a test: it asserts no error rate.
 
+--noise device takes the noise from the library's own channel stage (Awgn, dvbs2_awgn_add_device) in place on the symbols: one row per
+frame, the stream id the running frame number, so a frame's noise is a function of (--seed, frame number) alone and the counts do not
+depend on --batch (the frame's bytes are then a function of the same two as well). Every failed frame is named on stderr with the
+(seed, stream id) that regenerates its noise. With --pl the PLFRAME stream is one row, stream id 0, with a running first_index.
+--noise torch (the default) is the path above, unchanged.
+
 --pl pilots | nopilots puts the physical layer in between: FecEncoder -> PlFramer (the batch as a CCM sequence plus a closing header,
 PL scrambling code --gold) -> AWGN on the whole PLFRAME stream, headers and pilots included -> PlFrontEnd.work_device (trailing header,
 frames coarse-corrected: PLSC decoding, pilot / header phase estimates, de-rotation, descrambling) -> FecChain. The JSON line then also
@@ -39,9 +45,10 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--pl", choices=("off", "pilots", "nopilots"), default="off", help="frame into PLFRAMEs and receive through PlFrontEnd")
     ap.add_argument("--gold", type=int, default=0, help="PL scrambling code (with --pl)")
+    ap.add_argument("--noise", choices=("torch", "device"), default="torch", help="device: the library's AWGN stage, reproducible per frame")
     a = ap.parse_args()
     import torch
-    from dvbs2rx_amd import FecChain, FecEncoder, PlFramer, PlFrontEnd, capi
+    from dvbs2rx_amd import Awgn, FecChain, FecEncoder, PlFramer, PlFrontEnd, capi
     fs = capi.FECFRAME_NORMAL if a.framesize == "normal" else capi.FECFRAME_SHORT
     mod = {"qpsk": capi.MOD_QPSK, "8psk": capi.MOD_8PSK, "16apsk": capi.MOD_16APSK, "32apsk": capi.MOD_32APSK}[a.constellation]
     batch = min(a.batch, a.frames)
@@ -76,13 +83,28 @@ def main():
         d_cf = torch.zeros((batch,), dtype=torch.float32, device="cuda")  # read by the pilotless front end only
         d_plsc = torch.empty((batch,), dtype=torch.uint8, device="cuda")
         framed = 0
+    if a.noise == "device":
+        awgn = Awgn(a.seed, sigma, max_streams=batch, max_samples=enc.n_syms if a.pl == "off" else batch * front.plframe_len + 90)
+        byte_of = torch.arange(enc.in_bytes, dtype=torch.int64, device="cuda").view(1, -1)
+
+        def frame_bytes(first, count):  # a 64-bit mix of (seed, frame number, byte number): the same bytes however the frames are batched
+            x = torch.arange(first, first + count, dtype=torch.int64, device="cuda").view(-1, 1) * enc.in_bytes + byte_of + a.seed * 0x632BE5AB
+            for mul, shift in ((-7046029254386353131, 31), (-4658895280553007687, 29), (-7723592293110705685, 32)):
+                x = (x * mul) ^ ((x * mul) >> shift)
+            return ((x >> 24) & 255).to(torch.uint8)
     done, t0 = 0, time.time()
     while done < a.frames:
         nf = min(batch, a.frames - done)
-        d_in = torch.randint(0, 256, (nf, enc.in_bytes), dtype=torch.uint8, device="cuda", generator=gen)
+        if a.noise == "device":
+            d_in = frame_bytes(done, nf)
+        else:
+            d_in = torch.randint(0, 256, (nf, enc.in_bytes), dtype=torch.uint8, device="cuda", generator=gen)
         if a.pl == "off":
             enc.work_device(d_in.data_ptr(), nf, d_syms=d_syms.data_ptr(), stream=st)
-            d_syms[:nf].add_(torch.randn((nf, enc.n_syms, 2), dtype=torch.float32, device="cuda", generator=gen), alpha=sigma)
+            if a.noise == "device":
+                awgn.work_device(d_syms.data_ptr(), enc.n_syms, enc.n_syms, nf, d_syms.data_ptr(), enc.n_syms, first_stream=done, first_index=0, stream=st)
+            else:
+                d_syms[:nf].add_(torch.randn((nf, enc.n_syms, 2), dtype=torch.float32, device="cuda", generator=gen), alpha=sigma)
         else:
             if framed != nf:  # the last batch may be shorter
                 framer.set_sequence([plsc] * nf)
@@ -90,7 +112,10 @@ def main():
             n_pl = nf * front.plframe_len + 90
             enc.work_device(d_in.data_ptr(), nf, d_syms=d_xfec.data_ptr(), stream=st)
             framer.work_device(d_xfec.data_ptr(), nf, plsc, d_pl.data_ptr(), st)
-            d_pl[:n_pl].add_(torch.randn((n_pl, 2), dtype=torch.float32, device="cuda", generator=gen), alpha=sigma)
+            if a.noise == "device":
+                awgn.work_device(d_pl.data_ptr(), n_pl, n_pl, 1, d_pl.data_ptr(), n_pl, first_stream=0, stream=st)  # the running position
+            else:
+                d_pl[:n_pl].add_(torch.randn((n_pl, 2), dtype=torch.float32, device="cuda", generator=gen), alpha=sigma)
             front.work_device(d_pl.data_ptr(), nf, 1, d_cc.data_ptr(), d_cf.data_ptr(), d_syms.data_ptr(), st, plsc_decoded=d_plsc.data_ptr())
             plsc_err += (d_plsc[:nf] != plsc).sum()
         chain.work_device(d_syms.data_ptr(), nf, d_n0.data_ptr(), 1, d_msg.data_ptr(), 0, d_corr.data_ptr(), st)
@@ -98,6 +123,9 @@ def main():
         frame_err += (diff != 0).sum()
         bit_err += diff.sum()
         bch_fail += (d_corr[:nf] < 0).sum()
+        if a.noise == "device" and a.pl == "off":
+            for f in torch.nonzero(diff).view(-1).tolist():
+                print(f"failed frame: seed {a.seed} stream_id {done + f} ({int(diff[f])} bit errors)", file=sys.stderr)
         done += nf
     torch.cuda.synchronize()
     dt = time.time() - t0
@@ -105,6 +133,9 @@ def main():
     out = dict(framesize=a.framesize, rate=a.rate, constellation=a.constellation, esn0_db=a.esn0, frames=done, batch=batch,
                seed=a.seed, frame_errors=fe, bit_errors=be, bch_failures=int(bch_fail.item()), fer=fe / done,
                ber=be / (done * enc.in_bits), seconds=dt, frames_per_s=done / dt)
+    if a.noise == "device":
+        out.update(noise="device")
+        awgn.close()
     if a.pl != "off":
         out.update(pl=a.pl, gold=a.gold, plsc=plsc, plsc_errors=int(plsc_err.item()))
         framer.close()
