@@ -20,6 +20,7 @@ __all__ = ["get_fec_info", "rate_id", "LdpcDecoder", "BchDecoder", "Demapper", "
            "awgn_sample", "awgn_check", "Rotator",
            "SymbolSync", "symsync_loop_constants", "symsync_geometry", "symsync_taps", "FecEncoder", "enc_check",
            "PlFramer", "plframer_layout", "PulseShaper", "pulse_geometry", "pulse_taps", "pulse_scale_taps",
+           "Resampler", "resamp_step", "resamp_geometry", "resamp_max_out", "resamp_check",
            "BbFramer", "bbheader_build", "crc8"]
 
 DEFAULT_TRIALS = 25  # reference lib/ldpc_decoder_bb_impl.cc:391
@@ -1297,3 +1298,106 @@ class PulseShaper(_Handle):
         d_in + 8 * s * in_stride and writes n_syms * sps samples at d_out + 8 * s * out_stride. One call in flight per handle."""
         check(lib.dvbs2_pulse_shape_device(self._h, d_in or None, int(in_stride), int(n_syms), int(n_streams), d_out or None, int(out_stride),
                                            stream or None))
+
+
+def resamp_step(rate):
+    """nearbyint(2^32 / rate) for rate in [0.5, 64]: input samples per output sample with 32 fractional bits (dvbs2_resamp_step). The
+    effective rate is exactly 2^32 / step. Host only."""
+    step = C.c_uint64()
+    check(lib.dvbs2_resamp_step(float(rate), C.byref(step)))
+    return step.value
+
+
+def resamp_geometry(nfilts, ntaps):
+    """(terms per branch L, history in samples, delay_num: the delay is delay_num / nfilts input samples) (dvbs2_resamp_geometry).
+    Host only."""
+    return _ints(3, lib.dvbs2_resamp_geometry, int(nfilts), int(ntaps))
+
+
+def resamp_max_out(step, n_in):
+    """The largest n_out of a call of n_in samples for any position (dvbs2_resamp_max_out). Host only."""
+    n = lib.dvbs2_resamp_max_out(int(step), int(n_in))
+    check(min(n, 0))
+    return n
+
+
+def resamp_check(nfilts, taps, rate, max_streams=1, max_samples=1 << 20):
+    """Raises what Resampler(...) would raise for these arguments, without a device (dvbs2_resamp_check)."""
+    t = np.ascontiguousarray(taps, np.float32).reshape(-1)
+    check(lib.dvbs2_resamp_check(int(nfilts), t.ctypes.data if t.size else None, int(t.size), float(rate), int(max_streams), int(max_samples)))
+
+
+class Resampler(_Handle):
+    """Arbitrary-rate resampling: a polyphase bank of `nfilts` branches of the caller's prototype `taps` with linear interpolation
+    between neighbouring branches, real taps over complex samples, on a batch of independent streams whose histories and positions stay
+    on the device between calls (notes/resampler.md). n samples in give about n * rate samples out -- produce(n) says exactly how many --
+    delayed by delay_num / nfilts input samples; flush with `history` zero samples."""
+    _destroy = lib.dvbs2_resamp_destroy
+
+    TILE = capi.RESAMP_TILE
+
+    def __init__(self, nfilts, taps, rate, max_streams=1, max_samples=1 << 20, device=0):
+        t = np.ascontiguousarray(taps, np.float32).reshape(-1)
+        check(lib.dvbs2_resamp_create(C.byref(self._h), int(nfilts), t.ctypes.data if t.size else None, int(t.size), float(rate),
+                                      int(max_streams), int(max_samples), device))
+        self.max_streams, self.max_samples = max_streams, max_samples
+        self.nfilts, self.ntaps, self.terms, self.history, self.delay_num = _ints(5, lambda *a: lib.dvbs2_resamp_params(*a, None), self._h)
+
+    @property
+    def step(self):
+        step = C.c_uint64()
+        check(lib.dvbs2_resamp_params(self._h, None, None, None, None, None, C.byref(step)))
+        return step.value
+
+    def set_rate(self, rate):
+        """From the next call on; the positions are carried over."""
+        check(lib.dvbs2_resamp_set_rate(self._h, float(rate)))
+
+    def set_step(self, step):
+        check(lib.dvbs2_resamp_set_step(self._h, int(step)))
+
+    def reset(self):
+        check(lib.dvbs2_resamp_reset(self._h))
+
+    def reset_phase(self, frac=None):
+        """Position of stream s = frac[s] / 2^32 input samples (max_streams values below 2^32; None: zeros). Histories stay."""
+        if frac is None:
+            check(lib.dvbs2_resamp_reset_phase(self._h, None))
+            return
+        f = np.ascontiguousarray(frac, np.uint32).reshape(-1)
+        if f.size != self.max_streams:
+            raise ValueError(f"frac: expected {self.max_streams} values, got {f.size}")
+        check(lib.dvbs2_resamp_reset_phase(self._h, f.ctypes.data))
+
+    def produce(self, n_in, n_streams=1):
+        """int64 [n_streams]: what the next call of n_in samples writes per stream. From the host's mirror: no synchronisation."""
+        n = np.zeros(int(n_streams), np.int64)
+        check(lib.dvbs2_resamp_produce(self._h, int(n_in), int(n_streams), n.ctypes.data if n.size else None))
+        return n
+
+    def state(self):
+        """uint64 [max_streams]: the DEVICE's positions. Synchronous."""
+        acc = np.zeros(self.max_streams, np.uint64)
+        check(lib.dvbs2_resamp_state(self._h, acc.ctypes.data))
+        return acc
+
+    def work(self, samples):
+        """HOST buffer of complex64 samples of stream 0; returns the produce(samples.size)[0] complex64 samples."""
+        x = np.asarray(samples)
+        if x.dtype != np.complex64:
+            raise TypeError(f"samples must be complex64, not {x.dtype}")
+        if x.ndim != 1 or not x.flags.c_contiguous:
+            raise ValueError("samples must be a C-contiguous vector")
+        out = np.empty(max(int(self.produce(x.size)[0]), 1), np.complex64)
+        n = C.c_int64()
+        check(lib.dvbs2_resamp_process(self._h, x.ctypes.data if x.size else None, int(x.size), out.ctypes.data, int(out.size), C.byref(n)))
+        return out[:n.value]
+
+    def work_device(self, d_in, in_stride, n_in, n_streams, d_out, out_stride, stream=0):
+        """DEVICE addresses (8-byte aligned, not overlapping), asynchronous on `stream`: stream s reads n_in complex64 samples at
+        d_in + 8 * s * in_stride and writes n_out[s] samples at d_out + 8 * s * out_stride; out_stride >= max(n_out). Returns n_out as
+        int64 [n_streams] (what produce() said before the call). One call in flight per handle."""
+        n = np.zeros(int(n_streams), np.int64)
+        check(lib.dvbs2_resamp_process_device(self._h, d_in or None, int(in_stride), int(n_in), int(n_streams), d_out or None, int(out_stride),
+                                              n.ctypes.data if n.size else None, stream or None))
+        return n

@@ -26,6 +26,7 @@ OM_CODEWORD, OM_MESSAGE = 0, 1
 MOD_QPSK, MOD_8PSK, MOD_16APSK, MOD_32APSK = 0, 4, 6, 8
 ENC_NO_MAPPER = -1
 PULSE_TILE = 512  # DVBS2_PULSE_TILE: symbols per workgroup of the pulse shaper's kernel
+RESAMP_TILE = 1024  # DVBS2_RESAMP_TILE: output samples per workgroup of the resampler's kernel
 AGC_TILE = 64  # DVBS2_AGC_TILE: samples per stream and tile of the AGC's kernel
 AWGN_TILE = 512  # DVBS2_AWGN_TILE: samples of a row per workgroup of the AWGN channel's kernel
 
@@ -221,6 +222,21 @@ SYMBOLS = {
     "dvbs2_pulse_params": (_i, [_vp, _ip, _ip, _ip, _ip]),
     "dvbs2_pulse_shape_device": (_i, [_vp, _vp, C.c_int64, _i, _i, _vp, C.c_int64, _vp]),
     "dvbs2_pulse_shape": (_i, [_vp, _vp, _i, _vp]),
+    "dvbs2_resamp_step": (_i, [C.c_double, C.POINTER(C.c_uint64)]),
+    "dvbs2_resamp_geometry": (_i, [_i, _i, _ip, _ip, _ip]),
+    "dvbs2_resamp_max_out": (C.c_int64, [C.c_uint64, _i]),
+    "dvbs2_resamp_check": (_i, [_i, _vp, _i, C.c_double, _i, _i]),
+    "dvbs2_resamp_create": (_i, [C.POINTER(_vp), _i, _vp, _i, C.c_double, _i, _i, _i]),
+    "dvbs2_resamp_destroy": (None, [_vp]),
+    "dvbs2_resamp_reset": (_i, [_vp]),
+    "dvbs2_resamp_reset_phase": (_i, [_vp, _vp]),
+    "dvbs2_resamp_set_rate": (_i, [_vp, C.c_double]),
+    "dvbs2_resamp_set_step": (_i, [_vp, C.c_uint64]),
+    "dvbs2_resamp_params": (_i, [_vp, _ip, _ip, _ip, _ip, _ip, C.POINTER(C.c_uint64)]),
+    "dvbs2_resamp_produce": (_i, [_vp, _i, _i, _vp]),
+    "dvbs2_resamp_state": (_i, [_vp, _vp]),
+    "dvbs2_resamp_process_device": (_i, [_vp, _vp, C.c_int64, _i, _i, _vp, C.c_int64, _vp, _vp]),
+    "dvbs2_resamp_process": (_i, [_vp, _vp, _i, _vp, C.c_int64, C.POINTER(C.c_int64)]),
     "dvbs2_bbdeheader_create": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i]),
     "dvbs2_bbdeheader_create_raw": (_i, [C.POINTER(_vp), _i, _i, _i]),
     "dvbs2_bbdeheader_destroy": (None, [_vp]),

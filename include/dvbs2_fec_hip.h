@@ -890,6 +890,71 @@ int dvbs2_pulse_shape_device(dvbs2_pulse_t* h, const float* d_in, int64_t in_str
 /* host pointers, synchronous: stream 0 of the handle, staged through buffers of the handle */
 int dvbs2_pulse_shape(dvbs2_pulse_t* h, const float* in, int n_syms, float* out);
 
+/* ---- arbitrary-rate resampling: a polyphase filter bank of `nfilts` branches with linear interpolation between neighbouring branches
+ * through a bank of derivative taps, real taps over complex samples. Three uses: the fractional-sps branch of the reference's transmit
+ * flowgraph (apps/dvbs2-tx:641-686, GNU Radio's pfb_arb_resampler_ccf(sps, rrc_taps) with 32 branches, behind the PL framer in place of
+ * dvbs2_pulse_*), a sampling-clock offset of some ppm in a channel model (the impairment dvbs2_symsync_* tracks), and bringing a capture
+ * at, say, 2.5 samples per symbol to the 2 or 4 that dvbs2_symsync_* accepts. pfb_arb_resampler_ccf is not in the reference tree: the
+ * stage is UNPINNED against it. What is defined, and tested bit for bit against a float32 restatement (tests/resamp_model.py), is this:
+ *   POSITION, in integers and closed form. `step` is a 64-bit count of input samples per output sample with 32 fractional bits, in
+ *   [2^26, 2^33]; the rate is exactly 2^32 / step. dvbs2_resamp_step gives nearbyint(2^32 / rate) in double for rate in [0.5, 64]. Each
+ *   stream has a 64-bit acc, zero after create / reset. Output m (0-based in a call) of a call of n_in samples sits at T = acc + m step;
+ *   with N = n_in << 32 the call writes every m with T < N: n_out = 0 if acc >= N, else ceil((N - acc) / step), and afterwards
+ *   acc' = acc + n_out step - N. So the pieces of a stream give the samples of one call, and nothing drifts however long it runs.
+ *   From T: i = T >> 32 is the newest input sample used (0-based in the call's input), f = T & 0xffffffff the fraction, branch
+ *   j = f >> (32 - log2 nfilts), and a = float((f << log2 nfilts) >> 8) * 2^-24 on 32-bit words, the next 24 bits below the branch bits.
+ *   ARITHMETIC. Prototype taps h[0 .. ntaps), derivative taps d[n] = h[n + 1] - h[n] (n < ntaps - 1), d[ntaps - 1] = 0, one float
+ *   subtraction each, made at create (the rule of GNU Radio's create_diff_taps). For an output at (i, j, a), real and imaginary part
+ *   apart: o0 = sum over k of h[j + k nfilts] x[i - k], o1 = sum over k of d[j + k nfilts] x[i - k], k ascending from 0 while
+ *   j + k nfilts < ntaps, each term a float product and then a float addition (no fused multiply-add) onto an accumulator that starts at
+ *   +0.0f; then y = o0 + a * o1, a product and then an addition. x before the call is the stream's history: the last
+ *   L - 1 = ceil(ntaps / nfilts) - 1 samples of earlier calls, zeros after create / reset.
+ * The signal is delayed by ((ntaps - 1) / 2) / nfilts input samples. The taps are the caller's (dvbs2_pulse_taps(nfilts, rolloff, D, 0,
+ * nfilts) is the transmit prototype of apps/dvbs2-tx:669-676; with a wide rolloff the same call is a usable interpolation low-pass for a
+ * signal at 2 samples per symbol). One rate per handle; dvbs2_resamp_set_rate / _set_step take effect at the next call with acc carried
+ * over, so a drifting clock is a sequence of calls.
+ * The host keeps a mirror of every acc (plain integer arithmetic): dvbs2_resamp_produce says, without a synchronisation and without
+ * advancing anything, what the next call of n_in samples writes per stream; the call reports the same numbers through n_out_host
+ * (nullable, n_streams values); dvbs2_resamp_state copies the DEVICE's positions back (synchronous, max_streams values).
+ * Stream s of a call reads n_in samples at d_in + s in_stride and writes n_out[s] samples at d_out + s out_stride; data are interleaved
+ * (re, im) floats, strides count complex elements, buffers are 8-byte aligned and must NOT overlap (not detected). in_stride matters when
+ * n_streams > 1; out_stride is also the capacity of every stream's output and must be at least the call's largest n_out. At most two
+ * launches per call (the samples, then the new histories and positions), no allocation, no host synchronisation. ONE CALL IN FLIGHT PER
+ * HANDLE, as for dvbs2_pulse_*. The kernel works in tiles of DVBS2_RESAMP_TILE output samples per workgroup.
+ * Refused with DVBS2_ESIZE: n_in > max_samples, n_streams > max_streams. Refused with DVBS2_EINVAL and a text that names the argument:
+ * negative counts, a null buffer with n_in > 0, buffers that are not 8-byte aligned, with n_streams > 1 an in_stride < n_in, an
+ * out_stride (host entry: out_cap) below the largest n_out. A refused call leaves output, histories, positions and mirror untouched.
+ * n_in == 0 is a successful call that does nothing. Creation refuses (DVBS2_EINVAL) nfilts that is not a power of two in 2..256, ntaps
+ * outside 1..8192 or ceil(ntaps / nfilts) > 128, a tap that is not finite, a rate outside [0.5, 64], max_streams outside 1..65535,
+ * max_samples outside 1..2^24 (with that cap nothing overflows 64 bits and n_out < 2^31).
+ * Host only, no device needed: dvbs2_resamp_step, dvbs2_resamp_geometry (terms = L, history = L - 1, delay_num = (ntaps - 1) / 2),
+ * dvbs2_resamp_max_out (ceil((n_in << 32) / step): the largest n_out of a call of n_in samples for any acc; negative on a bad argument)
+ * and dvbs2_resamp_check (the argument check of dvbs2_resamp_create). ---- */
+typedef struct dvbs2_resamp dvbs2_resamp_t;
+#define DVBS2_RESAMP_TILE 1024
+int dvbs2_resamp_step(double rate, uint64_t* step);
+int dvbs2_resamp_geometry(int nfilts, int ntaps, int* terms, int* history, int* delay_num);
+int64_t dvbs2_resamp_max_out(uint64_t step, int n_in);
+int dvbs2_resamp_check(int nfilts, const float* taps, int ntaps, double rate, int max_streams, int max_samples);
+int dvbs2_resamp_create(dvbs2_resamp_t** h, int nfilts, const float* taps, int ntaps, double rate, int max_streams, int max_samples,
+                        int device);
+void dvbs2_resamp_destroy(dvbs2_resamp_t* h);
+/* every history and position back to zero; synchronous (waits for the device) */
+int dvbs2_resamp_reset(dvbs2_resamp_t* h);
+/* acc[s] = frac[s] for each of the handle's max_streams streams (null: zeros); histories stay; synchronous */
+int dvbs2_resamp_reset_phase(dvbs2_resamp_t* h, const uint32_t* frac);
+int dvbs2_resamp_set_rate(dvbs2_resamp_t* h, double rate);
+int dvbs2_resamp_set_step(dvbs2_resamp_t* h, uint64_t step);
+/* each nullable */
+int dvbs2_resamp_params(const dvbs2_resamp_t* h, int* nfilts, int* ntaps, int* terms, int* history, int* delay_num, uint64_t* step);
+int dvbs2_resamp_produce(const dvbs2_resamp_t* h, int n_in, int n_streams, int64_t* n_out);
+int dvbs2_resamp_state(dvbs2_resamp_t* h, uint64_t* acc);
+/* DEVICE pointers, asynchronous on `stream`; n_out_host is a HOST array, filled before the call returns */
+int dvbs2_resamp_process_device(dvbs2_resamp_t* h, const float* d_in, int64_t in_stride, int n_in, int n_streams, float* d_out,
+                                int64_t out_stride, int64_t* n_out_host, void* stream);
+/* host pointers, synchronous: stream 0 of the handle, staged through buffers of the handle; out_cap in complex elements */
+int dvbs2_resamp_process(dvbs2_resamp_t* h, const float* in, int n_in, float* out, int64_t out_cap, int64_t* n_out);
+
 /* ---- downstream neighbour: BBFRAME de-header, replaces bbdeheader_bb_impl::general_work (reference
  * lib/bbdeheader_bb_impl.cc:144-264) with parse_bbheader (:77-136) and check_crc8 (:138-142, generator
  * x^8 + x^7 + x^6 + x^4 + x^2 + 1, :55). Input: whole descrambled BBFRAMEs of kbch / 8 bytes (what dvbs2_bch_decode /
