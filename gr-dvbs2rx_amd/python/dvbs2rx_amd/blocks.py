@@ -17,7 +17,8 @@ __all__ = ["get_fec_info", "rate_id", "LdpcDecoder", "BchDecoder", "Demapper", "
            "ldpc_table_names", "bb_descramble_sequence", "PlPayload",
            "pl_scrambling_rn", "HostBuffer", "PlFrontEnd", "plheader_symbols", "pls_parse", "apsk_points", "demap_table_check",
            "PlSync", "plsync_taps", "plsync_thresholds", "PlCoarse", "plcoarse_weights", "Agc", "agc_check", "Awgn", "awgn_sigma", "awgn_words",
-           "awgn_sample", "awgn_check", "Rotator",
+           "awgn_sample", "awgn_check", "IqConverter", "IQ_FORMATS", "iqconv_bytes", "iqconv_check", "iqconv_unpack_host", "iqconv_pack_host",
+           "Rotator",
            "SymbolSync", "symsync_loop_constants", "symsync_geometry", "symsync_taps", "FecEncoder", "enc_check",
            "PlFramer", "plframer_layout", "PulseShaper", "pulse_geometry", "pulse_taps", "pulse_scale_taps",
            "Resampler", "resamp_step", "resamp_geometry", "resamp_max_out", "resamp_check",
@@ -760,6 +761,120 @@ class Awgn(_Handle):
                                         d_sigma or None, d_out or None, int(out_stride), stream or None))
         if first_index is None:
             self.position += int(n_samples)
+
+
+IQ_FORMATS = {"u8": capi.IQ_U8, "s8": capi.IQ_S8, "s16": capi.IQ_S16}
+_IQ_DTYPES = {capi.IQ_U8: np.uint8, capi.IQ_S8: np.int8, capi.IQ_S16: np.int16}
+
+
+def _iq_format(fmt):
+    return IQ_FORMATS[fmt] if isinstance(fmt, str) else int(fmt)
+
+
+def _iq_codes(fmt, codes):
+    """codes as a C-contiguous array of the format's dtype with an even number of elements (I, Q, I, Q, ...); any shape."""
+    c = np.asarray(codes)
+    if c.dtype != _IQ_DTYPES[fmt]:
+        raise TypeError(f"codes must be {np.dtype(_IQ_DTYPES[fmt])}, not {c.dtype}")
+    if not c.flags.c_contiguous or c.size % 2:
+        raise ValueError("codes must be C-contiguous and hold whole samples (I, Q)")
+    return c
+
+
+def _iq_stats(words):
+    return dict(samples=int(words[0]), clipped=int(words[1]), energy=int(words[2]))
+
+
+def iqconv_bytes(fmt):
+    """Bytes per complex sample of a format ("u8", "s8", "s16" or its number); -1 for an unknown number. Host only."""
+    return lib.dvbs2_iqconv_bytes(_iq_format(fmt))
+
+
+def iqconv_check(fmt, gain=1.0, max_streams=1, max_samples=1):
+    """Raises Dvbs2Error (EINVAL, the text names the argument) for what an IqConverter refuses: an unknown format, a gain that is not
+    finite, not positive or outside [2^-64, 2^64], max_streams outside 1..65535, max_samples outside 1..2^30. Host only."""
+    check(lib.dvbs2_iqconv_check(_iq_format(fmt), float(gain), int(max_streams), int(max_samples)))
+
+
+def iqconv_unpack_host(fmt, gain, codes, stats=False):
+    """The host compilation of the device's arithmetic: codes (I, Q, I, Q, ... of the format's dtype) to complex64. With stats, also
+    dict(samples, clipped, energy). Host only."""
+    f = _iq_format(fmt)
+    c = _iq_codes(f, codes)
+    out = np.empty(c.size // 2, np.complex64)
+    words = np.zeros(3, np.uint64)
+    check(lib.dvbs2_iqconv_unpack_host(f, float(gain), c.ctypes.data if c.size else None, c.size // 2, out.ctypes.data if c.size else None,
+                                       words.ctypes.data if stats else None))
+    return (out, _iq_stats(words)) if stats else out
+
+
+def iqconv_pack_host(fmt, gain, samples, stats=False):
+    """The host compilation of the device's arithmetic: complex64 samples to codes [n, 2] of the format's dtype. With stats, also
+    dict(samples, clipped, energy). Host only."""
+    f = _iq_format(fmt)
+    x = np.ascontiguousarray(samples, np.complex64).reshape(-1)
+    out = np.empty((x.size, 2), _IQ_DTYPES[f])
+    words = np.zeros(3, np.uint64)
+    check(lib.dvbs2_iqconv_pack_host(f, float(gain), x.ctypes.data if x.size else None, x.size, out.ctypes.data if x.size else None,
+                                     words.ctypes.data if stats else None))
+    return (out, _iq_stats(words)) if stats else out
+
+
+class IqConverter(_Handle):
+    """IQ sample converter, the stage at the ends of both flowgraphs (reference apps/dvbs2-rx:685-707, apps/dvbs2-tx:533-549): interleaved
+    u8 / s8 / s16 codes to complex64 samples (unpack, y = (c - B) / F * gain) and back (pack, rint(x * gain * F + B) clamped), with exact
+    integer statistics {samples, clipped, energy} added per row to a caller's buffer (notes/iqconv.md). No device state: any number of
+    device calls may be in flight."""
+    _destroy = lib.dvbs2_iqconv_destroy
+
+    TILE = capi.IQCONV_TILE
+
+    def __init__(self, fmt="u8", gain=1.0, max_streams=1, max_samples=1 << 20, device=0):
+        self.format = _iq_format(fmt)
+        check(lib.dvbs2_iqconv_create(C.byref(self._h), self.format, float(gain), int(max_streams), int(max_samples), device))
+        self.dtype = np.dtype(_IQ_DTYPES[self.format])
+        self.bytes = lib.dvbs2_iqconv_bytes(self.format)
+        self.max_streams, self.max_samples = max_streams, max_samples
+
+    def params(self):
+        """dict(format, gain as float32, max_streams, max_samples, tile)."""
+        gain, v = C.c_float(), [C.c_int() for _ in range(4)]
+        check(lib.dvbs2_iqconv_params(self._h, C.byref(v[0]), C.byref(gain), *[C.byref(x) for x in v[1:]]))
+        return dict(format=v[0].value, gain=np.float32(gain.value), max_streams=v[1].value, max_samples=v[2].value, tile=v[3].value)
+
+    def set_gain(self, gain):
+        """For the calls made after it."""
+        check(lib.dvbs2_iqconv_set_gain(self._h, float(gain)))
+
+    def unpack_device(self, d_in, in_stride, n_samples, n_streams, d_out, out_stride, d_stats=0, stream=0):
+        """DEVICE addresses, asynchronous on `stream`: row r reads n_samples samples of codes at d_in + bytes * r * in_stride (any byte
+        address; s16: any even one) and writes as many complex64 at d_out + 8 * r * out_stride (8-byte aligned). d_stats: n_streams x 3
+        uint64, added to."""
+        check(lib.dvbs2_iqconv_unpack_device(self._h, d_in or None, int(in_stride), int(n_samples), int(n_streams), d_out or None, int(out_stride),
+                                             d_stats or None, stream or None))
+
+    def pack_device(self, d_in, in_stride, n_samples, n_streams, d_out, out_stride, d_stats=0, stream=0):
+        """DEVICE addresses, asynchronous on `stream`: row r reads n_samples complex64 at d_in + 8 * r * in_stride and writes as many
+        samples of codes at d_out + bytes * r * out_stride. d_stats: n_streams x 3 uint64, added to."""
+        check(lib.dvbs2_iqconv_pack_device(self._h, d_in or None, int(in_stride), int(n_samples), int(n_streams), d_out or None, int(out_stride),
+                                           d_stats or None, stream or None))
+
+    def unpack_to_device(self, codes, d_out, stats=False):
+        """HOST codes (I, Q, I, Q, ... of the format's dtype) to complex64 at the DEVICE address d_out; synchronous, only the codes cross
+        the host link. With stats, returns dict(samples, clipped, energy)."""
+        c = _iq_codes(self.format, codes)
+        words = np.zeros(3, np.uint64)
+        check(lib.dvbs2_iqconv_unpack_to_device(self._h, c.ctypes.data if c.size else None, c.size // 2, d_out or None,
+                                                words.ctypes.data if stats else None))
+        return _iq_stats(words) if stats else None
+
+    def pack_from_device(self, d_in, n_samples, stats=False):
+        """n_samples complex64 at the DEVICE address d_in to HOST codes [n_samples, 2]; synchronous. With stats, also the dict."""
+        out = np.empty((max(int(n_samples), 0), 2), self.dtype)
+        words = np.zeros(3, np.uint64)
+        check(lib.dvbs2_iqconv_pack_from_device(self._h, d_in or None, int(n_samples), out.ctypes.data if out.size else None,
+                                                words.ctypes.data if stats else None))
+        return (out, _iq_stats(words)) if stats else out
 
 
 class Rotator(_Handle):

@@ -29,6 +29,8 @@ PULSE_TILE = 512  # DVBS2_PULSE_TILE: symbols per workgroup of the pulse shaper'
 RESAMP_TILE = 1024  # DVBS2_RESAMP_TILE: output samples per workgroup of the resampler's kernel
 AGC_TILE = 64  # DVBS2_AGC_TILE: samples per stream and tile of the AGC's kernel
 AWGN_TILE = 512  # DVBS2_AWGN_TILE: samples of a row per workgroup of the AWGN channel's kernel
+IQ_U8, IQ_S8, IQ_S16 = 0, 1, 2  # DVBS2_IQ_*: the code formats of the IQ sample converter
+IQCONV_TILE = 8192  # DVBS2_IQCONV_TILE: samples of a row per workgroup of the IQ sample converter's kernels
 
 
 class FecInfo(C.Structure):
@@ -190,6 +192,18 @@ SYMBOLS = {
     "dvbs2_awgn_params": (_i, [_vp, C.POINTER(C.c_uint64), _fp, _ip, _ip]),
     "dvbs2_awgn_add_device": (_i, [_vp, _vp, C.c_int64, _i, _i, C.c_uint64, C.c_int64, _vp, _vp, C.c_int64, _vp]),
     "dvbs2_awgn_add": (_i, [_vp, _vp, _i, C.c_uint64, C.c_int64, _vp]),
+    "dvbs2_iqconv_bytes": (_i, [_i]),
+    "dvbs2_iqconv_check": (_i, [_i, _f, _i, _i]),
+    "dvbs2_iqconv_unpack_host": (_i, [_i, _f, _vp, C.c_int64, _vp, _vp]),
+    "dvbs2_iqconv_pack_host": (_i, [_i, _f, _vp, C.c_int64, _vp, _vp]),
+    "dvbs2_iqconv_create": (_i, [C.POINTER(_vp), _i, _f, _i, _i, _i]),
+    "dvbs2_iqconv_destroy": (None, [_vp]),
+    "dvbs2_iqconv_set_gain": (_i, [_vp, _f]),
+    "dvbs2_iqconv_params": (_i, [_vp, _ip, _fp, _ip, _ip, _ip]),
+    "dvbs2_iqconv_unpack_device": (_i, [_vp, _vp, C.c_int64, _i, _i, _vp, C.c_int64, _vp, _vp]),
+    "dvbs2_iqconv_pack_device": (_i, [_vp, _vp, C.c_int64, _i, _i, _vp, C.c_int64, _vp, _vp]),
+    "dvbs2_iqconv_unpack_to_device": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "dvbs2_iqconv_pack_from_device": (_i, [_vp, _vp, _i, _vp, _vp]),
     "dvbs2_rotator_create": (_i, [C.POINTER(_vp), C.c_double, _i]),
     "dvbs2_rotator_destroy": (None, [_vp]),
     "dvbs2_rotator_reset": (_i, [_vp]),

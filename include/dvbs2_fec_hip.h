@@ -694,6 +694,73 @@ int dvbs2_awgn_add_device(dvbs2_awgn_t* h, const float* d_in, int64_t in_stride,
 /* host pointers, synchronous: one row, staged through a buffer of the handle; in nullable (noise only) */
 int dvbs2_awgn_add(dvbs2_awgn_t* h, const float* in, int n_samples, uint64_t stream_id, int64_t first_index, float* out);
 
+/* ---- IQ sample converter: the stage at the very ends of both flowgraphs, between a capture or a DAC stream of integer codes and the
+ * float samples every other stage works on. In the reference's receive flowgraph (apps/dvbs2-rx:685-707) it is blocks.deinterleave,
+ * uchar_to_float, add_const(-127.5), multiply_const(1/128) and float_to_complex in front of the AGC; in its transmit flowgraph
+ * (apps/dvbs2-tx:533-549, apps/dvbs2-rec:439-446) complex_to_float, multiply_const(128), add_const(127.5), float_to_uchar and interleave;
+ * the statistics are the block-mean form of the level reading that blocks.rms_cf gives the GUI (apps/dvbs2-rx:952). GNU Radio is not in
+ * the reference tree: the stage is UNPINNED against those blocks (float_to_uchar is taken as rint plus clamp), and rms_cf itself, a
+ * one-pole IIR, is not restated. What is defined, and tested bit for bit against a float32 restatement (tests/iqconv_model.py), is the
+ * arithmetic (csrc/iqconv_math.hpp). One complex sample is the I code, then the Q code; with bias B, full scale F and code range [lo, hi]
+ *   DVBS2_IQ_U8   B = 127.5, F = 128,   0..255            (RTL-SDR, the reference's recorder)
+ *   DVBS2_IQ_S8   B = 0,     F = 128,   -128..127         (HackRF)
+ *   DVBS2_IQ_S16  B = 0,     F = 32768, -32768..32767, int16 in host byte order (USRP, bladeRF, Pluto; a 12-bit device is s16, gain 16)
+ *   unpack   y = (float(c) - B) / F * gain per component: the float32 nearest to that real number, one rounding ((c - B) / F is exact,
+ *            and so is gain / F). With gain == 1 nothing is rounded and this is the reference's receive chain.
+ *   pack     t = x * gain (one float32 product); u = t * F (exact, or infinite and then saturating); w = u + B (one float32 addition,
+ *            nothing when B == 0); r = w rounded to the nearest integer, ties to even; the code is r clamped to [lo, hi]; a NaN gives
+ *            the middle code, 128 for u8 and 0 for the signed formats. With gain == 1 and u8 this is the reference's transmit wiring.
+ * No fused multiply-add, denormals kept. gain is a float32 of the handle, finite, positive and within [2^-64, 2^64].
+ * STATISTICS are exact integers, independent of any order of summation. d_stats is nullable: n_streams x 3 uint64, 8-byte aligned; a
+ * call ADDS per row {samples, clipped, energy} to it -- the caller zeroes it, and calls may be in flight concurrently on it. clipped
+ * counts components: in unpack those whose code sits on a rail (lo or hi), which is how a saturated ADC reads; in pack those with
+ * r < lo, r > hi or NaN -- a value that merely rounds onto the rail does not count. energy is the sum over I and Q of d * d mod 2^64,
+ * d = 2 c - 255 for u8 (units of 1/256 of full scale) and d = c for the signed formats, in pack over the codes written:
+ * rms = sqrt(energy / samples) / (256 or F). With d_stats == NULL the kernel does no reduction work.
+ * THERE IS NO DEVICE STATE: ANY NUMBER OF DEVICE CALLS MAY BE IN FLIGHT PER HANDLE. Row r of a call reads n_samples samples at
+ * d_in + r in_stride and writes exactly n_samples at d_out + r out_stride; strides count complex samples and matter only when
+ * n_streams > 1. Code buffers come from files and sockets: u8 / s8 rows may start at ANY byte address, s16 rows at any even one; float
+ * buffers are 8-byte aligned. Rows whose floats are 16-byte aligned and whose codes are 4-byte (s16: 8-byte) aligned in every row take
+ * the wide path -- 16 bytes per lane on the float side, a dword (s16: 8 bytes) on the code side, stored whole -- and every other
+ * combination a path with the same bits: an aligned interior, byte or short accesses at a row's head and tail only. Nothing outside
+ * [0, n_samples) of a row is read or written. A workgroup takes DVBS2_IQCONV_TILE samples of one row. In and out have different
+ * sizes: overlap is not allowed and not detected. One launch per call, no allocation, no host synchronisation.
+ * dvbs2_iqconv_bytes (host only) gives the bytes of a complex sample, -1 for an unknown format. dvbs2_iqconv_check (host only) refuses
+ * with DVBS2_EINVAL, in a text that names the argument, an unknown format, a gain that is not finite, not positive or outside
+ * [2^-64, 2^64], max_streams outside 1..65535 and max_samples outside 1..2^30; dvbs2_iqconv_create applies it; dvbs2_iqconv_set_gain
+ * applies its gain part and holds for the calls made after it. dvbs2_iqconv_unpack_host and dvbs2_iqconv_pack_host (host only) are the
+ * host compilation of the same arithmetic over n samples at any host address, stats three words, nullable, ADDED to; they refuse what
+ * check refuses of format and gain, a negative n and a null in or out with n > 0. The device entries refuse with DVBS2_ESIZE n_samples >
+ * max_samples and n_streams > max_streams, and with DVBS2_EINVAL and a text that names the argument negative counts, a null in or out
+ * with n_samples > 0, a misaligned buffer and, with n_streams > 1, a stride below n_samples. n_samples == 0 is a successful call that
+ * does nothing. A refused call writes nothing and adds nothing to the statistics.
+ * dvbs2_iqconv_unpack_to_device and dvbs2_iqconv_pack_from_device move HOST codes to and from DEVICE floats, one row, synchronously,
+ * through a staging buffer of the handle, so that only the codes cross the host link: 2 (s16: 4) bytes per sample instead of 8. They
+ * return with their output complete and the row's statistics ADDED to stats (three words on the host, nullable), and allow ONE call at
+ * a time per handle. ---- */
+typedef struct dvbs2_iqconv dvbs2_iqconv_t;
+#define DVBS2_IQ_U8 0
+#define DVBS2_IQ_S8 1
+#define DVBS2_IQ_S16 2
+#define DVBS2_IQCONV_TILE 8192
+int dvbs2_iqconv_bytes(int format);
+int dvbs2_iqconv_check(int format, float gain, int max_streams, int max_samples);
+int dvbs2_iqconv_unpack_host(int format, float gain, const void* in, int64_t n, float* out, uint64_t* stats);
+int dvbs2_iqconv_pack_host(int format, float gain, const float* in, int64_t n, void* out, uint64_t* stats);
+int dvbs2_iqconv_create(dvbs2_iqconv_t** h, int format, float gain, int max_streams, int max_samples, int device);
+void dvbs2_iqconv_destroy(dvbs2_iqconv_t* h);
+int dvbs2_iqconv_set_gain(dvbs2_iqconv_t* h, float gain);
+/* each nullable; tile = DVBS2_IQCONV_TILE */
+int dvbs2_iqconv_params(const dvbs2_iqconv_t* h, int* format, float* gain, int* max_streams, int* max_samples, int* tile);
+/* DEVICE pointers, asynchronous on `stream`; strides in complex samples; d_stats nullable */
+int dvbs2_iqconv_unpack_device(dvbs2_iqconv_t* h, const void* d_in, int64_t in_stride, int n_samples, int n_streams, float* d_out,
+                               int64_t out_stride, uint64_t* d_stats, void* stream);
+int dvbs2_iqconv_pack_device(dvbs2_iqconv_t* h, const float* d_in, int64_t in_stride, int n_samples, int n_streams, void* d_out,
+                             int64_t out_stride, uint64_t* d_stats, void* stream);
+/* HOST codes <-> DEVICE floats, synchronous, one row, staged through a buffer of the handle: only the codes cross the link */
+int dvbs2_iqconv_unpack_to_device(dvbs2_iqconv_t* h, const void* in, int n_samples, float* d_out, uint64_t* stats);
+int dvbs2_iqconv_pack_from_device(dvbs2_iqconv_t* h, const float* d_in, int n_samples, void* out, uint64_t* stats);
+
 /* ---- automatic gain control: the first stage of the receive flowgraph, in front of the rotator. There (apps/dvbs2-rx:873-887) it is GNU
  * Radio's analog.agc_cc(rate, reference, gain) with set_max_gain(65536) behind an optional blocks.swap_iq; the defaults are rate 1e-5,
  * reference 1, gain 1 (:1257-1269). The semantics are those of gr::analog::kernel::agc_cc::scale with max_gain, but GNU Radio is not in

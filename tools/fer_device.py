@@ -14,6 +14,11 @@ PL scrambling code --gold) -> AWGN on the whole PLFRAME stream, headers and pilo
 frames coarse-corrected: PLSC decoding, pilot / header phase estimates, de-rotation, descrambling) -> FecChain. The JSON line then also
 counts the frames whose decoded PLSC was wrong. --pl off (the default) is the path above, unchanged.
 
+--iq u8 | s8 | s16 puts the IQ sample converter (IqConverter, dvbs2_iqconv_*) behind the channel: its output is packed to these codes,
+with full scale --iq-backoff dB above the unit symbol amplitude, and unpacked again on the device before the receiver, as a capture in
+that format would leave it. The JSON line then also gives the clipped components and their share from the stage's statistics, so the
+loss of an 8-bit capture at a given back-off can be read off. Without --iq the tool behaves as before.
+
   python tools/fer_device.py --rate C1_2 --constellation qpsk --esn0 1.2 --frames 1000000 --batch 4096
   python tools/fer_device.py --rate C1_2 --constellation qpsk --esn0 1.2 --frames 100000 --batch 4096 --pl pilots --gold 5
 Prints one JSON line."""
@@ -46,9 +51,11 @@ def main():
     ap.add_argument("--pl", choices=("off", "pilots", "nopilots"), default="off", help="frame into PLFRAMEs and receive through PlFrontEnd")
     ap.add_argument("--gold", type=int, default=0, help="PL scrambling code (with --pl)")
     ap.add_argument("--noise", choices=("torch", "device"), default="torch", help="device: the library's AWGN stage, reproducible per frame")
+    ap.add_argument("--iq", choices=("u8", "s8", "s16"), default=None, help="pack the channel output to these codes and unpack it again")
+    ap.add_argument("--iq-backoff", type=float, default=12.0, metavar="DB", help="full scale above the unit symbol amplitude, in dB (with --iq)")
     a = ap.parse_args()
     import torch
-    from dvbs2rx_amd import Awgn, FecChain, FecEncoder, PlFramer, PlFrontEnd, capi
+    from dvbs2rx_amd import Awgn, FecChain, FecEncoder, IqConverter, PlFramer, PlFrontEnd, capi
     fs = capi.FECFRAME_NORMAL if a.framesize == "normal" else capi.FECFRAME_SHORT
     mod = {"qpsk": capi.MOD_QPSK, "8psk": capi.MOD_8PSK, "16apsk": capi.MOD_16APSK, "32apsk": capi.MOD_32APSK}[a.constellation]
     batch = min(a.batch, a.frames)
@@ -92,6 +99,17 @@ def main():
             for mul, shift in ((-7046029254386353131, 31), (-4658895280553007687, 29), (-7723592293110705685, 32)):
                 x = (x * mul) ^ ((x * mul) >> shift)
             return ((x >> 24) & 255).to(torch.uint8)
+    if a.iq:
+        iq_rows, iq_max = (batch, enc.n_syms) if a.pl == "off" else (1, batch * front.plframe_len + 90)
+        iq_gain = 10.0 ** (-a.iq_backoff / 20.0)
+        to_codes = IqConverter(a.iq, iq_gain, max_streams=iq_rows, max_samples=iq_max)
+        from_codes = IqConverter(a.iq, 1.0 / iq_gain, max_streams=iq_rows, max_samples=iq_max)
+        d_codes = torch.empty(iq_rows * iq_max * to_codes.bytes, dtype=torch.uint8, device="cuda")
+        d_iq_stats = torch.zeros((iq_rows, 3), dtype=torch.int64, device="cuda")  # {samples, clipped, energy} per row, added to by every batch
+
+        def through_codes(d_buf, n, rows):  # what an ADC or a recording of this format leaves of the channel output, in place
+            to_codes.pack_device(d_buf.data_ptr(), n, n, rows, d_codes.data_ptr(), n, d_stats=d_iq_stats.data_ptr(), stream=st)
+            from_codes.unpack_device(d_codes.data_ptr(), n, n, rows, d_buf.data_ptr(), n, stream=st)
     done, t0 = 0, time.time()
     while done < a.frames:
         nf = min(batch, a.frames - done)
@@ -105,6 +123,8 @@ def main():
                 awgn.work_device(d_syms.data_ptr(), enc.n_syms, enc.n_syms, nf, d_syms.data_ptr(), enc.n_syms, first_stream=done, first_index=0, stream=st)
             else:
                 d_syms[:nf].add_(torch.randn((nf, enc.n_syms, 2), dtype=torch.float32, device="cuda", generator=gen), alpha=sigma)
+            if a.iq:
+                through_codes(d_syms, enc.n_syms, nf)
         else:
             if framed != nf:  # the last batch may be shorter
                 framer.set_sequence([plsc] * nf)
@@ -116,6 +136,8 @@ def main():
                 awgn.work_device(d_pl.data_ptr(), n_pl, n_pl, 1, d_pl.data_ptr(), n_pl, first_stream=0, stream=st)  # the running position
             else:
                 d_pl[:n_pl].add_(torch.randn((n_pl, 2), dtype=torch.float32, device="cuda", generator=gen), alpha=sigma)
+            if a.iq:
+                through_codes(d_pl, n_pl, 1)
             front.work_device(d_pl.data_ptr(), nf, 1, d_cc.data_ptr(), d_cf.data_ptr(), d_syms.data_ptr(), st, plsc_decoded=d_plsc.data_ptr())
             plsc_err += (d_plsc[:nf] != plsc).sum()
         chain.work_device(d_syms.data_ptr(), nf, d_n0.data_ptr(), 1, d_msg.data_ptr(), 0, d_corr.data_ptr(), st)
@@ -136,6 +158,15 @@ def main():
     if a.noise == "device":
         out.update(noise="device")
         awgn.close()
+    if a.iq:
+        samples, clipped, energy = (int(v) for v in d_iq_stats.sum(dim=0).tolist())  # (the energy of a run stays far below 2^63)
+        unit = 256 if a.iq == "u8" else 128 if a.iq == "s8" else 32768
+        out.update(iq=a.iq, iq_backoff_db=a.iq_backoff, iq_clipped=clipped, iq_clipped_share=clipped / (2 * samples),
+                   iq_rms_of_full_scale=(energy / samples) ** 0.5 / unit)
+        print(f"iq {a.iq}: {clipped} of {2 * samples} components clipped ({100.0 * clipped / (2 * samples):.4f} %), "
+              f"rms {(energy / samples) ** 0.5 / unit:.4f} of full scale", file=sys.stderr)
+        to_codes.close()
+        from_codes.close()
     if a.pl != "off":
         out.update(pl=a.pl, gold=a.gold, plsc=plsc, plsc_errors=int(plsc_err.item()))
         framer.close()
