@@ -1,5 +1,6 @@
 // rotator_hip.hip -- see rotator_hip.h.
 #include "rotator_hip.h"
+#include "rotator_math.hpp"
 #include <algorithm>
 #include <cfloat>
 #include <climits>
@@ -29,14 +30,6 @@ struct RotSegs {
     int start[kSegs];      // relative to the launch, ascending; unused entries INT_MAX
     uint64_t phase[kSegs], inc[kSegs];
 };
-
-__device__ inline float2 rotate_one(float2 x, uint64_t ph)
-{
-    const float t = (float)(int32_t)(uint32_t)(ph >> 32) * 0x1p-31f; // half-turns in [-1, 1]
-    float s, c;
-    sincospif(t, &s, &c);
-    return make_float2(x.x * c - x.y * s, x.x * s + x.y * c);
-}
 
 template <bool kMulti> __device__ inline uint64_t phase_at(const RotSegs& g, int i)
 {

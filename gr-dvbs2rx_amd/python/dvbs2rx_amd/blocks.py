@@ -22,6 +22,7 @@ __all__ = ["get_fec_info", "rate_id", "LdpcDecoder", "BchDecoder", "Demapper", "
            "SymbolSync", "symsync_loop_constants", "symsync_geometry", "symsync_taps", "FecEncoder", "enc_check",
            "PlFramer", "plframer_layout", "PulseShaper", "pulse_geometry", "pulse_taps", "pulse_scale_taps",
            "Resampler", "resamp_step", "resamp_geometry", "resamp_max_out", "resamp_check",
+           "Ddc", "ddc_geometry", "ddc_produce", "ddc_check", "ddc_tile",
            "BbFramer", "bbheader_build", "crc8"]
 
 DEFAULT_TRIALS = 25  # reference lib/ldpc_decoder_bb_impl.cc:391
@@ -1516,3 +1517,98 @@ class Resampler(_Handle):
         check(lib.dvbs2_resamp_process_device(self._h, d_in or None, int(in_stride), int(n_in), int(n_streams), d_out or None, int(out_stride),
                                               n.ctypes.data if n.size else None, stream or None))
         return n
+
+
+def ddc_geometry(decim, ntaps):
+    """(history in mixed samples per channel, delay_num: the delay is delay_num / 2 input samples) (dvbs2_ddc_geometry). Host only."""
+    return _ints(2, lib.dvbs2_ddc_geometry, int(decim), int(ntaps))
+
+
+def ddc_produce(position, decim, n_in):
+    """What a call of n_in samples writes per channel when the sample counter stands at `position`:
+    ceil((position + n_in) / decim) - ceil(position / decim) (dvbs2_ddc_produce). Host only."""
+    n = lib.dvbs2_ddc_produce(int(position), int(decim), int(n_in))
+    check(min(n, 0))
+    return n
+
+
+def ddc_check(decim, taps, max_channels=1, max_inputs=1, max_samples=1 << 20):
+    """Raises what Ddc(...) would raise for these arguments, without a device (dvbs2_ddc_check)."""
+    t = np.ascontiguousarray(taps, np.float32).reshape(-1)
+    check(lib.dvbs2_ddc_check(int(decim), t.ctypes.data if t.size else None, int(t.size), int(max_channels), int(max_inputs), int(max_samples)))
+
+
+def ddc_tile(decim, ntaps):
+    """Output samples per workgroup of the down-converter's kernel: the tile rule of include/dvbs2_fec_hip.h. Host only."""
+    return min(capi.DDC_MAX_TILE, (capi.DDC_SPAN - (int(ntaps) - 1)) // int(decim))
+
+
+class Ddc(_Handle):
+    """Digital down-conversion: a frequency-translating decimating FIR with the caller's real `taps`. Channel c reads input stream
+    input[c], mixes it with its own phase increment (radians per input sample, the rotator's arithmetic), filters it and keeps every
+    decim-th sample; the last ntaps - 1 mixed samples and the phase of every channel stay on the device between calls (notes/ddc.md).
+    n samples in give produce(n) samples out per channel, delayed by delay_num / 2 input samples."""
+    _destroy = lib.dvbs2_ddc_destroy
+
+    def __init__(self, decim, taps, max_channels=1, max_inputs=1, max_samples=1 << 20, device=0):
+        t = np.ascontiguousarray(taps, np.float32).reshape(-1)
+        check(lib.dvbs2_ddc_create(C.byref(self._h), int(decim), t.ctypes.data if t.size else None, int(t.size), int(max_channels),
+                                   int(max_inputs), int(max_samples), device))
+        self.max_channels, self.max_inputs, self.max_samples = max_channels, max_inputs, max_samples
+        self.decim, self.ntaps, self.history, self.delay_num, self.tile = _ints(5, lib.dvbs2_ddc_params, self._h)
+
+    def set_channel(self, channel, phase_inc, input=0):
+        """From the next call on; the channel's phase is carried over."""
+        check(lib.dvbs2_ddc_set_channel(self._h, int(channel), int(input), float(phase_inc)))
+
+    def reset(self):
+        check(lib.dvbs2_ddc_reset(self._h))
+
+    def position(self):
+        """The sample counter, from the host's mirror."""
+        n = C.c_int64()
+        check(lib.dvbs2_ddc_position(self._h, C.byref(n)))
+        return n.value
+
+    def channel(self, channel):
+        """(input, increment, phase) of a channel from the host's mirror, the last two in 2^-64 turns."""
+        i, inc, ph = C.c_int(), C.c_uint64(), C.c_uint64()
+        check(lib.dvbs2_ddc_channel(self._h, int(channel), C.byref(i), C.byref(inc), C.byref(ph)))
+        return i.value, inc.value, ph.value
+
+    def produce(self, n_in):
+        """What the next call of n_in samples writes per channel. From the host's mirror: no synchronisation."""
+        return ddc_produce(self.position(), self.decim, n_in)
+
+    def state(self):
+        """uint64 [max_channels]: the DEVICE's phases in 2^-64 turns. Synchronous."""
+        ph = np.zeros(self.max_channels, np.uint64)
+        check(lib.dvbs2_ddc_state(self._h, ph.ctypes.data))
+        return ph
+
+    def work(self, samples, n_channels=None):
+        """HOST buffer: complex64 [n_inputs, n_in] (or a vector: one input). Returns complex64 [n_channels, produce(n_in)]."""
+        x = np.asarray(samples)
+        if x.dtype != np.complex64:
+            raise TypeError(f"samples must be complex64, not {x.dtype}")
+        if x.ndim == 1:
+            x = x.reshape(1, -1)
+        if x.ndim != 2 or not x.flags.c_contiguous:
+            raise ValueError("samples must be a C-contiguous vector or [n_inputs, n_in] matrix")
+        nc = self.max_channels if n_channels is None else int(n_channels)
+        n_inputs, n_in = x.shape
+        stride = max(self.produce(n_in), 1) if n_in <= self.max_samples else 1
+        out = np.empty((max(nc, 1), stride), np.complex64)
+        n = C.c_int64()
+        check(lib.dvbs2_ddc_process(self._h, x.ctypes.data if x.size else None, int(n_in), int(n_in), int(n_inputs), nc, out.ctypes.data,
+                                    int(stride), C.byref(n)))
+        return out[:nc, :n.value]
+
+    def work_device(self, d_in, in_stride, n_in, n_inputs, n_channels, d_out, out_stride, stream=0):
+        """DEVICE addresses (8-byte aligned, not overlapping), asynchronous on `stream`: channel c reads n_in complex64 samples at
+        d_in + 8 * input[c] * in_stride and writes n_out samples at d_out + 8 * c * out_stride; out_stride >= n_out. Returns n_out (what
+        produce() said before the call). One call in flight per handle."""
+        n = C.c_int64()
+        check(lib.dvbs2_ddc_process_device(self._h, d_in or None, int(in_stride), int(n_in), int(n_inputs), int(n_channels), d_out or None,
+                                           int(out_stride), C.byref(n), stream or None))
+        return n.value

@@ -27,6 +27,8 @@ MOD_QPSK, MOD_8PSK, MOD_16APSK, MOD_32APSK = 0, 4, 6, 8
 ENC_NO_MAPPER = -1
 PULSE_TILE = 512  # DVBS2_PULSE_TILE: symbols per workgroup of the pulse shaper's kernel
 RESAMP_TILE = 1024  # DVBS2_RESAMP_TILE: output samples per workgroup of the resampler's kernel
+DDC_SPAN, DDC_MAX_TILE = 9216, 1024  # DVBS2_DDC_SPAN, DVBS2_DDC_MAX_TILE: a workgroup of the down-converter's kernel stages at most DDC_SPAN
+# mixed samples and writes min(DDC_MAX_TILE, (DDC_SPAN - (ntaps - 1)) // decim) output samples
 AGC_TILE = 64  # DVBS2_AGC_TILE: samples per stream and tile of the AGC's kernel
 AWGN_TILE = 512  # DVBS2_AWGN_TILE: samples of a row per workgroup of the AWGN channel's kernel
 IQ_U8, IQ_S8, IQ_S16 = 0, 1, 2  # DVBS2_IQ_*: the code formats of the IQ sample converter
@@ -251,6 +253,19 @@ SYMBOLS = {
     "dvbs2_resamp_state": (_i, [_vp, _vp]),
     "dvbs2_resamp_process_device": (_i, [_vp, _vp, C.c_int64, _i, _i, _vp, C.c_int64, _vp, _vp]),
     "dvbs2_resamp_process": (_i, [_vp, _vp, _i, _vp, C.c_int64, C.POINTER(C.c_int64)]),
+    "dvbs2_ddc_geometry": (_i, [_i, _i, _ip, _ip]),
+    "dvbs2_ddc_produce": (C.c_int64, [C.c_int64, _i, _i]),
+    "dvbs2_ddc_check": (_i, [_i, _vp, _i, _i, _i, _i]),
+    "dvbs2_ddc_create": (_i, [C.POINTER(_vp), _i, _vp, _i, _i, _i, _i, _i]),
+    "dvbs2_ddc_destroy": (None, [_vp]),
+    "dvbs2_ddc_reset": (_i, [_vp]),
+    "dvbs2_ddc_set_channel": (_i, [_vp, _i, _i, C.c_double]),
+    "dvbs2_ddc_params": (_i, [_vp, _ip, _ip, _ip, _ip, _ip]),
+    "dvbs2_ddc_position": (_i, [_vp, C.POINTER(C.c_int64)]),
+    "dvbs2_ddc_channel": (_i, [_vp, _i, _ip, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "dvbs2_ddc_state": (_i, [_vp, _vp]),
+    "dvbs2_ddc_process_device": (_i, [_vp, _vp, C.c_int64, _i, _i, _i, _vp, C.c_int64, C.POINTER(C.c_int64), _vp]),
+    "dvbs2_ddc_process": (_i, [_vp, _vp, C.c_int64, _i, _i, _i, _vp, C.c_int64, C.POINTER(C.c_int64)]),
     "dvbs2_bbdeheader_create": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i]),
     "dvbs2_bbdeheader_create_raw": (_i, [C.POINTER(_vp), _i, _i, _i]),
     "dvbs2_bbdeheader_destroy": (None, [_vp]),

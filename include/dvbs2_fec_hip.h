@@ -1022,6 +1022,74 @@ int dvbs2_resamp_process_device(dvbs2_resamp_t* h, const float* d_in, int64_t in
 /* host pointers, synchronous: stream 0 of the handle, staged through buffers of the handle; out_cap in complex elements */
 int dvbs2_resamp_process(dvbs2_resamp_t* h, const float* in, int n_in, float* out, int64_t out_cap, int64_t* n_out);
 
+/* ---- digital down-conversion: a frequency-translating decimating FIR with real taps, the way from a wideband capture to baseband
+ * streams at 2 samples per symbol. One handle turns up to max_inputs sample streams into up to max_channels channels: channel c reads
+ * input stream input[c] (0 until set), mixes it with its own phase increment inc[c] (radians per input sample, 0 until set), filters it
+ * with the handle's taps h[0 .. ntaps) and keeps every decim-th sample. It is GNU Radio's freq_xlating_fir_filter_ccf, or a rotator
+ * followed by fir_filter_ccf with decimation; neither is in the reference tree: the stage is UNPINNED against it. It is the mirror image
+ * of dvbs2_pulse_* and reuses the phase of dvbs2_rotator_*. What is defined, and tested bit for bit against a float32 restatement
+ * (tests/ddc_model.py) applied to the output of dvbs2_rotator_rotate_device, is this:
+ *   MIX. z[n] = x[n] e^{j phi_c(n)} with the rotator's arithmetic: the phase in turns as unsigned 64-bit fixed point,
+ *   phi_c(n) = P_c + (n - n_call) I_c in wrapping integer arithmetic, n_call the first sample of the call, I_c the increment converted
+ *   once as the rotator converts it; the upper 32 bits as a float in half-turns go to sincospif; four products, a subtraction, an
+ *   addition, nothing fused. inc == 0 is no special case.
+ *   FILTER AND DECIMATE. Output k (absolute, k >= 0) is y[k] = sum over t = 0 .. ntaps - 1 of h[t] z[k decim - t], real and imaginary
+ *   part apart, each term a float product and then a float addition, t ascending, onto an accumulator that starts at +0.0f. z[n] for
+ *   n < 0 is zero after create / reset.
+ *   COUNTS. All inputs and channels of a handle share one 64-bit sample counter n0, zero after create / reset; every input stream of a
+ *   call has n_in samples. The call writes, for every channel, the outputs k with n0 <= k decim < n0 + n_in:
+ *   n_out = ceil((n0 + n_in) / decim) - ceil(n0 / decim), and leaves n0' = n0 + n_in and P_c' = P_c + n_in I_c for the channels of the
+ *   call. The first output of a stream uses its first sample.
+ *   STATE. Per channel the last ntaps - 1 MIXED samples stay on the device, so the stage equals "rotator, then decimating FIR" bit for
+ *   bit however the stream is cut into calls and whenever increments change between calls (dvbs2_ddc_set_channel: from the next call
+ *   on, the phase continuous). A call on fewer than max_channels channels leaves the state of the others alone.
+ * The signal is delayed by (ntaps - 1) / 2 input samples (delay_num = ntaps - 1 halves of an input sample). The taps are the caller's:
+ * with decim = sps / 2, dvbs2_pulse_taps(sps, rolloff, D, 0, 1) is the matched filter of a carrier at sps samples per symbol.
+ * The host keeps a mirror of the counter and of every phase (plain integer arithmetic): dvbs2_ddc_position and dvbs2_ddc_channel read
+ * it, and the call reports n_out (nullable), all without a synchronisation; dvbs2_ddc_state copies the DEVICE's phases back
+ * (synchronous, max_channels values).
+ * Channel c of a call reads n_in samples at d_in + input[c] in_stride and writes n_out samples at d_out + c out_stride; data are
+ * interleaved (re, im) floats, strides count complex elements, buffers are 8-byte aligned and must NOT overlap (not detected); the input
+ * is never written. in_stride matters when n_inputs > 1; out_stride is also the capacity of every channel's output. Two launches per
+ * call (the samples, then the new histories and phases; the first call behind a dvbs2_ddc_set_channel also copies the channel table on
+ * the stream), no allocation, no host synchronisation. ONE CALL IN FLIGHT PER HANDLE, as for dvbs2_pulse_*. A workgroup writes
+ * min(DVBS2_DDC_MAX_TILE, (DVBS2_DDC_SPAN - (ntaps - 1)) / decim) consecutive output samples of one channel.
+ * Refused with DVBS2_ESIZE: n_in > max_samples, n_inputs > max_inputs, n_channels > max_channels. Refused with DVBS2_EINVAL and a text
+ * that names the argument: negative counts, a null buffer with n_in > 0 and n_channels > 0, buffers that are not 8-byte aligned, with
+ * n_inputs > 1 an in_stride < n_in, an out_stride < n_out, a channel of the call whose input is not below n_inputs. A refused call leaves
+ * output, histories, phases and mirror untouched. n_in == 0 is a successful call that does nothing; n_channels == 0 only advances the
+ * counter. Creation refuses (DVBS2_EINVAL) decim outside 1..256, ntaps outside 1..4096, a tap that is not finite, max_channels or
+ * max_inputs outside 1..65535, max_samples outside 1..2^24.
+ * Host only, no device needed: dvbs2_ddc_geometry (history = ntaps - 1, delay_num = ntaps - 1; each nullable), dvbs2_ddc_produce (the
+ * count rule for a counter at `position`; -1 when position is negative or above 2^62, decim or n_in out of range) and dvbs2_ddc_check
+ * (the argument check of dvbs2_ddc_create). ---- */
+typedef struct dvbs2_ddc dvbs2_ddc_t;
+#define DVBS2_DDC_SPAN 9216
+#define DVBS2_DDC_MAX_TILE 1024
+int dvbs2_ddc_geometry(int decim, int ntaps, int* history, int* delay_num);
+int64_t dvbs2_ddc_produce(int64_t position, int decim, int n_in);
+int dvbs2_ddc_check(int decim, const float* taps, int ntaps, int max_channels, int max_inputs, int max_samples);
+int dvbs2_ddc_create(dvbs2_ddc_t** h, int decim, const float* taps, int ntaps, int max_channels, int max_inputs, int max_samples,
+                     int device);
+void dvbs2_ddc_destroy(dvbs2_ddc_t* h);
+/* counter 0, phases 0, histories zero; the channel table (inputs and increments) stays; synchronous (waits for the device) */
+int dvbs2_ddc_reset(dvbs2_ddc_t* h);
+/* host only; phase_inc in radians per input sample, any finite value */
+int dvbs2_ddc_set_channel(dvbs2_ddc_t* h, int channel, int input, double phase_inc);
+/* each nullable; tile: output samples per workgroup */
+int dvbs2_ddc_params(const dvbs2_ddc_t* h, int* decim, int* ntaps, int* history, int* delay_num, int* tile);
+/* host only, from the mirror */
+int dvbs2_ddc_position(const dvbs2_ddc_t* h, int64_t* counter);
+/* host only, from the mirror, each nullable: the channel's input, its increment and its phase in 2^-64 turns */
+int dvbs2_ddc_channel(const dvbs2_ddc_t* h, int channel, int* input, uint64_t* inc_turns, uint64_t* phase_turns);
+int dvbs2_ddc_state(dvbs2_ddc_t* h, uint64_t* phases);
+/* DEVICE pointers, asynchronous on `stream`; n_out is a HOST value, filled before the call returns */
+int dvbs2_ddc_process_device(dvbs2_ddc_t* h, const float* d_in, int64_t in_stride, int n_in, int n_inputs, int n_channels, float* d_out,
+                             int64_t out_stride, int64_t* n_out, void* stream);
+/* host pointers, synchronous, staged through buffers of the handle; the same arguments and checks */
+int dvbs2_ddc_process(dvbs2_ddc_t* h, const float* in, int64_t in_stride, int n_in, int n_inputs, int n_channels, float* out,
+                      int64_t out_stride, int64_t* n_out);
+
 /* ---- downstream neighbour: BBFRAME de-header, replaces bbdeheader_bb_impl::general_work (reference
  * lib/bbdeheader_bb_impl.cc:144-264) with parse_bbheader (:77-136) and check_crc8 (:138-142, generator
  * x^8 + x^7 + x^6 + x^4 + x^2 + 1, :55). Input: whole descrambled BBFRAMEs of kbch / 8 bytes (what dvbs2_bch_decode /
