@@ -52,7 +52,7 @@ public:
     int set_gain(int stream_index, float g); // synchronous; -1: every stream
     int state(float* gains, int n_streams);  // waits for the device
     // DEVICE pointers, samples 8-byte and gains 4-byte aligned, strides in elements; d_gain nullable; d_out == d_in with equal strides
-    // is allowed. One launch, asynchronous on `stream`. The entry (c_api_stream.hip) checks the arguments. One call in flight per
+    // is allowed. One launch, asynchronous on `stream`. The entry (c_api_agc.hip) checks the arguments. One call in flight per
     // handle: a call reads the gains and writes them back.
     int work_device(const float* d_in, int64_t in_stride, int n_samples, int n_streams, float* d_out, int64_t out_stride, float* d_gain,
                     int64_t gain_stride, hipStream_t stream);

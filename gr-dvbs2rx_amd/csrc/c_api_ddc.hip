@@ -1,6 +1,5 @@
 // c_api_ddc.hip -- extern "C" boundary (include/dvbs2_fec_hip.h): digital down-conversion, a frequency-translating decimating FIR over a
-// batch of channels. A translation unit of its own, as c_api_resamp.hip, because tests/test_agc_host.py links c_api_stream.hip with a
-// fixed list of the stage sources it binds.
+// batch of channels.
 #include <algorithm>
 #include "c_api_common.h"
 #include "ddc_hip.h"

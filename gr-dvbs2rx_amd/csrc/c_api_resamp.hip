@@ -1,6 +1,4 @@
-// c_api_resamp.hip -- extern "C" boundary (include/dvbs2_fec_hip.h): arbitrary-rate resampling of a running stream. The other stream
-// stages are bound in c_api_stream.hip; this one has a translation unit of its own because tests/test_agc_host.py links that file with a
-// fixed list of the stage sources it binds.
+// c_api_resamp.hip -- extern "C" boundary (include/dvbs2_fec_hip.h): arbitrary-rate resampling of a running stream.
 #include <algorithm>
 #include <vector>
 #include "c_api_common.h"

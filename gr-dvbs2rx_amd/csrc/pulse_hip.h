@@ -48,7 +48,7 @@ public:
     int max_streams() const { return max_streams_; }
     int max_symbols() const { return max_symbols_; }
     int reset(); // synchronous: waits for the device, then clears every history
-    // DEVICE pointers, 8-byte aligned, strides in complex elements; two launches, asynchronous on `stream`. The entry (c_api_stream.hip)
+    // DEVICE pointers, 8-byte aligned, strides in complex elements; two launches, asynchronous on `stream`. The entry (c_api_pulse.hip)
     // checks the arguments. One call in flight per handle: the histories are read by a call and rewritten behind it, so a second call on
     // ANOTHER stream needs the first to have finished; calls on the same stream may follow each other.
     int shape_device(const float* d_in, int64_t in_stride, int n_syms, int n_streams, float* d_out, int64_t out_stride, hipStream_t stream);

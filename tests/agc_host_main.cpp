@@ -1,6 +1,6 @@
 // stdin rows -> one line each. Drives the host-only side of the AGC's C ABI (dvbs2_agc_check, and every dvbs2_agc_* entry with a null
 // handle) outside Python, so that it can be built with -fsanitize=address,undefined together with the sources behind the entries
-// (csrc/c_api_stream.hip and the stage sources it binds). No device code runs and no GPU call is made: every row is answered before a
+// (csrc/c_api_agc.hip and csrc/agc_hip.hip, which it binds). No device code runs and no GPU call is made: every row is answered before a
 // device is looked for. Floats travel as the hexadecimal bits of a float32, so they arrive exactly.
 //   check rate reference gain max_gain                      -> "ok" or "refused -1: <text>"
 //   create rate reference gain max_gain max_streams max_samples -> "refused <code>: <text>" (only refused rows are sent)

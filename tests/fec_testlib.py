@@ -256,6 +256,18 @@ def build_ldpc_planner(out_dir, main=None):
     return exe
 
 
+def build_host_program(tmp_dir, main_cpp, sources, fp_contract_off=True):
+    """tests/<main_cpp> with the csrc/ sources it calls, as a stand-alone program in tmp_dir: host code under AddressSanitizer and UBSan
+    (device code is not instrumented and none of it runs). Returns the program's path."""
+    csrc = os.path.join(ROOT, "gr-dvbs2rx_amd", "csrc")
+    exe = os.path.join(str(tmp_dir), os.path.splitext(main_cpp)[0])
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined"]
+    subprocess.check_call([hipcc, "-x", "hip", "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", *(["-ffp-contract=off"] if fp_contract_off else []),
+                           *san, os.path.join(ROOT, "tests", main_cpp), *[os.path.join(csrc, s) for s in sources], "-o", exe])
+    return exe
+
+
 def run_ldpc_planner(exe, rows, group_size=32):
     """rows: (table, {override: value}). One dict per row: {"error": text}, or name / dmax / words_per_check / pr_shared_sv / lds_bytes /
     gsync_on, `check` (first broken format invariant, "" = none) and recs / wrecs, the truncated sha256 of the record words."""
@@ -278,6 +290,68 @@ def run_ldpc_planner(exe, rows, group_size=32):
                       "check": f[8] if len(f) > 8 else "", "recs": hashlib.sha256(recs).hexdigest()[:12], "wrecs": hashlib.sha256(wrecs).hexdigest()[:12]})
     assert len(plans) == len(rows)
     return plans
+
+
+# ------------------------------------------------------------------ device buffers of the stage tests (torch is imported where it is used)
+SENTINEL = 0xC3A55A3C  # a bit pattern no output of the stage tests holds
+PAD = 64               # sentinel elements behind the last output of run_strided
+
+
+def stream():
+    import torch
+    return torch.cuda.current_stream().cuda_stream
+
+
+def sentinel(n_words):
+    """n_words 32-bit words of SENTINEL on the device, as int32 (torch has no uint32 arithmetic worth the name); a complex element is two"""
+    import torch
+    return torch.full((n_words,), np.uint32(SENTINEL).astype(np.int32).item(), dtype=torch.int32, device="cuda")
+
+
+def refused(code, text, entry, *args):
+    """the C entry answers `code` and leaves exactly `text` behind"""
+    from dvbs2rx_amd import capi
+    assert entry(*args) == code, (entry.__name__, capi.lib.dvbs2_last_error())
+    assert capi.lib.dvbs2_last_error() == text.encode(), capi.lib.dvbs2_last_error()
+
+
+def same_bits(got, want_bits, what):
+    """got: uint32 (n, 2) complex samples read back from the device; want_bits: the model's samples as uint32 (the model's bits())"""
+    w = want_bits.reshape(-1, 2)
+    assert got.shape[0] == w.shape[0], (what, got.shape[0], w.shape[0])
+    if not np.array_equal(got, w):
+        bad = np.nonzero((got != w).any(axis=1))[0]
+        raise AssertionError(f"{what}: {bad.size} of {w.shape[0]} samples differ, the first at {bad[0]}: {got[bad[0]]} != {w[bad[0]]}")
+
+
+def run_strided(call, xs, counts, in_stride, out_stride, in_shift=0, out_shift=0):
+    """One device call over the input streams xs (complex64 vectors of one length) into len(counts) outputs. Input i lies at in_shift +
+    i * in_stride complex elements of a 16-byte-aligned buffer; output s is counts[s] elements at out_shift + s * out_stride of a
+    16-byte-aligned sentinel buffer. call(in_ptr, out_ptr) makes the call. Returns (one uint32 (counts[s], 2) array per output, what call
+    returned) after checking that everything else in the output buffer -- the shift in front, what lies between and behind the outputs and
+    PAD elements behind the last stride -- is still the sentinel, and that the input is unchanged."""
+    import torch
+    n = xs[0].size
+    host_in = np.full(in_shift + len(xs) * in_stride + 2, np.complex64(complex(9.5, -9.5)), np.complex64)
+    for i, x in enumerate(xs):
+        assert x.size == n
+        host_in[in_shift + i * in_stride:in_shift + i * in_stride + n] = x
+    d_in = torch.from_numpy(host_in.view(np.float32)).cuda()
+    n_buf = out_shift + max(len(counts), 1) * out_stride + PAD
+    d_out = sentinel(2 * n_buf)
+    assert d_in.data_ptr() % 16 == 0 and d_out.data_ptr() % 16 == 0
+    ret = call(d_in.data_ptr() + 8 * in_shift, d_out.data_ptr() + 8 * out_shift)
+    torch.cuda.synchronize()
+    got = d_out.cpu().numpy().view(np.uint32).reshape(-1, 2)
+    assert np.array_equal(d_in.cpu().numpy().view(np.uint32), host_in.view(np.uint32)), "the input was written"
+    touched = np.zeros(n_buf, bool)
+    outs = []
+    for s, k in enumerate(counts):
+        a = out_shift + s * out_stride
+        touched[a:a + k] = True
+        outs.append(got[a:a + k])
+    assert (got[~touched] == SENTINEL).all(), "a write outside the outputs"
+    return outs, ret
 
 
 # ------------------------------------------------------------------ input generators

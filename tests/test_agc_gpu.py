@@ -8,30 +8,14 @@ import numpy as np
 import pytest
 
 import agc_model as AM
-import plframe_model as M
-import plsync_model as P
-from dvbs2rx_amd import (Agc, FecChain, FecEncoder, PlCoarse, PlFramer, PlFrontEnd, PlSync, PulseShaper, SymbolSync, capi, plframer_layout,
-                         pulse_taps, symsync_taps)
+import loopback as L
+from dvbs2rx_amd import Agc, capi
+from fec_testlib import SENTINEL, refused, sentinel, stream
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0xC3A55A3C  # a bit pattern no output of these tests holds
 PAD = 64               # sentinel elements behind the last stream
 T = capi.AGC_TILE      # the kernel's tile in samples
-
-
-def _torch():
-    import torch
-    return torch
-
-
-def stream():
-    return _torch().cuda.current_stream().cuda_stream
-
-
-def sentinel(n_words):
-    torch = _torch()
-    return torch.full((n_words,), np.uint32(SENTINEL).astype(np.int32).item(), dtype=torch.int32, device="cuda")
 
 
 def run(agc, x, with_gain=True, in_stride=None, out_stride=None, gain_stride=None, in_shift=0, out_shift=0, in_place=False):
@@ -39,7 +23,7 @@ def run(agc, x, with_gain=True, in_stride=None, out_stride=None, gain_stride=Non
     16-byte-aligned input buffer and is written at out_shift + s * out_stride of a 16-byte-aligned sentinel buffer (in place: into the
     input buffer), its gains at s * gain_stride floats of a third. Returns (uint32 [ns, 2 n] samples, uint32 [ns, n] gains or None) after
     checking that everything else in the buffers is still what it was."""
-    torch = _torch()
+    import torch
     ns, n = x.shape
     in_stride = max(n, 1) if in_stride is None else in_stride
     out_stride = (in_stride if in_place else max(n, 1)) if out_stride is None else out_stride
@@ -268,24 +252,19 @@ def test_host_entry_equals_the_device_entry():
 
 
 # ------------------------------------------------------------------ 7. refusals
-def _refused(code, text, entry, *args):
-    assert entry(*args) == code, (entry.__name__, capi.lib.dvbs2_last_error())
-    assert capi.lib.dvbs2_last_error() == text.encode(), capi.lib.dvbs2_last_error()
-
-
 def test_refusals_leave_gains_and_output_untouched():
-    torch = _torch()
+    import torch
     lib, h = capi.lib, C.c_void_p()
     create = lib.dvbs2_agc_create
-    _refused(capi.EINVAL, "rate must be finite and not negative", create, C.byref(h), -1e-5, 1.0, 1.0, 1.0, 1, 16, 0)
-    _refused(capi.EINVAL, "reference must be finite", create, C.byref(h), 1e-5, float("inf"), 1.0, 1.0, 1, 16, 0)
-    _refused(capi.EINVAL, "gain must be finite", create, C.byref(h), 1e-5, 1.0, float("nan"), 1.0, 1, 16, 0)
-    _refused(capi.EINVAL, "max_gain must be finite and not negative (0: no cap)", create, C.byref(h), 1e-5, 1.0, 1.0, -1.0, 1, 16, 0)
-    _refused(capi.EINVAL, "max_streams out of range (1..65535)", create, C.byref(h), 1e-5, 1.0, 1.0, 1.0, 0, 16, 0)
-    _refused(capi.EINVAL, "max_streams out of range (1..65535)", create, C.byref(h), 1e-5, 1.0, 1.0, 1.0, 65536, 16, 0)
-    _refused(capi.EINVAL, "max_samples out of range (1..2^30)", create, C.byref(h), 1e-5, 1.0, 1.0, 1.0, 1, 0, 0)
-    _refused(capi.EINVAL, "max_samples out of range (1..2^30)", create, C.byref(h), 1e-5, 1.0, 1.0, 1.0, 1, (1 << 30) + 1, 0)
-    _refused(capi.EINVAL, "null handle pointer", create, None, 1e-5, 1.0, 1.0, 1.0, 1, 16, 0)
+    refused(capi.EINVAL, "rate must be finite and not negative", create, C.byref(h), -1e-5, 1.0, 1.0, 1.0, 1, 16, 0)
+    refused(capi.EINVAL, "reference must be finite", create, C.byref(h), 1e-5, float("inf"), 1.0, 1.0, 1, 16, 0)
+    refused(capi.EINVAL, "gain must be finite", create, C.byref(h), 1e-5, 1.0, float("nan"), 1.0, 1, 16, 0)
+    refused(capi.EINVAL, "max_gain must be finite and not negative (0: no cap)", create, C.byref(h), 1e-5, 1.0, 1.0, -1.0, 1, 16, 0)
+    refused(capi.EINVAL, "max_streams out of range (1..65535)", create, C.byref(h), 1e-5, 1.0, 1.0, 1.0, 0, 16, 0)
+    refused(capi.EINVAL, "max_streams out of range (1..65535)", create, C.byref(h), 1e-5, 1.0, 1.0, 1.0, 65536, 16, 0)
+    refused(capi.EINVAL, "max_samples out of range (1..2^30)", create, C.byref(h), 1e-5, 1.0, 1.0, 1.0, 1, 0, 0)
+    refused(capi.EINVAL, "max_samples out of range (1..2^30)", create, C.byref(h), 1e-5, 1.0, 1.0, 1.0, 1, (1 << 30) + 1, 0)
+    refused(capi.EINVAL, "null handle pointer", create, None, 1e-5, 1.0, 1.0, 1.0, 1, 16, 0)
     assert not h
     assert create(C.byref(h), 1e-5, 1.0, 1.0, 1.0, 1, 16, 99) < 0 and not h  # no such device
 
@@ -298,26 +277,26 @@ def test_refusals_leave_gains_and_output_untouched():
     st = stream()
     a, o, g = d_in.data_ptr(), d_out.data_ptr(), d_gain.data_ptr()
     entry = lib.dvbs2_agc_work_device
-    _refused(capi.ESIZE, "n_samples exceeds max_samples", entry, agc._h, a, n, n + 1, 1, o, n, g, n, st)
-    _refused(capi.ESIZE, "n_streams exceeds max_streams", entry, agc._h, a, n, n, 3, o, n, g, n, st)
-    _refused(capi.EINVAL, "n_samples is negative", entry, agc._h, a, n, -1, 2, o, n, g, n, st)
-    _refused(capi.EINVAL, "n_streams is negative", entry, agc._h, a, n, n, -1, o, n, g, n, st)
-    _refused(capi.EINVAL, "in is null", entry, agc._h, None, n, n, 2, o, n, g, n, st)
-    _refused(capi.EINVAL, "out is null", entry, agc._h, a, n, n, 2, None, n, g, n, st)
-    _refused(capi.EINVAL, "in and out must be 8-byte aligned", entry, agc._h, a + 4, n, n, 2, o, n, g, n, st)
-    _refused(capi.EINVAL, "in and out must be 8-byte aligned", entry, agc._h, a, n, n, 2, o + 4, n, g, n, st)
-    _refused(capi.EINVAL, "gain must be 4-byte aligned", entry, agc._h, a, n, n, 2, o, n, g + 2, n, st)
-    _refused(capi.EINVAL, "in_stride is below n_samples", entry, agc._h, a, n - 1, n, 2, o, n, g, n, st)
-    _refused(capi.EINVAL, "out_stride is below n_samples", entry, agc._h, a, n, n, 2, o, n - 1, g, n, st)
-    _refused(capi.EINVAL, "gain_stride is below n_samples", entry, agc._h, a, n, n, 2, o, n, g, n - 1, st)
-    _refused(capi.EINVAL, "rate must be finite and not negative", lib.dvbs2_agc_set_params, agc._h, float("nan"), 1.0, 1.0)
-    _refused(capi.EINVAL, "max_gain must be finite and not negative (0: no cap)", lib.dvbs2_agc_set_params, agc._h, 0.05, 1.0, -2.0)
-    _refused(capi.EINVAL, "stream index out of range", lib.dvbs2_agc_set_gain, agc._h, 2, 1.0)
-    _refused(capi.EINVAL, "stream index out of range", lib.dvbs2_agc_set_gain, agc._h, -2, 1.0)
-    _refused(capi.EINVAL, "gain must be finite", lib.dvbs2_agc_set_gain, agc._h, 0, float("inf"))
+    refused(capi.ESIZE, "n_samples exceeds max_samples", entry, agc._h, a, n, n + 1, 1, o, n, g, n, st)
+    refused(capi.ESIZE, "n_streams exceeds max_streams", entry, agc._h, a, n, n, 3, o, n, g, n, st)
+    refused(capi.EINVAL, "n_samples is negative", entry, agc._h, a, n, -1, 2, o, n, g, n, st)
+    refused(capi.EINVAL, "n_streams is negative", entry, agc._h, a, n, n, -1, o, n, g, n, st)
+    refused(capi.EINVAL, "in is null", entry, agc._h, None, n, n, 2, o, n, g, n, st)
+    refused(capi.EINVAL, "out is null", entry, agc._h, a, n, n, 2, None, n, g, n, st)
+    refused(capi.EINVAL, "in and out must be 8-byte aligned", entry, agc._h, a + 4, n, n, 2, o, n, g, n, st)
+    refused(capi.EINVAL, "in and out must be 8-byte aligned", entry, agc._h, a, n, n, 2, o + 4, n, g, n, st)
+    refused(capi.EINVAL, "gain must be 4-byte aligned", entry, agc._h, a, n, n, 2, o, n, g + 2, n, st)
+    refused(capi.EINVAL, "in_stride is below n_samples", entry, agc._h, a, n - 1, n, 2, o, n, g, n, st)
+    refused(capi.EINVAL, "out_stride is below n_samples", entry, agc._h, a, n, n, 2, o, n - 1, g, n, st)
+    refused(capi.EINVAL, "gain_stride is below n_samples", entry, agc._h, a, n, n, 2, o, n, g, n - 1, st)
+    refused(capi.EINVAL, "rate must be finite and not negative", lib.dvbs2_agc_set_params, agc._h, float("nan"), 1.0, 1.0)
+    refused(capi.EINVAL, "max_gain must be finite and not negative (0: no cap)", lib.dvbs2_agc_set_params, agc._h, 0.05, 1.0, -2.0)
+    refused(capi.EINVAL, "stream index out of range", lib.dvbs2_agc_set_gain, agc._h, 2, 1.0)
+    refused(capi.EINVAL, "stream index out of range", lib.dvbs2_agc_set_gain, agc._h, -2, 1.0)
+    refused(capi.EINVAL, "gain must be finite", lib.dvbs2_agc_set_gain, agc._h, 0, float("inf"))
     gains = np.zeros(4, np.float32)
-    _refused(capi.EINVAL, "n_streams out of range (1..max_streams)", lib.dvbs2_agc_state, agc._h, gains.ctypes.data, 3)
-    _refused(capi.EINVAL, "gains is null", lib.dvbs2_agc_state, agc._h, None, 1)
+    refused(capi.EINVAL, "n_streams out of range (1..max_streams)", lib.dvbs2_agc_state, agc._h, gains.ctypes.data, 3)
+    refused(capi.EINVAL, "gains is null", lib.dvbs2_agc_state, agc._h, None, 1)
     assert entry(agc._h, None, 0, 0, 2, None, 0, None, 0, st) == capi.OK  # n_samples == 0: a successful call that does nothing
     assert entry(agc._h, a, 0, 0, 2, o, 0, g, 0, st) == capi.OK
     assert agc.params()["rate"] == np.float32(0.05) and agc.params()["max_gain"] == np.float32(65536.0)
@@ -331,10 +310,10 @@ def test_refusals_leave_gains_and_output_untouched():
     assert (out[2 * n:] == SENTINEL).all() and (gg[n:] == SENTINEL).all()  # no refused call wrote anything
     # the host entry makes the same checks
     host_in, host_out = np.ascontiguousarray(second[0]), np.zeros(n, np.complex64)
-    _refused(capi.ESIZE, "n_samples exceeds max_samples", lib.dvbs2_agc_work, agc._h, host_in.ctypes.data, n + 1, host_out.ctypes.data, None)
-    _refused(capi.EINVAL, "n_samples is negative", lib.dvbs2_agc_work, agc._h, host_in.ctypes.data, -1, host_out.ctypes.data, None)
-    _refused(capi.EINVAL, "in is null", lib.dvbs2_agc_work, agc._h, None, n, host_out.ctypes.data, None)
-    _refused(capi.EINVAL, "out is null", lib.dvbs2_agc_work, agc._h, host_in.ctypes.data, n, None, None)
+    refused(capi.ESIZE, "n_samples exceeds max_samples", lib.dvbs2_agc_work, agc._h, host_in.ctypes.data, n + 1, host_out.ctypes.data, None)
+    refused(capi.EINVAL, "n_samples is negative", lib.dvbs2_agc_work, agc._h, host_in.ctypes.data, -1, host_out.ctypes.data, None)
+    refused(capi.EINVAL, "in is null", lib.dvbs2_agc_work, agc._h, None, n, host_out.ctypes.data, None)
+    refused(capi.EINVAL, "out is null", lib.dvbs2_agc_work, agc._h, host_in.ctypes.data, n, None, None)
     assert lib.dvbs2_agc_work(agc._h, None, 0, None, None) == capi.OK
     assert (host_out == 0).all()
     # no refusal touched a gain: both streams go on from where the good calls left them
@@ -346,104 +325,30 @@ def test_refusals_leave_gains_and_output_untouched():
 SCALE = 1.0 / 37.0
 
 
-def transmit(lead=2001):
-    """The transmit side of tests/test_pulse_gpu.py::test_closed_loop_through_the_receiver (QPSK 1/4 short, six data frames with dummies,
-    tau 0.3, sps 2) behind `lead` random QPSK symbols. Returns a dict with the shaped samples on the device and what the receiver's answers
-    are compared with."""
-    torch = _torch()
-    sps, rolloff, rrc_delay, tau = 2, 0.2, 5, 0.3
-    gold, plsc, dummy, nd = 5, P.plsc_of(1, 1, 1), P.plsc_of(0, 0, 0), 6
-    rng = np.random.default_rng(2027)
-    st = stream()
-    enc = FecEncoder(capi.STANDARD_DVBS2, capi.FECFRAME_SHORT, "C1_4", capi.MOD_QPSK, max_frames=nd)
-    enc.set_scramble(True)
-    sent = rng.integers(0, 256, (nd, enc.in_bytes), dtype=np.uint8)
-    seq = [plsc, plsc, dummy, plsc, plsc, dummy, plsc, plsc]
-    lay = plframer_layout(seq)
-    d_xfec = torch.zeros((nd, enc.n_syms, 2), dtype=torch.float32, device="cuda")
-    enc.work_device(torch.from_numpy(sent).cuda().data_ptr(), nd, d_syms=d_xfec.data_ptr(), stream=st)
-    fr = PlFramer(gold, max_frames=len(seq))
-    fr.set_sequence(seq)
-    bank0 = symsync_taps(sps, rolloff, rrc_delay, 128)[0].astype(np.float64)[::-1]
-    centre = np.convolve(pulse_taps(sps, rolloff, rrc_delay).astype(np.float64), bank0)[2 * sps * rrc_delay]
-    taps = (pulse_taps(sps, rolloff, rrc_delay, tau).astype(np.float64) / centre).astype(np.float32)  # unit symbols behind the matched filter
-    n = lead + lay["out_syms"] + 90
-    ps = PulseShaper(sps, taps=taps, max_symbols=n + 2 * rrc_delay + 64)
-    n_all = n + ps.history + 64
-    d_x = torch.zeros((n_all, 2), dtype=torch.float32, device="cuda")
-    d_x[:lead] = torch.from_numpy(P.qpsk(rng, lead).astype(np.complex64).view(np.float32).reshape(-1, 2)).cuda()
-    fr.work_device(d_xfec.data_ptr(), len(seq), seq[-1], d_x.data_ptr() + 8 * lead, st)
-    d_y = torch.zeros((n_all * sps, 2), dtype=torch.float32, device="cuda")
-    ps.work_device(d_x.data_ptr(), n_all, n_all, 1, d_y.data_ptr(), n_all * sps, st)
-    torch.cuda.synchronize()
-    for o in (ps, fr, enc):
-        o.close()
-    return dict(d_y=d_y, ns=n_all * sps, n_all=n_all, sps=sps, rolloff=rolloff, rrc_delay=rrc_delay, gold=gold, plsc=plsc, seq=seq, lay=lay, lead=lead,
-                sent=sent, L=M.pls_parse(plsc)["plframe_len"])
-
-
-def receive(tx, d_y):
-    """symsync -> plsync on the samples d_y. Returns (records behind the lead, symbols on the device, all records on the device, their
-    number, the PlSync, the tracker's state)."""
-    torch = _torch()
-    st, ns = stream(), tx["ns"]
-    ss = SymbolSync(sps=tx["sps"], loop_bw=0.01, damping=1.0, rolloff=tx["rolloff"], interp_method=0, max_samples=ns)
-    d_sym = torch.zeros(2 * ns, dtype=torch.float32, device="cuda")
-    ss.work_device(d_y.data_ptr(), ns, [ns], d_sym.data_ptr(), ns, ns, 0, 0, st)
-    n_out, _, status = ss.finish()
-    nsym = int(n_out[0])
-    ss.close()
-    assert status[0] == 0 and abs(nsym - tx["n_all"]) <= 12
-    sync = PlSync(plsc=-1, max_symbols=max(nsym, PlSync.MIN_SYMBOLS), max_frames=64)
-    d_rec = torch.zeros(64 * 16, dtype=torch.uint8, device="cuda")
-    sync.work_device(d_sym.data_ptr(), nsym, d_rec.data_ptr(), st)
-    nf, _, state = sync.finish()
-    recs = d_rec.cpu().numpy().view(PlSync.FRAME_DTYPE)[:nf]
-    return recs, d_sym, d_rec, nf, sync, state
-
-
 def test_closed_loop_through_the_receiver():
-    torch = _torch()
-    tx = transmit()
-    st, ns, seq, plsc, lead, L = stream(), tx["ns"], tx["seq"], tx["plsc"], tx["lead"], tx["L"]
+    import torch
+    seq, plsc, lead = L.SEQ6, L.PLSC, 2001
+    tx = L.shaped_six_frames(lead, seed=2027)
+    st, ns = stream(), tx.ns
     # the reference: the mean magnitude of the shaped samples at full scale, so that the settled gain is 37 and the symbols behind the
     # matched filter come out at the amplitude they were sent with
-    reference = float(torch.linalg.vector_norm(tx["d_y"][:2 * lead], dim=1).mean().item())
-    d_weak = tx["d_y"] * SCALE
+    reference = float(torch.linalg.vector_norm(tx.d_y[:2 * lead], dim=1).mean().item())
+    d_weak = tx.d_y * SCALE
     agc = Agc(rate=0.05, reference=reference, gain=1.0, max_gain=65536.0, max_samples=ns)
     d_gain = torch.zeros(ns, dtype=torch.float32, device="cuda")
     agc.work_device(d_weak.data_ptr(), ns, ns, 1, d_weak.data_ptr(), ns, d_gain.data_ptr(), ns, st)  # in place
     torch.cuda.synchronize()
-    settled = d_gain[2 * lead:2 * (lead + tx["lay"]["out_syms"])].cpu().numpy()
+    settled = d_gain[2 * lead:2 * (lead + tx.lay["out_syms"])].cpu().numpy()
     print(f"closed loop: reference {reference:.4f}, gain behind the lead {settled.min():.2f} .. {settled.max():.2f} (mean {settled.mean():.2f})")
     assert d_gain[0].item() == 1.0 and 30.0 < settled.min() and settled.max() < 45.0
-    recs, d_sym, d_rec, nf, sync, state = receive(tx, d_weak)
+    rx = L.timing_and_frames(d_weak, ns, L.SPS, L.ROLLOFF, 0, tx.n_all, tol=12)
+    recs = rx.recs
     behind = recs[recs["sof_index"] >= lead]
-    assert state == capi.PLSYNC_LOCKED and behind["plsc"].tolist() == seq  # every frame behind the settled lead is found
-    shifts = set((behind["sof_index"] - (lead + tx["lay"]["out_offset"])).tolist())
-    assert len(shifts) == 1 and abs(shifts.pop() - tx["rrc_delay"]) <= 12, shifts
-    locked = [f for f, r in enumerate(recs) if r["flags"] & capi.PLSYNC_FLAG_LOCKED and r["plsc"] == plsc and r["sof_index"] >= lead]
-    assert len(locked) >= 5 and len(locked) == sum(1 for r in recs if r["flags"] & capi.PLSYNC_FLAG_LOCKED and r["plsc"] == plsc)
-    d_fr = torch.zeros((len(locked) * L + 90) * 2, dtype=torch.float32, device="cuda")
-    d_cnt = torch.full((1,), -7, dtype=torch.int32, device="cuda")
-    sync.gather_device(d_sym.data_ptr(), d_rec.data_ptr(), nf, plsc, d_fr.data_ptr(), d_cnt.data_ptr(), st)
-    torch.cuda.synchronize()
-    cnt = int(d_cnt.item())
-    assert cnt == len(locked)
-    pc = PlCoarse(1, plsc, max_frames=64)
-    d_cc = torch.zeros(cnt, dtype=torch.int32, device="cuda")
-    d_f = torch.zeros(cnt, dtype=torch.float32, device="cuda")
-    pc.work_device(d_fr.data_ptr(), L, cnt, 0, d_f.data_ptr(), d_cc.data_ptr(), 0, st)
-    fe = PlFrontEnd(tx["gold"], plsc, max_frames=cnt)
-    d_rx = torch.zeros((cnt, fe.xfecframe_len * 2), dtype=torch.float32, device="cuda")
-    fe.work_device(d_fr.data_ptr(), cnt, 1, d_cc.data_ptr(), d_f.data_ptr(), d_rx.data_ptr(), st)
-    torch.cuda.synchronize()
-    chain = FecChain(capi.STANDARD_DVBS2, capi.FECFRAME_SHORT, "C1_4", capi.MOD_QPSK, group_size=4, max_frames=cnt, max_trials=25)
-    chain.set_descramble(True)
-    msg, ret, corr = chain.work(d_rx.cpu().numpy().view(np.complex64), np.float32(0.02))
-    assert (ret >= 0).all() and (corr >= 0).all()
-    first = int(np.nonzero(recs["sof_index"] >= lead)[0][0])
-    data_index = [sum(1 for q in seq[:f - first] if q == plsc) for f in locked]  # which encoder frame each gathered frame carries
-    assert np.array_equal(msg, tx["sent"][data_index])  # the encoder's input bytes
-    for o in (chain, fe, pc, sync, agc):
-        o.close()
+    assert rx.state == capi.PLSYNC_LOCKED and behind["plsc"].tolist() == seq  # every frame behind the settled lead is found
+    shifts = set((behind["sof_index"] - (lead + tx.lay["out_offset"])).tolist())
+    assert len(shifts) == 1 and abs(shifts.pop() - L.RRC_DELAY) <= 12, shifts
+    got = L.decode_frames(rx, plsc, L.GOLD, 0.02, first_sof=lead)
+    assert len(got.locked) >= 5 and len(got.locked) == sum(1 for r in recs if r["flags"] & capi.PLSYNC_FLAG_LOCKED and r["plsc"] == plsc)
+    assert np.array_equal(got.msg, tx.sent[got.data_index])  # the encoder's input bytes
+    rx.sync.close()
+    agc.close()

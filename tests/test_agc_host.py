@@ -2,7 +2,6 @@
 every new entry with a null handle -- once more in a stand-alone program built with the host sanitizers. Its answers must be the
 library's own. Nothing is loaded into Python by the program and no GPU call is made."""
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
@@ -11,21 +10,14 @@ import pytest
 import fec_testlib as T
 from dvbs2rx_amd import capi
 
-CSRC = os.path.join(T.ROOT, "gr-dvbs2rx_amd", "csrc")
-SOURCES = ("c_api_stream.hip", "agc_hip.hip", "rotator_hip.hip", "symsync_hip.hip", "pulse_hip.hip", "bbdeheader_hip.hip", "bbframer_hip.hip",
-           "fec_tables.cpp")  # the entries' translation unit and what it binds
+SOURCES = ("c_api_agc.hip", "agc_hip.hip")  # the entries' translation unit and what it binds
 
 
 @pytest.fixture(scope="module")
 def host_exe(tmp_path_factory):
     """tests/agc_host_main.cpp with the sources behind the entries, host code under AddressSanitizer and UBSan (device code is not
     instrumented and none of it runs)."""
-    exe = str(tmp_path_factory.mktemp("agc") / "agc_host_main")
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined"]
-    subprocess.check_call([hipcc, "-x", "hip", "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-ffp-contract=off", *san,
-                           os.path.join(T.ROOT, "tests", "agc_host_main.cpp"), *[os.path.join(CSRC, s) for s in SOURCES], "-o", exe])
-    return exe
+    return T.build_host_program(tmp_path_factory.mktemp("agc"), "agc_host_main.cpp", SOURCES)
 
 
 def _hex(*values):

@@ -9,28 +9,14 @@ import pytest
 
 import awgn_model as M
 from dvbs2rx_amd import Awgn, FecChain, FecEncoder, awgn_sigma, capi
+from fec_testlib import SENTINEL, sentinel, stream
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0xC3A55A3C  # a bit pattern no output of these tests holds
 PAD = 64               # sentinel elements in front of the first and behind the last row
 T = capi.AWGN_TILE     # samples of a row one workgroup covers
 SEED = 0x1F2E3D4C5B6A7988
 SIZES = (1, 2, 3, T - 1, T, T + 1, 3 * T + 5)
-
-
-def _torch():
-    import torch
-    return torch
-
-
-def stream():
-    return _torch().cuda.current_stream().cuda_stream
-
-
-def sentinel(n_words):
-    torch = _torch()
-    return torch.full((n_words,), np.uint32(SENTINEL).astype(np.int32).item(), dtype=torch.int32, device="cuda")
 
 
 @functools.lru_cache(maxsize=None)
@@ -56,7 +42,7 @@ def run(awgn, n, ns, x=None, first_stream=0, first_index=0, sigmas=None, in_stri
     r * in_stride complex elements of a 16-byte-aligned input buffer and is written at PAD + out_shift + r * out_stride of a
     16-byte-aligned sentinel buffer (in place: into the input buffer). sigmas: one float32 per row on the device, or None. Returns
     uint32 [ns, n, 2] after checking that everything else in the buffers is still what it was."""
-    torch = _torch()
+    import torch
     in_stride = max(n, 1) if in_stride is None else in_stride
     out_stride = (in_stride if in_place else max(n, 1)) if out_stride is None else out_stride
     d_in = None
@@ -154,7 +140,7 @@ def test_position(awgn, first_index, first_stream):
 def test_pieces_equal_one_call(awgn):
     """No state links two calls: a row cut anywhere, the pieces issued on two HIP streams with advancing first_index, has the bits of
     one call; so have the rows of a call issued one by one."""
-    torch = _torch()
+    import torch
     n, first = 3 * T + 5, (1 << 33) - T - 3
     x = data(4, 1, n)
     whole = check_call(awgn, 0.75, n, 1, "one call", x=x, first_stream=12, first_index=first)
@@ -255,7 +241,7 @@ def test_host_entry_equals_device_entry_and_setters_hold():
 
 
 def test_refusals_leave_the_output_untouched():
-    torch = _torch()
+    import torch
     a = Awgn(SEED, 1.0, max_streams=4, max_samples=64)
     d_in = torch.zeros(2 * 1024, dtype=torch.float32, device="cuda")
     d_out = sentinel(2 * 1024)
@@ -305,7 +291,7 @@ def test_closed_loop_qpsk_1_4_short():
     """FecEncoder (scrambler on) -> Awgn in place on the XFECFRAME symbols, one row per frame -> FecChain (descrambler on). At Es/N0 =
     1 dB, more than 3 dB above the MODCOD's ideal threshold of -2.35 dB (EN 302 307-1 table 13), every frame decodes; at -8 dB, far
     below it, at least one does not: the noise reaches the decoder."""
-    torch = _torch()
+    import torch
     nf = 8
     enc = FecEncoder(capi.STANDARD_DVBS2, capi.FECFRAME_SHORT, "C1_4", capi.MOD_QPSK, max_frames=nf)
     enc.set_scramble(True)

@@ -16,15 +16,6 @@ SENTINEL = 0xA5
 PAD = 64
 
 
-def _torch():
-    import torch
-    return torch
-
-
-def _stream():
-    return _torch().cuda.current_stream().cuda_stream
-
-
 def _dfls(kbch):
     mx = kbch // 8 - 10
     return [0, mx // TS * TS, 188, 189, mx - 5]
@@ -32,7 +23,7 @@ def _dfls(kbch):
 
 def _dev_at(a, off):
     """a copy of `a` on the device that starts `off` bytes behind a 16-byte boundary"""
-    torch = _torch()
+    import torch
     base = torch.zeros(a.size + 32, dtype=torch.uint8, device="cuda:0")
     assert base.data_ptr() % 16 == 0
     view = base[off:off + a.size]
@@ -43,14 +34,14 @@ def _dev_at(a, off):
 def _run(fr, ts, n_frames, dfl, in_off=0, out_off=0):
     """One work_device call; returns the frames after checking everything around them: the sentinels in front of and behind the output,
     the input unchanged."""
-    torch = _torch()
+    import torch
     need = fr.need(n_frames, dfl)
     src = np.array(ts[:need * TS], np.uint8)
     d_in = _dev_at(src, in_off)
     total = n_frames * fr.kbch_bytes
     d_out = torch.full((out_off + total + PAD + 16,), SENTINEL, dtype=torch.uint8, device="cuda:0")
     assert d_out.data_ptr() % 16 == 0
-    fr.work_device(d_in.data_ptr(), n_frames, d_out.data_ptr() + out_off, dfl, _stream())
+    fr.work_device(d_in.data_ptr(), n_frames, d_out.data_ptr() + out_off, dfl, T.stream())
     torch.cuda.synchronize()
     out = d_out.cpu().numpy()
     assert (out[:out_off] == SENTINEL).all() and (out[out_off + total:] == SENTINEL).all(), "wrote outside the frames"
@@ -86,12 +77,12 @@ def test_every_byte(kbch, dfl_index):
     for n in (1, 2, 7, 33):
         for in_off in (0, 1, 3):
             for out_off in (0, 1):
-                fr.reset(_stream())
+                fr.reset(T.stream())
                 got, need = _run(fr, ups, n, dfl, in_off, out_off)
                 assert need == -(-n * eff // TS)
                 assert np.array_equal(got, want[:n]), (n, in_off, out_off)
                 assert (got[:, 10 + eff:] == 0).all()
-                assert fr.counters(_stream()) == dict(packets=need, bbframes=n, sync_errors=0)
+                assert fr.counters(T.stream()) == dict(packets=need, bbframes=n, sync_errors=0)
     fr.close()
 
 
@@ -117,7 +108,7 @@ def test_wrong_sync_bytes_are_framed_and_counted():
     fr = BbFramer(kbch_bits=kbch, max_frames=8)
     got, need = _run(fr, ups, 7, 0, in_off=1)
     assert np.array_equal(got, want) and got[0, 10] == 0x12
-    assert fr.counters(_stream()) == m.counters() == dict(packets=need, bbframes=7, sync_errors=3)
+    assert fr.counters(T.stream()) == m.counters() == dict(packets=need, bbframes=7, sync_errors=3)
     fr.close()
 
 
@@ -137,8 +128,8 @@ def test_carry_walks_every_residue():
         assert np.array_equal(got, m.work(ups[pk * TS:], 1, 189)) and np.array_equal(got[0], want[f]), f
         pk += need
     assert seen == set(range(TS)) and pk * TS == ups.size
-    assert fr.counters(_stream()) == m.counters()
-    fr.reset(_stream())
+    assert fr.counters(T.stream()) == m.counters()
+    fr.reset(T.stream())
     got, _ = _run(fr, ups, n, 189)
     assert np.array_equal(got, want)
     fr.close()
@@ -158,7 +149,7 @@ def test_random_calls_with_changing_dfl_and_reset():
             assert fr.need(n, dfl) == need
             want = m.work(ups[pk * TS:], n, dfl)
             if n == 0:
-                fr.work_device(0, 0, 0, dfl, _stream())  # a valid call that changes nothing
+                fr.work_device(0, 0, 0, dfl, T.stream())  # a valid call that changes nothing
             else:
                 got, _ = _run(fr, ups[pk * TS:], n, dfl, in_off=int(rng.integers(0, 4)), out_off=int(rng.integers(0, 2)))
                 assert np.array_equal(got, want), (part, f, n, dfl)
@@ -167,9 +158,9 @@ def test_random_calls_with_changing_dfl_and_reset():
         dfl = 189 if (m.pos + 189) % TS else 190  # leave the stream inside a packet
         got, _ = _run(fr, ups[pk * TS:], 1, dfl)
         assert np.array_equal(got, m.work(ups[pk * TS:], 1, dfl)) and m.pos % TS != 0
-        assert fr.counters(_stream()) == m.counters()
-        fr.reset(_stream())
-        assert fr.counters(_stream()) == dict(packets=0, bbframes=0, sync_errors=0) and fr.need(1, 188) == 1
+        assert fr.counters(T.stream()) == m.counters()
+        fr.reset(T.stream())
+        assert fr.counters(T.stream()) == dict(packets=0, bbframes=0, sync_errors=0) and fr.need(1, 188) == 1
     fr.close()
 
 
@@ -177,13 +168,13 @@ def test_random_calls_with_changing_dfl_and_reset():
 @pytest.mark.parametrize("kbch", (7032, 58192))
 @pytest.mark.parametrize("whole_packets", (False, True), ids=("dfl-max", "dfl-whole-packets"))
 def test_into_the_device_deheader(kbch, whole_packets):
-    torch = _torch()
+    import torch
     mx = kbch // 8 - 10
     dfl = mx // TS * TS if whole_packets else 0
     total = 64 * (dfl or mx)
     ups = T.ts_up_stream(-(-total // TS), np.random.default_rng(kbch))
     fr, dh = BbFramer(kbch_bits=kbch, max_frames=64), BbDeheader(kbch_bits=kbch, max_frames=64)
-    st = _stream()
+    st = T.stream()
     d_ts = _dev_at(ups, 0)
     d_bb = torch.zeros((64, kbch // 8), dtype=torch.uint8, device="cuda:0")
     d_out = torch.zeros(64 * dh.max_out_bytes_per_frame, dtype=torch.uint8, device="cuda:0")
@@ -208,7 +199,7 @@ def test_into_the_device_deheader(kbch, whole_packets):
 def test_closed_loop_on_the_device(rate, constellation):
     """TS packets -> BbFramer -> FecEncoder (scramble on) -> noise-free symbols -> FecChain (descramble on) -> BbDeheader -> the TS
     packets, nothing copied to the host in between."""
-    torch = _torch()
+    import torch
     fs, nf = capi.FECFRAME_SHORT, 40
     kbch = get_fec_info(capi.STANDARD_DVBS2, fs, rate)["bch_k"]
     fr = BbFramer(capi.STANDARD_DVBS2, fs, rate, max_frames=nf)
@@ -219,7 +210,7 @@ def test_closed_loop_on_the_device(rate, constellation):
     chain.set_descramble(True)
     assert fr.kbch_bytes == enc.in_bytes == chain.msg_bytes == dh.kbch_bytes == kbch // 8
     ups = T.ts_up_stream(fr.need(nf), np.random.default_rng(kbch))
-    st = _stream()
+    st = T.stream()
     d_ts = _dev_at(ups, 0)
     d_bb = torch.zeros((nf, fr.kbch_bytes), dtype=torch.uint8, device="cuda:0")
     d_syms = torch.zeros((nf, enc.n_syms, 2), dtype=torch.float32, device="cuda:0")
@@ -265,7 +256,7 @@ def _refused(code, word, call, *args, **kwargs):
 
 
 def test_refusals_leave_the_handle_as_it_was():
-    torch = _torch()
+    import torch
     kbch = 3072
     mx = kbch // 8 - 10
     ups, want = _reference(kbch, 189, 190)
@@ -276,10 +267,10 @@ def test_refusals_leave_the_handle_as_it_was():
     fr = BbFramer(kbch_bits=kbch, max_frames=8)
     got, need = _run(fr, ups, 3, 189)  # pos = 567: inside a packet
     assert np.array_equal(got, want[:3])
-    before = fr.counters(_stream())
+    before = fr.counters(T.stream())
     d_in = _dev_at(ups[need * TS:], 0)
     d_out = torch.full((8 * fr.kbch_bytes,), SENTINEL, dtype=torch.uint8, device="cuda:0")
-    st = _stream()
+    st = T.stream()
     for dfl in (187, mx + 1, -1):
         _refused(capi.EINVAL, "dfl_bytes", fr.work_device, d_in.data_ptr(), 1, d_out.data_ptr(), dfl, st)
         _refused(capi.EINVAL, "dfl_bytes", fr.need, 1, dfl)

@@ -13,7 +13,6 @@ import fec_testlib as T
 from bbframer_model import BbFramerModel
 from dvbs2rx_amd import bbheader_build, capi, crc8
 
-CSRC = os.path.join(T.ROOT, "gr-dvbs2rx_amd", "csrc")
 HDR_TEXT = "matype1, matype2 and sync must be in 0..255, upl_bits, dfl_bits and syncd_bits in 0..65535"
 
 
@@ -21,12 +20,7 @@ HDR_TEXT = "matype1, matype2 and sync must be in 0..255, upl_bits, dfl_bits and 
 def host_exe(tmp_path_factory):
     """tests/bbframer_host_main.cpp with the source it calls, host code under AddressSanitizer and UBSan (device code is not instrumented
     and none of it runs)."""
-    exe = str(tmp_path_factory.mktemp("bbframer") / "bbframer_host_main")
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined"]
-    subprocess.check_call([hipcc, "-x", "hip", "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-ffp-contract=off", *san,
-                           os.path.join(T.ROOT, "tests", "bbframer_host_main.cpp"), os.path.join(CSRC, "bbframer_hip.hip"), "-o", exe])
-    return exe
+    return T.build_host_program(tmp_path_factory.mktemp("bbframer"), "bbframer_host_main.cpp", ("bbframer_hip.hip",))
 
 
 def _lib_refuses_create(kbch_bits, max_frames):

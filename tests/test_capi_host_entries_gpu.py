@@ -31,11 +31,6 @@ def dev(a):
     return torch.from_numpy(a.view(np.float32) if a.dtype == np.complex64 else a).cuda()
 
 
-def stream():
-    import torch
-    return torch.cuda.current_stream().cuda_stream
-
-
 def ptr(x):
     return None if x is None else x.ctypes.data if isinstance(x, np.ndarray) else x.data_ptr()
 
@@ -57,7 +52,7 @@ def run_frames(make, inputs, outputs, host, device):
         d_ins = [None if a is None else dev(a) for a in ins]
         d_outs = [None if a is None else dev(a) for a in outputs(n)]
         before = [None if a is None else a.copy() for a in outs]
-        rc_h, rc_d = host(hobj, n, ins, outs), device(dobj, n, d_ins, d_outs, stream())
+        rc_h, rc_d = host(hobj, n, ins, outs), device(dobj, n, d_ins, d_outs, T.stream())
         want = capi.ESIZE if n > MF else capi.OK
         assert (rc_h, rc_d) == (want, want), (call, n, rc_h, rc_d, lib.dvbs2_last_error())
         if n > MF:
@@ -209,14 +204,14 @@ def test_bbdeheader():
         out, d_x, d_out = filled(max(n, 1) * ob, np.uint8), dev(x if n else np.zeros(8, np.uint8)), dev(filled(max(n, 1) * ob, np.uint8))
         got = C.c_int64(-1)
         rc_h = lib.dvbs2_bbdeheader_process(hobj._h, ptr(x), n, ptr(out), C.byref(got))
-        rc_d = lib.dvbs2_bbdeheader_process_device(dobj._h, ptr(d_x), n, ptr(d_out), stream())
+        rc_d = lib.dvbs2_bbdeheader_process_device(dobj._h, ptr(d_x), n, ptr(d_out), T.stream())
         want = capi.ESIZE if n > MF else capi.OK
         assert (rc_h, rc_d) == (want, want), (call, n, rc_h, rc_d, lib.dvbs2_last_error())
         if n > MF:
             assert got.value == -1 and not (out != 90).any()
             continue
         at += n
-        k = dobj.finish(stream())
+        k = dobj.finish(T.stream())
         torch.cuda.synchronize()
         assert got.value == k and out[:k].tobytes() == d_out.cpu().numpy()[:k].tobytes(), (call, n, got.value, k)
         assert not (out[k:] != 90).any()
@@ -237,7 +232,7 @@ def test_plsync():
     for call, part in enumerate((x, x[:0], x)):  # the second presentation of the stream finds the handle locked
         recs, consumed, state = hobj.work(part)
         d_x, d_f = dev(part) if part.size else torch.zeros(2, device="cuda"), torch.zeros(16 * 16, dtype=torch.uint8, device="cuda")
-        dobj.work_device(d_x.data_ptr(), part.size, d_f.data_ptr(), stream())
+        dobj.work_device(d_x.data_ptr(), part.size, d_f.data_ptr(), T.stream())
         nf, d_consumed, d_state = dobj.finish()
         assert (len(recs), consumed, state) == (nf, d_consumed, d_state), call
         assert recs.tobytes() == d_f.cpu().numpy().view(PlSync.FRAME_DTYPE)[:nf].tobytes(), call
@@ -260,7 +255,7 @@ def test_rotator():
         x = P.qpsk(rng_of(8, call), n).astype(np.complex64)
         out = hobj.work(x)
         d_x, d_out = dev(x), torch.zeros(2 * n, device="cuda")
-        dobj.work_device(d_x.data_ptr(), n, d_out.data_ptr(), stream())
+        dobj.work_device(d_x.data_ptr(), n, d_out.data_ptr(), T.stream())
         torch.cuda.synchronize()
         assert out.tobytes() == d_out.cpu().numpy().tobytes(), (call, n)
     assert hobj.position() == dobj.position() == (sum(GROW), 0)
@@ -280,7 +275,7 @@ def test_symsync():
         syms, idx, mu, consumed, status = hobj.work(x)
         d_x, d_out = dev(x), torch.zeros(2 * n, device="cuda")
         d_idx, d_mu = torch.zeros(n, dtype=torch.int64, device="cuda"), torch.zeros(n, dtype=torch.float64, device="cuda")
-        dobj.work_device(d_x.data_ptr(), n, [n], d_out.data_ptr(), n, n, d_idx.data_ptr(), d_mu.data_ptr(), stream())
+        dobj.work_device(d_x.data_ptr(), n, [n], d_out.data_ptr(), n, n, d_idx.data_ptr(), d_mu.data_ptr(), T.stream())
         k, d_consumed, d_status = (int(v[0]) for v in dobj.finish())
         assert (len(syms), consumed, status) == (k, d_consumed, d_status), (call, n)
         assert syms.tobytes() == d_out.cpu().numpy()[:2 * k].tobytes(), (call, n)

@@ -10,33 +10,16 @@ import numpy as np
 import pytest
 
 import ddc_model as DM
+import fec_testlib as T
+import loopback as L
 import plcoarse_model as PC
-import plframe_model as M
-import plsync_model as P
 import pulse_model as PM
-from dvbs2rx_amd import (Agc, Awgn, Ddc, FecChain, FecEncoder, PlCoarse, PlFramer, PlFrontEnd, PlSync, PulseShaper, Rotator, SymbolSync,
-                         awgn_sigma, capi, ddc_tile, plframer_layout, pulse_taps)
+from dvbs2rx_amd import Agc, Awgn, Ddc, PulseShaper, Rotator, SymbolSync, awgn_sigma, capi, ddc_tile, plframer_layout, pulse_taps
+from fec_testlib import PAD, SENTINEL, refused, sentinel, stream
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0xC3A55A3C  # a bit pattern no output of these tests holds
-PAD = 64               # sentinel samples behind the last channel's output
 MASK = (1 << 64) - 1
-
-
-def _torch():
-    import torch
-    return torch
-
-
-def stream():
-    return _torch().cuda.current_stream().cuda_stream
-
-
-def sentinel(n_elems):
-    """n_elems complex elements of the sentinel, as int32"""
-    torch = _torch()
-    return torch.full((n_elems * 2,), np.uint32(SENTINEL).astype(np.int32).item(), dtype=torch.int32, device="cuda")
 
 
 @functools.lru_cache(maxsize=None)
@@ -48,7 +31,7 @@ def data(seed, n):
 
 def rotate_on_device(rot, x):
     """what the rotator stage gives on the device for the host samples x, continuing from the handle's phase"""
-    torch = _torch()
+    import torch
     if x.size == 0:
         return np.zeros(0, np.complex64)
     d_x = torch.from_numpy(np.array(x, np.complex64).view(np.float32)).cuda()  # (a copy: the cached data are read-only)
@@ -117,44 +100,21 @@ class Expect:
 
 
 def run_on_device(dd, xs, n_channels, in_stride=None, out_stride=None, in_shift=0, out_shift=0):
-    """One work_device call over the input streams xs (complex64 vectors of one length n). Input i lies at in_shift + i * in_stride complex
-    elements of a 16-byte-aligned buffer, channel c writes at out_shift + c * out_stride of a 16-byte-aligned sentinel buffer. Returns one
-    uint32 (n_out, 2) array per channel after checking that the reported count is what produce() gave before the call, that everything
-    else in the output buffer is still the sentinel, and that the input is unchanged."""
-    torch = _torch()
+    """One work_device call over the input streams xs (complex64 vectors of one length n) through fec_testlib.run_strided: input i lies at
+    in_shift + i * in_stride complex elements of the input buffer, channel c writes at out_shift + c * out_stride of a sentinel buffer.
+    Returns one uint32 (n_out, 2) array per channel after checking that the reported count is what produce() gave before the call."""
     ni, n = len(xs), xs[0].size
     said = dd.produce(n)
     in_stride = max(n, 1) if in_stride is None else in_stride
     out_stride = max(said, 1) if out_stride is None else out_stride
-    host_in = np.full(in_shift + ni * in_stride + 2, np.complex64(complex(9.5, -9.5)), np.complex64)
-    for i, x in enumerate(xs):
-        assert x.size == n
-        host_in[in_shift + i * in_stride:in_shift + i * in_stride + n] = x
-    d_in = torch.from_numpy(host_in.view(np.float32)).cuda()
-    n_buf = out_shift + max(n_channels, 1) * out_stride + PAD
-    d_out = sentinel(n_buf)
-    assert d_in.data_ptr() % 16 == 0 and d_out.data_ptr() % 16 == 0
-    n_out = dd.work_device(d_in.data_ptr() + 8 * in_shift, in_stride, n, ni, n_channels, d_out.data_ptr() + 8 * out_shift, out_stride, stream())
-    torch.cuda.synchronize()
+    outs, n_out = T.run_strided(lambda a, o: dd.work_device(a, in_stride, n, ni, n_channels, o, out_stride, stream()), xs, [said] * n_channels,
+                                in_stride, out_stride, in_shift, out_shift)
     assert n_out == said == DM.produce(dd.position() - n, dd.decim, n)
-    got = d_out.cpu().numpy().view(np.uint32).reshape(-1, 2)
-    assert np.array_equal(d_in.cpu().numpy().view(np.uint32), host_in.view(np.uint32)), "the input was written"
-    touched = np.zeros(n_buf, bool)
-    outs = []
-    for c in range(n_channels):
-        a = out_shift + c * out_stride
-        touched[a:a + n_out] = True
-        outs.append(got[a:a + n_out])
-    assert (got[~touched] == SENTINEL).all(), "a write outside the channels' outputs"
     return outs
 
 
 def same(got, want, what):
-    assert got.shape[0] == want.size, (what, got.shape[0], want.size)
-    w = DM.bits(want).reshape(-1, 2)
-    if not np.array_equal(got, w):
-        bad = np.nonzero((got != w).any(axis=1))[0]
-        raise AssertionError(f"{what}: {bad.size} of {want.size} samples differ, the first at {bad[0]}: {got[bad[0]]} != {w[bad[0]]}")
+    T.same_bits(got, DM.bits(want), what)
 
 
 def call(e, xs, n_channels, what, **where):
@@ -348,19 +308,14 @@ def test_accuracy_against_the_float64_model():
 
 
 # ------------------------------------------------------------------ 5. refusals
-def _refused(code, text, entry, *args):
-    assert entry(*args) == code, (entry.__name__, capi.lib.dvbs2_last_error())
-    assert capi.lib.dvbs2_last_error() == text.encode(), capi.lib.dvbs2_last_error()
-
-
 def test_refusals_leave_everything_untouched():
-    torch = _torch()
+    import torch
     lib, h = capi.lib, C.c_void_p()
     good = np.ones(21, np.float32)
     # creation (every argument refusal without a device: tests/test_ddc_model.py)
-    _refused(capi.EINVAL, "decim must be in 1..256", lib.dvbs2_ddc_create, C.byref(h), 0, good.ctypes.data, 21, 1, 1, 16, 0)
-    _refused(capi.EINVAL, "ntaps must be in 1..4096", lib.dvbs2_ddc_create, C.byref(h), 4, good.ctypes.data, 4097, 1, 1, 16, 0)
-    _refused(capi.EINVAL, "null handle pointer", lib.dvbs2_ddc_create, None, 4, good.ctypes.data, 21, 1, 1, 16, 0)
+    refused(capi.EINVAL, "decim must be in 1..256", lib.dvbs2_ddc_create, C.byref(h), 0, good.ctypes.data, 21, 1, 1, 16, 0)
+    refused(capi.EINVAL, "ntaps must be in 1..4096", lib.dvbs2_ddc_create, C.byref(h), 4, good.ctypes.data, 4097, 1, 1, 16, 0)
+    refused(capi.EINVAL, "null handle pointer", lib.dvbs2_ddc_create, None, 4, good.ctypes.data, 21, 1, 1, 16, 0)
     assert not h
     assert lib.dvbs2_ddc_create(C.byref(h), 4, good.ctypes.data, 21, 1, 1, 16, 99) < 0 and not h  # no such device
 
@@ -373,36 +328,36 @@ def test_refusals_leave_everything_untouched():
     n_out = dd.produce(n)
     assert n_out == DM.produce(n - 1, D, n) == 25
     d_in = torch.from_numpy(np.concatenate(second).view(np.float32)).cuda()
-    d_out = sentinel(2 * n_out + PAD)
+    d_out = sentinel(2 * (2 * n_out + PAD))
     st = stream()
     a, o = d_in.data_ptr(), d_out.data_ptr()
     count = C.c_int64(-7)
     c = C.byref(count)
     entry = lib.dvbs2_ddc_process_device
-    _refused(capi.ESIZE, "n_in exceeds max_samples", entry, dd._h, a, n, n + 1, 2, 2, o, n_out, c, st)
-    _refused(capi.ESIZE, "n_inputs exceeds max_inputs", entry, dd._h, a, n, n, 3, 2, o, n_out, c, st)
-    _refused(capi.ESIZE, "n_channels exceeds max_channels", entry, dd._h, a, n, n, 2, 3, o, n_out, c, st)
-    _refused(capi.EINVAL, "n_in is negative", entry, dd._h, a, n, -1, 2, 2, o, n_out, c, st)
-    _refused(capi.EINVAL, "n_inputs is negative", entry, dd._h, a, n, n, -1, 2, o, n_out, c, st)
-    _refused(capi.EINVAL, "n_channels is negative", entry, dd._h, a, n, n, 2, -1, o, n_out, c, st)
-    _refused(capi.EINVAL, "in is null", entry, dd._h, None, n, n, 2, 2, o, n_out, c, st)
-    _refused(capi.EINVAL, "out is null", entry, dd._h, a, n, n, 2, 2, None, n_out, c, st)
-    _refused(capi.EINVAL, "channel 1 reads input 1, which is not below n_inputs", entry, dd._h, a, n, n, 1, 2, o, n_out, c, st)
-    _refused(capi.EINVAL, "in_stride is below n_in", entry, dd._h, a, n - 1, n, 2, 2, o, n_out, c, st)
-    _refused(capi.EINVAL, "out_stride is below n_out", entry, dd._h, a, n, n, 2, 2, o, n_out - 1, c, st)  # before any launch
-    _refused(capi.EINVAL, "out_stride is below n_out", entry, dd._h, a, n, n, 2, 1, o, n_out - 1, c, st)
-    _refused(capi.EINVAL, "in and out must be 8-byte aligned", entry, dd._h, a + 4, n, n, 2, 2, o, n_out, c, st)
-    _refused(capi.EINVAL, "in and out must be 8-byte aligned", entry, dd._h, a, n, n, 2, 2, o + 4, n_out, c, st)
+    refused(capi.ESIZE, "n_in exceeds max_samples", entry, dd._h, a, n, n + 1, 2, 2, o, n_out, c, st)
+    refused(capi.ESIZE, "n_inputs exceeds max_inputs", entry, dd._h, a, n, n, 3, 2, o, n_out, c, st)
+    refused(capi.ESIZE, "n_channels exceeds max_channels", entry, dd._h, a, n, n, 2, 3, o, n_out, c, st)
+    refused(capi.EINVAL, "n_in is negative", entry, dd._h, a, n, -1, 2, 2, o, n_out, c, st)
+    refused(capi.EINVAL, "n_inputs is negative", entry, dd._h, a, n, n, -1, 2, o, n_out, c, st)
+    refused(capi.EINVAL, "n_channels is negative", entry, dd._h, a, n, n, 2, -1, o, n_out, c, st)
+    refused(capi.EINVAL, "in is null", entry, dd._h, None, n, n, 2, 2, o, n_out, c, st)
+    refused(capi.EINVAL, "out is null", entry, dd._h, a, n, n, 2, 2, None, n_out, c, st)
+    refused(capi.EINVAL, "channel 1 reads input 1, which is not below n_inputs", entry, dd._h, a, n, n, 1, 2, o, n_out, c, st)
+    refused(capi.EINVAL, "in_stride is below n_in", entry, dd._h, a, n - 1, n, 2, 2, o, n_out, c, st)
+    refused(capi.EINVAL, "out_stride is below n_out", entry, dd._h, a, n, n, 2, 2, o, n_out - 1, c, st)  # before any launch
+    refused(capi.EINVAL, "out_stride is below n_out", entry, dd._h, a, n, n, 2, 1, o, n_out - 1, c, st)
+    refused(capi.EINVAL, "in and out must be 8-byte aligned", entry, dd._h, a + 4, n, n, 2, 2, o, n_out, c, st)
+    refused(capi.EINVAL, "in and out must be 8-byte aligned", entry, dd._h, a, n, n, 2, 2, o + 4, n_out, c, st)
     assert count.value == -7
-    _refused(capi.EINVAL, "channel out of range", lib.dvbs2_ddc_set_channel, dd._h, 2, 0, 0.1)
-    _refused(capi.EINVAL, "channel out of range", lib.dvbs2_ddc_set_channel, dd._h, -1, 0, 0.1)
-    _refused(capi.EINVAL, "input out of range", lib.dvbs2_ddc_set_channel, dd._h, 0, 2, 0.1)
-    _refused(capi.EINVAL, "input out of range", lib.dvbs2_ddc_set_channel, dd._h, 0, -1, 0.1)
-    _refused(capi.EINVAL, "phase_inc must be finite", lib.dvbs2_ddc_set_channel, dd._h, 0, 0, float("nan"))
-    _refused(capi.EINVAL, "phase_inc must be finite", lib.dvbs2_ddc_set_channel, dd._h, 0, 0, float("inf"))
-    _refused(capi.EINVAL, "channel out of range", lib.dvbs2_ddc_channel, dd._h, 2, None, None, None)
-    _refused(capi.EINVAL, "counter is null", lib.dvbs2_ddc_position, dd._h, None)
-    _refused(capi.EINVAL, "phases is null", lib.dvbs2_ddc_state, dd._h, None)
+    refused(capi.EINVAL, "channel out of range", lib.dvbs2_ddc_set_channel, dd._h, 2, 0, 0.1)
+    refused(capi.EINVAL, "channel out of range", lib.dvbs2_ddc_set_channel, dd._h, -1, 0, 0.1)
+    refused(capi.EINVAL, "input out of range", lib.dvbs2_ddc_set_channel, dd._h, 0, 2, 0.1)
+    refused(capi.EINVAL, "input out of range", lib.dvbs2_ddc_set_channel, dd._h, 0, -1, 0.1)
+    refused(capi.EINVAL, "phase_inc must be finite", lib.dvbs2_ddc_set_channel, dd._h, 0, 0, float("nan"))
+    refused(capi.EINVAL, "phase_inc must be finite", lib.dvbs2_ddc_set_channel, dd._h, 0, 0, float("inf"))
+    refused(capi.EINVAL, "channel out of range", lib.dvbs2_ddc_channel, dd._h, 2, None, None, None)
+    refused(capi.EINVAL, "counter is null", lib.dvbs2_ddc_position, dd._h, None)
+    refused(capi.EINVAL, "phases is null", lib.dvbs2_ddc_state, dd._h, None)
     assert entry(dd._h, None, 0, 0, 2, 2, None, 0, c, st) == capi.OK  # n_in == 0: a successful call that does nothing and reports 0
     assert count.value == 0
     e.state_is("behind the refusals")
@@ -414,12 +369,12 @@ def test_refusals_leave_everything_untouched():
     c = C.byref(count)
     host = lib.dvbs2_ddc_process
     hi, ho = host_in.ctypes.data, host_out.ctypes.data
-    _refused(capi.ESIZE, "n_in exceeds max_samples", host, dd._h, hi, n, n + 1, 2, 2, ho, n_out, c)
-    _refused(capi.EINVAL, "n_in is negative", host, dd._h, hi, n, -1, 2, 2, ho, n_out, c)
-    _refused(capi.EINVAL, "in is null", host, dd._h, None, n, n, 2, 2, ho, n_out, c)
-    _refused(capi.EINVAL, "out is null", host, dd._h, hi, n, n, 2, 2, None, n_out, c)
-    _refused(capi.EINVAL, "in_stride is below n_in", host, dd._h, hi, n - 1, n, 2, 2, ho, n_out, c)
-    _refused(capi.EINVAL, "out_stride is below n_out", host, dd._h, hi, n, n, 2, 2, ho, n_out - 1, c)
+    refused(capi.ESIZE, "n_in exceeds max_samples", host, dd._h, hi, n, n + 1, 2, 2, ho, n_out, c)
+    refused(capi.EINVAL, "n_in is negative", host, dd._h, hi, n, -1, 2, 2, ho, n_out, c)
+    refused(capi.EINVAL, "in is null", host, dd._h, None, n, n, 2, 2, ho, n_out, c)
+    refused(capi.EINVAL, "out is null", host, dd._h, hi, n, n, 2, 2, None, n_out, c)
+    refused(capi.EINVAL, "in_stride is below n_in", host, dd._h, hi, n - 1, n, 2, 2, ho, n_out, c)
+    refused(capi.EINVAL, "out_stride is below n_out", host, dd._h, hi, n, n, 2, 2, ho, n_out - 1, c)
     assert (host_out == 0).all() and count.value == -7
     # no refusal touched a history, a phase or the mirror: both channels go on from where the good call left them
     e.state_is("behind the host entry's refusals")
@@ -432,8 +387,8 @@ def test_refusals_leave_everything_untouched():
 
 
 # ------------------------------------------------------------------ 6. closed loop: two carriers in one band
-GOLD, PLSC, DUMMY, ND, LEAD = 5, P.plsc_of(1, 1, 1), P.plsc_of(0, 0, 0), 4, 2001
-SEQ = [PLSC, PLSC, DUMMY, PLSC, PLSC]  # a dummy frame after data frame 2
+PLSC, ND, LEAD = L.PLSC, 4, 2001
+SEQ = [PLSC, PLSC, L.DUMMY, PLSC, PLSC]  # a dummy frame after data frame 2
 SPS, ROLLOFF, RRC_DELAY, SPACING = 8, 0.2, 5, 1.5
 ES_N0_DB = 10.0  # the chain alone decodes QPSK 1/4 short without an error from 1 dB on (tests/test_awgn_gpu.py)
 SCALE = 1.0 / 37.0  # the capture is weak: the AGC behind the down-converter has to bring it back
@@ -442,42 +397,32 @@ CARRIER_INC = 2 * np.pi * (SPACING / 2) / SPS  # +-0.75 symbol rates in radians 
 
 @functools.lru_cache(maxsize=None)
 def capture():
-    """Two carriers of short QPSK 1/4 frames with different payloads, each shaped at 8 samples per symbol (taps scaled so that the symbols
-    behind the channel filter have unit amplitude), moved to -+0.75 symbol rates and added; noise at Es/N0 = ES_N0_DB for the power of one
-    carrier; all of it scaled by SCALE. Returns (the encoders' inputs [2], the samples on the device, their number, symbols per carrier)."""
-    torch = _torch()
+    """Two carriers of short QPSK 1/4 frames with different payloads (loopback.transmit_symbols, 256 zero symbols of flush: more than the
+    histories of all stages behind), each shaped at 8 samples per symbol (taps scaled so that the symbols behind the channel filter have
+    unit amplitude), moved to -+0.75 symbol rates and added; noise at Es/N0 = ES_N0_DB for the power of one carrier; all of it scaled by
+    SCALE. Returns (the encoders' inputs [2], the samples on the device, their number, symbols per carrier)."""
+    import torch
     st = stream()
     rx = pulse_taps(SPS, ROLLOFF, RRC_DELAY, 0.0, 1.0)
     tx = pulse_taps(SPS, ROLLOFF, RRC_DELAY).astype(np.float64)
     tx = (tx / np.convolve(tx, rx.astype(np.float64))[2 * SPS * RRC_DELAY]).astype(np.float32)
-    lay = plframer_layout(SEQ)
-    n = LEAD + lay["out_syms"] + 90
-    n_all = n + 256  # the flush: more zero symbols than the histories of all stages behind
-    ns = n_all * SPS
-    d_sum = torch.zeros((ns, 2), dtype=torch.float32, device="cuda")
-    sent, power = [], []
+    d_sum, sent, power = None, [], []
     for k, sign in enumerate((-1.0, 1.0)):
-        rng = np.random.default_rng(3000 + k)
-        enc = FecEncoder(capi.STANDARD_DVBS2, capi.FECFRAME_SHORT, "C1_4", capi.MOD_QPSK, max_frames=ND)
-        enc.set_scramble(True)
-        sent.append(rng.integers(0, 256, (ND, enc.in_bytes), dtype=np.uint8))
-        d_xfec = torch.zeros((ND, enc.n_syms, 2), dtype=torch.float32, device="cuda")
-        enc.work_device(torch.from_numpy(sent[k]).cuda().data_ptr(), ND, d_syms=d_xfec.data_ptr(), stream=st)
-        fr = PlFramer(GOLD, max_frames=len(SEQ))
-        fr.set_sequence(SEQ)
-        d_x = torch.zeros((n_all, 2), dtype=torch.float32, device="cuda")
-        d_x[:LEAD] = torch.from_numpy(P.qpsk(rng, LEAD).astype(np.complex64).view(np.float32).reshape(-1, 2)).cuda()
-        fr.work_device(d_xfec.data_ptr(), len(SEQ), SEQ[-1], d_x.data_ptr() + 8 * LEAD, st)
+        sent_k, d_x, n, n_all, _ = L.transmit_symbols(SEQ, ND, L.GOLD, LEAD, seed=3000 + k, flush=256)
+        sent.append(sent_k)
+        ns = n_all * SPS
         ps = PulseShaper(SPS, taps=tx, max_symbols=n_all)
         d_y = torch.zeros((ns, 2), dtype=torch.float32, device="cuda")
         ps.work_device(d_x.data_ptr(), n_all, n_all, 1, d_y.data_ptr(), ns, st)
         power.append(float((d_y[:n * SPS] ** 2).sum(dim=1).mean().item()))
         rot = Rotator(sign * CARRIER_INC)
         rot.work_device(d_y.data_ptr(), ns, d_y.data_ptr(), st)
+        if d_sum is None:
+            d_sum = torch.zeros_like(d_y)
         d_sum += d_y
         torch.cuda.synchronize()
-        for o in (rot, ps, fr, enc):
-            o.close()
+        rot.close()
+        ps.close()
     assert abs(power[0] / power[1] - 1) < 0.05
     noise = Awgn(seed=77, sigma=awgn_sigma(ES_N0_DB, es=power[0], sps=SPS), max_samples=ns)
     noise.work_device(d_sum.data_ptr(), ns, ns, 1, d_sum.data_ptr(), ns, first_index=0, stream=st)
@@ -487,14 +432,13 @@ def capture():
     return sent, d_sum, ns, n_all
 
 
-def receive(d_y, ns, n_syms, sent, what):
+def receive(d_y, ns, n_syms, what):
     """d_y: ns samples of one channel at 2 per symbol on the device, behind the channel filter. AGC, timing recovery with the cubic
-    interpolator (the matched filter is already applied), frame search, gather, coarse estimate, front end, FEC, as in
-    tests/test_resamp_gpu.py. Returns the messages of the frames the tracker locked on and which encoder frame each carries."""
-    torch = _torch()
+    interpolator (the matched filter is already applied), frame search and the decode tail of tests/loopback.py. Returns the messages of
+    the frames the tracker locked on and which encoder frame each carries."""
+    import torch
     st = stream()
     lay = plframer_layout(SEQ)
-    L = M.pls_parse(PLSC)["plframe_len"]
     # the reference: the mean magnitude of the channel's samples at full scale, so that the settled gain is 1 / SCALE and the symbols
     # come out at the unit amplitude they were sent with
     reference = float(torch.linalg.vector_norm(d_y[:2 * LEAD], dim=1).mean().item()) / SCALE
@@ -502,50 +446,22 @@ def receive(d_y, ns, n_syms, sent, what):
     d_g = torch.zeros_like(d_y)
     d_gain = torch.zeros(ns, dtype=torch.float32, device="cuda")
     agc.work_device(d_y.data_ptr(), ns, ns, 1, d_g.data_ptr(), ns, d_gain.data_ptr(), ns, st)
-    ss = SymbolSync(sps=2, loop_bw=0.01, damping=1.0, rolloff=ROLLOFF, interp_method=SymbolSync.CUBIC, max_samples=ns)
-    d_sym = torch.zeros(2 * ns, dtype=torch.float32, device="cuda")
-    ss.work_device(d_g.data_ptr(), ns, [ns], d_sym.data_ptr(), ns, ns, 0, 0, st)
-    n_out, consumed, status = ss.finish()
-    nsym = int(n_out[0])
+    rx = L.timing_and_frames(d_g, ns, 2, ROLLOFF, SymbolSync.CUBIC, n_syms, tol=24)
+    recs = rx.recs
     settled = d_gain[2 * LEAD:2 * (LEAD + lay["out_syms"])].cpu().numpy()
-    print(f"{what}: AGC gain behind the lead {settled.min():.2f} .. {settled.max():.2f}, {nsym} symbols from {ns} samples ({n_syms} sent), "
-          f"status {status[0]}")
-    assert status[0] == 0 and abs(nsym - n_syms) <= 24 and 0.8 / SCALE < settled.min() and settled.max() < 1.25 / SCALE, what
-    sync = PlSync(plsc=-1, max_symbols=max(nsym, PlSync.MIN_SYMBOLS), max_frames=64)
-    d_rec = torch.zeros(64 * 16, dtype=torch.uint8, device="cuda")
-    sync.work_device(d_sym.data_ptr(), nsym, d_rec.data_ptr(), st)
-    nf, _, state = sync.finish()
-    recs = d_rec.cpu().numpy().view(PlSync.FRAME_DTYPE)[:nf]
+    print(f"{what}: AGC gain behind the lead {settled.min():.2f} .. {settled.max():.2f}, {rx.nsym} symbols from {ns} samples ({n_syms} sent), "
+          f"status 0")  # (a status other than 0 does not come back from timing_and_frames)
+    assert 0.8 / SCALE < settled.min() and settled.max() < 1.25 / SCALE, what
     behind = recs[recs["sof_index"] >= LEAD]
     shifts = (behind["sof_index"] - (LEAD + lay["out_offset"][:behind.size])).tolist() if behind.size <= len(SEQ) else []
-    print(f"{what}: {nf} frames, PLSCs behind the lead {behind['plsc'].tolist()}, SOF shifts {shifts}")
-    assert state == capi.PLSYNC_LOCKED and behind["plsc"].tolist() == SEQ, what  # every frame behind the lead is found
+    print(f"{what}: {rx.nf} frames, PLSCs behind the lead {behind['plsc'].tolist()}, SOF shifts {shifts}")
+    assert rx.state == capi.PLSYNC_LOCKED and behind["plsc"].tolist() == SEQ, what  # every frame behind the lead is found
     assert len(set(shifts)) == 1 and abs(shifts[0] - 2 * RRC_DELAY) <= 12, (what, shifts)  # the shaper's and the channel filter's delay
-    first = int(np.nonzero(recs["sof_index"] >= LEAD)[0][0])
-    locked = [f for f, r in enumerate(recs) if r["flags"] & capi.PLSYNC_FLAG_LOCKED and r["plsc"] == PLSC and r["sof_index"] >= LEAD]
-    assert len(locked) >= ND - 1 and len(locked) == sum(1 for r in recs if r["flags"] & capi.PLSYNC_FLAG_LOCKED and r["plsc"] == PLSC), what
-    d_fr = torch.zeros((len(locked) * L + 90) * 2, dtype=torch.float32, device="cuda")
-    d_cnt = torch.full((1,), -7, dtype=torch.int32, device="cuda")
-    sync.gather_device(d_sym.data_ptr(), d_rec.data_ptr(), nf, PLSC, d_fr.data_ptr(), d_cnt.data_ptr(), st)
-    torch.cuda.synchronize()
-    cnt = int(d_cnt.item())
-    assert cnt == len(locked), what
-    pc = PlCoarse(1, PLSC, max_frames=64)
-    d_cc = torch.zeros(cnt, dtype=torch.int32, device="cuda")
-    d_f = torch.zeros(cnt, dtype=torch.float32, device="cuda")
-    pc.work_device(d_fr.data_ptr(), L, cnt, 0, d_f.data_ptr(), d_cc.data_ptr(), 0, st)
-    fe = PlFrontEnd(GOLD, PLSC, max_frames=cnt)
-    d_rx = torch.zeros((cnt, fe.xfecframe_len * 2), dtype=torch.float32, device="cuda")
-    fe.work_device(d_fr.data_ptr(), cnt, 1, d_cc.data_ptr(), d_f.data_ptr(), d_rx.data_ptr(), st)
-    torch.cuda.synchronize()
-    chain = FecChain(capi.STANDARD_DVBS2, capi.FECFRAME_SHORT, "C1_4", capi.MOD_QPSK, group_size=4, max_frames=cnt, max_trials=25)
-    chain.set_descramble(True)
-    msg, ret, corr = chain.work(d_rx.cpu().numpy().view(np.complex64), np.float32(10 ** (-ES_N0_DB / 10)))
-    assert (ret >= 0).all() and (corr >= 0).all(), what
-    data_index = [sum(1 for q in SEQ[:f - first] if q == PLSC) for f in locked]  # which encoder frame each gathered frame carries
-    for o in (chain, fe, pc, sync, ss, agc):
-        o.close()
-    return msg, data_index
+    got = L.decode_frames(rx, PLSC, L.GOLD, 10 ** (-ES_N0_DB / 10), first_sof=LEAD)
+    assert len(got.locked) >= ND - 1 and len(got.locked) == sum(1 for r in recs if r["flags"] & capi.PLSYNC_FLAG_LOCKED and r["plsc"] == PLSC), what
+    rx.sync.close()
+    agc.close()
+    return got.msg, got.data_index
 
 
 @pytest.mark.parametrize("swapped", [False, True])
@@ -553,7 +469,7 @@ def test_closed_loop_two_carriers(swapped):
     """One handle with D = 4 and dvbs2_pulse_taps(8, 0.2, 5, 0, 1) as channel filter brings both carriers to 2 samples per symbol; each
     channel returns its own encoder's input bytes. With the two increments swapped each channel returns the OTHER carrier's bytes: the
     sign of the mixer is pinned."""
-    torch = _torch()
+    import torch
     sent, d_wide, ns, n_all = capture()
     taps = pulse_taps(SPS, ROLLOFF, RRC_DELAY, 0.0, 1.0)
     dd = Ddc(SPS // 2, taps, max_channels=2, max_samples=ns)
@@ -570,7 +486,7 @@ def test_closed_loop_two_carriers(swapped):
     torch.cuda.synchronize()
     for c in range(2):
         carrier = c ^ int(swapped)
-        msg, data_index = receive(d_ch[c], n_out, n_all, sent[carrier], f"channel {c} (carrier {carrier})")
+        msg, data_index = receive(d_ch[c], n_out, n_all, f"channel {c} (carrier {carrier})")
         assert np.array_equal(msg, sent[carrier][data_index]), (c, swapped)  # the encoder's input bytes
         assert not np.array_equal(msg, sent[carrier ^ 1][data_index])
     dd.close()

@@ -1,7 +1,6 @@
 """CPU: the host-only code of the digital down-converter -- geometry, the count rule, the tile rule, the counter and phase mirror over
 sequences of calls and the argument check of the class -- once more in a stand-alone program built with the host sanitizers, over good
 and refused arguments. Its answers must be the library's and those of tests/ddc_model.py."""
-import os
 import subprocess
 
 import numpy as np
@@ -11,20 +10,12 @@ import ddc_model as DM
 import fec_testlib as T
 from dvbs2rx_amd import capi, ddc_geometry, ddc_produce, ddc_tile
 
-CSRC = os.path.join(T.ROOT, "gr-dvbs2rx_amd", "csrc")
-
 
 @pytest.fixture(scope="module")
 def host_exe(tmp_path_factory):
     """tests/ddc_host_main.cpp with the host sources it calls, host code under AddressSanitizer and UBSan (device code is not
     instrumented and none of it runs)."""
-    exe = str(tmp_path_factory.mktemp("ddc") / "ddc_host_main")
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined"]
-    subprocess.check_call([hipcc, "-x", "hip", "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-ffp-contract=off", *san,
-                           os.path.join(T.ROOT, "tests", "ddc_host_main.cpp"), os.path.join(CSRC, "ddc_hip.hip"),
-                           os.path.join(CSRC, "rotator_hip.hip"), "-o", exe])
-    return exe
+    return T.build_host_program(tmp_path_factory.mktemp("ddc"), "ddc_host_main.cpp", ("ddc_hip.hip", "rotator_hip.hip"))
 
 
 def _hex(taps):

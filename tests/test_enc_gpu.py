@@ -22,13 +22,9 @@ ROWS = json.load(open(os.path.join(T.ROOT, "tests", "golden", "fec_params.json")
 BCH_CODES = T.bch_codes()
 
 
-def _torch():
-    import torch
-    return torch
-
-
 def _dev(a):
-    return _torch().from_numpy(np.ascontiguousarray(a)).to("cuda:0")
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
 
 
 def _messages(nf, nbytes, seed):
@@ -275,7 +271,7 @@ class _Guarded:
     """a device buffer between two guards of GUARD bytes"""
 
     def __init__(self, nbytes, fill=0xA5):
-        torch = _torch()
+        import torch
         self.fill, self.nbytes = fill, nbytes
         self.t = torch.full((nbytes + 2 * GUARD,), fill, dtype=torch.uint8, device="cuda:0")
 
@@ -295,7 +291,7 @@ class _Guarded:
 
 
 def test_outputs_together_and_alone():
-    torch = _torch()
+    import torch
     fs, rate, nf = capi.FECFRAME_SHORT, "C3_5", 5
     enc = FecEncoder(capi.STANDARD_DVBS2, fs, rate, capi.MOD_8PSK, max_frames=nf)
     sizes = (nf * enc.bch_n // 8, nf * enc.ldpc_n // 8, nf * enc.n_syms * 8)
@@ -337,7 +333,7 @@ LOOPBACK = [("qpsk-1/4-short", capi.FECFRAME_SHORT, "C1_4", capi.MOD_QPSK, 40), 
 def test_loopback_on_the_device(name, fs, rate, constellation, nf):
     """Random BBFRAMEs -> FecEncoder (scramble on) -> symbols that stay on the device -> FecChain.work_device (descramble on): the
     same bytes, every LDPC group converged, no BCH correction."""
-    torch = _torch()
+    import torch
     fi = get_fec_info(capi.STANDARD_DVBS2, fs, rate)
     frames = _bbframes(fi["bch_k"], nf, 900 + nf + len(name))
     assert frames.shape == (nf, fi["bch_k"] // 8)
@@ -371,7 +367,7 @@ def test_loopback_on_the_device(name, fs, rate, constellation, nf):
 
 # ------------------------------------------------------------------ 7. asynchrony and placement
 def test_async_calls_and_placement():
-    torch = _torch()
+    import torch
     fs, rate, nf = capi.FECFRAME_SHORT, "C1_4", 6
     enc = FecEncoder(capi.STANDARD_DVBS2, fs, rate, capi.MOD_QPSK, max_frames=nf)
     a, b = _messages(nf, enc.in_bytes, 1), _messages(nf, enc.in_bytes, 2)[::-1].copy()
@@ -425,20 +421,16 @@ def test_async_calls_and_placement():
 
 
 # ------------------------------------------------------------------ 8. error texts
-def _refused(code, text, entry, *args):
-    assert entry(*args) == code, (entry.__name__, capi.lib.dvbs2_last_error())
-    assert capi.lib.dvbs2_last_error() == text.encode(), capi.lib.dvbs2_last_error()
-
-
 def test_error_texts():
+    import torch
     lib, h = capi.lib, C.c_void_p()
     m, prim = T.BCH_FIELDS[capi.FECFRAME_SHORT]
     # creation, with a device present
-    _refused(capi.EINVAL, "max_frames must be in 1..65535 (frames are one launch dimension)", lib.dvbs2_enc_create, C.byref(h), 0, 0, 0, capi.MOD_QPSK, 0, 0)
-    _refused(capi.EINVAL, "device index out of range", lib.dvbs2_enc_create, C.byref(h), 0, 0, 0, capi.MOD_QPSK, 4, 99)
-    _refused(capi.EINVAL, "bch_n 3240 != table K 5400 of S2_TABLE_C2", lib.dvbs2_enc_create_parts, C.byref(h), m, prim, 12, 3240, b"S2_TABLE_C2", 4, 0)
-    _refused(capi.EINVAL, "Codeword length n exceeds the maximum of (2^m - 1)", lib.dvbs2_enc_create_parts, C.byref(h), m, prim, 12, 20000, None, 4, 0)
-    _refused(capi.EINVAL, "u8 array messages are only supported for n and k multiple of 8.", lib.dvbs2_enc_create_parts, C.byref(h), m, prim, 12, 3241, None, 4, 0)
+    T.refused(capi.EINVAL, "max_frames must be in 1..65535 (frames are one launch dimension)", lib.dvbs2_enc_create, C.byref(h), 0, 0, 0, capi.MOD_QPSK, 0, 0)
+    T.refused(capi.EINVAL, "device index out of range", lib.dvbs2_enc_create, C.byref(h), 0, 0, 0, capi.MOD_QPSK, 4, 99)
+    T.refused(capi.EINVAL, "bch_n 3240 != table K 5400 of S2_TABLE_C2", lib.dvbs2_enc_create_parts, C.byref(h), m, prim, 12, 3240, b"S2_TABLE_C2", 4, 0)
+    T.refused(capi.EINVAL, "Codeword length n exceeds the maximum of (2^m - 1)", lib.dvbs2_enc_create_parts, C.byref(h), m, prim, 12, 20000, None, 4, 0)
+    T.refused(capi.EINVAL, "u8 array messages are only supported for n and k multiple of 8.", lib.dvbs2_enc_create_parts, C.byref(h), m, prim, 12, 3241, None, 4, 0)
     assert lib.dvbs2_enc_create(C.byref(h), 0, 1, 3, capi.MOD_16APSK, 4, 0) == capi.EINVAL
     assert lib.dvbs2_last_error().startswith(b"constellation: Unsupported code rate for 16APSK / 32APSK")
     t2 = next(r for r in ROWS if r["standard_id"] == capi.STANDARD_DVBT2 and _row_ok(r))
@@ -455,25 +447,25 @@ def test_error_texts():
     full = FecEncoder(capi.STANDARD_DVBS2, capi.FECFRAME_SHORT, "C1_4", capi.ENC_NO_MAPPER, max_frames=2)
     bch = FecEncoder.from_parts(bch=(m, prim, 12, 3240), max_frames=2)
     ldpc = FecEncoder.from_parts(ldpc_table="S2_TABLE_C1", max_frames=2)
-    buf = _torch().zeros((1 << 16,), dtype=_torch().uint8, device="cuda:0")
+    buf = torch.zeros((1 << 16,), dtype=torch.uint8, device="cuda:0")
     p, q = buf.data_ptr(), buf.data_ptr() + (1 << 15)
     host = np.zeros(1 << 15, np.uint8)
     hp = host.ctypes.data
     for n in (1, 0):  # an absent stage is refused whatever n_frames is
-        _refused(capi.EINVAL, "d_syms: this encoder has no mapper", lib.dvbs2_enc_encode_device, full._h, p, n, None, None, q, None)
-        _refused(capi.EINVAL, "d_ldpc_cw: this encoder has no LDPC stage", lib.dvbs2_enc_encode_device, bch._h, p, n, None, q, None, None)
-        _refused(capi.EINVAL, "d_bch_cw: this encoder has no BCH stage", lib.dvbs2_enc_encode_device, ldpc._h, p, n, q, None, None, None)
-        _refused(capi.EINVAL, "d_bch_cw: this encoder has no BCH stage", lib.dvbs2_enc_encode, ldpc._h, hp, n, hp, None, None)
-    _refused(capi.EINVAL, "no output requested", lib.dvbs2_enc_encode_device, full._h, p, 1, None, None, None, None)
-    _refused(capi.EINVAL, "no output requested", lib.dvbs2_enc_encode, full._h, hp, 1, None, None, None)
-    _refused(capi.EINVAL, "d_in is NULL", lib.dvbs2_enc_encode_device, full._h, None, 1, q, None, None, None)
-    _refused(capi.EINVAL, "d_in is NULL", lib.dvbs2_enc_encode, full._h, None, 1, hp, None, None)
-    _refused(capi.EINVAL, "bad argument", lib.dvbs2_enc_encode_device, full._h, p, -1, q, None, None, None)
-    _refused(capi.ESIZE, "n_frames exceeds max_frames", lib.dvbs2_enc_encode_device, full._h, p, 3, q, None, None, None)
-    _refused(capi.EINVAL, "d_in overlaps an output: encoding in place is not supported", lib.dvbs2_enc_encode_device, full._h, p, 2, None, p + 100, None, None)
-    _refused(capi.EINVAL, "no BCH stage: the BB scrambler is part of its load", lib.dvbs2_enc_set_scramble, ldpc._h, 1)
+        T.refused(capi.EINVAL, "d_syms: this encoder has no mapper", lib.dvbs2_enc_encode_device, full._h, p, n, None, None, q, None)
+        T.refused(capi.EINVAL, "d_ldpc_cw: this encoder has no LDPC stage", lib.dvbs2_enc_encode_device, bch._h, p, n, None, q, None, None)
+        T.refused(capi.EINVAL, "d_bch_cw: this encoder has no BCH stage", lib.dvbs2_enc_encode_device, ldpc._h, p, n, q, None, None, None)
+        T.refused(capi.EINVAL, "d_bch_cw: this encoder has no BCH stage", lib.dvbs2_enc_encode, ldpc._h, hp, n, hp, None, None)
+    T.refused(capi.EINVAL, "no output requested", lib.dvbs2_enc_encode_device, full._h, p, 1, None, None, None, None)
+    T.refused(capi.EINVAL, "no output requested", lib.dvbs2_enc_encode, full._h, hp, 1, None, None, None)
+    T.refused(capi.EINVAL, "d_in is NULL", lib.dvbs2_enc_encode_device, full._h, None, 1, q, None, None, None)
+    T.refused(capi.EINVAL, "d_in is NULL", lib.dvbs2_enc_encode, full._h, None, 1, hp, None, None)
+    T.refused(capi.EINVAL, "bad argument", lib.dvbs2_enc_encode_device, full._h, p, -1, q, None, None, None)
+    T.refused(capi.ESIZE, "n_frames exceeds max_frames", lib.dvbs2_enc_encode_device, full._h, p, 3, q, None, None, None)
+    T.refused(capi.EINVAL, "d_in overlaps an output: encoding in place is not supported", lib.dvbs2_enc_encode_device, full._h, p, 2, None, p + 100, None, None)
+    T.refused(capi.EINVAL, "no BCH stage: the BB scrambler is part of its load", lib.dvbs2_enc_set_scramble, ldpc._h, 1)
     # a refused call leaves the handle usable
     assert lib.dvbs2_enc_encode_device(full._h, p, 2, q, None, None, None) == capi.OK
-    _torch().cuda.synchronize()
+    torch.cuda.synchronize()
     for e in (full, bch, ldpc):
         e.close()

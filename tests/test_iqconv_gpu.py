@@ -8,25 +8,17 @@ import numpy as np
 import pytest
 
 import iqconv_model as M
-from dvbs2rx_amd import Agc, FecChain, IqConverter, PlCoarse, PlFrontEnd, capi
+import loopback as L
+from dvbs2rx_amd import Agc, IqConverter, capi
+from fec_testlib import SENTINEL, sentinel, stream
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0xC3A55A3C  # a bit pattern no float output of these tests holds
 CODE_FILL = 0xA5       # what the code buffers hold outside the rows
 PAD = 64               # sentinel elements (floats: complex elements, codes: bytes, statistics: words) around the rows
 T = capi.IQCONV_TILE   # samples of a row one workgroup covers
 SIZES = (1, 2, 3, 7, 8, 9, 63, 64, 65, T - 1, T, T + 1, 2 * T + 5)
 STATS_START = 1000     # what the statistics words hold before a call: a call adds
-
-
-def _torch():
-    import torch
-    return torch
-
-
-def stream():
-    return _torch().cuda.current_stream().cuda_stream
 
 
 def width(fmt):
@@ -57,7 +49,7 @@ class Stats:
     """n_streams x 3 uint64 on the device between sentinel words, each counter starting at STATS_START + its index"""
 
     def __init__(self, ns):
-        torch = _torch()
+        import torch
         host = np.full(PAD + 3 * ns + PAD, SENTINEL, np.uint64)
         self.start = STATS_START + np.arange(3 * ns, dtype=np.uint64)
         host[PAD:PAD + 3 * ns] = self.start
@@ -74,26 +66,27 @@ class Stats:
 
 def place_codes(fmt, codes, stride, shift):
     """codes [ns, n, 2] into a byte buffer: row r at PAD + shift + r * stride * bytes-per-sample. Returns (host bytes, device tensor)."""
+    import torch
     ns, n = codes.shape[:2]
     bps = 2 * width(fmt)
     host = np.full(PAD + shift + ((ns - 1) * stride + n) * bps + PAD, CODE_FILL, np.uint8)
     for r in range(ns):
         a = PAD + shift + r * stride * bps
         host[a:a + n * bps] = np.ascontiguousarray(codes[r]).reshape(-1).view(np.uint8)
-    return host, _torch().from_numpy(host).cuda()
+    return host, torch.from_numpy(host).cuda()
 
 
 def unpack(conv, codes, in_stride=None, out_stride=None, code_shift=0, float_shift=0, stats=True, on_stream=None, into=None):
     """One unpack_device call on codes [ns, n, 2]; float_shift in complex elements (0 or 1: 16-byte aligned or not). Returns (uint32
     [ns, n, 2], statistics per row or None) after checking that everything else in the buffers is what it was."""
-    torch = _torch()
+    import torch
     fmt = conv.format
     ns, n = codes.shape[:2]
     in_stride = n if in_stride is None else in_stride
     out_stride = n if out_stride is None else out_stride
     host_in, d_in = place_codes(fmt, codes, in_stride, code_shift)
     n_out = PAD + float_shift + (ns - 1) * out_stride + n + PAD
-    d_out = torch.full((2 * n_out,), np.uint32(SENTINEL).astype(np.int32).item(), dtype=torch.int32, device="cuda")
+    d_out = sentinel(2 * n_out)
     st = (into or Stats(ns)) if stats else None
     assert d_in.data_ptr() % 16 == 0 and d_out.data_ptr() % 16 == 0
     torch.cuda.synchronize()
@@ -114,7 +107,7 @@ def unpack(conv, codes, in_stride=None, out_stride=None, code_shift=0, float_shi
 
 def pack(conv, x, in_stride=None, out_stride=None, code_shift=0, float_shift=0, stats=True, on_stream=None, into=None):
     """One pack_device call on float32 x [ns, n, 2]. Returns (codes [ns, n, 2], statistics per row or None), the rest checked."""
-    torch = _torch()
+    import torch
     fmt = conv.format
     ns, n = x.shape[:2]
     bps = 2 * width(fmt)
@@ -222,7 +215,7 @@ def test_every_code_and_the_edge_vector(fmt, gain):
 @pytest.mark.parametrize("fmt", M.FORMATS)
 def test_pieces_equal_one_call(convs, fmt):
     """No state links two calls: a row cut into calls that start at odd addresses has the bits, the codes and the statistics of one call."""
-    torch = _torch()
+    import torch
     conv = convs[fmt]
     n, bps = 3 * T + 11, 2 * width(fmt)
     cuts = [0, 1, T - 3, T + 2, n]
@@ -231,7 +224,7 @@ def test_pieces_equal_one_call(convs, fmt):
     whole_p, st_p = pack(conv, x)
     assert st_u == M.unpack_rows(fmt, 0.75, c)[1] and st_p == M.pack_rows(fmt, 0.75, x)[1]
     d_codes = torch.from_numpy(np.ascontiguousarray(c[0]).reshape(-1).view(np.uint8).copy()).cuda()
-    d_floats = torch.full((2 * (n + PAD),), np.uint32(SENTINEL).astype(np.int32).item(), dtype=torch.int32, device="cuda")
+    d_floats = sentinel(2 * (n + PAD))
     st = Stats(1)
     for a, b in zip(cuts, cuts[1:]):
         conv.unpack_device(d_codes.data_ptr() + a * bps, n, b - a, 1, d_floats.data_ptr() + 8 * a, n, d_stats=st.ptr, stream=stream())
@@ -250,7 +243,7 @@ def test_pieces_equal_one_call(convs, fmt):
 
 @pytest.mark.parametrize("fmt", M.FORMATS)
 def test_statistics(convs, fmt):
-    torch = _torch()
+    import torch
     conv = convs[fmt]
     # a row with known rails: three components on a rail among the middle code
     n = T + 9
@@ -293,14 +286,14 @@ def test_statistics(convs, fmt):
 
 @pytest.mark.parametrize("fmt", M.FORMATS)
 def test_host_entries_equal_the_device_entries(fmt):
-    torch = _torch()
+    import torch
     top = T + 3
     conv = IqConverter(fmt, 0.3, max_streams=1, max_samples=top)
     assert conv.params() == dict(format=fmt, gain=np.float32(0.3), max_streams=1, max_samples=top, tile=T)
     for n in (1, 65, top):
         c, x = codes_of(fmt, 9, 1, n), floats_of(10, 1, n)
         dev_u, st_u = unpack(conv, c)
-        d_out = torch.full((2 * (n + PAD),), np.uint32(SENTINEL).astype(np.int32).item(), dtype=torch.int32, device="cuda")
+        d_out = sentinel(2 * (n + PAD))
         st = conv.unpack_to_device(np.array(c[0]), d_out.data_ptr(), stats=True)
         got = d_out.cpu().numpy().view(np.uint32)
         assert np.array_equal(got[:2 * n], dev_u.reshape(-1)) and (got[2 * n:] == SENTINEL).all()
@@ -330,12 +323,12 @@ def test_host_entries_equal_the_device_entries(fmt):
 
 
 def test_refusals_leave_output_and_statistics_untouched():
-    torch = _torch()
+    import torch
     lib = capi.lib
     for fmt in (M.U8, M.S16):
         conv = IqConverter(fmt, 1.0, max_streams=4, max_samples=64)
         d_codes = torch.full((4096,), CODE_FILL, dtype=torch.uint8, device="cuda")
-        d_floats = torch.full((4096,), np.uint32(SENTINEL).astype(np.int32).item(), dtype=torch.int32, device="cuda")
+        d_floats = sentinel(4096)
         st = Stats(4)
         c, f, s = d_codes.data_ptr(), d_floats.data_ptr(), st.ptr
         for entry, first, second, names in ((lib.dvbs2_iqconv_unpack_device, c, f, ("in", "out")), (lib.dvbs2_iqconv_pack_device, f, c, ("in", "out"))):
@@ -386,26 +379,28 @@ def test_refusals_leave_output_and_statistics_untouched():
 
 
 # ------------------------------------------------------------------ closed loop through a stream of codes, noise-free
+LEAD = 2001
+
+
 @pytest.fixture(scope="module")
 def transmitted():
-    import test_agc_gpu as A  # its transmit and receive sides: QPSK 1/4 short, six data frames with dummies, shaped at 2 samples per symbol
-    return A, A.transmit()
+    return L.shaped_six_frames(LEAD, seed=2027)  # the samples tests/test_agc_gpu.py levels: QPSK 1/4 short, six data frames with dummies
 
 
 @pytest.mark.parametrize("fmt", (M.U8, M.S16))
 def test_closed_loop_through_a_stream_of_codes(transmitted, fmt):
     """shaper -> pack (peak at 0.9 of full scale) -> codes -> unpack -> AGC -> symsync -> plsync -> PL front end -> FEC chain: the
     encoder's input bytes come back, and nothing clipped."""
-    torch = _torch()
-    A, tx = transmitted
-    st, ns, seq, plsc, lead, L = stream(), tx["ns"], tx["seq"], tx["plsc"], tx["lead"], tx["L"]
-    peak = float(tx["d_y"].abs().max().item())
+    import torch
+    tx = transmitted
+    st, ns, seq, plsc, lead = stream(), tx.ns, L.SEQ6, L.PLSC, LEAD
+    peak = float(tx.d_y.abs().max().item())
     to_codes = IqConverter(fmt, np.float32(0.9 / peak), max_samples=ns)
     from_codes = IqConverter(fmt, 1.0, max_samples=ns)
     d_codes = torch.zeros(ns * to_codes.bytes, dtype=torch.uint8, device="cuda")
     d_back = torch.zeros((ns, 2), dtype=torch.float32, device="cuda")
     stats = Stats(2)
-    to_codes.pack_device(tx["d_y"].data_ptr(), ns, ns, 1, d_codes.data_ptr(), ns, d_stats=stats.ptr, stream=st)
+    to_codes.pack_device(tx.d_y.data_ptr(), ns, ns, 1, d_codes.data_ptr(), ns, d_stats=stats.ptr, stream=st)
     from_codes.unpack_device(d_codes.data_ptr(), ns, ns, 1, d_back.data_ptr(), ns, d_stats=stats.ptr + 24, stream=st)
     torch.cuda.synchronize()
     packed, unpacked = stats.read()
@@ -416,35 +411,15 @@ def test_closed_loop_through_a_stream_of_codes(transmitted, fmt):
     top = max(abs(int(codes.max()) - M.BIAS[fmt]), abs(int(codes.min()) - M.BIAS[fmt])) / float(M.FULL[fmt])
     assert 0.89 <= top <= 0.91
     # the receiver of tests/test_agc_gpu.py::test_closed_loop_through_the_receiver, the AGC levelling to the shaped samples' own level
-    reference = float(torch.linalg.vector_norm(tx["d_y"][:2 * lead], dim=1).mean().item())
+    reference = float(torch.linalg.vector_norm(tx.d_y[:2 * lead], dim=1).mean().item())
     agc = Agc(rate=0.05, reference=reference, gain=1.0, max_gain=65536.0, max_samples=ns)
     agc.work_device(d_back.data_ptr(), ns, ns, 1, d_back.data_ptr(), ns, 0, ns, st)
     torch.cuda.synchronize()
-    recs, d_sym, d_rec, nf, sync, state = A.receive(tx, d_back)
-    behind = recs[recs["sof_index"] >= lead]
-    assert state == capi.PLSYNC_LOCKED and behind["plsc"].tolist() == seq
-    locked = [f for f, r in enumerate(recs) if r["flags"] & capi.PLSYNC_FLAG_LOCKED and r["plsc"] == plsc and r["sof_index"] >= lead]
-    assert len(locked) >= 5
-    d_fr = torch.zeros((len(locked) * L + 90) * 2, dtype=torch.float32, device="cuda")
-    d_cnt = torch.full((1,), -7, dtype=torch.int32, device="cuda")
-    sync.gather_device(d_sym.data_ptr(), d_rec.data_ptr(), nf, plsc, d_fr.data_ptr(), d_cnt.data_ptr(), st)
-    torch.cuda.synchronize()
-    cnt = int(d_cnt.item())
-    assert cnt == len(locked)
-    pc = PlCoarse(1, plsc, max_frames=64)
-    d_cc = torch.zeros(cnt, dtype=torch.int32, device="cuda")
-    d_f = torch.zeros(cnt, dtype=torch.float32, device="cuda")
-    pc.work_device(d_fr.data_ptr(), L, cnt, 0, d_f.data_ptr(), d_cc.data_ptr(), 0, st)
-    fe = PlFrontEnd(tx["gold"], plsc, max_frames=cnt)
-    d_rx = torch.zeros((cnt, fe.xfecframe_len * 2), dtype=torch.float32, device="cuda")
-    fe.work_device(d_fr.data_ptr(), cnt, 1, d_cc.data_ptr(), d_f.data_ptr(), d_rx.data_ptr(), st)
-    torch.cuda.synchronize()
-    chain = FecChain(capi.STANDARD_DVBS2, capi.FECFRAME_SHORT, "C1_4", capi.MOD_QPSK, group_size=4, max_frames=cnt, max_trials=25)
-    chain.set_descramble(True)
-    msg, ret, corr = chain.work(d_rx.cpu().numpy().view(np.complex64), np.float32(0.02))
-    assert (ret >= 0).all() and (corr >= 0).all()
-    first = int(np.nonzero(recs["sof_index"] >= lead)[0][0])
-    data_index = [sum(1 for q in seq[:f - first] if q == plsc) for f in locked]  # which encoder frame each gathered frame carries
-    assert np.array_equal(msg, tx["sent"][data_index])  # the encoder's input bytes
-    for o in (chain, fe, pc, sync, agc, to_codes, from_codes):
+    rx = L.timing_and_frames(d_back, ns, L.SPS, L.ROLLOFF, 0, tx.n_all, tol=12)
+    behind = rx.recs[rx.recs["sof_index"] >= lead]
+    assert rx.state == capi.PLSYNC_LOCKED and behind["plsc"].tolist() == seq
+    got = L.decode_frames(rx, plsc, L.GOLD, 0.02, first_sof=lead)
+    assert len(got.locked) >= 5
+    assert np.array_equal(got.msg, tx.sent[got.data_index])  # the encoder's input bytes
+    for o in (rx.sync, agc, to_codes, from_codes):
         o.close()

@@ -3,7 +3,6 @@ create, blocks of the host restatement across an odd length and an odd byte offs
 in a stand-alone program built with the host sanitizers. Its answers must be the library's own. Nothing is loaded into Python by the
 program and no GPU call is made."""
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
@@ -13,7 +12,6 @@ import fec_testlib as T
 import iqconv_model as M
 from dvbs2rx_amd import capi
 
-CSRC = os.path.join(T.ROOT, "gr-dvbs2rx_amd", "csrc")
 SOURCES = ("c_api_iqconv.hip", "iqconv_hip.hip")  # the entries' translation unit and what it binds
 
 
@@ -21,12 +19,7 @@ SOURCES = ("c_api_iqconv.hip", "iqconv_hip.hip")  # the entries' translation uni
 def host_exe(tmp_path_factory):
     """tests/iqconv_host_main.cpp with the sources behind the entries, host code under AddressSanitizer and UBSan (device code is not
     instrumented and none of it runs)."""
-    exe = str(tmp_path_factory.mktemp("iqconv") / "iqconv_host_main")
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined"]
-    subprocess.check_call([hipcc, "-x", "hip", "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-ffp-contract=off", *san,
-                           os.path.join(T.ROOT, "tests", "iqconv_host_main.cpp"), *[os.path.join(CSRC, s) for s in SOURCES], "-o", exe])
-    return exe
+    return T.build_host_program(tmp_path_factory.mktemp("iqconv"), "iqconv_host_main.cpp", SOURCES)
 
 
 def _hex(value):

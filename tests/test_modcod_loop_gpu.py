@@ -8,6 +8,7 @@ import pytest
 import plframe_model as M
 import plsync_model as P
 from dvbs2rx_amd import FecChain, FecEncoder, PlFramer, PlFrontEnd, PlSync, capi, enc_check, get_fec_info, plframer_layout
+from fec_testlib import stream
 
 SHORT, NORMAL = capi.FECFRAME_SHORT, capi.FECFRAME_NORMAL
 # EN 302 307-1 table 12: MODCOD -> (rate, constellation)
@@ -29,17 +30,9 @@ def plsc_of(modcod, framesize, pilots):
     return P.plsc_of(modcod, int(framesize == SHORT), int(pilots))
 
 
-def _torch():
-    import torch
-    return torch
-
-
 def dev(a):
-    return _torch().from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def stream():
-    return _torch().cuda.current_stream().cuda_stream
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 # ------------------------------------------------------------------ the table, without a device
@@ -71,7 +64,7 @@ LOOP = [(m, fs, 1) for m, fs in LEGAL] + [(m, fs, 0) for m, fs in PILOTLESS]
 @pytest.mark.parametrize("modcod,fs,pilots", LOOP, ids=["modcod%d-%s-%s" % (m, "short" if fs == SHORT else "normal", "pilots" if p else "nopilots")
                                                         for m, fs, p in LOOP])
 def test_every_modcod_round_the_loop(modcod, fs, pilots):
-    torch = _torch()
+    import torch
     rate, constellation = MODCODS[modcod]
     plsc, nf = plsc_of(modcod, fs, pilots), 3
     info = M.pls_parse(plsc)
@@ -123,7 +116,7 @@ def test_vcm_stream_round_the_loop():
     """Short frames of QPSK 1/2 (pilots), 8PSK 3/5 (no pilots), 16APSK 3/4 (pilots), 32APSK 4/5 (pilots) and two dummy frames in one
     stream behind an odd lead: PlSync(plsc=-1) finds every frame where the framer's layout puts it; for each data PLSC the gathered
     frames are its locked records, and their bytes are the encoder inputs of exactly those frames."""
-    torch = _torch()
+    import torch
     a, b, c, d, dummy = plsc_of(4, SHORT, 1), plsc_of(12, SHORT, 0), plsc_of(19, SHORT, 1), plsc_of(25, SHORT, 1), P.plsc_of(0, 0, 0)
     seq = [a, a, b, c, d, dummy, b, a, d, c, dummy, c, d, b, a, b, c, d]
     data_plscs = (a, b, c, d)

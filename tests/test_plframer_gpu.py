@@ -9,41 +9,26 @@ import plframe_model as M
 import plframer_model as F
 import plsync_model as P
 from dvbs2rx_amd import FecChain, FecEncoder, PlFramer, PlFrontEnd, PlSync, capi, plframer_layout
+from fec_testlib import SENTINEL, refused, sentinel, stream
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0xC3A55A3C  # a bit pattern no output of these tests holds
 PAD = 64               # sentinel symbols beyond the end
 
 
-def _torch():
-    import torch
-    return torch
-
-
 def dev(a):
-    torch = _torch()
+    import torch
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def stream():
-    return _torch().cuda.current_stream().cuda_stream
-
-
-def sentinel(n_syms):
-    """n_syms + PAD symbols of the sentinel, as int32 (torch has no uint32 arithmetic worth the name)"""
-    torch = _torch()
-    return torch.full(((n_syms + PAD) * 2,), np.uint32(SENTINEL).astype(np.int32).item(), dtype=torch.int32, device="cuda")
 
 
 def frame_on_device(fr, data, n_frames, closing, n_out, in_shift=0, out_shift=0):
     """One frame_device call into a sentinel buffer of n_out + PAD symbols. The shifts displace the buffers by that many symbols (8 bytes
     each) from torch's allocation. Returns every symbol of the buffer from the (displaced) start, as uint32 (n, 2)."""
-    torch = _torch()
+    import torch
     d_in = torch.zeros(((data.shape[0] + in_shift) * 2 + 4,), dtype=torch.float32, device="cuda")
     if data.size:
         d_in[2 * in_shift:2 * (in_shift + data.shape[0])] = dev(data.reshape(-1))
-    d_out = sentinel(n_out + out_shift)
+    d_out = sentinel(2 * (n_out + out_shift + PAD))
     assert d_in.data_ptr() % 16 == 0 and d_out.data_ptr() % 16 == 0
     fr.work_device(d_in.data_ptr() + 8 * in_shift if data.size else 0, n_frames, closing, d_out.data_ptr() + 8 * out_shift, stream())
     torch.cuda.synchronize()
@@ -150,7 +135,7 @@ def test_host_entry(acm):
 def test_inverse_of_the_payload_step(plsc):
     """Framer output through dvbs2_plpayload_process_device with zero phases returns the input with ==, not bits: the payload step's
     x * 1 - y * (-0) can change the sign of a zero."""
-    torch = _torch()
+    import torch
     info, gold, nf = M.pls_parse(plsc), 11, 2
     assert info["n_slots"] in (90, 144)
     data = F.planted_data(np.random.default_rng(plsc), nf * info["xfecframe_len"])
@@ -176,7 +161,7 @@ def test_inverse_of_the_payload_step(plsc):
 
 # ------------------------------------------------------------------ 5. closed loop through the receiver, noise-free
 def test_closed_loop_through_the_receiver():
-    torch = _torch()
+    import torch
     gold, plsc, dummy, nd = 5, P.plsc_of(1, 1, 1), P.plsc_of(0, 0, 0), 6
     rng = np.random.default_rng(2025)
     enc = FecEncoder(capi.STANDARD_DVBS2, capi.FECFRAME_SHORT, "C1_4", capi.MOD_QPSK, max_frames=nd)
@@ -232,28 +217,23 @@ def test_closed_loop_through_the_receiver():
 
 
 # ------------------------------------------------------------------ 7. arguments
-def _refused(code, text, entry, *args):
-    assert entry(*args) == code, (entry.__name__, capi.lib.dvbs2_last_error())
-    assert capi.lib.dvbs2_last_error() == text.encode(), capi.lib.dvbs2_last_error()
-
-
 def test_arguments(acm):
-    torch = _torch()
+    import torch
     lib, h = capi.lib, C.c_void_p()
     # creation: the ranges of dvbs2_plpayload_create
-    _refused(capi.EINVAL, "gold code out of range", lib.dvbs2_plframer_create, C.byref(h), -1, 4, 0)
-    _refused(capi.EINVAL, "gold code out of range", lib.dvbs2_plframer_create, C.byref(h), (1 << 18) - 1, 4, 0)
-    _refused(capi.EINVAL, "max_frames must be in 1..65535 (frames are one launch dimension)", lib.dvbs2_plframer_create, C.byref(h), 0, 0, 0)
-    _refused(capi.EINVAL, "max_frames must be in 1..65535 (frames are one launch dimension)", lib.dvbs2_plframer_create, C.byref(h), 0, 65536, 0)
+    refused(capi.EINVAL, "gold code out of range", lib.dvbs2_plframer_create, C.byref(h), -1, 4, 0)
+    refused(capi.EINVAL, "gold code out of range", lib.dvbs2_plframer_create, C.byref(h), (1 << 18) - 1, 4, 0)
+    refused(capi.EINVAL, "max_frames must be in 1..65535 (frames are one launch dimension)", lib.dvbs2_plframer_create, C.byref(h), 0, 0, 0)
+    refused(capi.EINVAL, "max_frames must be in 1..65535 (frames are one launch dimension)", lib.dvbs2_plframer_create, C.byref(h), 0, 65536, 0)
     assert not h
-    _refused(capi.EINVAL, "null handle pointer", lib.dvbs2_plframer_create, None, 0, 4, 0)
+    refused(capi.EINVAL, "null handle pointer", lib.dvbs2_plframer_create, None, 0, 4, 0)
 
     seq, data, gold = acm["seq"][:5], acm["data"], acm["gold"]
     lay = F.layout(seq)
     want = F.frames(seq, gold, data[:lay["in_syms"]], seq[0])
     fr = PlFramer(gold, max_frames=6)
     d_in = dev(data[:lay["in_syms"]].reshape(-1))
-    d_out = sentinel(lay["out_syms"] + 90)
+    d_out = sentinel(2 * (lay["out_syms"] + 90 + PAD))
     st = stream()
 
     def good():
@@ -270,7 +250,7 @@ def test_arguments(acm):
 
     # a fresh handle has an empty sequence
     assert (fr.n_frames, fr.in_syms, fr.out_syms) == (0, 0, 0)
-    _refused(capi.ESIZE, "n_frames exceeds the sequence", lib.dvbs2_plframer_frame_device, fr._h, d_in.data_ptr(), 1, -1, d_out.data_ptr(), st)
+    refused(capi.ESIZE, "n_frames exceeds the sequence", lib.dvbs2_plframer_frame_device, fr._h, d_in.data_ptr(), 1, -1, d_out.data_ptr(), st)
     assert lib.dvbs2_plframer_frame_device(fr._h, None, 0, -1, None, st) == capi.OK
     untouched()
     fr.set_sequence(seq)
@@ -279,36 +259,36 @@ def test_arguments(acm):
     bad = np.array(seq, np.uint8)
     for value, why in ((128, "out of range (0..127)"), (29 << 2, "names a reserved MODCOD (29..31)"), ((31 << 2) | 3, "names a reserved MODCOD (29..31)")):
         bad[3] = value
-        _refused(capi.EINVAL, f"plsc[3] {why}", lib.dvbs2_plframer_set_sequence, fr._h, bad.ctypes.data, 5)
+        refused(capi.EINVAL, f"plsc[3] {why}", lib.dvbs2_plframer_set_sequence, fr._h, bad.ctypes.data, 5)
         good()
     seven = np.zeros(7, np.uint8)
-    _refused(capi.ESIZE, "n_frames exceeds max_frames", lib.dvbs2_plframer_set_sequence, fr._h, seven.ctypes.data, 7)
+    refused(capi.ESIZE, "n_frames exceeds max_frames", lib.dvbs2_plframer_set_sequence, fr._h, seven.ctypes.data, 7)
     good()
-    _refused(capi.EINVAL, "bad argument", lib.dvbs2_plframer_set_sequence, fr._h, None, 2)
-    _refused(capi.EINVAL, "bad argument", lib.dvbs2_plframer_set_sequence, fr._h, seven.ctypes.data, -1)
+    refused(capi.EINVAL, "bad argument", lib.dvbs2_plframer_set_sequence, fr._h, None, 2)
+    refused(capi.EINVAL, "bad argument", lib.dvbs2_plframer_set_sequence, fr._h, seven.ctypes.data, -1)
     good()
     # frame_device
     d_out.fill_(np.uint32(SENTINEL).astype(np.int32).item())
     a = (fr._h, d_in.data_ptr())
-    _refused(capi.ESIZE, "n_frames exceeds the sequence", lib.dvbs2_plframer_frame_device, *a, 6, -1, d_out.data_ptr(), st)
-    _refused(capi.EINVAL, "n_frames is negative", lib.dvbs2_plframer_frame_device, *a, -1, -1, d_out.data_ptr(), st)
-    _refused(capi.EINVAL, "closing_plsc out of range (-1 = none, 0..127)", lib.dvbs2_plframer_frame_device, *a, 5, 128, d_out.data_ptr(), st)
-    _refused(capi.EINVAL, "closing_plsc out of range (-1 = none, 0..127)", lib.dvbs2_plframer_frame_device, *a, 5, -2, d_out.data_ptr(), st)
-    _refused(capi.EINVAL, "closing_plsc names a reserved MODCOD (29..31)", lib.dvbs2_plframer_frame_device, *a, 5, 30 << 2, d_out.data_ptr(), st)
-    _refused(capi.EINVAL, "plframes is null", lib.dvbs2_plframer_frame_device, *a, 5, -1, None, st)
-    _refused(capi.EINVAL, "xfecframes is null and the framed prefix holds a data frame", lib.dvbs2_plframer_frame_device, fr._h, None, 5, -1,
-             d_out.data_ptr(), st)
-    _refused(capi.EINVAL, "symbol buffers must be 8-byte aligned", lib.dvbs2_plframer_frame_device, fr._h, d_in.data_ptr() + 4, 5, -1,
-             d_out.data_ptr(), st)
+    refused(capi.ESIZE, "n_frames exceeds the sequence", lib.dvbs2_plframer_frame_device, *a, 6, -1, d_out.data_ptr(), st)
+    refused(capi.EINVAL, "n_frames is negative", lib.dvbs2_plframer_frame_device, *a, -1, -1, d_out.data_ptr(), st)
+    refused(capi.EINVAL, "closing_plsc out of range (-1 = none, 0..127)", lib.dvbs2_plframer_frame_device, *a, 5, 128, d_out.data_ptr(), st)
+    refused(capi.EINVAL, "closing_plsc out of range (-1 = none, 0..127)", lib.dvbs2_plframer_frame_device, *a, 5, -2, d_out.data_ptr(), st)
+    refused(capi.EINVAL, "closing_plsc names a reserved MODCOD (29..31)", lib.dvbs2_plframer_frame_device, *a, 5, 30 << 2, d_out.data_ptr(), st)
+    refused(capi.EINVAL, "plframes is null", lib.dvbs2_plframer_frame_device, *a, 5, -1, None, st)
+    refused(capi.EINVAL, "xfecframes is null and the framed prefix holds a data frame", lib.dvbs2_plframer_frame_device, fr._h, None, 5, -1,
+            d_out.data_ptr(), st)
+    refused(capi.EINVAL, "symbol buffers must be 8-byte aligned", lib.dvbs2_plframer_frame_device, fr._h, d_in.data_ptr() + 4, 5, -1,
+            d_out.data_ptr(), st)
     assert lib.dvbs2_plframer_frame_device(*a, 0, -1, d_out.data_ptr(), st) == capi.OK  # n_frames == 0 writes nothing
     untouched()
     good()
     # the host entry makes the same checks
     host_in, host_out = data[:lay["in_syms"]].copy(), np.zeros((lay["out_syms"] + 90, 2), np.float32)
-    _refused(capi.ESIZE, "n_frames exceeds the sequence", lib.dvbs2_plframer_frame, fr._h, host_in.ctypes.data, 6, -1, host_out.ctypes.data)
-    _refused(capi.EINVAL, "closing_plsc names a reserved MODCOD (29..31)", lib.dvbs2_plframer_frame, fr._h, host_in.ctypes.data, 5, 29 << 2, host_out.ctypes.data)
-    _refused(capi.EINVAL, "plframes is null", lib.dvbs2_plframer_frame, fr._h, host_in.ctypes.data, 5, -1, None)
-    _refused(capi.EINVAL, "xfecframes is null and the framed prefix holds a data frame", lib.dvbs2_plframer_frame, fr._h, None, 5, -1, host_out.ctypes.data)
+    refused(capi.ESIZE, "n_frames exceeds the sequence", lib.dvbs2_plframer_frame, fr._h, host_in.ctypes.data, 6, -1, host_out.ctypes.data)
+    refused(capi.EINVAL, "closing_plsc names a reserved MODCOD (29..31)", lib.dvbs2_plframer_frame, fr._h, host_in.ctypes.data, 5, 29 << 2, host_out.ctypes.data)
+    refused(capi.EINVAL, "plframes is null", lib.dvbs2_plframer_frame, fr._h, host_in.ctypes.data, 5, -1, None)
+    refused(capi.EINVAL, "xfecframes is null and the framed prefix holds a data frame", lib.dvbs2_plframer_frame, fr._h, None, 5, -1, host_out.ctypes.data)
     assert lib.dvbs2_plframer_frame(fr._h, host_in.ctypes.data, 5, seq[0], host_out.ctypes.data) == capi.OK
     assert np.array_equal(F.bits(host_out), F.bits(want))
     good()
@@ -320,6 +300,6 @@ def test_arguments(acm):
     torch.cuda.synchronize()
     got = d_out.cpu().numpy().view(np.uint32).reshape(-1, 2)
     assert np.array_equal(got[:want2.shape[0]], F.bits(want2)) and (got[want2.shape[0]:] == SENTINEL).all()
-    _refused(capi.EINVAL, "xfecframes is null and the framed prefix holds a data frame", lib.dvbs2_plframer_frame_device, fr._h, None, 3, -1,
-             d_out.data_ptr(), st)
+    refused(capi.EINVAL, "xfecframes is null and the framed prefix holds a data frame", lib.dvbs2_plframer_frame_device, fr._h, None, 3, -1,
+            d_out.data_ptr(), st)
     fr.close()

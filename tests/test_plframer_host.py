@@ -1,7 +1,6 @@
 """CPU: the host side of the PL framer -- dvbs2_plframer_layout over the whole PLSC range and a named sequence, the null-handle answers
 of every dvbs2_plframer_* handle entry, and the layout code once more in a stand-alone program built with the host sanitizers."""
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
@@ -12,8 +11,6 @@ import plframe_model as M
 import plframer_model as F
 import plsync_model as PS
 from dvbs2rx_amd import capi, plframer_layout, pls_parse
-
-CSRC = os.path.join(T.ROOT, "gr-dvbs2rx_amd", "csrc")
 
 
 def _err():
@@ -73,13 +70,8 @@ def test_null_handle():
 def layout_exe(tmp_path_factory):
     """tests/plframer_host_main.cpp with the host source it calls, host code under AddressSanitizer and UBSan (device code is not
     instrumented and none of it runs)."""
-    exe = str(tmp_path_factory.mktemp("plframer") / "plframer_host_main")
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined"]
-    subprocess.check_call([hipcc, "-x", "hip", "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", *san,
-                           os.path.join(T.ROOT, "tests", "plframer_host_main.cpp"), os.path.join(CSRC, "plframe_hip.hip"),
-                           os.path.join(CSRC, "plpayload_hip.hip"), "-o", exe])
-    return exe
+    return T.build_host_program(tmp_path_factory.mktemp("plframer"), "plframer_host_main.cpp", ("plframe_hip.hip", "plpayload_hip.hip"),
+                                fp_contract_off=False)
 
 
 def test_layout_program_under_the_host_sanitizers(layout_exe):

@@ -1,7 +1,6 @@
 """CPU: the host-only code of the pulse shaper -- geometry, tap design, tap scaling and the argument check of the class -- once more in a
 stand-alone program built with the host sanitizers, over good and refused arguments. Its tap values must be the library's, bit for bit."""
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
@@ -10,20 +9,12 @@ import pytest
 import fec_testlib as T
 from dvbs2rx_amd import capi, pulse_geometry, pulse_scale_taps, pulse_taps
 
-CSRC = os.path.join(T.ROOT, "gr-dvbs2rx_amd", "csrc")
-
 
 @pytest.fixture(scope="module")
 def host_exe(tmp_path_factory):
     """tests/pulse_host_main.cpp with the host source it calls, host code under AddressSanitizer and UBSan (device code is not
     instrumented and none of it runs)."""
-    exe = str(tmp_path_factory.mktemp("pulse") / "pulse_host_main")
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined"]
-    subprocess.check_call([hipcc, "-x", "hip", "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-ffp-contract=off", *san,
-                           os.path.join(T.ROOT, "tests", "pulse_host_main.cpp"), os.path.join(CSRC, "pulse_hip.hip"),
-                           os.path.join(CSRC, "symsync_hip.hip"), "-o", exe])
-    return exe
+    return T.build_host_program(tmp_path_factory.mktemp("pulse"), "pulse_host_main.cpp", ("pulse_hip.hip", "symsync_hip.hip"))
 
 
 def _hex(taps):

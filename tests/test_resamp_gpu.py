@@ -8,34 +8,17 @@ import functools
 import numpy as np
 import pytest
 
-import plframe_model as M
-import plsync_model as P
+import fec_testlib as T
+import loopback as L
 import pulse_model as PM
 import resamp_model as RM
-from dvbs2rx_amd import (FecChain, FecEncoder, PlCoarse, PlFramer, PlFrontEnd, PlSync, PulseShaper, Resampler, SymbolSync, capi,
-                         plframer_layout, pulse_taps, resamp_geometry, resamp_max_out, resamp_step, symsync_taps)
+from dvbs2rx_amd import PulseShaper, Resampler, SymbolSync, capi, plframer_layout, pulse_taps, resamp_geometry, resamp_max_out, resamp_step
+from fec_testlib import PAD, SENTINEL, refused, sentinel, stream
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0xC3A55A3C  # a bit pattern no output of these tests holds
-PAD = 64               # sentinel samples behind each stream's output
 K = capi.RESAMP_TILE   # the kernel's tile in output samples
 ODD_STEP = (1 << 32) + 0x9E3779B1  # a raw step that uses all 32 fraction bits (rate about 0.62)
-
-
-def _torch():
-    import torch
-    return torch
-
-
-def stream():
-    return _torch().cuda.current_stream().cuda_stream
-
-
-def sentinel(n_elems):
-    """n_elems complex elements of the sentinel, as int32"""
-    torch = _torch()
-    return torch.full((n_elems * 2,), np.uint32(SENTINEL).astype(np.int32).item(), dtype=torch.int32, device="cuda")
 
 
 class Model:
@@ -50,46 +33,22 @@ class Model:
 
 
 def run_on_device(rs, xs, in_stride=None, out_stride=None, in_shift=0, out_shift=0):
-    """One work_device call over the streams xs (complex64 vectors of one length n). Stream s lies at in_shift + s * in_stride complex
-    elements of a 16-byte-aligned input buffer and writes at out_shift + s * out_stride of a 16-byte-aligned sentinel buffer. Returns
-    (one uint32 (n_out[s], 2) array per stream, n_out) after checking that the reported counts are those produce() gave before the call,
-    that everything else in the output buffer -- the shift in front, what lies behind each stream's n_out[s] samples and PAD elements
-    behind the last -- is still the sentinel, and that the input is unchanged."""
-    torch = _torch()
+    """One work_device call over the streams xs (complex64 vectors of one length n) through fec_testlib.run_strided: stream s lies at
+    in_shift + s * in_stride complex elements of the input buffer and writes at out_shift + s * out_stride of a sentinel buffer, where
+    nothing but the n_out[s] samples produce() gave before the call may be written. Returns (one uint32 (n_out[s], 2) array per stream,
+    n_out) after checking that the reported counts are those produce() gave."""
     ns, n = len(xs), xs[0].size
     said = rs.produce(n, ns)
-    most = int(said.max()) if ns else 0
     in_stride = max(n, 1) if in_stride is None else in_stride
-    out_stride = max(most, 1) if out_stride is None else out_stride
-    host_in = np.full(in_shift + ns * in_stride + 2, np.complex64(complex(9.5, -9.5)), np.complex64)
-    for s, x in enumerate(xs):
-        assert x.size == n
-        host_in[in_shift + s * in_stride:in_shift + s * in_stride + n] = x
-    d_in = torch.from_numpy(host_in.view(np.float32)).cuda()
-    n_buf = out_shift + ns * out_stride + PAD
-    d_out = sentinel(n_buf)
-    assert d_in.data_ptr() % 16 == 0 and d_out.data_ptr() % 16 == 0
-    n_out = rs.work_device(d_in.data_ptr() + 8 * in_shift, in_stride, n, ns, d_out.data_ptr() + 8 * out_shift, out_stride, stream())
-    torch.cuda.synchronize()
+    out_stride = max(int(said.max()), 1) if out_stride is None else out_stride
+    outs, n_out = T.run_strided(lambda a, o: rs.work_device(a, in_stride, n, ns, o, out_stride, stream()), xs, [int(k) for k in said],
+                                in_stride, out_stride, in_shift, out_shift)
     assert np.array_equal(n_out, said), (n_out, said)
-    got = d_out.cpu().numpy().view(np.uint32).reshape(-1, 2)
-    assert np.array_equal(d_in.cpu().numpy().view(np.uint32), host_in.view(np.uint32))
-    touched = np.zeros(n_buf, bool)
-    outs = []
-    for s in range(ns):
-        a = out_shift + s * out_stride
-        touched[a:a + int(n_out[s])] = True
-        outs.append(got[a:a + int(n_out[s])])
-    assert (got[~touched] == SENTINEL).all(), "a write outside the streams' outputs"
     return outs, n_out
 
 
 def same(got, want, what):
-    assert got.shape[0] == want.size, (what, got.shape[0], want.size)
-    w = RM.bits(want).reshape(-1, 2)
-    if not np.array_equal(got, w):
-        bad = np.nonzero((got != w).any(axis=1))[0]
-        raise AssertionError(f"{what}: {bad.size} of {want.size} samples differ, the first at {bad[0]}: {got[bad[0]]} != {w[bad[0]]}")
+    T.same_bits(got, RM.bits(want), what)
 
 
 def state_is(rs, models, what):
@@ -297,19 +256,14 @@ def test_host_entry_equals_the_device_entry():
 
 
 # ------------------------------------------------------------------ 6. refusals
-def _refused(code, text, entry, *args):
-    assert entry(*args) == code, (entry.__name__, capi.lib.dvbs2_last_error())
-    assert capi.lib.dvbs2_last_error() == text.encode(), capi.lib.dvbs2_last_error()
-
-
 def test_refusals_leave_everything_untouched():
-    torch = _torch()
+    import torch
     lib, h = capi.lib, C.c_void_p()
     good_taps = np.ones(21, np.float32)
     # creation (every argument refusal without a device: tests/test_resamp_model.py)
-    _refused(capi.EINVAL, "nfilts must be a power of two in 2..256", lib.dvbs2_resamp_create, C.byref(h), 3, good_taps.ctypes.data, 21, 1.0, 1, 16, 0)
-    _refused(capi.EINVAL, "rate must lie in [0.5, 64]", lib.dvbs2_resamp_create, C.byref(h), 2, good_taps.ctypes.data, 21, 0.25, 1, 16, 0)
-    _refused(capi.EINVAL, "null handle pointer", lib.dvbs2_resamp_create, None, 2, good_taps.ctypes.data, 21, 1.0, 1, 16, 0)
+    refused(capi.EINVAL, "nfilts must be a power of two in 2..256", lib.dvbs2_resamp_create, C.byref(h), 3, good_taps.ctypes.data, 21, 1.0, 1, 16, 0)
+    refused(capi.EINVAL, "rate must lie in [0.5, 64]", lib.dvbs2_resamp_create, C.byref(h), 2, good_taps.ctypes.data, 21, 0.25, 1, 16, 0)
+    refused(capi.EINVAL, "null handle pointer", lib.dvbs2_resamp_create, None, 2, good_taps.ctypes.data, 21, 1.0, 1, 16, 0)
     assert not h
     assert lib.dvbs2_resamp_create(C.byref(h), 2, good_taps.ctypes.data, 21, 1.0, 1, 16, 99) < 0 and not h  # no such device
 
@@ -325,35 +279,35 @@ def test_refusals_leave_everything_untouched():
     most = int(rs.produce(n, 2).max())
     assert 250 <= most <= resamp_max_out(step, n) == 251  # (the step is 2^32 / 2.5 rounded down: a hair above 2.5)
     d_in = torch.from_numpy(np.concatenate(second).view(np.float32)).cuda()
-    d_out = sentinel(2 * most + PAD)
+    d_out = sentinel(2 * (2 * most + PAD))
     st = stream()
     a, o = d_in.data_ptr(), d_out.data_ptr()
     counts = np.full(2, -7, np.int64)
     c = counts.ctypes.data
     entry = lib.dvbs2_resamp_process_device
-    _refused(capi.ESIZE, "n_in exceeds max_samples", entry, rs._h, a, n, n + 1, 1, o, most, c, st)
-    _refused(capi.ESIZE, "n_streams exceeds max_streams", entry, rs._h, a, n, n, 3, o, most, c, st)
-    _refused(capi.EINVAL, "in_stride is below n_in", entry, rs._h, a, n - 1, n, 2, o, most, c, st)
-    _refused(capi.EINVAL, "out_stride is below the call's largest n_out", entry, rs._h, a, n, n, 2, o, most - 1, c, st)
-    _refused(capi.EINVAL, "out_stride is below the call's largest n_out", entry, rs._h, a, n, n, 1, o, most - 1, c, st)
-    _refused(capi.EINVAL, "in is null", entry, rs._h, None, n, n, 2, o, most, c, st)
-    _refused(capi.EINVAL, "out is null", entry, rs._h, a, n, n, 2, None, most, c, st)
-    _refused(capi.EINVAL, "n_in is negative", entry, rs._h, a, n, -1, 2, o, most, c, st)
-    _refused(capi.EINVAL, "n_streams is negative", entry, rs._h, a, n, n, -1, o, most, c, st)
-    _refused(capi.EINVAL, "in and out must be 8-byte aligned", entry, rs._h, a + 4, n, n, 2, o, most, c, st)
-    _refused(capi.EINVAL, "in and out must be 8-byte aligned", entry, rs._h, a, n, n, 2, o + 4, most, c, st)
+    refused(capi.ESIZE, "n_in exceeds max_samples", entry, rs._h, a, n, n + 1, 1, o, most, c, st)
+    refused(capi.ESIZE, "n_streams exceeds max_streams", entry, rs._h, a, n, n, 3, o, most, c, st)
+    refused(capi.EINVAL, "in_stride is below n_in", entry, rs._h, a, n - 1, n, 2, o, most, c, st)
+    refused(capi.EINVAL, "out_stride is below the call's largest n_out", entry, rs._h, a, n, n, 2, o, most - 1, c, st)
+    refused(capi.EINVAL, "out_stride is below the call's largest n_out", entry, rs._h, a, n, n, 1, o, most - 1, c, st)
+    refused(capi.EINVAL, "in is null", entry, rs._h, None, n, n, 2, o, most, c, st)
+    refused(capi.EINVAL, "out is null", entry, rs._h, a, n, n, 2, None, most, c, st)
+    refused(capi.EINVAL, "n_in is negative", entry, rs._h, a, n, -1, 2, o, most, c, st)
+    refused(capi.EINVAL, "n_streams is negative", entry, rs._h, a, n, n, -1, o, most, c, st)
+    refused(capi.EINVAL, "in and out must be 8-byte aligned", entry, rs._h, a + 4, n, n, 2, o, most, c, st)
+    refused(capi.EINVAL, "in and out must be 8-byte aligned", entry, rs._h, a, n, n, 2, o + 4, most, c, st)
     assert (counts == -7).all()
-    _refused(capi.EINVAL, "step must lie in [2^26, 2^33]", lib.dvbs2_resamp_set_step, rs._h, (1 << 26) - 1)
-    _refused(capi.EINVAL, "step must lie in [2^26, 2^33]", lib.dvbs2_resamp_set_step, rs._h, (1 << 33) + 1)
-    _refused(capi.EINVAL, "rate must lie in [0.5, 64]", lib.dvbs2_resamp_set_rate, rs._h, 0.4)
-    _refused(capi.EINVAL, "rate must lie in [0.5, 64]", lib.dvbs2_resamp_set_rate, rs._h, float("nan"))
+    refused(capi.EINVAL, "step must lie in [2^26, 2^33]", lib.dvbs2_resamp_set_step, rs._h, (1 << 26) - 1)
+    refused(capi.EINVAL, "step must lie in [2^26, 2^33]", lib.dvbs2_resamp_set_step, rs._h, (1 << 33) + 1)
+    refused(capi.EINVAL, "rate must lie in [0.5, 64]", lib.dvbs2_resamp_set_rate, rs._h, 0.4)
+    refused(capi.EINVAL, "rate must lie in [0.5, 64]", lib.dvbs2_resamp_set_rate, rs._h, float("nan"))
     assert rs.step == step
-    _refused(capi.ESIZE, "n_in exceeds max_samples", lib.dvbs2_resamp_produce, rs._h, n + 1, 1, c)
-    _refused(capi.ESIZE, "n_streams exceeds max_streams", lib.dvbs2_resamp_produce, rs._h, n, 3, c)
-    _refused(capi.EINVAL, "n_in is negative", lib.dvbs2_resamp_produce, rs._h, -1, 1, c)
-    _refused(capi.EINVAL, "n_streams is negative", lib.dvbs2_resamp_produce, rs._h, n, -1, c)
-    _refused(capi.EINVAL, "n_out is null", lib.dvbs2_resamp_produce, rs._h, n, 1, None)
-    _refused(capi.EINVAL, "acc is null", lib.dvbs2_resamp_state, rs._h, None)
+    refused(capi.ESIZE, "n_in exceeds max_samples", lib.dvbs2_resamp_produce, rs._h, n + 1, 1, c)
+    refused(capi.ESIZE, "n_streams exceeds max_streams", lib.dvbs2_resamp_produce, rs._h, n, 3, c)
+    refused(capi.EINVAL, "n_in is negative", lib.dvbs2_resamp_produce, rs._h, -1, 1, c)
+    refused(capi.EINVAL, "n_streams is negative", lib.dvbs2_resamp_produce, rs._h, n, -1, c)
+    refused(capi.EINVAL, "n_out is null", lib.dvbs2_resamp_produce, rs._h, n, 1, None)
+    refused(capi.EINVAL, "acc is null", lib.dvbs2_resamp_state, rs._h, None)
     assert (counts == -7).all()
     assert entry(rs._h, None, 0, 0, 2, None, 0, c, st) == capi.OK  # n_in == 0: a successful call that does nothing and reports zeros
     assert counts.tolist() == [0, 0]
@@ -369,13 +323,13 @@ def test_refusals_leave_everything_untouched():
     host_in, host_out = second[0].copy(), np.zeros(most, np.complex64)
     n_out = C.c_int64(-7)
     host = lib.dvbs2_resamp_process
-    _refused(capi.ESIZE, "n_in exceeds max_samples", host, rs._h, host_in.ctypes.data, n + 1, host_out.ctypes.data, most, C.byref(n_out))
-    _refused(capi.EINVAL, "n_in is negative", host, rs._h, host_in.ctypes.data, -1, host_out.ctypes.data, most, C.byref(n_out))
-    _refused(capi.EINVAL, "in is null", host, rs._h, None, n, host_out.ctypes.data, most, C.byref(n_out))
-    _refused(capi.EINVAL, "out is null", host, rs._h, host_in.ctypes.data, n, None, most, C.byref(n_out))
-    _refused(capi.EINVAL, "out_cap is negative", host, rs._h, host_in.ctypes.data, n, host_out.ctypes.data, -1, C.byref(n_out))
-    _refused(capi.EINVAL, "out_cap is below n_out", host, rs._h, host_in.ctypes.data, n, host_out.ctypes.data,
-             int(rs.produce(n)[0]) - 1, C.byref(n_out))
+    refused(capi.ESIZE, "n_in exceeds max_samples", host, rs._h, host_in.ctypes.data, n + 1, host_out.ctypes.data, most, C.byref(n_out))
+    refused(capi.EINVAL, "n_in is negative", host, rs._h, host_in.ctypes.data, -1, host_out.ctypes.data, most, C.byref(n_out))
+    refused(capi.EINVAL, "in is null", host, rs._h, None, n, host_out.ctypes.data, most, C.byref(n_out))
+    refused(capi.EINVAL, "out is null", host, rs._h, host_in.ctypes.data, n, None, most, C.byref(n_out))
+    refused(capi.EINVAL, "out_cap is negative", host, rs._h, host_in.ctypes.data, n, host_out.ctypes.data, -1, C.byref(n_out))
+    refused(capi.EINVAL, "out_cap is below n_out", host, rs._h, host_in.ctypes.data, n, host_out.ctypes.data,
+            int(rs.produce(n)[0]) - 1, C.byref(n_out))
     assert lib.dvbs2_resamp_process(rs._h, None, 0, None, 0, None) == capi.OK
     assert (host_out == 0).all() and n_out.value == 0
     # no refusal touched a history, a position or the mirror: both streams go on from where the good calls left them
@@ -388,100 +342,45 @@ def test_refusals_leave_everything_untouched():
 
 
 # ------------------------------------------------------------------ 7. and 8. closed loops through the receiver, noise-free
-GOLD, PLSC, DUMMY, ND, LEAD = 5, P.plsc_of(1, 1, 1), P.plsc_of(0, 0, 0), 6, 301
-SEQ = [PLSC, PLSC, DUMMY, PLSC, PLSC, DUMMY, PLSC, PLSC]  # a dummy frame after data frames 2 and 4
+SEQ, PLSC, ND, LEAD = L.SEQ6, L.PLSC, 6, 301
 
 
 @functools.lru_cache(maxsize=None)
 def transmitted():
-    """The transmit side of test_pulse_gpu.py::test_closed_loop_through_the_receiver up to the PL framer: six short QPSK 1/4 frames and
-    two dummy frames behind LEAD random symbols, `flush` zero symbols behind them. Returns (the encoder's input, the symbols on the
-    device, their number without the flush)."""
-    torch = _torch()
-    rng = np.random.default_rng(2026)
-    st = stream()
-    enc = FecEncoder(capi.STANDARD_DVBS2, capi.FECFRAME_SHORT, "C1_4", capi.MOD_QPSK, max_frames=ND)
-    enc.set_scramble(True)
-    sent = rng.integers(0, 256, (ND, enc.in_bytes), dtype=np.uint8)
-    lay = plframer_layout(SEQ)
-    assert enc.n_syms == M.pls_parse(PLSC)["xfecframe_len"] and lay["in_syms"] == ND * enc.n_syms
-    d_xfec = torch.zeros((ND, enc.n_syms, 2), dtype=torch.float32, device="cuda")
-    enc.work_device(torch.from_numpy(sent).cuda().data_ptr(), ND, d_syms=d_xfec.data_ptr(), stream=st)
-    fr = PlFramer(GOLD, max_frames=len(SEQ))
-    fr.set_sequence(SEQ)
-    n = LEAD + lay["out_syms"] + 90
-    n_all = n + 256  # the flush: more zero symbols than the histories of all stages behind
-    d_x = torch.zeros((n_all, 2), dtype=torch.float32, device="cuda")
-    d_x[:LEAD] = torch.from_numpy(P.qpsk(rng, LEAD).astype(np.complex64).view(np.float32).reshape(-1, 2)).cuda()
-    fr.work_device(d_xfec.data_ptr(), len(SEQ), SEQ[-1], d_x.data_ptr() + 8 * LEAD, st)
-    torch.cuda.synchronize()
-    fr.close()
-    enc.close()
+    """The transmit side up to the PL framer (loopback.transmit_symbols): six short QPSK 1/4 frames and two dummy frames behind LEAD
+    random symbols, 256 zero symbols behind them: more than the histories of all stages behind. Returns (the encoder's input, the
+    symbols on the device, their number with the flush)."""
+    sent, d_x, _, n_all, _ = L.transmit_symbols(SEQ, ND, L.GOLD, LEAD, seed=2026, flush=256)
     return sent, d_x, n_all
 
 
 def receive(d_y, ns, n_syms, interp_method, sent, what):
-    """d_y: ns samples at 2 per symbol on the device. Timing recovery, frame search, gather, coarse estimate, front end, FEC, as in
-    test_pulse_gpu.py::test_closed_loop_through_the_receiver. Requires every frame at ONE constant symbol shift from LEAD + out_offset[f]
-    and the encoder's input out of the chain; returns (the shift, the number of symbols)."""
-    torch = _torch()
-    st = stream()
+    """d_y: ns samples at 2 per symbol on the device. Timing recovery, frame search and the decode tail of tests/loopback.py. Requires
+    every frame at ONE constant symbol shift from LEAD + out_offset[f] and the encoder's input out of the chain; returns (the shift, the
+    number of symbols)."""
     lay = plframer_layout(SEQ)
-    L = M.pls_parse(PLSC)["plframe_len"]
-    ss = SymbolSync(sps=2, loop_bw=0.01, damping=1.0, rolloff=0.2, interp_method=interp_method, max_samples=ns)
-    d_sym = torch.zeros(2 * ns, dtype=torch.float32, device="cuda")
-    ss.work_device(d_y.data_ptr(), ns, [ns], d_sym.data_ptr(), ns, ns, 0, 0, st)
-    n_out, consumed, status = ss.finish()
-    nsym = int(n_out[0])
-    print(f"{what}: {nsym} symbols from {ns} samples ({n_syms} sent), status {status[0]}, loop {ss.state()}")
-    assert status[0] == 0 and abs(nsym - n_syms) <= 24, what
-    sync = PlSync(plsc=-1, max_symbols=max(nsym, PlSync.MIN_SYMBOLS), max_frames=64)
-    d_rec = torch.zeros(64 * 16, dtype=torch.uint8, device="cuda")
-    sync.work_device(d_sym.data_ptr(), nsym, d_rec.data_ptr(), st)
-    nf, _, state = sync.finish()
-    recs = d_rec.cpu().numpy().view(PlSync.FRAME_DTYPE)[:nf]
+    rx = L.timing_and_frames(d_y, ns, 2, 0.2, interp_method, n_syms, tol=24)
+    recs, nf, nsym = rx.recs, rx.nf, rx.nsym
+    print(f"{what}: {nsym} symbols from {ns} samples ({n_syms} sent), status 0, loop {rx.loop}")  # (a status other than 0 does not come back from timing_and_frames)
     shifts = (recs["sof_index"] - (LEAD + lay["out_offset"][:nf])).tolist() if nf <= len(SEQ) else []
     print(f"{what}: {nf} frames, PLSCs {recs['plsc'].tolist()}, SOF shifts {shifts}")
-    assert state == capi.PLSYNC_LOCKED and nf == len(SEQ) and recs["plsc"].tolist() == SEQ, what  # every frame found
+    assert rx.state == capi.PLSYNC_LOCKED and nf == len(SEQ) and recs["plsc"].tolist() == SEQ, what  # every frame found
     assert len(set(shifts)) == 1, (what, shifts)  # one constant delay: no cycle slip
-    locked = [f for f, r in enumerate(recs) if r["flags"] & capi.PLSYNC_FLAG_LOCKED and r["plsc"] == PLSC]
-    assert len(locked) >= ND - 1, what  # the tracker locks at the second header
-    d_fr = torch.zeros((len(locked) * L + 90) * 2, dtype=torch.float32, device="cuda")
-    d_cnt = torch.full((1,), -7, dtype=torch.int32, device="cuda")
-    sync.gather_device(d_sym.data_ptr(), d_rec.data_ptr(), nf, PLSC, d_fr.data_ptr(), d_cnt.data_ptr(), st)
-    torch.cuda.synchronize()
-    cnt = int(d_cnt.item())
-    assert cnt == len(locked), what
-    pc = PlCoarse(1, PLSC, max_frames=64)
-    d_cc = torch.zeros(cnt, dtype=torch.int32, device="cuda")
-    d_f = torch.zeros(cnt, dtype=torch.float32, device="cuda")
-    pc.work_device(d_fr.data_ptr(), L, cnt, 0, d_f.data_ptr(), d_cc.data_ptr(), 0, st)
-    fe = PlFrontEnd(GOLD, PLSC, max_frames=cnt)
-    d_rx = torch.zeros((cnt, fe.xfecframe_len * 2), dtype=torch.float32, device="cuda")
-    fe.work_device(d_fr.data_ptr(), cnt, 1, d_cc.data_ptr(), d_f.data_ptr(), d_rx.data_ptr(), st)
-    torch.cuda.synchronize()
-    chain = FecChain(capi.STANDARD_DVBS2, capi.FECFRAME_SHORT, "C1_4", capi.MOD_QPSK, group_size=4, max_frames=cnt, max_trials=25)
-    chain.set_descramble(True)
-    msg, ret, corr = chain.work(d_rx.cpu().numpy().view(np.complex64), np.float32(0.02))
-    assert (ret >= 0).all() and (corr >= 0).all(), what
-    data_index = [sum(1 for q in SEQ[:f] if q == PLSC) for f in locked]  # which encoder frame each gathered frame carries
-    assert np.array_equal(msg, sent[data_index]), what  # the encoder's input bytes
-    for o in (chain, fe, pc, sync, ss):
-        o.close()
+    got = L.decode_frames(rx, PLSC, L.GOLD, 0.02)
+    assert len(got.locked) >= ND - 1, what  # the tracker locks at the second header
+    assert np.array_equal(got.msg, sent[got.data_index]), what  # the encoder's input bytes
+    rx.sync.close()
     return shifts[0], nsym
 
 
 @functools.lru_cache(maxsize=None)
 def shaped_at_two():
-    """transmitted() through the shaper at sps 2, tau = 0, scaled for unit symbol amplitude behind the receiver's matched filter as
-    test_closed_loop_through_the_receiver scales its taps"""
-    torch = _torch()
+    """transmitted() through the shaper at sps 2, tau = 0, scaled for unit symbol amplitude behind the receiver's matched filter
+    (loopback.unit_amplitude_taps)"""
+    import torch
     sent, d_x, n_all = transmitted()
-    sps, rolloff, rrc_delay = 2, 0.2, 5
-    bank0 = symsync_taps(sps, rolloff, rrc_delay, 128)[0].astype(np.float64)[::-1]  # the bank holds each subfilter flipped
-    centre = np.convolve(pulse_taps(sps, rolloff, rrc_delay).astype(np.float64), bank0)[2 * sps * rrc_delay]
-    taps = (pulse_taps(sps, rolloff, rrc_delay).astype(np.float64) / centre).astype(np.float32)
-    ps = PulseShaper(sps, taps=taps, max_symbols=n_all)
+    sps = 2
+    ps = PulseShaper(sps, taps=L.unit_amplitude_taps(sps, 0.2, 5), max_symbols=n_all)
     d_y = torch.zeros((n_all * sps, 2), dtype=torch.float32, device="cuda")
     ps.work_device(d_x.data_ptr(), n_all, n_all, 1, d_y.data_ptr(), n_all * sps, stream())
     torch.cuda.synchronize()
@@ -497,7 +396,7 @@ def test_closed_loop_with_a_sampling_clock_offset(ppm):
     """A: the shaper's samples at 2 per symbol through this stage at rate 1 + ppm 1e-6 (prototype dvbs2_pulse_taps(32, 0.35, 8, 0, 32):
     flat below 0.325 cycles per sample, the signal ends at 0.3), then symsync with the polyphase matched filter. Over the 114 thousand
     samples 100 ppm are 11 samples of drift: the loop has to follow them without a cycle slip. ppm = 0 is the control: rate exactly 1."""
-    torch = _torch()
+    import torch
     sent, _, n_all = transmitted()
     d_y = shaped_at_two()
     ns = 2 * n_all
@@ -520,7 +419,7 @@ def test_closed_loop_through_the_fractional_sps_transmitter():
     the matched filter at 16 taps per input sample (40 per symbol), then symsync with the cubic interpolator, so that nothing filters
     twice. The transmit taps are scaled for unit symbol amplitude: by the peak of the response of both stages to one unit symbol, from
     model (b)."""
-    torch = _torch()
+    import torch
     sent, d_x, n_all = transmitted()
     tx = pulse_taps(32, 0.2, 5, 0.0, 32.0)
     rx = pulse_taps(40, 0.2, 5, 0.0, 16.0)

@@ -1,7 +1,6 @@
 """CPU: the host-only code of the resampler -- step, geometry, max_out, the position rule over a sequence of calls and the argument check
 of the class -- once more in a stand-alone program built with the host sanitizers, over good and refused arguments. Its answers must be
 the library's, and the position rule's those of tests/resamp_model.py."""
-import os
 import subprocess
 
 import numpy as np
@@ -11,19 +10,12 @@ import fec_testlib as T
 import resamp_model as RM
 from dvbs2rx_amd import capi, resamp_geometry, resamp_max_out, resamp_step
 
-CSRC = os.path.join(T.ROOT, "gr-dvbs2rx_amd", "csrc")
-
 
 @pytest.fixture(scope="module")
 def host_exe(tmp_path_factory):
     """tests/resamp_host_main.cpp with the host source it calls, host code under AddressSanitizer and UBSan (device code is not
     instrumented and none of it runs)."""
-    exe = str(tmp_path_factory.mktemp("resamp") / "resamp_host_main")
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    san = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined"]
-    subprocess.check_call([hipcc, "-x", "hip", "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-ffp-contract=off", *san,
-                           os.path.join(T.ROOT, "tests", "resamp_host_main.cpp"), os.path.join(CSRC, "resamp_hip.hip"), "-o", exe])
-    return exe
+    return T.build_host_program(tmp_path_factory.mktemp("resamp"), "resamp_host_main.cpp", ("resamp_hip.hip",))
 
 
 def _hex(taps):

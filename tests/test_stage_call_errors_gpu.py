@@ -60,11 +60,6 @@ def dev(a):
     return torch.from_numpy(a.view(np.float32) if a.dtype == np.complex64 else a).cuda()
 
 
-def stream():
-    import torch
-    return torch.cuda.current_stream().cuda_stream
-
-
 # ------------------------------------------------------------------ per handle type: make(), the good call, the failing calls
 def ldpc_make():
     return LdpcDecoder(table=TABLE, message_bits=T.ldpc_info(TABLE)[1], group_size=2, max_frames=MF, max_trials=25)
@@ -86,7 +81,7 @@ def ldpc_busy_slot(o):
     d_llr = dev(ldpc_llr())
     d_bits, d_out = torch.zeros(o.out_bytes, dtype=torch.uint8, device="cuda"), torch.zeros(o.N, dtype=torch.int8, device="cuda")
     d_ret = torch.zeros(1, dtype=torch.int32, device="cuda")
-    args = (o._h, d_llr.data_ptr(), 1, o.max_trials, o.outputmode, d_bits.data_ptr(), d_out.data_ptr(), d_ret.data_ptr(), stream())
+    args = (o._h, d_llr.data_ptr(), 1, o.max_trials, o.outputmode, d_bits.data_ptr(), d_out.data_ptr(), d_ret.data_ptr(), T.stream())
     assert lib.dvbs2_ldpc_enqueue_device(*args) == OK
     rc = lib.dvbs2_ldpc_enqueue_device(*args)
     text = lib.dvbs2_last_error()
@@ -199,7 +194,7 @@ def chain_pending(o):
     d_syms, d_n0 = dev(chain_syms()), dev(np.array([0.5], np.float32))
     d_msg = torch.zeros(o.msg_bytes, dtype=torch.uint8, device="cuda")
     d_ret, d_corr = torch.zeros(1, dtype=torch.int32, device="cuda"), torch.zeros(1, dtype=torch.int32, device="cuda")
-    args = (o._h, d_syms.data_ptr(), 1, d_n0.data_ptr(), 1, o.max_trials, d_msg.data_ptr(), d_ret.data_ptr(), d_corr.data_ptr(), stream())
+    args = (o._h, d_syms.data_ptr(), 1, d_n0.data_ptr(), 1, o.max_trials, d_msg.data_ptr(), d_ret.data_ptr(), d_corr.data_ptr(), T.stream())
     assert lib.dvbs2_chain_enqueue_device(*args) == OK
     rc = lib.dvbs2_chain_enqueue_device(*args)
     text = lib.dvbs2_last_error()

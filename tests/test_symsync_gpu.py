@@ -12,11 +12,12 @@ import numpy as np
 import pytest
 
 import fec_testlib as T
+import loopback as L
 import plcoarse_model as K
 import plframe_model as M
 import plsync_model as P
 import symsync_model as S
-from dvbs2rx_amd import FecChain, PlCoarse, PlFrontEnd, PlSync, Rotator, SymbolSync, capi, symsync_taps
+from dvbs2rx_amd import Rotator, SymbolSync, capi, symsync_taps
 
 pytestmark = pytest.mark.gpu
 
@@ -272,50 +273,23 @@ def test_pipeline_from_samples_to_bbframes():
     import torch
     x, sofs, sent, plsc = K.e2e_stream()
     y = shaped_samples(x)
-    st = torch.cuda.current_stream().cuda_stream
     e = P.E2E["e2e-qpsk"]
-    L = M.pls_parse(plsc)["plframe_len"]
     d_y = dev(y)
     # Rotator on samples (the offset known here, as after a first coarse estimate), then timing recovery and matched filter
     rot = Rotator(-M.PI2 * K.E2E_FOFFSET / E2E_SPS)
-    rot.work_device(d_y.data_ptr(), y.size, d_y.data_ptr(), st)
-    ss = SymbolSync(sps=E2E_SPS, loop_bw=0.01, damping=1.0, rolloff=0.2, interp_method=0, max_samples=y.size)
-    d_sym = torch.zeros(2 * y.size, dtype=torch.float32, device="cuda")
-    ss.work_device(d_y.data_ptr(), y.size, [y.size], d_sym.data_ptr(), y.size, y.size, 0, 0, st)
-    n_out, consumed, status = ss.finish()
-    nsym = int(n_out[0])
-    assert status[0] == 0 and abs(nsym - x.size) <= 12
-    ps = PlSync(plsc=plsc, max_symbols=max(nsym, PlSync.MIN_SYMBOLS), max_frames=64)
-    d_rec = torch.zeros(64 * 16, dtype=torch.uint8, device="cuda")
-    ps.work_device(d_sym.data_ptr(), nsym, d_rec.data_ptr(), st)
-    nf, _, state = ps.finish()
-    recs = d_rec.cpu().numpy().view(PlSync.FRAME_DTYPE)[:nf]
-    assert state == capi.PLSYNC_LOCKED and nf == len(sofs)
-    shift = set((recs["sof_index"] - np.array(sofs)).tolist())
+    rot.work_device(d_y.data_ptr(), y.size, d_y.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    rx = L.timing_and_frames(d_y, y.size, E2E_SPS, 0.2, 0, x.size, tol=12, plsc=plsc)
+    assert rx.state == capi.PLSYNC_LOCKED and rx.nf == len(sofs)
+    shift = set((rx.recs["sof_index"] - np.array(sofs)).tolist())
     assert len(shift) == 1 and abs(shift.pop()) <= 12  # one constant delay: the loop's start-up and the filter
-    locked = [i for i, r in enumerate(recs) if r["flags"] & 2]
-    assert len(locked) >= len(sofs) - 1
-    d_fr = torch.zeros(2 * (len(locked) * L + 90), dtype=torch.float32, device="cuda")
-    d_cnt = torch.zeros(1, dtype=torch.int32, device="cuda")
-    ps.gather_device(d_sym.data_ptr(), d_rec.data_ptr(), nf, plsc, d_fr.data_ptr(), d_cnt.data_ptr(), st)
-    torch.cuda.synchronize()
-    cnt = int(d_cnt.item())
-    assert cnt == len(locked)
-    pc = PlCoarse(1, plsc, max_frames=64)
-    d_cc = torch.zeros(cnt, dtype=torch.int32, device="cuda")
-    d_f = torch.zeros(cnt, dtype=torch.float32, device="cuda")
-    pc.work_device(d_fr.data_ptr(), L, cnt, 0, d_f.data_ptr(), d_cc.data_ptr(), 0, st)
-    fe = PlFrontEnd(P.E2E_GOLD, plsc, max_frames=cnt)
-    d_xfec = torch.zeros((cnt, fe.xfecframe_len * 2), dtype=torch.float32, device="cuda")
-    fe.work_device(d_fr.data_ptr(), cnt, 1, d_cc.data_ptr(), d_f.data_ptr(), d_xfec.data_ptr(), st)
-    torch.cuda.synchronize()
-    print(f"{nsym} symbols from {y.size} samples, residual offsets {d_f.cpu().numpy()}, coarse_corrected {d_cc.cpu().tolist()}")
-    chain = FecChain(framesize=capi.FECFRAME_SHORT, rate=e["rate"], constellation=capi.MOD_QPSK, group_size=4, max_frames=cnt, max_trials=25)
-    msg, ret, corr = chain.work(d_xfec.cpu().numpy().view(np.complex64), np.float32(10 ** (-K.E2E_ES_N0_DB / 10)))
-    assert d_cc.cpu().numpy().all() and (ret >= 0).all()
-    assert np.array_equal(msg, sent[locked])  # the transmitted BBFRAMEs
-    for o in (chain, fe, pc, ps, ss, rot):
-        o.close()
+    got = L.decode_frames(rx, plsc, P.E2E_GOLD, 10 ** (-K.E2E_ES_N0_DB / 10), descramble=False,
+                          fec=dict(framesize=capi.FECFRAME_SHORT, rate=e["rate"], constellation=capi.MOD_QPSK))
+    print(f"{rx.nsym} symbols from {y.size} samples, residual offsets {got.offsets}, coarse_corrected {got.corrected.tolist()}")
+    assert len(got.locked) >= len(sofs) - 1
+    assert got.corrected.all()
+    assert np.array_equal(got.msg, sent[got.locked])  # the transmitted BBFRAMEs
+    rx.sync.close()
+    rot.close()
 
 
 # ------------------------------------------------------------------ 6. the C++ host mirror
