@@ -1,6 +1,6 @@
 // ddc_hip.hip -- see ddc_hip.h.
 #include "ddc_hip.h"
-#include "rotator_hip.h" // rotator_inc_turns
+#include "rotator_turns.h"
 #include "rotator_math.hpp"
 #include <algorithm>
 #include <cmath>

@@ -27,9 +27,6 @@ namespace dvbs2 {
 constexpr double kFineFoffsetCorrRange = 3.3875e-4; // lib/pl_freq_sync.h:18
 constexpr int kPlcoarseRecord = 90 + 26;            // float2 per frame between the kernels: R_full[0..89] | R_sof[0..25]
 
-// the weighting window of lib/pl_freq_sync.cc:74-85 as the floats the reference keeps: 89 values (full) or 25 (SOF)
-int plcoarse_weights(int full, float* w);
-
 struct PlCoarseState { // lives on the device
     float2 acc[90];    // pilot_corr[1..L] at [1..L]
     int32_t i_frame, corrected;

@@ -1,33 +1,19 @@
 // plcoarse_hip.hip -- see plcoarse_hip.h.
 #include "plcoarse_hip.h"
+#include "plsc_decode.hpp"
 #include <cmath>
 #include <cstring>
 #include <new>
 
 namespace dvbs2 {
 
-int plcoarse_weights(int full, float* w)
-{
-    const unsigned L = full ? 89 : 25; // lib/pl_freq_sync.cc:74-85, the same expression in double, kept as float
-    for (unsigned m = 0; m < L; m++)
-        w[m] = (float)(3.0 * ((2 * L + 1.0) * (2 * L + 1.0) - (2 * m + 1.0) * (2 * m + 1.0)) / (((2 * L + 1.0) * (2 * L + 1.0) - 1) * (2 * L + 1)));
-    return (int)L;
-}
-
 namespace {
 
+using plsc::kPi;
+using plsc::unmod;
 using plsc::wave_sum;
-constexpr double kPi = 3.14159265358979323846;
+using plsc::wrap_pi;
 constexpr int kBatch = 16; // frames the window kernel loads ahead of the serial walk
-
-// x_k conj(h_k) sqrt(2): conj(h_k) sqrt(2) = ((k odd ? -1 : 1), -1) (1 - 2 bit) (lib/pi2_bpsk.cc:18-43), so each component is one
-// sum or difference of the two input components: one rounding, no multiply
-__device__ inline float2 unmod(float2 x, int k, int bit)
-{
-    const float sg = bit ? -1.0f : 1.0f;
-    const float cr = (k & 1) ? -sg : sg, ci = -sg;
-    return make_float2(x.x * cr - x.y * ci, x.x * ci + x.y * cr);
-}
 
 // One pass over a header of N symbols held as z0 (symbols 0..63 in lanes 0..63) and z1 (symbols 64..N-1 in lanes 0..N-65): lane l
 // leaves lag l in *a (sum over u = 0 .. N-l-1 of z[u+l] conj(z[u]), ascending u) and lag N - l in *b (u = N-l .. N-1 of
@@ -71,10 +57,10 @@ __global__ __launch_bounds__(64) void plcoarse_autocorr_kernel(const float2* __r
         h = x + (long long)f * stride; p = plsc ? (plsc[f] & 127) : fixed_plsc;
     }
     const uint64_t cw = cwtab[p];
-    const int bit0 = l < 26 ? (int)((kSofWord >> (25 - l)) & 1) : (int)((cw >> (89 - l)) & 1);
+    const int bit0 = plheader_bit(cw, l);
     const float2 z0 = unmod(h[l], l, bit0);
     float2 z1 = make_float2(0.0f, 0.0f);
-    if (l < 26) z1 = unmod(h[64 + l], 64 + l, (int)((cw >> (25 - l)) & 1));
+    if (l < 26) z1 = unmod(h[64 + l], 64 + l, (int)((cw >> (25 - l)) & 1)); // plheader_bit(cw, 64 + l) without its SOF test
 
     float2 a, b;
     lag_pair<90>(z0, z1, l, &a, &b);
@@ -84,13 +70,6 @@ __global__ __launch_bounds__(64) void plcoarse_autocorr_kernel(const float2* __r
     if (l >= 1 && l <= 13) R[90 + l] = a;
     if (l >= 1 && l <= 12) R[90 + 26 - l] = b;
     if (l == 0) { R[0] = make_float2(1.0f, 0.0f); R[90] = make_float2(0.0f, 0.0f); }
-}
-
-__device__ inline float wrap_pi(float d) // lib/pl_freq_sync.cc:166-171: compared and corrected in double, kept as float
-{
-    if ((double)d > kPi) d = (float)((double)d - 2.0 * kPi);
-    else if ((double)d < -kPi) d = (float)((double)d + 2.0 * kPi);
-    return d;
 }
 
 // one wavefront; lane l holds lags l + 1 and l + 65

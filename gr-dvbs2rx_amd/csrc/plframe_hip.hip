@@ -3,94 +3,31 @@
 // reduction a butterfly of cross-lane exchanges -- no LDS, no barrier. It reads 90 + 36 n_pilots symbols of a frame;
 // the streaming payload step (plpayload_hip.hip) follows as a second launch on the same stream.
 #include "plframe_hip.h"
+#include "plsc_decode.hpp"
 #include <cmath>
 #include <vector>
 
 namespace dvbs2 {
 
-PlsInfo pls_parse(int plsc)
-{
-    PlsInfo p{};
-    p.plsc = plsc; p.modcod = plsc >> 2; p.short_fecframe = (plsc >> 1) & 1; p.has_pilots = plsc & 1;
-    p.dummy_frame = p.modcod == 0;
-    if (p.dummy_frame) p.has_pilots = 0; // a dummy frame cannot have pilots (lib/pl_signaling.cc:25-26)
-    if (p.modcod >= 1 && p.modcod <= 11) { p.n_mod = 2; p.n_slots = 360; }
-    else if (p.modcod >= 12 && p.modcod <= 17) { p.n_mod = 3; p.n_slots = 240; }
-    else if (p.modcod >= 18 && p.modcod <= 23) { p.n_mod = 4; p.n_slots = 180; }
-    else if (p.modcod >= 24 && p.modcod <= 28) { p.n_mod = 5; p.n_slots = 144; }
-    else { p.n_mod = 0; p.n_slots = 36; }
-    if (p.short_fecframe && !p.dummy_frame) p.n_slots >>= 2;
-    p.n_pilots = p.has_pilots ? ((p.n_slots - 1) >> 4) : 0;
-    p.plframe_len = (p.n_slots + 1) * 90 + 36 * p.n_pilots;
-    p.payload_len = p.plframe_len - 90;
-    p.xfecframe_len = p.n_slots * 90;
-    return p;
-}
-
-uint64_t plsc_codeword(int plsc)
-{
-    static const uint32_t G[6] = { 0x55555555u, 0x33333333u, 0x0f0f0f0fu, 0x00ff00ffu, 0x0000ffffu, 0xffffffffu };
-    const int i = (plsc >> 1) & 63;
-    uint32_t code32 = 0;
-    for (int row = 0; row < 6; row++) if (i & (0x20 >> row)) code32 ^= G[row];
-    const uint32_t b = (plsc & 1) ? ~code32 : code32; // (y1 !y1 y2 !y2 ...) when b7 = 1, (y1 y1 y2 y2 ...) otherwise
-    uint64_t cw = 0;
-    for (int t = 0; t < 32; t++) {
-        cw |= (uint64_t)((code32 >> t) & 1) << (2 * t + 1);
-        cw |= (uint64_t)((b >> t) & 1) << (2 * t);
-    }
-    return cw;
-}
-
-void plheader_symbols(int plsc, float* syms90)
-{
-    const double S = 0.7071067811865476;
-    const uint64_t cw = plsc_codeword(plsc) ^ kPlscScrambler;
-    for (int k = 0; k < 90; k++) {
-        const int bit = k < 26 ? (int)((kSofWord >> (25 - k)) & 1) : (int)((cw >> (89 - k)) & 1);
-        const double sg = bit ? -1.0 : 1.0;
-        syms90[2 * k] = (float)((k & 1) ? -S * sg : S * sg);
-        syms90[2 * k + 1] = (float)(S * sg);
-    }
-}
-
-bool pls_rank_table(const uint8_t* list, int n, uint8_t rank[128])
-{
-    if (n == 0) { for (int i = 0; i < 128; i++) rank[i] = (uint8_t)i; return true; }
-    for (int i = 0; i < 128; i++) rank[i] = 255;
-    int next = 0;
-    for (int i = 0; i < n; i++) {
-        if (list[i] >= 128) return false;
-        if (rank[list[i]] == 255) rank[list[i]] = (uint8_t)next++;
-    }
-    return true;
-}
-
 namespace {
 
+using plsc::kPi;
 using plsc::kS;
 using plsc::remove_modulation;
 using plsc::wave_sum;
-constexpr double kPi = 3.14159265358979323846;
+using plsc::wrap_pi;
 
 // the three data-aided sums over one PLHEADER (lib/pl_freq_sync.cc:201-226, :263-266); lane l holds symbols l and 64 + l
 __device__ inline void header_sums(const float2* __restrict__ x, int l, uint64_t cw, float2* sof, float2* hdr, float2* last36)
 {
-    const int bit0 = l < 26 ? (int)((kSofWord >> (25 - l)) & 1) : (int)((cw >> (89 - l)) & 1);
+    const int bit0 = plheader_bit(cw, l);
     const float2 t0 = remove_modulation(x[l], l, bit0);
     float2 t1 = make_float2(0.0f, 0.0f);
-    if (l < 26) t1 = remove_modulation(x[64 + l], 64 + l, (int)((cw >> (25 - l)) & 1));
+    if (l < 26) t1 = remove_modulation(x[64 + l], 64 + l, (int)((cw >> (25 - l)) & 1)); // plheader_bit(cw, 64 + l) without its SOF test
     const bool in_sof = l < 26, in_last = l >= 54;
     *sof = make_float2(wave_sum(in_sof ? t0.x : 0.0f), wave_sum(in_sof ? t0.y : 0.0f));
     *hdr = make_float2(wave_sum(t0.x + t1.x), wave_sum(t0.y + t1.y));
     *last36 = make_float2(wave_sum((in_last ? t0.x : 0.0f) + t1.x), wave_sum((in_last ? t0.y : 0.0f) + t1.y));
-}
-
-__device__ inline float wrap_pi(float d) // lib/pl_freq_sync.cc:280-285: the correction is made in double, the value kept as float
-{
-    if ((double)d > kPi) d = (float)((double)d - 2.0 * kPi);
-    else if ((double)d < -kPi) d = (float)((double)d + 2.0 * kPi);
-    return d;
 }
 
 // one wavefront per frame
@@ -165,7 +102,7 @@ __global__ __launch_bounds__(64) void pl_estimate_kernel(const float2* __restric
 
 } // namespace
 
-PlFrameHip::PlFrameHip(int gold_code, int plsc, int max_frames, int device) : DeviceStage(device), max_frames_(max_frames)
+PlFrameHip::PlFrameHip(int gold_code, int plsc, int max_frames, int device) : PlscListStage(device), max_frames_(max_frames)
 {
     pls_ = pls_parse(plsc);
     pp_ = new (std::nothrow) PlPayloadHip(gold_code, pls_.n_slots, pls_.has_pilots, max_frames, device);
@@ -181,7 +118,7 @@ PlFrameHip::PlFrameHip(int gold_code, int plsc, int max_frames, int device) : De
 
 PlFrameHip::~PlFrameHip() { delete pp_; }
 
-int PlFrameHip::set_expected_pls(const uint8_t* list, int n)
+int PlscListStage::set_expected_pls(const uint8_t* list, int n)
 {
     Entry on(*this);
     uint8_t rank[128];

@@ -29,7 +29,7 @@ __global__ __launch_bounds__(256) void pl_framer_kernel(const uint2* __restrict_
 {
     const PlFramerRec r = rec[blockIdx.y];
     const int s = 2 * (blockIdx.x * 256 + threadIdx.x); // first symbol of the pair, counted from the frame's start
-    const int plframe_len = 90 * (r.n_slots + 1) + 36 * r.n_pilots;
+    const int plframe_len = pl_frame_len(r.n_slots, r.n_pilots);
     const bool closing = closing_plsc >= 0 && blockIdx.y == gridDim.y - 1 && s >= plframe_len;
     if (s >= plframe_len + (closing ? 90 : 0)) return; // the spare blocks of a frame shorter than the longest one leave here
     const int n_pilots = r.n_pilots;
@@ -87,7 +87,7 @@ int PlFramerHip::set_sequence(const uint8_t* plsc, int n_frames)
     if (n_frames) HIP_RET(hipMemcpy(d_rec_, rec.data(), rec.size() * sizeof(PlFramerRec), hipMemcpyHostToDevice));
     rec_.swap(rec); in_syms_ = in; out_syms_ = out;
     longest_.resize(n_frames);
-    for (int f = 0, m = 0; f < n_frames; f++) longest_[f] = m = std::max(m, 90 * (rec_[f].n_slots + 1) + 36 * rec_[f].n_pilots);
+    for (int f = 0, m = 0; f < n_frames; f++) longest_[f] = m = std::max(m, pl_frame_len(rec_[f].n_slots, rec_[f].n_pilots));
     return 0;
 }
 
@@ -101,7 +101,7 @@ int PlFramerHip::frame_device(const float* d_xfecframes, int n_frames, int closi
     if (((uintptr_t)d_xfecframes | (uintptr_t)d_plframes) & 7) { call_err_.argument("symbol buffers must be 8-byte aligned"); return -1; }
     const bool wide = (((uintptr_t)d_xfecframes | (uintptr_t)d_plframes) & 15) == 0;
     const PlFramerRec& last = rec_[n_frames - 1];
-    const int longest = std::max(longest_[n_frames - 1], 90 * (last.n_slots + 1) + 36 * last.n_pilots + (closing_plsc >= 0 ? 90 : 0));
+    const int longest = std::max(longest_[n_frames - 1], pl_frame_len(last.n_slots, last.n_pilots) + (closing_plsc >= 0 ? 90 : 0));
     const dim3 grid((longest / 2 + 255) / 256, n_frames);
     hipLaunchKernelGGL(wide ? pl_framer_kernel<true> : pl_framer_kernel<false>, grid, dim3(256), 0, stream,
                        reinterpret_cast<const uint2*>(d_xfecframes), d_rn_, reinterpret_cast<const uint4*>(d_hdr_), d_rec_,

@@ -7,13 +7,9 @@
 #include <string>
 #include <vector>
 #include "device_stage.h"
+#include "pl_signal.h"
 
 namespace dvbs2 {
-
-// Rn(i) in 0..3, i < n, from the definition in ETSI EN 302 307-1 clause 5.5.4: x(i+18) = x(i+7) + x(i), x(0) = 1;
-// y(i+18) = y(i+10) + y(i+7) + y(i+5) + y(i), y(0..17) = 1; z_n(i) = x((i + n) mod (2^18 - 1)) + y(i);
-// Rn(i) = 2 z_n((i + 131072) mod (2^18 - 1)) + z_n(i). (The reference reaches the same numbers with register masks.)
-void pl_scrambling_rn(int gold_code, uint8_t* rn, int n);
 
 class PlPayloadHip : public DeviceStage {
 public:

@@ -4,19 +4,6 @@
 
 namespace dvbs2 {
 
-void pl_scrambling_rn(int gold_code, uint8_t* rn, int n)
-{
-    constexpr int P = (1 << 18) - 1;
-    std::vector<uint8_t> x(P), y(P);
-    for (int i = 0; i < 18; i++) { x[i] = i == 0; y[i] = 1; }
-    for (int i = 0; i + 18 < P; i++) {
-        x[i + 18] = x[i + 7] ^ x[i];
-        y[i + 18] = y[i + 10] ^ y[i + 7] ^ y[i + 5] ^ y[i];
-    }
-    auto z = [&](long i) { i %= P; return (uint8_t)(x[(i + gold_code) % P] ^ y[i]); };
-    for (int i = 0; i < n; i++) rn[i] = (uint8_t)(2 * z((long)i + 131072) + z(i));
-}
-
 // one thread per output (data) symbol; grid.y = frame. Frame f's payload starts at in[f * frame_stride + in_offset]:
 // (payload_len, 0) for payloads back to back, (plframe_len, 90) for whole PLFRAMEs (plframe_hip.hip)
 __global__ void pl_payload_kernel(const float2* __restrict__ in, const uint8_t* __restrict__ rn, const float* __restrict__ hphase,
@@ -39,7 +26,8 @@ __global__ void pl_payload_kernel(const float2* __restrict__ in, const uint8_t* 
         double s, c;
         sincos(-(theta0 + inc * (double)steps), &s, &c);
         const float2 x = in[(size_t)f * frame_stride + in_offset + k];
-        float dr, di; // descrambling: multiply by conj(exp(j Rn pi/2)) in {1, -j, -1, j} (lib/pl_descrambler.cc:56-58)
+        float dr, di; // descrambling: multiply by conj(exp(j Rn pi/2)) in {1, -j, -1, j} (lib/pl_descrambler.cc:56-58); the same
+                      // statement stands in pl_estimate_kernel (plframe_hip.hip), see plsc_decode.hpp for why it is no function
         switch (rn[k]) { case 0: dr = x.x; di = x.y; break; case 1: dr = x.y; di = -x.x; break;
                          case 2: dr = -x.x; di = -x.y; break; default: dr = -x.y; di = x.x; break; }
         const float pr = (float)c, pi = (float)s;
@@ -50,7 +38,7 @@ __global__ void pl_payload_kernel(const float2* __restrict__ in, const uint8_t* 
 PlPayloadHip::PlPayloadHip(int gold_code, int n_slots, int has_pilots, int max_frames, int device)
     : DeviceStage(device), n_slots_(n_slots), has_pilots_(has_pilots ? 1 : 0), max_frames_(max_frames)
 {
-    n_pilots_ = has_pilots_ ? ((n_slots_ - 1) >> 4) : 0; // lib/pl_signaling.cc:51
+    n_pilots_ = pl_pilot_blocks(n_slots_, has_pilots_);
     if (n_slots_ < 36 || n_slots_ > 360) { err_.argument("n_slots out of range (36..360)"); return; } // lib/pl_defs.h:19-20
     if (gold_code < 0 || gold_code >= (1 << 18) - 1) { err_.argument("gold code out of range"); return; }
     if (max_frames_ < 1 || max_frames_ > 65535) { err_.argument("max_frames must be in 1..65535 (frames are one launch dimension)"); return; }

@@ -1,20 +1,22 @@
 // plsc_decode.hpp -- the one-wavefront PLSC decoder shared by the PLFRAME front end (plframe_hip.hip, one wavefront per
 // frame) and the frame tracker (plsync_hip.hip, one wavefront per stream): closed-loop de-rotation by the SOF phase
 // (reference lib/pl_freq_sync.cc:429-436), pi/2 BPSK decisions (lib/pi2_bpsk.cc:45-196) and the RM(64,7) decoder
-// (lib/reed_muller.cc:120-210). The two PLHEADER constants are plain constexpr values that host code uses too (plframe_hip.h,
-// plsync_hip.h); the functions of namespace plsc are device code and expect all 64 lanes of the wavefront active.
+// (lib/reed_muller.cc:120-210); and the small device steps more than one PL kernel unit takes: wave_sum, the two ways of removing
+// the pi/2 BPSK modulation, wrap_pi. The PLHEADER constants and bit rule are pl_signal.h's. The functions of namespace plsc are device
+// code; those that exchange across lanes expect all 64 lanes of the wavefront active.
+// NOT here: the four-way Rn de-scrambling switch of pl_payload_kernel and pl_estimate_kernel. As a function, in either form (returned
+// pair, out-parameters, forced inline), it changes the order of the merge block's predecessors and with it the packed arithmetic the
+// compiler forms behind it in pl_payload_kernel (notes/pl_signal.md); the two statements stay until a change that may move kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "pl_signal.h" // kSofWord, kPlscScrambler, plheader_bit
 
 namespace dvbs2 {
-
-constexpr uint32_t kSofWord = 0x18D2E82u;                  // 26 bits, first transmitted bit is bit 25 (lib/pl_defs.h:42)
-constexpr uint64_t kPlscScrambler = 0x719d83c953422dfaull; // lib/pl_defs.h:44
-
 namespace plsc {
 
 constexpr float kS = 0.7071067811865476f;
+constexpr double kPi = 3.14159265358979323846;
 
 __device__ inline float wave_sum(float v)
 {
@@ -22,18 +24,36 @@ __device__ inline float wave_sum(float v)
     return v;
 }
 
-// x_k * conj(h_k): conj(h_k) = rot[k & 1] * (1 - 2 bit), rot = { (S, -S), (-S, -S) } (lib/pi2_bpsk.cc:23-34, :57-60)
+// Two ways of taking the pi/2 BPSK modulation off PLHEADER symbol k, kept side by side ON PURPOSE: they round differently.
+// remove_modulation: x_k * conj(h_k), conj(h_k) = rot[k & 1] * (1 - 2 bit), rot = { (S, -S), (-S, -S) } (lib/pi2_bpsk.cc:23-34, :57-60):
+// four products by S and two sums, the reference's values (plframe, plsync).
 __device__ inline float2 remove_modulation(float2 x, int k, int bit)
 {
     const float sg = bit ? -1.0f : 1.0f;
     const float cr = ((k & 1) ? -kS : kS) * sg, ci = -kS * sg;
     return make_float2(x.x * cr - x.y * ci, x.x * ci + x.y * cr);
 }
+// unmod: x_k conj(h_k) sqrt(2), conj(h_k) sqrt(2) = ((k odd ? -1 : 1), -1) (1 - 2 bit) (lib/pi2_bpsk.cc:18-43), so each component is one
+// sum or difference of the two input components: one rounding, no multiply (plcoarse, where the common scale does not reach an angle).
+__device__ inline float2 unmod(float2 x, int k, int bit)
+{
+    const float sg = bit ? -1.0f : 1.0f;
+    const float cr = (k & 1) ? -sg : sg, ci = -sg;
+    return make_float2(x.x * cr - x.y * ci, x.x * ci + x.y * cr);
+}
+
+// a phase difference back into [-pi, pi] (lib/pl_freq_sync.cc:166-171, :280-285): compared and corrected in double, kept as float
+__device__ inline float wrap_pi(float d)
+{
+    if ((double)d > kPi) d = (float)((double)d - 2.0 * kPi);
+    else if ((double)d < -kPi) d = (float)((double)d + 2.0 * kPi);
+    return d;
+}
 
 // the data-aided sum over the SOF (lib/pl_freq_sync.cc:217-220); lane l < 26 passes PLHEADER symbol l
 __device__ inline float2 sof_sum(float2 x_l, int l)
 {
-    const float2 t0 = remove_modulation(x_l, l, l < 26 ? (int)((kSofWord >> (25 - l)) & 1) : 0);
+    const float2 t0 = remove_modulation(x_l, l, l < 26 ? plheader_bit(0, l) : 0);
     const bool in_sof = l < 26;
     return make_float2(wave_sum(in_sof ? t0.x : 0.0f), wave_sum(in_sof ? t0.y : 0.0f));
 }

@@ -41,23 +41,17 @@ constexpr int kPlsyncMinSymbols = 33282 + 90;     // the longest PLFRAME and the
 // positions 0..63 in lo, 64..89 in hi. Bit 0 of a PLSC complements both bits of every pair's SECOND symbol relative to the
 // first, i.e. flips all 32 PLSC taps; no other PLSC bit reaches a within-pair differential.
 struct PlsyncTapBits { uint64_t lo, hi; };
-constexpr int plheader_bit0(int k) // bit k of the PLHEADER of PLSC 0: the RM codeword of PLSC 0 is all zeros
-{
-    return k < 26 ? (int)((kSofWord >> (25 - k)) & 1) : (int)((kPlscScrambler >> (89 - k)) & 1);
-}
 constexpr PlsyncTapBits plsync_tap_bits()
 {
     PlsyncTapBits t{ 0, 0 };
     for (int k = 1; k < 90; k++) {
-        const int flip = plheader_bit0(k) ^ plheader_bit0(k - 1);
+        const int flip = plheader_bit(kPlscScrambler, k) ^ plheader_bit(kPlscScrambler, k - 1); // the PLHEADER of PLSC 0
         const int tap_minus = (k & 1) ? flip : !flip; // tap = conj(differential): +j for odd k without a bit flip
         if (tap_minus) { if (k < 64) t.lo |= 1ull << k; else t.hi |= 1ull << (k - 64); }
     }
     return t;
 }
-// the same signs at run time from the 90 expected symbols of PLSC 0: imaginary parts (+-1) of the 25 SOF taps (header
-// positions 1..25) and the 32 PLSC taps (positions 27, 29 .. 89)
-void plsync_taps(float* sof25, float* plsc32);
+// (plsync_taps of pl_signal.h gives the same signs at run time from the 90 expected symbols of PLSC 0)
 
 struct PlSyncFrame { // one detected PLHEADER
     int64_t sof_index; // of the first PLHEADER symbol, counted from reset
@@ -78,14 +72,12 @@ struct PlSyncState { // lives on the device; read back by finish()
     int32_t hold;          // abs_base is the resume point of a pending frame: nothing is consumed before that frame is looked at again
 };
 
-class PlSyncHip : public DeviceStage {
+class PlSyncHip : public PlscListStage {
 public:
     // the ranges of the arguments are checked by dvbs2_plsync_create, which alone constructs this
     PlSyncHip(int plsc_or_minus1, int unlock_thresh, int max_symbols, int max_frames, int device);
     int max_symbols() const { return max_symbols_; }
     int max_frames() const { return max_frames_; }
-    void set_plsc_mode(int coherent, int soft) { coherent_ = coherent ? 1 : 0; soft_ = soft ? 1 : 0; }
-    int set_expected_pls(const uint8_t* list, int n);
     int reset();
     // DEVICE pointers. metric: n_syms floats, computed with the handle's history, the handle does not advance
     int metric_device(const float* d_syms, int n_syms, float* d_metric, hipStream_t stream);
@@ -97,8 +89,7 @@ public:
                       int32_t* d_count, hipStream_t stream);
 
 private:
-    int fixed_plsc_, unlock_thresh_, max_symbols_, max_frames_, coherent_ = 1, soft_ = 1;
-    uint8_t* d_rank_ = nullptr;
+    int fixed_plsc_, unlock_thresh_, max_symbols_, max_frames_;
     float* d_metric_ = nullptr;     // max_symbols floats
     float2* d_hist_ = nullptr;      // 2 x 89 symbols, the tracker writes the one the state does not select
     PlSyncState* d_state_ = nullptr;

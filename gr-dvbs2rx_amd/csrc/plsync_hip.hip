@@ -8,22 +8,11 @@
 // slower than a copy of the same bytes; notes/plsync_patches/metric_window_compile_time.patch restates the window as
 // compile-time recursion (straight-line packed adds) and awaits its run on the device.
 #include "plsync_hip.h"
+#include "plsc_decode.hpp"
 #include <cmath>
 #include <cstring>
 
 namespace dvbs2 {
-
-void plsync_taps(float* sof25, float* plsc32)
-{
-    float h[180];
-    plheader_symbols(0, h);
-    auto tap_im = [&](int k) { // the tap is conj(conj(h_k) h_{k-1}) = h_k conj(h_{k-1}): purely imaginary, magnitude 1
-        const double im = (double)h[2 * k + 1] * h[2 * k - 2] - (double)h[2 * k] * h[2 * k - 1];
-        return im < 0.0 ? -1.0f : 1.0f;
-    };
-    for (int k = 1; k <= 25; k++) sof25[k - 1] = tap_im(k);
-    for (int i = 0; i < 32; i++) plsc32[i] = tap_im(27 + 2 * i);
-}
 
 namespace {
 
@@ -33,17 +22,6 @@ constexpr PlsyncTapBits kTaps = plsync_tap_bits();
 enum { SEARCHING = 0, FOUND = 1, LOCKED = 2 }; // frame_sync_state_t, lib/pl_frame_sync.h
 
 constexpr bool tap_minus(int k) { return k < 64 ? ((kTaps.lo >> k) & 1) != 0 : ((kTaps.hi >> (k - 64)) & 1) != 0; }
-
-// pls_info_t::parse's plframe_len (lib/pl_signaling.cc:19-61), checked against pls_parse for all 128 values at create
-__host__ __device__ inline int plsync_frame_len(int plsc)
-{
-    const int modcod = plsc >> 2, dummy = modcod == 0;
-    int n_slots = modcod >= 1 && modcod <= 11 ? 360 : modcod >= 12 && modcod <= 17 ? 240 : modcod >= 18 && modcod <= 23 ? 180 :
-                  modcod >= 24 && modcod <= 28 ? 144 : 36;
-    if ((plsc & 2) && !dummy) n_slots >>= 2;
-    const int n_pilots = ((plsc & 1) && !dummy) ? ((n_slots - 1) >> 4) : 0;
-    return (n_slots + 1) * 90 + 36 * n_pilots;
-}
 
 // symbol g of the stream whose index 0 is x[0]: the 89 symbols before it come from the handle's history
 __device__ inline float2 stream_sym(const float2* __restrict__ x, const float2* __restrict__ hist, int n_syms, int g)
@@ -144,7 +122,7 @@ __global__ __launch_bounds__(64) void plsync_track_kernel(const float2* __restri
                 const float2 xa = stream_sym(x, hist, n_syms, n - 63 + l), xb = stream_sym(x, hist, n_syms, n - 64 + l);
                 plsc = plsc::decode_wave(xa, xb, atan2f(sof.y, sof.x), l, rank, coherent, soft);
             }
-            const int new_len = plsync_frame_len(plsc), sof_idx = n - 89;
+            const int new_len = pl_frame_shape(plsc).plframe_len, sof_idx = n - 89;
             if (nf >= max_frames || (int64_t)sof_idx + new_len + 90 > n_syms) {
                 // not reportable yet: leave the machine as it was before this index and ask for the stream from this SOF
                 consumed = sof_idx < 0 ? 0 : sof_idx;
@@ -186,7 +164,7 @@ __global__ __launch_bounds__(256) void plsync_gather_kernel(const float2* __rest
     const int f = blockIdx.x, t = threadIdx.x;
     const int nrec = n_frames < st->last_n_frames ? n_frames : st->last_n_frames, n_syms = st->last_n_syms;
     const int64_t base = st->last_base;
-    const int len = plsync_frame_len(wanted);
+    const int len = pl_frame_shape(wanted).plframe_len;
     auto selected = [&](int i) { // locked, of the wanted PLSC, and whole (with the header after it) inside the searched buffer
         if (i >= nrec) return false;
         const PlSyncFrame r = frames[i];
@@ -225,14 +203,13 @@ __global__ __launch_bounds__(256) void plsync_gather_kernel(const float2* __rest
 } // namespace
 
 PlSyncHip::PlSyncHip(int plsc_or_minus1, int unlock_thresh, int max_symbols, int max_frames, int device)
-    : DeviceStage(device), fixed_plsc_(plsc_or_minus1), unlock_thresh_(unlock_thresh), max_symbols_(max_symbols), max_frames_(max_frames)
+    : PlscListStage(device), fixed_plsc_(plsc_or_minus1), unlock_thresh_(unlock_thresh), max_symbols_(max_symbols), max_frames_(max_frames)
 {
-    // the compile-time tap signs against the expected symbols, the device's frame length against pls_parse
+    // the compile-time tap signs against the expected symbols
     float sof[25], pl[32];
     plsync_taps(sof, pl);
     for (int k = 1; k <= 25; k++) if ((sof[k - 1] < 0.0f) != tap_minus(k)) { err_.argument("SOF tap signs disagree with the PLHEADER"); return; }
     for (int i = 0; i < 32; i++) if ((pl[i] < 0.0f) != tap_minus(27 + 2 * i)) { err_.argument("PLSC tap signs disagree with the PLHEADER"); return; }
-    for (int p = 0; p < 128; p++) if (plsync_frame_len(p) != pls_parse(p).plframe_len) { err_.argument("frame length disagrees with pls_parse"); return; }
     DeviceGuard dev_guard(device_);
     if (!dev_guard.ok || alloc(&d_rank_, 128) != hipSuccess || alloc(&d_metric_, (size_t)max_symbols_) != hipSuccess ||
         alloc(&d_hist_, 2 * kHist) != hipSuccess || alloc(&d_state_, 1) != hipSuccess) {
@@ -241,22 +218,13 @@ PlSyncHip::PlSyncHip(int plsc_or_minus1, int unlock_thresh, int max_symbols, int
     if (set_expected_pls(nullptr, 0) || reset()) { err_.argument(call_err_.text); call_err_ = {}; } // (device failure, kArgument: notes/stage_error_codes.md)
 }
 
-int PlSyncHip::set_expected_pls(const uint8_t* list, int n)
-{
-    Entry on(*this);
-    uint8_t rank[128];
-    if (!pls_rank_table(list, n, rank)) { call_err_.argument("codeword indexes must be within [0, 128)"); return -1; } // lib/reed_muller.cc:48-52
-    if (!on.ok || hipMemcpy(d_rank_, rank, 128, hipMemcpyHostToDevice) != hipSuccess) { call_err_.device("copy of the codeword list failed"); return -1; }
-    return 0;
-}
-
 int PlSyncHip::reset()
 {
     Entry on(*this);
     PlSyncState s;
     std::memset(&s, 0, sizeof(s));
     s.abs_last_peak = -1; // d_sym_cnt = 0 before the first symbol (lib/pl_frame_sync.cc:23)
-    s.frame_len = fixed_plsc_ >= 0 ? plsync_frame_len(fixed_plsc_) : 0; // lib/plsync_cc_impl.cc:159, lib/pl_frame_sync.cc:28
+    s.frame_len = fixed_plsc_ >= 0 ? pl_frame_shape(fixed_plsc_).plframe_len : 0; // lib/plsync_cc_impl.cc:159, lib/pl_frame_sync.cc:28
     if (!on.ok || hipMemcpy(d_state_, &s, sizeof(s), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemset(d_hist_, 0, 2 * kHist * sizeof(float2)) != hipSuccess) { call_err_.device("reset of the device state failed"); return -1; }
     return 0;

@@ -1,6 +1,6 @@
 // pulse_hip.hip -- see pulse_hip.h.
 #include "pulse_hip.h"
-#include "symsync_hip.h" // rrc
+#include "rrc_pulse.h"
 #include <algorithm>
 #include <cmath>
 

@@ -27,9 +27,6 @@
 
 namespace dvbs2 {
 
-// inc (radians per sample, any finite value) as turns in 2^-64 units, reduced modulo one turn
-uint64_t rotator_inc_turns(double inc);
-
 // median over `regions` HIP-event regions of one rotation of n_syms symbols (one segment, out of place) and, in the same run, of a
 // plain 16-byte-per-lane copy of the same bytes on the same grid; 0, or the StageCode of the failure with its text in *err
 int rotator_measure(int device, int n_syms, int regions, double* rot_ms, double* copy_ms, std::string* err);

@@ -56,9 +56,6 @@ struct SymSyncGeom {
 void symsync_loop_constants(int sps, float loop_bw, float damping, float rolloff, float* Kp, float* K1, float* K2);
 // subfilter length and delay (:68-80) and the block's history (:244-256); -1 on a bad argument
 int symsync_geometry(int sps, int rrc_delay, int n_subfilt, int interp, int* subfilt_len, int* subfilt_delay, int* history);
-// the RRC impulse response at t symbols (unit symbol rate, rolloff a in [0, 1]) in closed form, the two singular points by their limits:
-// the one prototype behind symsync_taps and pulse_taps (pulse_hip.h). Host only.
-double rrc(double t, double a);
 // n_subfilt * subfilt_len floats, [subfilter][tap], each subfilter flipped (:82-110); -1 on a bad argument
 int symsync_taps(int sps, float rolloff, int rrc_delay, int n_subfilt, float* bank);
 

@@ -1,5 +1,6 @@
 // symsync_hip.hip -- see symsync_hip.h.
 #include "symsync_hip.h"
+#include "rrc_pulse.h"
 #include <cmath>
 #include <cstring>
 #include <new>
@@ -39,16 +40,6 @@ int symsync_geometry(int sps, int rrc_delay, int n_subfilt, int interp, int* sub
     if (subfilt_delay) *subfilt_delay = (L - 1) / 2;
     if (history) *history = (interp == 0 ? L - 1 : interp == 1 ? 1 : 3) + sps / 2;
     return 0;
-}
-
-// root raised cosine at t symbols, unit symbol rate; the two singular points by their limits (declared in symsync_hip.h: pulse_taps uses it too)
-double rrc(double t, double a)
-{
-    const double pi = M_PI;
-    if (t == 0.0) return 1.0 - a + 4.0 * a / pi;
-    if (a > 0.0 && fabs(fabs(4.0 * a * t) - 1.0) < 1e-9)
-        return a / sqrt(2.0) * ((1.0 + 2.0 / pi) * sin(pi / (4.0 * a)) + (1.0 - 2.0 / pi) * cos(pi / (4.0 * a)));
-    return (sin(pi * t * (1.0 - a)) + 4.0 * a * t * cos(pi * t * (1.0 + a))) / (pi * t * (1.0 - 16.0 * a * a * t * t));
 }
 
 int symsync_taps(int sps, float rolloff, int rrc_delay, int n_subfilt, float* bank)

@@ -1,11 +1,11 @@
 // stdin rows "plsc plsc ..." (one sequence each, values 0..255) -> one line "in_offset:out_offset ... | in_syms out_syms" each, or
-// "refused: <text>". Drives the host-only layout code of the PL framer (csrc/plframer_hip.h) outside Python, so that it can be built
-// with -fsanitize=address,undefined together with the host source it calls (csrc/plframe_hip.hip: pls_parse).
+// "refused: <text>". Drives the host-only layout code of the PL framer (csrc/pl_signal.cpp) outside Python, so that it can be built
+// with -fsanitize=address,undefined; it links no kernel unit.
 #include <cstdio>
 #include <iostream>
 #include <sstream>
 #include <vector>
-#include "../gr-dvbs2rx_amd/csrc/plframer_hip.h"
+#include "../gr-dvbs2rx_amd/csrc/pl_signal.h"
 
 int main()
 {

@@ -1,6 +1,6 @@
 // stdin rows -> one line each. Drives the host-only code of the pulse shaper (csrc/pulse_hip.hip: geometry, tap design, tap scaling, the
-// argument check of the class) outside Python, so that it can be built with -fsanitize=address,undefined together with the host source it
-// calls (csrc/symsync_hip.hip: rrc). Floats travel as the hexadecimal bits of a float32, so both directions are exact.
+// argument check of the class) outside Python, so that it can be built with -fsanitize=address,undefined (rrc is csrc/rrc_pulse.h's, a
+// header). Floats travel as the hexadecimal bits of a float32, so both directions are exact.
 //   geom sps rrc_delay                      -> "ntaps history delay" or "refused"
 //   taps sps rolloff rrc_delay tau gain     -> the taps, or "refused"
 //   scale sps fullscale n tap ... tap       -> the scaled taps, or "refused"

@@ -13,9 +13,9 @@ from dvbs2rx_amd import capi, ddc_geometry, ddc_produce, ddc_tile
 
 @pytest.fixture(scope="module")
 def host_exe(tmp_path_factory):
-    """tests/ddc_host_main.cpp with the host sources it calls, host code under AddressSanitizer and UBSan (device code is not
+    """tests/ddc_host_main.cpp with the host source it calls, host code under AddressSanitizer and UBSan (device code is not
     instrumented and none of it runs)."""
-    return T.build_host_program(tmp_path_factory.mktemp("ddc"), "ddc_host_main.cpp", ("ddc_hip.hip", "rotator_hip.hip"))
+    return T.build_host_program(tmp_path_factory.mktemp("ddc"), "ddc_host_main.cpp", ("ddc_hip.hip",))
 
 
 def _hex(taps):

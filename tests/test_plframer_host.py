@@ -70,8 +70,7 @@ def test_null_handle():
 def layout_exe(tmp_path_factory):
     """tests/plframer_host_main.cpp with the host source it calls, host code under AddressSanitizer and UBSan (device code is not
     instrumented and none of it runs)."""
-    return T.build_host_program(tmp_path_factory.mktemp("plframer"), "plframer_host_main.cpp", ("plframe_hip.hip", "plpayload_hip.hip"),
-                                fp_contract_off=False)
+    return T.build_host_program(tmp_path_factory.mktemp("plframer"), "plframer_host_main.cpp", ("pl_signal.cpp",), fp_contract_off=False)
 
 
 def test_layout_program_under_the_host_sanitizers(layout_exe):

@@ -14,7 +14,7 @@ from dvbs2rx_amd import capi, pulse_geometry, pulse_scale_taps, pulse_taps
 def host_exe(tmp_path_factory):
     """tests/pulse_host_main.cpp with the host source it calls, host code under AddressSanitizer and UBSan (device code is not
     instrumented and none of it runs)."""
-    return T.build_host_program(tmp_path_factory.mktemp("pulse"), "pulse_host_main.cpp", ("pulse_hip.hip", "symsync_hip.hip"))
+    return T.build_host_program(tmp_path_factory.mktemp("pulse"), "pulse_host_main.cpp", ("pulse_hip.hip",))
 
 
 def _hex(taps):
