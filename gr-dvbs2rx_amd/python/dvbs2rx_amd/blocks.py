@@ -23,6 +23,7 @@ __all__ = ["get_fec_info", "rate_id", "LdpcDecoder", "BchDecoder", "Demapper", "
            "PlFramer", "plframer_layout", "PulseShaper", "pulse_geometry", "pulse_taps", "pulse_scale_taps",
            "Resampler", "resamp_step", "resamp_geometry", "resamp_max_out", "resamp_check",
            "Ddc", "ddc_geometry", "ddc_produce", "ddc_check", "ddc_tile",
+           "Spectrum", "spectrum_geometry", "spectrum_window", "spectrum_twiddles", "spectrum_check", "spectrum_carriers",
            "BbFramer", "bbheader_build", "crc8"]
 
 DEFAULT_TRIALS = 25  # reference lib/ldpc_decoder_bb_impl.cc:391
@@ -1611,4 +1612,111 @@ class Ddc(_Handle):
         n = C.c_int64()
         check(lib.dvbs2_ddc_process_device(self._h, d_in or None, int(in_stride), int(n_in), int(n_inputs), int(n_channels), d_out or None,
                                            int(out_stride), C.byref(n), stream or None))
+        return n.value
+
+
+SPECTRUM_WINDOWS = {"rect": capi.SPECTRUM_RECT, "hann": capi.SPECTRUM_HANN, "hamming": capi.SPECTRUM_HAMMING,
+                    "blackman-harris": capi.SPECTRUM_BLACKMAN_HARRIS}
+
+
+def spectrum_geometry(nfft, hop, avg, n_in):
+    """(n_seg, n_rows, used_samples) of a call of n_in samples per stream (dvbs2_spectrum_geometry). Host only."""
+    return _ints(3, lib.dvbs2_spectrum_geometry, int(nfft), int(hop), int(avg), int(n_in))
+
+
+def spectrum_window(kind, nfft):
+    """The periodic window `kind` ("rect", "hann", "hamming", "blackman-harris" or its number) as float32 [nfft]
+    (dvbs2_spectrum_window). Host only."""
+    w = np.zeros(max(int(nfft), 1), np.float32)
+    check(lib.dvbs2_spectrum_window(SPECTRUM_WINDOWS.get(kind, kind), int(nfft), w.ctypes.data))
+    return w
+
+
+def spectrum_twiddles(nfft):
+    """The transform's one table, complex64 [nfft / 2] (dvbs2_spectrum_twiddles). Host only."""
+    t = np.zeros(max(int(nfft) // 2, 1), np.complex64)
+    check(lib.dvbs2_spectrum_twiddles(int(nfft), t.ctypes.data))
+    return t
+
+
+def _window_arg(window, nfft):
+    if window is None:
+        return None
+    if isinstance(window, (str, int)):
+        return spectrum_window(window, nfft)
+    w = np.ascontiguousarray(window, np.float32).reshape(-1)
+    if w.size != int(nfft):
+        raise ValueError("the window must have nfft values")
+    return w
+
+
+def spectrum_check(nfft, hop, avg=0, window=None, max_streams=1, max_samples=1 << 20):
+    """Raises what Spectrum(...) would raise for these arguments, without a device (dvbs2_spectrum_check)."""
+    w = _window_arg(window, nfft)
+    check(lib.dvbs2_spectrum_check(int(nfft), int(hop), int(avg), None if w is None else w.ctypes.data, int(max_streams), int(max_samples)))
+
+
+def spectrum_carriers(psd, shifted=True, max_out=64, smooth=None, floor_quantile=None, threshold_db=None, min_gap=None, min_width=None):
+    """The carriers of one row of a power spectrum (dvbs2_spectrum_carriers): a record array (capi.SPECTRUM_CARRIER_DTYPE) sorted by
+    centre -- centre and bandwidth in cycles per sample, level and floor in the row's units, the edge bins -- and the number found,
+    which may exceed max_out. Parameters left at None take the library's defaults. Host only."""
+    row = np.ascontiguousarray(psd, np.float32).reshape(-1)
+    params = None
+    if any(v is not None for v in (smooth, floor_quantile, threshold_db, min_gap, min_width)):
+        params = capi.SpectrumCarrierParams(0.25 if floor_quantile is None else float(floor_quantile), 6.0 if threshold_db is None else float(threshold_db),
+                                            9 if smooth is None else int(smooth), 4 if min_gap is None else int(min_gap),
+                                            8 if min_width is None else int(min_width), 0)
+    out = np.zeros(max(int(max_out), 1), capi.SPECTRUM_CARRIER_DTYPE)
+    n = C.c_int()
+    check(lib.dvbs2_spectrum_carriers(row.ctypes.data if row.size else None, int(row.size), int(bool(shifted)),
+                                      C.addressof(params) if params is not None else None, out.ctypes.data, int(max_out), C.byref(n)))
+    return out[:min(n.value, int(max_out))], n.value
+
+
+class Spectrum(_Handle):
+    """Power spectra of sample streams by Welch's method: segments of nfft samples every hop samples, windowed, transformed, their powers
+    averaged over avg segments per row (avg = 0: all segments of a call in one row) and scaled so that white noise of variance sigma^2
+    gives sigma^2 in every bin (notes/spectrum.md). No state between calls. window: None (periodic Hann), a name or number of
+    spectrum_window, or nfft values. shifted: DC at index nfft / 2, else first."""
+    _destroy = lib.dvbs2_spectrum_destroy
+
+    def __init__(self, nfft, hop=None, avg=0, window=None, shifted=True, max_streams=1, max_samples=1 << 20, device=0):
+        hop = int(nfft) // 2 if hop is None else hop
+        w = _window_arg(window, nfft)
+        check(lib.dvbs2_spectrum_create(C.byref(self._h), int(nfft), int(hop), int(avg), None if w is None else w.ctypes.data, int(bool(shifted)),
+                                        int(max_streams), int(max_samples), device))
+        self.max_streams, self.max_samples = max_streams, max_samples
+        v, p = [C.c_int() for _ in range(4)], C.c_double()
+        check(lib.dvbs2_spectrum_params(self._h, *v, C.byref(p)))
+        self.nfft, self.hop, self.avg, self.shifted = v[0].value, v[1].value, v[2].value, bool(v[3].value)
+        self.window_power = p.value  # sum w[n]^2 in double
+
+    def geometry(self, n_in):
+        """(n_seg, n_rows, used_samples) of a call of n_in samples per stream. Host only."""
+        return spectrum_geometry(self.nfft, self.hop, self.avg, n_in)
+
+    def work(self, samples):
+        """HOST buffer: complex64 [n_streams, n_in] (or a vector: one stream). Returns float32 [n_streams, n_rows, nfft]."""
+        x = np.asarray(samples)
+        if x.dtype != np.complex64:
+            raise TypeError(f"samples must be complex64, not {x.dtype}")
+        if x.ndim == 1:
+            x = x.reshape(1, -1)
+        if x.ndim != 2 or not x.flags.c_contiguous:
+            raise ValueError("samples must be a C-contiguous vector or [n_streams, n_in] matrix")
+        n_streams, n_in = x.shape
+        rows = self.geometry(n_in)[1] if n_in <= self.max_samples else 0
+        out = np.empty((max(n_streams, 1), max(rows, 1), self.nfft), np.float32)
+        n = C.c_int()
+        check(lib.dvbs2_spectrum_process(self._h, x.ctypes.data if x.size else None, int(n_in), int(n_in), int(n_streams), out.ctypes.data,
+                                         int(max(rows, 1) * self.nfft), C.byref(n)))
+        return out[:n_streams, :n.value]
+
+    def work_device(self, d_in, in_stride, n_in, n_streams, d_out, out_stride, stream=0):
+        """DEVICE addresses (d_in 8-byte, d_out 4-byte aligned, not overlapping), asynchronous on `stream`: stream i reads n_in complex64
+        samples at d_in + 8 * i * in_stride and writes n_rows rows of nfft float32 at d_out + 4 * i * out_stride; out_stride >= n_rows *
+        nfft. Returns n_rows (what geometry() said before the call). One call in flight per handle."""
+        n = C.c_int()
+        check(lib.dvbs2_spectrum_process_device(self._h, d_in or None, int(in_stride), int(n_in), int(n_streams), d_out or None, int(out_stride),
+                                                C.byref(n), stream or None))
         return n.value

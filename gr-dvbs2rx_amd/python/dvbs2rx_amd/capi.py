@@ -29,6 +29,8 @@ PULSE_TILE = 512  # DVBS2_PULSE_TILE: symbols per workgroup of the pulse shaper'
 RESAMP_TILE = 1024  # DVBS2_RESAMP_TILE: output samples per workgroup of the resampler's kernel
 DDC_SPAN, DDC_MAX_TILE = 9216, 1024  # DVBS2_DDC_SPAN, DVBS2_DDC_MAX_TILE: a workgroup of the down-converter's kernel stages at most DDC_SPAN
 # mixed samples and writes min(DDC_MAX_TILE, (DDC_SPAN - (ntaps - 1)) // decim) output samples
+SPECTRUM_CHUNK = 16  # DVBS2_SPECTRUM_CHUNK: segments whose powers one workgroup of the spectrum kernel adds in order
+SPECTRUM_RECT, SPECTRUM_HANN, SPECTRUM_HAMMING, SPECTRUM_BLACKMAN_HARRIS = 0, 1, 2, 3  # DVBS2_SPECTRUM_*: the windows
 AGC_TILE = 64  # DVBS2_AGC_TILE: samples per stream and tile of the AGC's kernel
 AWGN_TILE = 512  # DVBS2_AWGN_TILE: samples of a row per workgroup of the AWGN channel's kernel
 IQ_U8, IQ_S8, IQ_S16 = 0, 1, 2  # DVBS2_IQ_*: the code formats of the IQ sample converter
@@ -68,6 +70,13 @@ class SymSyncState(C.Structure):
                 ("last_xi_im", C.c_float), ("jump", C.c_int32), ("init", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
 
 
+class SpectrumCarrierParams(C.Structure):
+    """dvbs2_spectrum_carrier_params_t"""
+    _fields_ = [("floor_quantile", C.c_double), ("threshold_db", C.c_double), ("smooth", C.c_int32), ("min_gap", C.c_int32),
+                ("min_width", C.c_int32), ("reserved", C.c_int32)]
+
+
+SPECTRUM_CARRIER_DTYPE = [("centre", "<f8"), ("bandwidth", "<f8"), ("level", "<f8"), ("floor", "<f8"), ("lo_bin", "<i4"), ("hi_bin", "<i4")]  # dvbs2_spectrum_carrier_t
 PLSYNC_FRAME_DTYPE = [("sof_index", "<i8"), ("metric", "<f4"), ("plsc", "u1"), ("flags", "u1"), ("reserved", "u1", (2,))]
 PLSYNC_SEARCHING, PLSYNC_FOUND, PLSYNC_LOCKED = 0, 1, 2
 PLSYNC_REAL_PEAK, PLSYNC_FLAG_LOCKED = 1, 2
@@ -266,6 +275,16 @@ SYMBOLS = {
     "dvbs2_ddc_state": (_i, [_vp, _vp]),
     "dvbs2_ddc_process_device": (_i, [_vp, _vp, C.c_int64, _i, _i, _i, _vp, C.c_int64, C.POINTER(C.c_int64), _vp]),
     "dvbs2_ddc_process": (_i, [_vp, _vp, C.c_int64, _i, _i, _i, _vp, C.c_int64, C.POINTER(C.c_int64)]),
+    "dvbs2_spectrum_geometry": (_i, [_i, _i, _i, _i, _ip, _ip, _ip]),
+    "dvbs2_spectrum_window": (_i, [_i, _i, _vp]),
+    "dvbs2_spectrum_twiddles": (_i, [_i, _vp]),
+    "dvbs2_spectrum_check": (_i, [_i, _i, _i, _vp, _i, _i]),
+    "dvbs2_spectrum_carriers": (_i, [_vp, _i, _i, _vp, _vp, _i, _ip]),
+    "dvbs2_spectrum_create": (_i, [C.POINTER(_vp), _i, _i, _i, _vp, _i, _i, _i, _i]),
+    "dvbs2_spectrum_destroy": (None, [_vp]),
+    "dvbs2_spectrum_params": (_i, [_vp, _ip, _ip, _ip, _ip, C.POINTER(C.c_double)]),
+    "dvbs2_spectrum_process_device": (_i, [_vp, _vp, C.c_int64, _i, _i, _vp, C.c_int64, _ip, _vp]),
+    "dvbs2_spectrum_process": (_i, [_vp, _vp, C.c_int64, _i, _i, _vp, C.c_int64, _ip]),
     "dvbs2_bbdeheader_create": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i]),
     "dvbs2_bbdeheader_create_raw": (_i, [C.POINTER(_vp), _i, _i, _i]),
     "dvbs2_bbdeheader_destroy": (None, [_vp]),

@@ -1090,6 +1090,77 @@ int dvbs2_ddc_process_device(dvbs2_ddc_t* h, const float* d_in, int64_t in_strid
 int dvbs2_ddc_process(dvbs2_ddc_t* h, const float* in, int64_t in_stride, int n_in, int n_inputs, int n_channels, float* out,
                       int64_t out_stride, int64_t* n_out);
 
+/* ---- spectrum estimate and carrier finder: what tells dvbs2_ddc_set_channel, the down-converter's decimation and dvbs2_pulse_taps
+ * where the carriers of a capture sit. Power spectra by Welch's method (windowed, overlapped segments, averaged periodograms), the data
+ * of GNU Radio's freq_sink_c and waterfall_sink_c; neither is in the reference tree: the stage is UNPINNED against it. A handle holds
+ * nfft = 2^t (t in 6..13), hop (1..2^24), avg (>= 0), a real window of nfft floats (null: periodic Hann) and the bin order; it holds NO
+ * signal state: a call is a pure function of its input. What is defined, and tested bit for bit against a float32 restatement
+ * (tests/spectrum_model.py), is this:
+ *   SEGMENTS. Segment s of a stream is the call's samples [s hop, s hop + nfft); n_seg = (n_in - nfft) / hop + 1 for n_in >= nfft,
+ *   else 0. With avg > 0 a row is avg consecutive segments, n_rows = n_seg / avg, and what is left over is not used; with avg == 0 the
+ *   call's segments form one row. dvbs2_spectrum_geometry gives the counts before the call.
+ *   WINDOW. xw = (re w[n], im w[n]), one float product each.
+ *   TRANSFORM. X[k] = sum_n xw[n] e^{-2 pi j k n / nfft} as the radix-2 decimation-in-time graph over the bit-reversed input: stage
+ *   s = 1..t pairs i and i + 2^(s-1), (a, b) -> (a + T, a - T), T = W b, W entry (i mod 2^(s-1)) nfft / 2^s of ONE table of nfft / 2
+ *   entries (float(cos(2 pi i / nfft)), float(-sin(2 pi i / nfft))), computed in double (dvbs2_spectrum_twiddles). Stage 1 has no
+ *   product; every later stage does Tr = Wr br - Wi bi, Ti = Wr bi + Wi br for every index, nothing fused.
+ *   POWER AND AVERAGE. p = Xr Xr + Xi Xi. The segments of a row are cut into chunks of DVBS2_SPECTRUM_CHUNK consecutive segments; a
+ *   chunk's sum per bin is float additions in ascending segment order onto +0.0f, the row is the chunk sums added in ascending order
+ *   onto +0.0f, then one float product with scale = float(1 / (n sum w[n]^2)), n the row's segment count, in double on the host. White
+ *   noise of variance sigma^2 gives sigma^2 in every bin.
+ *   OUTPUT. Row r of stream i is nfft floats at d_out + i out_stride + r nfft: bins 0..nfft-1, DC first, or with shifted != 0 bins
+ *   nfft/2..nfft-1, 0..nfft/2-1, DC at index nfft/2. Non-finite input propagates as IEEE says; denormals are kept.
+ * Stream i reads n_in interleaved (re, im) samples at d_in + i in_stride (complex elements, 8-byte aligned); out_stride counts floats
+ * (4-byte aligned) and is also the capacity of a stream's rows. Two launches at most, no allocation, no host synchronisation; the chunk
+ * sums of a call live in a buffer of the handle sized at create from max_streams and max_samples: ONE CALL IN FLIGHT PER HANDLE.
+ * Refused with DVBS2_ESIZE: n_in > max_samples, n_streams > max_streams. Refused with DVBS2_EINVAL and a text that names the argument:
+ * negative counts, a null or misaligned buffer where something is to be written, with n_streams > 1 an in_stride < n_in, an out_stride
+ * < n_rows nfft. A refused call writes nothing. n_in < nfft (or fewer than avg segments) is a successful call with n_rows == 0 that
+ * writes nothing. Creation refuses (DVBS2_EINVAL) an nfft that is no power of two in 64..8192, hop outside 1..2^24, a negative avg, a
+ * window value that is not finite, a window of zeros, max_streams outside 1..65535, max_samples outside 1..2^24.
+ * Host only, no device needed: dvbs2_spectrum_geometry (each output nullable; used_samples is one past the last sample a row reads),
+ * dvbs2_spectrum_window (periodic rectangular, Hann, Hamming and 4-term Blackman-Harris windows, evaluated in double and rounded
+ * once), dvbs2_spectrum_twiddles (nfft / 2 (re, im) pairs), dvbs2_spectrum_check (the argument check of dvbs2_spectrum_create) and
+ * dvbs2_spectrum_carriers.
+ * CARRIER FINDER. One row in double arithmetic, deterministic (tests/spectrum_model.py restates it). The row is smoothed by a circular
+ * moving average of `smooth` bins (odd); the noise floor is the element floor(floor_quantile (nfft - 1)) of the sorted smoothed row;
+ * regions are circular runs of bins above floor 10^(threshold_db / 10), so a carrier across the band edge is one region; regions with
+ * fewer than min_gap bins between them become one and regions of fewer than min_width bins are dropped. Per region: `centre` in cycles
+ * per sample in [-0.5, 0.5), the centroid of (smoothed - floor) over the region and its skirts (outwards on either side while the
+ * difference stays positive, at most half way to the neighbouring region); `level`, the median of (smoothed - floor) over the region's middle
+ * half; `bandwidth` in cycles per sample between the two half-level crossings, linearly interpolated; `floor`; the two edge bins as
+ * indices of the caller's row. A root-raised-cosine carrier's power spectrum is at half its plateau at +-Rs / 2 for any roll-off:
+ * bandwidth is the symbol rate, 1 / bandwidth the samples per symbol, -2 pi centre the phase_inc of dvbs2_ddc_set_channel.
+ * params == NULL: smooth 9, floor_quantile 0.25, threshold_db 6, min_gap 4, min_width 8. Records come sorted by centre; *n_found is
+ * the number found, of which the first max_out are written. Refused: values that are negative or not finite in the row, nfft no power
+ * of two in 16..2^20, smooth even or outside 1..nfft/2, floor_quantile outside 0..1, threshold_db outside (0, 200], min_gap or
+ * min_width outside 1..nfft. ---- */
+typedef struct dvbs2_spectrum dvbs2_spectrum_t;
+#define DVBS2_SPECTRUM_CHUNK 16
+#define DVBS2_SPECTRUM_RECT 0
+#define DVBS2_SPECTRUM_HANN 1
+#define DVBS2_SPECTRUM_HAMMING 2
+#define DVBS2_SPECTRUM_BLACKMAN_HARRIS 3
+typedef struct { double floor_quantile, threshold_db; int32_t smooth, min_gap, min_width, reserved; } dvbs2_spectrum_carrier_params_t;
+typedef struct { double centre, bandwidth, level, floor; int32_t lo_bin, hi_bin; } dvbs2_spectrum_carrier_t;
+int dvbs2_spectrum_geometry(int nfft, int hop, int avg, int n_in, int* n_seg, int* n_rows, int* used_samples);
+int dvbs2_spectrum_window(int kind, int nfft, float* out);
+int dvbs2_spectrum_twiddles(int nfft, float* out);
+int dvbs2_spectrum_check(int nfft, int hop, int avg, const float* window, int max_streams, int max_samples);
+int dvbs2_spectrum_carriers(const float* psd, int nfft, int shifted, const dvbs2_spectrum_carrier_params_t* params,
+                            dvbs2_spectrum_carrier_t* out, int max_out, int* n_found);
+int dvbs2_spectrum_create(dvbs2_spectrum_t** h, int nfft, int hop, int avg, const float* window, int shifted, int max_streams,
+                          int max_samples, int device);
+void dvbs2_spectrum_destroy(dvbs2_spectrum_t* h);
+/* each nullable; window_power: sum w[n]^2 in double, ascending n */
+int dvbs2_spectrum_params(const dvbs2_spectrum_t* h, int* nfft, int* hop, int* avg, int* shifted, double* window_power);
+/* DEVICE pointers, asynchronous on `stream`; n_rows is a HOST value (nullable), known before anything is launched */
+int dvbs2_spectrum_process_device(dvbs2_spectrum_t* h, const float* d_in, int64_t in_stride, int n_in, int n_streams, float* d_out,
+                                  int64_t out_stride, int* n_rows, void* stream);
+/* host pointers, synchronous, staged through buffers of the handle; the same arguments and checks, alignment apart */
+int dvbs2_spectrum_process(dvbs2_spectrum_t* h, const float* in, int64_t in_stride, int n_in, int n_streams, float* out,
+                           int64_t out_stride, int* n_rows);
+
 /* ---- downstream neighbour: BBFRAME de-header, replaces bbdeheader_bb_impl::general_work (reference
  * lib/bbdeheader_bb_impl.cc:144-264) with parse_bbheader (:77-136) and check_crc8 (:138-142, generator
  * x^8 + x^7 + x^6 + x^4 + x^2 + 1, :55). Input: whole descrambled BBFRAMEs of kbch / 8 bytes (what dvbs2_bch_decode /
