@@ -24,7 +24,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <string>
-#include "device_stage.h"
+#include "stream_stage.h"
 
 namespace dvbs2 {
 
@@ -35,13 +35,11 @@ std::string agc_check(float rate, float reference, float gain, float max_gain);
 // Host only. Streams per wavefront for a batch of n_streams: the smallest of 8, 16, 32 that needs at most 2048 wavefronts
 int agc_lanes(int n_streams);
 
-class AgcHip : public DeviceStage {
+class AgcHip : public StreamStage {
 public:
     AgcHip(float rate, float reference, float gain, float max_gain, int max_streams, int max_samples, int device);
     // empty when the arguments are acceptable, else what is wrong with them (no device needed)
     static std::string check_args(float rate, float reference, float gain, float max_gain, int max_streams, int max_samples);
-    int max_streams() const { return max_streams_; }
-    int max_samples() const { return max_samples_; }
     float rate() const { return rate_; }
     float reference() const { return reference_; }
     float max_gain() const { return max_gain_; }
@@ -61,7 +59,6 @@ private:
     int fill(int first, int count, float g);
     float rate_ = 0, reference_ = 0, gain0_ = 0, max_gain_ = 0;
     bool swap_iq_ = false;
-    int max_streams_, max_samples_;
     float* d_state_ = nullptr; // max_streams gains
 };
 

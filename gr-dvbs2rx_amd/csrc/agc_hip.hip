@@ -170,7 +170,7 @@ std::string AgcHip::check_args(float rate, float reference, float gain, float ma
 }
 
 AgcHip::AgcHip(float rate, float reference, float gain, float max_gain, int max_streams, int max_samples, int device)
-    : DeviceStage(device), max_streams_(max_streams), max_samples_(max_samples)
+    : StreamStage(max_streams, max_samples, device)
 {
     if (const std::string bad = check_args(rate, reference, gain, max_gain, max_streams, max_samples); !bad.empty()) { err_.argument(bad); return; }
     rate_ = rate; reference_ = reference; gain0_ = gain; max_gain_ = max_gain;

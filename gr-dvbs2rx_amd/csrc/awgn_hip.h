@@ -18,7 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <string>
-#include "device_stage.h"
+#include "stream_stage.h"
 
 namespace dvbs2 {
 
@@ -33,11 +33,9 @@ std::string awgn_sigma(double esn0_db, double es, int sps, float* sigma);
 void awgn_words(uint64_t seed, uint64_t stream_id, int64_t index, uint32_t* wa_wb);
 void awgn_sample(uint64_t seed, uint64_t stream_id, int64_t index, float* re_im);
 
-class AwgnHip : public DeviceStage {
+class AwgnHip : public StreamStage {
 public:
     AwgnHip(uint64_t seed, float sigma, int max_streams, int max_samples, int device);
-    int max_streams() const { return max_streams_; }
-    int max_samples() const { return max_samples_; }
     uint64_t seed() const { return seed_; }
     float sigma() const { return sigma_; }
     int set_sigma(float sigma); // host side: calls made after it
@@ -51,7 +49,6 @@ public:
 private:
     uint64_t seed_;
     float sigma_ = 0;
-    int max_streams_, max_samples_;
 };
 
 } // namespace dvbs2

@@ -86,7 +86,7 @@ __global__ __launch_bounds__(kLanes) void awgn_kernel(const v2f* in, long long i
 } // namespace
 
 AwgnHip::AwgnHip(uint64_t seed, float sigma, int max_streams, int max_samples, int device)
-    : DeviceStage(device), seed_(seed), max_streams_(max_streams), max_samples_(max_samples)
+    : StreamStage(max_streams, max_samples, device), seed_(seed)
 {
     if (const std::string bad = awgn_check(sigma, max_streams, max_samples); !bad.empty()) { err_.argument(bad); return; }
     sigma_ = sigma;

@@ -13,20 +13,6 @@ struct dvbs2_agc {
 
 static_assert(kAgcTile == DVBS2_AGC_TILE, "the header names the kernel's tile");
 
-// the checks the two work entries share; *done: nothing to do
-static int agc_check_call(const dvbs2_agc_t* h, const void* in, int n_samples, int n_streams, const void* out, bool* done)
-{
-    *done = false;
-    if (n_samples < 0) return fail(DVBS2_EINVAL, "n_samples is negative");
-    if (n_streams < 0) return fail(DVBS2_EINVAL, "n_streams is negative");
-    if (n_samples > h->impl->max_samples()) return fail(DVBS2_ESIZE, "n_samples exceeds max_samples");
-    if (n_streams > h->impl->max_streams()) return fail(DVBS2_ESIZE, "n_streams exceeds max_streams");
-    if (n_samples == 0 || n_streams == 0) { *done = true; return DVBS2_OK; }
-    if (!in) return fail(DVBS2_EINVAL, "in is null");
-    if (!out) return fail(DVBS2_EINVAL, "out is null");
-    return DVBS2_OK;
-}
-
 extern "C" {
 
 int dvbs2_agc_check(float rate, float reference, float gain, float max_gain)
@@ -107,9 +93,9 @@ int dvbs2_agc_work_device(dvbs2_agc_t* h, const float* d_in, int64_t in_stride, 
     API_TRY
     NEED_HANDLE(h);
     bool done;
-    if (int rc = agc_check_call(h, d_in, n_samples, n_streams, d_out, &done)) return rc;
+    if (int rc = check_stream_call(h, d_in, n_samples, "n_samples", "max_samples", n_streams, d_out, &done)) return rc;
     if (done) return DVBS2_OK;
-    if (((uintptr_t)d_in | (uintptr_t)d_out) & 7) return fail(DVBS2_EINVAL, "in and out must be 8-byte aligned");
+    if (int rc = check_aligned8(d_in, d_out)) return rc;
     if ((uintptr_t)d_gain & 3) return fail(DVBS2_EINVAL, "gain must be 4-byte aligned");
     if (n_streams > 1 && in_stride < n_samples) return fail(DVBS2_EINVAL, "in_stride is below n_samples");
     if (n_streams > 1 && out_stride < n_samples) return fail(DVBS2_EINVAL, "out_stride is below n_samples");
@@ -124,7 +110,7 @@ int dvbs2_agc_work(dvbs2_agc_t* h, const float* in, int n_samples, float* out, f
     API_TRY
     NEED_HANDLE(h);
     bool done;
-    if (int rc = agc_check_call(h, in, n_samples, 1, out, &done)) return rc;
+    if (int rc = check_stream_call(h, in, n_samples, "n_samples", "max_samples", 1, out, &done)) return rc;
     if (done) return DVBS2_OK;
     HostStage& s = h->stage;
     HostEntry entry(s, h->device);

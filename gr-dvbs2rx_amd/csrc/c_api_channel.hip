@@ -15,14 +15,11 @@ struct dvbs2_awgn {
 
 static_assert(kAwgnTile == DVBS2_AWGN_TILE, "the header names the kernel's tile");
 
-// the checks the two add entries share; *done: nothing to do
+// the checks the two add entries share: first_index stands between the counts and *done (nothing to do); `in` may be null
 static int awgn_check_call(const dvbs2_awgn_t* h, int n_samples, int n_streams, int64_t first_index, const void* out, bool* done)
 {
     *done = false;
-    if (n_samples < 0) return fail(DVBS2_EINVAL, "n_samples is negative");
-    if (n_streams < 0) return fail(DVBS2_EINVAL, "n_streams is negative");
-    if (n_samples > h->impl->max_samples()) return fail(DVBS2_ESIZE, "n_samples exceeds max_samples");
-    if (n_streams > h->impl->max_streams()) return fail(DVBS2_ESIZE, "n_streams exceeds max_streams");
+    if (int rc = check_stream_counts(h, n_samples, "n_samples", "max_samples", n_streams)) return rc;
     if (first_index < 0) return fail(DVBS2_EINVAL, "first_index is negative");
     if (first_index > INT64_MAX - n_samples) return fail(DVBS2_EINVAL, "first_index + n_samples passes 2^63 - 1");
     if (n_samples == 0 || n_streams == 0) { *done = true; return DVBS2_OK; }
@@ -112,7 +109,7 @@ int dvbs2_awgn_add_device(dvbs2_awgn_t* h, const float* d_in, int64_t in_stride,
     bool done;
     if (int rc = awgn_check_call(h, n_samples, n_streams, first_index, d_out, &done)) return rc;
     if (done) return DVBS2_OK;
-    if (((uintptr_t)d_in | (uintptr_t)d_out) & 7) return fail(DVBS2_EINVAL, "in and out must be 8-byte aligned");
+    if (int rc = check_aligned8(d_in, d_out)) return rc;
     if ((uintptr_t)d_sigma & 3) return fail(DVBS2_EINVAL, "sigma must be 4-byte aligned");
     if (n_streams > 1 && d_in && in_stride < n_samples) return fail(DVBS2_EINVAL, "in_stride is below n_samples");
     if (n_streams > 1 && out_stride < n_samples) return fail(DVBS2_EINVAL, "out_stride is below n_samples");

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include <cstdint>
+#include <initializer_list>
 #include <new>
 #include <string>
 #include "device_stage.h"
@@ -106,6 +107,42 @@ template <class H> int check_frames(const H* h, int n_frames, bool buffers_ok, b
     if (n_frames < 0 || (n_frames && !buffers_ok) || also_bad) return fail(DVBS2_EINVAL, "bad argument");
     if (n_frames > h->impl->max_frames()) return fail(DVBS2_ESIZE, "n_frames exceeds max_frames");
     return DVBS2_OK;
+}
+
+// The checks of an entry of a stream stage, the counterpart of check_frames. A count of the call with its cap and their names in the
+// texts: every "<name> is negative" (EINVAL) in list order, then every "<name> exceeds <cap_name>" (ESIZE) in list order.
+struct Count { int n, cap; const char* name; const char* cap_name; };
+inline int check_counts(std::initializer_list<Count> counts)
+{
+    for (const Count& c : counts)
+        if (c.n < 0) return fail(DVBS2_EINVAL, std::string(c.name) + " is negative");
+    for (const Count& c : counts)
+        if (c.n > c.cap) return fail(DVBS2_ESIZE, std::string(c.name) + " exceeds " + c.cap_name);
+    return DVBS2_OK;
+}
+// the two counts most stream entries take, against the handle's capacities (stream_stage.h); the row count has one name everywhere
+template <class H> int check_stream_counts(const H* h, int n, const char* name, const char* cap_name, int n_streams)
+{
+    return check_counts({ { n, h->impl->max_samples(), name, cap_name }, { n_streams, h->impl->max_streams(), "n_streams", "max_streams" } });
+}
+inline int check_in_out(const void* in, const void* out)
+{
+    if (!in) return fail(DVBS2_EINVAL, "in is null");
+    if (!out) return fail(DVBS2_EINVAL, "out is null");
+    return DVBS2_OK;
+}
+inline int check_aligned8(const void* in, const void* out) // (device pointers of complex samples)
+{
+    if (((uintptr_t)in | (uintptr_t)out) & 7) return fail(DVBS2_EINVAL, "in and out must be 8-byte aligned");
+    return DVBS2_OK;
+}
+// An entry with nothing of its own in front of its buffers: the counts, *done (nothing to do: no sample or no row), in and out.
+template <class H> int check_stream_call(const H* h, const void* in, int n, const char* name, const char* cap_name, int n_streams, const void* out, bool* done)
+{
+    *done = false;
+    if (int rc = check_stream_counts(h, n, name, cap_name, n_streams)) return rc;
+    if (n == 0 || n_streams == 0) { *done = true; return DVBS2_OK; }
+    return check_in_out(in, out);
 }
 
 } // namespace dvbs2

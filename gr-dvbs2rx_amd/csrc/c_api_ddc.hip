@@ -21,17 +21,12 @@ static int ddc_check(const dvbs2_ddc_t* h, const void* in, int64_t in_stride, in
 {
     const DdcHip& d = *h->impl;
     *done = false;
-    if (n_in < 0) return fail(DVBS2_EINVAL, "n_in is negative");
-    if (n_inputs < 0) return fail(DVBS2_EINVAL, "n_inputs is negative");
-    if (n_channels < 0) return fail(DVBS2_EINVAL, "n_channels is negative");
-    if (n_in > d.max_samples()) return fail(DVBS2_ESIZE, "n_in exceeds max_samples");
-    if (n_inputs > d.max_inputs()) return fail(DVBS2_ESIZE, "n_inputs exceeds max_inputs");
-    if (n_channels > d.max_channels()) return fail(DVBS2_ESIZE, "n_channels exceeds max_channels");
+    if (int rc = check_counts({ { n_in, d.max_samples(), "n_in", "max_samples" }, { n_inputs, d.max_inputs(), "n_inputs", "max_inputs" },
+                                { n_channels, d.max_channels(), "n_channels", "max_channels" } })) return rc;
     *n_out = d.produce(n_in);
     if (*n_out < 0) return fail(DVBS2_EINVAL, "the sample counter is exhausted");
     if (n_in == 0 || n_channels == 0) { *done = true; return DVBS2_OK; }
-    if (!in) return fail(DVBS2_EINVAL, "in is null");
-    if (!out) return fail(DVBS2_EINVAL, "out is null");
+    if (int rc = check_in_out(in, out)) return rc;
     for (int c = 0; c < n_channels; c++)
         if (d.input_of(c) >= n_inputs) return fail(DVBS2_EINVAL, "channel " + std::to_string(c) + " reads input " + std::to_string(d.input_of(c)) + ", which is not below n_inputs");
     if (n_inputs > 1 && in_stride < n_in) return fail(DVBS2_EINVAL, "in_stride is below n_in");
@@ -134,7 +129,7 @@ int dvbs2_ddc_process_device(dvbs2_ddc_t* h, const float* d_in, int64_t in_strid
     bool done;
     int64_t n_out;
     if (int rc = ddc_check(h, d_in, in_stride, n_in, n_inputs, n_channels, d_out, out_stride, &n_out, &done)) return rc;
-    if (!done && (((uintptr_t)d_in | (uintptr_t)d_out) & 7)) return fail(DVBS2_EINVAL, "in and out must be 8-byte aligned");
+    if (!done && check_aligned8(d_in, d_out)) return DVBS2_EINVAL;
     if (int rc = impl_rc(h, h->impl->process_device(d_in, in_stride, n_in, n_channels, d_out, out_stride, (hipStream_t)stream))) return rc;
     if (n_out_host) *n_out_host = n_out;
     return DVBS2_OK;

@@ -21,10 +21,7 @@ static int iqconv_check_call(const dvbs2_iqconv_t* h, int n_samples, int n_strea
                              const float* floats, const char* floats_name, int64_t float_stride, const uint64_t* stats, bool* done)
 {
     *done = false;
-    if (n_samples < 0) return fail(DVBS2_EINVAL, "n_samples is negative");
-    if (n_streams < 0) return fail(DVBS2_EINVAL, "n_streams is negative");
-    if (n_samples > h->impl->max_samples()) return fail(DVBS2_ESIZE, "n_samples exceeds max_samples");
-    if (n_streams > h->impl->max_streams()) return fail(DVBS2_ESIZE, "n_streams exceeds max_streams");
+    if (int rc = check_stream_counts(h, n_samples, "n_samples", "max_samples", n_streams)) return rc;
     if (n_samples == 0 || n_streams == 0) { *done = true; return DVBS2_OK; }
     const std::string cn = codes_name, fn = floats_name;
     if (!codes) return fail(DVBS2_EINVAL, cn + " is null");

@@ -24,20 +24,6 @@ static int pulse_make(dvbs2_pulse_t** h, int sps, const float* taps, int ntaps, 
     return make_handle(h, device, [&] { return new (std::nothrow) PulseShaperHip(sps, taps, ntaps, max_streams, max_symbols, device); });
 }
 
-// the checks the two shape entries share; *done: nothing to do
-static int pulse_check(const dvbs2_pulse_t* h, const void* in, int n_syms, int n_streams, const void* out, bool* done)
-{
-    *done = false;
-    if (n_syms < 0) return fail(DVBS2_EINVAL, "n_syms is negative");
-    if (n_streams < 0) return fail(DVBS2_EINVAL, "n_streams is negative");
-    if (n_syms > h->impl->max_symbols()) return fail(DVBS2_ESIZE, "n_syms exceeds max_symbols");
-    if (n_streams > h->impl->max_streams()) return fail(DVBS2_ESIZE, "n_streams exceeds max_streams");
-    if (n_syms == 0 || n_streams == 0) { *done = true; return DVBS2_OK; }
-    if (!in) return fail(DVBS2_EINVAL, "in is null");
-    if (!out) return fail(DVBS2_EINVAL, "out is null");
-    return DVBS2_OK;
-}
-
 extern "C" {
 
 int dvbs2_pulse_geometry(int sps, int rrc_delay, int* ntaps, int* history, int* delay)
@@ -107,9 +93,9 @@ int dvbs2_pulse_shape_device(dvbs2_pulse_t* h, const float* d_in, int64_t in_str
     API_TRY
     NEED_HANDLE(h);
     bool done;
-    if (int rc = pulse_check(h, d_in, n_syms, n_streams, d_out, &done)) return rc;
+    if (int rc = check_stream_call(h, d_in, n_syms, "n_syms", "max_symbols", n_streams, d_out, &done)) return rc;
     if (done) return DVBS2_OK;
-    if (((uintptr_t)d_in | (uintptr_t)d_out) & 7) return fail(DVBS2_EINVAL, "in and out must be 8-byte aligned");
+    if (int rc = check_aligned8(d_in, d_out)) return rc;
     if (n_streams > 1 && in_stride < n_syms) return fail(DVBS2_EINVAL, "in_stride is below n_syms");
     if (n_streams > 1 && out_stride < (int64_t)n_syms * h->impl->sps()) return fail(DVBS2_EINVAL, "out_stride is below n_syms * sps");
     return impl_rc(h, h->impl->shape_device(d_in, in_stride, n_syms, n_streams, d_out, out_stride, (hipStream_t)stream));
@@ -122,7 +108,7 @@ int dvbs2_pulse_shape(dvbs2_pulse_t* h, const float* in, int n_syms, float* out)
     API_TRY
     NEED_HANDLE(h);
     bool done;
-    if (int rc = pulse_check(h, in, n_syms, 1, out, &done)) return rc;
+    if (int rc = check_stream_call(h, in, n_syms, "n_syms", "max_symbols", 1, out, &done)) return rc;
     if (done) return DVBS2_OK;
     HostStage& s = h->stage;
     HostEntry entry(s, h->device);

@@ -16,20 +16,6 @@ struct dvbs2_resamp {
 static_assert(kResampTile == DVBS2_RESAMP_TILE, "the header names the kernel's tile");
 static const char* const kResampStepText = "step must lie in [2^26, 2^33]";
 
-// the checks the work entries share; *done: nothing to do (no output, positions unchanged)
-static int resamp_check(const dvbs2_resamp_t* h, const void* in, int n_in, int n_streams, const void* out, bool* done)
-{
-    *done = false;
-    if (n_in < 0) return fail(DVBS2_EINVAL, "n_in is negative");
-    if (n_streams < 0) return fail(DVBS2_EINVAL, "n_streams is negative");
-    if (n_in > h->impl->max_samples()) return fail(DVBS2_ESIZE, "n_in exceeds max_samples");
-    if (n_streams > h->impl->max_streams()) return fail(DVBS2_ESIZE, "n_streams exceeds max_streams");
-    if (n_in == 0 || n_streams == 0) { *done = true; return DVBS2_OK; }
-    if (!in) return fail(DVBS2_EINVAL, "in is null");
-    if (!out) return fail(DVBS2_EINVAL, "out is null");
-    return DVBS2_OK;
-}
-
 extern "C" {
 
 int dvbs2_resamp_step(double rate, uint64_t* step)
@@ -117,10 +103,7 @@ int dvbs2_resamp_params(const dvbs2_resamp_t* h, int* nfilts, int* ntaps, int* t
 int dvbs2_resamp_produce(const dvbs2_resamp_t* h, int n_in, int n_streams, int64_t* n_out)
 {
     NEED_HANDLE(h);
-    if (n_in < 0) return fail(DVBS2_EINVAL, "n_in is negative");
-    if (n_streams < 0) return fail(DVBS2_EINVAL, "n_streams is negative");
-    if (n_in > h->impl->max_samples()) return fail(DVBS2_ESIZE, "n_in exceeds max_samples");
-    if (n_streams > h->impl->max_streams()) return fail(DVBS2_ESIZE, "n_streams exceeds max_streams");
+    if (int rc = check_stream_counts(h, n_in, "n_in", "max_samples", n_streams)) return rc;
     if (n_streams && !n_out) return fail(DVBS2_EINVAL, "n_out is null");
     h->impl->produce(n_in, n_streams, n_out);
     return DVBS2_OK;
@@ -141,12 +124,12 @@ int dvbs2_resamp_process_device(dvbs2_resamp_t* h, const float* d_in, int64_t in
     API_TRY
     NEED_HANDLE(h);
     bool done;
-    if (int rc = resamp_check(h, d_in, n_in, n_streams, d_out, &done)) return rc;
-    if (done) {
+    if (int rc = check_stream_call(h, d_in, n_in, "n_in", "max_samples", n_streams, d_out, &done)) return rc;
+    if (done) { // (no output, positions unchanged)
         for (int s = 0; n_out_host && s < n_streams; s++) n_out_host[s] = 0;
         return DVBS2_OK;
     }
-    if (((uintptr_t)d_in | (uintptr_t)d_out) & 7) return fail(DVBS2_EINVAL, "in and out must be 8-byte aligned");
+    if (int rc = check_aligned8(d_in, d_out)) return rc;
     if (n_streams > 1 && in_stride < n_in) return fail(DVBS2_EINVAL, "in_stride is below n_in");
     if (out_stride < h->impl->produce(n_in, n_streams, nullptr)) return fail(DVBS2_EINVAL, "out_stride is below the call's largest n_out");
     std::vector<int64_t> n_out((size_t)n_streams); // (before the launches: the mirror advances with them)
@@ -165,7 +148,7 @@ int dvbs2_resamp_process(dvbs2_resamp_t* h, const float* in, int n_in, float* ou
     bool done;
     if (n_out) *n_out = 0;
     if (out_cap < 0) return fail(DVBS2_EINVAL, "out_cap is negative");
-    if (int rc = resamp_check(h, in, n_in, 1, out, &done)) return rc;
+    if (int rc = check_stream_call(h, in, n_in, "n_in", "max_samples", 1, out, &done)) return rc;
     if (done) return DVBS2_OK;
     int64_t n;
     h->impl->produce(n_in, 1, &n);

@@ -26,14 +26,10 @@ static int spectrum_check_call(const dvbs2_spectrum_t* h, const void* in, int64_
 {
     const SpectrumHip& s = *h->impl;
     *done = false;
-    if (n_in < 0) return fail(DVBS2_EINVAL, "n_in is negative");
-    if (n_streams < 0) return fail(DVBS2_EINVAL, "n_streams is negative");
-    if (n_in > s.max_samples()) return fail(DVBS2_ESIZE, "n_in exceeds max_samples");
-    if (n_streams > s.max_streams()) return fail(DVBS2_ESIZE, "n_streams exceeds max_streams");
+    if (int rc = check_stream_counts(h, n_in, "n_in", "max_samples", n_streams)) return rc;
     spectrum_geometry(s.nfft(), s.hop(), s.avg(), n_in, nullptr, n_rows, nullptr);
     if (*n_rows == 0 || n_streams == 0) { *done = true; return DVBS2_OK; }
-    if (!in) return fail(DVBS2_EINVAL, "in is null");
-    if (!out) return fail(DVBS2_EINVAL, "out is null");
+    if (int rc = check_in_out(in, out)) return rc;
     if (n_streams > 1 && in_stride < n_in) return fail(DVBS2_EINVAL, "in_stride is below n_in");
     if (out_stride < (int64_t)*n_rows * s.nfft()) return fail(DVBS2_EINVAL, "out_stride is below n_rows nfft");
     return DVBS2_OK;

@@ -27,7 +27,7 @@
 #include <cstdint>
 #include <string>
 #include <vector>
-#include "device_stage.h"
+#include "stream_stage.h"
 
 namespace dvbs2 {
 
@@ -63,7 +63,7 @@ struct DdcMirror {
     }
 };
 
-class DdcHip : public DeviceStage {
+class DdcHip : public StreamStage {
 public:
     DdcHip(int decim, const float* taps, int ntaps, int max_channels, int max_inputs, int max_samples, int device);
     // empty when the arguments are acceptable, else what is wrong with them (no device needed)
@@ -72,9 +72,8 @@ public:
     int ntaps() const { return ntaps_; }
     int history() const { return ntaps_ - 1; }
     int tile() const { return tile_; }
-    int max_channels() const { return max_channels_; }
+    int max_channels() const { return max_streams(); } // the rows of this stage are its channels
     int max_inputs() const { return max_inputs_; }
-    int max_samples() const { return max_samples_; }
     // host only: channel reads input stream `input` and advances by phase_inc radians per input sample from the next call on; the phase
     // is carried over. -1 (an argument error): channel or input out of range, phase_inc not finite
     int set_channel(int channel, int input, double phase_inc);
@@ -94,7 +93,7 @@ public:
     struct Chan { uint64_t inc; int32_t input, reserved; }; // a row of the channel table, on the device as on the host
 
 private:
-    int decim_ = 0, ntaps_ = 0, tile_ = 0, max_channels_, max_inputs_, max_samples_;
+    int decim_ = 0, ntaps_ = 0, tile_ = 0, max_inputs_;
     DdcMirror mirror_;
     std::vector<Chan> table_;
     bool table_dirty_ = true;

@@ -136,9 +136,7 @@ std::string DdcHip::check_args(int decim, const float* taps, int ntaps, int max_
 {
     if (decim < 1 || decim > kDdcMaxDecim) return "decim must be in 1..256";
     if (ntaps < 1 || ntaps > kDdcMaxTaps) return "ntaps must be in 1..4096";
-    if (!taps) return "null taps";
-    for (int i = 0; i < ntaps; i++)
-        if (!std::isfinite(taps[i])) return "taps[" + std::to_string(i) + "] is not finite";
+    if (const std::string bad = check_taps(taps, ntaps, "taps"); !bad.empty()) return bad;
     if (max_channels < 1 || max_channels > 65535) return "max_channels out of range (1..65535)";
     if (max_inputs < 1 || max_inputs > 65535) return "max_inputs out of range (1..65535)";
     if (max_samples < 1 || max_samples > kDdcMaxSamples) return "max_samples out of range (1..2^24)";
@@ -146,23 +144,20 @@ std::string DdcHip::check_args(int decim, const float* taps, int ntaps, int max_
 }
 
 DdcHip::DdcHip(int decim, const float* taps, int ntaps, int max_channels, int max_inputs, int max_samples, int device)
-    : DeviceStage(device), max_channels_(max_channels), max_inputs_(max_inputs), max_samples_(max_samples)
+    : StreamStage(max_channels, max_samples, device), max_inputs_(max_inputs)
 {
     if (const std::string bad = check_args(decim, taps, ntaps, max_channels, max_inputs, max_samples); !bad.empty()) { err_.argument(bad); return; }
     decim_ = decim; ntaps_ = ntaps; tile_ = ddc_tile(decim, ntaps);
-    mirror_.phase.assign((size_t)max_channels_, 0);
-    mirror_.inc.assign((size_t)max_channels_, 0);
-    table_.assign((size_t)max_channels_, Chan{ 0, 0, 0 });
+    mirror_.phase.assign((size_t)max_channels, 0);
+    mirror_.inc.assign((size_t)max_channels, 0);
+    table_.assign((size_t)max_channels, Chan{ 0, 0, 0 });
     DeviceGuard dev_guard(device_);
     if (!dev_guard.ok) { err_.device("hipSetDevice failed"); return; }
-    const size_t H = (size_t)std::max(ntaps_ - 1, 1);
     HIP_OK_AS("hipMalloc of the taps", alloc(&d_taps_, (size_t)ntaps_));
-    HIP_OK_AS("hipMalloc of the histories", alloc(&d_hist_, (size_t)max_channels_ * H));
-    HIP_OK_AS("hipMalloc of the phases", alloc(&d_phase_, (size_t)max_channels_));
-    HIP_OK_AS("hipMalloc of the channel table", alloc(&d_table_, (size_t)max_channels_));
+    HIP_OK_AS("hipMalloc of the histories", alloc_zeroed(&d_hist_, (size_t)max_channels * std::max(ntaps_ - 1, 1)));
+    HIP_OK_AS("hipMalloc of the phases", alloc_zeroed(&d_phase_, (size_t)max_channels));
+    HIP_OK_AS("hipMalloc of the channel table", alloc(&d_table_, (size_t)max_channels));
     HIP_OK(hipMemcpy(d_taps_, taps, (size_t)ntaps_ * sizeof(float), hipMemcpyHostToDevice));
-    HIP_OK(hipMemset(d_hist_, 0, (size_t)max_channels_ * H * sizeof(float2)));
-    HIP_OK(hipMemset(d_phase_, 0, (size_t)max_channels_ * sizeof(unsigned long long)));
     // The largest span is above the 64 KiB a kernel gets unasked. The attribute belongs to the kernel, not to the handle: always the cap
     HIP_OK(hipFuncSetAttribute((const void*)ddc_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kMaxLds * sizeof(float2))));
     HIP_OK(hipFuncSetAttribute((const void*)ddc_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kMaxLds * sizeof(float2))));
@@ -172,7 +167,7 @@ DdcHip::DdcHip(int decim, const float* taps, int ntaps, int max_channels, int ma
 int DdcHip::set_channel(int channel, int input, double phase_inc)
 {
     call_err_ = {};
-    if (channel < 0 || channel >= max_channels_) { call_err_.argument("channel out of range"); return -1; }
+    if (channel < 0 || channel >= max_channels()) { call_err_.argument("channel out of range"); return -1; }
     if (input < 0 || input >= max_inputs_) { call_err_.argument("input out of range"); return -1; }
     if (!std::isfinite(phase_inc)) { call_err_.argument("phase_inc must be finite"); return -1; }
     table_[channel] = Chan{ rotator_inc_turns(phase_inc), input, 0 };
@@ -186,8 +181,8 @@ int DdcHip::reset()
     Entry on(*this);
     if (!on.ok) return -1;
     HIP_RET(hipDeviceSynchronize());
-    HIP_RET(hipMemset(d_hist_, 0, (size_t)max_channels_ * std::max(ntaps_ - 1, 1) * sizeof(float2)));
-    HIP_RET(hipMemset(d_phase_, 0, (size_t)max_channels_ * sizeof(unsigned long long)));
+    HIP_RET(zero(d_hist_));
+    HIP_RET(zero(d_phase_));
     mirror_.counter = 0;
     std::fill(mirror_.phase.begin(), mirror_.phase.end(), 0);
     return 0;
@@ -198,7 +193,7 @@ int DdcHip::state(uint64_t* phases)
     Entry on(*this);
     if (!on.ok) return -1;
     HIP_RET(hipDeviceSynchronize());
-    HIP_RET(hipMemcpy(phases, d_phase_, (size_t)max_channels_ * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIP_RET(hipMemcpy(phases, d_phase_, (size_t)max_channels() * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return 0;
 }
 

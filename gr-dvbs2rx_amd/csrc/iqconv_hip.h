@@ -25,7 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <string>
-#include "device_stage.h"
+#include "stream_stage.h"
 
 namespace dvbs2 {
 
@@ -40,13 +40,11 @@ std::string iqconv_check(int format, float gain, int max_streams, int max_sample
 void iqconv_unpack_host(int format, float gain, const void* in, int64_t n, float* out, uint64_t* stats);
 void iqconv_pack_host(int format, float gain, const float* in, int64_t n, void* out, uint64_t* stats);
 
-class IqconvHip : public DeviceStage {
+class IqconvHip : public StreamStage {
 public:
     IqconvHip(int format, float gain, int max_streams, int max_samples, int device);
     int format() const { return format_; }
     float gain() const { return gain_; }
-    int max_streams() const { return max_streams_; }
-    int max_samples() const { return max_samples_; }
     int set_gain(float gain); // host side: calls made after it
     // DEVICE pointers, strides in complex samples; codes at any byte address (s16: any even one), floats 8-byte aligned, d_stats
     // nullable (n_streams x 3 uint64, added to). One launch, asynchronous on `stream`, no allocation and no synchronisation. The
@@ -59,7 +57,6 @@ public:
 private:
     int format_ = 0;
     float gain_ = 1.0f;
-    int max_streams_, max_samples_;
 };
 
 } // namespace dvbs2

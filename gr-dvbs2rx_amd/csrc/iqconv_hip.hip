@@ -297,7 +297,7 @@ dim3 grid_of(int n_samples, int n_streams, bool wide)
 } // namespace
 
 IqconvHip::IqconvHip(int format, float gain, int max_streams, int max_samples, int device)
-    : DeviceStage(device), max_streams_(max_streams), max_samples_(max_samples)
+    : StreamStage(max_streams, max_samples, device)
 {
     if (const std::string bad = iqconv_check(format, gain, max_streams, max_samples); !bad.empty()) { err_.argument(bad); return; }
     format_ = format;

@@ -20,7 +20,7 @@
 #include <cstdint>
 #include <string>
 #include <vector>
-#include "device_stage.h"
+#include "stream_stage.h"
 
 namespace dvbs2 {
 
@@ -37,7 +37,7 @@ int pulse_taps(int sps, float rolloff, int rrc_delay, double tau, double gain, f
 // rounded once. -1 on a bad argument (no taps, sps < 1, a tap or fullscale that is not finite, taps that are all zero)
 int pulse_scale_taps(float* taps, int ntaps, int sps, double fullscale);
 
-class PulseShaperHip : public DeviceStage {
+class PulseShaperHip : public StreamStage {
 public:
     PulseShaperHip(int sps, const float* taps, int ntaps, int max_streams, int max_symbols, int device);
     // empty when the arguments are acceptable, else what is wrong with them (no device needed)
@@ -45,8 +45,7 @@ public:
     int sps() const { return sps_; }
     int ntaps() const { return ntaps_; }
     int history() const { return history_; }
-    int max_streams() const { return max_streams_; }
-    int max_symbols() const { return max_symbols_; }
+    int max_symbols() const { return max_samples(); } // the name the entry uses: a row of this stage is symbols
     int reset(); // synchronous: waits for the device, then clears every history
     // DEVICE pointers, 8-byte aligned, strides in complex elements; two launches, asynchronous on `stream`. The entry (c_api_pulse.hip)
     // checks the arguments. One call in flight per handle: the histories are read by a call and rewritten behind it, so a second call on
@@ -54,7 +53,7 @@ public:
     int shape_device(const float* d_in, int64_t in_stride, int n_syms, int n_streams, float* d_out, int64_t out_stride, hipStream_t stream);
 
 private:
-    int sps_ = 0, ntaps_ = 0, history_ = 0, max_streams_, max_symbols_;
+    int sps_ = 0, ntaps_ = 0, history_ = 0;
     float* d_taps_ = nullptr;
     float2* d_hist_ = nullptr; // max_streams * history, the oldest symbol first
 };

@@ -135,25 +135,22 @@ std::string PulseShaperHip::check_args(int sps, const float* taps, int ntaps, in
 {
     if (sps < 2 || (sps & 1) || sps > 64) return "sps must be an even integer in 2..64";
     if (ntaps < 1 || (ntaps + sps - 1) / sps > kPulseMaxTerms) return "ntaps must be at least 1 and at most 129 taps per phase (ceil(ntaps / sps) <= 129)";
-    if (!taps) return "null taps";
-    for (int i = 0; i < ntaps; i++)
-        if (!std::isfinite(taps[i])) return "taps[" + std::to_string(i) + "] is not finite";
+    if (const std::string bad = check_taps(taps, ntaps, "taps"); !bad.empty()) return bad;
     if (max_streams < 1 || max_streams > 65535) return "max_streams out of range (1..65535: streams are one launch dimension)";
     if (max_symbols < 1 || max_symbols > (1 << 30)) return "max_symbols out of range (1..2^30)";
     return "";
 }
 
 PulseShaperHip::PulseShaperHip(int sps, const float* taps, int ntaps, int max_streams, int max_symbols, int device)
-    : DeviceStage(device), max_streams_(max_streams), max_symbols_(max_symbols)
+    : StreamStage(max_streams, max_symbols, device)
 {
     if (const std::string bad = check_args(sps, taps, ntaps, max_streams, max_symbols); !bad.empty()) { err_.argument(bad); return; }
     sps_ = sps; ntaps_ = ntaps; history_ = (ntaps + sps - 1) / sps - 1;
     DeviceGuard dev_guard(device_);
     if (!dev_guard.ok) { err_.device("hipSetDevice failed"); return; }
     HIP_OK_AS("hipMalloc of the taps", alloc(&d_taps_, (size_t)ntaps));
-    HIP_OK_AS("hipMalloc of the histories", alloc(&d_hist_, (size_t)max_streams_ * std::max(history_, 1)));
+    HIP_OK_AS("hipMalloc of the histories", alloc_zeroed(&d_hist_, (size_t)max_streams_ * std::max(history_, 1)));
     HIP_OK(hipMemcpy(d_taps_, taps, (size_t)ntaps * sizeof(float), hipMemcpyHostToDevice));
-    HIP_OK(hipMemset(d_hist_, 0, (size_t)max_streams_ * std::max(history_, 1) * sizeof(float2)));
 }
 
 int PulseShaperHip::reset()
@@ -161,7 +158,7 @@ int PulseShaperHip::reset()
     Entry on(*this);
     if (!on.ok) return -1;
     HIP_RET(hipDeviceSynchronize());
-    HIP_RET(hipMemset(d_hist_, 0, (size_t)max_streams_ * std::max(history_, 1) * sizeof(float2)));
+    HIP_RET(zero(d_hist_));
     return 0;
 }
 

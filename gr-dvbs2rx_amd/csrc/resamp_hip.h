@@ -23,7 +23,7 @@
 #include <cstdint>
 #include <string>
 #include <vector>
-#include "device_stage.h"
+#include "stream_stage.h"
 
 namespace dvbs2 {
 
@@ -51,7 +51,7 @@ inline int64_t resamp_advance(uint64_t acc, uint64_t step, int n_in, uint64_t* a
 // outside 0..2^24
 int64_t resamp_max_out(uint64_t step, int n_in);
 
-class ResamplerHip : public DeviceStage {
+class ResamplerHip : public StreamStage {
 public:
     ResamplerHip(int nfilts, const float* taps, int ntaps, double rate, int max_streams, int max_samples, int device);
     // empty when the arguments are acceptable, else what is wrong with them (no device needed)
@@ -60,8 +60,6 @@ public:
     int ntaps() const { return ntaps_; }
     int terms() const { return L_; }
     int history() const { return L_ - 1; }
-    int max_streams() const { return max_streams_; }
-    int max_samples() const { return max_samples_; }
     uint64_t step() const { return step_; }
     // host only: the next call uses it, acc is carried over. -1 (an argument error): step outside [2^26, 2^33]
     int set_step(uint64_t step);
@@ -77,7 +75,7 @@ public:
     int process_device(const float* d_in, int64_t in_stride, int n_in, int n_streams, float* d_out, int64_t out_stride, hipStream_t stream);
 
 private:
-    int nfilts_ = 0, lg_ = 0, ntaps_ = 0, L_ = 0, row_ = 0, bank_elems_ = 0, max_streams_, max_samples_;
+    int nfilts_ = 0, lg_ = 0, ntaps_ = 0, L_ = 0, row_ = 0, bank_elems_ = 0;
     uint64_t step_ = 0;
     std::vector<uint64_t> acc_; // the host's mirror of d_acc_: plain integer arithmetic, advanced at every accepted call
     float2* d_bank_ = nullptr;  // {h, d} per [branch][term], rows of row_ = L | 1 pairs, zeros where a branch has no tap

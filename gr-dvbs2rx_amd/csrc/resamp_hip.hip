@@ -138,9 +138,7 @@ std::string ResamplerHip::check_args(int nfilts, const float* taps, int ntaps, d
     if (nfilts < 2 || nfilts > 256 || (nfilts & (nfilts - 1))) return "nfilts must be a power of two in 2..256";
     if (ntaps < 1 || ntaps > kResampMaxTaps || (ntaps + nfilts - 1) / nfilts > kResampMaxTerms)
         return "ntaps must be in 1..8192 with at most 128 taps per branch (ceil(ntaps / nfilts) <= 128)";
-    if (!taps) return "null taps";
-    for (int i = 0; i < ntaps; i++)
-        if (!std::isfinite(taps[i])) return "taps[" + std::to_string(i) + "] is not finite";
+    if (const std::string bad = check_taps(taps, ntaps, "taps"); !bad.empty()) return bad;
     uint64_t step;
     if (resamp_step(rate, &step)) return "rate must lie in [0.5, 64]";
     if (max_streams < 1 || max_streams > 65535) return "max_streams out of range (1..65535: streams are one launch dimension)";
@@ -149,7 +147,7 @@ std::string ResamplerHip::check_args(int nfilts, const float* taps, int ntaps, d
 }
 
 ResamplerHip::ResamplerHip(int nfilts, const float* taps, int ntaps, double rate, int max_streams, int max_samples, int device)
-    : DeviceStage(device), max_streams_(max_streams), max_samples_(max_samples)
+    : StreamStage(max_streams, max_samples, device)
 {
     if (const std::string bad = check_args(nfilts, taps, ntaps, rate, max_streams, max_samples); !bad.empty()) { err_.argument(bad); return; }
     nfilts_ = nfilts; ntaps_ = ntaps; L_ = (ntaps + nfilts - 1) / nfilts;
@@ -167,13 +165,10 @@ ResamplerHip::ResamplerHip(int nfilts, const float* taps, int ntaps, double rate
     acc_.assign((size_t)max_streams_, 0);
     DeviceGuard dev_guard(device_);
     if (!dev_guard.ok) { err_.device("hipSetDevice failed"); return; }
-    const size_t H = (size_t)std::max(L_ - 1, 1);
     HIP_OK_AS("hipMalloc of the bank", alloc(&d_bank_, (size_t)bank_elems_));
-    HIP_OK_AS("hipMalloc of the histories", alloc(&d_hist_, (size_t)max_streams_ * H));
-    HIP_OK_AS("hipMalloc of the positions", alloc(&d_acc_, (size_t)max_streams_));
+    HIP_OK_AS("hipMalloc of the histories", alloc_zeroed(&d_hist_, (size_t)max_streams_ * std::max(L_ - 1, 1)));
+    HIP_OK_AS("hipMalloc of the positions", alloc_zeroed(&d_acc_, (size_t)max_streams_));
     HIP_OK(hipMemcpy(d_bank_, bank.data(), bank.size() * sizeof(float2), hipMemcpyHostToDevice));
-    HIP_OK(hipMemset(d_hist_, 0, (size_t)max_streams_ * H * sizeof(float2)));
-    HIP_OK(hipMemset(d_acc_, 0, (size_t)max_streams_ * sizeof(unsigned long long)));
     // The largest bank is above the 64 KiB a kernel gets unasked. The attribute belongs to the kernel, not to the handle: always the cap
     HIP_OK(hipFuncSetAttribute((const void*)resamp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((kSpan + kMaxBank) * sizeof(float2))));
 }
@@ -202,7 +197,7 @@ int ResamplerHip::reset()
     if (reset_phase(nullptr)) return -1; // (waits for the device)
     Entry on(*this);
     if (!on.ok) return -1;
-    HIP_RET(hipMemset(d_hist_, 0, (size_t)max_streams_ * std::max(L_ - 1, 1) * sizeof(float2)));
+    HIP_RET(zero(d_hist_));
     return 0;
 }
 

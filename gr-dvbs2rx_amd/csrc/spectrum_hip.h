@@ -30,7 +30,7 @@
 #include <cstdint>
 #include <string>
 #include <vector>
-#include "device_stage.h"
+#include "stream_stage.h"
 
 namespace dvbs2 {
 
@@ -59,7 +59,7 @@ std::string spectrum_carriers_check(const float* psd, int nfft, const SpectrumCa
 // all carriers found, sorted by centre (arguments as checked above)
 std::vector<SpectrumCarrier> spectrum_carriers(const float* psd, int nfft, bool shifted, const SpectrumCarrierParams& p);
 
-class SpectrumHip : public DeviceStage {
+class SpectrumHip : public StreamStage {
 public:
     // window: nfft floats, or null for the periodic Hann window
     SpectrumHip(int nfft, int hop, int avg, const float* window, int shifted, int max_streams, int max_samples, int device);
@@ -69,8 +69,6 @@ public:
     int hop() const { return hop_; }
     int avg() const { return avg_; }
     int shifted() const { return shifted_; }
-    int max_streams() const { return max_streams_; }
-    int max_samples() const { return max_samples_; }
     double window_power() const { return window_power_; }
     // DEVICE pointers, d_in 8-byte and d_out 4-byte aligned, in_stride in complex elements, out_stride in floats: stream i reads n_in
     // samples at d_in + i in_stride and writes n_rows rows of nfft floats at d_out + i out_stride. Two launches at most, asynchronous
@@ -79,7 +77,7 @@ public:
     int process_device(const float* d_in, int64_t in_stride, int n_in, int n_streams, float* d_out, int64_t out_stride, hipStream_t stream);
 
 private:
-    int nfft_ = 0, log2_ = 0, hop_ = 0, avg_ = 0, shifted_ = 0, max_streams_, max_samples_;
+    int nfft_ = 0, log2_ = 0, hop_ = 0, avg_ = 0, shifted_ = 0;
     double window_power_ = 0.0;
     size_t scratch_floats_ = 0;
     float* d_window_ = nullptr;

@@ -267,12 +267,8 @@ std::string SpectrumHip::check_args(int nfft, int hop, int avg, const float* win
     if (hop < 1 || hop > kSpectrumMaxHop) return "hop must be in 1..2^24";
     if (avg < 0) return "avg is negative";
     if (window) {
-        bool any = false;
-        for (int n = 0; n < nfft; n++) {
-            if (!std::isfinite(window[n])) return "window[" + std::to_string(n) + "] is not finite";
-            any |= window[n] != 0.0f;
-        }
-        if (!any) return "the window is all zero";
+        if (const std::string bad = check_taps(window, nfft, "window"); !bad.empty()) return bad;
+        if (std::all_of(window, window + nfft, [](float w) { return w == 0.0f; })) return "the window is all zero";
     }
     if (max_streams < 1 || max_streams > 65535) return "max_streams out of range (1..65535)";
     if (max_samples < 1 || max_samples > kSpectrumMaxSamples) return "max_samples out of range (1..2^24)";
@@ -280,7 +276,7 @@ std::string SpectrumHip::check_args(int nfft, int hop, int avg, const float* win
 }
 
 SpectrumHip::SpectrumHip(int nfft, int hop, int avg, const float* window, int shifted, int max_streams, int max_samples, int device)
-    : DeviceStage(device), max_streams_(max_streams), max_samples_(max_samples)
+    : StreamStage(max_streams, max_samples, device)
 {
     if (const std::string bad = check_args(nfft, hop, avg, window, max_streams, max_samples); !bad.empty()) { err_.argument(bad); return; }
     nfft_ = nfft; log2_ = spectrum_log2(nfft); hop_ = hop; avg_ = avg; shifted_ = shifted ? 1 : 0;

@@ -29,7 +29,7 @@
 #include <cstdint>
 #include <string>
 #include <vector>
-#include "device_stage.h"
+#include "stream_stage.h"
 
 namespace dvbs2 {
 
@@ -59,7 +59,7 @@ int symsync_geometry(int sps, int rrc_delay, int n_subfilt, int interp, int* sub
 // n_subfilt * subfilt_len floats, [subfilter][tap], each subfilter flipped (:82-110); -1 on a bad argument
 int symsync_taps(int sps, float rolloff, int rrc_delay, int n_subfilt, float* bank);
 
-class SymSyncHip : public DeviceStage {
+class SymSyncHip : public StreamStage {
 public:
     // bank: n_subfilt * subfilt_len floats as symsync_taps lays them out, or null to design them here
     SymSyncHip(int sps, float loop_bw, float damping, float rolloff, int rrc_delay, int n_subfilt, int interp, const float* bank,
@@ -69,8 +69,6 @@ public:
                                   int max_samples);
     const SymSyncGeom& geom() const { return g_; }
     float Kp() const { return Kp_; }
-    int max_streams() const { return max_streams_; }
-    int max_samples() const { return max_samples_; }
     int reset();
     // DEVICE pointers except n_in (host, one count per stream). Stream s reads d_in + s * in_stride samples and writes
     // d_out / d_strobe_idx / d_mu + s * out_stride, at most max_out of each
@@ -85,7 +83,6 @@ public:
 private:
     SymSyncGeom g_{};
     float Kp_ = 0.0f;
-    int max_streams_, max_samples_;
     int last_streams_ = 0;
     hipStream_t last_stream_ = nullptr;
     float* d_bank_ = nullptr;

@@ -238,7 +238,7 @@ std::string SymSyncHip::check_args(int sps, float loop_bw, float damping, float 
 
 SymSyncHip::SymSyncHip(int sps, float loop_bw, float damping, float rolloff, int rrc_delay, int n_subfilt, int interp, const float* bank,
                        int max_streams, int max_samples, int device)
-    : DeviceStage(device), max_streams_(max_streams), max_samples_(max_samples)
+    : StreamStage(max_streams, max_samples, device)
 {
     if (const std::string bad = check_args(sps, loop_bw, damping, rolloff, rrc_delay, n_subfilt, interp, max_streams, max_samples); !bad.empty()) { err_.argument(bad); return; }
     int L, D, H;
@@ -250,8 +250,8 @@ SymSyncHip::SymSyncHip(int sps, float loop_bw, float damping, float rolloff, int
     if (bank) memcpy(taps.data(), bank, bank_bytes);
     else symsync_taps(sps, rolloff, rrc_delay, n_subfilt, taps.data());
     DeviceGuard dev_guard(device_);
-    if (!dev_guard.ok || alloc(&d_bank_, taps.size()) != hipSuccess || alloc(&d_hist_, (size_t)max_streams_ * 2 * H) != hipSuccess ||
-        alloc(&d_state_, max_streams_) != hipSuccess || alloc(&d_res_, max_streams_) != hipSuccess || alloc(&d_nin_, max_streams_) != hipSuccess ||
+    if (!dev_guard.ok || alloc(&d_bank_, taps.size()) != hipSuccess || alloc_zeroed(&d_hist_, (size_t)max_streams_ * 2 * H) != hipSuccess ||
+        alloc(&d_state_, max_streams_) != hipSuccess || alloc_zeroed(&d_res_, max_streams_) != hipSuccess || alloc(&d_nin_, max_streams_) != hipSuccess ||
         hipMemcpy(d_bank_, taps.data(), bank_bytes, hipMemcpyHostToDevice) != hipSuccess) {
         err_.argument("device setup failed"); return; // (device failure, kArgument: notes/stage_error_codes.md)
     }
@@ -269,8 +269,7 @@ int SymSyncHip::reset()
     std::vector<SymSyncState> all(max_streams_, s0);
     if (!on.ok || hipDeviceSynchronize() != hipSuccess ||
         hipMemcpy(d_state_, all.data(), all.size() * sizeof(SymSyncState), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemset(d_hist_, 0, (size_t)max_streams_ * 2 * g_.history * sizeof(float2)) != hipSuccess || // the history starts as zeros
-        hipMemset(d_res_, 0, (size_t)max_streams_ * sizeof(SymSyncResult)) != hipSuccess) {
+        zero(d_hist_) != hipSuccess || zero(d_res_) != hipSuccess) { // the history starts as zeros
         call_err_.device("reset of the device state failed"); return -1;
     }
     last_streams_ = 0;

@@ -36,6 +36,30 @@ def _ints(k, entry, *args):
     return tuple(x.value for x in v)
 
 
+def _ptr(a):
+    """The address of an array's data; None for an empty array or for None."""
+    return a.ctypes.data if a is not None and a.size else None
+
+
+def _f32_vector(x):
+    """(array, pointer, size) of x as a C-contiguous float32 vector: taps and windows. Keep the array while the pointer is in use."""
+    v = np.ascontiguousarray(x, np.float32).reshape(-1)
+    return v, _ptr(v), int(v.size)
+
+
+def _complex64(x, name, rows=None):
+    """x as a C-contiguous complex64 vector. rows names the matrix form ("[n_inputs, n_in]") where the stage takes one: a vector is then
+    one row of it."""
+    x = np.asarray(x)
+    if x.dtype != np.complex64:
+        raise TypeError(f"{name} must be complex64, not {x.dtype}")
+    if rows and x.ndim == 1:
+        x = x.reshape(1, -1)
+    if x.ndim != (2 if rows else 1) or not x.flags.c_contiguous:
+        raise ValueError(f"{name} must be a C-contiguous vector" + (f" or {rows} matrix" if rows else ""))
+    return x
+
+
 class _Handle:
     """One C handle: self._h is there (null) before a subclass's constructor runs and creates it; the subclass names the destroy entry.
     close() may be called again, and runs when the object is dropped."""
@@ -403,7 +427,7 @@ class PlFrontEnd(_Handle):
         if lst.size and (lst.dtype.kind not in "iu" or lst.min() < 0 or lst.max() > 255):
             raise ValueError("expected_pls: integers in 0..127")
         lst = np.ascontiguousarray(lst, np.uint8)
-        check(lib.dvbs2_plframe_set_expected_pls(self._h, lst.ctypes.data if lst.size else None, int(lst.size)))
+        check(lib.dvbs2_plframe_set_expected_pls(self._h, _ptr(lst), int(lst.size)))
 
     def _inputs(self, plframes, coarse_corrected, coarse_foffset, trailing_header):
         x = np.asarray(plframes)
@@ -437,7 +461,7 @@ class PlFrontEnd(_Handle):
 
     def _est_arrays(self, nf):
         arrs = {k: np.empty((nf, self.n_pilots) if k == "pilot_phase" else (nf,), dt) for k, dt in self.EST}
-        e = capi.PlFrameEstimates(**{k: (a.ctypes.data if a.size else None) for k, a in arrs.items()})
+        e = capi.PlFrameEstimates(**{k: _ptr(a) for k, a in arrs.items()})
         return arrs, e
 
     def estimate(self, plframes, coarse_corrected, coarse_foffset=None, trailing_header=None):
@@ -500,7 +524,7 @@ class PlSync(_Handle):
         if lst.size and (lst.dtype.kind not in "iu" or lst.min() < 0 or lst.max() > 127):
             raise ValueError("expected_pls: integers in 0..127")
         lst = np.ascontiguousarray(lst, np.uint8)
-        check(lib.dvbs2_plsync_set_expected_pls(self._h, lst.ctypes.data if lst.size else None, int(lst.size)))
+        check(lib.dvbs2_plsync_set_expected_pls(self._h, _ptr(lst), int(lst.size)))
 
     def metric_device(self, d_syms, n_syms, d_metric, stream=0):
         """DEVICE addresses; the timing metric of every index with the handle's history. Does not advance the handle."""
@@ -516,15 +540,11 @@ class PlSync(_Handle):
 
     def work(self, syms):
         """HOST buffer of complex64 symbols. Returns (frames as a FRAME_DTYPE array, consumed, state)."""
-        x = np.asarray(syms)
-        if x.dtype != np.complex64:
-            raise TypeError(f"syms must be complex64, not {x.dtype}")
-        if x.ndim != 1 or not x.flags.c_contiguous:
-            raise ValueError("syms must be a C-contiguous vector")
+        x = _complex64(syms, "syms")
         if x.size > self.max_symbols:
             raise ValueError(f"{x.size} symbols exceed max_symbols = {self.max_symbols}")
         frames = np.zeros(self.max_frames, self.FRAME_DTYPE)
-        nf, consumed, state = _ints(3, lib.dvbs2_plsync_search, self._h, x.ctypes.data if x.size else None, int(x.size), frames.ctypes.data)
+        nf, consumed, state = _ints(3, lib.dvbs2_plsync_search, self._h, _ptr(x), int(x.size), frames.ctypes.data)
         return frames[:nf].copy(), consumed, state
 
     def gather_device(self, d_syms, d_frames, n_frames, wanted_plsc, d_plframes, d_count, stream=0):
@@ -590,7 +610,7 @@ class PlCoarse(_Handle):
         elif self.plsc < 0:
             raise ValueError("a PlCoarse without a fixed PLSC needs plsc per frame")
         fo, cc, ne = np.zeros(nf, np.float32), np.zeros(nf, np.int32), np.zeros(nf, np.int32)
-        check(lib.dvbs2_plcoarse_estimate(self._h, x.ctypes.data if nf else None, int(x.shape[1]), p.ctypes.data if p is not None and nf else None,
+        check(lib.dvbs2_plcoarse_estimate(self._h, _ptr(x), int(x.shape[1]), p.ctypes.data if p is not None and nf else None,
                                           nf, fo.ctypes.data, cc.ctypes.data, ne.ctypes.data))
         return dict(coarse_foffset=fo, coarse_corrected=cc, new_est=ne)
 
@@ -651,19 +671,14 @@ class Agc(_Handle):
     def state(self, n_streams=None):
         """The gains of streams 0 .. n_streams - 1 (default: all) as float32; waits for the device."""
         g = np.zeros(self.max_streams if n_streams is None else int(n_streams), np.float32)
-        check(lib.dvbs2_agc_state(self._h, g.ctypes.data if g.size else None, int(g.size)))
+        check(lib.dvbs2_agc_state(self._h, _ptr(g), int(g.size)))
         return g
 
     def work(self, samples):
         """HOST buffer of complex64 samples of stream 0. Returns (out complex64, gain float32: what multiplied each sample)."""
-        x = np.asarray(samples)
-        if x.dtype != np.complex64:
-            raise TypeError(f"samples must be complex64, not {x.dtype}")
-        if x.ndim != 1 or not x.flags.c_contiguous:
-            raise ValueError("samples must be a C-contiguous vector")
+        x = _complex64(samples, "samples")
         out, gain = np.empty_like(x), np.empty(x.size, np.float32)
-        check(lib.dvbs2_agc_work(self._h, x.ctypes.data if x.size else None, int(x.size), out.ctypes.data if x.size else None,
-                                 gain.ctypes.data if x.size else None))
+        check(lib.dvbs2_agc_work(self._h, _ptr(x), int(x.size), _ptr(out), _ptr(gain)))
         return out, gain
 
     def work_device(self, d_in, in_stride, n_samples, n_streams, d_out, out_stride, d_gain=0, gain_stride=0, stream=0):
@@ -739,16 +754,11 @@ class Awgn(_Handle):
         if isinstance(samples, (int, np.integer)):
             x, n = None, int(samples)
         else:
-            x = np.asarray(samples)
-            if x.dtype != np.complex64:
-                raise TypeError(f"samples must be complex64, not {x.dtype}")
-            if x.ndim != 1 or not x.flags.c_contiguous:
-                raise ValueError("samples must be a C-contiguous vector")
+            x = _complex64(samples, "samples")
             n = x.size
         out = np.empty(max(n, 0), np.complex64)
         first = self.position if first_index is None else int(first_index)
-        check(lib.dvbs2_awgn_add(self._h, x.ctypes.data if x is not None and n else None, n, int(stream_id) & _U64, first,
-                                 out.ctypes.data if n > 0 else None))
+        check(lib.dvbs2_awgn_add(self._h, _ptr(x), n, int(stream_id) & _U64, first, _ptr(out)))
         if first_index is None:
             self.position += n
         return out
@@ -805,8 +815,7 @@ def iqconv_unpack_host(fmt, gain, codes, stats=False):
     c = _iq_codes(f, codes)
     out = np.empty(c.size // 2, np.complex64)
     words = np.zeros(3, np.uint64)
-    check(lib.dvbs2_iqconv_unpack_host(f, float(gain), c.ctypes.data if c.size else None, c.size // 2, out.ctypes.data if c.size else None,
-                                       words.ctypes.data if stats else None))
+    check(lib.dvbs2_iqconv_unpack_host(f, float(gain), _ptr(c), c.size // 2, _ptr(out), words.ctypes.data if stats else None))
     return (out, _iq_stats(words)) if stats else out
 
 
@@ -817,8 +826,7 @@ def iqconv_pack_host(fmt, gain, samples, stats=False):
     x = np.ascontiguousarray(samples, np.complex64).reshape(-1)
     out = np.empty((x.size, 2), _IQ_DTYPES[f])
     words = np.zeros(3, np.uint64)
-    check(lib.dvbs2_iqconv_pack_host(f, float(gain), x.ctypes.data if x.size else None, x.size, out.ctypes.data if x.size else None,
-                                     words.ctypes.data if stats else None))
+    check(lib.dvbs2_iqconv_pack_host(f, float(gain), _ptr(x), x.size, _ptr(out), words.ctypes.data if stats else None))
     return (out, _iq_stats(words)) if stats else out
 
 
@@ -866,7 +874,7 @@ class IqConverter(_Handle):
         the host link. With stats, returns dict(samples, clipped, energy)."""
         c = _iq_codes(self.format, codes)
         words = np.zeros(3, np.uint64)
-        check(lib.dvbs2_iqconv_unpack_to_device(self._h, c.ctypes.data if c.size else None, c.size // 2, d_out or None,
+        check(lib.dvbs2_iqconv_unpack_to_device(self._h, _ptr(c), c.size // 2, d_out or None,
                                                 words.ctypes.data if stats else None))
         return _iq_stats(words) if stats else None
 
@@ -874,7 +882,7 @@ class IqConverter(_Handle):
         """n_samples complex64 at the DEVICE address d_in to HOST codes [n_samples, 2]; synchronous. With stats, also the dict."""
         out = np.empty((max(int(n_samples), 0), 2), self.dtype)
         words = np.zeros(3, np.uint64)
-        check(lib.dvbs2_iqconv_pack_from_device(self._h, d_in or None, int(n_samples), out.ctypes.data if out.size else None,
+        check(lib.dvbs2_iqconv_pack_from_device(self._h, d_in or None, int(n_samples), _ptr(out),
                                                 words.ctypes.data if stats else None))
         return (out, _iq_stats(words)) if stats else out
 
@@ -910,13 +918,9 @@ class Rotator(_Handle):
 
     def work(self, syms):
         """HOST buffer of complex64 symbols; returns the rotated copy."""
-        x = np.asarray(syms)
-        if x.dtype != np.complex64:
-            raise TypeError(f"syms must be complex64, not {x.dtype}")
-        if x.ndim != 1 or not x.flags.c_contiguous:
-            raise ValueError("syms must be a C-contiguous vector")
+        x = _complex64(syms, "syms")
         out = np.empty_like(x)
-        check(lib.dvbs2_rotator_rotate(self._h, x.ctypes.data if x.size else None, int(x.size), out.ctypes.data if x.size else None))
+        check(lib.dvbs2_rotator_rotate(self._h, _ptr(x), int(x.size), _ptr(out)))
         return out
 
     def work_device(self, d_in, n_syms, d_out, stream=0):
@@ -999,16 +1003,12 @@ class SymbolSync(_Handle):
 
     def work(self, samples, max_out=None):
         """HOST buffer of complex64 samples of stream 0. Returns (symbols, strobe_idx int64, mu float64, consumed, status)."""
-        x = np.asarray(samples)
-        if x.dtype != np.complex64:
-            raise TypeError(f"samples must be complex64, not {x.dtype}")
-        if x.ndim != 1 or not x.flags.c_contiguous:
-            raise ValueError("samples must be a C-contiguous vector")
+        x = _complex64(samples, "samples")
         if x.size > self.max_samples:
             raise ValueError(f"{x.size} samples exceed max_samples = {self.max_samples}")
         cap = x.size if max_out is None else int(max_out)
         out, idx, mu = np.zeros(cap, np.complex64), np.zeros(cap, np.int64), np.zeros(cap, np.float64)
-        k, consumed, status = _ints(3, lib.dvbs2_symsync_work, self._h, x.ctypes.data if x.size else None, int(x.size),
+        k, consumed, status = _ints(3, lib.dvbs2_symsync_work, self._h, _ptr(x), int(x.size),
                                     out.ctypes.data if cap else None, cap, idx.ctypes.data, mu.ctypes.data)
         return out[:k].copy(), idx[:k].copy(), mu[:k].copy(), consumed, status
 
@@ -1069,7 +1069,7 @@ def bbheader_build(matype1=0xF2, matype2=0, upl_bits=188 * 8, dfl_bits=0, sync=0
 def crc8(data):
     """The CRC-8 check byte of DVB-S2 mode adaptation over a bytes-like (host only)."""
     d = np.frombuffer(bytes(data), np.uint8)
-    return check(lib.dvbs2_crc8(d.ctypes.data if d.size else None, d.size))
+    return check(lib.dvbs2_crc8(_ptr(d), d.size))
 
 
 class BbFramer(_Handle):
@@ -1100,8 +1100,7 @@ class BbFramer(_Handle):
         assert t.size >= 188 * self.need(n_frames, dfl_bytes)
         out = np.empty((max(n_frames, 0), self.kbch_bytes), np.uint8)
         n = C.c_int()
-        check(lib.dvbs2_bbframer_process(self._h, t.ctypes.data if t.size else None, n_frames, dfl_bytes,
-                                         out.ctypes.data if out.size else None, C.byref(n)))
+        check(lib.dvbs2_bbframer_process(self._h, _ptr(t), n_frames, dfl_bytes, _ptr(out), C.byref(n)))
         self.packets_read = n.value
         return out
 
@@ -1309,7 +1308,7 @@ def plframer_layout(plscs):
     a = _plsc_array(plscs)
     ino, outo = np.zeros(a.size, np.int64), np.zeros(a.size, np.int64)
     tin, tout = C.c_int64(), C.c_int64()
-    check(lib.dvbs2_plframer_layout(a.ctypes.data if a.size else None, int(a.size), ino.ctypes.data, outo.ctypes.data, C.byref(tin), C.byref(tout)))
+    check(lib.dvbs2_plframer_layout(_ptr(a), int(a.size), ino.ctypes.data, outo.ctypes.data, C.byref(tin), C.byref(tout)))
     return dict(in_offset=ino, out_offset=outo, in_syms=tin.value, out_syms=tout.value)
 
 
@@ -1331,7 +1330,7 @@ class PlFramer(_Handle):
     def set_sequence(self, plscs):
         """The PLSCs of the frames of one call, in stream order. Not while work of the handle is in flight."""
         a = _plsc_array(plscs)
-        check(lib.dvbs2_plframer_set_sequence(self._h, a.ctypes.data if a.size else None, int(a.size)))
+        check(lib.dvbs2_plframer_set_sequence(self._h, _ptr(a), int(a.size)))
         self.plscs = a
         self._params()
 
@@ -1348,7 +1347,7 @@ class PlFramer(_Handle):
         if not x.flags.c_contiguous or x.size != lay["in_syms"]:
             raise ValueError(f"xfecframes: expected {lay['in_syms']} C-contiguous symbols, got shape {x.shape}")
         out = np.empty(lay["out_syms"] + (90 if closing_plsc >= 0 and nf else 0), np.complex64)
-        check(lib.dvbs2_plframer_frame(self._h, x.ctypes.data if x.size else None, nf, int(closing_plsc), out.ctypes.data if out.size else None))
+        check(lib.dvbs2_plframer_frame(self._h, _ptr(x), nf, int(closing_plsc), _ptr(out)))
         return out
 
     def work_device(self, d_xfecframes, n_frames, closing_plsc, d_plframes, stream=0):
@@ -1373,7 +1372,7 @@ def pulse_scale_taps(taps, sps, fullscale=1.0):
     """A float32 copy of `taps` scaled by the rule of the reference's scale_rrc_taps (apps/dvbs2-tx:39-81): I and Q of the shaped
     samples of unit-magnitude symbols stay within +-fullscale. Host only."""
     t = np.array(taps, np.float32).reshape(-1)
-    check(lib.dvbs2_pulse_scale_taps(t.ctypes.data if t.size else None, int(t.size), int(sps), float(fullscale)))
+    check(lib.dvbs2_pulse_scale_taps(_ptr(t), int(t.size), int(sps), float(fullscale)))
     return t
 
 
@@ -1390,9 +1389,8 @@ class PulseShaper(_Handle):
         if taps is None:
             check(lib.dvbs2_pulse_create(C.byref(self._h), int(sps), float(rolloff), int(rrc_delay), int(max_streams), int(max_symbols), device))
         else:
-            t = np.ascontiguousarray(taps, np.float32).reshape(-1)
-            check(lib.dvbs2_pulse_create_taps(C.byref(self._h), int(sps), t.ctypes.data if t.size else None, int(t.size), int(max_streams),
-                                              int(max_symbols), device))
+            t, t_ptr, ntaps = _f32_vector(taps)
+            check(lib.dvbs2_pulse_create_taps(C.byref(self._h), int(sps), t_ptr, ntaps, int(max_streams), int(max_symbols), device))
         self.max_streams, self.max_symbols = max_streams, max_symbols
         self.sps, self.ntaps, self.history, self.delay = _ints(4, lib.dvbs2_pulse_params, self._h)
 
@@ -1401,13 +1399,9 @@ class PulseShaper(_Handle):
 
     def work(self, syms):
         """HOST buffer of complex64 symbols of stream 0; returns the syms.size * sps complex64 samples."""
-        x = np.asarray(syms)
-        if x.dtype != np.complex64:
-            raise TypeError(f"syms must be complex64, not {x.dtype}")
-        if x.ndim != 1 or not x.flags.c_contiguous:
-            raise ValueError("syms must be a C-contiguous vector")
+        x = _complex64(syms, "syms")
         out = np.empty(x.size * self.sps, np.complex64)
-        check(lib.dvbs2_pulse_shape(self._h, x.ctypes.data if x.size else None, int(x.size), out.ctypes.data if x.size else None))
+        check(lib.dvbs2_pulse_shape(self._h, _ptr(x), int(x.size), _ptr(out)))
         return out
 
     def work_device(self, d_in, in_stride, n_syms, n_streams, d_out, out_stride, stream=0):
@@ -1440,8 +1434,8 @@ def resamp_max_out(step, n_in):
 
 def resamp_check(nfilts, taps, rate, max_streams=1, max_samples=1 << 20):
     """Raises what Resampler(...) would raise for these arguments, without a device (dvbs2_resamp_check)."""
-    t = np.ascontiguousarray(taps, np.float32).reshape(-1)
-    check(lib.dvbs2_resamp_check(int(nfilts), t.ctypes.data if t.size else None, int(t.size), float(rate), int(max_streams), int(max_samples)))
+    t, t_ptr, ntaps = _f32_vector(taps)
+    check(lib.dvbs2_resamp_check(int(nfilts), t_ptr, ntaps, float(rate), int(max_streams), int(max_samples)))
 
 
 class Resampler(_Handle):
@@ -1454,9 +1448,8 @@ class Resampler(_Handle):
     TILE = capi.RESAMP_TILE
 
     def __init__(self, nfilts, taps, rate, max_streams=1, max_samples=1 << 20, device=0):
-        t = np.ascontiguousarray(taps, np.float32).reshape(-1)
-        check(lib.dvbs2_resamp_create(C.byref(self._h), int(nfilts), t.ctypes.data if t.size else None, int(t.size), float(rate),
-                                      int(max_streams), int(max_samples), device))
+        t, t_ptr, ntaps = _f32_vector(taps)
+        check(lib.dvbs2_resamp_create(C.byref(self._h), int(nfilts), t_ptr, ntaps, float(rate), int(max_streams), int(max_samples), device))
         self.max_streams, self.max_samples = max_streams, max_samples
         self.nfilts, self.ntaps, self.terms, self.history, self.delay_num = _ints(5, lambda *a: lib.dvbs2_resamp_params(*a, None), self._h)
 
@@ -1489,7 +1482,7 @@ class Resampler(_Handle):
     def produce(self, n_in, n_streams=1):
         """int64 [n_streams]: what the next call of n_in samples writes per stream. From the host's mirror: no synchronisation."""
         n = np.zeros(int(n_streams), np.int64)
-        check(lib.dvbs2_resamp_produce(self._h, int(n_in), int(n_streams), n.ctypes.data if n.size else None))
+        check(lib.dvbs2_resamp_produce(self._h, int(n_in), int(n_streams), _ptr(n)))
         return n
 
     def state(self):
@@ -1500,14 +1493,10 @@ class Resampler(_Handle):
 
     def work(self, samples):
         """HOST buffer of complex64 samples of stream 0; returns the produce(samples.size)[0] complex64 samples."""
-        x = np.asarray(samples)
-        if x.dtype != np.complex64:
-            raise TypeError(f"samples must be complex64, not {x.dtype}")
-        if x.ndim != 1 or not x.flags.c_contiguous:
-            raise ValueError("samples must be a C-contiguous vector")
+        x = _complex64(samples, "samples")
         out = np.empty(max(int(self.produce(x.size)[0]), 1), np.complex64)
         n = C.c_int64()
-        check(lib.dvbs2_resamp_process(self._h, x.ctypes.data if x.size else None, int(x.size), out.ctypes.data, int(out.size), C.byref(n)))
+        check(lib.dvbs2_resamp_process(self._h, _ptr(x), int(x.size), out.ctypes.data, int(out.size), C.byref(n)))
         return out[:n.value]
 
     def work_device(self, d_in, in_stride, n_in, n_streams, d_out, out_stride, stream=0):
@@ -1516,7 +1505,7 @@ class Resampler(_Handle):
         int64 [n_streams] (what produce() said before the call). One call in flight per handle."""
         n = np.zeros(int(n_streams), np.int64)
         check(lib.dvbs2_resamp_process_device(self._h, d_in or None, int(in_stride), int(n_in), int(n_streams), d_out or None, int(out_stride),
-                                              n.ctypes.data if n.size else None, stream or None))
+                                              _ptr(n), stream or None))
         return n
 
 
@@ -1535,8 +1524,8 @@ def ddc_produce(position, decim, n_in):
 
 def ddc_check(decim, taps, max_channels=1, max_inputs=1, max_samples=1 << 20):
     """Raises what Ddc(...) would raise for these arguments, without a device (dvbs2_ddc_check)."""
-    t = np.ascontiguousarray(taps, np.float32).reshape(-1)
-    check(lib.dvbs2_ddc_check(int(decim), t.ctypes.data if t.size else None, int(t.size), int(max_channels), int(max_inputs), int(max_samples)))
+    t, t_ptr, ntaps = _f32_vector(taps)
+    check(lib.dvbs2_ddc_check(int(decim), t_ptr, ntaps, int(max_channels), int(max_inputs), int(max_samples)))
 
 
 def ddc_tile(decim, ntaps):
@@ -1552,9 +1541,8 @@ class Ddc(_Handle):
     _destroy = lib.dvbs2_ddc_destroy
 
     def __init__(self, decim, taps, max_channels=1, max_inputs=1, max_samples=1 << 20, device=0):
-        t = np.ascontiguousarray(taps, np.float32).reshape(-1)
-        check(lib.dvbs2_ddc_create(C.byref(self._h), int(decim), t.ctypes.data if t.size else None, int(t.size), int(max_channels),
-                                   int(max_inputs), int(max_samples), device))
+        t, t_ptr, ntaps = _f32_vector(taps)
+        check(lib.dvbs2_ddc_create(C.byref(self._h), int(decim), t_ptr, ntaps, int(max_channels), int(max_inputs), int(max_samples), device))
         self.max_channels, self.max_inputs, self.max_samples = max_channels, max_inputs, max_samples
         self.decim, self.ntaps, self.history, self.delay_num, self.tile = _ints(5, lib.dvbs2_ddc_params, self._h)
 
@@ -1589,19 +1577,13 @@ class Ddc(_Handle):
 
     def work(self, samples, n_channels=None):
         """HOST buffer: complex64 [n_inputs, n_in] (or a vector: one input). Returns complex64 [n_channels, produce(n_in)]."""
-        x = np.asarray(samples)
-        if x.dtype != np.complex64:
-            raise TypeError(f"samples must be complex64, not {x.dtype}")
-        if x.ndim == 1:
-            x = x.reshape(1, -1)
-        if x.ndim != 2 or not x.flags.c_contiguous:
-            raise ValueError("samples must be a C-contiguous vector or [n_inputs, n_in] matrix")
+        x = _complex64(samples, "samples", rows="[n_inputs, n_in]")
         nc = self.max_channels if n_channels is None else int(n_channels)
         n_inputs, n_in = x.shape
         stride = max(self.produce(n_in), 1) if n_in <= self.max_samples else 1
         out = np.empty((max(nc, 1), stride), np.complex64)
         n = C.c_int64()
-        check(lib.dvbs2_ddc_process(self._h, x.ctypes.data if x.size else None, int(n_in), int(n_in), int(n_inputs), nc, out.ctypes.data,
+        check(lib.dvbs2_ddc_process(self._h, _ptr(x), int(n_in), int(n_in), int(n_inputs), nc, out.ctypes.data,
                                     int(stride), C.byref(n)))
         return out[:nc, :n.value]
 
@@ -1644,7 +1626,7 @@ def _window_arg(window, nfft):
         return None
     if isinstance(window, (str, int)):
         return spectrum_window(window, nfft)
-    w = np.ascontiguousarray(window, np.float32).reshape(-1)
+    w = _f32_vector(window)[0]
     if w.size != int(nfft):
         raise ValueError("the window must have nfft values")
     return w
@@ -1660,7 +1642,7 @@ def spectrum_carriers(psd, shifted=True, max_out=64, smooth=None, floor_quantile
     """The carriers of one row of a power spectrum (dvbs2_spectrum_carriers): a record array (capi.SPECTRUM_CARRIER_DTYPE) sorted by
     centre -- centre and bandwidth in cycles per sample, level and floor in the row's units, the edge bins -- and the number found,
     which may exceed max_out. Parameters left at None take the library's defaults. Host only."""
-    row = np.ascontiguousarray(psd, np.float32).reshape(-1)
+    row, row_ptr, nfft = _f32_vector(psd)
     params = None
     if any(v is not None for v in (smooth, floor_quantile, threshold_db, min_gap, min_width)):
         params = capi.SpectrumCarrierParams(0.25 if floor_quantile is None else float(floor_quantile), 6.0 if threshold_db is None else float(threshold_db),
@@ -1668,7 +1650,7 @@ def spectrum_carriers(psd, shifted=True, max_out=64, smooth=None, floor_quantile
                                             8 if min_width is None else int(min_width), 0)
     out = np.zeros(max(int(max_out), 1), capi.SPECTRUM_CARRIER_DTYPE)
     n = C.c_int()
-    check(lib.dvbs2_spectrum_carriers(row.ctypes.data if row.size else None, int(row.size), int(bool(shifted)),
+    check(lib.dvbs2_spectrum_carriers(row_ptr, nfft, int(bool(shifted)),
                                       C.addressof(params) if params is not None else None, out.ctypes.data, int(max_out), C.byref(n)))
     return out[:min(n.value, int(max_out))], n.value
 
@@ -1697,18 +1679,12 @@ class Spectrum(_Handle):
 
     def work(self, samples):
         """HOST buffer: complex64 [n_streams, n_in] (or a vector: one stream). Returns float32 [n_streams, n_rows, nfft]."""
-        x = np.asarray(samples)
-        if x.dtype != np.complex64:
-            raise TypeError(f"samples must be complex64, not {x.dtype}")
-        if x.ndim == 1:
-            x = x.reshape(1, -1)
-        if x.ndim != 2 or not x.flags.c_contiguous:
-            raise ValueError("samples must be a C-contiguous vector or [n_streams, n_in] matrix")
+        x = _complex64(samples, "samples", rows="[n_streams, n_in]")
         n_streams, n_in = x.shape
         rows = self.geometry(n_in)[1] if n_in <= self.max_samples else 0
         out = np.empty((max(n_streams, 1), max(rows, 1), self.nfft), np.float32)
         n = C.c_int()
-        check(lib.dvbs2_spectrum_process(self._h, x.ctypes.data if x.size else None, int(n_in), int(n_in), int(n_streams), out.ctypes.data,
+        check(lib.dvbs2_spectrum_process(self._h, _ptr(x), int(n_in), int(n_in), int(n_streams), out.ctypes.data,
                                          int(max(rows, 1) * self.nfft), C.byref(n)))
         return out[:n_streams, :n.value]
 

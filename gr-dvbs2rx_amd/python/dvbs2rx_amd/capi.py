@@ -348,9 +348,9 @@ lib = C.CDLL(LIB_PATH)
 for _name, (_res, _args) in SYMBOLS.items():
     if os.environ.get("DVBS2_LIB") and not hasattr(lib, _name):
         continue  # kernel experiments against a library built from an older tree (tools/ab.sh); the product library must export all
-    _f = getattr(lib, _name)
-    _f.restype = _res
-    _f.argtypes = _args
+    _fn = getattr(lib, _name)  # (not _f: that is the c_float alias SYMBOLS is written with)
+    _fn.restype = _res
+    _fn.argtypes = _args
 
 
 class Dvbs2Error(RuntimeError):
