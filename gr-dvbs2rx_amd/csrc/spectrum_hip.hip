@@ -1,5 +1,6 @@
 // spectrum_hip.hip -- see spectrum_hip.h.
 #include "spectrum_hip.h"
+#include "fft_twiddles.h"
 #include <algorithm>
 #include <cmath>
 
@@ -43,11 +44,7 @@ int spectrum_window(int kind, int nfft, float* out)
 int spectrum_twiddles(int nfft, float* out)
 {
     if (spectrum_log2(nfft) < 0 || !out) return -1;
-    for (int i = 0; i < nfft / 2; i++) {
-        const double x = 2.0 * M_PI * i / nfft;
-        out[2 * i] = (float)std::cos(x);
-        out[2 * i + 1] = (float)-std::sin(x);
-    }
+    fft_twiddles(nfft, out);
     return 0;
 }
 
@@ -280,17 +277,10 @@ SpectrumHip::SpectrumHip(int nfft, int hop, int avg, const float* window, int sh
 {
     if (const std::string bad = check_args(nfft, hop, avg, window, max_streams, max_samples); !bad.empty()) { err_.argument(bad); return; }
     nfft_ = nfft; log2_ = spectrum_log2(nfft); hop_ = hop; avg_ = avg; shifted_ = shifted ? 1 : 0;
-    std::vector<float> w((size_t)nfft), tw((size_t)nfft);
+    std::vector<float> w((size_t)nfft);
     if (window) std::copy(window, window + nfft, w.begin());
     else spectrum_window(kSpectrumHann, nfft, w.data());
-    spectrum_twiddles(nfft, tw.data());
-    std::vector<float> staged(2 * (size_t)nfft, 0.0f); // the same entries in stage order (SpecArgs::tw); nfft - 1 of them
-    for (int s = 1; s <= log2_; s++)
-        for (int k = 0; k < 1 << (s - 1); k++) {
-            const size_t to = (size_t)(1 << (s - 1)) - 1 + k, from = (size_t)k << (log2_ - s);
-            staged[2 * to] = tw[2 * from];
-            staged[2 * to + 1] = tw[2 * from + 1];
-        }
+    const std::vector<float> staged = fft_twiddles_staged(nfft, log2_); // the table's entries in stage order (SpecArgs::tw); nfft - 1 of them
     window_power_ = spectrum_window_power(w.data(), nfft);
     // the chunk sums of the largest call, where a row of it has more than one chunk
     int seg = 0;

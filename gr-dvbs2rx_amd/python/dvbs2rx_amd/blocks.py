@@ -24,6 +24,7 @@ __all__ = ["get_fec_info", "rate_id", "LdpcDecoder", "BchDecoder", "Demapper", "
            "Resampler", "resamp_step", "resamp_geometry", "resamp_max_out", "resamp_check",
            "Ddc", "ddc_geometry", "ddc_produce", "ddc_check", "ddc_tile",
            "Spectrum", "spectrum_geometry", "spectrum_window", "spectrum_twiddles", "spectrum_check", "spectrum_carriers",
+           "PfbChannelizer", "pfbch_geometry", "pfbch_produce", "pfbch_check", "pfbch_tile", "pfbch_twiddles",
            "BbFramer", "bbheader_build", "crc8"]
 
 DEFAULT_TRIALS = 25  # reference lib/ldpc_decoder_bb_impl.cc:391
@@ -1695,4 +1696,93 @@ class Spectrum(_Handle):
         n = C.c_int()
         check(lib.dvbs2_spectrum_process_device(self._h, d_in or None, int(in_stride), int(n_in), int(n_streams), d_out or None, int(out_stride),
                                                 C.byref(n), stream or None))
+        return n.value
+
+
+def pfbch_geometry(n_chan, decim, ntaps):
+    """(history in raw samples per stream, delay_num: the delay is delay_num / 2 input samples, taps per branch) (dvbs2_pfbch_geometry).
+    Host only."""
+    return _ints(3, lib.dvbs2_pfbch_geometry, int(n_chan), int(decim), int(ntaps))
+
+
+def pfbch_produce(position, decim, n_in):
+    """What a call of n_in samples writes per channel when the sample counter stands at `position` (dvbs2_pfbch_produce). Host only."""
+    n = lib.dvbs2_pfbch_produce(int(position), int(decim), int(n_in))
+    check(min(n, 0))
+    return n
+
+
+def pfbch_check(n_chan, decim, taps, max_streams=1, max_samples=1 << 20):
+    """Raises what PfbChannelizer(...) would raise for these arguments, without a device (dvbs2_pfbch_check)."""
+    t, t_ptr, ntaps = _f32_vector(taps)
+    check(lib.dvbs2_pfbch_check(int(n_chan), int(decim), t_ptr, ntaps, int(max_streams), int(max_samples)))
+
+
+def pfbch_tile(n_chan, decim, ntaps):
+    """Output instants per workgroup of the channelizer's kernel: the tile rule of include/dvbs2_fec_hip.h. Host only."""
+    return min(capi.PFBCH_MAX_TILE, (capi.PFBCH_SPAN - (int(ntaps) - 1) - int(n_chan)) // int(decim))
+
+
+def pfbch_twiddles(n_chan):
+    """The transform's one table, complex64 [n_chan / 2] (dvbs2_pfbch_twiddles). Host only."""
+    t = np.zeros(max(int(n_chan) // 2, 1), np.complex64)
+    check(lib.dvbs2_pfbch_twiddles(int(n_chan), t.ctypes.data))
+    return t
+
+
+class PfbChannelizer(_Handle):
+    """A polyphase filter bank channelizer: n_chan equally spaced channels of every input stream, channel c the band centred at
+    +c / n_chan of the input rate, each filtered by the caller's real `taps` and output at 1 / decim of the input rate
+    (notes/pfbch.md). The last ntaps - 1 raw samples of every stream stay on the device between calls. n samples in give produce(n)
+    samples out per selected channel, delayed by delay_num / 2 input samples."""
+    _destroy = lib.dvbs2_pfbch_destroy
+
+    def __init__(self, n_chan, decim, taps, max_streams=1, max_samples=1 << 20, device=0):
+        t, t_ptr, ntaps = _f32_vector(taps)
+        check(lib.dvbs2_pfbch_create(C.byref(self._h), int(n_chan), int(decim), t_ptr, ntaps, int(max_streams), int(max_samples), device))
+        self.max_streams, self.max_samples = max_streams, max_samples
+        self.n_chan, self.decim, self.ntaps, self.history, self.delay_num, self.tile = _ints(6, lib.dvbs2_pfbch_params, self._h)
+
+    def set_channels(self, channels):
+        """From the next call on row i of a stream holds channel channels[i]: 1..n_chan distinct indices in any order. Host only."""
+        sel = np.ascontiguousarray(channels, np.int32).reshape(-1)
+        check(lib.dvbs2_pfbch_set_channels(self._h, _ptr(sel), int(sel.size)))
+
+    def channels(self):
+        """The selection, read back."""
+        sel, n = np.zeros(self.n_chan, np.int32), C.c_int()
+        check(lib.dvbs2_pfbch_channels(self._h, sel.ctypes.data, C.byref(n)))
+        return sel[:n.value].tolist()
+
+    def reset(self):
+        check(lib.dvbs2_pfbch_reset(self._h))
+
+    def position(self):
+        """The sample counter, from the host's mirror."""
+        n = C.c_int64()
+        check(lib.dvbs2_pfbch_position(self._h, C.byref(n)))
+        return n.value
+
+    def produce(self, n_in):
+        """What the next call of n_in samples writes per channel. From the host's mirror: no synchronisation."""
+        return pfbch_produce(self.position(), self.decim, n_in)
+
+    def work(self, samples):
+        """HOST buffer: complex64 [n_streams, n_in] (or a vector: one stream). Returns complex64 [n_streams, n_sel, produce(n_in)]."""
+        x = _complex64(samples, "samples", rows="[n_streams, n_in]")
+        n_streams, n_in = x.shape
+        n_sel = len(self.channels())
+        stride = max(self.produce(n_in), 1) if n_in <= self.max_samples else 1
+        out = np.empty((max(n_streams, 1), n_sel, stride), np.complex64)
+        n = C.c_int64()
+        check(lib.dvbs2_pfbch_process(self._h, _ptr(x), int(n_in), int(n_in), int(n_streams), out.ctypes.data, int(stride), C.byref(n)))
+        return out[:n_streams, :, :n.value]
+
+    def work_device(self, d_in, in_stride, n_in, n_streams, d_out, out_stride, stream=0):
+        """DEVICE addresses (8-byte aligned, not overlapping), asynchronous on `stream`: stream s reads n_in complex64 samples at
+        d_in + 8 * s * in_stride and writes n_out samples of channel channels()[i] at d_out + 8 * (s * n_sel + i) * out_stride;
+        out_stride >= n_out. Returns n_out (what produce() said before the call). One call in flight per handle."""
+        n = C.c_int64()
+        check(lib.dvbs2_pfbch_process_device(self._h, d_in or None, int(in_stride), int(n_in), int(n_streams), d_out or None,
+                                             int(out_stride), C.byref(n), stream or None))
         return n.value

@@ -1161,6 +1161,72 @@ int dvbs2_spectrum_process_device(dvbs2_spectrum_t* h, const float* d_in, int64_
 int dvbs2_spectrum_process(dvbs2_spectrum_t* h, const float* in, int64_t in_stride, int n_in, int n_streams, float* out,
                            int64_t out_stride, int* n_rows);
 
+/* ---- polyphase filter bank channelizer: a capture split into M equally spaced carriers, the FIR work done ONCE for all channels and one
+ * M-point transform in place of M mixers. It is GNU Radio's pfb_channelizer_ccf; the block is not in the reference tree: the stage is
+ * UNPINNED against it. A handle holds n_chan = M (a power of two in 2..256), decim = D (1..M, any integer, not only a divisor of M),
+ * ntaps (1..4096) real taps h, a selection of channels (all M ascending until set), ONE 64-bit absolute sample counter n0 for all
+ * streams, and per stream the last ntaps - 1 RAW input samples; x[n] for n < 0 is zero after create / reset. What is defined, and tested
+ * bit for bit against a float32 restatement (tests/pfbch_model.py), is this:
+ *   COUNTS. The down-converter's: a call over the absolute inputs [n0, n0 + n_in) writes the outputs k with n0 <= k D < n0 + n_in,
+ *   n_out = ceil((n0 + n_in) / D) - ceil(n0 / D) per channel, and leaves n0' = n0 + n_in. n_in in 0..2^24, n0 at most 2^62.
+ *   BRANCH SUMS. For output k and residue r in 0..M-1: w[k][r] = sum over the taps t with (k D - t) mod M == r of h[t] x[k D - t], t
+ *   ascending, real and imaginary part apart, each term a float product and then a float addition onto +0.0f, nothing fused. A residue
+ *   without a tap (ntaps < M) is +0.0f. The residue is that of the ABSOLUTE sample index, so nothing depends on how a stream is cut.
+ *   TRANSFORM. Y[k][c] = sum_r w[k][r] e^{-2 pi j c r / M} by the graph of dvbs2_spectrum_*: input to bit-reversed places, stages
+ *   s = 1..log2 M, (a, b) -> (a + T, a - T), stage 1 with T = b, every later stage Tr = Wr br - Wi bi, Ti = Wr bi + Wi br for EVERY
+ *   index (unit twiddles included), W from one table of M / 2 entries (float(cos(2 pi i / M)), float(-sin(2 pi i / M))) computed in
+ *   double: dvbs2_pfbch_twiddles, the entries of dvbs2_spectrum_twiddles for 2..256.
+ *   MEANING. Y[k][c] = sum_t h[t] x[k D - t] e^{-2 pi j c (k D - t) / M}: channel c is the band centred at +c / M of the input rate (the
+ *   upper half of the indices are the negative frequencies), filtered by h and output at 1 / D of the input rate. In exact arithmetic
+ *   it is dvbs2_ddc_* from reset with phase_inc = -2 pi c / M, the same taps and the same decim. The delay is (ntaps - 1) / 2 input
+ *   samples (delay_num = ntaps - 1 halves of one).
+ *   OUTPUT. Row i of stream s is n_out complex samples at d_out + (s n_sel + i) out_stride and holds channel list[i].
+ *   dvbs2_pfbch_set_channels (host only) accepts 1..M distinct indices in any order and takes effect from the next call; channels that
+ *   are not selected are not written. The transform is computed whole.
+ *   STATE. Raw history only, no phases: cuts of any kind -- empty calls, calls shorter than D or than the history, a changed selection
+ *   between calls -- give the bits of one call.
+ * Stream s reads n_in interleaved (re, im) samples at d_in + s in_stride; strides count complex elements, buffers are 8-byte aligned;
+ * in == out is refused and other overlaps are not detected. in_stride matters when n_streams > 1; out_stride is also the capacity of
+ * every row. Two launches per call at most (the samples, then the new histories; the first call behind a dvbs2_pfbch_set_channels also
+ * copies the selection on the stream), no allocation, no host synchronisation; the counter is mirrored on the host, so
+ * dvbs2_pfbch_position and the reported n_out (nullable) need none. ONE CALL IN FLIGHT PER HANDLE. A workgroup writes
+ * min(DVBS2_PFBCH_MAX_TILE, (DVBS2_PFBCH_SPAN - (ntaps - 1) - n_chan) / decim) consecutive output instants of one stream.
+ * Refused with DVBS2_ESIZE: n_in > max_samples, n_streams > max_streams. Refused with DVBS2_EINVAL and a text that names the argument:
+ * negative counts, a null buffer with n_in > 0 and n_streams > 0, in == out, with n_streams > 1 an in_stride < n_in, an out_stride
+ * < n_out (checked before anything is launched), buffers that are not 8-byte aligned, a selection that is null, empty, longer than
+ * n_chan, out of range or repeating. A refused call leaves output, histories, counter and selection untouched. n_in == 0 is a
+ * successful call that does nothing; n_streams == 0 only advances the counter. That does not cover a DVBS2_EDEVICE between the two launches
+ * (the first accepted, the second not): the outputs are then written, histories and counter are not advanced, and the handle is to be
+ * reset. Creation refuses (DVBS2_EINVAL) an n_chan that is no
+ * power of two in 2..256, decim outside 1..n_chan, ntaps outside 1..4096, a tap that is not finite, max_streams outside 1..65535,
+ * max_samples outside 1..2^24.
+ * Host only, no device needed: dvbs2_pfbch_geometry (history = ntaps - 1, delay_num = ntaps - 1, taps_per_branch = ceil(ntaps /
+ * n_chan); each nullable), dvbs2_pfbch_produce (the count rule; decim in 1..256), dvbs2_pfbch_twiddles (n_chan / 2 (re, im) pairs),
+ * dvbs2_pfbch_check (the argument check of dvbs2_pfbch_create), dvbs2_pfbch_set_channels, dvbs2_pfbch_channels (list: room for n_chan
+ * values; each nullable), dvbs2_pfbch_params, dvbs2_pfbch_position. ---- */
+typedef struct dvbs2_pfbch dvbs2_pfbch_t;
+#define DVBS2_PFBCH_SPAN 5376
+#define DVBS2_PFBCH_MAX_TILE 1024
+int dvbs2_pfbch_geometry(int n_chan, int decim, int ntaps, int* history, int* delay_num, int* taps_per_branch);
+int64_t dvbs2_pfbch_produce(int64_t position, int decim, int n_in);
+int dvbs2_pfbch_twiddles(int n_chan, float* out);
+int dvbs2_pfbch_check(int n_chan, int decim, const float* taps, int ntaps, int max_streams, int max_samples);
+int dvbs2_pfbch_create(dvbs2_pfbch_t** h, int n_chan, int decim, const float* taps, int ntaps, int max_streams, int max_samples, int device);
+void dvbs2_pfbch_destroy(dvbs2_pfbch_t* h);
+/* counter 0, histories zero; the selection stays; synchronous (waits for the device) */
+int dvbs2_pfbch_reset(dvbs2_pfbch_t* h);
+int dvbs2_pfbch_set_channels(dvbs2_pfbch_t* h, const int* list, int n_sel);
+/* each nullable; tile: output instants per workgroup */
+int dvbs2_pfbch_params(const dvbs2_pfbch_t* h, int* n_chan, int* decim, int* ntaps, int* history, int* delay_num, int* tile);
+int dvbs2_pfbch_position(const dvbs2_pfbch_t* h, int64_t* counter);
+int dvbs2_pfbch_channels(const dvbs2_pfbch_t* h, int* list, int* n_sel);
+/* DEVICE pointers, asynchronous on `stream`; n_out is a HOST value, filled before the call returns */
+int dvbs2_pfbch_process_device(dvbs2_pfbch_t* h, const float* d_in, int64_t in_stride, int n_in, int n_streams, float* d_out,
+                               int64_t out_stride, int64_t* n_out, void* stream);
+/* host pointers, synchronous, staged through buffers of the handle; the same arguments and checks, alignment apart */
+int dvbs2_pfbch_process(dvbs2_pfbch_t* h, const float* in, int64_t in_stride, int n_in, int n_streams, float* out, int64_t out_stride,
+                        int64_t* n_out);
+
 /* ---- downstream neighbour: BBFRAME de-header, replaces bbdeheader_bb_impl::general_work (reference
  * lib/bbdeheader_bb_impl.cc:144-264) with parse_bbheader (:77-136) and check_crc8 (:138-142, generator
  * x^8 + x^7 + x^6 + x^4 + x^2 + 1, :55). Input: whole descrambled BBFRAMEs of kbch / 8 bytes (what dvbs2_bch_decode /
