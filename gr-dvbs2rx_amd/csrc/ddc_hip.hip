@@ -2,6 +2,7 @@
 #include "ddc_hip.h"
 #include "rotator_turns.h"
 #include "rotator_math.hpp"
+#include "stream_device.hpp"
 #include <algorithm>
 #include <cmath>
 
@@ -25,8 +26,6 @@ int64_t ddc_produce(int64_t position, int decim, int n_in)
 }
 
 namespace {
-
-typedef float v2f __attribute__((ext_vector_type(2))); // (re, im): one packed multiply and one packed add per term
 
 constexpr int kMaxLds = kDdcSpan + 2 * kDdcMaxDecim; // LDS slots at most: the span rounded up to whole columns, and one more column
 constexpr int kHistPerThread = (kDdcMaxTaps - 1 + 255) / 256;
@@ -102,32 +101,18 @@ __global__ __launch_bounds__(256) void ddc_kernel(const float2* __restrict__ in,
     }
 }
 
-// One block per channel behind ddc_kernel on the same HIP stream: the last H mixed samples of old history then the call's samples, mixed
-// once more with the same arithmetic, in place (every thread reads before any writes; H <= 4095), and the channel's phase after the call.
+// One block per channel behind ddc_kernel on the same HIP stream: roll_history over the call's samples, mixed once more with the same
+// arithmetic (the history holds mixed samples; H <= 4095), and the channel's phase after the call.
 __global__ __launch_bounds__(256) void ddc_state_kernel(const float2* __restrict__ in, long long in_stride, float2* __restrict__ hist,
                                                         const DdcHip::Chan* __restrict__ table, unsigned long long* __restrict__ phase,
                                                         int n_in, int H)
 {
-    const int t = threadIdx.x, c = blockIdx.x;
+    const int c = blockIdx.x;
     const DdcHip::Chan ch = table[c];
     const uint64_t P = phase[c];
     const float2* __restrict__ x = in + (long long)ch.input * in_stride;
-    float2* __restrict__ h = hist + (long long)c * H;
-    float2 v[kHistPerThread];
-#pragma unroll
-    for (int q = 0; q < kHistPerThread; q++) {
-        const int i = t + 256 * q;
-        v[q] = make_float2(0.0f, 0.0f);
-        if (i < H) {
-            const long long j = (long long)i + n_in - H; // the sample's index in the call: below 0 it is in the old history
-            v[q] = j < 0 ? h[j + H] : rotate_one(x[j], P + (uint64_t)j * ch.inc);
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < kHistPerThread; q++)
-        if (t + 256 * q < H) h[t + 256 * q] = v[q];
-    if (t == 0) phase[c] = P + (uint64_t)n_in * ch.inc;
+    roll_history<256, kHistPerThread>(hist + (long long)c * H, H, n_in, [&](long long j) { return rotate_one(x[j], P + (uint64_t)j * ch.inc); });
+    if (threadIdx.x == 0) phase[c] = P + (uint64_t)n_in * ch.inc;
 }
 
 } // namespace

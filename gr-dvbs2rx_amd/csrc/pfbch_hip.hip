@@ -1,6 +1,7 @@
 // pfbch_hip.hip -- see pfbch_hip.h.
 #include "pfbch_hip.h"
 #include "fft_twiddles.h"
+#include "stream_device.hpp"
 #include <algorithm>
 #include <cmath>
 
@@ -39,8 +40,6 @@ int pfbch_twiddles(int n_chan, float* out)
 }
 
 namespace {
-
-typedef float v2f __attribute__((ext_vector_type(2))); // (re, im): one packed multiply and one packed add per term
 
 constexpr int kThreads = 256;
 constexpr int kMaxLds = 80 * 1024; // bytes a block takes at most: two workgroups per CU
@@ -278,27 +277,11 @@ __global__ __launch_bounds__(kThreads) void pfbch_kernel(const float2* __restric
     }
 }
 
-// One block per stream behind pfbch_kernel on the same HIP stream: the last H raw samples of old history then the call's samples, in
-// place (every thread reads before any writes; H <= 4095).
+// One block per stream behind pfbch_kernel on the same HIP stream: roll_history over the call's raw samples. H <= 4095.
 __global__ __launch_bounds__(kThreads) void pfbch_state_kernel(const float2* __restrict__ in, long long in_stride, float2* __restrict__ hist, int n_in, int H)
 {
-    const int t = threadIdx.x;
     const float2* __restrict__ x = in + (long long)blockIdx.x * in_stride;
-    float2* __restrict__ h = hist + (long long)blockIdx.x * H;
-    float2 v[kHistPerThread];
-#pragma unroll
-    for (int q = 0; q < kHistPerThread; q++) {
-        const int i = t + kThreads * q;
-        v[q] = make_float2(0.0f, 0.0f);
-        if (i < H) {
-            const long long j = (long long)i + n_in - H; // the sample's index in the call: below 0 it is in the old history
-            v[q] = j < 0 ? h[j + H] : x[j];
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < kHistPerThread; q++)
-        if (t + kThreads * q < H) h[t + kThreads * q] = v[q];
+    roll_history<kThreads, kHistPerThread>(hist + (long long)blockIdx.x * H, H, n_in, [&](long long j) { return x[j]; });
 }
 
 template <int T> hipError_t allow_lds() { return hipFuncSetAttribute((const void*)pfbch_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds); }

@@ -1,6 +1,7 @@
 // pulse_hip.hip -- see pulse_hip.h.
 #include "pulse_hip.h"
 #include "rrc_pulse.h"
+#include "stream_device.hpp"
 #include <algorithm>
 #include <cmath>
 
@@ -48,8 +49,6 @@ int pulse_scale_taps(float* taps, int ntaps, int sps, double fullscale)
 
 namespace {
 
-typedef float v2f __attribute__((ext_vector_type(2))); // (re, im): one packed multiply and one packed add per term
-
 struct PulseGeom {
     int32_t sps, ntaps, history;
     int32_t full, rest; // ntaps = full * sps + rest, rest < sps: phase p has full + (p < rest) terms
@@ -76,7 +75,7 @@ __global__ __launch_bounds__(256) void pulse_kernel(const float2* __restrict__ i
 #pragma unroll
     for (int c = 0; c < kStage; c++) {
         const int j = t + 256 * c, i = base - H + j; // the LDS slot and the symbol's index in the call
-        if (j < n_here + H) stage[c] = i < 0 ? h0[i + H] : x[i];
+        if (j < n_here + H) stage[c] = history_or_input(h0, x, H, i);
     }
 #pragma unroll
     for (int c = 0; c < kStage; c++)
@@ -113,20 +112,12 @@ __global__ __launch_bounds__(256) void pulse_kernel(const float2* __restrict__ i
     }
 }
 
-// One block per stream behind pulse_kernel on the same HIP stream: the last H symbols of old history then input, in place. Every thread
-// reads before any writes. H <= 128.
+// One block per stream behind pulse_kernel on the same HIP stream: roll_history over the call's symbols. H <= 128.
 __global__ __launch_bounds__(128) void pulse_history_kernel(const float2* __restrict__ in, long long in_stride, float2* __restrict__ hist,
                                                             int n_syms, int H)
 {
-    const int i = threadIdx.x;
-    float2* __restrict__ h = hist + (long long)blockIdx.x * H;
-    float2 v = make_float2(0.0f, 0.0f);
-    if (i < H) {
-        const long long j = (long long)i + n_syms; // in old history then input
-        v = j < H ? h[j] : in[(long long)blockIdx.x * in_stride + (j - H)];
-    }
-    __syncthreads();
-    if (i < H) h[i] = v;
+    const float2* __restrict__ x = in + (long long)blockIdx.x * in_stride;
+    roll_history<128, 1>(hist + (long long)blockIdx.x * H, H, n_syms, [&](long long j) { return x[j]; });
 }
 
 } // namespace

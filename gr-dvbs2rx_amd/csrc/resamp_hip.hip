@@ -1,5 +1,6 @@
 // resamp_hip.hip -- see resamp_hip.h.
 #include "resamp_hip.h"
+#include "stream_device.hpp"
 #include <algorithm>
 #include <cmath>
 
@@ -32,8 +33,6 @@ int64_t resamp_max_out(uint64_t step, int n_in)
 }
 
 namespace {
-
-typedef float v2f __attribute__((ext_vector_type(2))); // (re, im): packed multiplies and additions
 
 constexpr int kSpan = 2 * kResampTile + kResampMaxTerms; // LDS slots for samples: at step <= 2^33 a tile's outputs span at most
                                                          // 2 (kResampTile - 1) + 1 newest samples, and L - 1 <= 127 before the first
@@ -71,7 +70,7 @@ __global__ __launch_bounds__(256) void resamp_kernel(const float2* __restrict__ 
 #pragma unroll
     for (int c = 0; c < kStage; c++) {
         const int q = t + 256 * c, i = i0 - H + q; // the LDS slot and the sample's index in the call; i + H = i0 + q >= 0
-        if (q < n_slots) stage[c] = i < 0 ? h0[i + H] : x[i];
+        if (q < n_slots) stage[c] = history_or_input(h0, x, H, i);
     }
     float4* __restrict__ lb4 = reinterpret_cast<float4*>(lds + kSpan);
     for (int e = t; e < g.bank_quads; e += 256) lb4[e] = bank[e];
@@ -110,21 +109,14 @@ __global__ __launch_bounds__(256) void resamp_kernel(const float2* __restrict__ 
     }
 }
 
-// One block per stream behind resamp_kernel on the same HIP stream: the last H samples of old history then input, in place (every thread
-// reads before any writes; H <= 127), and the stream's position after the call.
+// One block per stream behind resamp_kernel on the same HIP stream: roll_history over the call's samples (H <= 127), and the stream's
+// position after the call.
 __global__ __launch_bounds__(128) void resamp_state_kernel(const float2* __restrict__ in, long long in_stride, float2* __restrict__ hist,
                                                            unsigned long long* __restrict__ acc, unsigned long long step, int n_in, int H)
 {
-    const int i = threadIdx.x;
-    float2* __restrict__ h = hist + (long long)blockIdx.x * H;
-    float2 v = make_float2(0.0f, 0.0f);
-    if (i < H) {
-        const long long j = (long long)i + n_in; // in old history then input
-        v = j < H ? h[j] : in[(long long)blockIdx.x * in_stride + (j - H)];
-    }
-    __syncthreads();
-    if (i < H) h[i] = v;
-    if (i == 0) {
+    const float2* __restrict__ x = in + (long long)blockIdx.x * in_stride;
+    roll_history<128, 1>(hist + (long long)blockIdx.x * H, H, n_in, [&](long long j) { return x[j]; });
+    if (threadIdx.x == 0) {
         const unsigned long long N = (unsigned long long)n_in << 32, a = acc[blockIdx.x];
         const unsigned long long n = a >= N ? 0 : (N - a + step - 1) / step;
         acc[blockIdx.x] = a + n * step - N;

@@ -1,6 +1,7 @@
-// stream_stage.h -- what the stream stage classes (agc, awgn, iqconv, symsync, pulse, resamp, spectrum, ddc) have in common on top of
-// DeviceStage: the two capacities of a handle, the check of a caller's taps, and device buffers that start as zeros and that reset()
-// zeroes again. Host code only. Internal, not installed. The range texts of the capacities differ per stage and stay in its check_args.
+// stream_stage.h -- what the stream stage classes (agc, awgn, iqconv, symsync, pulse, resamp, spectrum, ddc, pfbch) have in common on top
+// of DeviceStage: the two capacities of a handle, the check of a caller's taps, and device buffers that start as zeros and that reset()
+// zeroes again. Host code only (what their kernels share is in stream_device.hpp). Internal, not installed. The range texts of the
+// capacities differ per stage and stay in its check_args.
 #pragma once
 #include <cmath>
 #include <string>
