@@ -1,4 +1,4 @@
-// stream_stage.h -- what the stream stage classes (agc, awgn, iqconv, symsync, pulse, resamp, spectrum, ddc, pfbch) have in common on top
+// stream_stage.h -- what the stream stage classes (agc, awgn, iqconv, symsync, pulse, resamp, spectrum, ddc, pfbch, pfbsyn) have in common on top
 // of DeviceStage: the two capacities of a handle, the check of a caller's taps, and device buffers that start as zeros and that reset()
 // zeroes again. Host code only (what their kernels share is in stream_device.hpp). Internal, not installed. The range texts of the
 // capacities differ per stage and stay in its check_args.

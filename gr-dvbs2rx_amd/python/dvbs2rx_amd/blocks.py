@@ -25,6 +25,7 @@ __all__ = ["get_fec_info", "rate_id", "LdpcDecoder", "BchDecoder", "Demapper", "
            "Ddc", "ddc_geometry", "ddc_produce", "ddc_check", "ddc_tile",
            "Spectrum", "spectrum_geometry", "spectrum_window", "spectrum_twiddles", "spectrum_check", "spectrum_carriers",
            "PfbChannelizer", "pfbch_geometry", "pfbch_produce", "pfbch_check", "pfbch_tile", "pfbch_twiddles",
+           "PfbSynthesizer", "pfbsyn_geometry", "pfbsyn_check", "pfbsyn_tile",
            "BbFramer", "bbheader_build", "crc8"]
 
 DEFAULT_TRIALS = 25  # reference lib/ldpc_decoder_bb_impl.cc:391
@@ -1785,4 +1786,90 @@ class PfbChannelizer(_Handle):
         n = C.c_int64()
         check(lib.dvbs2_pfbch_process_device(self._h, d_in or None, int(in_stride), int(n_in), int(n_streams), d_out or None,
                                              int(out_stride), C.byref(n), stream or None))
+        return n.value
+
+
+def pfbsyn_geometry(n_chan, interp, ntaps):
+    """(tail in partial sums per stream, delay_num: the delay is delay_num / 2 OUTPUT samples, taps per phase) (dvbs2_pfbsyn_geometry).
+    Host only."""
+    return _ints(3, lib.dvbs2_pfbsyn_geometry, int(n_chan), int(interp), int(ntaps))
+
+
+def pfbsyn_check(n_chan, interp, taps, max_streams=1, max_samples=1 << 20):
+    """Raises what PfbSynthesizer(...) would raise for these arguments, without a device (dvbs2_pfbsyn_check)."""
+    t, t_ptr, ntaps = _f32_vector(taps)
+    check(lib.dvbs2_pfbsyn_check(int(n_chan), int(interp), t_ptr, ntaps, int(max_streams), int(max_samples)))
+
+
+def pfbsyn_tile(n_chan, interp, ntaps):
+    """Input instants per workgroup of the synthesizer's kernel: the tile rule of include/dvbs2_fec_hip.h (dvbs2_pfbsyn_tile; raises for
+    a shape that creation refuses). Host only."""
+    n = lib.dvbs2_pfbsyn_tile(int(n_chan), int(interp), int(ntaps))
+    check(min(n, 0))
+    return n
+
+
+class PfbSynthesizer(_Handle):
+    """A polyphase synthesis filter bank, the transpose of PfbChannelizer: the rows of n_chan equally spaced channels become one
+    wideband stream at interp times their rate, row i shaped by the caller's real `taps` as an interpolating FIR and moved to
+    +channels()[i] / n_chan of the output rate (notes/pfbsyn.md). max(ntaps - interp, 0) partial sums of every stream stay on the
+    device between calls. n instants in give n * interp samples out, delayed by delay_num / 2 output samples."""
+    _destroy = lib.dvbs2_pfbsyn_destroy
+
+    def __init__(self, n_chan, interp, taps, max_streams=1, max_samples=1 << 20, device=0):
+        t, t_ptr, ntaps = _f32_vector(taps)
+        check(lib.dvbs2_pfbsyn_create(C.byref(self._h), int(n_chan), int(interp), t_ptr, ntaps, int(max_streams), int(max_samples), device))
+        self.max_streams, self.max_samples = max_streams, max_samples
+        self.n_chan, self.interp, self.ntaps, self.tail, self.delay_num, self.tile = _ints(6, lib.dvbs2_pfbsyn_params, self._h)
+
+    def set_channels(self, channels):
+        """From the next call on row i of a stream feeds channel channels[i]: 1..n_chan distinct indices in any order. Host only."""
+        sel = np.ascontiguousarray(channels, np.int32).reshape(-1)
+        check(lib.dvbs2_pfbsyn_set_channels(self._h, _ptr(sel), int(sel.size)))
+
+    def channels(self):
+        """The selection, read back."""
+        sel, n = np.zeros(self.n_chan, np.int32), C.c_int()
+        check(lib.dvbs2_pfbsyn_channels(self._h, sel.ctypes.data, C.byref(n)))
+        return sel[:n.value].tolist()
+
+    def reset(self):
+        check(lib.dvbs2_pfbsyn_reset(self._h))
+
+    def position(self):
+        """The counter of input instants, from the host's mirror."""
+        n = C.c_int64()
+        check(lib.dvbs2_pfbsyn_position(self._h, C.byref(n)))
+        return n.value
+
+    def produce(self, n_in):
+        """What a call of n_in instants writes per stream: n_in * interp. Host only, no synchronisation."""
+        if not 0 <= int(n_in) <= 1 << 24:
+            raise ValueError("n_in must be in 0..2^24")
+        return int(n_in) * self.interp
+
+    def work(self, samples):
+        """HOST buffer: complex64 [n_streams, n_sel, n_in] (or [n_sel, n_in]: one stream). Returns complex64 [n_streams, n_in * interp]."""
+        x = np.asarray(samples)
+        if x.dtype != np.complex64:
+            raise TypeError(f"samples must be complex64, not {x.dtype}")
+        if x.ndim == 2:
+            x = x.reshape((1,) + x.shape)
+        n_sel = len(self.channels())
+        if x.ndim != 3 or x.shape[1] != n_sel or not x.flags.c_contiguous:
+            raise ValueError("samples must be a C-contiguous [n_streams, n_sel, n_in] or [n_sel, n_in] array")
+        n_streams, _, n_in = x.shape
+        stride = max(n_in * self.interp, 1)
+        out = np.empty((max(n_streams, 1), stride), np.complex64)
+        n = C.c_int64()
+        check(lib.dvbs2_pfbsyn_process(self._h, _ptr(x), int(n_in), int(n_in), int(n_streams), out.ctypes.data, int(stride), C.byref(n)))
+        return out[:n_streams, :n.value]
+
+    def work_device(self, d_in, in_stride, n_in, n_streams, d_out, out_stride, stream=0):
+        """DEVICE addresses (8-byte aligned, not overlapping), asynchronous on `stream`: row i of stream s is n_in complex64 samples at
+        d_in + 8 * (s * n_sel + i) * in_stride; stream s writes n_in * interp samples at d_out + 8 * s * out_stride; out_stride >= that.
+        Returns n_out. One call in flight per handle."""
+        n = C.c_int64()
+        check(lib.dvbs2_pfbsyn_process_device(self._h, d_in or None, int(in_stride), int(n_in), int(n_streams), d_out or None,
+                                              int(out_stride), C.byref(n), stream or None))
         return n.value

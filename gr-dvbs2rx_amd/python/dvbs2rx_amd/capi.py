@@ -31,6 +31,8 @@ DDC_SPAN, DDC_MAX_TILE = 9216, 1024  # DVBS2_DDC_SPAN, DVBS2_DDC_MAX_TILE: a wor
 # mixed samples and writes min(DDC_MAX_TILE, (DDC_SPAN - (ntaps - 1)) // decim) output samples
 PFBCH_SPAN, PFBCH_MAX_TILE = 5376, 1024  # DVBS2_PFBCH_SPAN, DVBS2_PFBCH_MAX_TILE: a workgroup of the channelizer's kernel writes
 # min(PFBCH_MAX_TILE, (PFBCH_SPAN - (ntaps - 1) - n_chan) // decim) output instants
+PFBSYN_SPAN, PFBSYN_SPAN_LONG, PFBSYN_MAX_TILE, PFBSYN_MAX_PRODUCT = 6144, 13312, 512, 8192  # DVBS2_PFBSYN_*: the synthesizer's tile rule
+# (dvbs2_pfbsyn_tile) and the largest n_chan * ceil(ntaps / interp) that creation accepts
 SPECTRUM_CHUNK = 16  # DVBS2_SPECTRUM_CHUNK: segments whose powers one workgroup of the spectrum kernel adds in order
 SPECTRUM_RECT, SPECTRUM_HANN, SPECTRUM_HAMMING, SPECTRUM_BLACKMAN_HARRIS = 0, 1, 2, 3  # DVBS2_SPECTRUM_*: the windows
 AGC_TILE = 64  # DVBS2_AGC_TILE: samples per stream and tile of the AGC's kernel
@@ -300,6 +302,18 @@ SYMBOLS = {
     "dvbs2_pfbch_channels": (_i, [_vp, _vp, _ip]),
     "dvbs2_pfbch_process_device": (_i, [_vp, _vp, C.c_int64, _i, _i, _vp, C.c_int64, C.POINTER(C.c_int64), _vp]),
     "dvbs2_pfbch_process": (_i, [_vp, _vp, C.c_int64, _i, _i, _vp, C.c_int64, C.POINTER(C.c_int64)]),
+    "dvbs2_pfbsyn_geometry": (_i, [_i, _i, _i, _ip, _ip, _ip]),
+    "dvbs2_pfbsyn_tile": (_i, [_i, _i, _i]),
+    "dvbs2_pfbsyn_check": (_i, [_i, _i, _vp, _i, _i, _i]),
+    "dvbs2_pfbsyn_create": (_i, [C.POINTER(_vp), _i, _i, _vp, _i, _i, _i, _i]),
+    "dvbs2_pfbsyn_destroy": (None, [_vp]),
+    "dvbs2_pfbsyn_reset": (_i, [_vp]),
+    "dvbs2_pfbsyn_set_channels": (_i, [_vp, _vp, _i]),
+    "dvbs2_pfbsyn_params": (_i, [_vp, _ip, _ip, _ip, _ip, _ip, _ip]),
+    "dvbs2_pfbsyn_position": (_i, [_vp, C.POINTER(C.c_int64)]),
+    "dvbs2_pfbsyn_channels": (_i, [_vp, _vp, _ip]),
+    "dvbs2_pfbsyn_process_device": (_i, [_vp, _vp, C.c_int64, _i, _i, _vp, C.c_int64, C.POINTER(C.c_int64), _vp]),
+    "dvbs2_pfbsyn_process": (_i, [_vp, _vp, C.c_int64, _i, _i, _vp, C.c_int64, C.POINTER(C.c_int64)]),
     "dvbs2_bbdeheader_create": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i]),
     "dvbs2_bbdeheader_create_raw": (_i, [C.POINTER(_vp), _i, _i, _i]),
     "dvbs2_bbdeheader_destroy": (None, [_vp]),

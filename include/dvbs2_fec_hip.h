@@ -1227,6 +1227,80 @@ int dvbs2_pfbch_process_device(dvbs2_pfbch_t* h, const float* d_in, int64_t in_s
 int dvbs2_pfbch_process(dvbs2_pfbch_t* h, const float* in, int64_t in_stride, int n_in, int n_streams, float* out, int64_t out_stride,
                         int64_t* n_out);
 
+/* ---- polyphase SYNTHESIS filter bank, the transpose of dvbs2_pfbch_*: the rows of M equally spaced channels become one wideband stream
+ * at L times their rate, with ONE M-point inverse transform per input instant in place of M mixers and ONE FIR pass for all channels.
+ * It is GNU Radio's pfb_synthesizer_ccf; the block is not in the reference tree: the stage is UNPINNED against it. With interp = M and
+ * root-raised-cosine taps it takes the PLFRAME symbols of M carriers straight to the wideband stream (pulse shaper, mixers and sum in
+ * one stage). A handle holds n_chan = M (a power of two in 2..256), interp = L (1..M, any integer, not only a divisor of M), ntaps
+ * (1..4096) real finite taps h, a selection of channels (all M ascending until set), ONE 64-bit counter k0 of input INSTANTS for all
+ * streams (at most 2^54), and per stream a TAIL of max(ntaps - L, 0) complex partial sums, zero after create / reset. What is defined,
+ * and tested bit for bit against a float32 restatement (tests/pfbsyn_model.py), is this:
+ *   COUNTS. A call of n_in instants (0..max_samples) reads n_in samples from each of the n_sel rows of a stream and writes exactly
+ *   n_out = n_in L samples per stream, the absolute outputs n in [k0 L, (k0 + n_in) L); then k0' = k0 + n_in.
+ *   INPUT. Row i of stream s is at d_in + (s n_sel + i) in_stride and feeds channel list[i]; dvbs2_pfbsyn_set_channels (host only)
+ *   accepts 1..M distinct indices in any order and takes effect from the next call. A channel without a row is +0.0f in both parts.
+ *   Stream s writes at d_out + s out_stride.
+ *   TRANSFORM. For instant k with inputs a[c]: v[k][r] = sum_c a[c] e^{+2 pi j c r / M}, r = 0..M-1, unnormalised, on the graph and
+ *   the one table of dvbs2_spectrum_* / dvbs2_pfbch_* (dvbs2_pfbch_twiddles): the graph's input is (re, im) := (a.im, a.re) with
+ *   channel c at its bit-reversed place, stage 1 has no product, every later stage computes Tr = Wr br - Wi bi, Ti = Wr bi + Wi br for
+ *   EVERY index, nothing is fused, and the result is read as (v.im, v.re) := (re, im).
+ *   FIR. For the absolute output n let r = n mod M, p = n mod L, k1 = n div L. Over the j with t = p + j L <= ntaps - 1 and
+ *   k = k1 - j >= 0, j DESCENDING (the oldest instant first; the channelizer's order is the opposite): acc = acc + h[t] * v[k][r] from
+ *   +0.0f, real and imaginary part apart, the product rounded to float and then the addition. An instant that does not exist (k < 0
+ *   after a reset) is skipped, not multiplied by zero.
+ *   TAIL. After a call tail[i] holds, for output k0' L + i, the acc over the instants k < k0' (+0.0f where there is none). The next
+ *   call starts those outputs from the tail and goes on with its own instants: cuts of any kind -- empty calls, calls of one instant,
+ *   calls shorter than the tail, a changed selection between calls -- give the bits of one call. Every instant is synthesised with
+ *   the selection of its own call.
+ *   MEANING. y[n] = sum_c e^{+2 pi j c n / M} sum_k h[n - k L] x_c[k]: every row shaped by an interpolating FIR by L (the
+ *   dvbs2_pulse_* sum, for any L), moved by dvbs2_rotator_* with +2 pi c / M from phase 0 at n = 0, and the rows added. Channel c is
+ *   the band centred at +c / M of the OUTPUT rate, the channelizer's numbering: dvbs2_pfbch_* with (M, L, g) on the output returns row
+ *   c as x_c through h * g at the instants k L. The delay is (ntaps - 1) / 2 output samples (delay_num = ntaps - 1 halves of one).
+ * Strides count complex elements, buffers are 8-byte aligned; in == out is refused and other overlaps are not detected. in_stride
+ * matters when the call has more than one row. Two launches per call at most (the samples and the tails the call leaves, then those
+ * tails copied over the old ones; the first call behind a dvbs2_pfbsyn_set_channels also copies the selection on the stream), no
+ * allocation, no host synchronisation; the counter is mirrored on the host, so dvbs2_pfbsyn_position and the reported n_out
+ * (nullable) need none. ONE CALL IN FLIGHT PER HANDLE. A workgroup owns dvbs2_pfbsyn_tile(n_chan, interp, ntaps) consecutive
+ * instants of one stream: with q = ceil(ntaps / interp) and seg = (n_chan + n_chan / 16) | 1, fit = DVBS2_PFBSYN_SPAN / seg - (q - 1)
+ * where that is at least q and DVBS2_PFBSYN_SPAN_LONG / seg - (q - 1) otherwise, DVBS2_PFBSYN_MAX_TILE at most.
+ * Refused with DVBS2_ESIZE: n_in > max_samples, n_streams > max_streams. Refused with DVBS2_EINVAL and a text that names the argument:
+ * negative counts, a null buffer with n_in > 0 and n_streams > 0, in == out, with more than one row an in_stride < n_in, an out_stride
+ * < n_out (checked before anything is launched), buffers that are not 8-byte aligned, a counter that would pass 2^54, a selection that
+ * is null, empty, longer than n_chan, out of range or repeating. A refused call leaves output, tails, counter and selection
+ * untouched. n_in == 0 is a successful call that does nothing; n_streams == 0 only advances the counter. That does not cover a
+ * DVBS2_EDEVICE between the two launches (the first accepted, the second not): the outputs are then written, tails and counter are
+ * not advanced, and the handle is to be reset. Creation refuses (DVBS2_EINVAL) an n_chan that is no power of two in 2..256, interp
+ * outside 1..n_chan, ntaps outside 1..4096, a tap that is not finite, n_chan * ceil(ntaps / interp) > DVBS2_PFBSYN_MAX_PRODUCT (a
+ * workgroup holds the transformed instants that its first output needs on chip: interp = 1 with a long filter on many channels is
+ * not a use of this stage), max_streams outside 1..65535, max_samples outside 1..2^24, max_samples * interp > 2^28.
+ * Host only, no device needed: dvbs2_pfbsyn_geometry (tail = max(ntaps - interp, 0), delay_num = ntaps - 1, taps_per_phase =
+ * ceil(ntaps / interp); each nullable), dvbs2_pfbsyn_tile (the tile, or DVBS2_EINVAL for a shape that creation refuses),
+ * dvbs2_pfbsyn_check (the argument check of dvbs2_pfbsyn_create), dvbs2_pfbsyn_set_channels, dvbs2_pfbsyn_channels (list: room for
+ * n_chan values; each nullable), dvbs2_pfbsyn_params, dvbs2_pfbsyn_position. ---- */
+typedef struct dvbs2_pfbsyn dvbs2_pfbsyn_t;
+#define DVBS2_PFBSYN_SPAN 6144
+#define DVBS2_PFBSYN_SPAN_LONG 13312
+#define DVBS2_PFBSYN_MAX_TILE 512
+#define DVBS2_PFBSYN_MAX_PRODUCT 8192
+int dvbs2_pfbsyn_geometry(int n_chan, int interp, int ntaps, int* tail, int* delay_num, int* taps_per_phase);
+int dvbs2_pfbsyn_tile(int n_chan, int interp, int ntaps);
+int dvbs2_pfbsyn_check(int n_chan, int interp, const float* taps, int ntaps, int max_streams, int max_samples);
+int dvbs2_pfbsyn_create(dvbs2_pfbsyn_t** h, int n_chan, int interp, const float* taps, int ntaps, int max_streams, int max_samples, int device);
+void dvbs2_pfbsyn_destroy(dvbs2_pfbsyn_t* h);
+/* counter 0, tails zero; the selection stays; synchronous (waits for the device) */
+int dvbs2_pfbsyn_reset(dvbs2_pfbsyn_t* h);
+int dvbs2_pfbsyn_set_channels(dvbs2_pfbsyn_t* h, const int* list, int n_sel);
+/* each nullable; tile: input instants per workgroup */
+int dvbs2_pfbsyn_params(const dvbs2_pfbsyn_t* h, int* n_chan, int* interp, int* ntaps, int* tail, int* delay_num, int* tile);
+int dvbs2_pfbsyn_position(const dvbs2_pfbsyn_t* h, int64_t* counter);
+int dvbs2_pfbsyn_channels(const dvbs2_pfbsyn_t* h, int* list, int* n_sel);
+/* DEVICE pointers, asynchronous on `stream`; n_out is a HOST value, filled before the call returns */
+int dvbs2_pfbsyn_process_device(dvbs2_pfbsyn_t* h, const float* d_in, int64_t in_stride, int n_in, int n_streams, float* d_out,
+                                int64_t out_stride, int64_t* n_out, void* stream);
+/* host pointers, synchronous, staged through buffers of the handle; the same arguments and checks, alignment apart */
+int dvbs2_pfbsyn_process(dvbs2_pfbsyn_t* h, const float* in, int64_t in_stride, int n_in, int n_streams, float* out, int64_t out_stride,
+                         int64_t* n_out);
+
 /* ---- downstream neighbour: BBFRAME de-header, replaces bbdeheader_bb_impl::general_work (reference
  * lib/bbdeheader_bb_impl.cc:144-264) with parse_bbheader (:77-136) and check_crc8 (:138-142, generator
  * x^8 + x^7 + x^6 + x^4 + x^2 + 1, :55). Input: whole descrambled BBFRAMEs of kbch / 8 bytes (what dvbs2_bch_decode /
