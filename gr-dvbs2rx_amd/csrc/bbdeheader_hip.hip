@@ -203,7 +203,7 @@ BbDeheaderHip::BbDeheaderHip(int kbch_bits, int max_frames, int device)
     DeviceGuard guard(device_);
     if (!guard.ok) { err_.argument("hipSetDevice failed"); return; } // (device failure, kArgument: notes/stage_error_codes.md)
     hipError_t e = alloc(&d_state_, 1);
-    if (e == hipSuccess) e = hipMemset(d_state_, 0, sizeof(BbdhState));
+    if (e == hipSuccess) e = memset_done(d_state_, 0, sizeof(BbdhState));
     if (e == hipSuccess) e = alloc(&d_plan_, (size_t)max_frames_ + 1);
     if (e == hipSuccess) e = alloc(&d_hdr_, max_frames_);
     hip_ok(e, "bbdeheader buffers", err_, kArgument); // (device failure, kArgument: notes/stage_error_codes.md)

@@ -275,7 +275,7 @@ BbFramerHip::BbFramerHip(int kbch_bits, int max_frames, int device) : DeviceStag
     DeviceGuard guard(device_);
     if (!guard.ok) { err_.device("hipSetDevice failed"); return; }
     HIP_OK_AS("hipMalloc of the bbframer state", alloc(&d_, 1));
-    HIP_OK(hipMemset(d_, 0, sizeof(BbfDevice)));
+    HIP_OK(memset_done(d_, 0, sizeof(BbfDevice)));
 }
 
 int BbFramerHip::set_matype(int matype1, int matype2)

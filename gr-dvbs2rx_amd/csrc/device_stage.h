@@ -9,6 +9,15 @@
 
 namespace dvbs2 {
 
+// hipMemset of device memory for a constructor or a reset. The runtime may return from hipMemset before the device has written: the
+// fill is work on the null stream, and a caller's non-blocking stream does not wait for the null stream (measured:
+// notes/stream_order.md). The bytes are there when this returns. Not for a work path: it waits on the host.
+inline hipError_t memset_done(void* p, int value, size_t bytes)
+{
+    const hipError_t e = hipMemset(p, value, bytes);
+    return e != hipSuccess ? e : hipStreamSynchronize(nullptr);
+}
+
 enum StageCode { kArgument = -1, kDevice = -2, kSize = -3 }; // what the C ABI answers for a failure (c_api_common.h asserts the values)
 struct StageError { // the code is decided where the error is raised; = {} clears
     int code = 0; std::string text; // (code: a StageCode once there is a text)

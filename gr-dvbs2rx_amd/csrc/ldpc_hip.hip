@@ -97,7 +97,7 @@ int* cu_slot_table(int device_key, std::string* err)
     for (const auto& e : per_device) if (e.first == device_key) return e.second;
     int* slots = nullptr;
     if (hipMalloc(&slots, kCuSlots * 4) != hipSuccess) { if (err) *err = "hipMalloc of the per-CU counters failed"; return nullptr; }
-    if (hipMemset(slots, 0, kCuSlots * 4) != hipSuccess) { (void)hipFree(slots); if (err) *err = "hipMemset of the per-CU counters failed"; return nullptr; }
+    if (memset_done(slots, 0, kCuSlots * 4) != hipSuccess) { (void)hipFree(slots); if (err) *err = "hipMemset of the per-CU counters failed"; return nullptr; }
     per_device.push_back({ device_key, slots });
     return slots;
 }
@@ -154,7 +154,7 @@ LdpcDecoderHip::LdpcDecoderHip(const LdpcTableDesc* table, int out_bits_message,
     HIP_OK(hipHostMalloc(&h_flag_, 4 * kSlots));
     HIP_OK(hipEventCreate(&ev0_));
     HIP_OK(hipEventCreate(&ev1_));
-    if (ov.timing) { HIP_OK_AS("hipMalloc(&d_tdbg_, ((size_t)max_frames_ * 48 + 512) * 8)", alloc(&d_tdbg_, (size_t)max_frames_ * 48 + 512)); HIP_OK(hipMemset(d_tdbg_, 0, ((size_t)max_frames_ * 48 + 512) * 8)); }
+    if (ov.timing) { HIP_OK_AS("hipMalloc(&d_tdbg_, ((size_t)max_frames_ * 48 + 512) * 8)", alloc(&d_tdbg_, (size_t)max_frames_ * 48 + 512)); HIP_OK(memset_done(d_tdbg_, 0, ((size_t)max_frames_ * 48 + 512) * 8)); }
     if (is_solo(build_)) {
         // The per-CU pattern counters of the one-frame builds are shared by ALL handles of a device: two workgroups on a CU take
         // complementary wave patterns through them, whichever launch (handle, stream) they belong to. With one array per handle two

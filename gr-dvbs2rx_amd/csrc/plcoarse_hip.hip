@@ -155,7 +155,7 @@ int PlCoarseHip::reset()
 {
     Entry on(*this);
     // all zero: no frame counted, empty accumulator, estimate 0, not coarse-corrected (lib/pl_freq_sync.cc:24-31)
-    if (!on.ok || hipDeviceSynchronize() != hipSuccess || hipMemset(d_state_, 0, sizeof(PlCoarseState)) != hipSuccess) {
+    if (!on.ok || hipDeviceSynchronize() != hipSuccess || memset_done(d_state_, 0, sizeof(PlCoarseState)) != hipSuccess) {
         call_err_.device("reset of the device state failed"); return -1;
     }
     return 0;

@@ -225,8 +225,10 @@ int PlSyncHip::reset()
     std::memset(&s, 0, sizeof(s));
     s.abs_last_peak = -1; // d_sym_cnt = 0 before the first symbol (lib/pl_frame_sync.cc:23)
     s.frame_len = fixed_plsc_ >= 0 ? pl_frame_shape(fixed_plsc_).plframe_len : 0; // lib/plsync_cc_impl.cc:159, lib/pl_frame_sync.cc:28
-    if (!on.ok || hipMemcpy(d_state_, &s, sizeof(s), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemset(d_hist_, 0, 2 * kHist * sizeof(float2)) != hipSuccess) { call_err_.device("reset of the device state failed"); return -1; }
+    // a search that is still pending on the caller's stream writes the state and the history behind itself: wait for it first (the
+    // null stream of the two copies below does not order itself against a non-blocking stream)
+    if (!on.ok || hipDeviceSynchronize() != hipSuccess || hipMemcpy(d_state_, &s, sizeof(s), hipMemcpyHostToDevice) != hipSuccess ||
+        memset_done(d_hist_, 0, 2 * kHist * sizeof(float2)) != hipSuccess) { call_err_.device("reset of the device state failed"); return -1; }
     return 0;
 }
 

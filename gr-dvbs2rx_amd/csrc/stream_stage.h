@@ -29,7 +29,7 @@ protected:
     StreamStage(int max_streams, int max_samples, int device) : DeviceStage(device), max_streams_(max_streams), max_samples_(max_samples) {}
 
     // alloc() of `count` elements that start as zeros; zero(p) makes them zeros again, so the size is written once. The first failure is
-    // returned: the allocation's or the hipMemset's.
+    // returned: the allocation's or the fill's (memset_done: the zeros are on the device when it returns).
     template <class T> hipError_t alloc_zeroed(T** p, size_t count)
     {
         const hipError_t e = alloc(p, count);
@@ -40,7 +40,7 @@ protected:
     hipError_t zero(const void* p)
     {
         for (const auto& z : zeroed_)
-            if (z.first == p) return hipMemset(z.first, 0, z.second);
+            if (z.first == p) return memset_done(z.first, 0, z.second);
         return hipErrorInvalidValue; // not a buffer of alloc_zeroed
     }
 

@@ -578,6 +578,7 @@ typedef struct {
 } dvbs2_plsync_frame_t;
 int dvbs2_plsync_create(dvbs2_plsync_t** h, int plsc_or_minus1, int unlock_thresh, int max_symbols, int max_frames, int device);
 void dvbs2_plsync_destroy(dvbs2_plsync_t* h);
+/* the handle as created: state searching, absolute offset 0, history zeros; synchronous (waits for the device) */
 int dvbs2_plsync_reset(dvbs2_plsync_t* h);
 int dvbs2_plsync_set_plsc_mode(dvbs2_plsync_t* h, int coherent, int soft);
 int dvbs2_plsync_set_expected_pls(dvbs2_plsync_t* h, const uint8_t* plsc_list, int n);

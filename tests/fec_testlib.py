@@ -969,3 +969,81 @@ def bbframe_stream(kbch_bits, n_frames, up_stream, syncd_bits=0):
         syncd_bits = ((188 - partial) % 188) * 8  # (a packet that starts with the DATAFIELD: SYNCD = 0, EN 302 307-1 clause 5.1.6)
         off += dfl_bytes
     return frames
+
+
+# ------------------------------------------------------------------ a busy non-blocking stream (tests/test_stream_order_gpu.py)
+# A hold is a BOUNDED spin enqueued on a stream: what is enqueued behind it stays pending while the host goes on. There is no gate that
+# waits for the host, on purpose: a test that dies between enqueue and release must not leave a wave spinning on the card.
+HOLD_MIN_MS, HOLD_MAX_MS, HOLD_FACTOR = 20.0, 250.0, 20.0
+_sleep_cal = {}
+
+
+def side_stream():
+    """a stream the null stream does not order itself against (torch's pool streams are created with hipStreamNonBlocking)"""
+    import torch
+    return torch.cuda.Stream()
+
+
+def null_stream():
+    import torch
+    return torch.cuda.default_stream()
+
+
+def sleep_calibration():
+    """dict(cycles_per_ms, probe_cycles, probe_ms): torch.cuda._sleep's cycles per millisecond, measured once per session with two events
+    around one _sleep on an idle stream (a short one first, so that no code object loads between the events)."""
+    import torch
+    if not _sleep_cal:
+        s = side_stream()
+        with torch.cuda.stream(s):
+            torch.cuda._sleep(1000)
+            s.synchronize()
+            cycles, ms = 1_000_000, 0.0
+            for _ in range(4):  # lengthen the probe until it lasts 20 ms: the events' own resolution is then below a percent
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record(s)
+                torch.cuda._sleep(cycles)
+                b.record(s)
+                s.synchronize()
+                ms = a.elapsed_time(b)
+                if ms >= 20.0:
+                    break
+                cycles = int(cycles * max(2.0, 40.0 / max(ms, 1e-3)))
+        assert ms > 0.0, "torch.cuda._sleep takes no time on this device"
+        _sleep_cal.update(cycles_per_ms=cycles / ms, probe_cycles=cycles, probe_ms=ms)
+        print(f"sleep calibration: {cycles} cycles took {ms:.3f} ms: {cycles / ms:.0f} cycles per ms")
+    return _sleep_cal
+
+
+def hold(stream, ms):
+    """keeps `stream` busy for about `ms` milliseconds from the moment the device gets to it; returns at once"""
+    import torch
+    assert 0.0 < ms <= HOLD_MAX_MS, f"a hold of {ms} ms: cut the sequence, not the margin"
+    cycles = int(ms * sleep_calibration()["cycles_per_ms"])
+    with torch.cuda.stream(stream):
+        torch.cuda._sleep(cycles)
+
+
+def hold_for(host_ms):
+    """the hold behind which a sequence is enqueued whose host side took host_ms on an idle stream: 20 times that for the jitter of a
+    machine others are using, never below 20 ms"""
+    return max(HOLD_MIN_MS, HOLD_FACTOR * host_ms)
+
+
+def pending(stream):
+    return not stream.query()
+
+
+def hip_runtime():
+    """ctypes handle of the HIP runtime this process already runs on (the one torch brought, which the library bound to)"""
+    with open("/proc/self/maps") as f:
+        paths = {line.split()[-1] for line in f if "libamdhip64" in line}
+    assert len(paths) == 1, f"expected one HIP runtime in the process, found {sorted(paths)}"
+    rt = C.CDLL(paths.pop())
+    rt.hipMemset.restype = C.c_int
+    rt.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
+    rt.hipMemcpyAsync.restype = C.c_int
+    rt.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    rt.hipStreamSynchronize.restype = C.c_int
+    rt.hipStreamSynchronize.argtypes = [C.c_void_p]
+    return rt
