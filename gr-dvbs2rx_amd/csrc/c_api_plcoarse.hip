@@ -11,6 +11,12 @@ struct dvbs2_plcoarse {
     int device = 0;
 };
 
+struct dvbs2_plcoarse_batch {
+    PlCoarseBatchHip* impl = nullptr;
+    HostStage stage; // (no host-buffer entry: nothing is staged)
+    int device = 0;
+};
+
 static PlCoarseOut plcoarse_out(float* foffset, int32_t* corrected, int32_t* new_est)
 {
     PlCoarseOut o;
@@ -95,6 +101,51 @@ int dvbs2_plcoarse_estimate(dvbs2_plcoarse_t* h, const float* plframes, int64_t 
     if (coarse_corrected) HCHK(hipMemcpyAsync(coarse_corrected, d_cc, nf * 4, hipMemcpyDeviceToHost, s.stream));
     if (new_est) HCHK(hipMemcpyAsync(new_est, d_ne, nf * 4, hipMemcpyDeviceToHost, s.stream));
     return s.sync();
+    API_CATCH
+}
+
+/* ------------------------------------------------------------------ the same estimate over the slots of a batch of streams */
+int dvbs2_plcoarse_batch_create(dvbs2_plcoarse_batch_t** h, int period, int plsc_or_minus1, int max_streams, int max_slots, int device)
+{
+    API_TRY
+    if (int rc = null_out(h)) return rc;
+    // arguments first: a bad argument is the caller's mistake on any machine
+    if (const std::string bad = plcoarse_batch_check(period, plsc_or_minus1, max_streams, max_slots); !bad.empty()) return fail(DVBS2_EINVAL, bad);
+    return make_handle(h, device, [&] { return new (std::nothrow) PlCoarseBatchHip(period, plsc_or_minus1, max_streams, max_slots, device); });
+    API_CATCH
+}
+
+void dvbs2_plcoarse_batch_destroy(dvbs2_plcoarse_batch_t* h) { destroy_handle(h); }
+
+int dvbs2_plcoarse_batch_reset(dvbs2_plcoarse_batch_t* h)
+{
+    API_TRY
+    NEED_HANDLE(h);
+    return impl_rc(h, h->impl->reset());
+    API_CATCH
+}
+
+int dvbs2_plcoarse_batch_reset_stream(dvbs2_plcoarse_batch_t* h, int stream_index)
+{
+    API_TRY
+    NEED_HANDLE(h);
+    if (stream_index < 0 || stream_index >= h->impl->max_streams()) return fail(DVBS2_EINVAL, "stream index out of range");
+    return impl_rc(h, h->impl->reset_stream(stream_index));
+    API_CATCH
+}
+
+int dvbs2_plcoarse_batch_estimate_device(dvbs2_plcoarse_batch_t* h, const float* d_slots, int64_t stride_syms, const uint8_t* d_plsc,
+                                         const int32_t* d_offsets, int n_streams, float* d_coarse_foffset, int32_t* d_coarse_corrected,
+                                         int32_t* d_new_est, void* stream)
+{
+    API_TRY
+    NEED_HANDLE(h);
+    if (int rc = check_counts({ { n_streams, h->impl->max_streams(), "n_streams", "max_streams" } })) return rc;
+    if (n_streams && (!d_slots || !d_offsets)) return fail(DVBS2_EINVAL, "bad argument");
+    if (stride_syms < 90) return fail(DVBS2_EINVAL, "stride below the 90 header symbols");
+    if (!d_plsc && h->impl->fixed_plsc() < 0) return fail(DVBS2_EINVAL, "a handle without a fixed PLSC needs the per-slot PLSC array");
+    return impl_rc(h, h->impl->slots_device(d_slots, stride_syms, d_plsc, d_offsets, n_streams, plcoarse_out(d_coarse_foffset, d_coarse_corrected, d_new_est),
+                                            (hipStream_t)stream));
     API_CATCH
 }
 

@@ -145,6 +145,40 @@ int dvbs2_plframe_process_device(dvbs2_plframe_t* h, const float* d_plframes, in
     API_CATCH
 }
 
+/* ---- one slot per frame (what dvbs2_plsync_batch_gather_device writes): frame f at f * stride_syms with its next header behind it */
+int dvbs2_plframe_stride_check(int plsc, int64_t stride_syms)
+{
+    if (plsc < 0 || plsc > 127) return fail(DVBS2_EINVAL, "plsc out of range (0..127)");
+    if (stride_syms < (int64_t)pl_frame_shape(plsc).plframe_len + 90) return fail(DVBS2_EINVAL, "stride_syms below plframe_len + 90");
+    if (stride_syms > INT32_MAX) return fail(DVBS2_EINVAL, "stride_syms above 2^31 - 1");
+    return DVBS2_OK;
+}
+
+int dvbs2_plframe_estimate_strided_device(dvbs2_plframe_t* h, const float* d_slots, int64_t stride_syms, int n_frames,
+                                          const int32_t* d_coarse_corrected, const float* d_coarse_foffset,
+                                          const dvbs2_plframe_estimates_t* d_est, void* stream)
+{
+    API_TRY
+    if (int rc = plframe_check(h, d_slots, n_frames, d_coarse_corrected, d_coarse_foffset)) return rc;
+    if (int rc = dvbs2_plframe_stride_check(h->impl->pls().plsc, stride_syms)) return rc;
+    return impl_rc(h, h->impl->run_strided_device(d_slots, (int)stride_syms, n_frames, d_coarse_corrected, d_coarse_foffset, nullptr, plframe_est(d_est),
+                                                  (hipStream_t)stream));
+    API_CATCH
+}
+
+int dvbs2_plframe_process_strided_device(dvbs2_plframe_t* h, const float* d_slots, int64_t stride_syms, int n_frames,
+                                         const int32_t* d_coarse_corrected, const float* d_coarse_foffset, float* d_xfecframes,
+                                         const dvbs2_plframe_estimates_t* d_est, void* stream)
+{
+    API_TRY
+    if (int rc = plframe_check(h, d_slots, n_frames, d_coarse_corrected, d_coarse_foffset)) return rc;
+    if (int rc = dvbs2_plframe_stride_check(h->impl->pls().plsc, stride_syms)) return rc;
+    if (n_frames && !d_xfecframes) return fail(DVBS2_EINVAL, "bad argument");
+    return impl_rc(h, h->impl->run_strided_device(d_slots, (int)stride_syms, n_frames, d_coarse_corrected, d_coarse_foffset, d_xfecframes,
+                                                  plframe_est(d_est), (hipStream_t)stream));
+    API_CATCH
+}
+
 int dvbs2_plframe_estimate(dvbs2_plframe_t* h, const float* plframes, int n_frames, int has_trailing_header,
                            const int32_t* coarse_corrected, const float* coarse_foffset, const dvbs2_plframe_estimates_t* est)
 {

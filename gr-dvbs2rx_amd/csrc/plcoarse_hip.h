@@ -21,6 +21,7 @@
 #include <string>
 #include "device_stage.h"
 #include "plsync_hip.h"
+#include "plsync_batch_hip.h"
 
 namespace dvbs2 {
 
@@ -65,6 +66,36 @@ private:
     float* d_w_ = nullptr;       // 89 + 25 window weights
     float2* d_r_ = nullptr;      // max_frames * kPlcoarseRecord
     PlCoarseState* d_state_ = nullptr;
+};
+
+// host only: empty when the arguments of a batch create are in range, else what is wrong (always an argument error)
+std::string plcoarse_batch_check(int period, int plsc_or_minus1, int max_streams, int max_slots);
+
+// The same estimate for the slots PlSyncBatchHip::gather_device writes (plsync_batch_hip.h): one PlCoarseState per stream. The
+// autocorrelation runs over every slot; stream s's wavefront walks slots d_offsets[s] .. d_offsets[s + 1] in order, so its outputs
+// are the bits a PlCoarseHip of its own gives for those slots. d_offsets is read on the device: no host round trip lies between
+// gather and estimate. Slots at or beyond max_slots are not looked at (gather has not written them).
+class PlCoarseBatchHip : public DeviceStage {
+public:
+    // the ranges of the arguments are checked by dvbs2_plcoarse_batch_create (plcoarse_batch_check), which alone constructs this
+    PlCoarseBatchHip(int period, int plsc_or_minus1, int max_streams, int max_slots, int device);
+    int max_streams() const { return max_streams_; }
+    int max_slots() const { return max_slots_; }
+    int fixed_plsc() const { return fixed_plsc_; }
+    int reset();
+    int reset_stream(int s);
+    // DEVICE pointers. Slot i starts at d_slots + 2 * i * stride_syms floats; d_plsc: one byte per slot, or null for the handle's
+    // fixed PLSC; d_offsets: n_streams + 1 int32 prefix sums; the outputs are per slot
+    int slots_device(const float* d_slots, int64_t stride_syms, const uint8_t* d_plsc, const int32_t* d_offsets, int n_streams, const PlCoarseOut& out,
+                     hipStream_t stream);
+
+private:
+    int clear(int first_stream, int count);
+    int period_, fixed_plsc_, max_streams_, max_slots_;
+    uint64_t* d_cw_ = nullptr;   // 128 scrambled PLSC codewords
+    float* d_w_ = nullptr;       // 89 + 25 window weights
+    float2* d_r_ = nullptr;      // max_slots * kPlcoarseRecord
+    PlCoarseState* d_state_ = nullptr; // [max_streams]
 };
 
 } // namespace dvbs2

@@ -39,12 +39,15 @@ template <int N> __device__ inline void lag_pair(float2 z0, float2 z1, int l, fl
     *a = sa; *b = sb;
 }
 
-// one wavefront per header; r: kPlcoarseRecord float2 per frame, [0].x = 1 when the record holds a frame
+// one wavefront per header; r: kPlcoarseRecord float2 per frame, [0].x = 1 when the record holds a frame. total (nullable): the number
+// of frames there really are, on the device; a wavefront at or beyond it leaves at once
 __global__ __launch_bounds__(64) void plcoarse_autocorr_kernel(const float2* __restrict__ x, long long stride, const uint8_t* __restrict__ plsc,
                                                                int fixed_plsc, const PlSyncFrame* __restrict__ rec, int n_syms, long long base,
-                                                               const uint64_t* __restrict__ cwtab, float2* __restrict__ r)
+                                                               const uint64_t* __restrict__ cwtab, float2* __restrict__ r,
+                                                               const int32_t* __restrict__ total)
 {
     const int f = blockIdx.x, l = threadIdx.x;
+    if (total && f >= *total) return;
     float2* __restrict__ R = r + (size_t)f * kPlcoarseRecord;
     const float2* __restrict__ h;
     int p;
@@ -72,9 +75,9 @@ __global__ __launch_bounds__(64) void plcoarse_autocorr_kernel(const float2* __r
     if (l == 0) { R[0] = make_float2(1.0f, 0.0f); R[90] = make_float2(0.0f, 0.0f); }
 }
 
-// one wavefront; lane l holds lags l + 1 and l + 65
-__global__ __launch_bounds__(64) void plcoarse_window_kernel(const float2* __restrict__ r, int n_frames, int period, int always_full,
-                                                             const float* __restrict__ w, PlCoarseState* __restrict__ st, PlCoarseOut out)
+// one wavefront walks n_frames records in order over one state; lane l holds lags l + 1 and l + 65
+__device__ inline void window_walk(const float2* __restrict__ r, int n_frames, int period, int always_full, const float* __restrict__ w,
+                                   PlCoarseState* __restrict__ st, PlCoarseOut out)
 {
     const int l = threadIdx.x;
     const bool hi = l < 25; // the lane has a second lag (full form) / a lag at all (SOF form)
@@ -133,6 +136,27 @@ __global__ __launch_bounds__(64) void plcoarse_window_kernel(const float2* __res
     if (l == 0) { st->i_frame = i_frame; st->corrected = corrected; st->foffset = fo; }
 }
 
+__global__ __launch_bounds__(64) void plcoarse_window_kernel(const float2* __restrict__ r, int n_frames, int period, int always_full,
+                                                             const float* __restrict__ w, PlCoarseState* __restrict__ st, PlCoarseOut out)
+{
+    window_walk(r, n_frames, period, always_full, w, st, out);
+}
+
+// one wavefront per stream: stream s walks slots offsets[s] .. offsets[s + 1] (below max_slots) over its own state
+__global__ __launch_bounds__(64) void plcoarse_batch_window_kernel(const float2* __restrict__ r, const int32_t* __restrict__ offsets, int max_slots,
+                                                                   int period, int always_full, const float* __restrict__ w,
+                                                                   PlCoarseState* __restrict__ st, PlCoarseOut out)
+{
+    const int s = blockIdx.x;
+    const int a = offsets[s] < max_slots ? offsets[s] : max_slots, b = offsets[s + 1] < max_slots ? offsets[s + 1] : max_slots;
+    if (b <= a) return; // uniform: the stream has no slot in this call, its state stays
+    PlCoarseOut o;
+    o.foffset = out.foffset ? out.foffset + a : nullptr;
+    o.corrected = out.corrected ? out.corrected + a : nullptr;
+    o.new_est = out.new_est ? out.new_est + a : nullptr;
+    window_walk(r + (size_t)a * kPlcoarseRecord, b - a, period, always_full, w, st + s, o);
+}
+
 } // namespace
 
 PlCoarseHip::PlCoarseHip(int period, int plsc_or_minus1, int max_frames, int device)
@@ -169,7 +193,7 @@ int PlCoarseHip::launch(const float2* x, int64_t stride, const uint8_t* plsc, co
     if (n_frames < 0 || n_frames > max_frames_) { call_err_.device("n_frames exceeds max_frames"); return -1; } // (argument text, kDevice: notes/stage_error_codes.md)
     if (n_frames == 0) return 0;
     hipLaunchKernelGGL(plcoarse_autocorr_kernel, dim3(n_frames), dim3(64), 0, stream, x, (long long)stride, plsc, fixed_plsc_ < 0 ? 0 : fixed_plsc_,
-                       rec, n_syms, (long long)base, d_cw_, d_r_);
+                       rec, n_syms, (long long)base, d_cw_, d_r_, nullptr);
     if (launched("plcoarse autocorrelation kernel launch")) return -1;
     hipLaunchKernelGGL(plcoarse_window_kernel, dim3(1), dim3(64), 0, stream, d_r_, n_frames, period_, fixed_plsc_ >= 0 ? 1 : 0, d_w_, d_state_, out);
     return launched("plcoarse window kernel launch");
@@ -185,6 +209,70 @@ int PlCoarseHip::records_device(const float* d_syms, int n_syms, const PlSyncFra
                                 hipStream_t stream)
 {
     return launch(reinterpret_cast<const float2*>(d_syms), 0, nullptr, d_records, n_syms, base, n_frames, out, stream);
+}
+
+} // namespace dvbs2
+
+namespace dvbs2 {
+
+std::string plcoarse_batch_check(int period, int plsc_or_minus1, int max_streams, int max_slots)
+{
+    if (period < 1) return "period must be at least 1";
+    if (plsc_or_minus1 < -1 || plsc_or_minus1 > 127) return "plsc out of range (-1 = not known, 0..127)";
+    if (max_streams < 1 || max_streams > kPlsyncBatchMaxStreams) return "max_streams out of range (1..1024)";
+    if (max_slots < 1 || max_slots > (1 << 20)) return "max_slots out of range (1..1048576)";
+    return std::string();
+}
+
+PlCoarseBatchHip::PlCoarseBatchHip(int period, int plsc_or_minus1, int max_streams, int max_slots, int device)
+    : DeviceStage(device), period_(period), fixed_plsc_(plsc_or_minus1), max_streams_(max_streams), max_slots_(max_slots)
+{
+    if (const std::string bad = plcoarse_batch_check(period, plsc_or_minus1, max_streams, max_slots); !bad.empty()) { err_.argument(bad); return; }
+    uint64_t cw[128];
+    for (int p = 0; p < 128; p++) cw[p] = plsc_codeword(p) ^ kPlscScrambler;
+    float w[89 + 25];
+    plcoarse_weights(1, w); plcoarse_weights(0, w + 89);
+    DeviceGuard dev_guard(device_);
+    if (!dev_guard.ok || alloc(&d_cw_, 128) != hipSuccess || alloc(&d_w_, 89 + 25) != hipSuccess ||
+        alloc(&d_r_, (size_t)max_slots_ * kPlcoarseRecord) != hipSuccess || alloc(&d_state_, (size_t)max_streams_) != hipSuccess ||
+        hipMemcpy(d_cw_, cw, sizeof(cw), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_w_, w, sizeof(w), hipMemcpyHostToDevice) != hipSuccess) {
+        err_.argument("device setup failed"); return; // (device failure, kArgument: notes/stage_error_codes.md)
+    }
+    if (reset()) { err_.argument(call_err_.text); call_err_ = {}; } // (device failure, kArgument: notes/stage_error_codes.md)
+}
+
+int PlCoarseBatchHip::clear(int first_stream, int count)
+{
+    Entry on(*this);
+    // all zero, as PlCoarseHip::reset, for these streams only
+    if (!on.ok || hipDeviceSynchronize() != hipSuccess || memset_done(d_state_ + first_stream, 0, (size_t)count * sizeof(PlCoarseState)) != hipSuccess) {
+        call_err_.device("reset of the device state failed"); return -1;
+    }
+    return 0;
+}
+
+int PlCoarseBatchHip::reset() { return clear(0, max_streams_); }
+
+int PlCoarseBatchHip::reset_stream(int s)
+{
+    if (s < 0 || s >= max_streams_) { call_err_.argument("stream index out of range"); return -1; }
+    return clear(s, 1);
+}
+
+int PlCoarseBatchHip::slots_device(const float* d_slots, int64_t stride_syms, const uint8_t* d_plsc, const int32_t* d_offsets, int n_streams,
+                                   const PlCoarseOut& out, hipStream_t stream)
+{
+    Entry on(*this);
+    if (!on.ok) return -1;
+    if (n_streams < 0 || n_streams > max_streams_) { call_err_.device("n_streams exceeds max_streams"); return -1; } // (argument text, kDevice: notes/stage_error_codes.md)
+    if (n_streams == 0) return 0;
+    // over max_slots: the count is on the device, wavefronts at or beyond d_offsets[n_streams] leave at once
+    hipLaunchKernelGGL(plcoarse_autocorr_kernel, dim3(max_slots_), dim3(64), 0, stream, reinterpret_cast<const float2*>(d_slots), (long long)stride_syms, d_plsc,
+                       fixed_plsc_ < 0 ? 0 : fixed_plsc_, nullptr, 0, 0ll, d_cw_, d_r_, d_offsets + n_streams);
+    if (launched("plcoarse autocorrelation kernel launch")) return -1;
+    hipLaunchKernelGGL(plcoarse_batch_window_kernel, dim3(n_streams), dim3(64), 0, stream, d_r_, d_offsets, max_slots_, period_, fixed_plsc_ >= 0 ? 1 : 0,
+                       d_w_, d_state_, out);
+    return launched("plcoarse batch window kernel launch");
 }
 
 } // namespace dvbs2

@@ -48,8 +48,14 @@ public:
     // only): n_frames * xfecframe_len complex.
     int run_device(const float* d_plframes, int n_frames, int has_trailing_header, const int32_t* d_coarse_corrected,
                    const float* d_coarse_foffset, float* d_out, const PlFrameEstimates& est, hipStream_t stream);
+    // the same with frame f in a slot of its own at d_slots + 2 * f * stride_syms floats, stride_syms >= plframe_len + 90: the frame and
+    // the 90 symbols that follow it in its stream (what PlSyncBatchHip::gather_device writes), so every frame has its true next header
+    int run_strided_device(const float* d_slots, int stride_syms, int n_frames, const int32_t* d_coarse_corrected, const float* d_coarse_foffset,
+                           float* d_out, const PlFrameEstimates& est, hipStream_t stream);
 
 private:
+    int launch(const float* d_plframes, int stride_syms, int n_frames, int has_trailing_header, const int32_t* d_coarse_corrected,
+               const float* d_coarse_foffset, float* d_out, const PlFrameEstimates& est, hipStream_t stream);
     PlsInfo pls_{};
     int max_frames_;
     PlPayloadHip* pp_ = nullptr; // owns the Rn table and the payload kernel launch

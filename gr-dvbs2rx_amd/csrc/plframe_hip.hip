@@ -30,8 +30,8 @@ __device__ inline void header_sums(const float2* __restrict__ x, int l, uint64_t
     *last36 = make_float2(wave_sum((in_last ? t0.x : 0.0f) + t1.x), wave_sum((in_last ? t0.y : 0.0f) + t1.y));
 }
 
-// one wavefront per frame
-__global__ __launch_bounds__(64) void pl_estimate_kernel(const float2* __restrict__ in, const uint8_t* __restrict__ rn,
+// one wavefront per frame; frame f starts at in + f * stride (plframe_len: back to back; more: a slot with its own next header)
+__global__ __launch_bounds__(64) void pl_estimate_kernel(const float2* __restrict__ in, long long stride, const uint8_t* __restrict__ rn,
                                                          const uint8_t* __restrict__ rank, const int32_t* __restrict__ cc,
                                                          const float* __restrict__ cf, uint64_t hdr_cw, int plframe_len, int n_pilots,
                                                          int n_frames, int has_trailing, int coherent, int soft,
@@ -39,7 +39,7 @@ __global__ __launch_bounds__(64) void pl_estimate_kernel(const float2* __restric
                                                          PlFrameEstimates est)
 {
     const int f = blockIdx.x, l = threadIdx.x;
-    const float2* __restrict__ x = in + (size_t)f * plframe_len;
+    const float2* __restrict__ x = in + (size_t)f * (size_t)stride;
 
     float2 sof, hdr, last36;
     header_sums(x, l, hdr_cw, &sof, &hdr, &last36);
@@ -130,17 +130,30 @@ int PlscListStage::set_expected_pls(const uint8_t* list, int n)
 int PlFrameHip::run_device(const float* d_plframes, int n_frames, int has_trailing_header, const int32_t* d_coarse_corrected,
                            const float* d_coarse_foffset, float* d_out, const PlFrameEstimates& est, hipStream_t stream)
 {
+    return launch(d_plframes, pls_.plframe_len, n_frames, has_trailing_header, d_coarse_corrected, d_coarse_foffset, d_out, est, stream);
+}
+
+int PlFrameHip::run_strided_device(const float* d_slots, int stride_syms, int n_frames, const int32_t* d_coarse_corrected,
+                                   const float* d_coarse_foffset, float* d_out, const PlFrameEstimates& est, hipStream_t stream)
+{
+    if (stride_syms < pls_.plframe_len + 90) { call_err_.argument("stride below plframe_len + 90"); return -1; }
+    return launch(d_slots, stride_syms, n_frames, 1, d_coarse_corrected, d_coarse_foffset, d_out, est, stream); // every slot has its next header
+}
+
+int PlFrameHip::launch(const float* d_plframes, int stride_syms, int n_frames, int has_trailing_header, const int32_t* d_coarse_corrected,
+                       const float* d_coarse_foffset, float* d_out, const PlFrameEstimates& est, hipStream_t stream)
+{
     Entry on(*this);
     if (!on.ok) return -1;
     if (n_frames < 0 || n_frames > max_frames_) { call_err_.device("n_frames exceeds max_frames"); return -1; } // (argument text, kDevice: notes/stage_error_codes.md)
     if (n_frames == 0) return 0;
     float* d_hph = d_par_; float* d_inc = d_par_ + max_frames_; float* d_pil = d_par_ + 2 * (size_t)max_frames_;
-    hipLaunchKernelGGL(pl_estimate_kernel, dim3(n_frames), dim3(64), 0, stream, reinterpret_cast<const float2*>(d_plframes), pp_->d_rn(),
-                       d_rank_, d_coarse_corrected, d_coarse_foffset, plsc_codeword(pls_.plsc) ^ kPlscScrambler, pls_.plframe_len,
+    hipLaunchKernelGGL(pl_estimate_kernel, dim3(n_frames), dim3(64), 0, stream, reinterpret_cast<const float2*>(d_plframes), (long long)stride_syms,
+                       pp_->d_rn(), d_rank_, d_coarse_corrected, d_coarse_foffset, plsc_codeword(pls_.plsc) ^ kPlscScrambler, pls_.plframe_len,
                        pls_.n_pilots, n_frames, has_trailing_header ? 1 : 0, coherent_, soft_, d_hph, d_inc, d_pil, est);
     if (launched("pl estimate kernel launch")) return -1;
     if (!d_out) return 0;
-    if (!pp_->process_device_strided(d_plframes, pls_.plframe_len, 90, n_frames, d_hph, d_inc, d_coarse_corrected, d_pil, d_out, stream)) return 0;
+    if (!pp_->process_device_strided(d_plframes, stride_syms, 90, n_frames, d_hph, d_inc, d_coarse_corrected, d_pil, d_out, stream)) return 0;
     call_err_ = { pp_->error_code(), pp_->error() }; // what the payload stage recorded
     return -1;
 }

@@ -16,7 +16,7 @@ from .capi import lib, check
 __all__ = ["get_fec_info", "rate_id", "LdpcDecoder", "BchDecoder", "Demapper", "FecChain", "BbDeheader", "ldpc_table_info", "ldpc_layer_info",
            "ldpc_table_names", "bb_descramble_sequence", "PlPayload",
            "pl_scrambling_rn", "HostBuffer", "PlFrontEnd", "plheader_symbols", "pls_parse", "apsk_points", "demap_table_check",
-           "PlSync", "plsync_taps", "plsync_thresholds", "PlCoarse", "plcoarse_weights", "Agc", "agc_check", "Awgn", "awgn_sigma", "awgn_words",
+           "PlSync", "plsync_taps", "plsync_thresholds", "PlCoarse", "plcoarse_weights", "PlSyncBatch", "PlCoarseBatch", "plsync_batch_check", "Agc", "agc_check", "Awgn", "awgn_sigma", "awgn_words",
            "awgn_sample", "awgn_check", "IqConverter", "IQ_FORMATS", "iqconv_bytes", "iqconv_check", "iqconv_unpack_host", "iqconv_pack_host",
            "Rotator",
            "SymbolSync", "symsync_loop_constants", "symsync_geometry", "symsync_taps", "FecEncoder", "enc_check",
@@ -483,6 +483,21 @@ class PlFrontEnd(_Handle):
                                         cf.ctypes.data if cf is not None else None, out.ctypes.data, C.byref(e)))
         return out, arrs
 
+    def estimate_strided_device(self, d_slots, stride_syms, n_frames, d_coarse_corrected, d_coarse_foffset=0, stream=0, **d_est):
+        """DEVICE addresses, asynchronous on `stream`: the estimates of work_strided_device() without the payload step."""
+        self.work_strided_device(d_slots, stride_syms, n_frames, d_coarse_corrected, d_coarse_foffset, 0, stream, **d_est)
+
+    def work_strided_device(self, d_slots, stride_syms, n_frames, d_coarse_corrected, d_coarse_foffset=0, d_xfecframes=0, stream=0, **d_est):
+        """DEVICE addresses, asynchronous on `stream`: frame f in a slot of its own at symbol f * stride_syms, followed there by its
+        next header (stride_syms >= plframe_len + 90; what PlSyncBatch.gather_device writes). d_xfecframes = 0: estimates only."""
+        e = capi.PlFrameEstimates(**{k: (v or None) for k, v in d_est.items()})
+        if d_xfecframes:
+            check(lib.dvbs2_plframe_process_strided_device(self._h, d_slots, int(stride_syms), int(n_frames), d_coarse_corrected,
+                                                           d_coarse_foffset or None, d_xfecframes, C.byref(e), stream or None))
+        else:
+            check(lib.dvbs2_plframe_estimate_strided_device(self._h, d_slots, int(stride_syms), int(n_frames), d_coarse_corrected,
+                                                            d_coarse_foffset or None, C.byref(e), stream or None))
+
     def work_device(self, d_plframes, n_frames, has_trailing_header, d_coarse_corrected, d_coarse_foffset=0, d_xfecframes=0,
                     stream=0, **d_est):
         """DEVICE addresses, asynchronous on `stream`; d_xfecframes = 0: estimates only. d_est: addresses by field name."""
@@ -627,6 +642,99 @@ class PlCoarse(_Handle):
         PlSync.work_device left for it."""
         check(lib.dvbs2_plcoarse_estimate_records_device(self._h, d_syms, int(n_syms), int(base_index), d_frames, int(n_frames),
                                                          d_coarse_foffset or None, d_coarse_corrected or None, d_new_est or None, stream or None))
+
+
+def plsync_batch_check(plsc=-1, unlock_thresh=3, max_streams=1, max_symbols=1 << 20, max_frames=1024):
+    """Raises Dvbs2Error (EINVAL, the text names the argument) for arguments a PlSyncBatch refuses. Host only."""
+    check(lib.dvbs2_plsync_batch_check(int(plsc), int(unlock_thresh), int(max_streams), int(max_symbols), int(max_frames)))
+
+
+def _stream_ints(v, n_streams, name):
+    a = np.ascontiguousarray(v, np.int32).reshape(-1)
+    if a.size != n_streams:
+        raise ValueError(f"{name}: one integer per stream ({n_streams}), got {a.size}")
+    return a
+
+
+class PlSyncBatch(_Handle):
+    """PlSync for a batch of independent symbol streams in one handle: one tracker, with its own state and history, per stream, and
+    the launches of one search for any number of streams. Stream s of a batch gives the bits a PlSync of its own gives. The gather
+    step writes SLOTS of plframe_len + 90 symbols -- a frame and the header that follows it in its own stream -- which
+    PlCoarseBatch and PlFrontEnd.work_strided_device read; slots of all streams share one launch of each."""
+    _destroy = lib.dvbs2_plsync_batch_destroy
+
+    FRAME_DTYPE = PlSync.FRAME_DTYPE
+    MIN_SYMBOLS = PlSync.MIN_SYMBOLS
+    MAX_STREAMS = 1024
+
+    def __init__(self, plsc=-1, unlock_thresh=3, max_streams=1, max_symbols=1 << 20, max_frames=1024, device=0, coherent=True, soft=True,
+                 expected_pls=None):
+        """max_symbols and max_frames are per stream. plsc = -1: decode the PLSC of every header; 0..127: the fixed-PLSC mode."""
+        check(lib.dvbs2_plsync_batch_create(C.byref(self._h), int(plsc), int(unlock_thresh), int(max_streams), int(max_symbols), int(max_frames),
+                                            device))
+        self.plsc, self.unlock_thresh, self.max_streams, self.max_symbols, self.max_frames = plsc, unlock_thresh, max_streams, max_symbols, max_frames
+        self.set_plsc_mode(coherent, soft)
+        if expected_pls is not None:
+            self.set_expected_pls(expected_pls)
+
+    def reset(self):
+        check(lib.dvbs2_plsync_batch_reset(self._h))
+
+    def reset_stream(self, stream_index):
+        check(lib.dvbs2_plsync_batch_reset_stream(self._h, int(stream_index)))
+
+    def set_plsc_mode(self, coherent=True, soft=True):
+        check(lib.dvbs2_plsync_batch_set_plsc_mode(self._h, int(bool(coherent)), int(bool(soft))))
+
+    def set_expected_pls(self, plsc_list):
+        """The enabled-codeword list, in the given order (empty: all 128)."""
+        lst = np.asarray(plsc_list)
+        if lst.size and (lst.dtype.kind not in "iu" or lst.min() < 0 or lst.max() > 127):
+            raise ValueError("expected_pls: integers in 0..127")
+        lst = np.ascontiguousarray(lst, np.uint8)
+        check(lib.dvbs2_plsync_batch_set_expected_pls(self._h, _ptr(lst), int(lst.size)))
+
+    def work_device(self, d_syms, stride_syms, first, n_syms, d_frames, stream=0):
+        """DEVICE addresses, asynchronous on `stream`. first, n_syms: one integer per stream (host); stream s reads n_syms[s] symbols
+        from symbol s * stride_syms + first[s] of d_syms. d_frames: [n_streams, max_frames] records of FRAME_DTYPE."""
+        n = _stream_ints(n_syms, np.size(n_syms), "n_syms")
+        f = _stream_ints(first, n.size, "first")
+        self._n_streams = int(n.size)
+        check(lib.dvbs2_plsync_batch_search_device(self._h, d_syms, int(stride_syms), f.ctypes.data, n.ctypes.data, int(n.size), d_frames, stream or None))
+
+    def finish(self):
+        """Waits for the last work_device(); returns (n_frames, consumed, state), each an int32 array over its streams."""
+        v = [np.zeros(getattr(self, "_n_streams", 0), np.int32) for _ in range(3)]
+        check(lib.dvbs2_plsync_batch_finish(self._h, *[a.ctypes.data for a in v]))
+        return tuple(v)
+
+    def gather_device(self, d_syms, stride_syms, d_frames, n_streams, wanted_plsc, d_slots, max_slots, d_offsets, d_slot_record=0, stream=0):
+        """DEVICE addresses: the locked frames of wanted_plsc of the LAST work_device(), each with the 90 symbols behind it, into
+        slots of plframe_len + 90 symbols, stream-major; d_offsets: n_streams + 1 int32 prefix sums of the true counts; slots at or
+        beyond max_slots are not written; d_slot_record: per slot (stream, record index) as two int32, or 0."""
+        check(lib.dvbs2_plsync_batch_gather_device(self._h, d_syms, int(stride_syms), d_frames, int(n_streams), int(wanted_plsc), d_slots or None,
+                                                   int(max_slots), d_offsets, d_slot_record or None, stream or None))
+
+
+class PlCoarseBatch(_Handle):
+    """PlCoarse over the slots of PlSyncBatch.gather_device: one window state per stream, the slot ranges read from d_offsets on the
+    device. Outputs per slot, the arrays PlFrontEnd.work_strided_device reads; stream s's are the bits a PlCoarse of its own gives."""
+    _destroy = lib.dvbs2_plcoarse_batch_destroy
+
+    def __init__(self, period=1, plsc=-1, max_streams=1, max_slots=1024, device=0):
+        check(lib.dvbs2_plcoarse_batch_create(C.byref(self._h), int(period), int(plsc), int(max_streams), int(max_slots), device))
+        self.period, self.plsc, self.max_streams, self.max_slots = period, plsc, max_streams, max_slots
+
+    def reset(self):
+        check(lib.dvbs2_plcoarse_batch_reset(self._h))
+
+    def reset_stream(self, stream_index):
+        check(lib.dvbs2_plcoarse_batch_reset_stream(self._h, int(stream_index)))
+
+    def work_device(self, d_slots, stride_syms, d_offsets, n_streams, d_plsc=0, d_coarse_foffset=0, d_coarse_corrected=0, d_new_est=0, stream=0):
+        """DEVICE addresses, asynchronous on `stream`: slot i starts at symbol i * stride_syms; d_plsc = 0: the fixed PLSC."""
+        check(lib.dvbs2_plcoarse_batch_estimate_device(self._h, d_slots, int(stride_syms), d_plsc or None, d_offsets, int(n_streams),
+                                                       d_coarse_foffset or None, d_coarse_corrected or None, d_new_est or None, stream or None))
 
 
 def agc_check(rate, reference, gain, max_gain):

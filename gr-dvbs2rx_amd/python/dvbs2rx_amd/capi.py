@@ -370,11 +370,38 @@ SYMBOLS = {
     "dvbs2_plframer_frame": (_i, [_vp, _vp, _i, _i, _vp]),
 }
 
+# every symbol include/dvbs2_fec_hip_batch.h declares (the batched stages between the symbol synchroniser and the FEC chain), in a
+# table of its own as the header is a file of its own. SYMBOLS is also the census of two recorded tests -- the null-handle answers of
+# tests/test_capi_null_handle.py and the one row per handle type of tests/test_stream_order_gpu.py --; what is listed here has its
+# census in tests/test_plsync_batch_host.py (declared = bound = exported, the answer of every entry to a null handle) and
+# tests/test_plsync_batch_stream_gpu.py (a row on a busy non-blocking stream for every handle type and device entry).
+SYMBOLS_BATCH = {
+    "dvbs2_plsync_batch_check": (_i, [_i, _i, _i, _i, _i]),
+    "dvbs2_plsync_batch_check_search": (_i, [_i, _i, C.c_int64, _vp, _vp, _i]),
+    "dvbs2_plsync_batch_create": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i, _i]),
+    "dvbs2_plsync_batch_destroy": (None, [_vp]),
+    "dvbs2_plsync_batch_reset": (_i, [_vp]),
+    "dvbs2_plsync_batch_reset_stream": (_i, [_vp, _i]),
+    "dvbs2_plsync_batch_set_plsc_mode": (_i, [_vp, _i, _i]),
+    "dvbs2_plsync_batch_set_expected_pls": (_i, [_vp, _vp, _i]),
+    "dvbs2_plsync_batch_search_device": (_i, [_vp, _vp, C.c_int64, _vp, _vp, _i, _vp, _vp]),
+    "dvbs2_plsync_batch_finish": (_i, [_vp, _vp, _vp, _vp]),
+    "dvbs2_plsync_batch_gather_device": (_i, [_vp, _vp, C.c_int64, _vp, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "dvbs2_plframe_stride_check": (_i, [_i, C.c_int64]),
+    "dvbs2_plframe_estimate_strided_device": (_i, [_vp, _vp, C.c_int64, _i, _vp, _vp, _vp, _vp]),
+    "dvbs2_plframe_process_strided_device": (_i, [_vp, _vp, C.c_int64, _i, _vp, _vp, _vp, _vp, _vp]),
+    "dvbs2_plcoarse_batch_create": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i]),
+    "dvbs2_plcoarse_batch_destroy": (None, [_vp]),
+    "dvbs2_plcoarse_batch_reset": (_i, [_vp]),
+    "dvbs2_plcoarse_batch_reset_stream": (_i, [_vp, _i]),
+    "dvbs2_plcoarse_batch_estimate_device": (_i, [_vp, _vp, C.c_int64, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+}
+
 if not os.path.exists(LIB_PATH):
     raise ImportError(f"{LIB_PATH} not found: build it with `make -C gr-dvbs2rx_amd` "
                       "(or __graft_entry__.build()); there is no CPU fallback")
 lib = C.CDLL(LIB_PATH)
-for _name, (_res, _args) in SYMBOLS.items():
+for _name, (_res, _args) in {**SYMBOLS, **SYMBOLS_BATCH}.items():
     if os.environ.get("DVBS2_LIB") and not hasattr(lib, _name):
         continue  # kernel experiments against a library built from an older tree (tools/ab.sh); the product library must export all
     _fn = getattr(lib, _name)  # (not _f: that is the c_float alias SYMBOLS is written with)

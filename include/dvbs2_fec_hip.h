@@ -1390,4 +1390,8 @@ int dvbs2_crc8(const uint8_t* data, size_t n);
 #ifdef __cplusplus
 }
 #endif
+
+/* the batched stages between the symbol synchroniser and the FEC chain: search, gather, coarse estimate and front end for S streams */
+#include "dvbs2_fec_hip_batch.h"
+
 #endif /* DVBS2_FEC_HIP_H */

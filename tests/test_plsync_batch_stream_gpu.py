@@ -1,0 +1,231 @@
+"""The stream contract of the batched PL stages on a BUSY non-blocking stream: what tests/test_stream_order_gpu.py applies to every other
+stage (its docstring and notes/stream_order.md say how), for the handle types and device entries of include/dvbs2_fec_hip_batch.h.
+  A. search -> gather -> coarse estimate -> strided front end, enqueued back to back behind a hold with no host synchronisation, the
+     caller's first[] / n_syms[] arrays rewritten the moment the search returns, equal the same calls serialized;
+  B. the entries that wait (finish, reset, reset_stream of both handle types), called while work of the handle is pending, give what they
+     give in the serialized order.
+The machinery (Row, the serialized and the held pass, the comparison) is that file's. The expected value of a row is its serialized pass,
+and that pass is tied to the single-stream handles, which are the specification of the batched stages: every stream's records, counts and
+estimates are those of a PlSync / PlCoarse of its own (tests/plsync_batch_case.py), which their own tests tie to the float64 models."""
+import functools
+from types import SimpleNamespace as NS
+
+import numpy as np
+import pytest
+
+import fec_testlib as T
+import plframe_model as M
+import plsync_batch_case as B
+import test_stream_order_gpu as SO
+from dvbs2rx_amd import PlCoarse, PlCoarseBatch, PlFrontEnd, PlSync, capi
+
+pytestmark = pytest.mark.gpu
+
+STREAMS = (B.CLEAN_A, B.NOISE_ONLY, B.CLEAN_B)  # rows of the batch: two that give five slots each and one that gives none
+S = len(STREAMS)
+SLOTS = 10
+CUT = (34567, 20011, 35003)  # the first search of the rows that make two
+p, zeros, host = SO.p, SO.zeros, SO.host
+
+
+def lengths():
+    return [B.streams().n[s] for s in STREAMS]
+
+
+def prep(o):
+    c = B.streams()
+    xl = M.pls_parse(B.PLSC)["xfecframe_len"]
+    return NS(x=c.d_x[list(STREAMS)].contiguous(), stride=c.stride, rec=zeros(S * B.MAX_FRAMES * 16, "uint8"), slots=zeros(SLOTS * B.SLOT * 2),
+              off=zeros(S + 1, "int32"), sr=zeros(2 * SLOTS, "int32"), fo=zeros(SLOTS), cc=zeros(SLOTS, "int32"), ne=zeros(SLOTS, "int32"),
+              xfec=zeros(2 * SLOTS * xl), plsc=zeros(SLOTS, "uint8"), first=np.zeros(S, np.int32), n=np.zeros(S, np.int32), pos=[0] * S, said=[])
+
+
+def search(sizes=None):
+    """a search from every stream's own position, through the C entry with the caller's arrays, which are rewritten with other LEGAL
+    values the moment the call returns; sizes None: all that is left of every stream"""
+    def f(o, c, s):
+        ps = o[0] if isinstance(o, tuple) else o
+        left = [n - q for n, q in zip(lengths(), c.pos)]
+        c.first[:] = c.pos
+        c.n[:] = left if sizes is None else [min(a, b) for a, b in zip(sizes, left)]
+        rc = capi.lib.dvbs2_plsync_batch_search_device(ps._h, p(c.x), c.stride, c.first.ctypes.data, c.n.ctypes.data, S, p(c.rec), s or None)
+        ps._n_streams = S
+        c.first[:] = (5, 6, 7)
+        c.n[:] = (2, 3, 4)
+        assert rc == capi.OK
+    return f
+
+
+def finish(o, c, s):
+    ps = o[0] if isinstance(o, tuple) else o
+    nf, consumed, state = ps.finish()
+    c.pos = [q + int(k) for q, k in zip(c.pos, consumed)]
+    c.said.extend(np.concatenate([nf, consumed, state]).tolist())
+
+
+def chain_calls():
+    return [search(),
+            lambda o, c, s: o[0].gather_device(p(c.x), c.stride, p(c.rec), S, B.PLSC, p(c.slots), SLOTS, p(c.off), p(c.sr), s),
+            lambda o, c, s: o[1].work_device(p(c.slots), B.SLOT, p(c.off), S, 0, p(c.fo), p(c.cc), p(c.ne), s),
+            lambda o, c, s: o[2].work_strided_device(p(c.slots), B.SLOT, SLOTS, p(c.cc), p(c.fo), p(c.xfec), s, plsc_decoded=p(c.plsc))]
+
+
+def collect(o, c):
+    ps = o[0] if isinstance(o, tuple) else o
+    return dict(records=host(c.rec), finish=np.array(c.said + np.concatenate(ps.finish()).tolist(), np.int32), slots=host(c.slots), offsets=host(c.off),
+                slot_record=host(c.sr), foffset=host(c.fo), corrected=host(c.cc), new_est=host(c.ne), xfec=host(c.xfec), plsc=host(c.plsc))
+
+
+def single_calls(sizes):
+    """per stream of STREAMS the calls of a single-stream handle: whole, or a first call of sizes[i] and then the rest"""
+    c = B.streams()
+    out = []
+    for i, s in enumerate(STREAMS):
+        calls, ps, _ = B.run_single(c.d_x.data_ptr() + 8 * c.stride * s, c.n[s], None if sizes is None else (sizes[i], c.n[s]))
+        ps.close()
+        out.append(calls)
+    return out
+
+
+def records_model(sizes=None, last_only=True):
+    """the record buffer holds every stream's records of the LAST search, and finish() its counts: a single-stream handle's"""
+    def check(got):
+        want = single_calls(sizes)
+        recs = got["records"].reshape(S, B.MAX_FRAMES * 16)
+        for i in range(S):
+            n, b, nf, consumed, state = want[i][-1]
+            assert recs[i, :len(b)].tobytes() == b, f"stream {STREAMS[i]}: the serialized pass is not the single-stream handle"
+            assert got["finish"][-3 * S:].reshape(3, S)[:, i].tolist() == [nf, consumed, state]
+    return check
+
+
+def chain_model(got):
+    import torch
+    records_model()(got)
+    c = B.streams()
+    assert got["offsets"].tolist() == [0, 5, 5, 10] and got["slot_record"].reshape(SLOTS, 2)[:, 0].tolist() == [0] * 5 + [2] * 5
+    recs = got["records"].view(PlSync.FRAME_DTYPE).reshape(S, B.MAX_FRAMES)
+    slots = got["slots"].view(np.complex64).reshape(SLOTS, B.SLOT)
+    d_slots = SO.dev(slots)
+    fe = PlFrontEnd(B.GOLD, B.PLSC, max_frames=5)
+    for i, s in ((0, B.CLEAN_A), (2, B.CLEAN_B)):
+        a = got["offsets"][i]
+        for k in range(5):
+            f = int(got["slot_record"].reshape(SLOTS, 2)[a + k, 1])
+            sof = int(recs[i, f]["sof_index"])
+            assert f == (1, 3, 4, 6, 7)[k] and slots[a + k].tobytes()  # SEQ6: the data frames behind the lock, the dummy frames passed over == c.x[s, sof:sof + B.SLOT].tobytes()
+        pc = PlCoarse(1, B.PLSC, max_frames=5)
+        fo, cc, ne, xf = zeros(5), zeros(5, "int32"), zeros(5, "int32"), zeros(2 * 5 * fe.xfecframe_len)
+        pc.work_device(p(d_slots, a * B.SLOT), B.SLOT, 5, 0, p(fo), p(cc), p(ne), 0)
+        fe.work_strided_device(p(d_slots, a * B.SLOT), B.SLOT, 5, p(cc), p(fo), p(xf), 0)
+        torch.cuda.synchronize()
+        for name, w in (("foffset", fo), ("corrected", cc), ("new_est", ne)):
+            assert got[name][a:a + 5].tobytes() == host(w).tobytes(), f"{name} of stream {s} is not a single PlCoarse's"
+        assert got["xfec"].reshape(SLOTS, -1)[a:a + 5].tobytes() == host(xf).tobytes()
+        pc.close()
+    fe.close()
+    assert got["plsc"].tolist() == [B.PLSC] * SLOTS and got["corrected"].tolist() == [1] * SLOTS
+
+
+def make_chain():
+    return (B.make_batch(S), PlCoarseBatch(1, B.PLSC, max_streams=S, max_slots=SLOTS), PlFrontEnd(B.GOLD, B.PLSC, max_frames=SLOTS))
+
+
+def make_rows():
+    rows = {}
+
+    def add(name, handle, make, calls, model, check=None):
+        rows[name] = SO.Row(name, handle, make, prep, calls, collect, model, check)
+
+    add("plsync_batch-chain", ("plsync_batch", "plcoarse_batch", "plframe"), make_chain, chain_calls(), chain_model)
+    # B: finish between two searches; the second starts where the first said
+    add("plsync_batch-finish", "plsync_batch", lambda: B.make_batch(S), [search(CUT), ("wait", finish), search()], records_model(CUT))
+
+    def reset(o, c, s):
+        o.reset()
+        c.pos = [0] * S
+
+    def reset_stream(o, c, s):
+        o.reset_stream(2)
+        c.pos = [c.pos[0], c.pos[1], 0]
+
+    # a search, the reset, then every whole stream from its start: the records of a fresh handle
+    add("plsync_batch-reset", "plsync_batch", lambda: B.make_batch(S), [search(CUT), ("wait", reset), search()], records_model())
+
+    def one_stream_model(got):
+        # stream 2 behind its own reset: a fresh handle over the whole stream; stream 0 went on where its first call ended
+        whole, cut = single_calls(None), single_calls(CUT)
+        recs = got["records"].reshape(S, B.MAX_FRAMES * 16)
+        assert recs[2, :len(whole[2][-1][1])].tobytes() == whole[2][-1][1] and recs[0, :len(cut[0][-1][1])].tobytes() == cut[0][-1][1]
+        assert got["finish"][-3 * S:].reshape(3, S)[:, 2].tolist() == list(whole[2][-1][2:])
+
+    def consumed_then_reset_stream(o, c, s):
+        finish(o, c, s)
+        reset_stream(o, c, s)
+
+    add("plsync_batch-reset_stream", "plsync_batch", lambda: B.make_batch(S), [search(CUT), ("wait", consumed_then_reset_stream), search()], one_stream_model)
+
+    # the coarse handle: the chain, a reset (of all, of one stream), the estimate again over the same slots: the bits in front of the reset
+    def coarse_again(which):
+        def wait(o, c, s):
+            o[1].reset() if which is None else o[1].reset_stream(which)
+        return wait
+
+    def coarse_check(which):
+        def check(got):
+            # period 1 with a known PLSC: every slot is a window of its own, so the estimate does not depend on the state in front of it;
+            # what the row shows is that the reset waited for the pending estimate and did not disturb the next
+            assert got["new_est"].tolist() == [1] * SLOTS
+        return check
+
+    for name, which in (("plcoarse_batch-reset", None), ("plcoarse_batch-reset_stream", 2)):
+        add(name, ("plsync_batch", "plcoarse_batch", "plframe"), make_chain, chain_calls()[:3] + [("wait", coarse_again(which))] + chain_calls()[2:],
+            chain_model, coarse_check(which))
+    return rows
+
+
+@functools.lru_cache(None)
+def all_rows():
+    return make_rows()
+
+
+ROW_NAMES = ["plsync_batch-chain", "plsync_batch-finish", "plsync_batch-reset", "plsync_batch-reset_stream", "plcoarse_batch-reset",
+             "plcoarse_batch-reset_stream"]
+
+
+@functools.lru_cache(None)
+def reference(name):
+    """as test_stream_order_gpu.reference: the serialized pass twice, the first checked against the model"""
+    row = all_rows()[name]
+    want, _ = SO.run_serialized(row)
+    row.model(want)
+    if row.check is not None:
+        row.check(want)
+    again, spent = SO.run_serialized(row)
+    SO.same(again, want, f"{name}: the serialized pass, repeated")
+    return want, spent * 1e3
+
+
+@pytest.mark.parametrize("name", ROW_NAMES)
+def test_pending_calls_equal_the_serialized_ones(name):
+    want, host_ms = reference(name)
+    hold_ms = T.hold_for(host_ms)
+    print(f"stream-order: {name}: host side of the enqueues {host_ms:.3f} ms, hold {hold_ms:.0f} ms")
+    row = all_rows()[name]
+    got = SO.run_held(row, T.side_stream(), hold_ms)
+    if row.check is not None:
+        row.check(got)
+    SO.same(got, want, f"{name}: behind a hold")
+
+
+def test_every_batched_handle_and_device_entry_has_its_row():
+    """the census tests/test_stream_order_gpu.py keeps for capi.SYMBOLS, for capi.SYMBOLS_BATCH"""
+    rows = all_rows()
+    assert sorted(rows) == sorted(ROW_NAMES)
+    types = {name[len("dvbs2_"):-len("_destroy")] for name in capi.SYMBOLS_BATCH if name.endswith("_destroy")}
+    assert types == {"plsync_batch", "plcoarse_batch"} <= set().union(*(SO.handles_of(r) for r in rows.values()))
+    waiting = {"plsync_batch finish", "plsync_batch reset", "plsync_batch reset_stream", "plcoarse_batch reset", "plcoarse_batch reset_stream"}
+    assert {n.replace("-", " ") for n in ROW_NAMES if rows[n].waits} == waiting
+    device = {n for n in capi.SYMBOLS_BATCH if n.endswith("_device")}
+    assert device == {"dvbs2_plsync_batch_search_device", "dvbs2_plsync_batch_gather_device", "dvbs2_plcoarse_batch_estimate_device",
+                      "dvbs2_plframe_estimate_strided_device", "dvbs2_plframe_process_strided_device"}  # the chain row calls the first three and the last
