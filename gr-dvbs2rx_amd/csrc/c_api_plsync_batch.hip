@@ -1,4 +1,4 @@
-// c_api_plsync_batch.hip -- extern "C" boundary (include/dvbs2_fec_hip_batch.h): the PLFRAME search for a batch of streams.
+// c_api_plsync_batch.hip -- extern "C" boundary (include/dvbs2_fec_hip.h, the batched stages): the PLFRAME search for a batch of streams.
 #include "c_api_common.h"
 #include "plsync_batch_hip.h"
 

@@ -86,16 +86,6 @@ PLSYNC_SEARCHING, PLSYNC_FOUND, PLSYNC_LOCKED = 0, 1, 2
 PLSYNC_REAL_PEAK, PLSYNC_FLAG_LOCKED = 1, 2
 
 
-class ConstHandle(C.c_void_p):
-    """The `const dvbs2_demap_t*` of dvbs2_demap_table. tests/test_capi_null_handle.py lists the handle entries whose answers to a null
-    handle were recorded before the C-ABI layer was split, by a first argument of type c_void_p, and fixes their number; an entry added
-    since has this type and its null-handle answer is checked by its own test (tests/test_demap_table_model.py)."""
-
-    @classmethod
-    def from_param(cls, value):
-        return C.c_void_p.from_param(value)
-
-
 # every symbol include/dvbs2_fec_hip.h declares: name -> (restype, argtypes)
 _vp, _i, _ip = C.c_void_p, C.c_int, C.POINTER(C.c_int)
 _f, _fp = C.c_float, C.POINTER(C.c_float)
@@ -139,7 +129,7 @@ SYMBOLS = {
     "dvbs2_demap_create": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i]),
     "dvbs2_demap_table_check": (_i, [_i, _vp, _vp]),
     "dvbs2_demap_create_table": (_i, [C.POINTER(_vp), _i, _i, _vp, _vp, _i, _i]),
-    "dvbs2_demap_table": (_i, [ConstHandle, _ip, _vp, _vp]),
+    "dvbs2_demap_table": (_i, [_vp, _ip, _vp, _vp]),
     "dvbs2_demap_destroy": (None, [_vp]),
     "dvbs2_demap_params": (_i, [_vp, _ip, _ip, _ip, _ip]),
     "dvbs2_apsk_points": (_i, [_i, _i, _vp]),
@@ -368,14 +358,7 @@ SYMBOLS = {
     "dvbs2_plframer_params": (_i, [_vp, _ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "dvbs2_plframer_frame_device": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "dvbs2_plframer_frame": (_i, [_vp, _vp, _i, _i, _vp]),
-}
-
-# every symbol include/dvbs2_fec_hip_batch.h declares (the batched stages between the symbol synchroniser and the FEC chain), in a
-# table of its own as the header is a file of its own. SYMBOLS is also the census of two recorded tests -- the null-handle answers of
-# tests/test_capi_null_handle.py and the one row per handle type of tests/test_stream_order_gpu.py --; what is listed here has its
-# census in tests/test_plsync_batch_host.py (declared = bound = exported, the answer of every entry to a null handle) and
-# tests/test_plsync_batch_stream_gpu.py (a row on a busy non-blocking stream for every handle type and device entry).
-SYMBOLS_BATCH = {
+    # the batched stages between the symbol synchroniser and the FEC chain
     "dvbs2_plsync_batch_check": (_i, [_i, _i, _i, _i, _i]),
     "dvbs2_plsync_batch_check_search": (_i, [_i, _i, C.c_int64, _vp, _vp, _i]),
     "dvbs2_plsync_batch_create": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i, _i]),
@@ -401,7 +384,7 @@ if not os.path.exists(LIB_PATH):
     raise ImportError(f"{LIB_PATH} not found: build it with `make -C gr-dvbs2rx_amd` "
                       "(or __graft_entry__.build()); there is no CPU fallback")
 lib = C.CDLL(LIB_PATH)
-for _name, (_res, _args) in {**SYMBOLS, **SYMBOLS_BATCH}.items():
+for _name, (_res, _args) in SYMBOLS.items():
     if os.environ.get("DVBS2_LIB") and not hasattr(lib, _name):
         continue  # kernel experiments against a library built from an older tree (tools/ab.sh); the product library must export all
     _fn = getattr(lib, _name)  # (not _f: that is the c_float alias SYMBOLS is written with)

@@ -6,22 +6,10 @@
 //   tile decim ntaps                          -> "tile"
 //   mirror decim nch inc ... inc k (n_in n_channels) ... -> "n_out counter phase ... phase" per call, counter and phases carried over
 //   check decim max_channels max_inputs max_samples n tap ... tap -> "ok" or "refused: <text>" (DdcHip::check_args)
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <iostream>
-#include <sstream>
-#include <vector>
 #include "../gr-dvbs2rx_amd/csrc/ddc_hip.h"
-
-static float from_bits(uint32_t b) { float f; std::memcpy(&f, &b, 4); return f; }
-
-static std::vector<float> read_taps(std::istringstream& is, int n)
-{
-    std::vector<float> t; // exactly n floats: a read past the end is the sanitizer's to find
-    for (int i = 0; i < n; i++) { uint32_t b = 0; is >> std::hex >> b >> std::dec; t.push_back(from_bits(b)); }
-    return t;
-}
+#include "host_main.h"
 
 int main()
 {

@@ -6,6 +6,7 @@ module: it is the bridge to oracle/ and is never used by the product path.
 import ctypes as C
 import hashlib
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -266,6 +267,64 @@ def build_host_program(tmp_dir, main_cpp, sources, fp_contract_off=True):
     subprocess.check_call([hipcc, "-x", "hip", "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", *(["-ffp-contract=off"] if fp_contract_off else []),
                            *san, os.path.join(ROOT, "tests", main_cpp), *[os.path.join(csrc, s) for s in sources], "-o", exe])
     return exe
+
+
+def run_host_program(exe, rows):
+    """One of the stand-alone host programs (build_host_program) with `rows` on its standard input, one per line: the stripped lines of
+    its standard output."""
+    r = subprocess.run([exe], input="".join(row + "\n" for row in rows), capture_output=True, text=True)
+    assert r.returncode == 0 and r.stderr == "", r.stderr  # a sanitizer report goes to stderr and ends the program
+    return [line.strip() for line in r.stdout.splitlines()]
+
+
+# ------------------------------------------------------------------ the C ABI as the public header declares it (notes/capi_census.md)
+def c_abi_declarations():
+    """Every function include/dvbs2_fec_hip.h declares, by one rule: comments stripped, declarations matched by `name ( params ) ;`, the
+    first parameter decides the class. One record per function, in header order: name, ret (the text of the return type), params (the
+    parameter texts, [] for `void`), kind and type. The handle types are those with a dvbs2_<type>_destroy; kind is "handle" where the
+    first parameter is `[const] dvbs2_<type>_t*` of a handle type (type names it), "create" where it is `dvbs2_<type>_t**`, else "other"."""
+    from types import SimpleNamespace as NS
+    hdr = re.sub(r"/\*.*?\*/|//[^\n]*", " ", open(os.path.join(ROOT, "include", "dvbs2_fec_hip.h")).read(), flags=re.S)
+    found = re.findall(r"\b((?:const\s+)?[a-z_0-9]+\s*\**)\s*\b(dvbs2_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", hdr)
+    types = {name[len("dvbs2_"):-len("_destroy")] for _, name, _ in found if name.endswith("_destroy")}
+    decls = []
+    for ret, name, params in found:
+        params = [" ".join(p.split()) for p in params.split(",")]
+        d = NS(name=name, ret="".join(ret.split()).replace("const", "const "), params=[] if params == ["void"] else params, kind="other", type=None)
+        first = re.fullmatch(r"(?:const )?dvbs2_([a-z0-9_]+)_t ?(\*\*?) ?\w+", d.params[0]) if d.params else None
+        if first and first.group(2) == "**":
+            d.kind, d.type = "create", first.group(1)
+        elif first and first.group(1) in types:
+            d.kind, d.type = "handle", first.group(1)
+        decls.append(d)
+    return decls
+
+
+def c_kind_of_text(text):
+    """the kind of a parameter or return type as the header spells it: "pointer" (an array parameter such as `uint8_t out[10]` is one),
+    "i32", "i64" (size_t is taken as 64-bit), "float", "double" or "void" """
+    if "*" in text or "[" in text:
+        return "pointer"
+    words = [w for w in text.split() if w != "const"]
+    base = words[0] if len(words) == 1 else " ".join(words[:-1])  # a return type stands alone; a parameter carries its name
+    return {"void": "void", "int": "i32", "unsigned": "i32", "int32_t": "i32", "uint32_t": "i32", "int64_t": "i64", "uint64_t": "i64",
+            "size_t": "i64", "float": "float", "double": "double"}[base]
+
+
+def c_kind_of_ctype(t):
+    """the same kinds for a ctypes type of an argtypes list or a restype"""
+    if t is None:
+        return "void"
+    code = getattr(t, "_type_", None)
+    if not isinstance(code, str):
+        assert issubclass(t, C._Pointer), t
+        return "pointer"
+    return {"f": "float", "d": "double", "P": "pointer", "z": "pointer"}.get(code) or {4: "i32", 8: "i64"}[C.sizeof(t)]
+
+
+def c_zero_args(argtypes):
+    """zero for every numeric kind and None for every pointer: the arguments of the null-handle census"""
+    return [None if c_kind_of_ctype(a) == "pointer" else 0 for a in argtypes]
 
 
 def run_ldpc_planner(exe, rows, group_size=32):

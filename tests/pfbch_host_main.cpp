@@ -12,34 +12,10 @@
 //   create n_chan decim max_streams max_samples n tap ... tap -> "refused <code>: <text>" (only refused rows are sent)
 //   channels n_chan n c ... c                     -> "ok" or "refused: <text>" (PfbchHip::check_channels)
 //   null                                          -> one "<entry> <code>: <text>" line per entry called with a null handle
-#include <cstdio>
-#include <cstring>
 #include <iostream>
-#include <sstream>
-#include <string>
-#include <vector>
-#include "../gr-dvbs2rx_amd/csrc/c_api_common.h"
+#define HOST_MAIN_LINKS_C_API
+#include "host_main.h"
 #include "../gr-dvbs2rx_amd/csrc/pfbch_hip.h"
-
-// what c_api_core.hip defines in the library; that file binds the LDPC decoder too, which this program does not link
-thread_local std::string dvbs2::g_api_error;
-int dvbs2::check_device(int) { return dvbs2::fail(DVBS2_EDEVICE, "this program looks for no device"); }
-
-static float from_bits(uint32_t b) { float f; std::memcpy(&f, &b, 4); return f; }
-static uint32_t to_bits(float f) { uint32_t b; std::memcpy(&b, &f, 4); return b; }
-
-static std::vector<float> read_taps(std::istringstream& is, int n)
-{
-    std::vector<float> t; // exactly n floats: a read past the end is the sanitizer's to find
-    for (int i = 0; i < n; i++) { uint32_t b = 0; is >> std::hex >> b >> std::dec; t.push_back(from_bits(b)); }
-    return t;
-}
-
-static void answer(const char* entry, int code)
-{
-    if (code) std::printf("%s%s%d: %s\n", entry, *entry ? " " : "refused ", code, dvbs2::g_api_error.c_str());
-    else std::printf("%s%sok\n", entry, *entry ? " " : "");
-}
 
 int main()
 {

@@ -1,7 +1,7 @@
 // stdin rows -> one line each. Drives the host-only side of the batched PL stages (csrc/c_api_plsync_batch.hip, csrc/plsync_batch_hip.hip:
 // dvbs2_plsync_batch_check, dvbs2_plsync_batch_check_search and the refusals of dvbs2_plsync_batch_create; csrc/c_api_plcoarse.hip: the
 // refusals of dvbs2_plcoarse_batch_create; csrc/c_api_plframe.hip: dvbs2_plframe_stride_check; every entry of
-// include/dvbs2_fec_hip_batch.h with a null handle) outside Python, so that it can be built with -fsanitize=address,undefined. No device
+// the batched stages of include/dvbs2_fec_hip.h with a null handle) outside Python, so that it can be built with -fsanitize=address,undefined. No device
 // code runs and no GPU call is made: every row is answered before a device is looked for.
 //   check plsc unlock_thresh max_streams max_symbols max_frames   -> "ok" or "refused <code>: <text>" (dvbs2_plsync_batch_check; the class's
 //                                                                    rule must agree)
@@ -11,24 +11,11 @@
 //                                                                 -> "ok" or "refused <code>: <text>" (dvbs2_plsync_batch_check_search)
 //   stride plsc stride_syms                                       -> "ok" or "refused <code>: <text>" (dvbs2_plframe_stride_check)
 //   null                                                          -> one "<entry> <code>: <text>" line per entry called with a null handle
-#include <cstdio>
 #include <iostream>
-#include <sstream>
-#include <string>
-#include <vector>
-#include "../gr-dvbs2rx_amd/csrc/c_api_common.h"
+#define HOST_MAIN_LINKS_C_API
+#include "host_main.h"
 #include "../gr-dvbs2rx_amd/csrc/plcoarse_hip.h"
 #include "../gr-dvbs2rx_amd/csrc/plsync_batch_hip.h"
-
-// what c_api_core.hip defines in the library; that file binds the LDPC decoder too, which this program does not link
-thread_local std::string dvbs2::g_api_error;
-int dvbs2::check_device(int) { return dvbs2::fail(DVBS2_EDEVICE, "this program looks for no device"); }
-
-static void answer(const char* entry, int code)
-{
-    if (code) std::printf("%s%s%d: %s\n", entry, *entry ? " " : "refused ", code, dvbs2::g_api_error.c_str());
-    else std::printf("%s%sok\n", entry, *entry ? " " : "");
-}
 
 int main()
 {

@@ -5,22 +5,9 @@
 //   taps sps rolloff rrc_delay tau gain     -> the taps, or "refused"
 //   scale sps fullscale n tap ... tap       -> the scaled taps, or "refused"
 //   check sps max_streams max_symbols n tap ... tap -> "ok" or "refused: <text>" (PulseShaperHip::check_args)
-#include <cstdio>
-#include <cstring>
 #include <iostream>
-#include <sstream>
-#include <vector>
 #include "../gr-dvbs2rx_amd/csrc/pulse_hip.h"
-
-static float from_bits(uint32_t b) { float f; std::memcpy(&f, &b, 4); return f; }
-static uint32_t to_bits(float f) { uint32_t b; std::memcpy(&b, &f, 4); return b; }
-
-static std::vector<float> read_taps(std::istringstream& is, int n)
-{
-    std::vector<float> t; // exactly n floats: a read or write past the end is the sanitizer's to find
-    for (int i = 0; i < n; i++) { uint32_t b = 0; is >> std::hex >> b >> std::dec; t.push_back(from_bits(b)); }
-    return t;
-}
+#include "host_main.h"
 
 static void print_taps(const std::vector<float>& t)
 {

@@ -6,22 +6,10 @@
 //   maxout step n_in                         -> "n" or "refused"
 //   produce step acc k n_in ... n_in         -> "n_out acc'" per call, acc carried over
 //   check nfilts rate max_streams max_samples n tap ... tap -> "ok" or "refused: <text>" (ResamplerHip::check_args)
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <iostream>
-#include <sstream>
-#include <vector>
 #include "../gr-dvbs2rx_amd/csrc/resamp_hip.h"
-
-static float from_bits(uint32_t b) { float f; std::memcpy(&f, &b, 4); return f; }
-
-static std::vector<float> read_taps(std::istringstream& is, int n)
-{
-    std::vector<float> t; // exactly n floats: a read past the end is the sanitizer's to find
-    for (int i = 0; i < n; i++) { uint32_t b = 0; is >> std::hex >> b >> std::dec; t.push_back(from_bits(b)); }
-    return t;
-}
+#include "host_main.h"
 
 static double read_double(std::istringstream& is)
 {

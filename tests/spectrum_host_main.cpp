@@ -7,28 +7,15 @@
 //   check nfft hop avg max_streams max_samples n w ... w   -> "ok" or "refused: <text>" (SpectrumHip::check_args; n == 0: null window)
 //   carriers shifted smooth quantile threshold_db min_gap min_width nfft p ... p
 //                                              -> "k" then per carrier "centre bandwidth level floor lo hi", or "refused: <text>"
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <iostream>
-#include <sstream>
-#include <vector>
 #include "../gr-dvbs2rx_amd/csrc/spectrum_hip.h"
+#include "host_main.h"
 
-static float from_bits(uint32_t b) { float f; std::memcpy(&f, &b, 4); return f; }
-static uint32_t bits_of(float f) { uint32_t b; std::memcpy(&b, &f, 4); return b; }
 static unsigned long long bits_of(double f) { unsigned long long b; std::memcpy(&b, &f, 8); return b; }
-
-static std::vector<float> read_floats(std::istringstream& is, int n)
-{
-    std::vector<float> t; // exactly n floats: a read past the end is the sanitizer's to find
-    for (int i = 0; i < n; i++) { uint32_t b = 0; is >> std::hex >> b >> std::dec; t.push_back(from_bits(b)); }
-    return t;
-}
 
 static void print_floats(const std::vector<float>& v)
 {
-    for (float f : v) std::printf("%08x ", bits_of(f));
+    for (float f : v) std::printf("%08x ", to_bits(f));
     std::printf("\n");
 }
 
@@ -58,14 +45,14 @@ int main()
         } else if (what == "check") {
             int nfft, hop, avg, max_streams, max_samples, n;
             is >> nfft >> hop >> avg >> max_streams >> max_samples >> n;
-            const std::vector<float> w = read_floats(is, n);
+            const std::vector<float> w = read_taps(is, n);
             const std::string bad = dvbs2::SpectrumHip::check_args(nfft, hop, avg, w.empty() ? nullptr : w.data(), max_streams, max_samples);
             std::printf("%s%s\n", bad.empty() ? "ok" : "refused: ", bad.c_str());
         } else if (what == "carriers") {
             int shifted, nfft;
             dvbs2::SpectrumCarrierParams p = dvbs2::kSpectrumCarrierDefaults;
             is >> shifted >> p.smooth >> p.floor_quantile >> p.threshold_db >> p.min_gap >> p.min_width >> nfft;
-            const std::vector<float> row = read_floats(is, nfft > 0 ? nfft : 0);
+            const std::vector<float> row = read_taps(is, nfft > 0 ? nfft : 0);
             const std::string bad = dvbs2::spectrum_carriers_check(row.empty() ? nullptr : row.data(), nfft, p);
             if (!bad.empty()) { std::printf("refused: %s\n", bad.c_str()); continue; }
             const std::vector<dvbs2::SpectrumCarrier> found = dvbs2::spectrum_carriers(row.data(), nfft, shifted != 0, p);

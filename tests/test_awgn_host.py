@@ -2,7 +2,6 @@
 create, a block of the host restatement, and every new entry with a null handle -- once more in a stand-alone program built with the
 host sanitizers. Its answers must be the library's own. Nothing is loaded into Python by the program and no GPU call is made."""
 import ctypes as C
-import subprocess
 
 import numpy as np
 import pytest
@@ -70,26 +69,8 @@ def test_host_program_under_the_host_sanitizers(host_exe):
     rows.append("null")
     entries = ["set_sigma", "set_seed", "params", "add_device", "add"]
     want += [f"{e} -1: null handle" for e in entries] + ["create -1: null handle pointer", "destroy nothing written"]
-    r = subprocess.run([host_exe], input="".join(row + "\n" for row in rows), capture_output=True, text=True)
-    assert r.returncode == 0 and r.stderr == "", r.stderr  # a sanitizer report goes to stderr and ends the program
-    lines = [line.strip() for line in r.stdout.splitlines()]
+    lines = T.run_host_program(host_exe, rows)
     assert len(lines) == len(want)
     for got, w_ in zip(lines, want):
         assert got == w_
     assert sum(w_.startswith("refused") for w_ in want) == len(bad) + len(bad_creates)
-
-
-def test_null_handle_through_every_new_entry():
-    """The convention of tests/test_capi_null_handle.py for the entries of the new handle type, through the library; no device is touched."""
-    host_only = {"dvbs2_awgn_check", "dvbs2_awgn_sigma", "dvbs2_awgn_words", "dvbs2_awgn_sample"}
-    names = [n for n in capi.SYMBOLS if n.startswith("dvbs2_awgn_") and "_create" not in n and n not in host_only]
-    assert len(names) == 6 and "dvbs2_awgn_destroy" in names
-    for name in names:
-        zero = [0 if a in (C.c_int, C.c_int64, C.c_uint64, C.c_float) else None for a in capi.SYMBOLS[name][1]]
-        assert capi.lib.dvbs2_get_fec_info(0, 0, 0, None) == capi.EINVAL  # leaves another text behind: the one below is this entry's own
-        ret = getattr(capi.lib, name)(*zero)
-        if name.endswith("_destroy"):
-            assert ret is None
-        else:
-            assert (ret, capi.lib.dvbs2_last_error()) == (capi.EINVAL, b"null handle"), name
-    assert capi.lib.dvbs2_awgn_create(None, 1, 1.0, 1, 16, 0) == capi.EINVAL and capi.lib.dvbs2_last_error() == b"null handle pointer"

@@ -4,7 +4,6 @@ fec_testlib, of the reference's known CRC answers, of the model's need() and of 
 import ctypes as C
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -102,9 +101,7 @@ def test_host_program_under_the_host_sanitizers(host_exe):
                       (-1, 0, "refused -3: n_frames must be in 0..max_frames")):
         rows.append(f"call 64 {mx} {n} {dfl}")
         want.append(w)
-    r = subprocess.run([host_exe], input="".join(row + "\n" for row in rows), capture_output=True, text=True)
-    assert r.returncode == 0 and r.stderr == "", r.stderr  # a sanitizer report goes to stderr and ends the program
-    lines = [line.strip() for line in r.stdout.splitlines()]
+    lines = T.run_host_program(host_exe, rows)
     assert len(lines) == len(rows)
     for row, got, w in zip(rows, lines, want):
         assert got == w, row[:60]
@@ -115,19 +112,3 @@ def test_host_entries_answer_null():
     assert capi.lib.dvbs2_bbheader_build(None, 0, 0, 0, 0, 0, 0) == capi.EINVAL and capi.lib.dvbs2_last_error() == b"out is null"
     assert capi.lib.dvbs2_crc8(None, 3) == capi.EINVAL and capi.lib.dvbs2_last_error() == b"data is null"
     assert capi.lib.dvbs2_crc8(None, 0) == 0
-
-
-def test_null_handle_through_every_new_entry():
-    """The convention of tests/test_capi_null_handle.py for the entries of the new handle type; no device is touched."""
-    names = [n for n in capi.SYMBOLS if n.startswith("dvbs2_bbframer_") and "_create" not in n]
-    assert len(names) == 8 and "dvbs2_bbframer_destroy" in names
-    for name in names:
-        zero = [0 if a in (C.c_int, C.c_int64, C.c_size_t) else None for a in capi.SYMBOLS[name][1]]
-        assert capi.lib.dvbs2_get_fec_info(0, 0, 0, None) == capi.EINVAL  # leaves another text behind: the one below is this entry's own
-        ret = getattr(capi.lib, name)(*zero)
-        if name.endswith("_destroy"):
-            assert ret is None
-        else:
-            assert (ret, capi.lib.dvbs2_last_error()) == (capi.EINVAL, b"null handle"), name
-    for create, args in (("dvbs2_bbframer_create", (0, 0, 0, 8, 0)), ("dvbs2_bbframer_create_raw", (3072, 8, 0))):
-        assert getattr(capi.lib, create)(None, *args) == capi.EINVAL and capi.lib.dvbs2_last_error() == b"null handle pointer"

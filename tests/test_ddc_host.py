@@ -1,7 +1,6 @@
 """CPU: the host-only code of the digital down-converter -- geometry, the count rule, the tile rule, the counter and phase mirror over
 sequences of calls and the argument check of the class -- once more in a stand-alone program built with the host sanitizers, over good
 and refused arguments. Its answers must be the library's and those of tests/ddc_model.py."""
-import subprocess
 
 import numpy as np
 import pytest
@@ -80,9 +79,7 @@ def test_host_program_under_the_host_sanitizers(host_exe):
     for D, mc, mi, ms, taps in bad_check:
         rows.append(f"check {D} {mc} {mi} {ms} {len(taps)} {_hex(taps)}")
         want.append("refused: " + _lib_refuses(D, taps, mc, mi, ms))
-    r = subprocess.run([host_exe], input="".join(row + "\n" for row in rows), capture_output=True, text=True)
-    assert r.returncode == 0 and r.stderr == "", r.stderr  # a sanitizer report goes to stderr and ends the program
-    lines = [line.strip() for line in r.stdout.splitlines()]
+    lines = T.run_host_program(host_exe, rows)
     assert len(lines) == len(rows)
     for row, got, w in zip(rows, lines, want):
         assert got == w, row[:60]

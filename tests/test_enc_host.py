@@ -1,4 +1,5 @@
-"""The encoder's host-only surface (dvbs2_enc_check, null handles, no device): needs no GPU.
+"""The encoder's host-only surface (dvbs2_enc_check, create without a device): needs no GPU. The answers to a null handle are
+in tests/test_capi_null_handle.py.
 
 dvbs2_enc_check is the verdict dvbs2_enc_create gives before it touches a device: DVBS2_OK exactly for the rows of
 tests/golden/fec_params.json whose bch_n is the K of their LDPC table with n and k multiples of 8, combined with DVBS2_ENC_NO_MAPPER or a
@@ -90,20 +91,6 @@ def test_create_judges_its_arguments_before_the_device():
     assert capi.lib.dvbs2_last_error() == b"ldpc_table: unknown LDPC table S2_TABLE_NONE"
     assert capi.lib.dvbs2_enc_create(None, 0, 1, 3, capi.MOD_QPSK, 4, 0) == capi.EINVAL
     assert capi.lib.dvbs2_last_error() == b"null handle pointer"
-
-
-ENC_HANDLE_ENTRIES = ("dvbs2_enc_params", "dvbs2_enc_set_scramble", "dvbs2_enc_encode_device", "dvbs2_enc_encode")
-
-
-def test_null_handle():
-    names = [n for n, (_, args) in capi.SYMBOLS.items() if n.startswith("dvbs2_enc_") and args and args[0] is C.c_void_p]
-    assert sorted(names) == sorted(ENC_HANDLE_ENTRIES + ("dvbs2_enc_destroy",))
-    assert capi.lib.dvbs2_enc_destroy(None) is None  # a no-op
-    for name in ENC_HANDLE_ENTRIES:
-        zero = [0 if a is C.c_int else None for a in capi.SYMBOLS[name][1]]
-        assert capi.lib.dvbs2_get_fec_info(0, 0, 0, None) == capi.EINVAL  # leaves "null out" behind
-        assert getattr(capi.lib, name)(*zero) == capi.EINVAL, name
-        assert capi.lib.dvbs2_last_error() == b"null handle", name
 
 
 def test_create_without_a_device_is_edevice():

@@ -210,12 +210,23 @@ def test_fec_params_match_reference():
 
 
 def test_c_abi_exports_every_declared_symbol():
-    hdr = open(os.path.join(T.ROOT, "include", "dvbs2_fec_hip.h")).read()
-    declared = set(re.findall(r"\b(dvbs2_[a-z0-9_]+)\s*\(", hdr))
-    declared -= {n for n in declared if n.endswith("_t")}
-    assert declared == set(capi.SYMBOLS), declared ^ set(capi.SYMBOLS)
-    for name in declared:
-        assert getattr(capi.lib, name) is not None
+    """declared in the header = listed in capi.SYMBOLS = exported, and every entry is bound as it is declared: the arity, the kind of every
+    position (pointer, 32-bit integer, 64-bit integer or size_t, float, double; an array parameter is a pointer) and the return type"""
+    decls = T.c_abi_declarations()
+    declared = {d.name for d in decls}
+    assert len(decls) == len(declared) and declared == set(capi.SYMBOLS), declared ^ set(capi.SYMBOLS)
+    wrong = []
+    for d in decls:
+        fn = getattr(capi.lib, d.name)
+        assert fn is not None
+        res, args = capi.SYMBOLS[d.name]
+        assert fn.restype is res and list(fn.argtypes) == args, d.name  # the table is what the loader applied
+        if [T.c_kind_of_text(p) for p in d.params] != [T.c_kind_of_ctype(a) for a in args]:
+            wrong.append((d.name, d.params, args))
+        want = None if d.ret == "void" else C.c_char_p if d.ret == "const char*" else {"i32": C.c_int, "i64": C.c_int64}[T.c_kind_of_text(d.ret)]
+        if res is not want:
+            wrong.append((d.name, d.ret, res))
+    assert not wrong, wrong
 
 
 def test_create_fails_loudly_without_device_or_with_bad_args():

@@ -1,7 +1,6 @@
 """CPU: the host-only code of the polyphase channelizer -- geometry, the count rule over sequences of calls up to a counter of 2^62, the
 tile rule, the twiddle table, every refusal of the argument checks with its code and text, and the answers to a null handle -- once more
 in a stand-alone program built with the host sanitizers. Its answers must be the library's and those of tests/pfbch_model.py."""
-import subprocess
 
 import numpy as np
 import pytest
@@ -123,9 +122,7 @@ def test_host_program_under_the_host_sanitizers(host_exe):
     rows.append("null")
     null_lines = [f"{e} {capi.EINVAL}: null handle" for e in ("reset", "set_channels", "params", "position", "channels", "process_device", "process")]
     null_lines += [f"create {capi.EINVAL}: null handle pointer", "destroy nothing written"]
-    r = subprocess.run([host_exe], input="".join(row + "\n" for row in rows), capture_output=True, text=True)
-    assert r.returncode == 0 and r.stderr == "", r.stderr  # a sanitizer report goes to stderr and ends the program
-    lines = [line.strip() for line in r.stdout.splitlines()]
+    lines = T.run_host_program(host_exe, rows)
     assert len(lines) == len(rows) - 1 + len(null_lines)
     for row, got, w in zip(rows[:-1], lines, want):
         assert got == w, (row[:60], got[:80], w[:80])

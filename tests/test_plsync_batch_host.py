@@ -1,13 +1,10 @@
 """CPU: the host-only side of the batched PL stages -- the argument ranges of dvbs2_plsync_batch_check and of the two batch creates, the
 checks of a search call (dvbs2_plsync_batch_check_search: a null first or n_syms, counts, rows that run into each other), the stride rule
 of the strided front end (dvbs2_plframe_stride_check), each refusal with its code and text -- through the library and once more in a
-stand-alone program built with the host sanitizers, whose answers must be the library's. Then the census that tests/test_oracle_kat.py
-and tests/test_capi_null_handle.py keep for capi.SYMBOLS, for capi.SYMBOLS_BATCH: what include/dvbs2_fec_hip_batch.h declares is what is
-bound and exported, and every entry answers a null handle as every other entry does."""
+stand-alone program built with the host sanitizers, whose answers must be the library's. That the entries are bound and exported as
+declared and answer a null handle as every other entry does is held by the censuses of tests/test_oracle_kat.py and
+tests/test_capi_null_handle.py."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -138,42 +135,8 @@ def test_host_program_under_the_host_sanitizers(host_exe):
     rows.append("null")
     null_lines = [f"{e} {EINVAL}: null handle" for e in NULL_ENTRIES]
     null_lines += [f"batch_create {EINVAL}: null handle pointer", f"coarse_batch_create {EINVAL}: null handle pointer", "destroy nothing written"]
-    r = subprocess.run([host_exe], input="".join(row + "\n" for row in rows), capture_output=True, text=True)
-    assert r.returncode == 0 and r.stderr == "", r.stderr  # a sanitizer report goes to stderr and ends the program
-    lines = [ln.strip() for ln in r.stdout.splitlines()]
+    lines = T.run_host_program(host_exe, rows)
     assert len(lines) == len(rows) - 1 + len(null_lines)
     for row, got, w in zip(rows[:-1], lines, want):
         assert got == w, (row[:80], got[:100], w[:100])
     assert lines[len(rows) - 1:] == null_lines
-
-
-def test_the_batch_header_is_bound_and_exported():
-    """declared in include/dvbs2_fec_hip_batch.h = listed in capi.SYMBOLS_BATCH = exported; the main header includes the batch header, and
-    the two tables do not overlap"""
-    inc = os.path.join(T.ROOT, "include")
-    hdr = open(os.path.join(inc, "dvbs2_fec_hip_batch.h")).read()
-    declared = set(re.findall(r"\b(dvbs2_[a-z0-9_]+)\s*\(", hdr))
-    declared -= {n for n in declared if n.endswith("_t")}
-    assert declared == set(capi.SYMBOLS_BATCH), declared ^ set(capi.SYMBOLS_BATCH)
-    assert not set(capi.SYMBOLS_BATCH) & set(capi.SYMBOLS)
-    assert '#include "dvbs2_fec_hip_batch.h"' in open(os.path.join(inc, "dvbs2_fec_hip.h")).read()
-    for name, (res, args) in capi.SYMBOLS_BATCH.items():
-        fn = getattr(capi.lib, name)
-        assert fn.restype is res and list(fn.argtypes) == args, name
-
-
-def test_null_handle():
-    """as tests/test_capi_null_handle.py: every entry that takes a handle answers a null one with EINVAL and "null handle" and writes nothing"""
-    host_only = {"dvbs2_plsync_batch_check", "dvbs2_plsync_batch_check_search", "dvbs2_plframe_stride_check"}
-    names = [n for n in capi.SYMBOLS_BATCH if n not in host_only and "_create" not in n]
-    assert len(names) == len(NULL_ENTRIES) + 2  # and the two destroys
-    for name in names:
-        zero = [0 if a in (C.c_int, C.c_int64) else None for a in capi.SYMBOLS_BATCH[name][1]]
-        assert capi.lib.dvbs2_get_fec_info(0, 0, 0, None) == EINVAL  # leaves another text behind: the one below is this entry's own
-        ret = getattr(capi.lib, name)(*zero)
-        if name.endswith("_destroy"):
-            assert ret is None
-        else:
-            assert (ret, capi.lib.dvbs2_last_error()) == (EINVAL, b"null handle"), name
-    for create, args in (("dvbs2_plsync_batch_create", (-1, 3, 1, MIN, 16, 0)), ("dvbs2_plcoarse_batch_create", (1, -1, 1, 16, 0))):
-        assert getattr(capi.lib, create)(None, *args) == EINVAL and capi.lib.dvbs2_last_error() == b"null handle pointer"

@@ -1,5 +1,5 @@
 """The stream contract of the batched PL stages on a BUSY non-blocking stream: what tests/test_stream_order_gpu.py applies to every other
-stage (its docstring and notes/stream_order.md say how), for the handle types and device entries of include/dvbs2_fec_hip_batch.h.
+stage (its docstring and notes/stream_order.md say how), for the handle types and device entries of the batched stages.
   A. search -> gather -> coarse estimate -> strided front end, enqueued back to back behind a hold with no host synchronisation, the
      caller's first[] / n_syms[] arrays rewritten the moment the search returns, equal the same calls serialized;
   B. the entries that wait (finish, reset, reset_stream of both handle types), called while work of the handle is pending, give what they
@@ -219,13 +219,14 @@ def test_pending_calls_equal_the_serialized_ones(name):
 
 
 def test_every_batched_handle_and_device_entry_has_its_row():
-    """the census tests/test_stream_order_gpu.py keeps for capi.SYMBOLS, for capi.SYMBOLS_BATCH"""
+    """the rows that tests/test_stream_order_gpu.py's census (ELSEWHERE) refers to: the two batch handle types and the device entries of
+    the batched stages"""
     rows = all_rows()
     assert sorted(rows) == sorted(ROW_NAMES)
-    types = {name[len("dvbs2_"):-len("_destroy")] for name in capi.SYMBOLS_BATCH if name.endswith("_destroy")}
+    types = {name[len("dvbs2_"):-len("_destroy")] for name in capi.SYMBOLS if name.endswith("_batch_destroy")}
     assert types == {"plsync_batch", "plcoarse_batch"} <= set().union(*(SO.handles_of(r) for r in rows.values()))
     waiting = {"plsync_batch finish", "plsync_batch reset", "plsync_batch reset_stream", "plcoarse_batch reset", "plcoarse_batch reset_stream"}
     assert {n.replace("-", " ") for n in ROW_NAMES if rows[n].waits} == waiting
-    device = {n for n in capi.SYMBOLS_BATCH if n.endswith("_device")}
+    device = {n for n in capi.SYMBOLS if n.endswith("_device") and ("_batch_" in n or "_strided_" in n)}
     assert device == {"dvbs2_plsync_batch_search_device", "dvbs2_plsync_batch_gather_device", "dvbs2_plcoarse_batch_estimate_device",
                       "dvbs2_plframe_estimate_strided_device", "dvbs2_plframe_process_strided_device"}  # the chain row calls the first three and the last

@@ -1,7 +1,6 @@
 """CPU: the host-only code of the pulse shaper -- geometry, tap design, tap scaling and the argument check of the class -- once more in a
 stand-alone program built with the host sanitizers, over good and refused arguments. Its tap values must be the library's, bit for bit."""
 import ctypes as C
-import subprocess
 
 import numpy as np
 import pytest
@@ -68,9 +67,7 @@ def test_host_program_under_the_host_sanitizers(host_exe):
                               (2, 65536, 16, np.ones(3)), (2, 1, 0, np.ones(3)), (2, 1, (1 << 30) + 1, np.ones(3))):
         rows.append(f"check {sps} {ms} {mx} {len(taps)} {_hex(taps)}")
         want.append("refused: " + _lib_refuses_create(sps, taps, ms, mx))
-    r = subprocess.run([host_exe], input="".join(row + "\n" for row in rows), capture_output=True, text=True)
-    assert r.returncode == 0 and r.stderr == "", r.stderr  # a sanitizer report goes to stderr and ends the program
-    lines = [line.strip() for line in r.stdout.splitlines()]
+    lines = T.run_host_program(host_exe, rows)
     assert len(lines) == len(rows)
     for row, got, w in zip(rows, lines, want):
         assert got == w, row[:60]

@@ -1,7 +1,6 @@
 """CPU: the host-only code of the spectrum stage -- geometry, the windows, the twiddle table, the argument check of the class and the
 carrier finder -- once more in a stand-alone program built with the host sanitizers, over good and refused arguments. Its answers must
 be the library's (bit for bit) and those of tests/spectrum_model.py."""
-import subprocess
 
 import numpy as np
 import pytest
@@ -99,9 +98,7 @@ def test_host_program_under_the_host_sanitizers(host_exe):
         rows.append(f"carriers {head} {r.size} {_hex(r)}")
         want.append("refused: " + text)
         n_refused += 1
-    r = subprocess.run([host_exe], input="".join(row + "\n" for row in rows), capture_output=True, text=True)
-    assert r.returncode == 0 and r.stderr == "", r.stderr  # a sanitizer report goes to stderr and ends the program
-    lines = [line.strip() for line in r.stdout.splitlines()]
+    lines = T.run_host_program(host_exe, rows)
     assert len(lines) == len(rows)
     for row, got, w in zip(rows, lines, want):
         assert got == w, row[:60]

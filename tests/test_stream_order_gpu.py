@@ -1211,7 +1211,8 @@ row("demap_table", demap_table_row)
 
 # ================================================================== the tests
 # handle types whose side-stream behaviour has its own test elsewhere instead of a row here
-ELSEWHERE = {"ldpc": "tests/test_ldpc_gpu.py: the enqueue / finish tests on a side stream", "chain": "tests/test_ldpc_gpu.py, tests/test_enc_gpu.py: enqueue_device on a side stream"}
+ELSEWHERE = {"ldpc": "tests/test_ldpc_gpu.py: the enqueue / finish tests on a side stream", "chain": "tests/test_ldpc_gpu.py, tests/test_enc_gpu.py: enqueue_device on a side stream",
+             "plsync_batch": "tests/test_plsync_batch_stream_gpu.py: its rows, by this file's machinery", "plcoarse_batch": "tests/test_plsync_batch_stream_gpu.py: its rows, by this file's machinery"}
 # every entry whose header comment says "waits" or "synchronous" and that may be called while work is pending -> its row
 WAITING = {"agc reset": "agc-reset", "agc set_gain": "agc-set_gain", "agc state": "agc-state", "symsync reset": "symsync-reset",
            "symsync state": "symsync-state", "symsync finish": "symsync-finish", "pulse reset": "pulse-reset", "resamp reset": "resamp-reset",
