@@ -18,7 +18,8 @@ __all__ = ["get_fec_info", "rate_id", "LdpcDecoder", "BchDecoder", "Demapper", "
            "pl_scrambling_rn", "HostBuffer", "PlFrontEnd", "plheader_symbols", "pls_parse", "apsk_points", "demap_table_check",
            "PlSync", "plsync_taps", "plsync_thresholds", "PlCoarse", "plcoarse_weights", "PlSyncBatch", "PlCoarseBatch", "plsync_batch_check", "Agc", "agc_check", "Awgn", "awgn_sigma", "awgn_words",
            "awgn_sample", "awgn_check", "IqConverter", "IQ_FORMATS", "iqconv_bytes", "iqconv_check", "iqconv_unpack_host", "iqconv_pack_host",
-           "Rotator",
+           "Rotator", "ROTATOR_STATE", "rotator_state_init", "rotator_state_read", "rotator_adjust_turns", "rotator_rows_device",
+           "rotator_retune_device", "rotator_control_device",
            "SymbolSync", "symsync_loop_constants", "symsync_geometry", "symsync_taps", "FecEncoder", "enc_check",
            "PlFramer", "plframer_layout", "PulseShaper", "pulse_geometry", "pulse_taps", "pulse_scale_taps",
            "Resampler", "resamp_step", "resamp_geometry", "resamp_max_out", "resamp_check",
@@ -1036,6 +1037,61 @@ class Rotator(_Handle):
     def work_device(self, d_in, n_syms, d_out, stream=0):
         """DEVICE addresses (8-byte aligned), asynchronous on `stream`; d_out == d_in rotates in place."""
         check(lib.dvbs2_rotator_rotate_device(self._h, d_in, int(n_syms), d_out, stream or None))
+
+
+ROTATOR_STATE = np.dtype(capi.ROTATOR_STATE_DTYPE)  # dvbs2_rotator_state_t: phase and inc in 2^-64 turns, index, reserved
+
+
+def rotator_state_init(phase_inc):
+    """One ROTATOR_STATE record per increment (radians per sample): phase 0 at index 0, the increment converted as Rotator converts
+    it, so that a row started this way equals Rotator(phase_inc[s]) bit for bit. Host only; copy the array to the device."""
+    inc = np.ascontiguousarray(phase_inc, np.float64).reshape(-1)
+    state = np.zeros(inc.size, ROTATOR_STATE)
+    check(lib.dvbs2_rotator_state_init(_ptr(inc), int(inc.size), _ptr(state)))
+    return state
+
+
+def rotator_state_read(state):
+    """(phase_inc, phase_at_index) of HOST records as radians in (-pi, pi], one float64 array each. For printing and tests."""
+    st = np.ascontiguousarray(state, ROTATOR_STATE).reshape(-1)
+    inc, phase = np.zeros(st.size), np.zeros(st.size)
+    check(lib.dvbs2_rotator_state_read(_ptr(st), int(st.size), _ptr(inc), _ptr(phase)))
+    return inc, phase
+
+
+def rotator_adjust_turns(estimate, scale):
+    """(delta, applies): the control step's one conversion of an estimate (float32) and a scale (float64) into the 2^-64 turns that
+    rotator_control_device subtracts from an increment; applies is False for a product that is not finite or not below 0.5 turns.
+    Host only."""
+    delta, applies = C.c_int64(), C.c_int()
+    check(lib.dvbs2_rotator_adjust_turns(float(np.float32(estimate)), float(scale), C.byref(delta), C.byref(applies)))
+    return delta.value, bool(applies.value)
+
+
+def rotator_rows_device(d_in, in_stride, d_out, out_stride, n_samples, n_streams, base_index, d_state, device=0, stream=0):
+    """DEVICE addresses (samples 8-byte aligned, d_state n_streams ROTATOR_STATE records, 16-byte aligned), asynchronous on `stream`,
+    one launch: row s reads n_samples complex64 samples at d_in + 8 * s * in_stride, rotates sample i by its record's phase at the
+    absolute index base_index + i and writes it at d_out + 8 * s * out_stride. The records are only read. d_out == d_in with equal
+    strides works in place."""
+    check(lib.dvbs2_rotator_rows_device(d_in or None, int(in_stride), d_out or None, int(out_stride), int(n_samples), int(n_streams),
+                                        int(base_index), d_state or None, int(device), stream or None))
+
+
+def rotator_retune_device(d_state, stream_index, at_index, phase_inc, device=0, stream=0):
+    """DEVICE records: rebases record stream_index at the absolute index at_index and gives it the increment phase_inc (radians per
+    sample); the phase stays continuous. Asynchronous on `stream`. Rotator.schedule(at_index, phase_inc) with the state on the device."""
+    check(lib.dvbs2_rotator_retune_device(d_state or None, int(stream_index), int(at_index), float(phase_inc), int(device), stream or None))
+
+
+def rotator_control_device(d_offsets, n_streams, max_slots, d_coarse_foffset, d_coarse_corrected, d_new_est, d_fine_foffset, d_fine_valid,
+                           coarse_scale, fine_scale, at_index, d_state, d_applied=0, d_delta=0, device=0, stream=0):
+    """DEVICE addresses, asynchronous on `stream`, one launch, nothing read back: the frequency-control step over the slots of one
+    pass. Per stream the last qualifying slot decides (coarse: new_est and not coarse_corrected; fine: coarse_corrected and
+    fine_valid); its estimate times its scale (gain / sps) is subtracted from the record's increment, rebased at at_index.
+    d_fine_foffset / d_fine_valid: both or neither. d_applied: int32 per stream (0, 1 coarse, 2 fine, -1 did not apply); d_delta: int64."""
+    check(lib.dvbs2_rotator_control_device(d_offsets or None, int(n_streams), int(max_slots), d_coarse_foffset or None, d_coarse_corrected or None,
+                                           d_new_est or None, d_fine_foffset or None, d_fine_valid or None, float(coarse_scale), float(fine_scale),
+                                           int(at_index), d_state or None, d_applied or None, d_delta or None, int(device), stream or None))
 
 
 def symsync_loop_constants(sps, loop_bw, damping, rolloff):

@@ -82,6 +82,7 @@ class SpectrumCarrierParams(C.Structure):
 
 SPECTRUM_CARRIER_DTYPE = [("centre", "<f8"), ("bandwidth", "<f8"), ("level", "<f8"), ("floor", "<f8"), ("lo_bin", "<i4"), ("hi_bin", "<i4")]  # dvbs2_spectrum_carrier_t
 PLSYNC_FRAME_DTYPE = [("sof_index", "<i8"), ("metric", "<f4"), ("plsc", "u1"), ("flags", "u1"), ("reserved", "u1", (2,))]
+ROTATOR_STATE_DTYPE = [("phase", "<u8"), ("inc", "<u8"), ("index", "<i8"), ("reserved", "<u8")]  # dvbs2_rotator_state_t
 PLSYNC_SEARCHING, PLSYNC_FOUND, PLSYNC_LOCKED = 0, 1, 2
 PLSYNC_REAL_PEAK, PLSYNC_FLAG_LOCKED = 1, 2
 
@@ -219,6 +220,14 @@ SYMBOLS = {
     "dvbs2_rotator_rotate_device": (_i, [_vp, _vp, _i, _vp, _vp]),
     "dvbs2_rotator_rotate": (_i, [_vp, _vp, _i, _vp]),
     "dvbs2_rotator_measure": (_i, [_i, _i, _i, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    # rotator rows: state in the caller's device memory, no handle
+    "dvbs2_rotator_state_init": (_i, [_vp, _i, _vp]),
+    "dvbs2_rotator_state_read": (_i, [_vp, _i, _vp, _vp]),
+    "dvbs2_rotator_adjust_turns": (_i, [_f, C.c_double, C.POINTER(C.c_int64), _ip]),
+    "dvbs2_rotator_rows_check": (_i, [C.c_int64, C.c_int64, _i, _i, C.c_int64]),
+    "dvbs2_rotator_rows_device": (_i, [_vp, C.c_int64, _vp, C.c_int64, _i, _i, C.c_int64, _vp, _i, _vp]),
+    "dvbs2_rotator_retune_device": (_i, [_vp, _i, C.c_int64, C.c_double, _i, _vp]),
+    "dvbs2_rotator_control_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_int64, _vp, _vp, _vp, _i, _vp]),
     "dvbs2_symsync_loop_constants": (_i, [_i, _f, _f, _f, _fp, _fp, _fp]),
     "dvbs2_symsync_geometry": (_i, [_i, _i, _i, _i, _ip, _ip, _ip]),
     "dvbs2_symsync_taps": (_i, [_i, _f, _i, _i, _vp]),

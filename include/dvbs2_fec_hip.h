@@ -621,8 +621,9 @@ int dvbs2_plsync_thresholds(float* unlocked, float* locked);
  * dvbs2_plcoarse_estimate is the host-buffer form of the first (synchronous; it stages the 90 header symbols of each frame).
  * n_frames <= max_frames. There is no CPU fallback. dvbs2_plcoarse_weights (host only) writes the 89 (full != 0) or 25 window
  * weights as the floats the kernel uses and returns their count.
- * What stays in the GNU Radio block: the message to the rotator (control_rotator_freq, tag calibration) and the open-loop
- * de-rotation inside the tracker's PLSC decode.
+ * The message to the rotator (control_rotator_freq) is restated for a batch of streams as dvbs2_rotator_control_device in the section
+ * "rotator rows" behind dvbs2_rotator_*; what stays in the GNU Radio block is the tag-delay calibration and the open-loop de-rotation
+ * inside the tracker's PLSC decode.
  * Accuracy: the sums are float, each lag in ascending symbol order and the frames in order, where the reference uses VOLK's dot
  * product; the angles are atan2f where it uses gr::fast_atan2f (a table). Neither is available to compare with, so the estimate is
  * tested against a float64 model under a derived float32 bound and is UNPINNED against the genuine reference, like the plframe
@@ -845,6 +846,79 @@ int dvbs2_rotator_rotate(dvbs2_rotator_t* h, const float* in, int n_syms, float*
 /* measurement aid (tools/plcoarse_time.py): median over `regions` HIP-event regions of one rotation of n_syms symbols and, in the same
  * run, of a plain 16-byte-per-lane copy kernel over the same bytes on the same grid; it allocates 2 * 8 * n_syms bytes for the run */
 int dvbs2_rotator_measure(int device, int n_syms, int regions, double* rotate_ms, double* copy_ms);
+
+/* ---- rotator rows: the rotator for a BATCH of streams in one launch, from state held in the CALLER'S device memory, and the
+ * frequency-control step that steers it from the PL estimates of one pass without a host read. There is no handle.
+ * STATE. One record per stream, an array of them, 16-byte aligned, in DEVICE memory for the _device entries:
+ *   phase: turns, 2^64 = one turn, AT sample `index`;  inc: turns per sample;  index: the absolute sample index `phase` refers to.
+ * Sample m (absolute) of a stream has the phase  phase + (uint64_t)(m - index) * inc  modulo 2^64: exact integer arithmetic, also
+ * defined for m < index. The sample itself is the single handle's (the upper 32 bits of the phase as half-turns into sincospif, four
+ * products, a subtraction and an addition, no contraction): a rotated sample is a pure function of (record, absolute index), as a
+ * noise sample of dvbs2_awgn_* is of (seed, stream, index). The rotation only READS the records: any number of calls may be in
+ * flight, a block can be replayed, and pieces equal one call by construction. `reserved` is never read or written by a _device entry.
+ * An increment changes by REBASING a record at an absolute index `at`:  phase += (at - index) * inc; index = at; inc = new.  The
+ * phase stays continuous across the change: this is dvbs2_rotator_schedule(offset, inc) with the state on the device. The rotation,
+ * the control step and a caller's own kernel all act on the same 32 bytes, in stream order.
+ *
+ * Host only, no device needed:
+ *   dvbs2_rotator_state_init   phase = 0, index = 0, reserved = 0, inc = the conversion of dvbs2_rotator_create (radians per sample, in
+ *                              extended precision, to 2^-64 turns, modulo one turn). A row started this way equals
+ *                              dvbs2_rotator_create(phase_inc[s]) bit for bit. A phase_inc[s] that is not finite is refused, the text
+ *                              names it ("phase_inc[3] must be finite"), and nothing is written. `state` is a HOST array here.
+ *   dvbs2_rotator_state_read   inc and phase of HOST records back as radians in (-pi, pi]; each output nullable. For printing and tests:
+ *                              a record need not be expressible in radians.
+ *   dvbs2_rotator_adjust_turns the ONE conversion of the control step, so that a run can be replayed on the CPU (as dvbs2_awgn_sample
+ *                              does for the noise): d = (double)estimate * scale, one float64 product; *applies = d is finite and
+ *                              |d| < 0.5; *delta = d * 2^64 (exact) rounded to nearest even, which fits int64 because |d| < 0.5; without
+ *                              *applies, *delta = 0.
+ *   dvbs2_rotator_rows_check   the ranges dvbs2_rotator_rows_device applies first: n_streams 1..65535, n_samples 0..2^30, with
+ *                              n_streams > 1 no stride below n_samples, base_index >= 0 and base_index + n_samples without overflow.
+ *
+ * DEVICE entries, asynchronous on `stream` (a hipStream_t) of `device`; no allocation, no host synchronisation, ONE launch each. The
+ * argument checks come first, the device is looked for after them; a refused call writes nothing.
+ *   dvbs2_rotator_rows_device  row s reads n_samples complex samples at d_in + 2 * s * in_stride floats and writes as many at d_out +
+ *                              2 * s * out_stride; its sample i has the absolute index base_index + i, the SAME for all rows, so the
+ *                              caller keeps one running int64. Buffers 8-byte aligned, strides in complex samples (they matter only with
+ *                              n_streams > 1). d_out == d_in with equal strides is allowed, any other overlap is not. n_samples == 0
+ *                              succeeds and launches nothing. A call does NOT split itself at a change of increment: it rotates all
+ *                              its samples by the records as the device finds them; the caller cuts its calls at `at`.
+ *   dvbs2_rotator_retune_device rebases record stream_index at at_index (>= 0), then inc = the conversion of phase_inc, which runs on
+ *                              the host and is passed by value. stream_index is 0..65534; the array's length is the caller's to know,
+ *                              as with every device array, so there is no n_streams argument and no "-1 for all".
+ *   dvbs2_rotator_control_device the control rule below over the outputs of one pass: d_offsets as dvbs2_plsync_batch_gather_device
+ *                              writes it (read on the DEVICE: stream s owns slots d_offsets[s] .. d_offsets[s + 1], those at or above
+ *                              max_slots are ignored), the per-slot arrays of dvbs2_plcoarse_batch_estimate_device and fine_foffset /
+ *                              fine_valid of dvbs2_plframe_*_strided_device. d_fine_foffset / d_fine_valid are nullable TOGETHER.
+ *                              d_applied (nullable, per stream): 0 nothing, 1 a coarse step, 2 a fine step, -1 an estimate qualified but
+ *                              did not apply. d_delta (nullable, per stream, int64): the turns subtracted, 0 where none were.
+ * THE CONTROL RULE restates lib/plsync_cc_impl.cc:622-628 and :683-691 for a block. All slots of one pass were rotated by ONE
+ * increment, so their estimates are not cumulative and the latest decides. Walking a stream's slots in order, a slot qualifies as
+ * COARSE when new_est != 0 && coarse_corrected == 0, as FINE when coarse_corrected != 0 && fine_valid != 0; the LAST qualifying slot
+ * of either kind decides. With its estimate e and its scale: delta = adjust_turns(e, scale); if it applies, rebase at at_index, then
+ * inc -= delta (the rotator's frequency is the negative of the estimated offset). A stream without a qualifying slot is not touched
+ * at all, not even rebased, and neither is one whose estimate does not apply. The reference's "locked" and "not a dummy frame"
+ * conditions are met by construction: the gather copies locked frames of wanted_plsc only. The scales are gain / sps: the estimates
+ * are cycles per SYMBOL and the rotator works on samples; gain is the caller's loop gain, 1 in the reference. A scale that is not
+ * finite is refused on the host.
+ * NOT restated: the tag-delay calibration (calibrate_tag_delay). In this block form the change takes effect at at_index, which the
+ * caller sets to its running sample count: the first sample of the next call. */
+typedef struct {
+    uint64_t phase;
+    uint64_t inc;
+    int64_t index;
+    uint64_t reserved;
+} dvbs2_rotator_state_t;
+int dvbs2_rotator_state_init(const double* phase_inc, int n_streams, dvbs2_rotator_state_t* state);
+int dvbs2_rotator_state_read(const dvbs2_rotator_state_t* state, int n_streams, double* phase_inc, double* phase_at_index);
+int dvbs2_rotator_adjust_turns(float estimate, double scale, int64_t* delta, int* applies);
+int dvbs2_rotator_rows_check(int64_t in_stride, int64_t out_stride, int n_samples, int n_streams, int64_t base_index);
+int dvbs2_rotator_rows_device(const float* d_in, int64_t in_stride, float* d_out, int64_t out_stride, int n_samples, int n_streams,
+                              int64_t base_index, const dvbs2_rotator_state_t* d_state, int device, void* stream);
+int dvbs2_rotator_retune_device(dvbs2_rotator_state_t* d_state, int stream_index, int64_t at_index, double phase_inc, int device, void* stream);
+int dvbs2_rotator_control_device(const int32_t* d_offsets, int n_streams, int max_slots, const float* d_coarse_foffset,
+                                 const int32_t* d_coarse_corrected, const int32_t* d_new_est, const float* d_fine_foffset,
+                                 const int32_t* d_fine_valid, double coarse_scale, double fine_scale, int64_t at_index,
+                                 dvbs2_rotator_state_t* d_state, int32_t* d_applied, int64_t* d_delta, int device, void* stream);
 
 /* ---- symbol timing recovery: symbol_sync_cc_impl::loop (reference lib/symbol_sync_cc_impl.cc:283-401) with its four interpolators
  * (:23-66, :122-132: polyphase RRC bank = the matched filter, linear, quadratic and cubic Farrow), its loop constants (:156-199), its
