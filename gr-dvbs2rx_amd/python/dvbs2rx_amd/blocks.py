@@ -27,6 +27,7 @@ __all__ = ["get_fec_info", "rate_id", "LdpcDecoder", "BchDecoder", "Demapper", "
            "Spectrum", "spectrum_geometry", "spectrum_window", "spectrum_twiddles", "spectrum_check", "spectrum_carriers",
            "PfbChannelizer", "pfbch_geometry", "pfbch_produce", "pfbch_check", "pfbch_tile", "pfbch_twiddles",
            "PfbSynthesizer", "pfbsyn_geometry", "pfbsyn_check", "pfbsyn_tile",
+           "BBDEHEADER_STATE", "bbdeheader_rows_check", "bbdeheader_rows_geometry", "bbdeheader_state_counters", "bbdeheader_rows_device",
            "BbFramer", "bbheader_build", "crc8"]
 
 DEFAULT_TRIALS = 25  # reference lib/ldpc_decoder_bb_impl.cc:391
@@ -1223,6 +1224,43 @@ class BbDeheader(_Handle):
 
     def reset(self, stream=0):
         check(lib.dvbs2_bbdeheader_reset(self._h, stream))
+
+
+BBDEHEADER_STATE = np.dtype(capi.BBDEHEADER_STATE_DTYPE)  # dvbs2_bbdeheader_state_t, 256 bytes: all-zero bytes are the block as constructed
+
+
+def bbdeheader_rows_check(kbch_bits, n_streams, max_frames):
+    """None, or the text with which bbdeheader_rows_device refuses these ranges. Host only."""
+    if lib.dvbs2_bbdeheader_rows_check(int(kbch_bits), int(n_streams), int(max_frames)) == capi.OK:
+        return None
+    return lib.dvbs2_last_error().decode()
+
+
+def bbdeheader_rows_geometry(kbch_bits, n_streams, max_frames):
+    """dict(kbch_bytes, max_out_bytes_per_frame, work_bytes, out_bytes): the sizes of a bbdeheader_rows_device call. Host only."""
+    kb, mo, wb, ob = C.c_int(), C.c_int(), C.c_int64(), C.c_int64()
+    check(lib.dvbs2_bbdeheader_rows_geometry(int(kbch_bits), int(n_streams), int(max_frames), C.byref(kb), C.byref(mo), C.byref(wb), C.byref(ob)))
+    return dict(kbch_bytes=kb.value, max_out_bytes_per_frame=mo.value, work_bytes=wb.value, out_bytes=ob.value)
+
+
+def bbdeheader_state_counters(state):
+    """HOST records (BBDEHEADER_STATE) as one dict per stream with the keys of BbDeheader.counters()."""
+    st = np.ascontiguousarray(state, BBDEHEADER_STATE).reshape(-1)
+    out = (capi.BbDeheaderCounters * max(st.size, 1))()
+    check(lib.dvbs2_bbdeheader_state_counters(_ptr(st), int(st.size), C.addressof(out)))
+    return [{k: getattr(c, k) for k, _ in c._fields_} for c in out[:st.size]]
+
+
+def bbdeheader_rows_device(d_bbframes, kbch_bits, d_offsets, n_streams, max_frames, d_state, d_work, work_bytes, d_ts_out, out_bytes,
+                           d_pkt_offsets, device=0, stream=0):
+    """DEVICE addresses, asynchronous on `stream`, five launches for any n_streams, nothing read back: stream s owns the BBFRAMEs
+    d_offsets[s] .. d_offsets[s + 1] (int32, read on the device; those at or above max_frames are ignored) and its record d_state[s]
+    (BBDEHEADER_STATE, 16-byte aligned). Its 188-byte packets go to d_ts_out at packet d_pkt_offsets[s], compact and stream-major;
+    d_pkt_offsets gets n_streams + 1 int32. d_work / work_bytes and out_bytes: at least bbdeheader_rows_geometry's. The records are
+    read and written: order calls on the same records or workspace on one stream."""
+    check(lib.dvbs2_bbdeheader_rows_device(d_bbframes or None, int(kbch_bits), d_offsets or None, int(n_streams), int(max_frames), d_state or None,
+                                           d_work or None, int(work_bytes), d_ts_out or None, int(out_bytes), d_pkt_offsets or None, int(device),
+                                           stream or None))
 
 
 def bbheader_build(matype1=0xF2, matype2=0, upl_bits=188 * 8, dfl_bits=0, sync=0x47, syncd_bits=0):

@@ -83,6 +83,9 @@ class SpectrumCarrierParams(C.Structure):
 SPECTRUM_CARRIER_DTYPE = [("centre", "<f8"), ("bandwidth", "<f8"), ("level", "<f8"), ("floor", "<f8"), ("lo_bin", "<i4"), ("hi_bin", "<i4")]  # dvbs2_spectrum_carrier_t
 PLSYNC_FRAME_DTYPE = [("sof_index", "<i8"), ("metric", "<f4"), ("plsc", "u1"), ("flags", "u1"), ("reserved", "u1", (2,))]
 ROTATOR_STATE_DTYPE = [("phase", "<u8"), ("inc", "<u8"), ("index", "<i8"), ("reserved", "<u8")]  # dvbs2_rotator_state_t
+BBDEHEADER_STATE_DTYPE = [("synched", "<i4"), ("partial_ts_bytes", "<i4"), ("packets", "<u8"), ("errors", "<u8"), ("bbframes", "<u8"), ("dropped", "<u8"),
+                          ("gaps", "<u8"), ("overruns", "<u8"), ("last_packets", "<i4"), ("reserved", "<i4"), ("partial_pkt", "u1", (188,)),
+                          ("padding", "u1", (4,))]  # dvbs2_bbdeheader_state_t
 PLSYNC_SEARCHING, PLSYNC_FOUND, PLSYNC_LOCKED = 0, 1, 2
 PLSYNC_REAL_PEAK, PLSYNC_FLAG_LOCKED = 1, 2
 
@@ -322,6 +325,11 @@ SYMBOLS = {
     "dvbs2_bbdeheader_finish": (_i, [_vp, C.POINTER(C.c_int64), _vp]),
     "dvbs2_bbdeheader_counters": (_i, [_vp, _vp, _vp]),
     "dvbs2_bbdeheader_reset": (_i, [_vp, _vp]),
+    # de-header rows: state in the caller's device memory, no handle
+    "dvbs2_bbdeheader_rows_check": (_i, [_i, _i, _i]),
+    "dvbs2_bbdeheader_rows_geometry": (_i, [_i, _i, _i, _ip, _ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "dvbs2_bbdeheader_state_counters": (_i, [_vp, _i, _vp]),
+    "dvbs2_bbdeheader_rows_device": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp, _i, _vp]),
     "dvbs2_bbframer_create": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i]),
     "dvbs2_bbframer_create_raw": (_i, [C.POINTER(_vp), _i, _i, _i]),
     "dvbs2_bbframer_destroy": (None, [_vp]),

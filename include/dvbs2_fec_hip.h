@@ -1406,6 +1406,60 @@ int dvbs2_bbdeheader_finish(dvbs2_bbdeheader_t* h, int64_t* produced, void* stre
 int dvbs2_bbdeheader_counters(dvbs2_bbdeheader_t* h, dvbs2_bbdeheader_counters_t* out, void* stream);
 int dvbs2_bbdeheader_reset(dvbs2_bbdeheader_t* h, void* stream);
 
+/* ---- de-header rows: the de-header above for a BATCH of streams in a fixed number of launches, from state held in the CALLER'S
+ * device memory. There is no handle, and the host reads nothing: not the frame ranges, not the byte counts.
+ * FRAMES. Stream s of a call owns the BBFRAMEs d_offsets[s] .. d_offsets[s + 1] of d_bbframes: kbch_bits / 8 bytes each, back to back,
+ * stream-major, as dvbs2_chain_* and dvbs2_bch_* write the slots that dvbs2_plsync_batch_gather_device counted. d_offsets (n_streams + 1
+ * entries, non-decreasing, d_offsets[n_streams] = the frames of the call) is read on the DEVICE. Frames at or above max_frames are
+ * ignored (the rule of dvbs2_rotator_control_device for max_slots): presented again in the next call they give the bytes of one call.
+ * Whatever d_offsets holds, device code stays inside its buffers: every offset is clamped to [0, min(d_offsets[n_streams], max_frames)]
+ * and a pair with d_offsets[s + 1] <= d_offsets[s] is an empty stream. Ranges that overlap (offsets that decrease and rise again) give
+ * undefined packets and records for the streams that overlap, and nothing worse.
+ * STATE. One record per stream, an array of them, 16-byte aligned, in DEVICE memory for the _device entry. What stream s emits and
+ * what its record holds afterwards equal, byte for byte, what one dvbs2_bbdeheader_t gives that is fed the same frames in the same
+ * sequence of calls: the packets, the transport error indicators, the synchronised flag, the carried partial packet, the six counters
+ * (the defined deviation `overruns` included). ALL-ZERO BYTES ARE THE BLOCK AS CONSTRUCTED: a hipMemsetAsync of one record resets that
+ * stream, one of the array resets the batch; there is no init entry. A stream without frames in a call is not touched at all: its
+ * record's bytes stay as they are. last_packets: the packets the stream wrote in the last call that touched it. `reserved` and the
+ * padding are never read or written.
+ *
+ * Host only, no device needed:
+ *   dvbs2_bbdeheader_rows_check     kbch_bits by the rules of dvbs2_bbdeheader_create_raw (>= 88, a multiple of 8, kbch_bits - 80 <= 65535,
+ *                                   at most 64 packets per BBFRAME), n_streams 1..1024 (the limit of the gather that writes d_offsets),
+ *                                   max_frames 1..2^20. DVBS2_EINVAL with a text that names the argument.
+ *   dvbs2_bbdeheader_rows_geometry  kbch_bytes = kbch_bits / 8; max_out_bytes_per_frame as dvbs2_bbdeheader_params gives it; out_bytes =
+ *                                   max_frames * max_out_bytes_per_frame, an upper bound whatever the headers say (a frame completes at
+ *                                   most ceil(max DFL bytes / 188) packets: floor((187 + x) / 188) = ceil(x / 188)); work_bytes = the
+ *                                   scratch of a call (per frame a header word, a plan and the stream it belongs to; per stream a tail
+ *                                   plan). Every output nullable.
+ *   dvbs2_bbdeheader_state_counters HOST copies of n_streams records as n_streams dvbs2_bbdeheader_counters_t.
+ *
+ * DEVICE entry, asynchronous on `stream` (a hipStream_t) of `device`; no allocation, no host synchronisation, FIVE launches for any
+ * n_streams. The argument checks come first (the ranges above; no null pointer; d_offsets and d_pkt_offsets 4-byte aligned, d_state and
+ * d_work 16-byte aligned: DVBS2_EINVAL; work_bytes and out_bytes at least the geometry's: DVBS2_ESIZE), the device is looked for after
+ * them; a refused call writes nothing.
+ *   dvbs2_bbdeheader_rows_device    188-byte packets, compact and stream-major, in d_ts_out. d_pkt_offsets (required, n_streams + 1
+ *                                   entries) receives the exclusive prefix sums of the packets per stream: stream s owns the packets
+ *                                   d_pkt_offsets[s] .. d_pkt_offsets[s + 1] of d_ts_out. It mirrors d_offsets, so the next consumer
+ *                                   needs no host read either.
+ * ORDER. Unlike the rotator rows, a call READS AND WRITES the records, and the workspace belongs to one call at a time: calls on the
+ * same records or the same workspace must be ordered on one stream (or by events). d_ts_out and d_pkt_offsets are the call's own. */
+typedef struct {
+    int32_t synched, partial_ts_bytes;                          /* d_synched, d_partial_ts_bytes */
+    uint64_t packets, errors, bbframes, dropped, gaps, overruns; /* as dvbs2_bbdeheader_counters_t */
+    int32_t last_packets;
+    int32_t reserved;
+    uint8_t partial_pkt[188];                                   /* d_partial_pkt: its first partial_ts_bytes bytes count */
+    uint8_t padding[4];                                         /* to 256 bytes */
+} dvbs2_bbdeheader_state_t;
+int dvbs2_bbdeheader_rows_check(int kbch_bits, int n_streams, int max_frames);
+int dvbs2_bbdeheader_rows_geometry(int kbch_bits, int n_streams, int max_frames, int* kbch_bytes, int* max_out_bytes_per_frame,
+                                   int64_t* work_bytes, int64_t* out_bytes);
+int dvbs2_bbdeheader_state_counters(const dvbs2_bbdeheader_state_t* state, int n_streams, dvbs2_bbdeheader_counters_t* out);
+int dvbs2_bbdeheader_rows_device(const uint8_t* d_bbframes, int kbch_bits, const int32_t* d_offsets, int n_streams, int max_frames,
+                                 dvbs2_bbdeheader_state_t* d_state, void* d_work, int64_t work_bytes, uint8_t* d_ts_out, int64_t out_bytes,
+                                 int32_t* d_pkt_offsets, int device, void* stream);
+
 /* ---- BB framing: mode adaptation for MPEG-TS (EN 302 307-1 clauses 5.1.4 to 5.1.6), the mirror of dvbs2_bbdeheader_* above. In the
  * reference's transmit flowgraph the place is held by gr-dtv's dvb_bbheader_bb(..., INPUTMODE_NORMAL, ...) (apps/dvbs2-tx:619-621).
  * 188-byte TS packets in, BBFRAMEs of kbch_bytes out, every byte defined by the standard. Bytes only: nothing here has a tolerance.
