@@ -71,23 +71,26 @@ def sizes_of(s):
     return SIZES[k:] + SIZES[:k]
 
 
-def run_batch(ps, d_x, stride, lengths, sizes=None, d_f=None, first0=None):
+def run_batch(ps, d_x, stride, lengths, sizes=None, d_f=None, first0=None, start_call=None):
     """Every stream through ps from its first symbol to its last, each following its OWN `consumed` through first[]. sizes: None (one
     call holds a whole stream) or stream -> the cycle of its call sizes. A stream that has been presented to its end takes part in the
-    later calls with n_syms = 0. Returns NS(calls: per stream the list of (n_syms, records bytes, n_frames, consumed, state) of the
-    calls it took part in, recs: per stream all its records, pos, state, n_calls, d_f: the record buffer of the LAST call)."""
+    later calls with n_syms = 0. start_call: None, or per stream the call with which it begins: in front of it the stream takes part
+    with n_syms = 0, and its cycle of sizes begins with its own first call. Returns NS(calls: per stream the list of (n_syms, records
+    bytes, n_frames, consumed, state) of the calls it took part in, recs: per stream all its records, pos, state, n_calls, d_f: the record buffer of the LAST call)."""
     S = len(lengths)
     d_f = zeros(S * ps.max_frames * 16, "uint8") if d_f is None else d_f
     first0 = [0] * S if first0 is None else first0
+    start_call = [0] * S if start_call is None else start_call
     pos, done, calls, state = [0] * S, [n == 0 for n in lengths], [[] for _ in range(S)], [None] * S
     i = 0
     while not all(done):
-        n = [0 if done[s] else min(lengths[s] - pos[s], sizes[s][i % len(sizes[s])] if sizes else lengths[s]) for s in range(S)]
+        idle = [done[s] or i < start_call[s] for s in range(S)]
+        n = [0 if idle[s] else min(lengths[s] - pos[s], sizes[s][(i - start_call[s]) % len(sizes[s])] if sizes else lengths[s]) for s in range(S)]
         ps.work_device(d_x.data_ptr(), stride, [first0[s] + pos[s] for s in range(S)], n, d_f.data_ptr(), T.stream())
         nf, consumed, st = ps.finish()
         recs = records(d_f, S, ps.max_frames)
         for s in range(S):
-            if done[s]:
+            if idle[s]:
                 assert (nf[s], consumed[s]) == (0, 0), f"stream {s} was presented nothing and reports {nf[s]} frames, {consumed[s]} consumed"
                 assert state[s] is None or st[s] == state[s]
                 continue
